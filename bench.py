@@ -22,11 +22,17 @@ One "step" = one pass of the hot path over one batch of synthetic boxes resident
   `--pairs P` changes the pairs per GPU; `--total-pairs T` (strong) the batch.
 `value` = pairs processed by all ranks / max-over-ranks wall time of the K timed steps.
 Timing: W warm-up steps as asked, topped up to 3 000 untimed steps (the clocks only settle after a few thousand
-back-to-back launches; reported as config.untimed_steps_before_timing, and the figure measured with exactly W warm-up
-steps is reported next to it as `unsettled`), barrier + synchronize, exactly K timed steps, barrier + synchronize, max
-over ranks.
+back-to-back launches; reported as config.untimed_steps_before_timing, and with --full the figure measured with exactly W
+warm-up steps is reported next to it as `unsettled`), barrier + synchronize, exactly K timed steps, barrier + synchronize,
+max over ranks.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line; nothing else runs.  `--dump-outputs DIR` then also
+writes what the last timed step computed as DIR/iou.npy (float32; rank 0's vector, or the gathered one when the step
+gathers; above 64 MB in all, a fixed seeded sample of it with its indices in DIR/iou_index.npy).  The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
+`--full` adds the side measurements below (each has runs of its own); `--no-extras`, `--no-parity` and `--no-cpu-baseline`
+leave parts of them out.  Extra objects on the JSON line with --full:
   roofline      the dominant kernel (iou_aligned_chunk_kernel) against the HBM roofline: algorithmic bytes = 36 B/pair
                 (2 x 16 B boxes in + 4 B IoU out) / average launch duration measured here with HIP events
                 on the launch stream, median of 5 runs of K/5 back-to-back launches (`rocprof_traced_kernel_ms`: the committed rocprofv3 kernel-trace average of the same
@@ -36,6 +42,11 @@ Extra objects on the JSON line:
                 configuration matches the one profiled; `cold` repeats the measurement rotating through 10 distinct
                 input / output sets (360 MB > the 256 MiB Infinity Cache: every launch streams from HBM), `at_8m` is one
                 8 M-pair launch (288 MB).
+  unsettled     the K steps timed after exactly W warm-up steps, before the top-up.
+  no_gather, gather_only, strong_scaling
+                N > 1 with the gather: the sharded step without it, the gather alone, the whole batch on one GPU.
+  north_star_configs4
+                N > 1, default scaling: configs[4] with the gather, without it and the gather alone (see above).
   two_streams   N = 1: the same steps issued alternately on two HIP streams (independent launches: the ramp-up of one
                 overlaps the tail of the other); a side figure, never `value`.
                 `frac` divides by the event-timed launch (`kernel_ms`); `frac_step` by the driver-visible `ms_per_step`;
@@ -70,6 +81,7 @@ HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s 
 VARIANT = 'standard'
 CLOCK_SETTLE_STEPS = 3000
 COLD_SETS = 10               # x 36 MB per 1 M pairs = 360 MB > 256 MiB Infinity Cache
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
 
 
 def parse_args(argv=None):
@@ -87,13 +99,18 @@ def parse_args(argv=None):
     ap.add_argument('--arithmetic', default='fast', choices=['fast', 'robust', 'reference'],
                     help="'fast' = default closed-form core ('robust' is an alias of it since round 2); 'reference' = the "
                          "reference's fp32 operation order")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true', help='skip the max |dIoU| block (oracle on the host, outside the timed region)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side measurements (roofline, cold HBM, 8 M pairs, two streams, parity, CPU baseline, '
+                         'north star, gather splits); a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's output as DIR/iou.npy (float32; a seeded sample above 64 MB)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the max |dIoU| block (oracle on the host, outside the timed region)')
     ap.add_argument('--gather', dest='gather', action='store_true', default=None,
                     help='N > 1: one RCCL all-gather of the per-shard IoU vectors per step, pipelined one step deep '
                          '(default with --scaling strong)')
     ap.add_argument('--no-gather', dest='gather', action='store_false', help='N > 1: time the sharded step only')
-    ap.add_argument('--no-extras', action='store_true', help='skip the cold-HBM / 8 M-pair / unsettled side measurements')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the cold-HBM / 8 M-pair / unsettled / north-star side measurements')
     ap.add_argument('--force-dist', action='store_true', help='initialise the process group even with one rank (tests)')
     ap.add_argument('--north-star', action='store_true', help='with --force-dist: run the configs[4] exchange phase with one rank too (tests)')
     ap.add_argument('--dry-run', action='store_true',
@@ -235,6 +252,19 @@ def cpu_baseline(n_sample=1_000_000):
                                  'source': 'BASELINE.md §3 (measured in the build container, not on this host)'}}
 
 
+def dump_outputs(path, iou, limit_bytes=DUMP_LIMIT_BYTES):
+    """Write the step's output vector as path/iou.npy (float32).  Above `limit_bytes`, a fixed seeded sample in index order
+    instead, with its indices as path/iou_index.npy (float64: exact below 2**53); values + indices stay within the limit."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    iou = np.ascontiguousarray(iou, dtype=np.float32)
+    if iou.nbytes > limit_bytes:
+        idx = np.sort(np.random.default_rng(0).choice(iou.size, size=limit_bytes // 12, replace=False))
+        np.save(os.path.join(path, 'iou_index.npy'), idx.astype(np.float64))
+        iou = iou[idx]
+    np.save(os.path.join(path, 'iou.npy'), iou)
+
+
 def err_stats(got, want):
     import numpy as np
     d = np.abs(got.astype(np.float64) - want.astype(np.float64))
@@ -294,6 +324,9 @@ def main(argv=None):
     import torch.distributed as dist
     from sph_retina_amd import _lib, _torch_glue as G
     dry = args.dry_run
+    full = args.full
+    want_parity = full and not args.no_parity
+    want_cpu_baseline = full and not args.no_cpu_baseline
     # host-side tensor work here is only the synthetic boxes' RNG: torch sizes its CPU pool by the cores it SEES (128 on a
     # GPU box) while the box grants a share of them; an oversubscribed pool runs into the cgroup's CPU quota and the
     # launching thread is stalled with it (seen as one ~60 ms hole in a later measurement)
@@ -301,7 +334,7 @@ def main(argv=None):
     if not dry:
         if rank == 0:
             _lib.build()   # no-op when sph_retina_amd/lib/libsph2pob_hip.so is up to date
-            if not (args.no_cpu_baseline and args.no_parity) and world == 1:
+            if (want_parity or want_cpu_baseline) and world == 1:
                 # the CPU-baseline leg's checker is built here, BEFORE this process initialises the GPU: on this pool a
                 # process must not fork + exec (make / gcc) once it has touched the device
                 from oracle import oracle as _O
@@ -406,7 +439,7 @@ def main(argv=None):
         return el
 
     settle = 0 if dry else CLOCK_SETTLE_STEPS
-    extras = not args.no_extras and not dry
+    extras = full and not args.no_extras and not dry
     unsettled = None
     for i in range(args.warmup):
         step(i, gather)
@@ -417,8 +450,11 @@ def main(argv=None):
     for i in range(max(settle - args.warmup - (args.steps if extras else 0), 0)):
         step(i, gather)
     elapsed = timed(args.steps, gather)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (the barrier above has completed its gather)
+        dump_outputs(args.dump_outputs, (gathered if gather else shards)[(args.steps - 1) & 1].cpu().numpy())
     no_gather = gather_only = None
-    if gather:
+    if gather and full:
         el = timed(args.steps, False)
         no_gather = {'ms_per_step': el / args.steps * 1e3, 'value': total * args.steps / el}
         # ... and the exchange alone (no kernel): what bounds the step when the collective outlasts the 7 us kernel
@@ -437,14 +473,14 @@ def main(argv=None):
     checksum = float(shards[0].double().sum().item())
     # the north star's exchange (configs[4]: 8 M pairs split N ways + one all-gather per step), measured beside the default
     north_star = None
-    if ((world > 1 and not args.no_extras) or (args.north_star and use_dist)) and scaling == 'weak' and not gather:
+    if ((world > 1 and full and not args.no_extras) or (args.north_star and use_dist)) and scaling == 'weak' and not gather:
         north_star = north_star_exchange(kernel, make_boxes, world, rank, dev, dist, min(args.steps, 500),
                                          min(max(args.warmup, 20), 200), barrier, dry)
-    iou_benched = shards[0].clone() if (world == 1 and not dry and not args.no_parity) else None
+    iou_benched = shards[0].clone() if (world == 1 and not dry and want_parity) else None
 
     # ---- side measurements on rank 0 (the other ranks wait at the final barrier) ----
     kernel_ms = cold = at_8m = one_gpu_ms = two_streams = parity_gpu = None
-    if not dry:
+    if not dry and full:
         def events_ms(fn, reps):
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize(dev)
@@ -550,7 +586,7 @@ def main(argv=None):
                        'untimed_steps_before_timing': max(settle, args.warmup)},
             'checksum': checksum,
         }
-        if not dry:
+        if not dry and full:
             achieved = BYTES_PER_PAIR * n / (kernel_ms * 1e-3) / 1e9
             pmc = pmc_summary(n, args.variant, 'fast' if args.arithmetic == 'robust' else args.arithmetic, kern)
             out['roofline'] = {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
@@ -585,7 +621,7 @@ def main(argv=None):
                 north_star['speedup_with_gather'] = at_8m['kernel_ms'] / north_star['with_gather']['ms_per_step']
                 north_star['speedup_no_gather'] = at_8m['kernel_ms'] / north_star['no_gather']['ms_per_step']
             out['north_star_configs4'] = north_star
-        if world > 1 and scaling == 'strong':
+        if world > 1 and scaling == 'strong' and full:
             ss = {'total_pairs': total, 'one_gpu_ms': one_gpu_ms}
             if one_gpu_ms:
                 ss['speedup'] = one_gpu_ms / ms
@@ -594,7 +630,7 @@ def main(argv=None):
             out['strong_scaling'] = ss
         if parity_gpu is not None:
             out['parity'] = parity_block(b1.cpu().numpy(), b2.cpu().numpy(), parity_gpu, args.variant)
-        if not args.no_cpu_baseline and not dry and world == 1:   # rank 0 at N = 1 only
+        if want_cpu_baseline and not dry and world == 1:   # rank 0 at N = 1 only
             out['cpu_baseline'] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_dist:

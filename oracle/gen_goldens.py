@@ -478,7 +478,9 @@ def transform_bwd_only():
             torch.set_default_dtype(torch.float32)
         arrs.update({key + 'b1': g, key + 'b2': p, key + 'go1': go1, key + 'go2': go2, key + 'p1': q1, key + 'p2': q2,
                      key + 'g1': ga, key + 'g2': gb, key + 'g1_64': ga64, key + 'g2_64': gb64})
-    save('transform_bwd', **arrs)
+    # two files, each below the size limit of a committed fixture; tests/test_transform_bwd_general.py reads both
+    save('transform_bwd', **{k: v for k, v in arrs.items() if not k.startswith('efficient_project_')})
+    save('transform_bwd_efficient', **{k: v for k, v in arrs.items() if k.startswith('efficient_project_')})
 
 
 if __name__ == '__main__':

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +44,7 @@ def check(d, steps, warmup):
 
 
 def test_bench_single_process_contract():
-    d = run([sys.executable, 'bench.py', '--steps', '200', '--warmup', '20'])
+    d = run([sys.executable, 'bench.py', '--steps', '200', '--warmup', '20', '--full'])
     check(d, 200, 20)
     c = d['cpu_baseline']
     assert c['kind'] == 'port' and c['unit'] == 'pairs/s' and c['cores'] >= 1 and c['value'] > 1e5 and 'sample' in c
@@ -82,13 +83,31 @@ def test_bench_single_process_contract():
 def test_bench_under_torch_distributed_run_one_rank():
     d = run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
              '--master-port', '29577', 'bench.py', '--gpus', '1', '--steps', '100', '--warmup', '10', '--force-dist',
-             '--no-cpu-baseline', '--no-extras', '--north-star'])
+             '--full', '--no-cpu-baseline', '--no-extras', '--north-star'])
     check(d, 100, 10)
     # the north star's exchange phase (configs[4] + all_gather_into_tensor) on real RCCL, one rank: the code the N > 1 runs take
     ns = d['north_star_configs4']
     assert ns['total_pairs'] == 8_000_000 and ns['pairs_per_gpu'] == 8_000_000 and ns['own_shard_intact_in_gathered'] is True
     assert 0.03 < ns['no_gather']['ms_per_step'] < 0.2 and ns['with_gather']['ms_per_step'] >= 0.9 * ns['no_gather']['ms_per_step']
     assert ns['gather_only']['ms_per_step'] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_step_computed(tmp_path, oracle):
+    """The command every change is timed with: the headline only, and --dump-outputs writes the last timed step's IoUs,
+    held here to the f64 evaluation of the reference's formula on the run's own seeded boxes (the parity block's bounds)."""
+    d = run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '200', '--warmup', '20', '--dump-outputs', str(tmp_path)])
+    assert d['unit'] == 'pairs/s' and d['steps'] == 200 and d['warmup'] == 20 and d['dtype'] == 'f32' and d['higher_is_better'] is True
+    assert abs(d['value'] - 1_000_000 / (d['ms_per_step'] * 1e-3)) < 1e-3 * d['value'] and 1e10 < d['value'] < 5e11
+    assert not {'roofline', 'parity', 'cpu_baseline', 'unsettled', 'two_streams'} & set(d)
+    iou = np.load(tmp_path / 'iou.npy')
+    assert iou.dtype == np.float32 and iou.shape == (1_000_000,) and not (tmp_path / 'iou_index.npy').exists()
+    assert abs(d['checksum'] - iou.sum(dtype=np.float64)) < 1e-6 * abs(d['checksum'])
+    sys.path.insert(0, ROOT)
+    import bench
+    b1, b2 = bench.make_boxes(1_000_000, 0, 'cpu').numpy(), bench.make_boxes(1_000_000, 1, 'cpu').numpy()
+    f64 = oracle.iou_aligned(b1, b2, variant='standard', planar='exact', dtype=np.float64, nthreads=min(oracle.max_threads(), 16))
+    t = bench.err_stats(iou, f64)
+    assert t['mean'] < 1e-6 and t['p99_9'] < 1e-5 and t['n_gt_1e-5'] <= 30 and t['n_gt_1e-4'] == 0 and t['max'] < 1e-4, t
 
 
 @pytest.mark.parametrize('scenario', ['recipe', 'stale'])
