@@ -24,6 +24,14 @@
 
 namespace sph2pob {
 
+// the lanes of the wave for which `cond` holds (a wave-uniform mask; on the host, where a "wave" is one pair: 1 or 0)
+SPH_DEV unsigned long long sph_lane_mask(bool cond) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(cond);
+#else
+    return cond ? 1ull : 0ull;
+#endif
+}
 SPH_DEV unsigned float_bits(float x) { return __builtin_bit_cast(unsigned, x); }
 SPH_DEV unsigned max3_u32(unsigned a, unsigned b, unsigned c) {
     const unsigned m = a > b ? a : b;
@@ -182,8 +190,8 @@ SPH_DEV void angle_floor(float& c, float& s) {
 
 // Clipped length of one rectangle edge inside the other rectangle's slabs, pre-sorted-bound form: the edge is
 // P(tau) = k + tau * u^ (tau in [0, len]); per axis tau lies in [m - r, m + r] with m = -k_axis / u^_axis and
-// r = h_axis * |1 / u^_axis|.  Reciprocals are clamped to +-1e18 so that parallel edges give finite, correctly
-// ordered bounds (inside: (-huge, +huge); outside: both bounds on one side => empty) without NaNs.
+// r = h_axis * |1 / u^_axis|.  The reciprocals are not clamped: an edge parallel to an axis (|1 / u^_axis| = inf,
+// bounds inf or NaN) only occurs where lean_finish replaces the whole integral by near_parallel_inter.
 SPH_DEV float clip_len3(float mx, float my, float rx, float ry, float len) {
     float lo = fmaxf(fmaxf(mx - rx, my - ry), 0.0f);
     float hi = fminf(fminf(mx + rx, my + ry), len);
@@ -312,8 +320,12 @@ SPH_DEV bool cull_pair(const CullBox& g, const CullBox& p) {
 // the great-circle distance L, not at L itself (d^2 / 4 = t^2 + b^2 >= sin^2 t + sin^2 b >= sin^2(L / 2) with b = half the
 // latitude difference and sin t = sqrt(sin^2(L/2) - sin^2 b) / cos b: sph2pob_legacy.py:38-83), so the circles are
 // certainly apart only when the chord exceeds the sum of the radii: cos L < 1 - R^2 / 2.
+// The test's three compares, apart: the pair is culled when all three hold (fast_cull).  A kernel that needs the wave's
+// mask of culled lanes ANDs their three ballots: the ballot of the combined condition would first turn it into 0 / 1 per
+// lane and compare again (see SPH_ANY_LANE).
+struct CullParts { bool in_sizes, in_theta, apart; };
 template <int DIM, bool CHORD = false>
-SPH_DEV bool fast_cull(const float (&g)[5], const float (&p)[5], int edge) {
+SPH_DEV CullParts fast_cull_parts(const float (&g)[5], const float (&p)[5], int edge) {
 #pragma clang fp contract(fast)
     // Every coordinate inside the range the spherical jitter clamps it to (theta in [0, 360], phi and the extents in
     // [0, 180] degrees)?  Tested on the bit patterns as unsigned integers — for non-negative floats the order of the
@@ -324,7 +336,7 @@ SPH_DEV bool fast_cull(const float (&g)[5], const float (&p)[5], int edge) {
     const unsigned mg = max3_u32(float_bits(g[1]), float_bits(g[2]), float_bits(g[3]));
     const unsigned mp = max3_u32(float_bits(p[1]), float_bits(p[2]), float_bits(p[3]));
     const unsigned mth = float_bits(g[0]) > float_bits(p[0]) ? float_bits(g[0]) : float_bits(p[0]);
-    const bool in_range = ((mg > mp ? mg : mp) <= 0x43340000u) & (mth <= 0x43b40000u);   // 180.0f, 360.0f
+    const bool in_sizes = (mg > mp ? mg : mp) <= 0x43340000u, in_theta = mth <= 0x43b40000u;   // 180.0f, 360.0f
     // (r_g + r_p)^2 with r = half the diagonal: (d_g + d_p + 2 sqrt(d_g d_p)) / 4, d = w^2 + h^2.  For arc edges the
     // degrees -> radians factor is folded into the last FMA; a degenerate box (d = 0) gives 0 * inf = NaN: never culled.
     float dg, dp, quarter;
@@ -355,8 +367,14 @@ SPH_DEV bool fast_cull(const float (&g)[5], const float (&p)[5], int edge) {
     // CHORD (sph2pob_legacy): cos L < 1 - R^2/2, which is below -1 from R^2 = 4 on
     const float bound2 = CHORD ? (2.0f - 2e-4f) - R2
                                : fmaf(fmaf(fmaf(-1.0f / 360.0f, R2, 1.0f / 12.0f), R2, -1.0f), R2, 2.0f - 2e-4f);
-    return in_range & (C2 < bound2);
+    return CullParts{in_sizes, in_theta, C2 < bound2};
 }
+template <int DIM, bool CHORD = false>
+SPH_DEV bool fast_cull(const float (&g)[5], const float (&p)[5], int edge) {
+    const CullParts c = fast_cull_parts<DIM, CHORD>(g, p, edge);
+    return c.in_sizes & c.in_theta & c.apart;
+}
+
 
 // trig by-products of stage 1 that the loss adjoint reuses
 struct FastTrig { float sg, cg, sp, cp, sD, cD; };
@@ -415,13 +433,18 @@ __host__ __device__ __attribute__((noinline)) inline WideGamma wide_gamma_clamp(
 // and measured: 10.4 us against 8.4 us per 1 M pairs (profiles/r02o_ab_two_tier_*.log).
 #if defined(SPH_ANY_LANE)
 // (a microbenchmark's own definition: tools/ubench/finish_rate.hip -DNO_GUARDS prices the guards)
+#define SPH_ANY_LANE2(a, b) (SPH_ANY_LANE(a) || SPH_ANY_LANE(b))
 #elif defined(__HIP_DEVICE_COMPILE__)
-// (Hand it ONE compare where possible and combine guards with ||: the mask of a single v_cmp is the ballot, whereas a
-// condition built from several compares is first turned into 0 / 1 per lane and compared again, two more VALU
-// instructions.  __builtin_expect: the rare blocks are laid out behind the loop, the common path falls through.)
+// (Hand it ONE compare where possible: the mask of a single v_cmp is the ballot, whereas a condition built from several
+// compares is first turned into 0 / 1 per lane and compared again, two more VALU instructions.  Two conditions: OR the
+// two ballots (SPH_ANY_LANE2) — `SPH_ANY_LANE(a) || SPH_ANY_LANE(b)` branches between them, and a compare whose mask
+// crosses that branch is turned into 0 / 1 and compared again all the same.  __builtin_expect: the rare blocks are laid
+// out behind the loop, the common path falls through.)
 #define SPH_ANY_LANE(cond) __builtin_expect(__builtin_amdgcn_ballot_w64(cond) != 0ull, 0)
+#define SPH_ANY_LANE2(a, b) __builtin_expect((__builtin_amdgcn_ballot_w64(a) | __builtin_amdgcn_ballot_w64(b)) != 0ull, 0)
 #else
 #define SPH_ANY_LANE(cond) (cond)
+#define SPH_ANY_LANE2(a, b) ((a) || (b))
 #endif
 // diagnostic: -DSPH_GUARDS_OFF=<bit mask> compiles the guarded block of site k out (tools/ubench/finish_rate.hip prices
 // the sites one by one); 0 in every build of the library
@@ -546,7 +569,7 @@ SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, Pl
     float dx = A, dy = 0.0f;
     // ONE guard for the decisions and the adjustments (the wave-level test of the candidates is on the sine alone: a
     // single compare's mask, see SPH_ANY_LANE)
-    if (SPH_SITE(2) (SPH_ANY_LANE(cand_s) || SPH_ANY_LANE(sim_dist) || SPH_ANY_LANE(sim_size))) {
+    if (SPH_SITE(2) (SPH_ANY_LANE2(cand_s, sim_size) || SPH_ANY_LANE(sim_dist))) {
         SPH_SITE_HIT(2);
         if (cand) {
             float dang;   // a_g - a_p as the reference forms it: the difference of two angles in [-pi, pi], not wrapped
@@ -616,25 +639,52 @@ template <int VARIANT, int DIM, int PRE = 0>
 SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode, int edge, ColatTrig pre1 = ColatTrig{0.0f, 1.0f},
                           ColatTrig pre2 = ColatTrig{0.0f, 1.0f}) {
     const float e = (float)kEpsS, e2 = (float)(2 * kEpsS);
-    // evaluated HERE, not where it is used: left to the scheduler the test sinks to the end of the pass and keeps the
-    // eight raw coordinates alive (and copied) through all of it
-    float carrier = pair_nan_carrier<DIM>(in1, in2);
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(carrier));
-#endif
     // ---- jitter_spherical (sph_iou_api.py:244-260): shift only where `similar`, clamps always ----
     float x1[5], x2[5];
-    bool similar = false;
 #pragma unroll
     for (int k = 0; k < 5; k++) { x1[k] = in1[k]; x2[k] = in2[k]; }
-#pragma unroll
-    for (int k = 0; k < DIM; k++) similar |= fabsf(in1[k] - in2[k]) < e;
-    if (SPH_SITE(0) SPH_ANY_LANE(similar)) {
-        SPH_SITE_HIT(0);
+    // The pair's NaN test.  DIM 4: folded into the `similar` test — the NaN-propagating minimum of the four |x1 - x2|
+    // (v_minimum3 + v_minimum with abs modifiers, as many instructions as the non-propagating v_min3 + v_min it replaces)
+    // is NaN whenever a coordinate is, so ONE compare `!(min >= e)` sends every lane that is `similar` or may carry a NaN
+    // (also +inf - +inf: a superset) into the guarded block, which takes the exact decisions of both.  A wave with
+    // neither skips the carrier (4 v_maximum3) and the final NaN select (v_cmp + v_cndmask).  DIM 5 keeps the carrier on
+    // the common path: an infinite gamma counts as NaN there (pair_nan_carrier), which the differences cannot see.
+    bool nan_lane = false;
+    unsigned long long nan_wave = 0ull;   // DIM 4, wave-uniform: the lanes that carry a NaN
+    float carrier = 0.0f;                 // DIM 5
+    auto jitter_shift = [&](bool similar) {
         const float sh1 = similar ? e2 : 0.0f, sh2 = similar ? e : 0.0f;  // x - 0 == x exactly
 #pragma unroll
         for (int k = 0; k < DIM; k++) { x1[k] = x1[k] - sh1; x2[k] = x2[k] + sh2; }
         if (PRE && similar) { pre1 = colat_trig(x1[1], 1); if (PRE == 1) pre2 = colat_trig(x2[1], 2); }   // the shifted colatitudes
+    };
+    if (DIM == 4) {
+        float dmin = min_nan(min_nan(fabsf(in1[0] - in2[0]), fabsf(in1[1] - in2[1])), fabsf(in1[2] - in2[2]));
+        dmin = min_nan(dmin, fabsf(in1[3] - in2[3]));
+        if (SPH_SITE(0) SPH_ANY_LANE(!(dmin >= e))) {
+            SPH_SITE_HIT(0);
+            bool similar = false;
+#pragma unroll
+            for (int k = 0; k < DIM; k++) similar |= fabsf(in1[k] - in2[k]) < e;
+            const float carrier = pair_nan_carrier<DIM>(in1, in2);
+            nan_lane = carrier != carrier;
+            nan_wave = sph_lane_mask(nan_lane);
+            jitter_shift(similar);
+        }
+    } else {
+        // evaluated HERE, not where it is used: left to the scheduler the test sinks to the end of the pass and keeps the
+        // eight raw coordinates alive (and copied) through all of it
+        carrier = pair_nan_carrier<DIM>(in1, in2);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(carrier));
+#endif
+        bool similar = false;
+#pragma unroll
+        for (int k = 0; k < DIM; k++) similar |= fabsf(in1[k] - in2[k]) < e;
+        if (SPH_SITE(0) SPH_ANY_LANE(similar)) {
+            SPH_SITE_HIT(0);
+            jitter_shift(similar);
+        }
     }
     x1[0] = clampf(x1[0], e2, (float)(360.0 - kEpsS));
     x2[0] = clampf(x2[0], e, (float)(360.0 - 2 * kEpsS));
@@ -647,8 +697,9 @@ SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode
     PlanarPair q;
     lean_front<VARIANT, DIM, false, true, PRE>(x1, x2, edge, q, nullptr, pre1, pre2);
     // ---- stage 2: boundary integral of the two rectangles (P at the origin, T at (dx, dy)) ----
-    const float kBig = 1e18f;
-    const float ic = fminf(fmaxf(fast_rcp(q.c), -kBig), kBig), is = fminf(fmaxf(fast_rcp(q.s), -kBig), kBig);
+    // (no clamp of the reciprocals: where |c| or |s| < kNearParallel — 1 / 2.5e-4 = 4e3 bounds them everywhere else — the
+    // near-parallel block below replaces t2, whatever inf or NaN the slabs made of it)
+    const float ic = fast_rcp(q.c), is = fast_rcp(q.s);
     const float aic = fabsf(ic), ais = fabsf(is);
     const float hwa = 0.5f * q.wg, hha = 0.5f * q.hg, hwb = 0.5f * q.wp, hhb = 0.5f * q.hp;
     const float pax = -fmaf(q.dx, q.cb, q.dy * q.sb), pay = fmaf(q.dx, q.sb, -(q.dy * q.cb));
@@ -658,7 +709,7 @@ SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode
     // the two jitter steps cancelled: DESIGN.md §9.  (Two compares and a scalar OR of their masks; written as one
     // condition the compiler turns them into abs / canonicalise / min / compare: five VALU instructions)
     const bool near_s = fabsf(q.s) < kNearParallel, near_c = fabsf(q.c) < kNearParallel;
-    if (SPH_SITE(3) (SPH_ANY_LANE(near_s) || SPH_ANY_LANE(near_c))) {
+    if (SPH_SITE(3) SPH_ANY_LANE2(near_s, near_c)) {
         SPH_SITE_HIT(3);
         if (near_s | near_c) t2 = 2.0f * near_parallel_inter(pax, pay, q.c, q.s, hwa, hha, hwb, hhb);
     }
@@ -668,7 +719,9 @@ SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode
     float rb = fast_rcp(base);
     rb = rb * fmaf(-base, rb, 2.0f);  // one Newton step: ~0.5 ulp quotient without the IEEE divide expansion
     const float iou = fminf(fmaxf(inter * rb, 0.0f), 1.0f);
-    return carrier != carrier ? __builtin_nanf("") : iou;
+    if (DIM == 5) return carrier != carrier ? __builtin_nanf("") : iou;
+    if (__builtin_expect(nan_wave != 0ull, 0)) return nan_lane ? __builtin_nanf("") : iou;
+    return iou;
 }
 
 // VARIANT: 0 standard, 1 efficient.  Returns clamp(IoU, 0, 1) of one pair (one-lane-per-pair kernels, NMS rows, host

@@ -211,7 +211,12 @@ __global__ __launch_bounds__(kBlock, REF ? 4 : (DIM == 4 ? 7 : 5)) void iou_alig
 //   * workgroups of 1 / 2 / 4 / 8 / 16 independent waves: the same within 1 % from 100 k to 8 M pairs (16: +3 %;
 //     r02z_ab_wg*.log); 4 stays;
 //   * rotating which wave of the persistent form takes which leftover chunk: the hardware already rotates the
-//     wave -> SIMD placement from workgroup to workgroup (tools/ubench/hwid.hip); +0.3 us, removed.
+//     wave -> SIMD placement from workgroup to workgroup (tools/ubench/hwid.hip); +0.3 us, removed;
+//   * finishing-pass trim, bit-identical (profiles/r08a_finish_trim.log): NaN test folded into the
+//     `similar` test, no clamp of the clip's reciprocals, survivor mask and two-condition guards from ballots of single
+//     compares: SQ_INSTS_VALU 3.62 -> 3.49 M per launch, 7.21 -> 7.05 us per 1 M pairs.  Measured on the ISA and not kept: a
+//     "clean" bit from the cull (its range tests cost the cull more than the clamps they would skip), passes peeled out
+//     of the loop (no hoisted rare-block constants, but every common one re-materialised per use: -5 v_mov, twice the code).
 template <int DIM, int SLICES>
 struct ChunkQueue {
     float f[2 * DIM][64 * SLICES];
@@ -269,11 +274,20 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
 #if defined(SPH_ABL_NOCULL)
         const bool culled = ((lane * 2654435761u + s * 40503u + blockIdx.x) >> 7) % 5 >= 2;   // ABLATION: 40 % survive, no cull arithmetic
 #else
-        const bool culled = fast_cull<DIM, VARIANT == VARIANT_LEGACY>(x[s], y[s], edge);
+        const CullParts cp = fast_cull_parts<DIM, VARIANT == VARIANT_LEGACY>(x[s], y[s], edge);
+        const bool culled = cp.in_sizes & cp.in_theta & cp.apart;
+        const unsigned long long cm = __builtin_amdgcn_ballot_w64(cp.in_sizes) & __builtin_amdgcn_ballot_w64(cp.in_theta) &
+                                      __builtin_amdgcn_ballot_w64(cp.apart);
 #endif
         const bool inside = i < n, surv = inside & !culled;
-        if (inside & culled) out[i] = 0.0f;   // (non-temporal stores here and below: 8.42 vs 8.30 us at 1 M, 51.4 vs 48.1 at 8 M)
+#if defined(SPH_ABL_NOCULL)
         const unsigned long long m = __builtin_amdgcn_ballot_w64(surv);
+#else
+        // (the mask from the ballots of single compares, taken before the branch of the store: the ballot of `surv`, or of a
+        // compare whose mask crosses a branch, costs two more VALU instructions; see CullParts)
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(inside) & ~cm;
+#endif
+        if (inside & culled) out[i] = 0.0f;   // (non-temporal stores here and below: 8.42 vs 8.30 us at 1 M, 51.4 vs 48.1 at 8 M)
         if (surv) {
             const int slot = count + rank_below(m);
 #pragma unroll
