@@ -186,6 +186,46 @@ int sph2pob_loss_grad_scale_f32(const float* stash, const float* grad_out, int g
                                 int box_dim, void* stream);
 
 /*
+ * Sph2PobGDLoss / Sph2PobKFLoss: mmrotate's Gaussian-distance (gaussian_dist_loss.py) and KFIoU (kf_iou_loss.py) bodies
+ * on the Sph2Pob planar boxes (the same front end as the IoU family: spherical jitter, sph2pob_standard(..., 'rad'),
+ * rotated jitter), box X -> N((x, y), R(a) diag(w^2/4, h^2/4) R(a)^T) with w, h clamped to [1e-7, 1e7].  The bodies are
+ * restated from mmrotate 0.3.2's published source (parity unpinned).  Per element, P = planar pred, T = planar target:
+ *   GWD        d = sqrt(max(|mu_P - mu_T|^2 + alpha^2 * (tr S_P + tr S_T - 2 sqrt(max(tr(S_P S_T) + 2t, 1e-7))), 1e-7)),
+ *              t = sqrt(max(det S_P det S_T, 1e-7)); OPT_NORMALIZE divides by 2 t^(1/4) (with mmrotate's clamps)
+ *   KLD        d = KL(P || T)-like kld_loss with alpha (P is the reference Gaussian); OPT_SQRT: sqrt(max(d, 1e-7))
+ *   JD         d = (kld(P, T) + kld(T, P)) / 2 before the sqrt; OPT_SQRT as KLD
+ *   KLD_SYMMAX / KLD_SYMMIN   d = max | min of kld(P, T), kld(T, P), each after the OPT_SQRT step
+ *   GD result: post(d) = [log1p(d) | sqrt(max(d, 1e-7)) | d], then 1 - 1 / (tau + .) if tau >= 1
+ *   KF         loss = max(smoothL1_beta(|mu_P - mu_T|) summed over x, y + kf, 0), kf = 1 - KFIoU | -ln(KFIoU + eps) |
+ *              exp(1 - KFIoU) - 1, KFIoU = Vb / (Vb_P + Vb_T - Vb + eps), Vb = 4 sqrt(det) of S_T - S_T (S_T + S_P)^-1 S_T
+ *              (in closed form: always positive, where mmrotate's fp32 matrix inverse can give NaN)
+ * type_flags: SPH2POB_GAUSS_* | SPH2POB_FLAG_REFERENCE_ORDER (reference-order front end).  fun: SPH2POB_GAUSS_FUN_NONE |
+ * LOG1P | SQRT for the GD types, NONE | LN | EXP for KF.  opts: SPH2POB_GAUSS_OPT_* (KF ignores them, GWD reads NORMALIZE,
+ * the kld family SQRT).  tau / alpha: GD only; beta / eps: KF only.  Every clamp gates the gradient as torch.clamp does.
+ * The four entry points have the contracts of their sph2pob_loss_* counterparts (weights, scale, the deterministic sum,
+ * grad_stride, the one-pass form + sph2pob_loss_grad_scale_f32, sph2pob_loss_sum_workspace_floats workspace).
+ */
+enum { SPH2POB_GAUSS_GWD = 0, SPH2POB_GAUSS_KLD = 1, SPH2POB_GAUSS_JD = 2, SPH2POB_GAUSS_KLD_SYMMAX = 3,
+       SPH2POB_GAUSS_KLD_SYMMIN = 4, SPH2POB_GAUSS_KF = 5 };
+enum { SPH2POB_GAUSS_FUN_NONE = 0, SPH2POB_GAUSS_FUN_LOG1P = 1, SPH2POB_GAUSS_FUN_SQRT = 2, SPH2POB_GAUSS_FUN_LN = 3,
+       SPH2POB_GAUSS_FUN_EXP = 4 };
+enum { SPH2POB_GAUSS_OPT_SQRT = 1, SPH2POB_GAUSS_OPT_NORMALIZE = 2 };
+int sph2pob_gauss_loss_fwd_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
+                               float* loss, int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha,
+                               int opts, float beta, float eps, void* stream);
+int sph2pob_gauss_loss_bwd_f32(const float* pred, const float* target, const float* weight, int weight_dim,
+                               const float* grad_out, int grad_stride, float scale, float* grad_pred, float* grad_target,
+                               int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha, int opts,
+                               float beta, float eps, void* stream);
+int sph2pob_gauss_loss_fwd_sum_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
+                                   float* out, float* workspace, int64_t n, int box_dim, int type_flags, int fun, float tau,
+                                   float alpha, int opts, float beta, float eps, void* stream);
+int sph2pob_gauss_loss_fwd_grad_f32(const float* pred, const float* target, const float* weight, int weight_dim,
+                                    float scale, float* loss, float* out_sum, float* workspace, float* grad_pred,
+                                    float* grad_target, int64_t n, int box_dim, int type_flags, int fun, float tau,
+                                    float alpha, int opts, float beta, float eps, void* stream);
+
+/*
  * out[0] = scale * sum(x[0..n)) — deterministic two-pass tree (bitwise reproducible, no float atomics); the
  * reduction step of weight_reduce_loss (mmdet/models/losses/utils.py:47-55).  workspace: device buffer of at
  * least sph2pob_sum_workspace_floats() floats.

@@ -40,7 +40,9 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_transform_bwd_f32', 'sph2pob_transform_bwd_general_f32', 'sph2pob_loss_fwd_f32', 'sph2pob_loss_bwd_f32',
               'sph2pob_loss_fwd_sum_f32', 'sph2pob_loss_fwd_grad_f32', 'sph2pob_loss_grad_scale_f32', 'sph2pob_sum_f32',
               'sph2pob_nms_segmented_f32', 'sph2pob_nms_f32', 'sph2pob_assign_f32', 'sph2pob_coder_encode_f32',
-              'sph2pob_coder_decode_f32', 'sph2pob_coder_decode_bwd_f32', 'sph2pob_obb_l1_fwd_f32', 'sph2pob_obb_l1_bwd_f32']
+              'sph2pob_coder_decode_f32', 'sph2pob_coder_decode_bwd_f32', 'sph2pob_obb_l1_fwd_f32', 'sph2pob_obb_l1_bwd_f32',
+              'sph2pob_gauss_loss_fwd_f32', 'sph2pob_gauss_loss_bwd_f32', 'sph2pob_gauss_loss_fwd_sum_f32',
+              'sph2pob_gauss_loss_fwd_grad_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_kernels_common.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
 # half the rate of plain VALU on gfx950 (tools/ubench/valu_rate2.hip), measured 12 % slower on the dominant kernel
@@ -55,6 +57,7 @@ HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
 _c_f32p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
+_GAUSS_TAIL = [_int, _int, ctypes.c_float, ctypes.c_float, _int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
 
 # name -> argtypes (restype is always int unless listed in _RESTYPES); mirrors include/sph2pob_hip.h
 SIGNATURES = {
@@ -80,6 +83,14 @@ SIGNATURES = {
     'sph2pob_loss_fwd_grad_f32': [_c_f32p, _c_f32p, _c_f32p, _int, ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
                                   _i64, _int, _int, ctypes.c_float, ctypes.c_void_p],
     'sph2pob_loss_grad_scale_f32': [_c_f32p, _c_f32p, _int, _c_f32p, _i64, _int, ctypes.c_void_p],
+    # Gaussian losses: the sph2pob_loss_* leading arguments, then (type_flags, fun, tau, alpha, opts, beta, eps)
+    'sph2pob_gauss_loss_fwd_f32': [_c_f32p, _c_f32p, _c_f32p, _int, ctypes.c_float, _c_f32p, _i64, _int] + _GAUSS_TAIL,
+    'sph2pob_gauss_loss_bwd_f32': [_c_f32p, _c_f32p, _c_f32p, _int, _c_f32p, _int, ctypes.c_float, _c_f32p, _c_f32p, _i64,
+                                   _int] + _GAUSS_TAIL,
+    'sph2pob_gauss_loss_fwd_sum_f32': [_c_f32p, _c_f32p, _c_f32p, _int, ctypes.c_float, _c_f32p, _c_f32p, _i64, _int] +
+                                      _GAUSS_TAIL,
+    'sph2pob_gauss_loss_fwd_grad_f32': [_c_f32p, _c_f32p, _c_f32p, _int, ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                        _c_f32p, _i64, _int] + _GAUSS_TAIL,
     'sph2pob_sum_workspace_floats': [],
     'sph2pob_sum_f32': [_c_f32p, _i64, ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_void_p],
     'sph2pob_assign_workspace_bytes': [_i64, _i64],

@@ -173,9 +173,10 @@ int loss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int 
     return SPH2POB_OK;
 }
 // one pass over the pairs: loss element (times w), IoU, gradients (times g) as asked for; returns the sum of the elements
-template <int DIM, bool FAST>
-double loss_pass(const float* pred, const float* target, const float* weight, int wd, float scale, const float* grad_out, int grad_stride,
-                 float* loss, float* iou, float* gpred, float* gtarget, int64_t n, int mode, float eps) {
+// (Body: the per-pair body of the kernels, IouBody | GaussBody of sph2pob_loss.hpp)
+template <int DIM, bool FAST, class Body>
+double loss_pass(const Body& body, const float* pred, const float* target, const float* weight, int wd, float scale,
+                 const float* grad_out, int grad_stride, float* loss, float* iou, float* gpred, float* gtarget, int64_t n) {
     const int t = cpu_threads();
     std::vector<double> partial((size_t)t + 1, 0.0);
     const int64_t per = (n + t - 1) / std::max(t, 1);
@@ -188,8 +189,8 @@ double loss_pass(const float* pred, const float* target, const float* weight, in
             load_box<DIM>(pred, i, x);
             load_box<DIM>(target, i, y);
             const bool need_grad = gpred || gtarget;
-            const float l = need_grad ? pair_loss<DIM, true, FAST>(x, y, mode, eps, &io, gx, gy)
-                                      : pair_loss<DIM, false, FAST>(x, y, mode, eps, &io, gx, gy);
+            const float l = need_grad ? body.template eval<DIM, true, FAST>(x, y, &io, gx, gy)
+                                      : body.template eval<DIM, false, FAST>(x, y, &io, gx, gy);
             const float lw = w == 0.0f ? 0.0f : l * w;   // the kernels skip all-zero-weight waves: a zero weight gives exact zeros
             if (loss) loss[i] = lw;
             if (iou) iou[i] = io;
@@ -205,10 +206,31 @@ double loss_pass(const float* pred, const float* target, const float* weight, in
     for (double v : partial) s += v;   // fixed order: reproducible for a given thread count
     return s;
 }
-template <class... A>
-double loss_pass_sel(int box_dim, bool fast, A... a) {
-    if (box_dim == 4) return fast ? loss_pass<4, true>(a...) : loss_pass<4, false>(a...);
-    return fast ? loss_pass<5, true>(a...) : loss_pass<5, false>(a...);
+template <class Body, class... A>
+double loss_pass_body(int box_dim, bool fast, const Body& body, A... a) {
+    if (box_dim == 4) return fast ? loss_pass<4, true>(body, a...) : loss_pass<4, false>(body, a...);
+    return fast ? loss_pass<5, true>(body, a...) : loss_pass<5, false>(body, a...);
+}
+// the IoU family: (..., n, mode, eps) as the entry points pass them
+double loss_pass_sel(int box_dim, bool fast, const float* pred, const float* target, const float* weight, int wd, float scale,
+                     const float* grad_out, int grad_stride, float* loss, float* iou, float* gpred, float* gtarget, int64_t n,
+                     int mode, float eps) {
+    return loss_pass_body(box_dim, fast, IouBody{mode, eps}, pred, target, weight, wd, scale, grad_out, grad_stride, loss, iou,
+                          gpred, gtarget, n);
+}
+// the Gaussian family: the launchers' argument checks (sph2pob_loss.hip: gauss_check)
+int gauss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int type_flags, int fun, int opts) {
+    const int type = type_flags & 0xff;
+    if (type_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    if (type < SPH2POB_GAUSS_GWD || type > SPH2POB_GAUSS_KF) return SPH2POB_ERR_OPTION;
+    const bool fun_ok = type == SPH2POB_GAUSS_KF
+                            ? (fun == SPH2POB_GAUSS_FUN_NONE || fun == SPH2POB_GAUSS_FUN_LN || fun == SPH2POB_GAUSS_FUN_EXP)
+                            : (fun >= SPH2POB_GAUSS_FUN_NONE && fun <= SPH2POB_GAUSS_FUN_SQRT);
+    if (!fun_ok || (opts & ~(SPH2POB_GAUSS_OPT_SQRT | SPH2POB_GAUSS_OPT_NORMALIZE))) return SPH2POB_ERR_OPTION;
+    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
+    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+    return SPH2POB_OK;
 }
 
 // greedy NMS per class segment (sph2pob_nms_segmented_f32)
@@ -351,6 +373,62 @@ int sph2pob_loss_fwd_grad_f32_cpu(const float* pred, const float* target, const 
     if (n > 0 && (!pred || !target || !grad_pred)) return SPH2POB_ERR_NULL;
     const double s = n ? loss_pass_sel(box_dim, !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER), pred, target, weight, weight_dim, scale,
                                        (const float*)nullptr, 0, loss, (float*)nullptr, grad_pred, grad_target, n, loss_mode_flags & 0xff, eps)
+                       : 0.0;
+    if (out_sum) out_sum[0] = (float)s;
+    return SPH2POB_OK;
+}
+
+int sph2pob_gauss_loss_fwd_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
+                                   float* loss, int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha, int opts,
+                                   float beta, float eps, void*) {
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
+    loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER), GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps},
+                   pred, target, weight, weight_dim, scale, (const float*)nullptr, 0, loss, (float*)nullptr, (float*)nullptr,
+                   (float*)nullptr, n);
+    return SPH2POB_OK;
+}
+
+int sph2pob_gauss_loss_bwd_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, const float* grad_out,
+                                   int grad_stride, float scale, float* grad_pred, float* grad_target, int64_t n, int box_dim,
+                                   int type_flags, int fun, float tau, float alpha, int opts, float beta, float eps, void*) {
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
+    loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER), GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps},
+                   pred, target, weight, weight_dim, scale, grad_out, grad_stride, (float*)nullptr, (float*)nullptr, grad_pred,
+                   grad_target, n);
+    return SPH2POB_OK;
+}
+
+int sph2pob_gauss_loss_fwd_sum_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
+                                       float* out, float* workspace, int64_t n, int box_dim, int type_flags, int fun, float tau,
+                                       float alpha, int opts, float beta, float eps, void*) {
+    (void)workspace;
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if (!out || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
+    const double s = n ? loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER),
+                                        GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps}, pred, target, weight,
+                                        weight_dim, 1.0f, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr,
+                                        (float*)nullptr, (float*)nullptr, n)
+                       : 0.0;
+    out[0] = (float)(s * (double)scale);
+    return SPH2POB_OK;
+}
+
+int sph2pob_gauss_loss_fwd_grad_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
+                                        float* loss, float* out_sum, float* workspace, float* grad_pred, float* grad_target,
+                                        int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha, int opts,
+                                        float beta, float eps, void*) {
+    (void)workspace;
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if (n > 0 && (!pred || !target || !grad_pred)) return SPH2POB_ERR_NULL;
+    const double s = n ? loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER),
+                                        GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps}, pred, target, weight,
+                                        weight_dim, scale, (const float*)nullptr, 0, loss, (float*)nullptr, grad_pred,
+                                        grad_target, n)
                        : 0.0;
     if (out_sum) out_sum[0] = (float)s;
     return SPH2POB_OK;

@@ -1,4 +1,4 @@
-// libsph2pob_hip.so — IoU / GIoU / DIoU / CIoU loss forward + backward and the deterministic sum: kernels + C-ABI launchers
+// libsph2pob_hip.so — IoU / GIoU / DIoU / CIoU and Gaussian (GWD / KLD / JD / KFIoU) loss forward + backward and the deterministic sum: kernels + C-ABI launchers
 // (include/sph2pob_hip.h).  gfx950 only.
 
 #include "sph2pob_kernels_common.hpp"
@@ -205,6 +205,150 @@ __global__ __launch_bounds__(kBlock) void sum_pass2(const float* __restrict__ ws
 }
 
 
+
+// ---- Sph2PobGDLoss / Sph2PobKFLoss kernels: the IoU family's four kernels above with the per-pair body GaussBody
+// (sph2pob_loss.hpp), passed by value.  The IoU kernels keep their own templates: routing them through a generic body
+// changes their instruction schedule (same instruction count, different register assignment), and their ISA is pinned.
+template <int DIM, bool FAST>
+__global__ __launch_bounds__(kBlock) void gauss_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                          const float* __restrict__ weight, int wd, float scale,
+                                                          float* __restrict__ loss, int64_t n, const GaussBody body) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float x[5], y[5], gx[5], gy[5];
+    const float w = scale * element_weight<DIM>(weight, wd, i);
+    if (__builtin_amdgcn_ballot_w64(w != 0.0f) == 0) {   // all-zero-weight wave (see loss_fwd_kernel)
+        loss[i] = 0.0f;
+        return;
+    }
+    load_box<DIM>(pred, i, x);
+    load_box<DIM>(target, i, y);
+    loss[i] = pair_gauss_loss<DIM, false, FAST>(x, y, body, gx, gy) * w;
+}
+
+template <int DIM, bool FAST>
+__global__ __launch_bounds__(kBlock) void gauss_fwd_sum_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                              const float* __restrict__ weight, int wd,
+                                                              float* __restrict__ partial, int64_t n, const GaussBody body) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    float v = 0.0f;
+    const bool live = i < n;
+    const float w = live ? element_weight<DIM>(weight, wd, i) : 0.0f;
+    if (__builtin_amdgcn_ballot_w64(w != 0.0f) != 0) {
+        if (live) {
+            float x[5], y[5], gx[5], gy[5];
+            load_box<DIM>(pred, i, x);
+            load_box<DIM>(target, i, y);
+            v = pair_gauss_loss<DIM, false, FAST>(x, y, body, gx, gy) * w;
+        }
+    }
+    const float r = block_sum(v);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// the gradient rows of a pair, times g (GT: also the target's)
+template <int DIM, bool GT>
+__device__ __forceinline__ void store_grads(float* __restrict__ gpred, float* __restrict__ gtarget, int64_t i, float g,
+                                            const float (&gx)[5], const float (&gy)[5]) {
+    if (DIM == 4) {
+        reinterpret_cast<float4*>(gpred)[i] = make_float4(g * gx[0], g * gx[1], g * gx[2], g * gx[3]);
+        if (GT) reinterpret_cast<float4*>(gtarget)[i] = make_float4(g * gy[0], g * gy[1], g * gy[2], g * gy[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 5; k++) gpred[i * 5 + k] = g * gx[k];
+        if (GT) {
+#pragma unroll
+            for (int k = 0; k < 5; k++) gtarget[i * 5 + k] = g * gy[k];
+        }
+    }
+}
+
+template <int DIM, bool FAST, bool GT>
+__global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void gauss_bwd_kernel(const float* __restrict__ pred,
+                                                          const float* __restrict__ target,
+                                                          const float* __restrict__ weight, int wd,
+                                                          const float* __restrict__ grad_out, int grad_stride,
+                                                          float scale, float* __restrict__ gpred,
+                                                          float* __restrict__ gtarget, int64_t n, const GaussBody body) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float x[5], y[5], gx[5], gy[5];
+    const float g = grad_out[i * grad_stride] * scale * element_weight<DIM>(weight, wd, i);
+    if (__builtin_amdgcn_ballot_w64(g != 0.0f) == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) gx[k] = gy[k] = 0.0f;
+    } else {
+        load_box<DIM>(pred, i, x);
+        load_box<DIM>(target, i, y);
+        pair_gauss_loss<DIM, true, FAST>(x, y, body, gx, gy);
+    }
+    store_grads<DIM, GT>(gpred, gtarget, i, g, gx, gy);
+}
+
+template <int DIM, bool FAST, bool GT>
+__global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void gauss_fwd_grad_kernel(const float* __restrict__ pred,
+                                                               const float* __restrict__ target,
+                                                               const float* __restrict__ weight, int wd, float scale,
+                                                               float* __restrict__ loss, float* __restrict__ partial,
+                                                               float* __restrict__ gpred, float* __restrict__ gtarget,
+                                                               int64_t n, const GaussBody body) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < n;
+    const float w = live ? scale * element_weight<DIM>(weight, wd, i) : 0.0f;
+    float x[5], y[5], gx[5], gy[5], l = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 5; k++) gx[k] = gy[k] = 0.0f;
+    if (__builtin_amdgcn_ballot_w64(w != 0.0f) != 0) {
+        if (live) {
+            load_box<DIM>(pred, i, x);
+            load_box<DIM>(target, i, y);
+            l = pair_gauss_loss<DIM, true, FAST>(x, y, body, gx, gy) * w;
+        }
+    }
+    if (live) {
+        if (loss) loss[i] = l;
+        store_grads<DIM, GT>(gpred, gtarget, i, w, gx, gy);
+    }
+    if (partial) {
+        const float r = block_sum(live ? l : 0.0f);
+        if (threadIdx.x == 0) partial[blockIdx.x] = r;
+    }
+}
+
+// out[0] = scale * the fixed-order sum of nb workgroup partials in `workspace` (as sph2pob_loss_fwd_sum_f32 adds them)
+void launch_partial_sum(float* workspace, int64_t nb, float scale, float* out, hipStream_t s) {
+    if (nb <= 65536) {
+        hipLaunchKernelGGL(sum_pass2, dim3(1), dim3(kBlock), 0, s, workspace, (int)nb, scale, out);
+    } else {
+        float* ws2 = workspace + nb;
+        hipLaunchKernelGGL(sum_pass1, dim3(kSumBlocks), dim3(kBlock), 0, s, workspace, nb, ws2);
+        hipLaunchKernelGGL(sum_pass2, dim3(1), dim3(kBlock), 0, s, ws2, kSumBlocks, scale, out);
+    }
+}
+
+static_assert(SPH2POB_GAUSS_GWD == GAUSS_GWD && SPH2POB_GAUSS_KLD == GAUSS_KLD && SPH2POB_GAUSS_JD == GAUSS_JD &&
+              SPH2POB_GAUSS_KLD_SYMMAX == GAUSS_KLD_SYMMAX && SPH2POB_GAUSS_KLD_SYMMIN == GAUSS_KLD_SYMMIN &&
+              SPH2POB_GAUSS_KF == GAUSS_KF, "loss type codes");
+static_assert(SPH2POB_GAUSS_FUN_NONE == GFUN_NONE && SPH2POB_GAUSS_FUN_LOG1P == GFUN_LOG1P && SPH2POB_GAUSS_FUN_SQRT == GFUN_SQRT &&
+              SPH2POB_GAUSS_FUN_LN == GFUN_LN && SPH2POB_GAUSS_FUN_EXP == GFUN_EXP, "post-map codes");
+static_assert(SPH2POB_GAUSS_OPT_SQRT == GOPT_SQRT && SPH2POB_GAUSS_OPT_NORMALIZE == GOPT_NORMALIZE, "option bits");
+
+// argument checks of the Gaussian launchers: SPH2POB_GAUSS_* type (| SPH2POB_FLAG_REFERENCE_ORDER), a post-map the type
+// accepts (GD: none | log1p | sqrt, KF: none | ln | exp), SPH2POB_GAUSS_OPT_* options
+int gauss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int type_flags, int fun, int opts) {
+    const int type = type_flags & 0xff;
+    if (type_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    if (type < SPH2POB_GAUSS_GWD || type > SPH2POB_GAUSS_KF) return SPH2POB_ERR_OPTION;
+    const bool fun_ok = type == SPH2POB_GAUSS_KF
+                            ? (fun == SPH2POB_GAUSS_FUN_NONE || fun == SPH2POB_GAUSS_FUN_LN || fun == SPH2POB_GAUSS_FUN_EXP)
+                            : (fun >= SPH2POB_GAUSS_FUN_NONE && fun <= SPH2POB_GAUSS_FUN_SQRT);
+    if (!fun_ok || (opts & ~(SPH2POB_GAUSS_OPT_SQRT | SPH2POB_GAUSS_OPT_NORMALIZE))) return SPH2POB_ERR_OPTION;
+    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
+    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+    return SPH2POB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -321,6 +465,91 @@ int sph2pob_loss_fwd_grad_f32(const float* pred, const float* target, const floa
     }
     return launch_status();
 }
+
+// ---- Sph2PobGDLoss / Sph2PobKFLoss: the four forms of the IoU family, per-pair body GaussBody ----
+#define SPH_GAUSS_SEL(LAUNCH)                                                           \
+    do {                                                                                \
+        const bool fast = !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER);                 \
+        if (box_dim == 4) { if (fast) LAUNCH(4, true); else LAUNCH(4, false); }         \
+        else { if (fast) LAUNCH(5, true); else LAUNCH(5, false); }                      \
+    } while (0)
+
+int sph2pob_gauss_loss_fwd_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
+                               float* loss, int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha,
+                               int opts, float beta, float eps, void* stream) {
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
+    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
+    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    hipStream_t s = (hipStream_t)stream;
+#define SPH_GAUSS_FWD(D, F) \
+    hipLaunchKernelGGL((gauss_fwd_kernel<D, F>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, n, body)
+    SPH_GAUSS_SEL(SPH_GAUSS_FWD);
+#undef SPH_GAUSS_FWD
+    return launch_status();
+}
+
+int sph2pob_gauss_loss_bwd_f32(const float* pred, const float* target, const float* weight, int weight_dim,
+                               const float* grad_out, int grad_stride, float scale, float* grad_pred, float* grad_target,
+                               int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha, int opts,
+                               float beta, float eps, void* stream) {
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
+    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
+    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    hipStream_t s = (hipStream_t)stream;
+#define SPH_GAUSS_BWD(D, F) \
+    do { if (grad_target) hipLaunchKernelGGL((gauss_bwd_kernel<D, F, true>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, body); \
+         else hipLaunchKernelGGL((gauss_bwd_kernel<D, F, false>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, body); } while (0)
+    SPH_GAUSS_SEL(SPH_GAUSS_BWD);
+#undef SPH_GAUSS_BWD
+    return launch_status();
+}
+
+int sph2pob_gauss_loss_fwd_sum_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
+                                   float* out, float* workspace, int64_t n, int box_dim, int type_flags, int fun, float tau,
+                                   float alpha, int opts, float beta, float eps, void* stream) {
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if (!out || !workspace || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
+    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = (n + kBlock - 1) / kBlock;
+    if (nb > 0) {
+        dim3 grid((unsigned)nb);
+#define SPH_GAUSS_FWDS(D, F) \
+        hipLaunchKernelGGL((gauss_fwd_sum_kernel<D, F>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, workspace, n, body)
+        SPH_GAUSS_SEL(SPH_GAUSS_FWDS);
+#undef SPH_GAUSS_FWDS
+    }
+    launch_partial_sum(workspace, nb, scale, out, s);
+    return launch_status();
+}
+
+int sph2pob_gauss_loss_fwd_grad_f32(const float* pred, const float* target, const float* weight, int weight_dim,
+                                    float scale, float* loss, float* out_sum, float* workspace, float* grad_pred,
+                                    float* grad_target, int64_t n, int box_dim, int type_flags, int fun, float tau,
+                                    float alpha, int opts, float beta, float eps, void* stream) {
+    if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
+    if ((out_sum && !workspace) || (n > 0 && (!pred || !target || !grad_pred))) return SPH2POB_ERR_NULL;
+    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = (n + kBlock - 1) / kBlock;
+    float* partial = out_sum ? workspace : nullptr;
+    if (nb > 0) {
+        dim3 grid((unsigned)nb);
+#define SPH_GAUSS_FG(D, F) \
+        do { if (grad_target) hipLaunchKernelGGL((gauss_fwd_grad_kernel<D, F, true>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, partial, grad_pred, grad_target, n, body); \
+             else hipLaunchKernelGGL((gauss_fwd_grad_kernel<D, F, false>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, partial, grad_pred, grad_target, n, body); } while (0)
+        SPH_GAUSS_SEL(SPH_GAUSS_FG);
+#undef SPH_GAUSS_FG
+    }
+    if (out_sum) launch_partial_sum(workspace, nb, 1.0f, out_sum, s);   // scale is already inside the elements
+    return launch_status();
+}
+#undef SPH_GAUSS_SEL
 
 int sph2pob_loss_grad_scale_f32(const float* stash, const float* grad_out, int grad_stride, float* out, int64_t n,
                                 int box_dim, void* stream) {

@@ -405,4 +405,254 @@ SPH_DEV void pair_transform_bwd(const float (&in1)[5], const float (&in2)[5], co
     planar_to_spherical_grads<DIM>(f, gP, gT, VARIANT == VARIANT_STANDARD ? 0.5f : 0.0f, in1, in2, jitter, edge, gin1, gin2);
 }
 
+// ================= Gaussian losses: Sph2PobGDLoss (GWD / KLD / JD / KLD sym-max / sym-min) and Sph2PobKFLoss =================
+// mmrotate's gaussian_dist_loss.py / kf_iou_loss.py bodies (restated from the published source: parity UNPINNED) on the
+// planar boxes the Sph2Pob front end produces.  Box X -> N(mu = (x, y), Sigma = R(a) diag(A, B) R(a)^T), A = w^2/4,
+// B = h^2/4 (w, h clamped to [1e-7, 1e7]); with D = a_P - a_T, c2 = cos^2 D, s2 = sin^2 D every matrix expression has a
+// closed form in (A_P, B_P, A_T, B_T, c2, s2) and the centre offset in the reference box's axes.  Every clamp gates its
+// gradient as torch.clamp does (passes on the closed interval).
+enum : int { GAUSS_GWD = 0, GAUSS_KLD = 1, GAUSS_JD = 2, GAUSS_KLD_SYMMAX = 3, GAUSS_KLD_SYMMIN = 4, GAUSS_KF = 5 };
+enum : int { GFUN_NONE = 0, GFUN_LOG1P = 1, GFUN_SQRT = 2, GFUN_LN = 3, GFUN_EXP = 4 };
+enum : int { GOPT_SQRT = 1, GOPT_NORMALIZE = 2 };
+
+// sqrt(max(x, lo)) and its gate
+SPH_DEV float sqrt_floor(float x, float lo, bool& pass) {
+    pass = x >= lo;
+    return sqrtf(fmaxf(x, lo));
+}
+
+// post-map of gaussian_dist_loss.postprocess: log1p | sqrt(max(., 1e-7)) | identity, then 1 - 1 / (tau + d) when tau >= 1
+SPH_DEV float gauss_post(float d, int fun, float tau, float& dpost) {
+    float v = d, g = 1.0f;
+    if (fun == GFUN_LOG1P) {
+        v = log1pf(d);
+        g = rcp_nr(1.0f + d);
+    } else if (fun == GFUN_SQRT) {
+        bool pass;
+        v = sqrt_floor(d, 1e-7f, pass);
+        g = pass ? 0.5f * rcp_nr(v) : 0.0f;
+    }
+    if (tau >= 1.0f) {
+        const float q = rcp_nr(tau + v);
+        g *= q * q;
+        v = 1.0f - q;
+    }
+    dpost = g;
+    return v;
+}
+
+// kld_loss before its sqrt / post-map, reference box a (the inverse is taken of a's covariance), other box b:
+//   0.5 d^T Sa^-1 d / alpha^2 + 0.5 tr(Sa^-1 Sb) + 0.5 ln(det Sa / det Sb) - 1,   (u, v) = d in a's axes
+SPH_DEV float kld_raw(float Aa, float Ba, float Ab, float Bb, float u, float v, float c2, float s2, float ia2, float lr) {
+    const float iAa = rcp_nr(Aa), iBa = rcp_nr(Ba);
+    const float xy = 0.5f * (u * u * iAa + v * v * iBa);
+    const float tr = (Ab * c2 + Bb * s2) * iAa + (Ab * s2 + Bb * c2) * iBa;
+    return xy * ia2 + 0.5f * tr + 0.5f * lr - 1.0f;
+}
+// its adjoint for an upstream gradient G: accumulates d/d(Aa, Ba, Ab, Bb), d/d(centre offset x), d/d(a_a) through the
+// axes of (u, v) [(ca, sa) = cos / sin a_a] and d/d(a_a - a_b) [cs = cos * sin of a_a - a_b]
+SPH_DEV void kld_raw_adj(float G, float Aa, float Ba, float Ab, float Bb, float u, float v, float ca, float sa, float c2,
+                         float s2, float cs, float ia2, float& gAa, float& gBa, float& gAb, float& gBb, float& gdx,
+                         float& gaa, float& gdab) {
+    const float iAa = rcp_nr(Aa), iBa = rcp_nr(Ba);
+    const float gu = G * ia2 * u * iAa, gv = G * ia2 * v * iBa;
+    gdx += gu * ca - gv * sa;
+    gaa += gu * v - gv * u;
+    const float hG = 0.5f * G;
+    gAa += hG * (iAa - (ia2 * u * u + Ab * c2 + Bb * s2) * (iAa * iAa));
+    gBa += hG * (iBa - (ia2 * v * v + Ab * s2 + Bb * c2) * (iBa * iBa));
+    gAb += hG * ((c2 * iAa + s2 * iBa) - rcp_nr(Ab));
+    gBb += hG * ((s2 * iAa + c2 * iBa) - rcp_nr(Bb));
+    gdab += G * cs * (Bb - Ab) * (iAa - iBa);
+}
+
+// The trailing parameters of the Gaussian launchers, and the per-pair body of their kernels and host twins.
+struct GaussBody {
+    int type, fun;   // GAUSS_*, GFUN_*
+    float tau, alpha;
+    int opts;        // GOPT_SQRT (kld family), GOPT_NORMALIZE (gwd)
+    float beta, eps; // KF: smooth-L1 beta of the centre term, eps of the KFIoU denominator
+    template <int DIM, bool BWD, bool FAST>
+    SPH_DEV float eval(const float (&pred)[5], const float (&target)[5], float* iou_out, float (&gpred)[5],
+                       float (&gtarget)[5]) const;
+};
+
+// Per-pair Gaussian loss element; when BWD, also d(loss)/d(pred[0..DIM)) and d(loss)/d(target[0..DIM)) in 1/degree.
+template <int DIM, bool BWD, bool FAST>
+SPH_DEV float pair_gauss_loss(const float (&pred)[5], const float (&target)[5], const GaussBody& p, float (&gpred)[5],
+                              float (&gtarget)[5]) {
+    if (pair_has_nan<DIM>(pred, target)) {   // a NaN coordinate: NaN loss and NaN gradients for the pair (as pair_loss)
+        const float qnan = __builtin_nanf("");
+#pragma unroll
+        for (int k = 0; k < 5; k++) { gpred[k] = k < DIM ? qnan : 0.0f; gtarget[k] = k < DIM ? qnan : 0.0f; }
+        return qnan;
+    }
+    float b1[5], b2[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) { b1[k] = pred[k]; b2[k] = target[k]; }
+    jitter_spherical<DIM>(b1, b2);
+    LossFront f;
+    if (FAST) loss_front_fast<DIM>(b1, b2, f);
+    else loss_front_reference<DIM>(b1, b2, f);
+    const float dx = f.dx, dy = f.dy, c2 = f.c * f.c, s2 = f.s * f.s, cs = f.c * f.s;
+    // xy_wh_r_2_xy_sigma: wh.clamp(1e-7, 1e7), Sigma = R diag(wh / 2)^2 R^T
+    const float wP = fminf(fmaxf(f.wg, 1e-7f), 1e7f), hP = fminf(fmaxf(f.hg, 1e-7f), 1e7f);
+    const float wT = fminf(fmaxf(f.wp, 1e-7f), 1e7f), hT = fminf(fmaxf(f.hp, 1e-7f), 1e7f);
+    const float AP = 0.25f * wP * wP, BP = 0.25f * hP * hP, AT = 0.25f * wT * wT, BT = 0.25f * hT * hT;
+    const float detP = AP * BP, detT = AT * BT;
+    // adjoint accumulators: d/d(A_P, B_P, A_T, B_T), d/d(dx = T.x - P.x), d/d(a_P - a_T), d/d(a_P), d/d(a_T) (centre axes)
+    float gAP = 0.0f, gBP = 0.0f, gAT = 0.0f, gBT = 0.0f, gdx = 0.0f, gD = 0.0f, gaP = 0.0f, gaT = 0.0f;
+    float loss;
+    if (p.type == GAUSS_KF) {
+        // kfiou_loss with pred_decode = T, targets_decode = P (Sigma_1 from T, Sigma_2 from P)
+        const float V1 = 4.0f * sqrtf(detT), V2 = 4.0f * sqrtf(detP);
+        // det(S_P + S_T); det of S_1 - S_1 (S_1 + S_2)^-1 S_1 = det S_P det S_T / det(S_P + S_T) > 0: Vb is never NaN here
+        const float Ds = (AP + AT) * (BP + BT) * c2 + (AP + BT) * (BP + AT) * s2;
+        const float iDs = rcp_nr(Ds);
+        const float Vb = 4.0f * sqrtf(detP * detT * iDs);
+        const float den = V1 + V2 - Vb + p.eps;
+        const float iden = rcp_nr(den);
+        const float K = Vb * iden;
+        float kf;
+        if (p.fun == GFUN_LN) kf = -logf(K + p.eps);
+        else if (p.fun == GFUN_EXP) kf = expf(1.0f - K) - 1.0f;
+        else kf = 1.0f - K;
+        const float ax = fabsf(dx), ay = fabsf(dy), beta = p.beta;
+        const float xy = (ax < beta ? 0.5f * ax * ax / beta : ax - 0.5f * beta) +
+                         (ay < beta ? 0.5f * ay * ay / beta : ay - 0.5f * beta);
+        const float raw = xy + kf;
+        loss = fmaxf(raw, 0.0f);
+        if (BWD && raw >= 0.0f) {
+            const float sx = dx > 0.0f ? 1.0f : (dx < 0.0f ? -1.0f : 0.0f);
+            gdx = sx * (ax < beta ? ax / beta : 1.0f);
+            float gK;
+            if (p.fun == GFUN_LN) gK = -rcp_nr(K + p.eps);
+            else if (p.fun == GFUN_EXP) gK = -expf(1.0f - K);
+            else gK = -1.0f;
+            const float gVb = gK * (den + Vb) * (iden * iden), gV = -gK * Vb * (iden * iden);
+            // V = 4 sqrt(A B): dV/dA = V / (2A)
+            gAT += gV * 0.5f * V1 * rcp_nr(AT); gBT += gV * 0.5f * V1 * rcp_nr(BT);
+            gAP += gV * 0.5f * V2 * rcp_nr(AP); gBP += gV * 0.5f * V2 * rcp_nr(BP);
+            // ln Vb = ln 4 + (ln A_P + ln B_P + ln A_T + ln B_T - ln Ds) / 2
+            const float h = 0.5f * gVb * Vb;
+            gAP += h * (rcp_nr(AP) - ((BP + BT) * c2 + (BP + AT) * s2) * iDs);
+            gBP += h * (rcp_nr(BP) - ((AP + AT) * c2 + (AP + BT) * s2) * iDs);
+            gAT += h * (rcp_nr(AT) - ((BP + BT) * c2 + (AP + BT) * s2) * iDs);
+            gBT += h * (rcp_nr(BT) - ((AP + AT) * c2 + (BP + AT) * s2) * iDs);
+            gD -= h * 2.0f * cs * (AP - BP) * (AT - BT) * iDs;
+        }
+    } else if (p.type == GAUSS_GWD) {
+        const float targ = detP * detT;
+        bool pt, pr, pd;
+        const float t = sqrt_floor(targ, 1e-7f, pt);
+        const float Q = (AP * AT + BP * BT) * c2 + (AP * BT + BP * AT) * s2;   // tr(S_P S_T)
+        const float R = Q + 2.0f * t;
+        const float S = sqrt_floor(R, 1e-7f, pr);
+        const float whr = (AP + BP) + (AT + BT) - 2.0f * S;
+        const float d2 = (dx * dx + dy * dy) + p.alpha * p.alpha * whr;
+        const float Dd = sqrt_floor(d2, 1e-7f, pd);
+        float d = Dd, norm = 1.0f, r1 = 1.0f, r2 = 1.0f;
+        bool p1 = true, p2 = true, p3 = true;
+        const bool normalize = p.opts & GOPT_NORMALIZE;
+        if (normalize) {   // 2 * sqrt(max(sqrt(max(t, 1e-7)), 1e-7)).clamp(1e-7)
+            r1 = sqrt_floor(t, 1e-7f, p1);
+            r2 = sqrt_floor(r1, 1e-7f, p2);
+            p3 = r2 >= 1e-7f;
+            norm = 2.0f * fmaxf(r2, 1e-7f);
+            d = Dd * rcp_nr(norm);
+        }
+        float gd;
+        loss = gauss_post(d, p.fun, p.tau, gd);
+        if (BWD) {
+            float gDd = gd, gt = 0.0f;
+            if (normalize) {
+                gDd = gd * rcp_nr(norm);
+                const float gnorm = -gDd * Dd * rcp_nr(norm);
+                // d norm / d t = 2 * (1 / (2 r2)) * (1 / (2 r1)), gated
+                if (p1 && p2 && p3) gt += gnorm * 0.5f * rcp_nr(r1 * r2);
+            }
+            const float gd2 = pd ? gDd * 0.5f * rcp_nr(Dd) : 0.0f;
+            gdx = 2.0f * dx * gd2;
+            const float gwhr = p.alpha * p.alpha * gd2;
+            gAP = gBP = gAT = gBT = gwhr;
+            const float gR = pr ? -gwhr * rcp_nr(S) : 0.0f;   // whr = ... - 2 S
+            gt += 2.0f * gR;
+            const float gtarg = pt ? gt * 0.5f * rcp_nr(t) : 0.0f;
+            gAP += gtarg * BP * detT + gR * (AT * c2 + BT * s2);
+            gBP += gtarg * AP * detT + gR * (BT * c2 + AT * s2);
+            gAT += gtarg * BT * detP + gR * (AP * c2 + BP * s2);
+            gBT += gtarg * AT * detP + gR * (BP * c2 + AP * s2);
+            gD = gR * 2.0f * cs * (AP - BP) * (BT - AT);
+        }
+    } else {   // kld family: P is the reference Gaussian of kld(P, T)
+        const float ia2 = 1.0f / (p.alpha * p.alpha);
+        const bool sq = p.opts & GOPT_SQRT;
+        const float ca = f.ca, sa = f.sa, cb = f.cb, sb = f.sb;
+        const float uP = dx * ca + dy * sa, vP = dy * ca - dx * sa;   // centre offset in P's axes
+        const float uT = dx * cb + dy * sb, vT = dy * cb - dx * sb;   // ... in T's axes
+        const float lr = logf(detP * rcp_nr(detT));
+        const float kPT = kld_raw(AP, BP, AT, BT, uP, vP, c2, s2, ia2, lr);
+        const float kTP = p.type == GAUSS_KLD ? 0.0f : kld_raw(AT, BT, AP, BP, uT, vT, c2, s2, ia2, -lr);
+        float d, gPT = 0.0f, gTP = 0.0f;   // d(d) / d(kPT), d(d) / d(kTP)
+        if (p.type == GAUSS_KLD || p.type == GAUSS_JD) {
+            const float r = p.type == GAUSS_KLD ? kPT : 0.5f * (kPT + kTP);
+            const float gr = p.type == GAUSS_KLD ? 1.0f : 0.5f;
+            d = r;
+            float gs = 1.0f;
+            if (sq) { bool ps; d = sqrt_floor(r, 1e-7f, ps); gs = ps ? 0.5f * rcp_nr(d) : 0.0f; }
+            gPT = gr * gs;
+            gTP = p.type == GAUSS_KLD ? 0.0f : gr * gs;
+        } else {
+            float s1 = kPT, s2v = kTP, g1 = 1.0f, g2 = 1.0f;
+            if (sq) {
+                bool ps1, ps2;
+                s1 = sqrt_floor(kPT, 1e-7f, ps1); g1 = ps1 ? 0.5f * rcp_nr(s1) : 0.0f;
+                s2v = sqrt_floor(kTP, 1e-7f, ps2); g2 = ps2 ? 0.5f * rcp_nr(s2v) : 0.0f;
+            }
+            const bool mx = p.type == GAUSS_KLD_SYMMAX;
+            d = mx ? fmaxf(s1, s2v) : fminf(s1, s2v);
+            // torch.maximum / torch.minimum split the gradient evenly on a tie
+            const float w1 = s1 == s2v ? 0.5f : ((s1 > s2v) == mx ? 1.0f : 0.0f);
+            gPT = w1 * g1;
+            gTP = (1.0f - w1) * g2;
+        }
+        float gd;
+        loss = gauss_post(d, p.fun, p.tau, gd);
+        if (BWD) {
+            if (gPT != 0.0f)
+                kld_raw_adj(gd * gPT, AP, BP, AT, BT, uP, vP, ca, sa, c2, s2, cs, ia2, gAP, gBP, gAT, gBT, gdx, gaP, gD);
+            if (gTP != 0.0f) {
+                float gDtp = 0.0f;   // d/d(a_T - a_P)
+                kld_raw_adj(gd * gTP, AT, BT, AP, BP, uT, vT, cb, sb, c2, s2, -cs, ia2, gAT, gBT, gAP, gBP, gdx, gaT, gDtp);
+                gD -= gDtp;
+            }
+        }
+    }
+    if (!BWD) return loss;
+    // A = w^2 / 4: dA/dw = w / 2; the clamp of w passes the gradient on [1e-7, 1e7]
+    const bool gwP = f.wg >= 1e-7f && f.wg <= 1e7f, ghP = f.hg >= 1e-7f && f.hg <= 1e7f;
+    const bool gwT = f.wp >= 1e-7f && f.wp <= 1e7f, ghT = f.hp >= 1e-7f && f.hp <= 1e7f;
+    PlanarGrad gP{-gdx, gwP ? 0.5f * wP * gAP : 0.0f, ghP ? 0.5f * hP * gBP : 0.0f, gD + gaP};
+    PlanarGrad gT{gdx, gwT ? 0.5f * wT * gAT : 0.0f, ghT ? 0.5f * hT * gBT : 0.0f, gaT - gD};
+    planar_to_spherical_grads<DIM>(f, gP, gT, /*x_split=*/0.5f, pred, target, /*jitter=*/true, EDGE_ARC, gpred, gtarget);
+    return loss;
+}
+
+template <int DIM, bool BWD, bool FAST>
+SPH_DEV float GaussBody::eval(const float (&pred)[5], const float (&target)[5], float*, float (&gpred)[5],
+                              float (&gtarget)[5]) const {
+    return pair_gauss_loss<DIM, BWD, FAST>(pred, target, *this, gpred, gtarget);
+}
+
+// The IoU family's trailing launcher parameters as a per-pair body (the host twins' loss pass is generic over the body).
+struct IouBody {
+    int loss_mode;
+    float eps;
+    template <int DIM, bool BWD, bool FAST>
+    SPH_DEV float eval(const float (&pred)[5], const float (&target)[5], float* iou_out, float (&gpred)[5],
+                       float (&gtarget)[5]) const {
+        return pair_loss<DIM, BWD, FAST>(pred, target, loss_mode, eps, iou_out, gpred, gtarget);
+    }
+};
+
 }  // namespace sph2pob

@@ -1,11 +1,14 @@
 from .sph2pob_iou_loss import (OBBIoULoss, Sph2PobIoULoss, SphIoULoss, SphIoULossLegacy,  # noqa: F401
                                sph2pob_iou_loss)
+from .sph2pob_gaussian_loss import (Sph2PobGDLoss, Sph2PobKFLoss, sph2pob_gd_loss,  # noqa: F401
+                                    sph2pob_kf_loss)
 from .sph2pob_l1_loss import Sph2PobL1Loss  # noqa: F401
 from .sph2pob_transform import Sph2PobTransfrom  # noqa: F401
 
-__all__ = ['Sph2PobIoULoss', 'SphIoULoss', 'OBBIoULoss', 'Sph2PobTransfrom', 'sph2pob_iou_loss', 'Sph2PobL1Loss', 'SphIoULossLegacy']
+__all__ = ['Sph2PobIoULoss', 'SphIoULoss', 'OBBIoULoss', 'Sph2PobTransfrom', 'sph2pob_iou_loss', 'Sph2PobL1Loss', 'SphIoULossLegacy',
+           'Sph2PobGDLoss', 'Sph2PobKFLoss', 'sph2pob_gd_loss', 'sph2pob_kf_loss']
 
-from . import sph2pob_mmrotate_losses as _mm  # noqa: E402  (defines Sph2PobGDLoss / Sph2PobKFLoss when mmrotate is present)
+# with mmrotate importable, its GDLoss / KFLoss bodies take the two names over (registry and namespace)
+from . import sph2pob_mmrotate_losses as _mm  # noqa: E402
 for _name in _mm.__all__:
     globals()[_name] = getattr(_mm, _name)
-    __all__.append(_name)

@@ -17,6 +17,9 @@ from .. import _torch_glue as G
 from ..registry import LOSSES
 
 LOSS_MODES = {'iou': 0, 'giou': 1, 'diou': 2, 'ciou': 3}
+# launcher families of _Sph2PobLossFunction: (name prefix of the four C-ABI entry points, element forward takes an `iou` out)
+IOU_FAMILY = ('sph2pob_loss', True)          # trailing arguments: (mode | flags, eps)
+GAUSS_FAMILY = ('sph2pob_gauss_loss', False)  # trailing arguments: (type | flags, fun, tau, alpha, opts, beta, eps)
 
 
 def _mode_code(mode):
@@ -33,6 +36,7 @@ def _f32c(t):
 
 class _Sph2PobLossFunction(torch.autograd.Function):
     """(pred, target[, weight]) -> scale * weighted element losses (reduce=False) or scale * their sum (reduce=True).
+    `fam` picks the launcher family (IOU_FAMILY | GAUSS_FAMILY), `tail` is the tuple of its trailing arguments.
     One node in the autograd graph: `scale` carries loss_weight AND the 1 / n | 1 / (avg_factor + eps) of
     weight_reduce_loss, so 'mean' costs no extra torch op (and no extra backward node).
     When a gradient will be asked for (pred or target requires grad) the forward launch is the fused one
@@ -41,7 +45,7 @@ class _Sph2PobLossFunction(torch.autograd.Function):
     (`sph2pob_loss_grad_scale_f32`).  Without a gradient in sight (evaluation) the plain forward kernels run."""
 
     @staticmethod
-    def forward(ctx, pred, target, weight, mode_c, eps, scale, reduce):
+    def forward(ctx, pred, target, weight, fam, tail, scale, reduce):
         G.require_hip(pred, target)
         n, dim = pred.shape
         p, t = _f32c(pred), _f32c(target)
@@ -51,30 +55,31 @@ class _Sph2PobLossFunction(torch.autograd.Function):
         dev = p.device
         stream = G.raw_stream_of(dev)
         need_p, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        prefix, has_iou = fam
         out = torch.empty(() if reduce else (n,), dtype=torch.float32, device=dev)
         if need_p or need_t:
             gp = torch.empty_like(p)
             gt = torch.empty_like(t) if need_t else None
             ws = G.loss_sum_workspace(dev, n) if reduce else None
-            G.call('sph2pob_loss_fwd_grad_f32', dev, p.data_ptr() if n else None, t.data_ptr() if n else None, wp, wd, scale,
+            G.call(prefix + '_fwd_grad_f32', dev, p.data_ptr() if n else None, t.data_ptr() if n else None, wp, wd, scale,
                    None if reduce else (out.data_ptr() if n else None), out.data_ptr() if reduce else None,
                    ws.data_ptr() if reduce else None, gp.data_ptr() if n else None, gt.data_ptr() if need_t and n else None,
-                   n, dim, mode_c, eps, stream)
+                   n, dim, *tail, stream)
             ctx.save_for_backward(gp, gt, p, t, w)
             ctx.first = True
         elif reduce:
-            G.call('sph2pob_loss_fwd_sum_f32', dev, p.data_ptr() if n else None, t.data_ptr() if n else None, wp, wd, scale,
-                   out.data_ptr(), G.loss_sum_workspace(dev, n).data_ptr(), n, dim, mode_c, eps, stream)
+            G.call(prefix + '_fwd_sum_f32', dev, p.data_ptr() if n else None, t.data_ptr() if n else None, wp, wd, scale,
+                   out.data_ptr(), G.loss_sum_workspace(dev, n).data_ptr(), n, dim, *tail, stream)
         elif n:
-            G.call('sph2pob_loss_fwd_f32', dev, p.data_ptr(), t.data_ptr(), wp, wd, scale, out.data_ptr(), None, n, dim,
-                   mode_c, eps, stream)
-        ctx.meta = (reduce, need_p, need_t, pred.dtype, target.dtype, mode_c, eps, scale, wd)
+            G.call(prefix + '_fwd_f32', dev, p.data_ptr(), t.data_ptr(), wp, wd, scale, out.data_ptr(), *((None,) if has_iou else ()),
+                   n, dim, *tail, stream)
+        ctx.meta = (reduce, need_p, need_t, pred.dtype, target.dtype, prefix, tail, scale, wd)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         gp, gt, p, t, w = ctx.saved_tensors
-        reduce, need_p, need_t, pdt, tdt, mode_c, eps, scale, wd = ctx.meta
+        reduce, need_p, need_t, pdt, tdt, prefix, tail, scale, wd = ctx.meta
         n, dim = gp.shape
         g = _f32c(grad_out)
         stream = G.raw_stream_of(gp.device)
@@ -83,9 +88,9 @@ class _Sph2PobLossFunction(torch.autograd.Function):
             # autograd by the first one — recompute with the two-pass backward kernel
             ngp, ngt = torch.empty_like(p), (torch.empty_like(t) if need_t else None)
             if n:
-                G.call('sph2pob_loss_bwd_f32', p.device, p.data_ptr(), t.data_ptr(), w.data_ptr() if w is not None else None, wd,
+                G.call(prefix + '_bwd_f32', p.device, p.data_ptr(), t.data_ptr(), w.data_ptr() if w is not None else None, wd,
                        g.data_ptr(), 0 if reduce else 1, scale, ngp.data_ptr(), ngt.data_ptr() if need_t else None, n, dim,
-                       mode_c, eps, stream)
+                       *tail, stream)
             return ((ngp if pdt is torch.float32 else ngp.to(pdt)) if need_p else None,
                     (ngt if tdt is torch.float32 else ngt.to(tdt)) if need_t else None, None, None, None, None, None)
         ctx.first = False
@@ -101,30 +106,37 @@ class _Sph2PobLossFunction(torch.autograd.Function):
         return outs[0], outs[1], None, None, None, None, None
 
 
-def sph2pob_iou_loss(pred, target, weight=None, mode='iou', eps=1e-6, reduction='mean', avg_factor=None,
-                     loss_weight=1.0):
-    """Functional form: loss_weight * weight_reduce_loss(obb_iou_loss(sph2pob(pred, target)), weight, ...)."""
-    assert mode in LOSS_MODES
+def weighted_loss_apply(pred, target, weight, fam, tail, reduction, avg_factor, loss_weight):
+    """loss_weight * weight_reduce_loss(element losses of launcher family `fam`, weight, reduction, avg_factor) through
+    one _Sph2PobLossFunction node (mmdet/models/losses/utils.py:30-58)."""
     if pred.dim() != 2 or pred.shape != target.shape or pred.size(1) not in (4, 5):
         raise ValueError(f'pred/target must both be (n, 4) or (n, 5), got {tuple(pred.shape)}, {tuple(target.shape)}')
     if avg_factor is not None and reduction == 'sum':
         raise ValueError('avg_factor can not be used with reduction="sum"')
     n = pred.size(0)
     if reduction == 'none':
-        return _Sph2PobLossFunction.apply(pred, target, weight, _mode_code(mode), float(eps), float(loss_weight), False)
+        return _Sph2PobLossFunction.apply(pred, target, weight, fam, tail, float(loss_weight), False)
     assert reduction in ('mean', 'sum')
     if reduction == 'sum':
         scale = float(loss_weight)
     elif avg_factor is None:
         if n == 0:   # torch: mean of an empty tensor is nan
-            return _Sph2PobLossFunction.apply(pred, target, weight, _mode_code(mode), float(eps), 1.0, True) * float('nan')
+            return _Sph2PobLossFunction.apply(pred, target, weight, fam, tail, 1.0, True) * float('nan')
         scale = float(loss_weight) / n
     elif isinstance(avg_factor, torch.Tensor):   # a device scalar (e.g. an all-reduced positive count): no host sync
-        total = _Sph2PobLossFunction.apply(pred, target, weight, _mode_code(mode), float(eps), float(loss_weight), True)
+        total = _Sph2PobLossFunction.apply(pred, target, weight, fam, tail, float(loss_weight), True)
         return total / (avg_factor + _F32_EPS)
     else:
         scale = float(loss_weight) / (float(avg_factor) + _F32_EPS)
-    return _Sph2PobLossFunction.apply(pred, target, weight, _mode_code(mode), float(eps), scale, True)
+    return _Sph2PobLossFunction.apply(pred, target, weight, fam, tail, scale, True)
+
+
+def sph2pob_iou_loss(pred, target, weight=None, mode='iou', eps=1e-6, reduction='mean', avg_factor=None,
+                     loss_weight=1.0):
+    """Functional form: loss_weight * weight_reduce_loss(obb_iou_loss(sph2pob(pred, target)), weight, ...)."""
+    assert mode in LOSS_MODES
+    return weighted_loss_apply(pred, target, weight, IOU_FAMILY, (_mode_code(mode), float(eps)), reduction, avg_factor,
+                               loss_weight)
 
 
 class OBBIoULoss(nn.Module):

@@ -325,11 +325,68 @@ def variants(n=1_000_000):
     return out
 
 
+def gaussian(n=1_000_000):
+    """Sph2PobGDLoss (kld) and Sph2PobKFLoss forward+backward on config3's 1 M RBFoV pairs, through autograd and through the C
+    ABI (fwd_grad + final sum + grad_scale, as the autograd Function launches), timed beside the CIoU step."""
+    import ctypes
+    from sph_retina_amd import _lib, _torch_glue as G
+    from sph_retina_amd.losses import Sph2PobGDLoss, Sph2PobKFLoss
+    tgt = boxes(n, 0, 5, alpha=(5, 90), gamma=(-60, 60))
+    g = torch.Generator().manual_seed(1)
+    pred = tgt + (torch.randn((n, 5), generator=g) * torch.tensor([8., 8., 6., 6., 10.])).cuda()
+    pred[:, 0] %= 360
+    pred[:, 1].clamp_(1, 179)
+    pred[:, 2:4].clamp_(1, 170)
+    pred.requires_grad_(True)
+    lib = _lib.lib()
+    p_, t_ = pred.detach().contiguous(), tgt.contiguous()
+    out, one = torch.empty((), device='cuda'), torch.ones((), device='cuda')
+    ws2 = torch.empty(lib.sph2pob_loss_sum_workspace_floats(n), device='cuda')
+    stash = torch.empty_like(p_)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    nn, null = ctypes.c_int64(n), ctypes.c_void_p(0)
+    res = {'config': 'configs[2] pairs (1,000,000 RBFoV), Sph2PobGDLoss / Sph2PobKFLoss forward+backward', 'pairs': n}
+    ciou = Sph2PobIoULoss(mode='ciou', reduction='mean')
+
+    def ciou_abi():
+        lib.sph2pob_loss_fwd_grad_f32(G.ptr(p_), G.ptr(t_), null, 0, ctypes.c_float(1.0 / n), null, ctypes.c_void_p(out.data_ptr()),
+                                      G.ptr(ws2), G.ptr(stash), null, nn, 5, 3, ctypes.c_float(1e-6), st)
+        lib.sph2pob_loss_grad_scale_f32(G.ptr(stash), ctypes.c_void_p(one.data_ptr()), 0, G.ptr(stash), nn, 5, st)
+
+    def ciou_step():
+        pred.grad = None
+        ciou(pred, tgt).backward()
+    res['ciou_c_abi_fwd_bwd_ms'] = timeit(ciou_abi) * 1e3
+    res['ciou_autograd_fwd_bwd_ms'] = timeit(ciou_step) * 1e3
+    # (name, module, C-ABI trailing arguments: type, fun, tau, alpha, opts, beta, eps)
+    for name, mod, tail in (('kld', Sph2PobGDLoss(loss_type='kld'), (1, 1, 0.0, 1.0, 1, 1 / 9, 1e-6)),
+                            ('gwd', Sph2PobGDLoss(loss_type='gwd'), (0, 1, 0.0, 1.0, 2, 1 / 9, 1e-6)),
+                            ('kf', Sph2PobKFLoss(), (5, 0, 0.0, 1.0, 0, 1 / 9, 1e-6))):
+        ct = (ctypes.c_int(tail[0]), ctypes.c_int(tail[1]), ctypes.c_float(tail[2]), ctypes.c_float(tail[3]), ctypes.c_int(tail[4]),
+              ctypes.c_float(tail[5]), ctypes.c_float(tail[6]))
+
+        def abi():
+            lib.sph2pob_gauss_loss_fwd_grad_f32(G.ptr(p_), G.ptr(t_), null, 0, ctypes.c_float(1.0 / n), null,
+                                                ctypes.c_void_p(out.data_ptr()), G.ptr(ws2), G.ptr(stash), null, nn, 5, *ct, st)
+            lib.sph2pob_loss_grad_scale_f32(G.ptr(stash), ctypes.c_void_p(one.data_ptr()), 0, G.ptr(stash), nn, 5, st)
+
+        def step():
+            pred.grad = None
+            mod(pred, tgt).backward()
+        ta = timeit(abi)
+        res[f'{name}_c_abi_fwd_bwd_ms'] = ta * 1e3
+        res[f'{name}_autograd_fwd_bwd_ms'] = timeit(step) * 1e3
+        res[f'{name}_roofline'] = pmc_roofline('gauss_fwd_grad_kernel', ta, 60.0 * n)
+    res['note'] = ('c_abi = gauss_loss_fwd_grad (forward + gradients + partial sums in one pass) + final sum + grad_scale (in '
+                   'place, g = 1); roofline at 60 B/pair (pred, target, grad_pred)')
+    return res
+
+
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 config4 config4b coder unbiased variants; none = all)
-    table = dict(config3=config3, config4=config4, config4b=lambda: config4(1024, 2048), coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)
