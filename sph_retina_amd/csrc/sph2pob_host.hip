@@ -98,7 +98,6 @@ int check_common(int box_dim, int variant_flags, int edge, int angle) {
     if (variant >= SPH2POB_VARIANT_LEGACY && variant <= SPH2POB_VARIANT_FOV_IOU && box_dim == 5) return SPH2POB_ERR_DIM;
     return SPH2POB_OK;
 }
-constexpr int64_t kMaxElems = (int64_t)1 << 38;
 
 struct Aligned {
     const float *b1, *b2; float* out; int64_t n; int mode, edge, angle; bool fast = true;
@@ -153,27 +152,8 @@ struct Transform {
     }
 };
 
-// ---- loss ----
-template <int DIM>
-inline float element_weight(const float* w, int wd, int64_t i) {   // sph2pob_loss.hip: element_weight
-    if (!w) return 1.0f;
-    if (wd == 1) return w[i];
-    float s = 0.0f;
-    for (int k = 0; k < DIM; k++) s += w[i * DIM + k];
-    if (DIM == 4) return (s + s / 4.0f) / 5.0f;
-    return s / (float)DIM;
-}
-int loss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int loss_mode_flags) {
-    const int loss_mode = loss_mode_flags & 0xff;
-    if (loss_mode_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (loss_mode < 0 || loss_mode > 3) return SPH2POB_ERR_OPTION;
-    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    return SPH2POB_OK;
-}
+// ---- loss: the checks, element_weight and the per-pair bodies are sph2pob_loss.hpp's, as the kernels' ----
 // one pass over the pairs: loss element (times w), IoU, gradients (times g) as asked for; returns the sum of the elements
-// (Body: the per-pair body of the kernels, IouBody | GaussBody of sph2pob_loss.hpp)
 template <int DIM, bool FAST, class Body>
 double loss_pass(const Body& body, const float* pred, const float* target, const float* weight, int wd, float scale,
                  const float* grad_out, int grad_stride, float* loss, float* iou, float* gpred, float* gtarget, int64_t n) {
@@ -206,30 +186,56 @@ double loss_pass(const Body& body, const float* pred, const float* target, const
     for (double v : partial) s += v;   // fixed order: reproducible for a given thread count
     return s;
 }
+
+// (box_dim, flags) select loss_pass<DIM, FAST> as they select the kernel
 template <class Body, class... A>
-double loss_pass_body(int box_dim, bool fast, const Body& body, A... a) {
+double loss_pass_sel(const Body& body, int box_dim, int flags, A... a) {
+    const bool fast = !(flags & SPH2POB_FLAG_REFERENCE_ORDER);
     if (box_dim == 4) return fast ? loss_pass<4, true>(body, a...) : loss_pass<4, false>(body, a...);
     return fast ? loss_pass<5, true>(body, a...) : loss_pass<5, false>(body, a...);
 }
-// the IoU family: (..., n, mode, eps) as the entry points pass them
-double loss_pass_sel(int box_dim, bool fast, const float* pred, const float* target, const float* weight, int wd, float scale,
-                     const float* grad_out, int grad_stride, float* loss, float* iou, float* gpred, float* gtarget, int64_t n,
-                     int mode, float eps) {
-    return loss_pass_body(box_dim, fast, IouBody{mode, eps}, pred, target, weight, wd, scale, grad_out, grad_stride, loss, iou,
-                          gpred, gtarget, n);
+
+// the four forms of both families after the entry point's argument check (sph2pob_loss.hip: launch_fwd ...), each with
+// its form's null-pointer and n == 0 rules
+template <class Body>
+int cpu_fwd(const float* pred, const float* target, const float* weight, int wd, float scale, float* loss, float* iou,
+            int64_t n, int box_dim, int flags, const Body& body) {
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
+    loss_pass_sel(body, box_dim, flags, pred, target, weight, wd, scale, nullptr, 0, loss, iou, nullptr, nullptr, n);
+    return SPH2POB_OK;
 }
-// the Gaussian family: the launchers' argument checks (sph2pob_loss.hip: gauss_check)
-int gauss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int type_flags, int fun, int opts) {
-    const int type = type_flags & 0xff;
-    if (type_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (type < SPH2POB_GAUSS_GWD || type > SPH2POB_GAUSS_KF) return SPH2POB_ERR_OPTION;
-    const bool fun_ok = type == SPH2POB_GAUSS_KF
-                            ? (fun == SPH2POB_GAUSS_FUN_NONE || fun == SPH2POB_GAUSS_FUN_LN || fun == SPH2POB_GAUSS_FUN_EXP)
-                            : (fun >= SPH2POB_GAUSS_FUN_NONE && fun <= SPH2POB_GAUSS_FUN_SQRT);
-    if (!fun_ok || (opts & ~(SPH2POB_GAUSS_OPT_SQRT | SPH2POB_GAUSS_OPT_NORMALIZE))) return SPH2POB_ERR_OPTION;
-    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+
+template <class Body>
+int cpu_bwd(const float* pred, const float* target, const float* weight, int wd, const float* grad_out, int grad_stride,
+            float scale, float* grad_pred, float* grad_target, int64_t n, int box_dim, int flags, const Body& body) {
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
+    loss_pass_sel(body, box_dim, flags, pred, target, weight, wd, scale, grad_out, grad_stride, nullptr, nullptr, grad_pred,
+                  grad_target, n);
+    return SPH2POB_OK;
+}
+
+// (no workspace on the host; the elements are summed unscaled and the scale applied once, as the HIP form does)
+template <class Body>
+int cpu_fwd_sum(const float* pred, const float* target, const float* weight, int wd, float scale, float* out, int64_t n,
+                int box_dim, int flags, const Body& body) {
+    if (!out || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
+    const double s = n ? loss_pass_sel(body, box_dim, flags, pred, target, weight, wd, 1.0f, nullptr, 0, nullptr, nullptr,
+                                       nullptr, nullptr, n)
+                       : 0.0;
+    out[0] = (float)(s * (double)scale);
+    return SPH2POB_OK;
+}
+
+template <class Body>
+int cpu_fwd_grad(const float* pred, const float* target, const float* weight, int wd, float scale, float* loss, float* out_sum,
+                 float* grad_pred, float* grad_target, int64_t n, int box_dim, int flags, const Body& body) {
+    if (n > 0 && (!pred || !target || !grad_pred)) return SPH2POB_ERR_NULL;
+    const double s = n ? loss_pass_sel(body, box_dim, flags, pred, target, weight, wd, scale, nullptr, 0, loss, nullptr,
+                                       grad_pred, grad_target, n)
+                       : 0.0;
+    if (out_sum) out_sum[0] = (float)s;
     return SPH2POB_OK;
 }
 
@@ -327,67 +333,38 @@ int sph2pob_planar_iou_f32_cpu(const float* p1, int64_t m, const float* p2, int6
 
 int sph2pob_loss_fwd_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale, float* loss,
                              float* iou, int64_t n, int box_dim, int loss_mode_flags, float eps, void*) {
-    int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags);
-    if (rc) return rc;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
-    loss_pass_sel(box_dim, !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER), pred, target, weight, weight_dim, scale, (const float*)nullptr, 0,
-                  loss, iou, (float*)nullptr, (float*)nullptr, n, loss_mode_flags & 0xff, eps);
-    return SPH2POB_OK;
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags)) return rc;
+    return cpu_fwd(pred, target, weight, weight_dim, scale, loss, iou, n, box_dim, loss_mode_flags, IouBody{loss_mode_flags & 0xff, eps});
 }
 
 int sph2pob_loss_bwd_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, const float* grad_out,
                              int grad_stride, float scale, float* grad_pred, float* grad_target, int64_t n, int box_dim,
                              int loss_mode_flags, float eps, void*) {
-    int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags);
-    if (rc) return rc;
-    if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
-    loss_pass_sel(box_dim, !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER), pred, target, weight, weight_dim, scale, grad_out, grad_stride,
-                  (float*)nullptr, (float*)nullptr, grad_pred, grad_target, n, loss_mode_flags & 0xff, eps);
-    return SPH2POB_OK;
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags, grad_stride)) return rc;
+    return cpu_bwd(pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, box_dim, loss_mode_flags,
+                   IouBody{loss_mode_flags & 0xff, eps});
 }
 
 int sph2pob_loss_fwd_sum_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale, float* out,
-                                 float* workspace, int64_t n, int box_dim, int loss_mode_flags, float eps, void*) {
-    (void)workspace;
-    int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags);
-    if (rc) return rc;
-    if (!out || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
-    // (the elements are summed unscaled and the scale applied once, as the HIP form does)
-    const double s = n ? loss_pass_sel(box_dim, !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER), pred, target, weight, weight_dim, 1.0f,
-                                       (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, n,
-                                       loss_mode_flags & 0xff, eps)
-                       : 0.0;
-    out[0] = (float)(s * (double)scale);
-    return SPH2POB_OK;
+                                 float*, int64_t n, int box_dim, int loss_mode_flags, float eps, void*) {
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags)) return rc;
+    return cpu_fwd_sum(pred, target, weight, weight_dim, scale, out, n, box_dim, loss_mode_flags, IouBody{loss_mode_flags & 0xff, eps});
 }
 
 int sph2pob_loss_fwd_grad_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale, float* loss,
-                                  float* out_sum, float* workspace, float* grad_pred, float* grad_target, int64_t n, int box_dim,
+                                  float* out_sum, float*, float* grad_pred, float* grad_target, int64_t n, int box_dim,
                                   int loss_mode_flags, float eps, void*) {
-    (void)workspace;
-    int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags);
-    if (rc) return rc;
-    if (n > 0 && (!pred || !target || !grad_pred)) return SPH2POB_ERR_NULL;
-    const double s = n ? loss_pass_sel(box_dim, !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER), pred, target, weight, weight_dim, scale,
-                                       (const float*)nullptr, 0, loss, (float*)nullptr, grad_pred, grad_target, n, loss_mode_flags & 0xff, eps)
-                       : 0.0;
-    if (out_sum) out_sum[0] = (float)s;
-    return SPH2POB_OK;
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags)) return rc;
+    return cpu_fwd_grad(pred, target, weight, weight_dim, scale, loss, out_sum, grad_pred, grad_target, n, box_dim, loss_mode_flags,
+                        IouBody{loss_mode_flags & 0xff, eps});
 }
 
 int sph2pob_gauss_loss_fwd_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                                    float* loss, int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha, int opts,
                                    float beta, float eps, void*) {
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
-    loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER), GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps},
-                   pred, target, weight, weight_dim, scale, (const float*)nullptr, 0, loss, (float*)nullptr, (float*)nullptr,
-                   (float*)nullptr, n);
-    return SPH2POB_OK;
+    return cpu_fwd(pred, target, weight, weight_dim, scale, loss, nullptr, n, box_dim, type_flags,
+                   GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
 
 int sph2pob_gauss_loss_bwd_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, const float* grad_out,
@@ -395,47 +372,29 @@ int sph2pob_gauss_loss_bwd_f32_cpu(const float* pred, const float* target, const
                                    int type_flags, int fun, float tau, float alpha, int opts, float beta, float eps, void*) {
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
     if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
-    loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER), GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps},
-                   pred, target, weight, weight_dim, scale, grad_out, grad_stride, (float*)nullptr, (float*)nullptr, grad_pred,
-                   grad_target, n);
-    return SPH2POB_OK;
+    return cpu_bwd(pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, box_dim, type_flags,
+                   GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
 
 int sph2pob_gauss_loss_fwd_sum_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
-                                       float* out, float* workspace, int64_t n, int box_dim, int type_flags, int fun, float tau,
+                                       float* out, float*, int64_t n, int box_dim, int type_flags, int fun, float tau,
                                        float alpha, int opts, float beta, float eps, void*) {
-    (void)workspace;
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
-    if (!out || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
-    const double s = n ? loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER),
-                                        GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps}, pred, target, weight,
-                                        weight_dim, 1.0f, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr,
-                                        (float*)nullptr, (float*)nullptr, n)
-                       : 0.0;
-    out[0] = (float)(s * (double)scale);
-    return SPH2POB_OK;
+    return cpu_fwd_sum(pred, target, weight, weight_dim, scale, out, n, box_dim, type_flags,
+                       GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
 
 int sph2pob_gauss_loss_fwd_grad_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
-                                        float* loss, float* out_sum, float* workspace, float* grad_pred, float* grad_target,
+                                        float* loss, float* out_sum, float*, float* grad_pred, float* grad_target,
                                         int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha, int opts,
                                         float beta, float eps, void*) {
-    (void)workspace;
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
-    if (n > 0 && (!pred || !target || !grad_pred)) return SPH2POB_ERR_NULL;
-    const double s = n ? loss_pass_body(box_dim, !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER),
-                                        GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps}, pred, target, weight,
-                                        weight_dim, scale, (const float*)nullptr, 0, loss, (float*)nullptr, grad_pred,
-                                        grad_target, n)
-                       : 0.0;
-    if (out_sum) out_sum[0] = (float)s;
-    return SPH2POB_OK;
+    return cpu_fwd_grad(pred, target, weight, weight_dim, scale, loss, out_sum, grad_pred, grad_target, n, box_dim, type_flags,
+                        GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
 
 int sph2pob_loss_grad_scale_f32_cpu(const float* stash, const float* grad_out, int grad_stride, float* out, int64_t n, int box_dim, void*) {
-    if (n < 0 || (box_dim != 4 && box_dim != 5) || (grad_stride != 0 && grad_stride != 1)) return SPH2POB_ERR_OPTION;
+    if (int rc = grad_scale_check(n, box_dim, grad_stride)) return rc;
     if (n == 0) return SPH2POB_OK;
     if (!stash || !grad_out || !out) return SPH2POB_ERR_NULL;
     if (grad_stride == 0 && out == stash && grad_out[0] == 1.0f) return SPH2POB_OK;

@@ -1,5 +1,6 @@
 // Shared by the translation units of libsph2pob_hip.so (sph2pob_{iou,assign,loss,nms}.hip): constants, launch knobs, box loads,
-// the (VARIANT, DIM) dispatch and the argument checks every entry point starts with.  Internal: include/sph2pob_hip.h is the ABI.
+// the (VARIANT, DIM) dispatch and the argument checks every entry point starts with (the kMaxElems bound is sph2pob_loss.hpp's,
+// shared with the host twins).  Internal: include/sph2pob_hip.h is the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,7 +109,5 @@ int dispatch(int variant_flags, int box_dim, F&& f) {
     if (variant == SPH2POB_VARIANT_NAIVE) return box_dim == 4 ? f.template run<6, 4>() : f.template run<6, 5>();
     return f.template run<2, 4>();
 }
-
-constexpr int64_t kMaxElems = (int64_t)1 << 38;  // grid.x = n / 256 must stay below 2^31
 
 }  // namespace

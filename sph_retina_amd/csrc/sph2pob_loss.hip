@@ -1,25 +1,19 @@
 // libsph2pob_hip.so — IoU / GIoU / DIoU / CIoU and Gaussian (GWD / KLD / JD / KFIoU) loss forward + backward and the deterministic sum: kernels + C-ABI launchers
 // (include/sph2pob_hip.h).  gfx950 only.
 
+#include <type_traits>
+
 #include "sph2pob_kernels_common.hpp"
 
 namespace {
 
-
-// ---- loss: per-element weight = mean over weight_dim columns (reference: sph2pob_transform.py:32-34 widens a
-// (n,4) weight with its own mean, OBBIoULoss.forward then takes weight.mean(-1): sph2pob_iou_loss.py:48) ----
-template <int DIM>
-__device__ __forceinline__ float element_weight(const float* __restrict__ w, int wd, int64_t i) {
-    if (!w) return 1.0f;
-    if (wd == 1) return w[i];
-    float v[DIM], s = 0.0f;   // wd == DIM here (the launchers reject anything else): DIM loads in flight, not a loop of load + wait
-#pragma unroll
-    for (int k = 0; k < DIM; k++) v[k] = w[i * DIM + k];
-#pragma unroll
-    for (int k = 0; k < DIM; k++) s += v[k];
-    if (DIM == 4) return (s + s / 4.0f) / 5.0f;
-    return s / (float)DIM;
-}
+// The four loss kernels serve both families.  Body is the per-pair body of sph2pob_loss.hpp; the kernel's trailing
+// parameters `a...` build it: IouBody from the flat (loss_mode, eps), GaussBody from itself, passed by value.  Each call
+// site calls pair_loss / pair_gauss_loss directly behind `if constexpr`.  A wrapper level in between (the body's eval()
+// member, or a static apply()) keeps the instruction count but moves the register assignment and schedule of 18 of the
+// 24 IoU kernels; in this form their ISA is the one they had as templates of their own.
+template <class Body>
+constexpr bool kGauss = std::is_same<Body, GaussBody>::value;
 
 // waves per SIMD the loss kernels that carry the adjoint are compiled for (closed-form front end): 4 = ~105 VGPRs, no
 // scratch; 5 = 96 VGPRs with 2-5 spilled dwords; 6 = 80 VGPRs with ~20.  Measured on MI355X, 1 M RBFoV pairs, CIoU
@@ -28,76 +22,11 @@ __device__ __forceinline__ float element_weight(const float* __restrict__ w, int
 #define SPH_LOSS_WAVES 4
 #endif
 constexpr int kLossWaves = SPH_LOSS_WAVES;
-template <int DIM, bool FAST>
-__global__ __launch_bounds__(kBlock) void loss_fwd_kernel(const float* __restrict__ pred,
-                                                         const float* __restrict__ target,
-                                                         const float* __restrict__ weight, int wd,
-                                                         float scale, float* __restrict__ loss,
-                                                         float* __restrict__ iou, int64_t n, int loss_mode,
-                                                         float eps) {
-    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float x[5], y[5], gx[5], gy[5], io;
-    const float w = scale * element_weight<DIM>(weight, wd, i);
-    // dense heads pass every anchor with weight 0 on the negatives (sph_retina_head.py:261-264): a wave whose 64
-    // weights are all zero writes its zeros and leaves (loss * 0 == 0 for every finite loss)
-    if (!iou && __builtin_amdgcn_ballot_w64(w != 0.0f) == 0) {
-        loss[i] = 0.0f;
-        return;
-    }
-    load_box<DIM>(pred, i, x);
-    load_box<DIM>(target, i, y);
-    float l = pair_loss<DIM, false, FAST>(x, y, loss_mode, eps, &io, gx, gy);
-    loss[i] = l * w;
-    if (iou) iou[i] = io;
-}
 
-__device__ __forceinline__ float block_sum(float v);
-// forward + per-workgroup partial sum (reduction 'mean' / 'sum'): no element buffer
-template <int DIM, bool FAST>
-__global__ __launch_bounds__(kBlock) void loss_fwd_sum_kernel(const float* __restrict__ pred,
-                                                             const float* __restrict__ target,
-                                                             const float* __restrict__ weight, int wd,
-                                                             float* __restrict__ partial, int64_t n, int loss_mode,
-                                                             float eps) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    float v = 0.0f;
-    const bool live = i < n;
-    const float w = live ? element_weight<DIM>(weight, wd, i) : 0.0f;
-    if (__builtin_amdgcn_ballot_w64(w != 0.0f) != 0) {   // an all-zero-weight wave contributes exact zeros (see loss_fwd_kernel)
-        if (live) {
-            float x[5], y[5], gx[5], gy[5];
-            load_box<DIM>(pred, i, x);
-            load_box<DIM>(target, i, y);
-            v = pair_loss<DIM, false, FAST>(x, y, loss_mode, eps, nullptr, gx, gy) * w;
-        }
-    }
-    const float r = block_sum(v);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-
-// GT: the caller wants the target's gradient too.  A training step does not (the target carries no gradient): with GT =
-// false the target half of the chain rule back to the spherical inputs is dead code and the compiler drops it.
-template <int DIM, bool FAST, bool GT>
-__global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void loss_bwd_kernel(const float* __restrict__ pred,
-                                                         const float* __restrict__ target,
-                                                         const float* __restrict__ weight, int wd,
-                                                         const float* __restrict__ grad_out, int grad_stride,
-                                                         float scale, float* __restrict__ gpred,
-                                                         float* __restrict__ gtarget, int64_t n, int loss_mode,
-                                                         float eps) {
-    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float x[5], y[5], gx[5], gy[5];
-    float g = grad_out[i * grad_stride] * scale * element_weight<DIM>(weight, wd, i);
-    if (__builtin_amdgcn_ballot_w64(g != 0.0f) == 0) {  // all-negative wave (see loss_fwd_kernel): zero gradients, no geometry
-#pragma unroll
-        for (int k = 0; k < 5; k++) gx[k] = gy[k] = 0.0f;
-    } else {
-        load_box<DIM>(pred, i, x);
-        load_box<DIM>(target, i, y);
-        pair_loss<DIM, true, FAST>(x, y, loss_mode, eps, nullptr, gx, gy);
-    }
+// the gradient rows of a pair, times g (GT: also the target's)
+template <int DIM, bool GT>
+__device__ __forceinline__ void store_grads(float* __restrict__ gpred, float* __restrict__ gtarget, int64_t i, float g,
+                                            const float (&gx)[5], const float (&gy)[5]) {
     if (DIM == 4) {
         reinterpret_cast<float4*>(gpred)[i] = make_float4(g * gx[0], g * gx[1], g * gx[2], g * gx[3]);
         if (GT) reinterpret_cast<float4*>(gtarget)[i] = make_float4(g * gy[0], g * gy[1], g * gy[2], g * gy[3]);
@@ -111,14 +40,95 @@ __global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void loss_bwd_kernel
     }
 }
 
+// iou: the IoU family's optional IoU output (the Gaussian launchers pass null)
+template <int DIM, bool FAST, class Body, class... A>
+__global__ __launch_bounds__(kBlock) void loss_fwd_kernel(const float* __restrict__ pred,
+                                                         const float* __restrict__ target,
+                                                         const float* __restrict__ weight, int wd,
+                                                         float scale, float* __restrict__ loss,
+                                                         float* __restrict__ iou, int64_t n, A... a) {
+    const Body body{a...};
+    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float x[5], y[5], gx[5], gy[5], io;
+    const float w = scale * element_weight<DIM>(weight, wd, i);
+    // dense heads pass every anchor with weight 0 on the negatives (sph_retina_head.py:261-264): a wave whose 64
+    // weights are all zero writes its zeros and leaves (loss * 0 == 0 for every finite loss)
+    if ((kGauss<Body> || !iou) && __builtin_amdgcn_ballot_w64(w != 0.0f) == 0) {
+        loss[i] = 0.0f;
+        return;
+    }
+    load_box<DIM>(pred, i, x);
+    load_box<DIM>(target, i, y);
+    if constexpr (kGauss<Body>) {
+        loss[i] = pair_gauss_loss<DIM, false, FAST>(x, y, body, gx, gy) * w;
+    } else {
+        float l = pair_loss<DIM, false, FAST>(x, y, body.loss_mode, body.eps, &io, gx, gy);
+        loss[i] = l * w;
+        if (iou) iou[i] = io;
+    }
+}
+
+__device__ __forceinline__ float block_sum(float v);
+// forward + per-workgroup partial sum (reduction 'mean' / 'sum'): no element buffer
+template <int DIM, bool FAST, class Body, class... A>
+__global__ __launch_bounds__(kBlock) void loss_fwd_sum_kernel(const float* __restrict__ pred,
+                                                             const float* __restrict__ target,
+                                                             const float* __restrict__ weight, int wd,
+                                                             float* __restrict__ partial, int64_t n, A... a) {
+    const Body body{a...};
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    float v = 0.0f;
+    const bool live = i < n;
+    const float w = live ? element_weight<DIM>(weight, wd, i) : 0.0f;
+    if (__builtin_amdgcn_ballot_w64(w != 0.0f) != 0) {   // an all-zero-weight wave contributes exact zeros (see loss_fwd_kernel)
+        if (live) {
+            float x[5], y[5], gx[5], gy[5];
+            load_box<DIM>(pred, i, x);
+            load_box<DIM>(target, i, y);
+            if constexpr (kGauss<Body>) v = pair_gauss_loss<DIM, false, FAST>(x, y, body, gx, gy) * w;
+            else v = pair_loss<DIM, false, FAST>(x, y, body.loss_mode, body.eps, nullptr, gx, gy) * w;
+        }
+    }
+    const float r = block_sum(v);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// GT: the caller wants the target's gradient too.  A training step does not (the target carries no gradient): with GT =
+// false the target half of the chain rule back to the spherical inputs is dead code and the compiler drops it.
+template <int DIM, bool FAST, bool GT, class Body, class... A>
+__global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void loss_bwd_kernel(const float* __restrict__ pred,
+                                                         const float* __restrict__ target,
+                                                         const float* __restrict__ weight, int wd,
+                                                         const float* __restrict__ grad_out, int grad_stride,
+                                                         float scale, float* __restrict__ gpred,
+                                                         float* __restrict__ gtarget, int64_t n, A... a) {
+    const Body body{a...};
+    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float x[5], y[5], gx[5], gy[5];
+    float g = grad_out[i * grad_stride] * scale * element_weight<DIM>(weight, wd, i);
+    if (__builtin_amdgcn_ballot_w64(g != 0.0f) == 0) {  // all-negative wave (see loss_fwd_kernel): zero gradients, no geometry
+#pragma unroll
+        for (int k = 0; k < 5; k++) gx[k] = gy[k] = 0.0f;
+    } else {
+        load_box<DIM>(pred, i, x);
+        load_box<DIM>(target, i, y);
+        if constexpr (kGauss<Body>) pair_gauss_loss<DIM, true, FAST>(x, y, body, gx, gy);
+        else pair_loss<DIM, true, FAST>(x, y, body.loss_mode, body.eps, nullptr, gx, gy);
+    }
+    store_grads<DIM, GT>(gpred, gtarget, i, g, gx, gy);
+}
+
 // forward + gradients for an upstream gradient of 1 (+ per-workgroup partial sum of the loss when `partial`)
-template <int DIM, bool FAST, bool GT>
+template <int DIM, bool FAST, bool GT, class Body, class... A>
 __global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void loss_fwd_grad_kernel(const float* __restrict__ pred,
                                                               const float* __restrict__ target,
                                                               const float* __restrict__ weight, int wd, float scale,
                                                               float* __restrict__ loss, float* __restrict__ partial,
                                                               float* __restrict__ gpred, float* __restrict__ gtarget,
-                                                              int64_t n, int loss_mode, float eps) {
+                                                              int64_t n, A... a) {
+    const Body body{a...};
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool live = i < n;
     const float w = live ? scale * element_weight<DIM>(weight, wd, i) : 0.0f;
@@ -129,22 +139,13 @@ __global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void loss_fwd_grad_k
         if (live) {
             load_box<DIM>(pred, i, x);
             load_box<DIM>(target, i, y);
-            l = pair_loss<DIM, true, FAST>(x, y, loss_mode, eps, nullptr, gx, gy) * w;
+            if constexpr (kGauss<Body>) l = pair_gauss_loss<DIM, true, FAST>(x, y, body, gx, gy) * w;
+            else l = pair_loss<DIM, true, FAST>(x, y, body.loss_mode, body.eps, nullptr, gx, gy) * w;
         }
     }
     if (live) {
         if (loss) loss[i] = l;
-        if (DIM == 4) {
-            reinterpret_cast<float4*>(gpred)[i] = make_float4(w * gx[0], w * gx[1], w * gx[2], w * gx[3]);
-            if (GT) reinterpret_cast<float4*>(gtarget)[i] = make_float4(w * gy[0], w * gy[1], w * gy[2], w * gy[3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 5; k++) gpred[i * 5 + k] = w * gx[k];
-            if (GT) {
-#pragma unroll
-                for (int k = 0; k < 5; k++) gtarget[i * 5 + k] = w * gy[k];
-            }
-        }
+        store_grads<DIM, GT>(gpred, gtarget, i, w, gx, gy);
     }
     if (partial) {   // workgroup-uniform
         const float r = block_sum(live ? l : 0.0f);
@@ -206,115 +207,6 @@ __global__ __launch_bounds__(kBlock) void sum_pass2(const float* __restrict__ ws
 
 
 
-// ---- Sph2PobGDLoss / Sph2PobKFLoss kernels: the IoU family's four kernels above with the per-pair body GaussBody
-// (sph2pob_loss.hpp), passed by value.  The IoU kernels keep their own templates: routing them through a generic body
-// changes their instruction schedule (same instruction count, different register assignment), and their ISA is pinned.
-template <int DIM, bool FAST>
-__global__ __launch_bounds__(kBlock) void gauss_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                          const float* __restrict__ weight, int wd, float scale,
-                                                          float* __restrict__ loss, int64_t n, const GaussBody body) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float x[5], y[5], gx[5], gy[5];
-    const float w = scale * element_weight<DIM>(weight, wd, i);
-    if (__builtin_amdgcn_ballot_w64(w != 0.0f) == 0) {   // all-zero-weight wave (see loss_fwd_kernel)
-        loss[i] = 0.0f;
-        return;
-    }
-    load_box<DIM>(pred, i, x);
-    load_box<DIM>(target, i, y);
-    loss[i] = pair_gauss_loss<DIM, false, FAST>(x, y, body, gx, gy) * w;
-}
-
-template <int DIM, bool FAST>
-__global__ __launch_bounds__(kBlock) void gauss_fwd_sum_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                              const float* __restrict__ weight, int wd,
-                                                              float* __restrict__ partial, int64_t n, const GaussBody body) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    float v = 0.0f;
-    const bool live = i < n;
-    const float w = live ? element_weight<DIM>(weight, wd, i) : 0.0f;
-    if (__builtin_amdgcn_ballot_w64(w != 0.0f) != 0) {
-        if (live) {
-            float x[5], y[5], gx[5], gy[5];
-            load_box<DIM>(pred, i, x);
-            load_box<DIM>(target, i, y);
-            v = pair_gauss_loss<DIM, false, FAST>(x, y, body, gx, gy) * w;
-        }
-    }
-    const float r = block_sum(v);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-
-// the gradient rows of a pair, times g (GT: also the target's)
-template <int DIM, bool GT>
-__device__ __forceinline__ void store_grads(float* __restrict__ gpred, float* __restrict__ gtarget, int64_t i, float g,
-                                            const float (&gx)[5], const float (&gy)[5]) {
-    if (DIM == 4) {
-        reinterpret_cast<float4*>(gpred)[i] = make_float4(g * gx[0], g * gx[1], g * gx[2], g * gx[3]);
-        if (GT) reinterpret_cast<float4*>(gtarget)[i] = make_float4(g * gy[0], g * gy[1], g * gy[2], g * gy[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 5; k++) gpred[i * 5 + k] = g * gx[k];
-        if (GT) {
-#pragma unroll
-            for (int k = 0; k < 5; k++) gtarget[i * 5 + k] = g * gy[k];
-        }
-    }
-}
-
-template <int DIM, bool FAST, bool GT>
-__global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void gauss_bwd_kernel(const float* __restrict__ pred,
-                                                          const float* __restrict__ target,
-                                                          const float* __restrict__ weight, int wd,
-                                                          const float* __restrict__ grad_out, int grad_stride,
-                                                          float scale, float* __restrict__ gpred,
-                                                          float* __restrict__ gtarget, int64_t n, const GaussBody body) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float x[5], y[5], gx[5], gy[5];
-    const float g = grad_out[i * grad_stride] * scale * element_weight<DIM>(weight, wd, i);
-    if (__builtin_amdgcn_ballot_w64(g != 0.0f) == 0) {
-#pragma unroll
-        for (int k = 0; k < 5; k++) gx[k] = gy[k] = 0.0f;
-    } else {
-        load_box<DIM>(pred, i, x);
-        load_box<DIM>(target, i, y);
-        pair_gauss_loss<DIM, true, FAST>(x, y, body, gx, gy);
-    }
-    store_grads<DIM, GT>(gpred, gtarget, i, g, gx, gy);
-}
-
-template <int DIM, bool FAST, bool GT>
-__global__ __launch_bounds__(kBlock, FAST ? kLossWaves : 4) void gauss_fwd_grad_kernel(const float* __restrict__ pred,
-                                                               const float* __restrict__ target,
-                                                               const float* __restrict__ weight, int wd, float scale,
-                                                               float* __restrict__ loss, float* __restrict__ partial,
-                                                               float* __restrict__ gpred, float* __restrict__ gtarget,
-                                                               int64_t n, const GaussBody body) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool live = i < n;
-    const float w = live ? scale * element_weight<DIM>(weight, wd, i) : 0.0f;
-    float x[5], y[5], gx[5], gy[5], l = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 5; k++) gx[k] = gy[k] = 0.0f;
-    if (__builtin_amdgcn_ballot_w64(w != 0.0f) != 0) {
-        if (live) {
-            load_box<DIM>(pred, i, x);
-            load_box<DIM>(target, i, y);
-            l = pair_gauss_loss<DIM, true, FAST>(x, y, body, gx, gy) * w;
-        }
-    }
-    if (live) {
-        if (loss) loss[i] = l;
-        store_grads<DIM, GT>(gpred, gtarget, i, w, gx, gy);
-    }
-    if (partial) {
-        const float r = block_sum(live ? l : 0.0f);
-        if (threadIdx.x == 0) partial[blockIdx.x] = r;
-    }
-}
-
 // out[0] = scale * the fixed-order sum of nb workgroup partials in `workspace` (as sph2pob_loss_fwd_sum_f32 adds them)
 void launch_partial_sum(float* workspace, int64_t nb, float scale, float* out, hipStream_t s) {
     if (nb <= 65536) {
@@ -326,27 +218,88 @@ void launch_partial_sum(float* workspace, int64_t nb, float scale, float* out, h
     }
 }
 
-static_assert(SPH2POB_GAUSS_GWD == GAUSS_GWD && SPH2POB_GAUSS_KLD == GAUSS_KLD && SPH2POB_GAUSS_JD == GAUSS_JD &&
-              SPH2POB_GAUSS_KLD_SYMMAX == GAUSS_KLD_SYMMAX && SPH2POB_GAUSS_KLD_SYMMIN == GAUSS_KLD_SYMMIN &&
-              SPH2POB_GAUSS_KF == GAUSS_KF, "loss type codes");
-static_assert(SPH2POB_GAUSS_FUN_NONE == GFUN_NONE && SPH2POB_GAUSS_FUN_LOG1P == GFUN_LOG1P && SPH2POB_GAUSS_FUN_SQRT == GFUN_SQRT &&
-              SPH2POB_GAUSS_FUN_LN == GFUN_LN && SPH2POB_GAUSS_FUN_EXP == GFUN_EXP, "post-map codes");
-static_assert(SPH2POB_GAUSS_OPT_SQRT == GOPT_SQRT && SPH2POB_GAUSS_OPT_NORMALIZE == GOPT_NORMALIZE, "option bits");
+template <int D> using Dim = std::integral_constant<int, D>;
+template <bool B> using Flag = std::integral_constant<bool, B>;
 
-// argument checks of the Gaussian launchers: SPH2POB_GAUSS_* type (| SPH2POB_FLAG_REFERENCE_ORDER), a post-map the type
-// accepts (GD: none | log1p | sqrt, KF: none | ln | exp), SPH2POB_GAUSS_OPT_* options
-int gauss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int type_flags, int fun, int opts) {
-    const int type = type_flags & 0xff;
-    if (type_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (type < SPH2POB_GAUSS_GWD || type > SPH2POB_GAUSS_KF) return SPH2POB_ERR_OPTION;
-    const bool fun_ok = type == SPH2POB_GAUSS_KF
-                            ? (fun == SPH2POB_GAUSS_FUN_NONE || fun == SPH2POB_GAUSS_FUN_LN || fun == SPH2POB_GAUSS_FUN_EXP)
-                            : (fun >= SPH2POB_GAUSS_FUN_NONE && fun <= SPH2POB_GAUSS_FUN_SQRT);
-    if (!fun_ok || (opts & ~(SPH2POB_GAUSS_OPT_SQRT | SPH2POB_GAUSS_OPT_NORMALIZE))) return SPH2POB_ERR_OPTION;
-    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    return SPH2POB_OK;
+// calls f(Dim<box_dim>, Flag<FAST>, Flag<gt>): FAST unless the flags ask for SPH2POB_FLAG_REFERENCE_ORDER
+template <class F>
+void select_kernel(int box_dim, int flags, bool gt, F&& f) {
+    auto by_gt = [&](auto d, auto fast) {
+        if (gt) f(d, fast, Flag<true>{});
+        else f(d, fast, Flag<false>{});
+    };
+    auto by_fast = [&](auto d) {
+        if (flags & SPH2POB_FLAG_REFERENCE_ORDER) by_gt(d, Flag<false>{});
+        else by_gt(d, Flag<true>{});
+    };
+    if (box_dim == 4) by_fast(Dim<4>{});
+    else by_fast(Dim<5>{});
+}
+
+// The four launch forms of both families, after the entry point's argument check: (Body, a...) as the kernels take them.
+// Each form keeps its own null-pointer and n == 0 rules.
+template <class Body, class... A>
+int launch_fwd(const float* pred, const float* target, const float* weight, int wd, float scale, float* loss, float* iou,
+               int64_t n, int box_dim, int flags, void* stream, A... a) {
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
+    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    hipStream_t s = (hipStream_t)stream;
+    select_kernel(box_dim, flags, false, [&](auto d, auto fast, auto) {
+        hipLaunchKernelGGL((loss_fwd_kernel<decltype(d)::value, decltype(fast)::value, Body, A...>), grid, dim3(kBlock), 0, s,
+                           pred, target, weight, wd, scale, loss, iou, n, a...);
+    });
+    return launch_status();
+}
+
+template <class Body, class... A>
+int launch_bwd(const float* pred, const float* target, const float* weight, int wd, const float* grad_out, int grad_stride,
+               float scale, float* grad_pred, float* grad_target, int64_t n, int box_dim, int flags, void* stream, A... a) {
+    if (n == 0) return SPH2POB_OK;
+    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
+    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    hipStream_t s = (hipStream_t)stream;
+    select_kernel(box_dim, flags, grad_target != nullptr, [&](auto d, auto fast, auto gt) {
+        hipLaunchKernelGGL((loss_bwd_kernel<decltype(d)::value, decltype(fast)::value, decltype(gt)::value, Body, A...>), grid,
+                           dim3(kBlock), 0, s, pred, target, weight, wd, grad_out, grad_stride, scale, grad_pred, grad_target, n,
+                           a...);
+    });
+    return launch_status();
+}
+
+template <class Body, class... A>
+int launch_fwd_sum(const float* pred, const float* target, const float* weight, int wd, float scale, float* out,
+                   float* workspace, int64_t n, int box_dim, int flags, void* stream, A... a) {
+    if (!out || !workspace || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = (n + kBlock - 1) / kBlock;
+    if (nb > 0) {
+        select_kernel(box_dim, flags, false, [&](auto d, auto fast, auto) {
+            hipLaunchKernelGGL((loss_fwd_sum_kernel<decltype(d)::value, decltype(fast)::value, Body, A...>), dim3((unsigned)nb),
+                               dim3(kBlock), 0, s, pred, target, weight, wd, workspace, n, a...);
+        });
+    }
+    launch_partial_sum(workspace, nb, scale, out, s);
+    return launch_status();
+}
+
+template <class Body, class... A>
+int launch_fwd_grad(const float* pred, const float* target, const float* weight, int wd, float scale, float* loss,
+                    float* out_sum, float* workspace, float* grad_pred, float* grad_target, int64_t n, int box_dim, int flags,
+                    void* stream, A... a) {
+    if ((out_sum && !workspace) || (n > 0 && (!pred || !target || !grad_pred))) return SPH2POB_ERR_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = (n + kBlock - 1) / kBlock;
+    float* partial = out_sum ? workspace : nullptr;
+    if (nb > 0) {
+        select_kernel(box_dim, flags, grad_target != nullptr, [&](auto d, auto fast, auto gt) {
+            hipLaunchKernelGGL((loss_fwd_grad_kernel<decltype(d)::value, decltype(fast)::value, decltype(gt)::value, Body, A...>),
+                               dim3((unsigned)nb), dim3(kBlock), 0, s, pred, target, weight, wd, scale, loss, partial, grad_pred,
+                               grad_target, n, a...);
+        });
+    }
+    if (out_sum) launch_partial_sum(workspace, nb, 1.0f, out_sum, s);   // scale is already inside the elements
+    return launch_status();
 }
 
 }  // namespace
@@ -356,46 +309,17 @@ extern "C" {
 
 int sph2pob_loss_fwd_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                          float* loss, float* iou, int64_t n, int box_dim, int loss_mode_flags, float eps, void* stream) {
-    const int loss_mode = loss_mode_flags & 0xff;
-    const bool fast = !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER);
-    if (loss_mode_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (loss_mode < 0 || loss_mode > 3) return SPH2POB_ERR_OPTION;
-    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
-    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    hipStream_t s = (hipStream_t)stream;
-#define SPH_LOSS_FWD(D, F) \
-    hipLaunchKernelGGL((loss_fwd_kernel<D, F>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, iou, n, loss_mode, eps)
-    if (box_dim == 4) { if (fast) SPH_LOSS_FWD(4, true); else SPH_LOSS_FWD(4, false); }
-    else { if (fast) SPH_LOSS_FWD(5, true); else SPH_LOSS_FWD(5, false); }
-#undef SPH_LOSS_FWD
-    return launch_status();
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags)) return rc;
+    return launch_fwd<IouBody>(pred, target, weight, weight_dim, scale, loss, iou, n, box_dim, loss_mode_flags, stream,
+                               loss_mode_flags & 0xff, eps);
 }
 
 int sph2pob_loss_bwd_f32(const float* pred, const float* target, const float* weight, int weight_dim,
                          const float* grad_out, int grad_stride, float scale, float* grad_pred, float* grad_target,
                          int64_t n, int box_dim, int loss_mode_flags, float eps, void* stream) {
-    const int loss_mode = loss_mode_flags & 0xff;
-    const bool fast = !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER);
-    if (loss_mode_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (loss_mode < 0 || loss_mode > 3 || (grad_stride != 0 && grad_stride != 1)) return SPH2POB_ERR_OPTION;
-    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
-    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    hipStream_t s = (hipStream_t)stream;
-#define SPH_LOSS_BWD(D, F) \
-    do { if (grad_target) hipLaunchKernelGGL((loss_bwd_kernel<D, F, true>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, loss_mode, eps); \
-         else hipLaunchKernelGGL((loss_bwd_kernel<D, F, false>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, loss_mode, eps); } while (0)
-    if (box_dim == 4) { if (fast) SPH_LOSS_BWD(4, true); else SPH_LOSS_BWD(4, false); }
-    else { if (fast) SPH_LOSS_BWD(5, true); else SPH_LOSS_BWD(5, false); }
-#undef SPH_LOSS_BWD
-    return launch_status();
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags, grad_stride)) return rc;
+    return launch_bwd<IouBody>(pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n,
+                               box_dim, loss_mode_flags, stream, loss_mode_flags & 0xff, eps);
 }
 
 int64_t sph2pob_loss_sum_workspace_floats(int64_t n) { return (n + kBlock - 1) / kBlock + kSumBlocks; }
@@ -403,91 +327,26 @@ int64_t sph2pob_loss_sum_workspace_floats(int64_t n) { return (n + kBlock - 1) /
 int sph2pob_loss_fwd_sum_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                              float* out, float* workspace, int64_t n, int box_dim, int loss_mode_flags, float eps,
                              void* stream) {
-    const int loss_mode = loss_mode_flags & 0xff;
-    const bool fast = !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER);
-    if (loss_mode_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (loss_mode < 0 || loss_mode > 3) return SPH2POB_ERR_OPTION;
-    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (!out || !workspace || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nb = (n + kBlock - 1) / kBlock;
-    if (nb > 0) {
-        dim3 grid((unsigned)nb);
-#define SPH_LOSS_FWDS(D, F) \
-        hipLaunchKernelGGL((loss_fwd_sum_kernel<D, F>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, workspace, n, loss_mode, eps)
-        if (box_dim == 4) { if (fast) SPH_LOSS_FWDS(4, true); else SPH_LOSS_FWDS(4, false); }
-        else { if (fast) SPH_LOSS_FWDS(5, true); else SPH_LOSS_FWDS(5, false); }
-#undef SPH_LOSS_FWDS
-    }
-    if (nb <= 65536) {   // one workgroup adds the partials in a fixed order
-        hipLaunchKernelGGL(sum_pass2, dim3(1), dim3(kBlock), 0, s, workspace, (int)nb, scale, out);
-    } else {             // very large batches: the two-pass tree over the partials
-        float* ws2 = workspace + nb;
-        hipLaunchKernelGGL(sum_pass1, dim3(kSumBlocks), dim3(kBlock), 0, s, workspace, nb, ws2);
-        hipLaunchKernelGGL(sum_pass2, dim3(1), dim3(kBlock), 0, s, ws2, kSumBlocks, scale, out);
-    }
-    return launch_status();
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags)) return rc;
+    return launch_fwd_sum<IouBody>(pred, target, weight, weight_dim, scale, out, workspace, n, box_dim, loss_mode_flags,
+                                   stream, loss_mode_flags & 0xff, eps);
 }
 
 int sph2pob_loss_fwd_grad_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                               float* loss, float* out_sum, float* workspace, float* grad_pred, float* grad_target,
                               int64_t n, int box_dim, int loss_mode_flags, float eps, void* stream) {
-    const int loss_mode = loss_mode_flags & 0xff;
-    const bool fast = !(loss_mode_flags & SPH2POB_FLAG_REFERENCE_ORDER);
-    if (loss_mode_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (loss_mode < 0 || loss_mode > 3) return SPH2POB_ERR_OPTION;
-    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if ((out_sum && !workspace) || (n > 0 && (!pred || !target || !grad_pred))) return SPH2POB_ERR_NULL;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nb = (n + kBlock - 1) / kBlock;
-    float* partial = out_sum ? workspace : nullptr;
-    if (nb > 0) {
-        dim3 grid((unsigned)nb);
-#define SPH_LOSS_FG(D, F) \
-        do { if (grad_target) hipLaunchKernelGGL((loss_fwd_grad_kernel<D, F, true>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, partial, grad_pred, grad_target, n, loss_mode, eps); \
-             else hipLaunchKernelGGL((loss_fwd_grad_kernel<D, F, false>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, partial, grad_pred, grad_target, n, loss_mode, eps); } while (0)
-        if (box_dim == 4) { if (fast) SPH_LOSS_FG(4, true); else SPH_LOSS_FG(4, false); }
-        else { if (fast) SPH_LOSS_FG(5, true); else SPH_LOSS_FG(5, false); }
-#undef SPH_LOSS_FG
-    }
-    if (out_sum) {   // scale is already inside the elements
-        if (nb <= 65536) {
-            hipLaunchKernelGGL(sum_pass2, dim3(1), dim3(kBlock), 0, s, workspace, (int)nb, 1.0f, out_sum);
-        } else {
-            float* ws2 = workspace + nb;
-            hipLaunchKernelGGL(sum_pass1, dim3(kSumBlocks), dim3(kBlock), 0, s, workspace, nb, ws2);
-            hipLaunchKernelGGL(sum_pass2, dim3(1), dim3(kBlock), 0, s, ws2, kSumBlocks, 1.0f, out_sum);
-        }
-    }
-    return launch_status();
+    if (int rc = loss_check(weight, weight_dim, n, box_dim, loss_mode_flags)) return rc;
+    return launch_fwd_grad<IouBody>(pred, target, weight, weight_dim, scale, loss, out_sum, workspace, grad_pred, grad_target,
+                                    n, box_dim, loss_mode_flags, stream, loss_mode_flags & 0xff, eps);
 }
 
-// ---- Sph2PobGDLoss / Sph2PobKFLoss: the four forms of the IoU family, per-pair body GaussBody ----
-#define SPH_GAUSS_SEL(LAUNCH)                                                           \
-    do {                                                                                \
-        const bool fast = !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER);                 \
-        if (box_dim == 4) { if (fast) LAUNCH(4, true); else LAUNCH(4, false); }         \
-        else { if (fast) LAUNCH(5, true); else LAUNCH(5, false); }                      \
-    } while (0)
-
+// ---- Sph2PobGDLoss / Sph2PobKFLoss: the same four forms with the per-pair body GaussBody ----
 int sph2pob_gauss_loss_fwd_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                                float* loss, int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha,
                                int opts, float beta, float eps, void* stream) {
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !loss) return SPH2POB_ERR_NULL;
-    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
-    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    hipStream_t s = (hipStream_t)stream;
-#define SPH_GAUSS_FWD(D, F) \
-    hipLaunchKernelGGL((gauss_fwd_kernel<D, F>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, n, body)
-    SPH_GAUSS_SEL(SPH_GAUSS_FWD);
-#undef SPH_GAUSS_FWD
-    return launch_status();
+    return launch_fwd<GaussBody>(pred, target, weight, weight_dim, scale, loss, nullptr, n, box_dim, type_flags, stream,
+                                 GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
 
 int sph2pob_gauss_loss_bwd_f32(const float* pred, const float* target, const float* weight, int weight_dim,
@@ -496,36 +355,16 @@ int sph2pob_gauss_loss_bwd_f32(const float* pred, const float* target, const flo
                                float beta, float eps, void* stream) {
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
     if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
-    if (n == 0) return SPH2POB_OK;
-    if (!pred || !target || !grad_out || !grad_pred) return SPH2POB_ERR_NULL;
-    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
-    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    hipStream_t s = (hipStream_t)stream;
-#define SPH_GAUSS_BWD(D, F) \
-    do { if (grad_target) hipLaunchKernelGGL((gauss_bwd_kernel<D, F, true>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, body); \
-         else hipLaunchKernelGGL((gauss_bwd_kernel<D, F, false>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n, body); } while (0)
-    SPH_GAUSS_SEL(SPH_GAUSS_BWD);
-#undef SPH_GAUSS_BWD
-    return launch_status();
+    return launch_bwd<GaussBody>(pred, target, weight, weight_dim, grad_out, grad_stride, scale, grad_pred, grad_target, n,
+                                 box_dim, type_flags, stream, GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
 
 int sph2pob_gauss_loss_fwd_sum_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                                    float* out, float* workspace, int64_t n, int box_dim, int type_flags, int fun, float tau,
                                    float alpha, int opts, float beta, float eps, void* stream) {
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
-    if (!out || !workspace || (n > 0 && (!pred || !target))) return SPH2POB_ERR_NULL;
-    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nb = (n + kBlock - 1) / kBlock;
-    if (nb > 0) {
-        dim3 grid((unsigned)nb);
-#define SPH_GAUSS_FWDS(D, F) \
-        hipLaunchKernelGGL((gauss_fwd_sum_kernel<D, F>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, workspace, n, body)
-        SPH_GAUSS_SEL(SPH_GAUSS_FWDS);
-#undef SPH_GAUSS_FWDS
-    }
-    launch_partial_sum(workspace, nb, scale, out, s);
-    return launch_status();
+    return launch_fwd_sum<GaussBody>(pred, target, weight, weight_dim, scale, out, workspace, n, box_dim, type_flags, stream,
+                                     GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
 
 int sph2pob_gauss_loss_fwd_grad_f32(const float* pred, const float* target, const float* weight, int weight_dim,
@@ -533,29 +372,13 @@ int sph2pob_gauss_loss_fwd_grad_f32(const float* pred, const float* target, cons
                                     float* grad_target, int64_t n, int box_dim, int type_flags, int fun, float tau,
                                     float alpha, int opts, float beta, float eps, void* stream) {
     if (int rc = gauss_check(weight, weight_dim, n, box_dim, type_flags, fun, opts)) return rc;
-    if ((out_sum && !workspace) || (n > 0 && (!pred || !target || !grad_pred))) return SPH2POB_ERR_NULL;
-    const GaussBody body{type_flags & 0xff, fun, tau, alpha, opts, beta, eps};
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nb = (n + kBlock - 1) / kBlock;
-    float* partial = out_sum ? workspace : nullptr;
-    if (nb > 0) {
-        dim3 grid((unsigned)nb);
-#define SPH_GAUSS_FG(D, F) \
-        do { if (grad_target) hipLaunchKernelGGL((gauss_fwd_grad_kernel<D, F, true>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, partial, grad_pred, grad_target, n, body); \
-             else hipLaunchKernelGGL((gauss_fwd_grad_kernel<D, F, false>), grid, dim3(kBlock), 0, s, pred, target, weight, weight_dim, scale, loss, partial, grad_pred, grad_target, n, body); } while (0)
-        SPH_GAUSS_SEL(SPH_GAUSS_FG);
-#undef SPH_GAUSS_FG
-    }
-    if (out_sum) launch_partial_sum(workspace, nb, 1.0f, out_sum, s);   // scale is already inside the elements
-    return launch_status();
+    return launch_fwd_grad<GaussBody>(pred, target, weight, weight_dim, scale, loss, out_sum, workspace, grad_pred, grad_target,
+                                      n, box_dim, type_flags, stream, GaussBody{type_flags & 0xff, fun, tau, alpha, opts, beta, eps});
 }
-#undef SPH_GAUSS_SEL
 
 int sph2pob_loss_grad_scale_f32(const float* stash, const float* grad_out, int grad_stride, float* out, int64_t n,
                                 int box_dim, void* stream) {
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+    if (int rc = grad_scale_check(n, box_dim, grad_stride)) return rc;
     if (n == 0) return SPH2POB_OK;
     if (!stash || !grad_out || !out) return SPH2POB_ERR_NULL;
     const int64_t total = n * box_dim;

@@ -18,6 +18,9 @@
 //   The acos(clamp(.)) of the reference has zero gradient where the clamp is active (A/2 < 4.88e-4,
 //   |cos a| > 1 - 1e-7); in-place clamps of the two jitters gate the gradient the same way torch.clamp_ does.
 #pragma once
+#include <stdint.h>
+
+#include "../../include/sph2pob_hip.h"
 #include "sph2pob_device.hpp"
 
 namespace sph2pob {
@@ -644,7 +647,8 @@ SPH_DEV float GaussBody::eval(const float (&pred)[5], const float (&target)[5], 
     return pair_gauss_loss<DIM, BWD, FAST>(pred, target, *this, gpred, gtarget);
 }
 
-// The IoU family's trailing launcher parameters as a per-pair body (the host twins' loss pass is generic over the body).
+// The IoU family's trailing launcher parameters as a per-pair body (the kernels build it from the flat (loss_mode, eps) and
+// call pair_loss themselves; the host twins' loss pass calls eval()).
 struct IouBody {
     int loss_mode;
     float eps;
@@ -654,5 +658,66 @@ struct IouBody {
         return pair_loss<DIM, BWD, FAST>(pred, target, loss_mode, eps, iou_out, gpred, gtarget);
     }
 };
+
+// ---- shared by the loss launchers (sph2pob_loss.hip) and their host twins (sph2pob_host.hip) ----
+constexpr int64_t kMaxElems = (int64_t)1 << 38;  // grid.x = n / 256 must stay below 2^31
+
+// per-element weight = mean over weight_dim columns (reference: sph2pob_transform.py:32-34 widens a (n,4) weight with its
+// own mean, OBBIoULoss.forward then takes weight.mean(-1): sph2pob_iou_loss.py:48)
+template <int DIM>
+SPH_DEV float element_weight(const float* __restrict__ w, int wd, int64_t i) {
+    if (!w) return 1.0f;
+    if (wd == 1) return w[i];
+    float v[DIM], s = 0.0f;   // wd == DIM here (the checks reject anything else): DIM loads in flight, not a loop of load + wait
+#pragma unroll
+    for (int k = 0; k < DIM; k++) v[k] = w[i * DIM + k];
+#pragma unroll
+    for (int k = 0; k < DIM; k++) s += v[k];
+    if (DIM == 4) return (s + s / 4.0f) / 5.0f;
+    return s / (float)DIM;
+}
+
+// argument checks of the IoU family: loss mode 0..3 (| SPH2POB_FLAG_REFERENCE_ORDER); the backward's grad_stride is
+// checked with the mode (the other forms pass 0)
+inline int loss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int loss_mode_flags, int grad_stride = 0) {
+    const int loss_mode = loss_mode_flags & 0xff;
+    if (loss_mode_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    if (loss_mode < 0 || loss_mode > 3 || (grad_stride != 0 && grad_stride != 1)) return SPH2POB_ERR_OPTION;
+    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
+    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+    return SPH2POB_OK;
+}
+
+// argument checks of the Gaussian family: SPH2POB_GAUSS_* type (| SPH2POB_FLAG_REFERENCE_ORDER), a post-map the type
+// accepts (GD: none | log1p | sqrt, KF: none | ln | exp), SPH2POB_GAUSS_OPT_* options
+inline int gauss_check(const float* weight, int weight_dim, int64_t n, int box_dim, int type_flags, int fun, int opts) {
+    const int type = type_flags & 0xff;
+    if (type_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    if (type < SPH2POB_GAUSS_GWD || type > SPH2POB_GAUSS_KF) return SPH2POB_ERR_OPTION;
+    const bool fun_ok = type == SPH2POB_GAUSS_KF
+                            ? (fun == SPH2POB_GAUSS_FUN_NONE || fun == SPH2POB_GAUSS_FUN_LN || fun == SPH2POB_GAUSS_FUN_EXP)
+                            : (fun >= SPH2POB_GAUSS_FUN_NONE && fun <= SPH2POB_GAUSS_FUN_SQRT);
+    if (!fun_ok || (opts & ~(SPH2POB_GAUSS_OPT_SQRT | SPH2POB_GAUSS_OPT_NORMALIZE))) return SPH2POB_ERR_OPTION;
+    if (weight && weight_dim != 1 && weight_dim != box_dim) return SPH2POB_ERR_OPTION;
+    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+    return SPH2POB_OK;
+}
+
+// argument checks of sph2pob_loss_grad_scale_f32
+inline int grad_scale_check(int64_t n, int box_dim, int grad_stride) {
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
+    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+    return SPH2POB_OK;
+}
+
+static_assert(SPH2POB_GAUSS_GWD == GAUSS_GWD && SPH2POB_GAUSS_KLD == GAUSS_KLD && SPH2POB_GAUSS_JD == GAUSS_JD &&
+              SPH2POB_GAUSS_KLD_SYMMAX == GAUSS_KLD_SYMMAX && SPH2POB_GAUSS_KLD_SYMMIN == GAUSS_KLD_SYMMIN &&
+              SPH2POB_GAUSS_KF == GAUSS_KF, "loss type codes");
+static_assert(SPH2POB_GAUSS_FUN_NONE == GFUN_NONE && SPH2POB_GAUSS_FUN_LOG1P == GFUN_LOG1P && SPH2POB_GAUSS_FUN_SQRT == GFUN_SQRT &&
+              SPH2POB_GAUSS_FUN_LN == GFUN_LN && SPH2POB_GAUSS_FUN_EXP == GFUN_EXP, "post-map codes");
+static_assert(SPH2POB_GAUSS_OPT_SQRT == GOPT_SQRT && SPH2POB_GAUSS_OPT_NORMALIZE == GOPT_NORMALIZE, "option bits");
 
 }  // namespace sph2pob

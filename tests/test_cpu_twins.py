@@ -131,6 +131,38 @@ def test_loss_forward_and_backward_on_cpu(S, box):
     assert torch.allclose(q.grad, 3.0 * g1, rtol=1e-5, atol=1e-9)
 
 
+def test_loss_launcher_error_codes_match_the_device_library():
+    """The IoU-family launchers and sph2pob_loss_grad_scale_f32 return the same error codes, in the same order of
+    precedence, from the device library and from their host twins (argument errors come before any device work)."""
+    import ctypes
+    from sph_retina_amd import _lib
+    null, big = ctypes.c_void_p(0), (1 << 38) + 1
+    p = ctypes.c_void_p(8)
+    for lib, suf in ((_lib.lib(), ''), (_lib.host_lib(), '_cpu')):
+        scale = getattr(lib, 'sph2pob_loss_grad_scale_f32' + suf)
+        assert scale(null, null, 0, null, 0, 5, null) == 0
+        assert scale(null, null, 0, null, 10, 5, null) == -1
+        assert scale(null, null, 0, null, 10, 3, null) == -2
+        assert scale(null, null, 0, null, -1, 3, null) == -2        # box_dim before the count
+        assert scale(null, null, 2, null, 10, 4, null) == -3
+        assert scale(null, null, 2, null, -1, 4, null) == -3        # grad_stride before the count
+        assert scale(null, null, 1, null, -1, 4, null) == -4
+        assert scale(null, null, 0, null, big, 4, null) == -4
+        fwd = getattr(lib, 'sph2pob_loss_fwd_f32' + suf)
+        bwd = getattr(lib, 'sph2pob_loss_bwd_f32' + suf)
+        assert fwd(null, null, null, 0, 1.0, null, null, 0, 5, 3, 1e-6, null) == 0
+        assert fwd(null, null, null, 0, 1.0, null, null, 10, 5, 3, 1e-6, null) == -1
+        assert fwd(null, null, null, 0, 1.0, null, null, 10, 3, 3, 1e-6, null) == -2
+        assert fwd(null, null, null, 0, 1.0, null, null, 10, 5, 4, 1e-6, null) == -3
+        assert fwd(null, null, null, 0, 1.0, null, null, 10, 5, 0x203, 1e-6, null) == -3
+        assert fwd(p, p, p, 3, 1.0, null, null, 10, 5, 3, 1e-6, null) == -3
+        assert fwd(null, null, null, 0, 1.0, null, null, big, 5, 3, 1e-6, null) == -4
+        assert bwd(null, null, null, 0, null, 2, 1.0, null, null, 10, 5, 3, 1e-6, null) == -3
+        assert bwd(null, null, null, 0, null, 2, 1.0, null, null, -1, 5, 3, 1e-6, null) == -3   # grad_stride before the count
+        assert bwd(null, null, null, 0, null, 1, 1.0, null, null, -1, 5, 3, 1e-6, null) == -4
+        assert bwd(null, null, null, 0, null, 0, 1.0, null, null, 0, 4, 3, 1e-6, null) == 0
+
+
 def test_nms_and_assigner_on_cpu(S, oracle):
     from sph_retina_amd.bbox.nms import SphNMS, sph_nms_op
     from sph_retina_amd.bbox.assigners import SphMaxIoUAssigner, assign_wrt_overlaps

@@ -36,17 +36,20 @@ def timeit(fn, warm=5, reps=30, settle_s=0.03):
     return e0.elapsed_time(e1) / reps * 1e-3
 
 
-def pmc_roofline(kernel_prefix, seconds, algorithmic_bytes, grid=None):
+def pmc_roofline(kernel_prefix, seconds, algorithmic_bytes, grid=None, gauss=False):
     """What bounds a kernel, from this round's committed counter passes (profiles/configs_pmc_summary.json, made by
     tools/profile_configs_pmc.sh + tools/summarize_configs_pmc.py): HBM-side bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, the
-    guide's gfx950 correction) and the VALU issue-slot fraction, next to the algorithmic bytes and THIS run's time."""
+    guide's gfx950 correction) and the VALU issue-slot fraction, next to the algorithmic bytes and THIS run's time.
+    The IoU and Gaussian losses share their kernel templates: `gauss` picks the kernels with the GaussBody template argument,
+    otherwise those are left out."""
     out = {'algorithmic_bytes': algorithmic_bytes, 'hbm_frac_algorithmic': algorithmic_bytes / seconds / 8e12 if algorithmic_bytes else None}
     try:
         with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'configs_pmc_summary.json')) as f:
             ks = json.load(f)['kernels']
     except (OSError, ValueError):
         return out
-    cands = [e for k, e in ks.items() if e['kernel'].startswith(kernel_prefix) and (grid is None or e['grid_threads'] == grid)]
+    cands = [e for k, e in ks.items() if e['kernel'].startswith(kernel_prefix) and ('GaussBody' in e['kernel']) == gauss and
+             (grid is None or e['grid_threads'] == grid)]
     if not cands:
         return out
     e = max(cands, key=lambda c: c['grid_threads'])
@@ -376,7 +379,7 @@ def gaussian(n=1_000_000):
         ta = timeit(abi)
         res[f'{name}_c_abi_fwd_bwd_ms'] = ta * 1e3
         res[f'{name}_autograd_fwd_bwd_ms'] = timeit(step) * 1e3
-        res[f'{name}_roofline'] = pmc_roofline('gauss_fwd_grad_kernel', ta, 60.0 * n)
+        res[f'{name}_roofline'] = pmc_roofline('loss_fwd_grad_kernel', ta, 60.0 * n, gauss=True)
     res['note'] = ('c_abi = gauss_loss_fwd_grad (forward + gradients + partial sums in one pass) + final sum + grad_scale (in '
                    'place, g = 1); roofline at 60 B/pair (pred, target, grad_pred)')
     return res

@@ -79,7 +79,8 @@ def main():
             if 'SQ_ACTIVE_INST_VALU' in s:
                 e['valu_issue_frac'] = s['SQ_ACTIVE_INST_VALU'] * 4 / (1024 * e['avg_ns'] * 2.4)
         for k2, (desc, fn) in ALGO.items():
-            if name.startswith(k2) and fn is not None:
+            # (the loss entry is the IoU family's: the Gaussian losses share its kernel templates, with GaussBody)
+            if name.startswith(k2) and 'GaussBody' not in name and fn is not None:
                 e['algorithmic_bytes'] = fn(grid)
                 e['algorithmic_bytes_note'] = desc
                 e['hbm_frac_algorithmic'] = e['algorithmic_bytes'] / (e['avg_ns'] * 1e-9) / HBM_PEAK
