@@ -94,6 +94,7 @@ int sph2pob_iou_pairwise_f32(const float* b1, int64_t m, const float* b2, int64_
  * (sphdet/losses/sph2pob_transform.py:26-30) — the shared front end of every Sph2Pob-wrapped OBB loss.
  * Replaces sph2pob_{standard,efficient,legacy}(sph_gt, sph_pred, rbb_angle_version='rad', ...):
  * sphdet/iou/sph2pob_standard.py:8-80, sph2pob_efficient.py:9-73, sph2pob_legacy.py:8-31.
+ * variant: STANDARD, EFFICIENT or LEGACY (BFoV only); any other variant returns SPH2POB_ERR_OPTION.
  */
 int sph2pob_transform_f32(const float* b1, const float* b2, float* planar1, float* planar2, int64_t n,
                           int box_dim, int variant, int edge, int angle, int jitter, void* stream);
@@ -104,6 +105,7 @@ int sph2pob_transform_f32(const float* b1, const float* b2, float* planar1, floa
  * (degrees).  This is what lets every Sph2Pob-wrapped OBB loss (Sph2PobTransfrom.new_forward,
  * sphdet/losses/sph2pob_transform.py:24-35: L1 / GD / KF / IoU bodies) back-propagate to the spherical inputs without
  * torch autograd through the ~70 transform ops.  With jitter != 0 the clamp gates of both jitters are applied.
+ * Any variant other than STANDARD or EFFICIENT returns SPH2POB_ERR_OPTION.
  */
 int sph2pob_transform_bwd_f32(const float* b1, const float* b2, const float* grad_planar1, const float* grad_planar2,
                               float* grad_b1, float* grad_b2, int64_t n, int box_dim, int variant, int edge, int jitter,

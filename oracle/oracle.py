@@ -196,17 +196,21 @@ def loss_grad_fd(pred, target, mode='iou', eps=1e-6, h=1e-5):
     return gp, gt
 
 
-def transform_vjp_fd(b1, b2, g1, g2, variant='standard', edge='arc', jitter=True, h=1e-5):
+def transform_vjp_fd(b1, b2, g1, g2, variant='standard', edge='arc', jitter=True, h=1e-5, angle='equator',
+                     return_smooth=False):
     """f64 central finite differences of  sum(g1 * planar1 + g2 * planar2)  w.r.t. the spherical inputs (degrees):
-    the vector-Jacobian product the HIP transform adjoint must reproduce."""
+    the vector-Jacobian product the HIP transform adjoint must reproduce.  With ``return_smooth`` also a per-pair mask
+    that is False where a kink lies inside the step (the one-sided slopes of some input column disagree)."""
     b1 = _np(b1, np.float64)
     b2 = _np(b2, np.float64)
     g1 = _np(g1, np.float64)
     g2 = _np(g2, np.float64)
 
     def f():
-        p1, p2 = transform(b1, b2, variant=variant, edge=edge, jitter=jitter, dtype=np.float64)
+        p1, p2 = transform(b1, b2, variant=variant, edge=edge, angle=angle, jitter=jitter, dtype=np.float64)
         return (g1 * p1).sum(1) + (g2 * p2).sum(1)
+    base = f() if return_smooth else None
+    smooth = np.ones(b1.shape[0], bool)
     out = []
     for arr in (b1, b2):
         g = np.zeros_like(arr)
@@ -218,8 +222,10 @@ def transform_vjp_fd(b1, b2, g1, g2, variant='standard', edge='arc', jitter=True
             fm = f()
             arr[:, k] = save
             g[:, k] = (fp - fm) / (2 * h)
+            if return_smooth:
+                smooth &= np.abs((fp - base) - (base - fm)) < 1e-3 * np.abs(fp - fm) + 1e-9
         out.append(g)
-    return out
+    return (out, smooth) if return_smooth else out
 
 
 def nms_op(boxes, scores, iou_threshold, variant='efficient', planar='mmcv', nthreads=1):

@@ -309,6 +309,7 @@ int sph2pob_transform_f32_cpu(const float* b1, const float* b2, float* planar1, 
                               int edge, int angle, int jitter, void*) {
     int rc = check_common(box_dim, variant, edge, angle);
     if (rc) return rc;
+    if ((variant & 0xff) > SPH2POB_VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
     if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
     if (n == 0) return SPH2POB_OK;
     if (!b1 || !b2 || !planar1 || !planar2) return SPH2POB_ERR_NULL;
@@ -404,9 +405,8 @@ int sph2pob_loss_grad_scale_f32_cpu(const float* stash, const float* grad_out, i
 }
 
 int sph2pob_sum_f32_cpu(const float* x, int64_t n, float scale, float* out, float* workspace, void*) {
-    (void)workspace;
-    if (n < 0) return SPH2POB_ERR_SIZE;
-    if (!out || (n > 0 && !x)) return SPH2POB_ERR_NULL;
+    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
+    if (!out || !workspace || (n > 0 && !x)) return SPH2POB_ERR_NULL;   // the device's checks (no workspace is used here)
     double s = 0.0;
     for (int64_t i = 0; i < n; i++) s += x[i];
     out[0] = (float)(s * (double)scale);

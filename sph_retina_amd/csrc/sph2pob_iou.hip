@@ -437,9 +437,12 @@ struct AlignedLaunch {
 struct TransformLaunch {
     const float *b1, *b2; float *o1, *o2; int64_t n; int edge, angle, jitter; hipStream_t s; bool fast = true;
     template <int V, int D> int run() {
-        dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-        hipLaunchKernelGGL((transform_kernel<V, D>), grid, dim3(kBlock), 0, s, b1, b2, o1, o2, n, edge, angle, jitter);
-        return launch_status();
+        if constexpr (V > 2) return SPH2POB_ERR_OPTION;   // transform<V, D> computes nothing for the other IoU variants
+        else {
+            dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+            hipLaunchKernelGGL((transform_kernel<V, D>), grid, dim3(kBlock), 0, s, b1, b2, o1, o2, n, edge, angle, jitter);
+            return launch_status();
+        }
     }
 };
 
@@ -479,6 +482,7 @@ int sph2pob_transform_f32(const float* b1, const float* b2, float* planar1, floa
                           int box_dim, int variant, int edge, int angle, int jitter, void* stream) {
     int rc = check_common(box_dim, variant, edge, angle);
     if (rc) return rc;
+    if ((variant & 0xff) > SPH2POB_VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
     if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
     if (n == 0) return SPH2POB_OK;
     if (!b1 || !b2 || !planar1 || !planar2) return SPH2POB_ERR_NULL;
@@ -514,7 +518,7 @@ int sph2pob_transform_bwd_f32(const float* b1, const float* b2, const float* gra
                               void* stream) {
     int rc = check_common(box_dim, variant, edge, 0);
     if (rc) return rc;
-    if ((variant & 0xff) == SPH2POB_VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
+    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT) return SPH2POB_ERR_OPTION;
     if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
     if (n == 0) return SPH2POB_OK;
     if (!b1 || !b2 || !grad_planar1 || !grad_planar2 || !grad_b1 || !grad_b2) return SPH2POB_ERR_NULL;
