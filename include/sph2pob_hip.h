@@ -337,6 +337,49 @@ int sph2pob_iou_assign_f32(const float* gt, int64_t k, const float* boxes, int64
                            float* max_overlaps, int64_t* argmax_overlaps, float* gt_max_overlaps, int64_t* gt_argmax_overlaps,
                            int64_t* assigned_gt_inds, int64_t* assigned_labels, void* workspace, void* state, void* stream);
 
+/*
+ * Anchor targets for a whole minibatch: the fused assigner above with the image as a grid dimension, and the target
+ * construction of AnchorHead._get_targets_single (mmdet/models/dense_heads/anchor_head.py:254-285 with PseudoSampler) as the
+ * finalize pass's epilogue.  Replaces multi_apply(_get_targets_single, ...) over the images (anchor_head.py:202-299, :301-396)
+ * for unmap_outputs-free heads (allowed_border = -1: every anchor is valid for every image): two launches for the batch, no
+ * (k, n) matrix, nothing read back to the host.
+ *   anchors      (n, box_dim), shared by all images
+ *   gt           (num_gt, box_dim), the images' GT boxes concatenated; gt_labels (num_gt) int64 or NULL (RPN: label 0)
+ *   gt_offsets   (num_images + 1) int64 ON THE DEVICE: image b owns rows gt_offsets[b] .. gt_offsets[b + 1] (it may own none).
+ *                The host never reads them: offsets are clamped to [0, num_gt] before use
+ *   k_max        HOST upper bound on the GT count of one image (<= num_gt; num_gt itself is always sufficient).  Grid,
+ *                workspace and state are sized by it.  An image with more rows than k_max is CLAMPED to its first k_max rows
+ *                (the later ones are not assigned): nothing is read or written out of bounds, and nothing is reported
+ *   thresholds / match_low_quality / gt_max_assign_all as for sph2pob_iou_assign_f32 (no ignore mask in this form)
+ * For image b and anchor j, with g = assigned_gt_inds[b, j] exactly what sph2pob_iou_assign_f32 gives for that image alone
+ * (all 0, max_overlaps 0, for an image without GT: max_iou_assigner.py:148-165):
+ *   assigned_gt_inds (B, n) int64, max_overlaps (B, n) f32, assigned_labels (B, n) int64 (optional; gt_labels[g - 1] | -1)
+ *   labels         (B, n) int64       g > 0: gt_labels[g - 1] (0 when gt_labels is NULL); otherwise num_classes
+ *   label_weights  (B, n) f32         g > 0: 1, or pos_weight when pos_weight > 0; g == 0: 1; g == -1: 0
+ *   bbox_targets   (B, n, box_dim)    g > 0: the GT box (encode == 0: reg_decoded_bbox=True) or its deltas w.r.t. anchor j
+ *                                     (encode != 0: the arithmetic of sph2pob_coder_encode_f32 with means_host / stds_host); else 0
+ *   bbox_weights   (B, n, box_dim)    g > 0: 1; else 0
+ *   num_pos, num_neg (B) int64        anchors with g > 0 / g == 0 (PseudoSampler's pos_inds / neg_inds)
+ *   avg_factor     (1) f32            sum_b max(num_pos[b], 1): mmdet's num_total_pos (anchor_head.py:385) as a device scalar
+ *   workspace    sph2pob_anchor_targets_workspace_bytes(num_images, num_gt, k_max, n) bytes of scratch, no initialisation
+ *   state        sph2pob_anchor_targets_state_bytes(num_images, k_max, n) bytes, ZERO when a call is enqueued and left zero by
+ *                every completed call, as the state of sph2pob_iou_assign_f32 (zero once after allocation, reuse stream-ordered;
+ *                clean for any shape it is large enough for)
+ * Limits: num_images <= 65 535, k_max <= 262 140, n < 2^31 - 256.  Errors, checked in this order before anything is enqueued:
+ * box_dim -> SPH2POB_ERR_DIM; a variant other than STANDARD | EFFICIENT, SPH2POB_FLAG_REFERENCE_ORDER, a bad edge ->
+ * SPH2POB_ERR_OPTION; num_images <= 0, num_gt < 0, n <= 0, k_max < 0 or > num_gt, a limit exceeded -> SPH2POB_ERR_SIZE; a NULL
+ * among the required pointers (gt, and gt_labels with assigned_labels, only when num_gt > 0; workspace only when k_max > 0) -> SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_anchor_targets_workspace_bytes(int64_t num_images, int64_t num_gt, int64_t k_max, int64_t n);
+int64_t sph2pob_anchor_targets_state_bytes(int64_t num_images, int64_t k_max, int64_t n);
+int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
+                               int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
+                               float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
+                               int64_t num_classes, float pos_weight, int encode, const float* means_host, const float* stds_host,
+                               int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
+                               float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
+                               float* avg_factor, void* workspace, void* state, void* stream);
+
 /* ---- box coder: the step immediately in front of the loss when reg_decoded_bbox=True --------------
  * Replaces sphdet/bbox/coder/delta_xywh_sph_bbox_coder.py:116-161 (bbox2delta), :164-263 (delta2bbox) for box_dim 4
  * and sphdet/bbox/coder/delta_xywha_rsph_bbox_coder.py:116-164, :167-268 for box_dim 5 (fifth delta = deg2rad of the

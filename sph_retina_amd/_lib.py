@@ -42,7 +42,7 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_nms_segmented_f32', 'sph2pob_nms_f32', 'sph2pob_assign_f32', 'sph2pob_coder_encode_f32',
               'sph2pob_coder_decode_f32', 'sph2pob_coder_decode_bwd_f32', 'sph2pob_obb_l1_fwd_f32', 'sph2pob_obb_l1_bwd_f32',
               'sph2pob_gauss_loss_fwd_f32', 'sph2pob_gauss_loss_bwd_f32', 'sph2pob_gauss_loss_fwd_sum_f32',
-              'sph2pob_gauss_loss_fwd_grad_f32']
+              'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_kernels_common.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
 # half the rate of plain VALU on gfx950 (tools/ubench/valu_rate2.hip), measured 12 % slower on the dominant kernel
@@ -104,6 +104,12 @@ SIGNATURES = {
     'sph2pob_iou_assign_f32': [_c_f32p, _i64, _c_f32p, _i64, _int, _int, _int, ctypes.c_void_p, _c_f32p] +
                               [ctypes.c_float] * 4 + [_int, _int] + [ctypes.c_void_p] * 10,
     'sph2pob_iou_assign_state_bytes': [_i64, _i64],
+    'sph2pob_anchor_targets_workspace_bytes': [_i64, _i64, _i64, _i64],
+    'sph2pob_anchor_targets_state_bytes': [_i64, _i64, _i64],
+    # anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt, k_max, box_dim, variant, edge, 4 thresholds, 2 flags, num_classes,
+    # pos_weight, encode, means, stds, 10 outputs, workspace, state, stream
+    'sph2pob_anchor_targets_f32': [_c_f32p, _i64, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, _int, _int, _int] +
+                                  [ctypes.c_float] * 4 + [_int, _int, _i64, ctypes.c_float, _int] + [ctypes.c_void_p] * 15,
     'sph2pob_nms_max_boxes': [],
     'sph2pob_nms_workspace_bytes': [_i64],
     'sph2pob_nms_f32': [_c_f32p, ctypes.c_void_p, _i64, _int, _int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
@@ -127,6 +133,7 @@ SIGNATURES = {
 _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_target_arch': ctypes.c_char_p, 'sph2pob_error_string': ctypes.c_char_p,
              'sph2pob_nms_workspace_bytes': ctypes.c_int64, 'sph2pob_nms_segmented_workspace_bytes': ctypes.c_int64, 'sph2pob_assign_workspace_bytes': ctypes.c_int64,
              'sph2pob_iou_assign_workspace_bytes': ctypes.c_int64, 'sph2pob_iou_assign_state_bytes': ctypes.c_int64,
+             'sph2pob_anchor_targets_workspace_bytes': ctypes.c_int64, 'sph2pob_anchor_targets_state_bytes': ctypes.c_int64,
              'sph2pob_batched_nms_workspace_bytes': ctypes.c_int64}
 
 ABI_VERSION = 1

@@ -203,6 +203,27 @@ class SphMaxIoUAssigner:
             overlaps[:, ignore_mask] = -1
         return self.assign_wrt_overlaps(overlaps, gt_labels)
 
+    def assign_batch(self, bboxes, gt_bboxes_list, gt_labels_list=None):
+        """`assign(bboxes, gt_bboxes_list[b], gt_labels=gt_labels_list[b])` for every image of a minibatch -> list of
+        AssignResult.  With a closed-form Sph2Pob calculator the whole batch is one call of the batched kernels
+        (`sph_anchor_targets`: two launches, no host synchronisation) and the results are views into its outputs; otherwise
+        (another backend, the 'reference' arithmetic, `fused=False`, `gpu_assign_thr`) a loop over `assign`."""
+        from .anchor_targets import batched_variant, sph_anchor_targets
+        if gt_labels_list is not None:
+            assert len(gt_labels_list) == len(gt_bboxes_list)
+        if len(gt_bboxes_list) == 0:
+            return []
+        if batched_variant(self, bboxes) is None or self.gpu_assign_thr > 0:
+            return [self.assign(bboxes, gt, gt_labels=None if gt_labels_list is None else gt_labels_list[b])
+                    for b, gt in enumerate(gt_bboxes_list)]
+        out = sph_anchor_targets(bboxes, list(gt_bboxes_list), None if gt_labels_list is None else list(gt_labels_list),
+                                 assigner=self, num_classes=0)
+        results = out.assign_results(out.num_gts)
+        if bboxes.is_floating_point() and bboxes.dtype != torch.float32:
+            for r in results:
+                r.max_overlaps = r.max_overlaps.to(bboxes.dtype)
+        return results
+
     def _fused_variant(self, bboxes, gt_bboxes):
         """The closed-form variant the fused path serves, or None (another calculator / backend / arithmetic, empty inputs)."""
         from ...iou.sph_iou_calculator import SphOverlaps2D

@@ -1,7 +1,9 @@
-// libsph2pob_hip.so — pairwise IoU (the assigner call pattern) and the MaxIoUAssigner epilogues, matrix and fused: kernels +
-// C-ABI launchers (include/sph2pob_hip.h).  gfx950 only.
+// libsph2pob_hip.so — pairwise IoU (the assigner call pattern), the MaxIoUAssigner epilogues, matrix and fused, and the fused
+// assigner batched over a minibatch with the anchor-target construction as its epilogue: kernels + C-ABI launchers
+// (include/sph2pob_hip.h).  gfx950 only.
 
 #include "sph2pob_kernels_common.hpp"
+#include "sph2pob_coder.hpp"
 
 namespace {
 
@@ -72,16 +74,17 @@ __host__ __device__ inline int64_t acc_stride(int64_t k) { return k <= 1024 ? 32
 __host__ __device__ inline int64_t acc_words(int64_t k) { return (k * acc_stride(k) + kAccLine - 1) / kAccLine * kAccLine; }
 __host__ __device__ inline int64_t ticket_groups(int64_t tiles) { return (tiles + kTicketGroup - 1) / kTicketGroup; }
 constexpr int kRowSlots = 4;   // LDS copies of a row's running maximum (lane & 3): a pass holds a few rows, 64 lanes on one address serialise
-template <int VARIANT, int DIM, bool ARC, int OUT = 1>
-__global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void iou_pairwise_compact_kernel(const float* __restrict__ b1, int m,
-                                                                     const float* __restrict__ b2, int n,
-                                                                     float* __restrict__ out, int mode, int edge_arg,
-                                                                     int rows_per_wg,
-                                                                     const unsigned char* __restrict__ ignore = nullptr,
-                                                                     unsigned long long* __restrict__ col_part = nullptr,
-                                                                     unsigned long long* __restrict__ row_part = nullptr,
-                                                                     unsigned col_offset = 0,
-                                                                     unsigned long long* __restrict__ row_acc = nullptr) {
+// The tile's work, shared by the single-image kernel and the batched one (anchor_targets_pairwise_kernel): column tile bx of
+// `tiles`, row chunk by; `stride` = distance of the per-GT accumulators in row_acc (acc_stride of the count the state was laid
+// out for).
+template <int VARIANT, int DIM, bool ARC, int OUT>
+__device__ __forceinline__ void pairwise_compact_tile(const float* __restrict__ b1, int m, const float* __restrict__ b2, int n,
+                                                      float* __restrict__ out, int mode, int edge_arg, int rows_per_wg,
+                                                      const unsigned char* __restrict__ ignore,
+                                                      unsigned long long* __restrict__ col_part,
+                                                      unsigned long long* __restrict__ row_part, unsigned col_offset,
+                                                      unsigned long long* __restrict__ row_acc, const int bx, const int by,
+                                                      const int tiles, const int64_t stride) {
     constexpr bool MATRIX = (OUT & 1) != 0, REDUCE = (OUT & 2) != 0;
     __shared__ float row_raw[kPwRows][5];
     __shared__ float4 row_cull[kPwRows];
@@ -100,17 +103,6 @@ __global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void iou_pairwise_compact_kern
     __shared__ unsigned long long tile_base;   // what a row holds before any survivor: (0, first live column) or (-1, first ignored one)
     const int edge = ARC ? (int)EDGE_ARC : edge_arg;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // dispatch order = LAST column tile first, all of its row chunks, then the tile before it: anchor grids end with their
-    // coarsest level (mmdet's AnchorGenerator walks the strides upwards) and their tiles grow heavier towards the end —
-    // the coarsest anchors survive the cull against nearly every GT and carry the longest serial chains of passes —, and
-    // the grid is larger than what is resident at once: dispatched last, the heaviest tiles started last.  Heaviest first:
-    // 64 x 98 208 anchors 21.7 -> 18.5 us, 64 x 392 832 47.2 -> 41.3 us with the rows-per-workgroup rule retuned for it
-    // (profiles/r03y_ab_pairwise*.log, r03z_ab_pairwise.log); tiles taken from both ends inwards instead: 20.2 / 42.1 us.
-    // A caller that lists the coarse level first gets the previous behaviour.  (tiles x chunks <= m n / 1024 + ..., and the
-    // m x n matrix has to fit the device: the linear id stays far below 2^32.  The same order from a transposed grid —
-    // chunks on x, tiles on y, no division — measured 1 % slower at 392 832 anchors: r04b_ab_pairwise_transposed.log.)
-    const unsigned lid = blockIdx.y * gridDim.x + blockIdx.x;
-    const int bx = (int)(gridDim.x - 1 - lid / gridDim.y), by = (int)(lid % gridDim.y);
     const int r0 = by * rows_per_wg, rows = (m - r0 < rows_per_wg) ? m - r0 : rows_per_wg;
     if ((int)threadIdx.x < rows) {
         float g[5];
@@ -208,14 +200,39 @@ __global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void iou_pairwise_compact_kern
 #pragma unroll
             for (int t = 0; t < kRowSlots; t++) same += (unsigned)(row_key[threadIdx.x][t] >> 32) == (unsigned)(best >> 32);
             // flag: conservative (a tie seen at a lower value also sets it; the finalize pass then only re-evaluates for nothing)
-            row_part[(int64_t)(r0 + threadIdx.x) * gridDim.x + bx] = best | (unsigned long long)(row_tie[threadIdx.x] | (same > 1));
+            row_part[(int64_t)(r0 + threadIdx.x) * tiles + bx] = best | (unsigned long long)(row_tie[threadIdx.x] | (same > 1));
             // the row's running maximum over all tiles: relaxed device-scope atomic, only from tiles that hold something
             // above the rows' common floor (0 at the shard's first column) — with an ignore mask the floor is not known
             // here, and every tile contributes
             if (ignore != nullptr || (unsigned)(best >> 32) > 0x80000000u)
-                __hip_atomic_fetch_max(row_acc + (r0 + threadIdx.x) * acc_stride(m), best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_max(row_acc + (r0 + threadIdx.x) * stride, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+template <int VARIANT, int DIM, bool ARC, int OUT = 1>
+__global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void iou_pairwise_compact_kernel(const float* __restrict__ b1, int m,
+                                                                     const float* __restrict__ b2, int n,
+                                                                     float* __restrict__ out, int mode, int edge_arg,
+                                                                     int rows_per_wg,
+                                                                     const unsigned char* __restrict__ ignore = nullptr,
+                                                                     unsigned long long* __restrict__ col_part = nullptr,
+                                                                     unsigned long long* __restrict__ row_part = nullptr,
+                                                                     unsigned col_offset = 0,
+                                                                     unsigned long long* __restrict__ row_acc = nullptr) {
+    // dispatch order = LAST column tile first, all of its row chunks, then the tile before it: anchor grids end with their
+    // coarsest level (mmdet's AnchorGenerator walks the strides upwards) and their tiles grow heavier towards the end —
+    // the coarsest anchors survive the cull against nearly every GT and carry the longest serial chains of passes —, and
+    // the grid is larger than what is resident at once: dispatched last, the heaviest tiles started last.  Heaviest first:
+    // 64 x 98 208 anchors 21.7 -> 18.5 us, 64 x 392 832 47.2 -> 41.3 us with the rows-per-workgroup rule retuned for it
+    // (profiles/r03y_ab_pairwise*.log, r03z_ab_pairwise.log); tiles taken from both ends inwards instead: 20.2 / 42.1 us.
+    // A caller that lists the coarse level first gets the previous behaviour.  (tiles x chunks <= m n / 1024 + ..., and the
+    // m x n matrix has to fit the device: the linear id stays far below 2^32.  The same order from a transposed grid —
+    // chunks on x, tiles on y, no division — measured 1 % slower at 392 832 anchors: r04b_ab_pairwise_transposed.log.)
+    const unsigned lid = blockIdx.y * gridDim.x + blockIdx.x;
+    const int bx = (int)(gridDim.x - 1 - lid / gridDim.y), by = (int)(lid % gridDim.y);
+    pairwise_compact_tile<VARIANT, DIM, ARC, OUT>(b1, m, b2, n, out, mode, edge_arg, rows_per_wg, ignore, col_part, row_part, col_offset,
+                                                  row_acc, bx, by, (int)gridDim.x, acc_stride(m));
 }
 
 // out[i*n + j]: consecutive lanes walk j (coalesced stores, b2 loads coalesced, b1 row is a broadcast).
@@ -390,27 +407,26 @@ __global__ __launch_bounds__(kBlock) void assign_keys_from_acc_kernel(unsigned l
 // Later GTs overwrite earlier ones in the reference's loop: the largest matching i wins.
 // FROM_ACC: the per-GT keys are phase 1's accumulators (one device); the last workgroup to finish zeroes them and the arrival
 // counter for the next call.  Otherwise they are `gt_keys` (all-reduced by the caller).
+// The column's share of C', common to the single-image kernel and the batched one (anchor_targets_finalize_kernel): returns
+// the assigned index (-1 / 0 / GT + 1) of column `tile * 256 + threadIdx.x` (clamped to n - 1 past the end) and its maximum
+// (m, am).  `stride`: distance of the per-GT accumulators (acc_stride of the count the state was laid out for).
 template <int VARIANT, int DIM, bool ARC, bool FROM_ACC>
-__global__ __launch_bounds__(kBlock) void assign_fused_finalize_kernel(const float* __restrict__ b1, int k, const float* __restrict__ b2, int n,
-                                                                      int edge_arg, const unsigned long long* __restrict__ col_part, int chunks,
-                                                                      const unsigned long long* __restrict__ row_part,
-                                                                      const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc,
-                                                                      bool has_ignore, unsigned col_offset,
-                                                                      float pos_thr, float neg_lo, float neg_hi, float min_pos,
-                                                                      int low_quality, int assign_all,
-                                                                      const int64_t* __restrict__ gt_labels,
-                                                                      float* __restrict__ max_ov, int64_t* __restrict__ argmax_ov,
-                                                                      float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax,
-                                                                      int64_t* __restrict__ gt_inds, int64_t* __restrict__ labels) {
+__device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict__ b1, int k, const float* __restrict__ b2, int n, int edge_arg,
+                                                         const unsigned long long* __restrict__ col_part, int chunks,
+                                                         const unsigned long long* __restrict__ row_part,
+                                                         const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc,
+                                                         const int64_t stride, bool has_ignore, unsigned col_offset, float pos_thr,
+                                                         float neg_lo, float neg_hi, float min_pos, int low_quality, int assign_all,
+                                                         float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax, const int tile,
+                                                         const int tiles, float& m_out, int64_t& am_out) {
     const int edge = ARC ? (int)EDGE_ARC : edge_arg;
     const int lane = threadIdx.x & 63;
-    const int tile = blockIdx.x, tiles = gridDim.x;
     const int jraw = tile * kBlock + threadIdx.x;
     const bool valid = jraw < n;
     const int j = valid ? jraw : n - 1;
     const unsigned long long fl = row_floor(has_ignore, col_offset);
     auto row_key_of = [&](int i) -> unsigned long long {
-        if (FROM_ACC) { const unsigned long long a = row_acc[i * acc_stride(k)]; return (a > fl ? a : fl) & ~1ull; }
+        if (FROM_ACC) { const unsigned long long a = row_acc[i * stride]; return (a > fl ? a : fl) & ~1ull; }
         return key_from_signed(gt_keys[i]);
     };
     if (tile == 0 && gt_max) {   // the per-GT results, decoded once
@@ -486,31 +502,217 @@ __global__ __launch_bounds__(kBlock) void assign_fused_finalize_kernel(const flo
         }
         if (best >= 0) a = best + 1;
     }
-    if (valid) {
+    m_out = m;
+    am_out = am;
+    return a;
+}
+// Arrival of one finalize workgroup at the two-level counters behind the accumulators (a returning atomic per workgroup on ONE
+// address serialises): the last of each group of 32 tiles reports to the top counter; true (for the whole workgroup) in the
+// last workgroup of the last group to report.  counters[0]: top, [1 + g]: group g, kAccLine words apart.  `extra` (thread 0's)
+// is added to the first atomic: a caller passes 0 made to depend on an earlier returning atomic, which orders the two.
+__device__ __forceinline__ bool finalize_arrive(unsigned long long* __restrict__ counters, const int tile, const int tiles, const unsigned extra = 0u) {
+    __shared__ unsigned ticket;
+    const int groups = (int)ticket_groups(tiles), grp = tile / kTicketGroup;
+    const int members = grp == groups - 1 ? tiles - grp * kTicketGroup : kTicketGroup;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = __hip_atomic_fetch_add((unsigned*)(counters + (int64_t)(1 + grp) * kAccLine), 1u + extra, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned last = 0;
+        if ((int)t == members - 1)
+            last = (int)__hip_atomic_fetch_add((unsigned*)counters, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1;
+        ticket = last;
+    }
+    __syncthreads();
+    return ticket != 0;
+}
+template <int VARIANT, int DIM, bool ARC, bool FROM_ACC>
+__global__ __launch_bounds__(kBlock) void assign_fused_finalize_kernel(const float* __restrict__ b1, int k, const float* __restrict__ b2, int n,
+                                                                      int edge_arg, const unsigned long long* __restrict__ col_part, int chunks,
+                                                                      const unsigned long long* __restrict__ row_part,
+                                                                      const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc,
+                                                                      bool has_ignore, unsigned col_offset,
+                                                                      float pos_thr, float neg_lo, float neg_hi, float min_pos,
+                                                                      int low_quality, int assign_all,
+                                                                      const int64_t* __restrict__ gt_labels,
+                                                                      float* __restrict__ max_ov, int64_t* __restrict__ argmax_ov,
+                                                                      float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax,
+                                                                      int64_t* __restrict__ gt_inds, int64_t* __restrict__ labels) {
+    const int tile = blockIdx.x, tiles = gridDim.x;
+    const int j = tile * kBlock + threadIdx.x;
+    float m;
+    int64_t am;
+    const int64_t a = fused_finalize_column<VARIANT, DIM, ARC, FROM_ACC>(b1, k, b2, n, edge_arg, col_part, chunks, row_part, gt_keys, row_acc,
+                                                                         acc_stride(k), has_ignore, col_offset, pos_thr, neg_lo, neg_hi, min_pos,
+                                                                         low_quality, assign_all, gt_max, gt_argmax, tile, tiles, m, am);
+    if (j < n) {
         max_ov[j] = m;
         if (argmax_ov) argmax_ov[j] = am;
         gt_inds[j] = a;
         if (labels) labels[j] = a > 0 ? gt_labels[a - 1] : -1;
     }
-    if (FROM_ACC) {   // every read of the accumulators above has returned (its value was used); the last arrival cleans up.
-        // Two levels of arrival counters (a returning atomic per workgroup on ONE address serialises): the last of each group of
-        // 32 tiles reports to the top counter, the last group to report zeroes the accumulators and every counter.
-        __shared__ unsigned ticket;
-        unsigned long long* counters = row_acc + acc_words(k);   // [0]: top, [1 + g]: group g, kAccLine words apart
-        const int groups = (int)ticket_groups(tiles), grp = tile / kTicketGroup;
-        const int members = grp == groups - 1 ? tiles - grp * kTicketGroup : kTicketGroup;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned t = __hip_atomic_fetch_add((unsigned*)(counters + (int64_t)(1 + grp) * kAccLine), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            unsigned last = 0;
-            if ((int)t == members - 1)
-                last = (int)__hip_atomic_fetch_add((unsigned*)counters, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1;
-            ticket = last;
-        }
-        __syncthreads();
-        if (ticket) {
+    if (FROM_ACC) {   // every read of the accumulators above has returned (its value was used); the last arrival zeroes them and
+        // every counter for the next call
+        unsigned long long* counters = row_acc + acc_words(k);
+        if (finalize_arrive(counters, tile, tiles)) {
             for (int i = threadIdx.x; i < k; i += kBlock) row_acc[i * acc_stride(k)] = 0ull;
-            for (int i = threadIdx.x; i <= groups; i += kBlock) counters[(int64_t)i * kAccLine] = 0ull;
+            for (int i = threadIdx.x; i <= (int)ticket_groups(tiles); i += kBlock) counters[(int64_t)i * kAccLine] = 0ull;
+        }
+    }
+}
+
+
+// ---- anchor targets for a minibatch (sph2pob_anchor_targets_f32): the fused assigner with the image as a grid dimension and
+// the target construction of mmdet's AnchorHead._get_targets_single (anchor_head.py:254-285, PseudoSampler) as the finalize
+// pass's epilogue.  Two launches for B images; every image owns a slice of the workspace and of the state, laid out for k_max
+// rows whatever its own count. ----
+// per-image workspace: col_part[chunks_max][n] then row_part[k_max][tiles]; per-image state: the single-image layout for k_max
+// rows (accumulators, 1 + groups arrival counters) + one line for the packed (positives | negatives << 32) count; behind the
+// last image one line: [0] images that finished, [1] sum of max(positives, 1)
+struct BatchLayout { int64_t ws_words, col_words, state_words, acc, chunks_max, tiles; };
+__host__ __device__ inline BatchLayout batch_layout(int64_t k_max, int64_t n, int64_t rpw) {
+    BatchLayout l;
+    l.tiles = (n + kBlock - 1) / kBlock;
+    l.chunks_max = k_max > 0 ? (k_max + rpw - 1) / rpw : 0;
+    l.col_words = l.chunks_max * n;
+    l.ws_words = l.col_words + k_max * l.tiles;
+    l.acc = acc_words(k_max);
+    l.state_words = l.acc + (2 + ticket_groups(l.tiles)) * kAccLine;
+    return l;
+}
+// rows of image b in the concatenated GT: offsets clamped to [0, K], the count to [0, k_max] (later rows are not assigned)
+struct ImageRows { int64_t lo; int k; };
+__device__ __forceinline__ ImageRows image_rows(const int64_t* __restrict__ gt_offsets, int b, int64_t K, int k_max) {
+    int64_t lo = gt_offsets[b], hi = gt_offsets[b + 1];
+    lo = lo < 0 ? 0 : (lo > K ? K : lo);
+    hi = hi < 0 ? 0 : (hi > K ? K : hi);
+    const int64_t k = hi - lo;
+    return ImageRows{lo, k < 0 ? 0 : (k > k_max ? k_max : (int)k)};
+}
+// an image's rows in chunks of equal size, at most rows_per_wg each
+__device__ __forceinline__ int image_chunks(int k, int rows_per_wg) { return (k + rows_per_wg - 1) / rows_per_wg; }
+
+// grid (tiles, chunks_max, B): per image the tail-first order of iou_pairwise_compact_kernel; workgroups past the image's own
+// chunks (all of them for an image without GT) exit at once
+template <int VARIANT, int DIM, bool ARC>
+__global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void anchor_targets_pairwise_kernel(const float* __restrict__ gt, const int64_t* __restrict__ gt_offsets,
+                                                                                  int64_t K, int k_max, const float* __restrict__ anchors, int n,
+                                                                                  int edge_arg, int rows_per_wg,
+                                                                                  unsigned long long* __restrict__ workspace,
+                                                                                  unsigned long long* __restrict__ state) {
+    const int b = blockIdx.z;
+    const unsigned lid = blockIdx.y * gridDim.x + blockIdx.x;
+    const int bx = (int)(gridDim.x - 1 - lid / gridDim.y), by = (int)(lid % gridDim.y);
+    const ImageRows im = image_rows(gt_offsets, b, K, k_max);
+    const int chunks = image_chunks(im.k, rows_per_wg);
+    if (by >= chunks) return;
+    const BatchLayout l = batch_layout(k_max, n, rows_per_wg);
+    unsigned long long* col_part = workspace + b * l.ws_words;
+    pairwise_compact_tile<VARIANT, DIM, ARC, 2>(gt + im.lo * DIM, im.k, anchors, n, nullptr, (int)MODE_IOU, edge_arg, (im.k + chunks - 1) / chunks,
+                                                nullptr, col_part, col_part + l.col_words, 0u, state + b * l.state_words, bx, by, (int)l.tiles,
+                                                acc_stride(k_max));
+}
+
+struct TargetOut {
+    int64_t* gt_inds; float* max_ov; int64_t* assigned_labels; int64_t* labels; float* label_weights; float* bbox_targets;
+    float* bbox_weights; int64_t* num_pos; int64_t* num_neg; float* avg_factor;
+};
+// grid (tiles, B).  The targets of column j of image b from its assigned index a (g > 0 positive, 0 negative, -1 neither):
+//   labels gt_labels[a - 1] (0 without labels) | num_classes; label_weights 1 (pos_weight on positives when > 0) | 0 for -1;
+//   bbox_targets the GT box, or its deltas w.r.t. the anchor (ENCODE: sph2pob_coder::encode_one, the coder kernel's function)
+//   | 0; bbox_weights 1 | 0.
+// Counts: one ballot per wave into LDS, one packed atomic per workgroup into the image's state line; the image's last
+// workgroup writes num_pos / num_neg and adds max(num_pos, 1) to the batch's sum, the batch's last image writes avg_factor.
+// Each of these atomics returns before the arrival that publishes it is issued (finalize_arrive's `extra`).
+template <int VARIANT, int DIM, bool ARC, bool ENCODE>
+__global__ __launch_bounds__(kBlock) void anchor_targets_finalize_kernel(const float* __restrict__ gt, const int64_t* __restrict__ gt_labels,
+                                                                        const int64_t* __restrict__ gt_offsets, int64_t K, int k_max,
+                                                                        const float* __restrict__ anchors, int n, int edge_arg, int rows_per_wg,
+                                                                        unsigned long long* __restrict__ workspace,
+                                                                        unsigned long long* __restrict__ state, float pos_thr, float neg_lo,
+                                                                        float neg_hi, float min_pos, int low_quality, int assign_all,
+                                                                        int64_t num_classes, float pos_weight, sph2pob_coder::Norm nm, TargetOut o) {
+    __shared__ unsigned wg_count[2];
+    const int tile = blockIdx.x, tiles = gridDim.x, b = blockIdx.y, images = gridDim.y;
+    const ImageRows im = image_rows(gt_offsets, b, K, k_max);
+    const BatchLayout l = batch_layout(k_max, n, rows_per_wg);
+    const float* gt_b = gt + im.lo * DIM;
+    unsigned long long* acc = state + b * l.state_words;
+    if (threadIdx.x < 2) wg_count[threadIdx.x] = 0u;
+    float m = 0.0f;
+    int64_t am = 0, a = 0;   // an image without GT: every anchor is background (max_iou_assigner.py:148-165)
+    if (im.k > 0) {
+        const unsigned long long* col_part = workspace + b * l.ws_words;
+        a = fused_finalize_column<VARIANT, DIM, ARC, true>(gt_b, im.k, anchors, n, edge_arg, col_part, image_chunks(im.k, rows_per_wg),
+                                                           col_part + l.col_words, nullptr, acc, acc_stride(k_max), false, 0u, pos_thr, neg_lo,
+                                                           neg_hi, min_pos, low_quality, assign_all, nullptr, nullptr, tile, tiles, m, am);
+    }
+    const int j = tile * kBlock + threadIdx.x;
+    const bool valid = j < n, pos = valid && a > 0, neg = valid && a == 0;
+    if (valid) {
+        const int64_t e = (int64_t)b * n + j;
+        const int64_t lab = (pos && gt_labels) ? gt_labels[im.lo + a - 1] : 0;
+        o.gt_inds[e] = a;
+        o.max_ov[e] = m;
+        if (o.assigned_labels) o.assigned_labels[e] = pos ? lab : -1;
+        o.labels[e] = pos ? lab : num_classes;
+        o.label_weights[e] = pos ? (pos_weight <= 0.0f ? 1.0f : pos_weight) : (neg ? 1.0f : 0.0f);
+        float t[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (pos) {
+            float g[5];
+            load_box<DIM>(gt_b, a - 1, g);
+            if constexpr (ENCODE) {
+                float p[5];
+                load_box<DIM>(anchors, j, p);
+                sph2pob_coder::encode_one<DIM>(p, g, nm, t);
+            } else {
+#pragma unroll
+                for (int c = 0; c < DIM; c++) t[c] = g[c];
+            }
+        }
+        const float w = pos ? 1.0f : 0.0f;
+        if constexpr (DIM == 4) {   // one 16-byte store per row
+            reinterpret_cast<float4*>(o.bbox_targets)[e] = make_float4(t[0], t[1], t[2], t[3]);
+            reinterpret_cast<float4*>(o.bbox_weights)[e] = make_float4(w, w, w, w);
+        } else {
+#pragma unroll
+            for (int c = 0; c < DIM; c++) { o.bbox_targets[e * DIM + c] = t[c]; o.bbox_weights[e * DIM + c] = w; }
+        }
+    }
+    __syncthreads();   // wg_count is zero
+    const unsigned long long mp = __builtin_amdgcn_ballot_w64(pos), mn = __builtin_amdgcn_ballot_w64(neg);
+    if ((threadIdx.x & 63) == 0) {
+        if (mp) atomicAdd(&wg_count[0], (unsigned)__popcll(mp));
+        if (mn) atomicAdd(&wg_count[1], (unsigned)__popcll(mn));
+    }
+    __syncthreads();
+    unsigned long long* counters = acc + l.acc;
+    unsigned long long* count = counters + (1 + ticket_groups(tiles)) * kAccLine;
+    unsigned dep = 0u;
+    if (threadIdx.x == 0) {
+        const unsigned long long prev = __hip_atomic_fetch_add(count, (unsigned long long)wg_count[0] | ((unsigned long long)wg_count[1] << 32),
+                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("" : "+v"(dep) : "v"(prev));   // dep stays 0, and is not known before the count's atomic has returned
+    }
+    if (finalize_arrive(counters, tile, tiles, dep)) {   // the image's last workgroup: its state back to zero, its counts out
+        for (int i = threadIdx.x; i < im.k; i += kBlock) acc[i * acc_stride(k_max)] = 0ull;
+        for (int i = threadIdx.x; i <= (int)ticket_groups(tiles); i += kBlock) counters[(int64_t)i * kAccLine] = 0ull;
+        if (threadIdx.x == 0) {
+            const unsigned long long c = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(count, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned np = (unsigned)c;
+            o.num_pos[b] = (int64_t)np;
+            o.num_neg[b] = (int64_t)(unsigned)(c >> 32);
+            unsigned long long* batch = state + images * l.state_words;
+            const unsigned long long prev = __hip_atomic_fetch_add(batch + 1, (unsigned long long)(np > 0u ? np : 1u), __ATOMIC_RELAXED,
+                                                                   __HIP_MEMORY_SCOPE_AGENT);
+            unsigned d2 = 0u;
+            asm volatile("" : "+v"(d2) : "v"(prev));
+            const unsigned done = __hip_atomic_fetch_add((unsigned*)batch, 1u + d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((int)done == images - 1) {
+                *o.avg_factor = (float)__hip_atomic_load(batch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(batch, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(batch + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     }
 }
@@ -581,6 +783,42 @@ static AssignWs assign_ws(void* workspace, void* state, int64_t k, int64_t n) {
     w.row_part = w.col_part + w.chunks * n;
     return w;
 }
+// the batched form: rows per workgroup from the rows the whole batch can hold (an image has at most k_max, the batch K)
+static int64_t batch_rows_per_wg(int64_t images, int64_t K, int64_t k_max, int64_t n) {
+    const int64_t total = images * k_max < K ? images * k_max : K;
+    int64_t rpw = pairwise_rows_per_wg(total, n);
+    return rpw > k_max ? k_max : rpw;
+}
+struct AnchorTargetsLaunch {
+    const float* anchors; int64_t n; const float* gt; const int64_t* gt_labels; const int64_t* gt_offsets; int64_t images, K, k_max; int edge;
+    float pos, neg_lo, neg_hi, min_pos; int low_quality, assign_all; int64_t num_classes; float pos_weight; bool encode; sph2pob_coder::Norm nm;
+    TargetOut o; void* workspace; void* state; hipStream_t s; bool fast = true;
+    template <int V, int D> int run() {
+        if constexpr (V >= 2) return SPH2POB_ERR_OPTION;
+        else {
+            if (!fast) return SPH2POB_ERR_OPTION;
+            const int64_t rpw = k_max > 0 ? batch_rows_per_wg(images, K, k_max, n) : 1;
+            const BatchLayout l = batch_layout(k_max, n, rpw);
+            unsigned long long *ws = (unsigned long long*)workspace, *st = (unsigned long long*)state;
+            const bool arc = edge == SPH2POB_EDGE_ARC;
+            if (k_max > 0) {
+                dim3 grid((unsigned)l.tiles, (unsigned)l.chunks_max, (unsigned)images);
+#define SPH_AT(ARC) hipLaunchKernelGGL((anchor_targets_pairwise_kernel<V, D, ARC>), grid, dim3(kBlock), 0, s, gt, gt_offsets, K, (int)k_max, anchors, \
+                                       (int)n, edge, (int)rpw, ws, st)
+                if (arc) SPH_AT(true); else SPH_AT(false);
+#undef SPH_AT
+            }
+            dim3 grid((unsigned)l.tiles, (unsigned)images);
+#define SPH_AT(ARC, ENC) hipLaunchKernelGGL((anchor_targets_finalize_kernel<V, D, ARC, ENC>), grid, dim3(kBlock), 0, s, gt, gt_labels, gt_offsets, K, \
+                                            (int)k_max, anchors, (int)n, edge, (int)rpw, ws, st, pos, neg_lo, neg_hi, min_pos, low_quality, assign_all,  \
+                                            num_classes, pos_weight, nm, o)
+            if (arc) { if (encode) SPH_AT(true, true); else SPH_AT(true, false); }
+            else { if (encode) SPH_AT(false, true); else SPH_AT(false, false); }
+#undef SPH_AT
+            return launch_status();
+        }
+    }
+};
 struct AssignReduceLaunch {
     const float* b1; int64_t m; const float* b2; int64_t n; float* out; int edge; const unsigned char* ignore; unsigned col_offset;
     long long* gt_keys /* NULL: leave the keys in the accumulators */; void* workspace; void* state; hipStream_t s; bool fast = true;
@@ -732,5 +970,38 @@ int sph2pob_iou_assign_f32(const float* gt, int64_t k, const float* boxes, int64
                                          gt_max_overlaps, gt_argmax_overlaps, assigned_gt_inds, assigned_labels, workspace, state,
                                          (hipStream_t)stream});
 }
+
+int64_t sph2pob_anchor_targets_workspace_bytes(int64_t num_images, int64_t num_gt, int64_t k_max, int64_t n) {
+    if (num_images <= 0 || num_gt <= 0 || k_max <= 0 || n <= 0) return 0;
+    return num_images * batch_layout(k_max, n, batch_rows_per_wg(num_images, num_gt, k_max, n)).ws_words * 8;
+}
+int64_t sph2pob_anchor_targets_state_bytes(int64_t num_images, int64_t k_max, int64_t n) {
+    if (num_images <= 0 || k_max < 0 || n <= 0) return 0;
+    return (num_images * batch_layout(k_max, n, 1).state_words + kAccLine) * 8;
+}
+
+int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
+                               int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
+                               float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
+                               int64_t num_classes, float pos_weight, int encode, const float* means_host, const float* stds_host,
+                               int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
+                               float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
+                               float* avg_factor, void* workspace, void* state, void* stream) {
+    int rc = check_common(box_dim, variant, edge, 0);
+    if (rc) return rc;
+    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT || (variant & SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
+    if (num_images <= 0 || num_images > 65535 || num_gt < 0 || k_max < 0 || k_max > num_gt || k_max > (int64_t)65535 * 4 || n <= 0 ||
+        n >= ((int64_t)1 << 31) - kBlock || num_gt > kMaxElems)
+        return SPH2POB_ERR_SIZE;
+    if (!anchors || !gt_offsets || (num_gt > 0 && !gt) || (k_max > 0 && !workspace) || !state || !assigned_gt_inds || !max_overlaps ||
+        (assigned_labels && !gt_labels && num_gt > 0) || !labels || !label_weights || !bbox_targets || !bbox_weights || !num_pos || !num_neg || !avg_factor)
+        return SPH2POB_ERR_NULL;
+    const TargetOut o{assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg, avg_factor};
+    return dispatch(variant, box_dim,
+                    AnchorTargetsLaunch{anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt, k_max, edge, pos_iou_thr, neg_iou_lo, neg_iou_hi,
+                                        min_pos_iou, match_low_quality, gt_max_assign_all, num_classes, pos_weight, encode != 0,
+                                        sph2pob_coder::make_norm(means_host, stds_host, box_dim), o, workspace, state, (hipStream_t)stream});
+}
+
 
 }  // extern "C"

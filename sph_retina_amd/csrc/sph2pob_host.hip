@@ -549,6 +549,72 @@ int sph2pob_assign_f32_cpu(const float* ov, int64_t k, int64_t n, float pos_iou_
     return SPH2POB_OK;
 }
 
+
+// ---- anchor targets for a minibatch: sph2pob_anchor_targets_f32 (a loop over the images on the two twins above, then the
+// target table of include/sph2pob_hip.h; workspace and state are not used) ----
+int sph2pob_anchor_targets_f32_cpu(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
+                                   int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
+                                   float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
+                                   int64_t num_classes, float pos_weight, int encode, const float* means_host, const float* stds_host,
+                                   int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
+                                   float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
+                                   float* avg_factor, void* workspace, void* state, void*) {
+    (void)workspace; (void)state;
+    int rc = check_common(box_dim, variant, edge, 0);
+    if (rc) return rc;
+    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT || (variant & SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
+    if (num_images <= 0 || num_images > 65535 || num_gt < 0 || k_max < 0 || k_max > num_gt || k_max > (int64_t)65535 * 4 || n <= 0 ||
+        n >= ((int64_t)1 << 31) - 256 || num_gt > kMaxElems)
+        return SPH2POB_ERR_SIZE;
+    if (!anchors || !gt_offsets || (num_gt > 0 && !gt) || !assigned_gt_inds || !max_overlaps || (assigned_labels && !gt_labels && num_gt > 0) || !labels ||
+        !label_weights || !bbox_targets || !bbox_weights || !num_pos || !num_neg || !avg_factor)
+        return SPH2POB_ERR_NULL;
+    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
+    const int dim = box_dim;
+    std::vector<float> ov, gt_max;
+    std::vector<int64_t> argmax(n), gt_argmax;
+    int64_t total = 0;
+    for (int64_t b = 0; b < num_images; b++) {
+        const int64_t lo = std::min(std::max<int64_t>(gt_offsets[b], 0), num_gt), hi = std::min(std::max<int64_t>(gt_offsets[b + 1], 0), num_gt);
+        const int64_t k = std::min(std::max<int64_t>(hi - lo, 0), k_max);
+        int64_t* gi = assigned_gt_inds + b * n;
+        float* mo = max_overlaps + b * n;
+        const float* gt_b = gt + lo * dim;
+        if (k == 0) {   // every anchor is background (max_iou_assigner.py:148-165)
+            for (int64_t j = 0; j < n; j++) { gi[j] = 0; mo[j] = 0.0f; }
+            if (assigned_labels) std::fill(assigned_labels + b * n, assigned_labels + (b + 1) * n, (int64_t)-1);
+        } else {
+            ov.resize(k * n); gt_max.resize(k); gt_argmax.resize(k);
+            rc = sph2pob_iou_pairwise_f32_cpu(gt_b, k, anchors, n, ov.data(), box_dim, variant, SPH2POB_MODE_IOU, edge, SPH2POB_ANGLE_EQUATOR, nullptr);
+            if (!rc)
+                rc = sph2pob_assign_f32_cpu(ov.data(), k, n, pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all,
+                                            gt_labels ? gt_labels + lo : nullptr, mo, argmax.data(), gt_max.data(), gt_argmax.data(), gi,
+                                            assigned_labels ? assigned_labels + b * n : nullptr, nullptr, nullptr);
+            if (rc) return rc;
+        }
+        int64_t np = 0, nn = 0;
+        for (int64_t j = 0; j < n; j++) {
+            const int64_t a = gi[j], e = b * n + j;
+            const bool pos = a > 0;
+            np += pos; nn += a == 0;
+            labels[e] = pos ? (gt_labels ? gt_labels[lo + a - 1] : 0) : num_classes;
+            label_weights[e] = pos ? (pos_weight <= 0.0f ? 1.0f : pos_weight) : (a == 0 ? 1.0f : 0.0f);
+            float t[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            if (pos) {
+                const float* g = gt_b + (a - 1) * dim;
+                if (!encode) for (int c = 0; c < dim; c++) t[c] = g[c];
+                else if (dim == 4) sph2pob_coder::encode_one<4>(anchors + j * 4, g, nm, t);
+                else sph2pob_coder::encode_one<5>(anchors + j * 5, g, nm, t);
+            }
+            for (int c = 0; c < dim; c++) { bbox_targets[e * dim + c] = t[c]; bbox_weights[e * dim + c] = pos ? 1.0f : 0.0f; }
+        }
+        num_pos[b] = np; num_neg[b] = nn;
+        total += std::max<int64_t>(np, 1);
+    }
+    *avg_factor = (float)total;
+    return SPH2POB_OK;
+}
+
 }  // extern "C"
 
 // ---- box coders and the OBB L1 loss body (sph2pob_coder.hpp: the rows the kernels of sph2pob_coder.hip compute) ----

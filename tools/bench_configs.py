@@ -253,6 +253,74 @@ def config4(h=512, w=1024):
             'nms_5000x37cls_c_abi_ms': t_nms_abi * 1e3, 'nms_5000_single_class_c_abi_ms': t_nms1_abi * 1e3, 'roofline': roof}
 
 
+def config4_batch(images=8, num_gt=64, h=512, w=1024, rounds=7):
+    """Anchor targets for a minibatch (sph2pob_anchor_targets_f32) against the per-image loop it replaces, through the C ABI
+    with every buffer allocated once: (a) the batched entry, two launches for all images; (b) `images` calls of
+    sph2pob_iou_assign_f32 on the same data; (c) = (b) + the torch target construction of tools/demo_hot_path.py's
+    single-image step per image (boolean-mask indexing and int(pos.sum()): host synchronisations).  The three are timed in
+    alternation `rounds` times in this one process; the spread of (b) over the rounds is the yardstick for (a) <= (b)."""
+    from sph_retina_amd import _lib, _torch_glue as G
+    lib = _lib.lib()
+    anchors = retina_anchors(h, w)
+    n, K = anchors.size(0), images * num_gt
+    g = torch.Generator().manual_seed(0)
+    u = torch.rand((K, 4), generator=g)
+    gt = torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85], 1).cuda()
+    labels = torch.randint(0, 37, (K,), generator=g).cuda()
+    off = (torch.arange(images + 1) * num_gt).cuda()
+    st = G.raw_stream_of(gt.device)
+    i64, f32 = dict(dtype=torch.int64, device='cuda'), dict(dtype=torch.float32, device='cuda')
+    o = [torch.empty((images, n), **i64), torch.empty((images, n), **f32), torch.empty((images, n), **i64), torch.empty((images, n), **i64),
+         torch.empty((images, n), **f32), torch.empty((images, n, 4), **f32), torch.empty((images, n, 4), **f32), torch.empty(images, **i64),
+         torch.empty(images, **i64), torch.empty(1, **f32)]
+    op = [G.ptr(t) for t in o]
+    wsb = torch.empty(lib.sph2pob_anchor_targets_workspace_bytes(images, K, num_gt, n) // 8, **i64)
+    stb = torch.zeros(lib.sph2pob_anchor_targets_state_bytes(images, num_gt, n) // 8, **i64)
+    ws1 = torch.empty(lib.sph2pob_iou_assign_workspace_bytes(num_gt, n) // 8, **i64)
+    st1 = torch.zeros(lib.sph2pob_iou_assign_state_bytes(num_gt, n) // 8, **i64)
+    mo, gi, lab = torch.empty((images, n), **f32), torch.empty((images, n), **i64), torch.empty((images, n), **i64)
+    import ctypes
+    cf = [ctypes.c_float(v) for v in (0.5, 0.0, 0.4, 0.0, -1.0)]
+
+    def batched():
+        rc = lib.sph2pob_anchor_targets_f32(G.ptr(anchors), n, G.ptr(gt), G.ptr(labels), G.ptr(off), images, K, num_gt, 4, 0, 0, cf[0], cf[1],
+                                            cf[2], cf[3], 1, 1, 37, cf[4], 0, None, None, *op, G.ptr(wsb), G.ptr(stb), st)
+        assert rc == 0, rc
+
+    def loop():
+        for b in range(images):
+            lib.sph2pob_iou_assign_f32(G.ptr(gt[b * num_gt:]), num_gt, G.ptr(anchors), n, 4, 0, 0, None, None, 0.5, 0.0, 0.4, 0.0, 1, 1,
+                                       G.ptr(labels[b * num_gt:]), G.ptr(mo[b]), None, None, None, G.ptr(gi[b]), G.ptr(lab[b]), G.ptr(ws1),
+                                       G.ptr(st1), st)
+
+    def loop_targets():
+        loop()
+        total = 0
+        for b in range(images):
+            pos = gi[b] > 0
+            total += max(int(pos.sum()), 1)
+            bbox_targets = torch.zeros_like(anchors)
+            bbox_weights = torch.zeros_like(anchors)
+            bbox_targets[pos] = gt[b * num_gt:(b + 1) * num_gt][gi[b][pos] - 1]
+            bbox_weights[pos] = 1.0
+        return total
+    batched(), loop()
+    torch.cuda.synchronize()
+    assert torch.equal(o[0], gi) and torch.equal(o[1], mo) and torch.equal(o[2], lab), 'batched and per-image assignments differ'
+    assert float(o[9]) == float(loop_targets())
+    ta, tb, tc = [], [], []
+    for _ in range(rounds):
+        ta.append(timeit(batched, reps=200) * 1e6)
+        tb.append(timeit(loop, reps=200) * 1e6)
+        tc.append(timeit(loop_targets, reps=20) * 1e6)
+    med = lambda v: float(np.median(v))
+    return {'config': 'anchor targets: %d images x %d GT x %d anchors (%dx%d ERP grid), C ABI' % (images, num_gt, n, h, w),
+            'a_batched_us': med(ta), 'b_loop_assign_us': med(tb), 'c_loop_assign_plus_torch_targets_us': med(tc),
+            'a_rounds_us': ta, 'b_rounds_us': tb, 'c_rounds_us': tc, 'b_spread_us': max(tb) - min(tb),
+            'a_over_b': med(ta) / med(tb), 'a_over_c': med(ta) / med(tc), 'num_pos': o[7].tolist(),
+            'note': '(a) also writes labels, label_weights, bbox_targets, bbox_weights and the counts, which (b) does not'}
+
+
 def coder(n=1_000_000):
     """§8f-2: decode (the op in front of loss_bbox) and encode on n RBFoV / BFoV boxes, via the C ABI."""
     import ctypes
@@ -388,8 +456,8 @@ def gaussian(n=1_000_000):
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 gaussian config4 config4b coder unbiased variants; none = all)
-    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)

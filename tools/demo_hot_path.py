@@ -7,6 +7,11 @@ strings it together (no network — the regression deltas are a leaf tensor):
   inference  decode -> multiclass_nms(SphNMS)                              (_get_bboxes_single / test_cfg)
 
 Prints one JSON line with the stage times; `run()` is also used by tests/test_gpu_pipeline.py.
+
+`run()` is the single-image step and keeps the few torch lines of `_get_targets_single` between the assigner and the loss
+(boolean-mask indexing and `int(pos.sum())`: host synchronisations).  `run_batch()` is the minibatch step built on
+`sph_anchor_targets`: one call from the boxes to the loss's targets and a device `avg_factor`, no synchronisation — the
+sync-free one, and the one that captures into a hipGraph (tests/test_gpu_anchor_targets.py).
 """
 import json
 import math
@@ -96,8 +101,47 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
                      gt=gt, bbox_targets=bbox_targets)
 
 
+def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1):
+    """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
+    images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) with the device avg_factor -> backward."""
+    dev = 'cuda'
+    g = torch.Generator().manual_seed(seed)
+    anchors = retina_anchors()
+    n, images = anchors.size(0), len(counts)
+    gts, labels = [], []
+    for k in counts:
+        u = torch.rand((k, 4), generator=g)
+        gts.append(torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85], 1).to(dev))
+        labels.append(torch.randint(0, num_classes, (k,), generator=g).to(dev))
+    assigner = S.SphMaxIoUAssigner(pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1,
+                                   iou_calculator=dict(type='SphOverlaps2D', backend=backend, box_version=4))
+    coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(1., 1., 1., 1.))
+    loss_bbox = S.Sph2PobIoULoss(mode='ciou', loss_weight=1.0)
+    deltas = (torch.randn((images * n, 4), generator=g) * 0.05).to(dev).requires_grad_(True)
+    rois = anchors.repeat(images, 1)
+
+    def step():
+        deltas.grad = None
+        t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=num_classes)
+        pred = coder.decode(rois, deltas)
+        loss = loss_bbox(pred, t.bbox_targets.reshape(-1, 4), t.bbox_weights.reshape(-1, 4), avg_factor=t.avg_factor)
+        loss.backward()
+        return loss.detach(), t
+    step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        loss, t = step()
+    torch.cuda.synchronize()
+    out = {'anchors': n, 'images': images, 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
+           'loss': float(loss), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()), 'backend': backend,
+           'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
+    return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels)
+
+
 if __name__ == '__main__':
     run()                                   # warm-up (lazy initialisation, workspace allocation)
     for backend, nms in (('sph2pob_standard_iou', 'sph2pob_efficient'), ('unbiased_iou', 'unbiased_iou'),
                          ('naive_iou', 'naive_iou')):
         print(json.dumps(run(backend=backend, nms_calculator=nms, reps=5)[0]), flush=True)
+    print(json.dumps(run_batch(reps=5)[0]), flush=True)
