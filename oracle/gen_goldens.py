@@ -483,6 +483,36 @@ def transform_bwd_only():
     save('transform_bwd_efficient', **{k: v for k, v in arrs.items() if k.startswith('efficient_project_')})
 
 
+def loss_regimes_only():
+    """tests/golden/loss_regimes.npz and loss_regimes_tiny.npz: the unmodified reference's Sph2PobIoULoss, fp32 on the CPU, on
+    the first golden_pairs(regime) pairs of every input regime of tests/test_loss_host.py (near, disjoint, contained, wide,
+    polar, seam, tiny, crossed, half; BFoV and RBFoV) and on its clamp-gate pairs (`<box>_gates_*`): pred, target, and per
+    mode the loss elements and the autograd gradients w.r.t. both.  The test module, which holds the generators, measures
+    these against f64 to derive its bounds; what is not finite here is stored as it came out."""
+    sys.path.insert(0, os.path.join(os.path.dirname(OUT)))
+    import test_loss_host as T
+    arrs = {}
+
+    def run(key, p, t):
+        arrs[key + 'pred'], arrs[key + 'target'] = torch.from_numpy(p.copy()), torch.from_numpy(t.copy())
+        for mode in T.MODES:
+            L = R.iou_loss.Sph2PobIoULoss(mode=mode, reduction='none')
+            pr, tg = arrs[key + 'pred'].clone().requires_grad_(True), arrs[key + 'target'].clone().requires_grad_(True)
+            el = L(pr, tg)
+            el.sum().backward()
+            arrs[key + 'loss_' + mode], arrs[key + 'gpred_' + mode], arrs[key + 'gtarget_' + mode] = el, pr.grad, tg.grad
+    for box in ('bfov', 'rbfov'):
+        for regime in T.regimes_of(box):
+            p, t = T.regime_pairs(regime, box)
+            m = T.golden_pairs(regime)
+            run(f'{box}_{regime}_', p[:m], t[:m])
+        p, t = T.gate_pairs(box)[:2]
+        run(box + '_gates_', p, t)
+    # two files, each below the size limit of a committed fixture
+    save('loss_regimes', **{k: v for k, v in arrs.items() if '_tiny_' not in k})
+    save('loss_regimes_tiny', **{k: v for k, v in arrs.items() if '_tiny_' in k})
+
+
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'transform_bwd':
         transform_bwd_only()
@@ -500,6 +530,8 @@ if __name__ == '__main__':
         assign_only()
     elif len(sys.argv) > 1 and sys.argv[1] == 'naive':
         naive_only()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'loss_regimes':
+        loss_regimes_only()
     else:
         main()
         approx_only()
@@ -510,3 +542,4 @@ if __name__ == '__main__':
         transform_bwd_only()
         assign_only()
         naive_only()
+        loss_regimes_only()

@@ -176,24 +176,62 @@ def sph2pob_iou_loss(pred, target, weight=None, avg_factor=None, mode='iou', eps
     return np.dtype(dtype).type(loss_weight) * weight_reduce_loss(el, weight, reduction, avg_factor)
 
 
-def loss_grad_fd(pred, target, mode='iou', eps=1e-6, h=1e-5):
+def loss_grad_fd(pred, target, mode='iou', eps=1e-6, h=1e-5, nthreads=1, return_smooth=False, freeze_alpha=False):
     """fp64 central finite differences of the per-pair loss element w.r.t. pred and target (degrees).
-    Independent check for the hand-derived HIP adjoint; only meaningful away from the kinks of the loss."""
-    pred = _np(pred, np.float64)
-    target = _np(target, np.float64)
+    Independent check for the hand-derived HIP adjoint; only meaningful away from the kinks of the loss.  With
+    ``return_smooth`` also a per-pair mask that is False where a kink lies inside the step: the one-sided slopes of some
+    input column disagree (beyond a curvature of 10 per square degree), or (CIoU) the f64 IoU is on different sides of 0.5
+    (the ``alpha`` gate) at -h, 0 and +h.
+    ``freeze_alpha`` (CIoU): the reference computes ``alpha`` under torch.no_grad (sph2pob_iou_loss.py:188-189), so what
+    its autograd differentiates is  diou + alpha * v  with alpha held at its value: the differences of the DIoU element
+    plus alpha times the differences of v, with v recovered from  ciou - diou = v^2 / (1 - iou + v + eps)."""
+    if freeze_alpha and mode == 'ciou':
+        pred, target = _np(pred, np.float64), _np(target, np.float64)
+        out = loss_grad_fd(pred, target, 'diou', eps, h, nthreads, return_smooth)
+
+        def v_of(p, t):
+            c, iou = loss_elements(p, t, 'ciou', eps, np.float64, nthreads, return_iou=True)
+            q = np.maximum(c - loss_elements(p, t, 'diou', eps, np.float64, nthreads), 0.0)
+            return 0.5 * (q + np.sqrt(q * q + 4.0 * q * (1.0 - iou + eps))), iou
+        v0, iou0 = v_of(pred, target)
+        alpha = (iou0 > 0.5) * v0 / (1.0 - iou0 + v0 + eps)
+        grads, smooth = [g.copy() for g in out[:2]], (out[2].copy() if return_smooth else None)
+        for arr, g in zip((pred.copy(), target.copy()), grads):
+            for k in range(arr.shape[1]):
+                args = lambda: (arr, target) if g is grads[0] else (pred, arr)   # noqa: E731
+                save = arr[:, k].copy()
+                arr[:, k] = save + h
+                vp, ip = v_of(*args())
+                arr[:, k] = save - h
+                vm, im = v_of(*args())
+                arr[:, k] = save
+                g[:, k] += alpha * (vp - vm) / (2 * h)
+                if return_smooth:
+                    smooth &= np.abs((vp - v0) - (v0 - vm)) < 1e-3 * np.abs(vp - vm) + 10.0 * h * h
+                    smooth &= ((ip > 0.5) == (iou0 > 0.5)) & ((im > 0.5) == (iou0 > 0.5))
+        return (grads[0], grads[1], smooth) if return_smooth else (grads[0], grads[1])
+    pred = _np(pred, np.float64).copy()
+    target = _np(target, np.float64).copy()
     n, dim = pred.shape
     gp = np.zeros_like(pred)
     gt = np.zeros_like(target)
+    smooth = np.ones(n, bool)
+    if return_smooth:
+        base, iou0 = loss_elements(pred, target, mode, eps, np.float64, nthreads, return_iou=True)
     for k in range(dim):
         for arr, g in ((pred, gp), (target, gt)):
             save = arr[:, k].copy()
             arr[:, k] = save + h
-            lp = loss_elements(pred, target, mode, eps, np.float64)
+            lp, ip = loss_elements(pred, target, mode, eps, np.float64, nthreads, return_iou=True)
             arr[:, k] = save - h
-            lm = loss_elements(pred, target, mode, eps, np.float64)
+            lm, im = loss_elements(pred, target, mode, eps, np.float64, nthreads, return_iou=True)
             arr[:, k] = save
             g[:, k] = (lp - lm) / (2 * h)
-    return gp, gt
+            if return_smooth:
+                smooth &= np.abs((lp - base) - (base - lm)) < 1e-3 * np.abs(lp - lm) + 10.0 * h * h
+                if mode == 'ciou':
+                    smooth &= ((ip > 0.5) == (iou0 > 0.5)) & ((im > 0.5) == (iou0 > 0.5))
+    return (gp, gt, smooth) if return_smooth else (gp, gt)
 
 
 def transform_vjp_fd(b1, b2, g1, g2, variant='standard', edge='arc', jitter=True, h=1e-5, angle='equator',

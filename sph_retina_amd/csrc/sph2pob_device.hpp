@@ -46,6 +46,11 @@ constexpr double kEpsS = 1e-4 * 1.2345678;              // spherical / rotated "
 constexpr double kEpsA = 1e-3 * 1.2345678;              // rotated angle eps
 constexpr float kClampHi = (float)(1 - 1e-7);           // 0.99999988
 constexpr float kClampLo = (float)(-1 + 1e-7);
+// The gradient gate of acos(clamp(cos a, -1 + 1e-7, 1 - 1e-7)): torch.clamp passes the gradient on the closed range, and
+// the bound 1 - 1e-7 is the cosine of 4.4721e-4.  From there up to acos(kClampHi) = 4.8828e-4 the fp32 cosine rounds onto
+// the bound: the VALUE of the angle is floored (as the reference's fp32 value is) while the gradient still passes (as in
+// the reference's autograd, and in f64).
+constexpr float kGateAng = 4.4721360e-4f;                // acos(1 - 1e-7)
 
 // clamp for NaN-free x: a single v_med3_f32 on the device
 SPH_DEV float clampf(float x, float lo, float hi) {

@@ -535,9 +535,8 @@ SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, Pl
         const bool fa = fabsf(sa) < kMinAng, fb = fabsf(sb) < kMinAng;
         if (SPH_SITE(1) ((with_coincident && SPH_ANY_LANE(coincident)) || SPH_ANY_LANE(fa) || SPH_ANY_LANE(fb))) {
             SPH_SITE_HIT(1);
-            bool fa2 = fa, fb2 = fb;
-            if (with_coincident) { fix_coincident(); fa2 = fabsf(sa) < kMinAng; fb2 = fabsf(sb) < kMinAng; }
-            if (GATES) { o.g_ag = !fa2; o.g_ap = !fb2; }
+            if (with_coincident) fix_coincident();
+            if (GATES) { o.g_ag = !(fabsf(sa) < kGateAng); o.g_ap = !(fabsf(sb) < kGateAng); }   // kGateAng < kMinAng
             angle_floor(ca, sa);
             angle_floor(cb, sb);
         } else if (GATES) { o.g_ag = true; o.g_ap = true; }

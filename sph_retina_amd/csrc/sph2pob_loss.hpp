@@ -110,9 +110,8 @@ SPH_DEV void loss_front_reference(const float (&b1)[5], const float (&b2)[5], Lo
         f.g_wp = tw >= (float)(kEpsA / 10);     f.g_hp = th >= (float)(kEpsA / 10);
         bool in_a = !(pa < (float)(-2 * pi + 2 * kEpsA) || pa > (float)(2 * pi - kEpsA));
         bool in_b = !(ta < (float)(-2 * pi + kEpsA) || ta > (float)(2 * pi - 2 * kEpsA));
-        // acos(clamp(., -1+1e-7, 1-1e-7)) of compute_internal_angle: zero gradient where the clamp is active
-        f.g_ag = in_a && fabsf(cosf(P0.a)) < kClampHi;
-        f.g_ap = in_b && fabsf(cosf(T0.a)) < kClampHi;
+        f.g_ag = in_a;
+        f.g_ap = in_b;
     }
     SBox g = load_sbox<DIM>(b1), p = load_sbox<DIM>(b2);
     f.sg = g.sp; f.cg = g.cp; f.sp = p.sp; f.cp = p.cp;
@@ -122,6 +121,13 @@ SPH_DEV void loss_front_reference(const float (&b1)[5], const float (&b2)[5], Lo
     float N = f.sp * f.cg * f.cD - f.cp * f.sg, D = -f.sp * f.sD;
     float C = f.cg * f.cp + f.sg * f.sp * f.cD;
     f.g_A = atan2f(sqrtf(N * N + D * D), C) > 2.0f * 4.8828125e-4f;
+    // acos(clamp(., -1+1e-7, 1-1e-7)) of compute_internal_angle: zero gradient where the clamp is active, i.e. where the
+    // planar angle BEFORE its floor is within kGateAng of 0 | pi.  P0.a / T0.a are already floored (to kMinAng, whose
+    // cosine is the clamp bound itself), so the angle is taken again from the bearings: a = atan2(N, D) - k * gamma
+    float Np = f.cg * f.sp - f.sg * f.cp * f.cD, Dp = -f.sg * f.sD;
+    const float kg = DIM == 5 ? b1[4] * kDeg2Rad : 0.0f, kp = DIM == 5 ? b2[4] * kDeg2Rad : 0.0f;
+    f.g_ag = f.g_ag && fabsf(sinf(atan2f(N, D) - kg)) >= kGateAng;
+    f.g_ap = f.g_ap && fabsf(sinf(atan2f(Np, Dp) - kp)) >= kGateAng;
 }
 
 }  // namespace sph2pob
