@@ -276,6 +276,47 @@ int sph2pob_batched_nms_f32(const float* boxes, const float* scores, const int64
                             void* stream);
 
 /*
+ * Detection post-processing for a whole minibatch: what SphRetinaHead._get_bboxes_single / _bbox_post_process
+ * (sphdet/models/heads/sph_retina_head.py:101-216, :22-99) compute per image and level — sigmoid, filter_scores_and_topk
+ * (mmdet/core/utils/misc.py:119-165), bbox_coder.decode, cat over the levels, SphNMS, [:max_per_img] — for B images as ten
+ * launches whatever B is, nothing read back to the host, nothing allocated: capturable into a hipGraph.
+ * Level tables are HOST arrays of num_levels <= 8 entries:
+ *   cls_scores   device pointers, level l either the head's NCHW (B, A C, H_l, W_l) or the flattened (B, n_l, C); read in
+ *                place.  The logical candidate index of (h, w, a, c) is the reference's ((h W + w) A + a) C + c
+ *   bbox_preds   device pointers, laid out like cls_scores: (B, A box_dim, H_l, W_l) or (B, n_l, box_dim)
+ *   anchors      device pointers, (n_l, box_dim), shared by the images
+ *   level_n      n_l = H_l W_l A anchors;  level_hw: H_l W_l for the NCHW layout, 0 for the flattened one
+ *   activation   0: cls_scores are probabilities; 1: logits, score = 1 / (1 + expf(-x)) in fp32 — the score a candidate is
+ *                selected on is the score it is reported with
+ * Per image and level: a candidate is valid iff score > score_thr (a NaN is dropped); the min(nms_pre, #valid) candidates that
+ * come first in (score descending, candidate index ascending) order — torch's stable descending sort — are kept, in that
+ * order; their boxes are decoded from their anchor and deltas with the arithmetic of sph2pob_coder_decode_f32 (means_host /
+ * stds_host / max_ratio / coder_flags / ctr_clamp as there).  The levels' candidates, concatenated, then go through exactly
+ * what sph2pob_batched_nms_f32 does for that image alone (per-class greedy NMS keeping iou <= iou_threshold, the first
+ * max_per_img in descending score order, ties by candidate position).
+ *   dets         (B, max_per_img, box_dim + 1) f32: box and score; rows from num_dets[b] on are 0
+ *   labels       (B, max_per_img) int64, -1 from num_dets[b] on
+ *   prior_inds   (B, max_per_img) int64: the detection's anchor as an index into the concatenated levels, -1 padded
+ *   num_dets     (B) int64
+ *   workspace    sph2pob_get_bboxes_workspace_bytes(level_n, num_levels, B, C, box_dim, nms_pre) bytes, no initialisation
+ *                (0 = the shapes are not accepted): histograms, one 8-byte survivor slot per score, the candidate blocks of
+ *                K_cap = sum_l min(nms_pre, n_l C) rows per image and B suppression matrices of K_cap^2 / 8 bytes
+ * Errors, checked in this order before anything is enqueued: box_dim -> SPH2POB_ERR_DIM; a variant other than STANDARD |
+ * EFFICIENT, SPH2POB_FLAG_REFERENCE_ORDER, activation, coder_flags, max_ratio < 0 -> SPH2POB_ERR_OPTION; num_levels outside
+ * [1, 8], B outside [1, 65 535], C outside [1, 262 144], nms_pre <= 0, max_per_img < 0 -> SPH2POB_ERR_SIZE; a NULL table ->
+ * SPH2POB_ERR_NULL; n_l < 1, n_l C >= 2^31 - 2^17, level_hw that does not divide n_l, K_cap > sph2pob_batched_nms_max_boxes()
+ * -> SPH2POB_ERR_SIZE; a NULL table entry, output or workspace -> SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_get_bboxes_workspace_bytes(const int64_t* level_n, int num_levels, int64_t num_images, int64_t num_classes,
+                                           int box_dim, int64_t nms_pre);
+int sph2pob_get_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors,
+                           const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                           int64_t num_classes, int box_dim, int activation, float score_thr, int64_t nms_pre,
+                           const float* means_host, const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp,
+                           int variant, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
+                           int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream);
+
+/*
  * MaxIoUAssigner epilogue on a (k, n) overlaps matrix (rows = GT, columns = boxes), SURVEY §8f-1.
  * Replaces assign_wrt_overlaps (mmdet/core/bbox/assigners/max_iou_assigner.py:135-220) for k > 0, n > 0:
  *   max_overlaps, argmax_overlaps       = overlaps.max(dim=0)   (:171)   first maximal index on ties

@@ -6,7 +6,7 @@ from .iou import (SphOverlaps2D, sph2pob_efficient_iou, sph2pob_legacy_iou, sph2
                   sph_overlaps)
 
 from .losses import Sph2PobIoULoss, SphIoULoss  # noqa: F401,E402
-from .bbox.nms import SphNMS, multiclass_nms  # noqa: F401,E402
+from .bbox.nms import DetBBoxes, SphNMS, multiclass_nms, sph_get_bboxes  # noqa: F401,E402
 from .bbox.assigners import AnchorTargets, SphMaxIoUAssigner, sph_anchor_targets  # noqa: F401,E402
 from .bbox.coder import DeltaXYWHASphBBoxCoder, DeltaXYWHSphBBoxCoder  # noqa: F401,E402
 

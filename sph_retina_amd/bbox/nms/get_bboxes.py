@@ -1,0 +1,149 @@
+"""Detection post-processing for a whole minibatch in one call, without a host synchronisation.
+
+`sph_get_bboxes` is what `SphRetinaHead._get_bboxes_single` -> `_bbox_post_process` compute per image
+(sphdet/models/heads/sph_retina_head.py:101-216, :22-99): per level sigmoid, `filter_scores_and_topk(score_thr, nms_pre)`
+(mmdet/core/utils/misc.py:119-165) and `bbox_coder.decode`, then cat over the levels, `SphNMS` and `[:max_per_img]` — from the
+head's raw per-level outputs for B images to padded, fixed-shape detections as ONE C-ABI call (`sph2pob_get_bboxes_f32`: ten
+launches whatever B is).  Nothing is read back and nothing is sized on the host, so inference can be captured into a hipGraph;
+the counts stay on the device (`num_dets`).
+
+The reference's unstable parts are pinned: the per-level order is (score descending, candidate index ascending) — a stable
+descending sort — and NMS ties go by candidate position, as `sph_batched_nms` has them here.
+
+The per-image API (`multiclass_nms`, or `filter` + `bbox_coder.decode` + `sph_batched_nms` on each image and level) keeps serving
+what this entry does not: score factors, softmax heads, `with_nms=False`, planar NMS, the unbiased / naive calculators, the
+reference arithmetic and more than 16 384 candidates per image.
+"""
+import ctypes
+import math
+
+import torch
+
+from ... import _lib
+from ... import _torch_glue as G
+from .sph_nms import _variant_of
+
+_PER_IMAGE = 'use the per-image API (per level: score filter, top-k and bbox_coder.decode; then sph_batched_nms / multiclass_nms on each image)'
+_MAX_LEVELS = 8
+
+
+class DetBBoxes:
+    """Result of `sph_get_bboxes`, B images, all tensors on the inputs' device:
+    dets (B, max_per_img, dim + 1) f32 = (box, score), rows from num_dets[b] on are zero; labels (B, max_per_img) int64, -1
+    padded; prior_inds (B, max_per_img) int64, the detection's anchor as an index into cat(mlvl_anchors), -1 padded;
+    num_dets (B,) int64."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    @property
+    def num_images(self):
+        return self.num_dets.size(0)
+
+    def to_list(self):
+        """[(det_bboxes (k_b, dim + 1), det_labels (k_b,))] per image: the reference's return.  Reads the counts: synchronises."""
+        return [(self.dets[b, :k], self.labels[b, :k]) for b, k in enumerate(self.num_dets.tolist())]
+
+
+def _level(t, name, per_anchor, n, images):
+    """(tensor, hw) of one level: hw = H W for the head's NCHW (B, A per_anchor, H, W), 0 for the flattened (B, n, per_anchor)."""
+    if t.dim() == 4:
+        hw = t.size(2) * t.size(3)
+        if t.size(0) != images or hw == 0 or t.size(1) * hw != n * per_anchor:
+            raise ValueError(f'{name}: expected (B, A * {per_anchor}, H, W) with H W A = {n} anchors and B = {images}, got {tuple(t.shape)}')
+    elif t.dim() == 3:
+        hw = 0
+        if tuple(t.shape) != (images, n, per_anchor):
+            raise ValueError(f'{name}: expected ({images}, {n}, {per_anchor}), got {tuple(t.shape)}')
+    else:
+        raise ValueError(f'{name}: expected (B, A * {per_anchor}, H, W) or (B, n, {per_anchor}), got {tuple(t.shape)}')
+    return G.as_f32_nograd(t), hw
+
+
+def sph_get_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, score_thr=0.05, nms_pre=1000, nms=None, max_per_img=100,
+                   iou_calculator='sph2pob_efficient', box_version=4, activation='sigmoid', score_factors=None, with_nms=True,
+                   wh_ratio_clip=16 / 1000, arithmetic=None):
+    """Detections of every image of a minibatch (see the module docstring and include/sph2pob_hip.h).
+
+    cls_scores: L tensors (B, A*C, H_l, W_l) — the head's NCHW, read in place — or (B, n_l, C); bbox_preds laid out alike with
+    `box_version` values per anchor; mlvl_anchors: L tensors (n_l, box_version) shared by the images.  `bbox_coder`: a
+    DeltaXYWHSphBBoxCoder / DeltaXYWHASphBBoxCoder (its means / stds / clip flags).  `nms`: dict(type='nms', iou_threshold=...).
+    `activation`: 'sigmoid' (the inputs are logits) or 'none' (they are probabilities).  Returns `DetBBoxes`."""
+    if score_factors is not None:
+        raise NotImplementedError('sph_get_bboxes does not take score factors (FCOS-style heads): ' + _PER_IMAGE)
+    if activation == 'softmax':
+        raise NotImplementedError('sph_get_bboxes implements sigmoid heads only (use_sigmoid_cls=True), not softmax: ' + _PER_IMAGE)
+    if activation not in ('sigmoid', 'none'):
+        raise ValueError(f"activation must be 'sigmoid' or 'none', got {activation!r}")
+    if not with_nms:
+        raise NotImplementedError('sph_get_bboxes always runs the NMS (with_nms=True): ' + _PER_IMAGE)
+    nms_cfg = dict(nms or {})
+    if nms_cfg.pop('type', 'nms') != 'nms':
+        raise NotImplementedError("sph_get_bboxes implements nms=dict(type='nms', ...) only: " + _PER_IMAGE)
+    if iou_calculator == 'planar' or type(iou_calculator).__name__ == 'PlanarNMS':
+        raise NotImplementedError('sph_get_bboxes runs the spherical NMS only, not PlanarNMS: ' + _PER_IMAGE)
+    variant = _variant_of(iou_calculator)
+    if variant not in ('efficient', 'standard'):
+        raise NotImplementedError(f'sph_get_bboxes serves the sph2pob_efficient / sph2pob_standard calculators, not {variant}: ' + _PER_IMAGE)
+    if (arithmetic or G.get_arithmetic()) == 'reference':
+        raise NotImplementedError("sph_get_bboxes runs the default arithmetic only, not arithmetic='reference': " + _PER_IMAGE)
+    nms_pre, max_per_img = int(nms_pre), int(max_per_img)
+    if nms_pre <= 0:
+        raise ValueError(f'nms_pre must be positive, got {nms_pre} (the reference slices with min(-1, n); that quirk is not reproduced)')
+    if max_per_img < 0:
+        raise ValueError('max_per_img must be >= 0')
+    dim = int(box_version)
+    if dim not in (4, 5) or getattr(bbox_coder, 'box_dim', None) != dim:
+        raise ValueError(f'box_version must be 4 or 5 and match the bbox_coder, got {box_version} and {type(bbox_coder).__name__}')
+    levels = len(mlvl_anchors)
+    if not (1 <= levels <= _MAX_LEVELS) or len(cls_scores) != levels or len(bbox_preds) != levels:
+        raise ValueError(f'sph_get_bboxes takes 1 to {_MAX_LEVELS} levels with one cls_scores / bbox_preds / anchors tensor each')
+    tensors = list(cls_scores) + list(bbox_preds) + list(mlvl_anchors)
+    G.require_hip(*tensors)
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError('sph_get_bboxes: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
+    dev = tensors[0].device
+    images = cls_scores[0].size(0)
+    num_classes = None
+    held, cls_p, box_p, anc_p, ns, hws = [], [], [], [], [], []   # held: converted copies stay alive until the call is enqueued
+    for l in range(levels):
+        anc = G.as_f32_nograd(mlvl_anchors[l][..., :dim])
+        n = anc.size(0)
+        if anc.dim() != 2 or n == 0 or cls_scores[l].numel() % (images * n) != 0:
+            raise ValueError(f'level {l}: anchors {tuple(mlvl_anchors[l].shape)} do not match cls_scores {tuple(cls_scores[l].shape)}')
+        c = cls_scores[l].numel() // (images * n)
+        if num_classes is None:
+            num_classes = c
+        if c != num_classes or c == 0:
+            raise ValueError(f'level {l}: {c} classes, level 0 has {num_classes}')
+        cs, hw = _level(cls_scores[l], f'cls_scores[{l}]', c, n, images)
+        bp, hw_b = _level(bbox_preds[l], f'bbox_preds[{l}]', dim, n, images)
+        if hw != hw_b:
+            raise ValueError(f'level {l}: cls_scores and bbox_preds must use the same layout')
+        held += [cs, bp, anc]
+        cls_p.append(cs.data_ptr()); box_p.append(bp.data_ptr()); anc_p.append(anc.data_ptr()); ns.append(n); hws.append(hw)
+    lib = _lib.lib()
+    k_cap = sum(min(nms_pre, n * num_classes) for n in ns)
+    if k_cap > lib.sph2pob_batched_nms_max_boxes():
+        raise NotImplementedError(f'sph_get_bboxes holds at most {lib.sph2pob_batched_nms_max_boxes()} candidates per image (the NMS key\'s '
+                                  f'index field), nms_pre={nms_pre} over {levels} levels gives {k_cap}: ' + _PER_IMAGE)
+    ptrs = ctypes.c_void_p * levels
+    i64s = ctypes.c_int64 * levels
+    level_n = i64s(*ns)
+    f32, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
+    out = DetBBoxes(dets=torch.empty((images, max_per_img, dim + 1), **f32), labels=torch.empty((images, max_per_img), **i64),
+                    prior_inds=torch.empty((images, max_per_img), **i64), num_dets=torch.empty((images,), **i64))
+    ws = None
+    if dev.type != 'cpu':
+        need = lib.sph2pob_get_bboxes_workspace_bytes(level_n, levels, images, num_classes, dim, nms_pre)
+        if need <= 0:
+            raise ValueError('sph_get_bboxes: these shapes are outside the limits of sph2pob_get_bboxes_f32 (include/sph2pob_hip.h)')
+        ws = G.scratch(dev, need)
+    means = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.means])
+    stds = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.stds])
+    flags = (1 if bbox_coder.clip_border else 0) | (2 if bbox_coder.add_ctr_clamp else 0)
+    G.call('sph2pob_get_bboxes_f32', dev, ptrs(*cls_p), ptrs(*box_p), ptrs(*anc_p), level_n, i64s(*hws), levels, images, num_classes, dim,
+           int(activation == 'sigmoid'), float(score_thr), nms_pre, means, stds, float(abs(math.log(wh_ratio_clip))), flags,
+           float(bbox_coder.ctr_clamp), G.VARIANTS[variant], float(nms_cfg.get('iou_threshold', 0.5)), max_per_img, G.ptr(out.dets),
+           G.ptr(out.labels), G.ptr(out.prior_inds), out.num_dets.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
+    return out

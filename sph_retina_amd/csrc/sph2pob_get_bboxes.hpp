@@ -1,0 +1,159 @@
+// Shared by the batched detection post-processing (sph2pob_get_bboxes_f32: sph2pob_get_bboxes.hip, its NMS stage in
+// sph2pob_nms.hip) and its CPU twin (sph2pob_host.hip): the level table, the order-preserving score keys, the score
+// activation and the argument checks, so that a CPU tensor gets the order and the checks a device tensor gets.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/sph2pob_hip.h"
+
+namespace sph2pob_gb {
+
+#define SPHG_DEV __host__ __device__ __forceinline__
+
+constexpr int kMaxLevels = 8;
+constexpr int kNmsIdxBits = 14, kNmsClsBits = 18;   // the composite NMS key: K <= 16 384 candidates, class ids in [0, 262 143]
+
+// One level of the head for one call.  A score tensor is read in MEMORY order m in [0, count) per image and mapped to the
+// reference's logical candidate index f = ((h W + w) A + a) C + c:
+//   NCHW (B, A C, H, W):  m = ch * hw + p  ->  f = p * (A C) + ch      (hw = H W, ac = A C)
+//   flat (B, n, C):       m = f                                        (hw = count, ac = 1: the same formula)
+struct Level {
+    const float* cls;      // scores or logits
+    const float* bbox;     // deltas, laid out like cls
+    const float* anchors;  // (n, dim)
+    int n;                 // anchors of the level
+    int count;             // n * C candidates per image
+    int hw, ac;            // see above
+    int sp, a;             // bbox gather: spatial size and anchors per location (NCHW), sp = 0 for the flat layout
+    int cap;               // min(nms_pre, count): the level's share of the candidate block
+    int prior_off;         // index of the level's first anchor in cat(mlvl_anchors)
+    int chunk_off;         // first streaming chunk of the level (the next level's follows; see Levels::chunks)
+    int64_t buf_off;       // first survivor slot of the level inside one image's survivor buffer
+};
+struct Levels {
+    Level lv[kMaxLevels];
+    int num;
+    int chunks;            // streaming chunks of one image, all levels
+    int k_cap;             // sum of cap: candidate stride of one image
+    int64_t total;         // sum of count: survivor slots of one image
+};
+
+// larger score -> smaller unsigned; the order of torch's device sort by bit pattern except that -0 is +0
+SPHG_DEV unsigned bits_of(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float_as_uint(v);
+#else
+    unsigned u; __builtin_memcpy(&u, &v, 4); return u;
+#endif
+}
+SPHG_DEV float float_of(unsigned u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float(u);
+#else
+    float v; __builtin_memcpy(&v, &u, 4); return v;
+#endif
+}
+SPHG_DEV unsigned desc_score_bits(float v) {
+    unsigned u = bits_of(v + 0.0f);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~u;
+}
+SPHG_DEV float score_of_desc_bits(unsigned d) {
+    const unsigned u = ~d;
+    return float_of((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+SPHG_DEV unsigned long long nms_class_key(int64_t c, float score, int j) {
+    return ((unsigned long long)(c & (((int64_t)1 << kNmsClsBits) - 1)) << (32 + kNmsIdxBits)) |
+           ((unsigned long long)desc_score_bits(score) << kNmsIdxBits) | (unsigned)j;
+}
+
+// the score a candidate is selected on AND reported with: fp32, 1 / (1 + exp(-x)) with the library expf and an IEEE divide
+SPHG_DEV float activate(float x, int activation) { return activation ? 1.0f / (1.0f + expf(-x)) : x; }
+
+// Selection histogram: a monotone map of the descending score key onto kBins bins, 512 bins per octave downwards from 1.0
+// (probabilities fill the bins evenly; anything above 1 lands in bin 0, anything below 2^-16 in the last bin).  Any monotone
+// map is correct: the bins only bound how many survivors the exact stage has to look at.
+constexpr int kBins = 8192, kBinShift = 14;
+SPHG_DEV int score_bin(unsigned dkey) {
+    const unsigned one = 0x407fffffu;   // desc_score_bits(1.0f)
+    if (dkey <= one) return 0;
+    const unsigned b = (dkey - one) >> kBinShift;
+    return b < (unsigned)kBins ? (int)b : kBins - 1;
+}
+
+inline int64_t k_cap_of(const int64_t* level_n, int num_levels, int64_t num_classes, int64_t nms_pre) {
+    int64_t k = 0;
+    for (int l = 0; l < num_levels; l++) {
+        const int64_t c = level_n[l] * num_classes;
+        k += c < nms_pre ? c : nms_pre;
+    }
+    return k;
+}
+
+// Argument checks of sph2pob_get_bboxes_f32 and its twin, in the documented order, in two parts: the shapes (all the workspace
+// size needs; level_hw may be NULL = flattened layout) fill the level table, then the pointer tables are checked and entered.
+inline int make_level_shapes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes,
+                             int box_dim, int activation, int variant, int64_t nms_pre, int64_t max_per_img, float max_ratio,
+                             int coder_flags, int chunk_elems, bool have_tables, Levels* out) {
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    const int v = variant & 0xff;
+    if ((v != SPH2POB_VARIANT_STANDARD && v != SPH2POB_VARIANT_EFFICIENT) || (variant & ~(0xff | SPH2POB_FLAG_ROBUST_PARALLEL)) ||
+        activation < 0 || activation > 1 || (coder_flags & ~3) || !(max_ratio >= 0.0f))
+        return SPH2POB_ERR_OPTION;
+    if (num_levels < 1 || num_levels > kMaxLevels || num_images < 1 || num_images > 65535 || num_classes < 1 ||
+        num_classes > ((int64_t)1 << kNmsClsBits) || nms_pre <= 0 || max_per_img < 0 || max_per_img > ((int64_t)1 << 30))
+        return SPH2POB_ERR_SIZE;
+    if (!have_tables || !level_n) return SPH2POB_ERR_NULL;
+    Levels L{};
+    L.num = num_levels;
+    int64_t k_cap = 0, total = 0, chunks = 0, prior = 0;
+    for (int l = 0; l < num_levels; l++) {
+        const int64_t n = level_n[l], hw = level_hw ? level_hw[l] : 0, count = n * num_classes;
+        if (n < 1 || count >= ((int64_t)1 << 31) - 8 * chunk_elems || hw < 0 || (hw > 0 && n % hw != 0)) return SPH2POB_ERR_SIZE;
+        Level& d = L.lv[l];
+        d.n = (int)n; d.count = (int)count;
+        d.hw = hw > 0 ? (int)hw : (int)count;
+        d.ac = hw > 0 ? (int)(count / hw) : 1;
+        d.sp = (int)hw; d.a = hw > 0 ? (int)(n / hw) : 1;
+        d.cap = (int)(count < nms_pre ? count : nms_pre);
+        d.prior_off = (int)prior; d.chunk_off = (int)chunks; d.buf_off = total;
+        prior += n; total += count; k_cap += d.cap;
+        chunks += (count + chunk_elems - 1) / chunk_elems;
+        if (prior >= ((int64_t)1 << 31) || chunks >= ((int64_t)1 << 31)) return SPH2POB_ERR_SIZE;
+    }
+    if (k_cap > ((int64_t)1 << kNmsIdxBits)) return SPH2POB_ERR_SIZE;
+    L.chunks = (int)chunks; L.k_cap = (int)k_cap; L.total = total;
+    *out = L;
+    return SPH2POB_OK;
+}
+inline int make_levels(const void* const* cls, const void* const* bbox, const void* const* anchors, const int64_t* level_n,
+                       const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                       int variant, int64_t nms_pre, int64_t max_per_img, float max_ratio, int coder_flags, int chunk_elems, Levels* out) {
+    if (int rc = make_level_shapes(level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation, variant, nms_pre, max_per_img,
+                                   max_ratio, coder_flags, chunk_elems, cls && bbox && anchors && level_hw, out))
+        return rc;
+    for (int l = 0; l < num_levels; l++) {
+        if (!cls[l] || !bbox[l] || !anchors[l]) return SPH2POB_ERR_NULL;
+        out->lv[l].cls = (const float*)cls[l]; out->lv[l].bbox = (const float*)bbox[l]; out->lv[l].anchors = (const float*)anchors[l];
+    }
+    return SPH2POB_OK;
+}
+
+// the deltas of anchor `ai` of image b, from the head layout
+template <int DIM>
+SPHG_DEV void gather_deltas(const Level& lv, int64_t b, int ai, float* d) {
+    if (lv.sp > 0) {
+        const int p = ai / lv.a, a = ai - p * lv.a;
+        const float* q = lv.bbox + (b * lv.a + a) * (int64_t)DIM * lv.sp + p;
+#pragma unroll
+        for (int k = 0; k < DIM; k++) d[k] = q[(int64_t)k * lv.sp];
+    } else {
+        const float* q = lv.bbox + (b * lv.n + ai) * (int64_t)DIM;
+#pragma unroll
+        for (int k = 0; k < DIM; k++) d[k] = q[k];
+    }
+}
+
+}  // namespace sph2pob_gb

@@ -24,6 +24,7 @@
 #include "sph2pob_fast.hpp"
 #include "sph2pob_unbiased.hpp"
 #include "sph2pob_coder.hpp"
+#include "sph2pob_get_bboxes.hpp"
 
 namespace {
 
@@ -612,6 +613,87 @@ int sph2pob_anchor_targets_f32_cpu(const float* anchors, int64_t n, const float*
         total += std::max<int64_t>(np, 1);
     }
     *avg_factor = (float)total;
+    return SPH2POB_OK;
+}
+
+// ---- detection post-processing for a minibatch: sph2pob_get_bboxes_f32 (the same keys, in the same order, sorted instead of
+// selected; the NMS twin above on each image's candidates; the workspace is not used) ----
+int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                               const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                               float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                               int coder_flags, float ctr_clamp, int variant, float iou_threshold, int64_t max_per_img, float* dets,
+                               int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
+    (void)workspace;
+    namespace GB = sph2pob_gb;
+    GB::Levels L;
+    if (int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                                 variant, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &L))
+        return rc;
+    if (!num_dets || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
+    const int dim = box_dim;
+    std::vector<unsigned long long> keys, order;
+    std::vector<float> boxes, scores, sorted;
+    std::vector<int64_t> cls, prior, cls_sorted;
+    std::vector<unsigned char> keep;
+    for (int64_t b = 0; b < num_images; b++) {
+        boxes.clear(); scores.clear(); cls.clear(); prior.clear();
+        for (int l = 0; l < L.num; l++) {
+            const GB::Level& lv = L.lv[l];
+            const float* base = lv.cls + b * (int64_t)lv.count;
+            keys.clear();
+            for (int m = 0; m < lv.count; m++) {
+                const float s = GB::activate(base[m], activation);
+                if (!(s > score_thr)) continue;
+                const int ch = m / lv.hw, p = m - ch * lv.hw;
+                keys.push_back(((unsigned long long)GB::desc_score_bits(s) << 32) | (unsigned)(p * lv.ac + ch));
+            }
+            const size_t want = std::min<size_t>(keys.size(), (size_t)lv.cap);
+            std::partial_sort(keys.begin(), keys.begin() + want, keys.end());
+            for (size_t i = 0; i < want; i++) {
+                const unsigned flat = (unsigned)keys[i];
+                const int ai = (int)(flat / (unsigned)num_classes);
+                float p[5] = {0, 0, 0, 0, 0}, d[5], box[5];
+                for (int k = 0; k < dim; k++) p[k] = lv.anchors[(int64_t)ai * dim + k];
+                if (dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); sph2pob_coder::decode_one<4, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
+                else { GB::gather_deltas<5>(lv, b, ai, d); sph2pob_coder::decode_one<5, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
+                boxes.insert(boxes.end(), box, box + dim);
+                scores.push_back(GB::score_of_desc_bits((unsigned)(keys[i] >> 32)));
+                cls.push_back((int64_t)(flat - (unsigned)ai * (unsigned)num_classes));
+                prior.push_back(lv.prior_off + ai);
+            }
+        }
+        // the batched NMS on this image: (class | descending score | position) order, the sweeps, the kept by (score | position)
+        const int64_t k = (int64_t)scores.size();
+        order.resize(k);
+        for (int64_t j = 0; j < k; j++) order[j] = GB::nms_class_key(cls[j], scores[j], (int)j);
+        std::sort(order.begin(), order.end());
+        sorted.resize(k * dim); cls_sorted.resize(k); keep.assign(k, 0);
+        for (int64_t r = 0; r < k; r++) {
+            const int64_t j = (int64_t)(order[r] & ((1u << GB::kNmsIdxBits) - 1u));
+            for (int c = 0; c < dim; c++) sorted[r * dim + c] = boxes[j * dim + c];
+            cls_sorted[r] = cls[j];
+        }
+        if (k > 0)
+            if (int rc = sph2pob_nms_segmented_f32_cpu(sorted.data(), cls_sorted.data(), k, box_dim, variant, iou_threshold, k, nullptr, keep.data(), nullptr))
+                return rc;
+        keys.clear();
+        for (int64_t r = 0; r < k; r++) {
+            const int64_t j = (int64_t)(order[r] & ((1u << GB::kNmsIdxBits) - 1u));
+            if (keep[r]) keys.push_back(((unsigned long long)GB::desc_score_bits(scores[j]) << 32) | (unsigned)j);
+        }
+        std::sort(keys.begin(), keys.end());
+        const int64_t n = std::min<int64_t>((int64_t)keys.size(), max_per_img);
+        num_dets[b] = n;
+        for (int64_t r = 0; r < max_per_img; r++) {
+            const int64_t e = b * max_per_img + r;
+            const int64_t j = r < n ? (int64_t)(unsigned)keys[r] : -1;
+            for (int c = 0; c < dim; c++) dets[e * (dim + 1) + c] = j >= 0 ? boxes[j * dim + c] : 0.0f;
+            dets[e * (dim + 1) + dim] = j >= 0 ? scores[j] : 0.0f;
+            labels[e] = j >= 0 ? cls[j] : -1;
+            prior_inds[e] = j >= 0 ? prior[j] : -1;
+        }
+    }
     return SPH2POB_OK;
 }
 

@@ -2,6 +2,7 @@
 // launchers (include/sph2pob_hip.h).  gfx950 only.
 
 #include "sph2pob_kernels_common.hpp"
+#include "sph2pob_get_bboxes.hpp"
 
 namespace {
 
@@ -92,9 +93,9 @@ constexpr int kNmsMaxWords = 512;  // <= 32768 boxes per class segment (the swee
 // stack, lean_finish runs on 64 of them at a time, and a hit sets its bit in the row's bitmap in LDS (ds_or), which is
 // written out once.  50 M candidate pairs of the 61 k-candidate pipeline scene: 465 us with one lane per pair.
 template <int VARIANT, int DIM>
-__global__ __launch_bounds__(kBlock) void nms_mask_compact_kernel(const float* __restrict__ boxes, const int64_t* __restrict__ cls,
-                                                                 int64_t k, int words, float thr,
-                                                                 unsigned long long* __restrict__ mask) {
+__device__ __forceinline__ void nms_mask_compact_body(const float* __restrict__ boxes, const int64_t* __restrict__ cls,
+                                                      int64_t k, int words, float thr,
+                                                      unsigned long long* __restrict__ mask) {
     __shared__ int stack[kBlock / 64][kQCap];
     __shared__ unsigned int bits[kBlock / 64][2 * kNmsMaxWords];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -162,6 +163,22 @@ __global__ __launch_bounds__(kBlock) void nms_mask_compact_kernel(const float* _
     }
     for (int w = lane; w < words; w += 64) row[w] = (unsigned long long)bm[2 * w] | ((unsigned long long)bm[2 * w + 1] << 32);
 }
+template <int VARIANT, int DIM>
+__global__ __launch_bounds__(kBlock) void nms_mask_compact_kernel(const float* __restrict__ boxes, const int64_t* __restrict__ cls,
+                                                                 int64_t k, int words, float thr,
+                                                                 unsigned long long* __restrict__ mask) {
+    nms_mask_compact_body<VARIANT, DIM>(boxes, cls, k, words, thr, mask);
+}
+// The batched form (sph2pob_get_bboxes_f32): blockIdx.y is the image, its candidates start at b * k_cap, its live count is read
+// from the device and its matrix is laid out for that count (rows of (k + 63) / 64 words), as the single-image call lays it out.
+template <int VARIANT, int DIM>
+__global__ __launch_bounds__(kBlock) void nms_mask_compact_batch_kernel(const float* __restrict__ boxes, const int64_t* __restrict__ cls,
+                                                                       const int* __restrict__ counts, int k_cap, float thr,
+                                                                       unsigned long long* __restrict__ mask, int64_t mask_stride) {
+    const int b = blockIdx.y, k = counts[b];
+    if ((int)blockIdx.x * (kBlock / 64) >= k) return;
+    nms_mask_compact_body<VARIANT, DIM>(boxes + (int64_t)b * k_cap * DIM, cls + (int64_t)b * k_cap, k, (k + 63) / 64, thr, mask + b * mask_stride);
+}
 
 // Greedy sweep, one WORKGROUP per class segment (classes are independent).  Every workgroup looks at 4 candidate rows;
 // a row that starts a class segment makes the whole workgroup sweep that segment's 64-row blocks in order, as a two-stage
@@ -190,9 +207,9 @@ __global__ __launch_bounds__(kBlock) void nms_mask_compact_kernel(const float* _
 // instruction chain — a lone wave issues a dependent instruction every ~9 cycles, 14 per kept row, ~7 kept rows per block, plus
 // the LDS read, the ballot, the store and the barrier.)
 constexpr int kSweepBlock = 512, kSweepCands = 4;
-__global__ __launch_bounds__(kSweepBlock) void nms_sweep_kernel(const unsigned long long* __restrict__ mask,
-                                                                const int64_t* __restrict__ cls, int64_t k, int words,
-                                                                unsigned char* __restrict__ keep) {
+__device__ __forceinline__ void nms_sweep_body(const unsigned long long* __restrict__ mask,
+                                               const int64_t* __restrict__ cls, int64_t k, int words,
+                                               unsigned char* __restrict__ keep) {
     __shared__ unsigned long long removed[kNmsMaxWords];
     __shared__ unsigned long long kept_sh[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -284,6 +301,18 @@ __global__ __launch_bounds__(kSweepBlock) void nms_sweep_kernel(const unsigned l
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(kSweepBlock) void nms_sweep_kernel(const unsigned long long* __restrict__ mask,
+                                                                const int64_t* __restrict__ cls, int64_t k, int words,
+                                                                unsigned char* __restrict__ keep) {
+    nms_sweep_body(mask, cls, k, words, keep);
+}
+__global__ __launch_bounds__(kSweepBlock) void nms_sweep_batch_kernel(const unsigned long long* __restrict__ mask, int64_t mask_stride,
+                                                                      const int64_t* __restrict__ cls, const int* __restrict__ counts,
+                                                                      int k_cap, unsigned char* __restrict__ keep) {
+    const int b = blockIdx.y, k = counts[b];
+    if ((int)blockIdx.x * kSweepCands >= k) return;
+    nms_sweep_body(mask + b * mask_stride, cls + (int64_t)b * k_cap, k, (k + 63) / 64, keep + (int64_t)b * k_cap);
+}
 
 // ---- batched NMS without the host (sph_batched_nms, sphdet/bbox/nms/sph_nms.py:22-60, for K <= 16 384 candidates) ----
 // The reference sorts per class on the host and loops; round 2 sorted with two stable torch sorts (2 x ~30 us of rocPRIM
@@ -297,18 +326,14 @@ __global__ __launch_bounds__(kSweepBlock) void nms_sweep_kernel(const unsigned l
 //   nms_select_kernel    the same rank sort among the KEPT boxes by (descending score | index) -> the first max_num kept indices
 //                        in the reference's final order (:49-52), dets = (box, score), and their count.
 // Ties are broken by the original index (stable), as in round 2.  One host read (the count) sizes the outputs.
-__device__ __forceinline__ unsigned desc_score_bits(float v) {   // larger score -> smaller unsigned
-    // the order of torch's device sort (cub's radix keys): by bit pattern — +NaN first, -NaN last — except that -0 is +0
-    // (equal scores keep the index order)
-    unsigned u = __float_as_uint(v + 0.0f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ~u;
-}
-constexpr int kNmsIdxBits = 14, kNmsClsBits = 18;   // K <= 16 384 candidates, class ids in [0, 262 143]
-__device__ __forceinline__ unsigned long long nms_class_key(int64_t c, float score, int j) {
-    return ((unsigned long long)(c & (((int64_t)1 << kNmsClsBits) - 1)) << (32 + kNmsIdxBits)) |
-           ((unsigned long long)desc_score_bits(score) << kNmsIdxBits) | (unsigned)j;
-}
+// desc_score_bits (larger score -> smaller unsigned): the order of torch's device sort (cub's radix keys): by bit pattern — +NaN
+// first, -NaN last — except that -0 is +0 (equal scores keep the index order).  Shared with the selection stage of
+// sph2pob_get_bboxes_f32 and with the CPU twins: sph2pob_get_bboxes.hpp.
+using sph2pob_gb::desc_score_bits;
+using sph2pob_gb::score_of_desc_bits;
+using sph2pob_gb::nms_class_key;
+using sph2pob_gb::kNmsIdxBits;
+using sph2pob_gb::kNmsClsBits;
 // Rank of IPW keys among all keys, the keys held in REGISTERS: wave w of the workgroup holds the slice [w * T * 64, (w + 1) * T * 64)
 // of the key sequence, one key per lane and register (coalesced loads, no LDS); the key whose rank is wanted is wave-uniform
 // (v_readlane -> SGPR pair), one v_cmp_lt_u64 tests it against 64 keys and s_bcnt1 counts.  (First form: all keys in LDS, the
@@ -354,11 +379,11 @@ __device__ __forceinline__ int rank_against_slices(const unsigned long long (&ke
     return r;
 }
 template <int T, int DIM, int IPW, int BS>
-__global__ __launch_bounds__(BS) void nms_prepare_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
-                                                                const int64_t* __restrict__ idxs, int k,
-                                                                float* __restrict__ boxes_sorted, int64_t* __restrict__ cls_sorted,
-                                                                int* __restrict__ order, unsigned long long* __restrict__ skey_sorted,
-                                                                int* __restrict__ status) {
+__device__ __forceinline__ void nms_prepare_body(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                 const int64_t* __restrict__ idxs, int k,
+                                                 float* __restrict__ boxes_sorted, int64_t* __restrict__ cls_sorted,
+                                                 int* __restrict__ order, unsigned long long* __restrict__ skey_sorted,
+                                                 int* __restrict__ status) {
     __shared__ int part[BS / 64][64];   // (T keys per lane)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tcount = ((k + BS - 1) / BS);   // registers in use: the slices cover [0, tcount * BS)
@@ -404,18 +429,38 @@ __global__ __launch_bounds__(BS) void nms_prepare_kernel(const float* __restrict
         }
     }
 }
+template <int T, int DIM, int IPW, int BS>
+__global__ __launch_bounds__(BS) void nms_prepare_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                                const int64_t* __restrict__ idxs, int k,
+                                                                float* __restrict__ boxes_sorted, int64_t* __restrict__ cls_sorted,
+                                                                int* __restrict__ order, unsigned long long* __restrict__ skey_sorted,
+                                                                int* __restrict__ status) {
+    nms_prepare_body<T, DIM, IPW, BS>(boxes, scores, idxs, k, boxes_sorted, cls_sorted, order, skey_sorted, status);
+}
+// (batched: T, IPW and BS are chosen for k_cap, which bounds every image's count; rows from an image's count on are never read)
+template <int T, int DIM, int IPW, int BS>
+__global__ __launch_bounds__(BS) void nms_prepare_batch_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                                      const int64_t* __restrict__ idxs, const int* __restrict__ counts, int k_cap,
+                                                                      float* __restrict__ boxes_sorted, int64_t* __restrict__ cls_sorted,
+                                                                      int* __restrict__ order, unsigned long long* __restrict__ skey_sorted,
+                                                                      int* __restrict__ status) {
+    const int b = blockIdx.y, k = counts[b];
+    const int64_t o = (int64_t)b * k_cap;
+    if ((int)blockIdx.x * IPW >= k) return;
+    nms_prepare_body<T, DIM, IPW, BS>(boxes + o * DIM, scores + o, idxs + o, k, boxes_sorted + o * DIM, cls_sorted + o, order + o, skey_sorted + o,
+                                      status + b);
+}
 // (dets come from the SORTED boxes and the score inside the key: everything the kernel reads is indexed by the sorted position,
 // nothing by a loaded value — one round trip)
-__device__ __forceinline__ float score_of_desc_bits(unsigned d) {
-    const unsigned u = ~d;
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-template <int T, int DIM, int IPW, int BS>
-__global__ __launch_bounds__(BS) void nms_select_kernel(const float* __restrict__ boxes_sorted,
-                                                               const unsigned char* __restrict__ keep_sorted,
-                                                               const unsigned long long* __restrict__ skey_sorted, int k, int max_num,
-                                                               int64_t* __restrict__ keep_out, float* __restrict__ dets,
-                                                               int* __restrict__ status) {
+// BATCH (sph2pob_get_bboxes_f32): the padded outputs of one image — labels / prior indices looked up through the kept
+// candidate's position, -1 and zero rows from the count on up to max_rows, the count as int64 — instead of keep_out / status.
+struct SelectBatch { const int64_t* labels_in; const int* prior_in; int64_t* labels_out; int64_t* prior_out; int64_t* num_dets; int max_rows; };
+template <int T, int DIM, int IPW, int BS, bool BATCH>
+__device__ __forceinline__ void nms_select_body(const float* __restrict__ boxes_sorted,
+                                                const unsigned char* __restrict__ keep_sorted,
+                                                const unsigned long long* __restrict__ skey_sorted, int k, int max_num,
+                                                int64_t* __restrict__ keep_out, float* __restrict__ dets,
+                                                int* __restrict__ status, const SelectBatch& sb) {
     __shared__ int part[BS / 64][64];
     __shared__ int kept_waves[BS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -447,18 +492,74 @@ __global__ __launch_bounds__(BS) void nms_select_kernel(const float* __restrict_
     if (lane == 0) kept_waves[wave] = kept_here;
     const unsigned long long mine = (r < k && my_keep != 0) ? my_skey : ~0ull;
     const int pos = rank_against_slices<T, IPW, BS>(key, mine, part);   // (its barrier also publishes kept_waves)
-    if (blockIdx.x == 0 && threadIdx.x == 0 && *status >= 0) {
+    if constexpr (BATCH) {
+        if (blockIdx.x == 0) {
+            int total = 0;
+#pragma unroll
+            for (int w = 0; w < BS / 64; w++) total += kept_waves[w];
+            const int n = total < max_num ? total : max_num;
+            if (threadIdx.x == 0) *sb.num_dets = n;
+            for (int row = n + threadIdx.x; row < sb.max_rows; row += BS) {
+                sb.labels_out[row] = -1;
+                sb.prior_out[row] = -1;
+#pragma unroll
+                for (int c = 0; c <= DIM; c++) dets[(int64_t)row * (DIM + 1) + c] = 0.0f;
+            }
+        }
+    } else if (blockIdx.x == 0 && threadIdx.x == 0 && *status >= 0) {
         int total = 0;
 #pragma unroll
         for (int w = 0; w < BS / 64; w++) total += kept_waves[w];
         *status = total < max_num ? total : max_num;
     }
     if (threadIdx.x < IPW && mine != ~0ull && pos < max_num) {
-        keep_out[pos] = (int64_t)(unsigned)mine;
+        if constexpr (BATCH) {
+            const unsigned at = (unsigned)mine;
+            sb.labels_out[pos] = sb.labels_in[at];
+            sb.prior_out[pos] = sb.prior_in[at];
+        } else {
+            keep_out[pos] = (int64_t)(unsigned)mine;
+        }
 #pragma unroll
         for (int c = 0; c < DIM; c++) dets[(int64_t)pos * (DIM + 1) + c] = bx[c];
         dets[(int64_t)pos * (DIM + 1) + DIM] = score_of_desc_bits((unsigned)(mine >> 32));
     }
+}
+template <int T, int DIM, int IPW, int BS>
+__global__ __launch_bounds__(BS) void nms_select_kernel(const float* __restrict__ boxes_sorted,
+                                                               const unsigned char* __restrict__ keep_sorted,
+                                                               const unsigned long long* __restrict__ skey_sorted, int k, int max_num,
+                                                               int64_t* __restrict__ keep_out, float* __restrict__ dets,
+                                                               int* __restrict__ status) {
+    nms_select_body<T, DIM, IPW, BS, false>(boxes_sorted, keep_sorted, skey_sorted, k, max_num, keep_out, dets, status, SelectBatch{});
+}
+template <int T, int DIM, int IPW, int BS>
+__global__ __launch_bounds__(BS) void nms_select_batch_kernel(const float* __restrict__ boxes_sorted,
+                                                                     const unsigned char* __restrict__ keep_sorted,
+                                                                     const unsigned long long* __restrict__ skey_sorted,
+                                                                     const int* __restrict__ counts, int k_cap, int max_rows,
+                                                                     const int64_t* __restrict__ labels_in, const int* __restrict__ prior_in,
+                                                                     float* __restrict__ dets, int64_t* __restrict__ labels_out,
+                                                                     int64_t* __restrict__ prior_out, int64_t* __restrict__ num_dets) {
+    const int b = blockIdx.y, k = counts[b];
+    const int64_t o = (int64_t)b * k_cap, r = (int64_t)b * max_rows;
+    float* d = dets + r * (DIM + 1);
+    if (k == 0) {   // nothing above the threshold: all padding
+        if (blockIdx.x == 0) {
+            if (threadIdx.x == 0) num_dets[b] = 0;
+            for (int row = threadIdx.x; row < max_rows; row += BS) {
+                labels_out[r + row] = -1;
+                prior_out[r + row] = -1;
+#pragma unroll
+                for (int c = 0; c <= DIM; c++) d[(int64_t)row * (DIM + 1) + c] = 0.0f;
+            }
+        }
+        return;
+    }
+    if ((int)blockIdx.x * IPW >= k) return;
+    const SelectBatch sb{labels_in + o, prior_in + o, labels_out + r, prior_out + r, num_dets + b, max_rows};
+    nms_select_body<T, DIM, IPW, BS, true>(boxes_sorted + o * DIM, keep_sorted + o, skey_sorted + o, k, max_rows < k ? max_rows : k, nullptr, d,
+                                           nullptr, sb);
 }
 
 
@@ -594,6 +695,63 @@ int sph2pob_batched_nms_f32(const float* boxes, const float* scores, const int64
 #undef SPH_PREP
 #undef SPH_SEL
 #undef SPH_BY_SIZE
+    return launch_status();
+}
+
+// The NMS stage of sph2pob_get_bboxes_f32 (sph2pob_get_bboxes.hip): the four kernels above with the image as grid dimension y.
+// Candidate blocks have the fixed stride k_cap, every kernel reads its image's live count from `counts`; closed-form variants
+// only (the caller has checked), so the suppression matrix always comes from the compacting kernel.
+__attribute__((visibility("hidden"))) int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim) {
+    return num_images * batched_nms_ws(nullptr, k_cap, box_dim).bytes + (num_images * 4 + 255) / 256 * 256;   // + one status word per image
+}
+__attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(const float* boxes, const float* scores, const int64_t* labels, const int* prior,
+                                                                   const int* counts, int64_t num_images, int k_cap, int box_dim, int variant_flags,
+                                                                   float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
+                                                                   int64_t* labels_out, int64_t* prior_out, int64_t* num_dets, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t k = k_cap;
+    const unsigned B = (unsigned)num_images;
+    // one image's layout B times over: every array of image b starts b * k_cap elements into its B-fold region
+    const BatchedNmsWs one = batched_nms_ws(nullptr, k, box_dim);
+    auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
+    char* p = (char*)nms_workspace;
+    BatchedNmsWs w = one;
+    int64_t off = 0;
+    w.boxes = (float*)(p + off); off += up(num_images * k * box_dim * 4);
+    w.cls = (int64_t*)(p + off); off += up(num_images * k * 8);
+    w.order = (int*)(p + off); off += up(num_images * k * 4);
+    w.skey = (unsigned long long*)(p + off); off += up(num_images * k * 8);
+    w.keep = (unsigned char*)(p + off); off += up(num_images * k);
+    int* status = (int*)(p + off); off += up(num_images * 4);
+    w.mask = (unsigned long long*)(p + off);
+    const int64_t mask_stride = k * (int64_t)one.words;
+    const int variant = variant_flags & 0xff, rows = (int)max_per_img;
+#define SPH_PREP(T, D, I, Bs) hipLaunchKernelGGL((nms_prepare_batch_kernel<T, D, I, Bs>), dim3((unsigned)((k + I - 1) / I), B), dim3(Bs), 0, s, boxes, scores, \
+                                                 labels, counts, k_cap, w.boxes, w.cls, w.order, w.skey, status)
+#define SPH_SEL(T, D, I, Bs) hipLaunchKernelGGL((nms_select_batch_kernel<T, D, I, Bs>), dim3((unsigned)((k + I - 1) / I), B), dim3(Bs), 0, s, \
+                                                (const float*)w.boxes, (const unsigned char*)w.keep, (const unsigned long long*)w.skey, counts, k_cap, rows, \
+                                                labels, prior, dets, labels_out, prior_out, num_dets)
+#define SPH_BY_SIZE(M, D) do { if (k <= 2048) M(4, D, 16, 512); else if (k <= 4096) M(8, D, 16, 512); else if (k <= 6144) M(12, D, 24, 512); \
+                               else if (k <= 8192) M(16, D, 32, 512); else if (k <= 12288) M(12, D, 48, 1024); else M(16, D, 64, 1024); } while (0)
+    if (box_dim == 4) SPH_BY_SIZE(SPH_PREP, 4); else SPH_BY_SIZE(SPH_PREP, 5);
+    int rc = launch_status();
+    if (rc) return rc;
+    const dim3 mgrid((unsigned)((k + kBlock / 64 - 1) / (kBlock / 64)), B);
+#define SPH_MASK(V, D) hipLaunchKernelGGL((nms_mask_compact_batch_kernel<V, D>), mgrid, dim3(kBlock), 0, s, (const float*)w.boxes, (const int64_t*)w.cls, \
+                                          counts, k_cap, iou_threshold, w.mask, mask_stride)
+    if (variant == SPH2POB_VARIANT_EFFICIENT) { if (box_dim == 4) SPH_MASK(1, 4); else SPH_MASK(1, 5); }
+    else { if (box_dim == 4) SPH_MASK(0, 4); else SPH_MASK(0, 5); }
+    rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(nms_sweep_batch_kernel, dim3((unsigned)((k + kSweepCands - 1) / kSweepCands), B), dim3(kSweepBlock), 0, s,
+                       (const unsigned long long*)w.mask, mask_stride, (const int64_t*)w.cls, counts, k_cap, w.keep);
+    rc = launch_status();
+    if (rc) return rc;
+    if (box_dim == 4) SPH_BY_SIZE(SPH_SEL, 4); else SPH_BY_SIZE(SPH_SEL, 5);
+#undef SPH_PREP
+#undef SPH_SEL
+#undef SPH_BY_SIZE
+#undef SPH_MASK
     return launch_status();
 }
 

@@ -321,6 +321,94 @@ def config4_batch(images=8, num_gt=64, h=512, w=1024, rounds=7):
             'note': '(a) also writes labels, label_weights, bbox_targets, bbox_weights and the counts, which (b) does not'}
 
 
+def get_bboxes(images=8, rounds=7):
+    """Detection post-processing for a minibatch (sph_get_bboxes) at the reference's test shape — 512 x 1024 ERP, 5 levels, 9
+    anchors, 37 classes, nms_pre 1000, max_per_img 100 — on the head's NCHW outputs: (a) one eager call for the batch; (b) the
+    same call replayed from a graph; (c) the per-image composition it replaces (per level: permute, `> thr`, nonzero, stable
+    sort, gather, bbox_coder.decode; then sph_batched_nms), looped over the images.  The three are timed in alternation
+    `rounds` times in this one process, medians and spreads reported.  `stream_floor_us`: the bytes of one pass over the scores
+    over the bandwidth of a device copy of the same tensors measured here (a copy moves each byte twice)."""
+    import demo_hot_path as D
+    from sph_retina_amd.bbox.nms import sph_batched_nms
+    anchors = D.retina_level_anchors()
+    cls, box = D.head_outputs(images, 37)
+    coder_ = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
+    nms = dict(type='nms', iou_threshold=0.5)
+
+    def batched():
+        return S.sph_get_bboxes(cls, box, anchors, bbox_coder=coder_, score_thr=0.05, nms_pre=1000, nms=nms, max_per_img=100,
+                                iou_calculator='sph2pob_efficient', box_version=4, activation='none')
+
+    def per_image():
+        out = []
+        for b in range(images):
+            bs, ss, ls = [], [], []
+            for c, d, a in zip(cls, box, anchors):
+                flat = c[b].permute(1, 2, 0).reshape(-1)
+                valid = torch.nonzero(flat > 0.05, as_tuple=False).squeeze(1)
+                idx = valid[torch.sort(flat[valid], descending=True, stable=True).indices[:1000]]
+                ai = torch.div(idx, 37, rounding_mode='floor')
+                bs.append(coder_.decode(a[ai], d[b].permute(1, 2, 0).reshape(-1, 4)[ai]))
+                ss.append(flat[idx])
+                ls.append(idx - ai * 37)
+            dets, keep = sph_batched_nms(torch.cat(bs), torch.cat(ss), torch.cat(ls), dict(nms), 'efficient')
+            out.append((dets[:100], torch.cat(ls)[keep][:100]))
+        return out
+    r, ref = batched(), per_image()
+    torch.cuda.synchronize()
+    for b, ((dets, labels), (d2, l2)) in enumerate(zip(r.to_list(), ref)):
+        assert torch.equal(dets, d2) and torch.equal(labels, l2), 'batched and per-image detections differ'
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        batched()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        batched()
+    dst = [torch.empty_like(c) for c in cls]
+
+    def copy():
+        for x, y in zip(dst, cls):
+            x.copy_(y)
+    ta, tb, tc, tcopy = [], [], [], []
+    for _ in range(rounds):
+        ta.append(timeit(batched, reps=50) * 1e6)
+        tb.append(timeit(graph.replay, reps=50) * 1e6)
+        tc.append(timeit(per_image, warm=2, reps=5) * 1e6)
+        tcopy.append(timeit(copy, reps=50) * 1e6)
+    med = lambda v: float(np.median(v))
+    score_bytes = sum(c.numel() for c in cls) * 4
+    bw = 2 * score_bytes / (med(tcopy) * 1e-6)
+    # the kernels' own times in this process: torch's device-activity trace of 20 eager calls, averaged per kernel name
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(20):
+            batched()
+        torch.cuda.synchronize()
+    kernels = {}
+    for e in prof.key_averages():
+        t = getattr(e, 'device_time_total', None) or getattr(e, 'cuda_time_total', 0.0)
+        if t > 0:
+            kernels[e.key.split('(')[0].split('::')[-1][:60]] = t / 20
+    sel = sum(v for k, v in kernels.items() if 'topk_hist' in k or 'topk_compact' in k)
+    # worst case of the exact stage: every score of level 0 equal (2.7 M keys in one bin, per image)
+    cls_eq = [torch.full_like(cls[0], 0.5)] + cls[1:]
+    t_eq = timeit(lambda: S.sph_get_bboxes(cls_eq, box, anchors, bbox_coder=coder_, score_thr=0.05, nms_pre=1000, nms=nms, max_per_img=100,
+                                           iou_calculator='sph2pob_efficient', box_version=4, activation='none'), warm=2, reps=5) * 1e6
+    return {'config': 'get_bboxes: %d images x 98208 anchors x 37 classes (512x1024 ERP, NCHW), nms_pre 1000, max_per_img 100' % images,
+            'a_batched_eager_us': med(ta), 'b_batched_graph_us': med(tb), 'c_per_image_loop_us': med(tc),
+            'a_rounds_us': ta, 'b_rounds_us': tb, 'c_rounds_us': tc, 'a_spread_us': max(ta) - min(ta), 'b_spread_us': max(tb) - min(tb),
+            'c_spread_us': max(tc) - min(tc), 'a_over_c': med(ta) / med(tc), 'b_over_c': med(tb) / med(tc),
+            'score_bytes': score_bytes, 'copy_bandwidth_TBps': bw / 1e12, 'stream_floor_us_one_pass': score_bytes / bw * 1e6,
+            'stream_floor_us_two_passes': 2 * score_bytes / bw * 1e6, 'num_dets': r.num_dets.tolist(),
+            'kernel_us': kernels, 'selection_streams_us': sel, 'selection_over_two_pass_floor': sel / (2 * score_bytes / bw * 1e6) if sel else None,
+            'all_equal_level0_eager_us': t_eq,
+            'note': 'kernel_us: average device time per kernel name over 20 eager calls (torch device-activity trace); selection_streams_us '
+                    '= topk_hist + topk_compact, the two passes over the scores'}
+
+
 def coder(n=1_000_000):
     """§8f-2: decode (the op in front of loss_bbox) and encode on n RBFoV / BFoV boxes, via the C ABI."""
     import ctypes
@@ -456,8 +544,8 @@ def gaussian(n=1_000_000):
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch coder unbiased variants; none = all)
-    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch get_bboxes coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, get_bboxes=get_bboxes, coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)

@@ -11,7 +11,9 @@ Prints one JSON line with the stage times; `run()` is also used by tests/test_gp
 `run()` is the single-image step and keeps the few torch lines of `_get_targets_single` between the assigner and the loss
 (boolean-mask indexing and `int(pos.sum())`: host synchronisations).  `run_batch()` is the minibatch step built on
 `sph_anchor_targets`: one call from the boxes to the loss's targets and a device `avg_factor`, no synchronisation — the
-sync-free one, and the one that captures into a hipGraph (tests/test_gpu_anchor_targets.py).
+sync-free one, and the one that captures into a hipGraph (tests/test_gpu_anchor_targets.py).  `run_batch_infer()` is the
+minibatch inference step built on `sph_get_bboxes`, from the head's NCHW outputs to padded detections, equally sync-free
+(tests/test_gpu_get_bboxes.py).
 """
 import json
 import math
@@ -139,9 +141,54 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels)
 
 
+LEVEL_SHAPES = ((64, 128), (32, 64), (16, 32), (8, 16), (4, 8))   # the 512 x 1024 ERP at strides 8 ... 128
+
+
+def retina_level_anchors(device='cuda'):
+    """`retina_anchors()` split by level and ordered as the head's outputs are, ((h W + w) A + a): 5 tensors (H W 9, 4)."""
+    flat, out, lo = retina_anchors(device=device), [], 0
+    for h, w in LEVEL_SHAPES:
+        out.append(flat[lo:lo + 9 * h * w].reshape(9, h * w, 4).permute(1, 0, 2).reshape(-1, 4).contiguous())
+        lo += 9 * h * w
+    return out
+
+
+def head_outputs(images=8, num_classes=37, dim=4, seed=0, device='cuda', sparse=(8, 8, 8, 256, 64)):
+    """Synthetic head outputs in the head's NCHW: probabilities u ** p per level (p = 8: a third of the scores above 0.05, far
+    more than nms_pre; the last two levels ~500 each, fewer than nms_pre = 1000) and small deltas."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    cls, box = [], []
+    for (h, w), p in zip(LEVEL_SHAPES, sparse):
+        cls.append(torch.rand((images, 9 * num_classes, h, w), generator=g, device=device) ** p)
+        box.append(torch.randn((images, 9 * dim, h, w), generator=g, device=device) * 0.5)
+    return cls, box
+
+
+def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1):
+    """The inference half of `run()` for a minibatch (SphRetinaHead.get_bboxes over the images): the head's per-level NCHW scores
+    and deltas -> sph_get_bboxes (per-level top-k, decode, NMS, max_per_img) -> padded detections, no synchronisation."""
+    anchors = retina_level_anchors()
+    cls, box = head_outputs(images, num_classes, seed=seed)
+    coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
+
+    def step():
+        return S.sph_get_bboxes(cls, box, anchors, bbox_coder=coder, score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5),
+                                max_per_img=100, iou_calculator=nms_calculator, box_version=4, activation='none')
+    step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        r = step()
+    torch.cuda.synchronize()
+    out = {'anchors': sum(a.size(0) for a in anchors), 'images': images, 'num_dets': r.num_dets.tolist(), 'dets': tuple(r.dets.shape),
+           'nms': nms_calculator, 'get_bboxes_ms': (time.perf_counter() - t0) / reps * 1e3}
+    return out, dict(result=r, cls_scores=cls, bbox_preds=box, anchors=anchors, coder=coder)
+
+
 if __name__ == '__main__':
     run()                                   # warm-up (lazy initialisation, workspace allocation)
     for backend, nms in (('sph2pob_standard_iou', 'sph2pob_efficient'), ('unbiased_iou', 'unbiased_iou'),
                          ('naive_iou', 'naive_iou')):
         print(json.dumps(run(backend=backend, nms_calculator=nms, reps=5)[0]), flush=True)
     print(json.dumps(run_batch(reps=5)[0]), flush=True)
+    print(json.dumps(run_batch_infer(reps=5)[0]), flush=True)
