@@ -327,7 +327,7 @@ int sph2pob_planar_iou_f32_cpu(const float* p1, int64_t m, const float* p2, int6
         for (int64_t e = lo; e < hi; e++) {
             const float* a = p1 + (aligned ? e : e / n) * 5;
             const float* b = p2 + (aligned ? e : e % n) * 5;
-            out[e] = planar_iou(PBox{a[0], a[1], a[2], a[3], a[4]}, PBox{b[0], b[1], b[2], b[3], b[4]}, mode);
+            out[e] = planar_iou_given(PBox{a[0], a[1], a[2], a[3], a[4]}, PBox{b[0], b[1], b[2], b[3], b[4]}, mode);
         }
     });
     return SPH2POB_OK;

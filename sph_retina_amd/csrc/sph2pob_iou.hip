@@ -344,6 +344,8 @@ __global__ __launch_bounds__(kBlock) void transform_kernel(const float* __restri
 
 
 // ---- planar rotated IoU on given planar boxes (mmcv box_iou_rotated / diff_iou_rotated_2d values) ----
+// planar_iou_given, not planar_iou: no jitter runs in front of this entry, so coincident and near-parallel edges are its
+// everyday input (sph2pob_device.hpp)
 __global__ __launch_bounds__(kBlock) void planar_iou_kernel(const float* __restrict__ p1, int64_t m, const float* __restrict__ p2,
                                                            int64_t n, float* __restrict__ out, int aligned, int mode) {
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void planar_iou_kernel(const float* __restr
     const float* a = p1 + i * 5;
     const float* b = p2 + j * 5;
     const PBox A{a[0], a[1], a[2], a[3], a[4]}, B{b[0], b[1], b[2], b[3], b[4]};
-    out[aligned ? j : i * n + j] = planar_iou(A, B, mode);
+    out[aligned ? j : i * n + j] = planar_iou_given(A, B, mode);
 }
 
 // ---- adjoint of the Sph2Pob transform: gradients of the planar boxes -> gradients of the spherical boxes ----

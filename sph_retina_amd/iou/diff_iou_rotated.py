@@ -6,6 +6,16 @@
         value-equivalent the reference's own script calls directly (tests/test_all_ious.py:22-24)
 
 Both are served by `sph2pob_planar_iou_f32` (boundary-integral clip; boxes (x, y, w, h, a) with the angle in radians).
+
+No jitter runs in front of this op (the Sph2Pob path has one), so it is built for the boxes detections are made of and is
+held, per pair, to the exact clip in float64 within max(5e-6, 4 x that clip's own float32 noise) on them
+(tests/test_planar_degenerate_host.py, tests/test_gpu_planar_degenerate.py): identical boxes (1), a box inside another on
+shared edge lines, boxes slid along a common axis, touching boxes (0), integer grids, the same rectangle in another spelling
+((w, h, a), (h, w, a + pi / 2), a + pi, a + 2 pi k: one input after the quarter-turn reduction of the angle difference),
+angle differences down to 1e-7 rad from any quarter turn.  Every value is finite and in [0, 1], for 'iou' and 'iof'.
+Convention for boxes without area (w = 0 or h = 0): their intersection with anything has no area, so the value is 0, also
+where the union is 0 (0 / 0) and for 'iof' of a zero-area first box.  A NaN or infinite coordinate gives NaN.  Negative
+sizes are outside the domain.
 Values only: the differentiable use of this op inside the reference — the IoU-family losses — is fused end to end in
 `sph_retina_amd.losses` (forward and hand-derived backward in one kernel each), so a tensor that requires grad is
 rejected here instead of silently returning a constant.

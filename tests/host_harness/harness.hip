@@ -101,11 +101,21 @@ int harness_near_parallel_iou(const float* p1, const float* p2, int64_t n, float
     }
     return 0;
 }
+// planar_iou: the planar stage of the Sph2Pob path, which always has jitter_rotated in front of it (coincident edges are
+// outside its domain).  The stand-alone op on given boxes is planar_iou_given: harness_planar_iou_given below.
 int harness_planar_iou(const float* p1, const float* p2, int64_t n, int mode, float* out) {
     for (int64_t i = 0; i < n; i++) {
         PBox A{p1[i * 5], p1[i * 5 + 1], p1[i * 5 + 2], p1[i * 5 + 3], p1[i * 5 + 4]};
         PBox B{p2[i * 5], p2[i * 5 + 1], p2[i * 5 + 2], p2[i * 5 + 3], p2[i * 5 + 4]};
         out[i] = planar_iou(A, B, mode);
+    }
+    return 0;
+}
+int harness_planar_iou_given(const float* p1, const float* p2, int64_t n, int mode, float* out) {
+    for (int64_t i = 0; i < n; i++) {
+        PBox A{p1[i * 5], p1[i * 5 + 1], p1[i * 5 + 2], p1[i * 5 + 3], p1[i * 5 + 4]};
+        PBox B{p2[i * 5], p2[i * 5 + 1], p2[i * 5 + 2], p2[i * 5 + 3], p2[i * 5 + 4]};
+        out[i] = planar_iou_given(A, B, mode);
     }
     return 0;
 }

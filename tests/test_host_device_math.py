@@ -17,8 +17,10 @@ def test_boundary_integral_intersection_vs_exact_clip(host_harness, oracle):
     assert s['max'] < 5e-6 and s['mean'] < 2e-7, s
     assert ((got == 0) == (truth == 0)).mean() > 0.999
     # disjoint / contained after a 90-degree turn / exactly parallel edges (rcp(0) = inf path) / contained / cross.
-    # Exactly COINCIDENT edges are outside the function's domain: jiter_rotated_bboxes always runs first and
-    # separates sizes by 1.2e-4 and angles by >= 1.2e-3 (sph_iou_api.py:222-242).
+    # host_harness.planar_iou is the planar stage of the Sph2Pob path: jiter_rotated_bboxes always runs in front of it and
+    # separates sizes by 1.2e-4 and angles by >= 1.2e-3 (sph_iou_api.py:222-242), so exactly COINCIDENT edges never reach
+    # it.  They do reach the stand-alone op (box_iou_rotated on given boxes), which is planar_iou_given: below, and
+    # tests/test_planar_degenerate_host.py.
     a = np.array([[0, 0, 2, 1, 0.3], [0, 0, 2, 1, 0.0], [0, 0, 2, 1, 0.0], [0, 0, 4, 4, 0.0], [0, 0, 2, 1, 0.0]],
                  np.float32)
     b = np.array([[5, 5, 1, 1, 1.0], [0, 0, 1.2, 2.2, np.pi / 2], [0.5, 0.1, 2, 1.4, 0.0], [0.2, -0.1, 1, 1, 0.7],
@@ -26,6 +28,25 @@ def test_boundary_integral_intersection_vs_exact_clip(host_harness, oracle):
     np.testing.assert_allclose(host_harness.planar_iou(a, b), [0.0, 2 / 2.64, 1.5 / 3.3, 1.0 / 16.0, 1.0 / 3.0],
                                atol=2e-6)
     np.testing.assert_allclose(host_harness.planar_iou(b, a, mode='iof')[3], 1.0, atol=2e-6)
+    # the stand-alone op: the same five pairs, then an identical pair, the same rectangle in its other spelling and a
+    # contained box on one of the outer box's edge lines (exact values: the axis-aligned branch has no rounding to speak of)
+    a2 = np.concatenate([a, np.array([[1, -2, 2, 1, 0.3], [0, 0, 2, 1, 0.0], [0, 0, 4, 2, 0.0]], np.float32)])
+    b2 = np.concatenate([b, np.array([[1, -2, 2, 1, 0.3], [0, 0, 1, 2, np.pi / 2], [1, 0.5, 2, 1, 0.0]], np.float32)])
+    given = _planar_iou_given(a2, b2)
+    np.testing.assert_allclose(given[:5], [0.0, 2 / 2.64, 1.5 / 3.3, 1.0 / 16.0, 1.0 / 3.0], atol=2e-6)
+    np.testing.assert_allclose(given[5:], [1.0, 1.0, 0.25], atol=2e-7, rtol=0)
+    np.testing.assert_allclose(_planar_iou_given(b2, a2, mode='iof')[[3, 5, 6, 7]], 1.0, atol=2e-6)
+
+
+def _planar_iou_given(p1, p2, mode='iou'):
+    """planar_iou_given through the host harness (built by the host_harness fixture)."""
+    import ctypes
+    lib = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'host_harness', '_build', 'libhost_harness.so'))
+    p1, p2 = np.ascontiguousarray(p1, np.float32), np.ascontiguousarray(p2, np.float32)
+    out = np.empty(p1.shape[0], np.float32)
+    lib.harness_planar_iou_given(p1.ctypes.data_as(ctypes.c_void_p), p2.ctypes.data_as(ctypes.c_void_p),
+                                 ctypes.c_int64(p1.shape[0]), {'iou': 0, 'iof': 1}[mode], out.ctypes.data_as(ctypes.c_void_p))
+    return out
 
 
 @pytest.mark.parametrize('name,variants', [('uniform_bfov', ['standard', 'efficient', 'legacy']),
