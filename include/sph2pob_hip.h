@@ -65,7 +65,9 @@ enum {
     SPH2POB_ERR_SIZE = -4     /* negative count or a product that overflows the launch geometry */
 };
 
-/* Library identification: ABI version (bumped on any signature change) and the code-object target. */
+/* Library identification: ABI version (bumped on any signature change or new entry point; sph2pob_abi_version() returns the
+ * value the library was built with) and the code-object target. */
+#define SPH2POB_ABI_VERSION 2
 int sph2pob_abi_version(void);
 const char* sph2pob_target_arch(void);
 const char* sph2pob_error_string(int code);
@@ -462,6 +464,63 @@ int sph2pob_obb_l1_fwd_f32(const float* planar_pred, const float* planar_target,
 int sph2pob_obb_l1_bwd_f32(const float* planar_pred, const float* planar_target, const float* weight,
                            const float* grad_loss, float scale, float* grad_pred, float* grad_target, int64_t n,
                            int flags, void* stream);
+
+/* ---- sigmoid focal loss: the classification half of SphRetinaHead.loss_single -------------------------------------------
+ * Replaces FocalLoss(use_sigmoid=True) (mmdet/models/losses/focal_loss.py:159-244), i.e. mmcv.ops.sigmoid_focal_loss + the
+ * weight step and reduction of weight_reduce_loss (mmdet/models/losses/utils.py:30-58), and the
+ * cls_score.permute(0, 2, 3, 1).reshape(-1, C) copy in front of it (sphdet/models/heads/sph_retina_head.py:247-248).
+ * Per element, x = logit, t = (label == c), in the logit-stable form (z = t ? -x : x, e = exp(-|z|), q = sigmoid(z) and
+ * sigmoid(-z) both from e, s = softplus(z) = max(z, 0) + log1p(e), a = t ? alpha : 1 - alpha):
+ *     L = a q^gamma s,    dL/dz = a q^gamma (q + gamma sigmoid(-z) s),    dL/dx = t ? -dL/dz : dL/dz
+ * which is py_sigmoid_focal_loss (focal_loss.py:12-57) in exact arithmetic; it differs from mmcv's kernel only where that kernel
+ * clamps log at FLT_MIN (logits beyond about +-16 on the wrong side).  gamma >= 0; 2 and 0 are multiplications, a general gamma
+ * takes its integer part as multiplications and the rest through exp2(frac * log2 q).  A label is only ever COMPARED with the
+ * class index: any value outside [0, C) (the background label C, -1, ...) means that no class of the row is positive.
+ * weight_mode: NONE; ROW: weight (B, n) per anchor; ELEM: weight in logical (B, n, C) order.
+ *
+ * sph2pob_focal_loss_sum_f32 — the training call, for all levels of a head at once.  Level tables are HOST arrays of
+ * num_levels <= 8 entries, as for sph2pob_get_bboxes_f32:
+ *   logits       device pointers, level l either the head's NCHW (B, A C, H_l, W_l), read in place, or the flattened
+ *                (B, n_l, C); anchor i of a level is (h W + w) A + a, its class c is channel a C + c.  (N, C): one level, B = 1
+ *   grads        NULL (forward only), or device pointers laid out exactly like logits that receive
+ *                scale_eff * w * dL/dx: the gradient of out[0] for an upstream gradient of 1
+ *   level_n      n_l = H_l W_l A anchors (>= 0);  level_hw: H_l W_l for NCHW, 0 for the flattened layout (NULL: all flattened)
+ *   labels       (B, n) int64, n = sum n_l, rows in level order: what sph2pob_anchor_targets_f32 writes; weight likewise
+ *   scale        host factor (loss_weight, possibly over a host divisor); avg_factor: NULL, or a DEVICE float: then
+ *                scale_eff = scale / (*avg_factor + FLT_EPSILON) (one fp32 division), else scale_eff = scale
+ *   out          (1) f32 = scale_eff * sum w L.  The weighted element losses are added in double, one partial per workgroup in
+ *                `workspace`, and the partials in a fixed order by one workgroup: no float atomics, the same bits on every call
+ *   workspace    sph2pob_focal_loss_workspace_bytes(level_n, level_hw, num_levels, B, C) bytes (0: shapes not accepted), no
+ *                initialisation
+ * Two launches whatever B and the number of levels are; nothing is read back, nothing is allocated.  NCHW levels whose H W is a
+ * multiple of 4 and whose pointers are 16-byte aligned are walked with 16-byte accesses, the others with the same arithmetic
+ * one element at a time.  B n C == 0 writes out[0] = 0.
+ * Errors, checked in this order before anything is enqueued: gamma < 0 (or NaN), weight_mode -> SPH2POB_ERR_OPTION; num_levels
+ * outside [1, 8], B outside [0, 65 535], C outside [1, 2^24] -> SPH2POB_ERR_SIZE; a NULL level_n / logits table ->
+ * SPH2POB_ERR_NULL; n_l < 0, level_hw that does not divide n_l, B n_l C >= 2^31 - 4096 -> SPH2POB_ERR_SIZE; a NULL table entry of
+ * a level with elements, out, workspace, labels or (weight_mode != NONE) weight with elements -> SPH2POB_ERR_NULL.
+ *
+ * sph2pob_focal_loss_fwd_f32: loss[i, c] = scale * w * L on a flat (n, C) input (reduction 'none').
+ * sph2pob_focal_loss_bwd_f32: grad_logits[i, c] = grad_out[(i C + c) * grad_stride] * scale_eff * w * dL/dx (grad_stride 0: one
+ * device scalar, 1: per element) — reduction 'none', and a second backward through a retained graph.
+ * sph2pob_focal_loss_grad_scale_f32: out[e] = stash[e] * grad_out[0], e < total; out may be the stash (in place), and in place
+ * with grad_out[0] == 1 the launch returns after one scalar load per workgroup, as sph2pob_loss_grad_scale_f32 does.
+ * The flat entries: weight_mode, gamma, grad_stride -> SPH2POB_ERR_OPTION; n < 0, C <= 0, n C > 2^38 -> SPH2POB_ERR_SIZE; n == 0
+ * is a no-op; a NULL pointer with work to do -> SPH2POB_ERR_NULL.
+ */
+enum { SPH2POB_FOCAL_WEIGHT_NONE = 0, SPH2POB_FOCAL_WEIGHT_ROW = 1, SPH2POB_FOCAL_WEIGHT_ELEM = 2 };
+int64_t sph2pob_focal_loss_workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                           int64_t num_classes);
+int sph2pob_focal_loss_sum_f32(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                               int num_levels, int64_t num_images, int64_t num_classes, const int64_t* labels, const float* weight,
+                               int weight_mode, float gamma, float alpha, float scale, const float* avg_factor, float* out,
+                               void* workspace, void* stream);
+int sph2pob_focal_loss_fwd_f32(const float* logits, const int64_t* labels, const float* weight, int weight_mode, float gamma, float alpha,
+                               float scale, float* loss, int64_t n, int64_t num_classes, void* stream);
+int sph2pob_focal_loss_bwd_f32(const float* logits, const int64_t* labels, const float* weight, int weight_mode, const float* grad_out,
+                               int grad_stride, float gamma, float alpha, float scale, const float* avg_factor, float* grad_logits,
+                               int64_t n, int64_t num_classes, void* stream);
+int sph2pob_focal_loss_grad_scale_f32(const float* stash, const float* grad_out, float* out, int64_t total, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@
 #include "sph2pob_unbiased.hpp"
 #include "sph2pob_coder.hpp"
 #include "sph2pob_get_bboxes.hpp"
+#include "sph2pob_focal.hpp"
 
 namespace {
 
@@ -792,6 +793,111 @@ int sph2pob_obb_l1_bwd_f32_cpu(const float* planar_pred, const float* planar_tar
             if (grad_target)
                 for (int k = 0; k < 5; k++) grad_target[i * 5 + k] = gb[k];
         }
+    });
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- sigmoid focal loss: the twins of sph2pob_focal.hip on the element function of sph2pob_focal.hpp ----
+namespace {
+namespace FL = sph2pob_focal;
+constexpr int64_t kFocalRows = 1024;   // rows of one partial sum: the partials do not move with the thread count
+}  // namespace
+
+extern "C" {
+
+int sph2pob_focal_loss_sum_f32_cpu(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                   int num_levels, int64_t num_images, int64_t num_classes, const int64_t* labels, const float* weight,
+                                   int weight_mode, float gamma, float alpha, float scale, const float* avg_factor, float* out,
+                                   void* workspace, void*) {
+    FL::Levels L;
+    if (int rc = FL::make_levels(logits, grads, level_n, level_hw, num_levels, num_images, num_classes, weight_mode, gamma, true, &L)) return rc;
+    if (!out || !workspace || (L.elems > 0 && (!labels || (weight_mode != 0 && !weight)))) return SPH2POB_ERR_NULL;
+    const FL::Params P = FL::make_params(gamma, alpha);
+    const float k0 = FL::effective_scale(scale, avg_factor);
+    const int64_t rows = L.elems > 0 ? num_images * L.n_total : 0, C = num_classes;
+    const int64_t chunks = (rows + kFocalRows - 1) / kFocalRows;
+    std::vector<double> part((size_t)chunks, 0.0);
+    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
+        for (int64_t ch = lo; ch < hi; ch++) {
+            double acc = 0.0;
+            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
+                const int64_t b = row / L.n_total, j = row - b * L.n_total;
+                int l = 0;
+                for (int q = 1; q < L.num; q++) l += j >= L.lv[q].row_off ? 1 : 0;
+                const FL::Level& lv = L.lv[l];
+                const int64_t i = j - lv.row_off;
+                int64_t base, stride;   // element (row, c) = base + c * stride
+                if (lv.hw > 0) {
+                    const int64_t p = i / lv.a, a = i - p * lv.a;
+                    base = (b * lv.a + a) * C * lv.hw + p; stride = lv.hw;
+                } else {
+                    base = (b * lv.n + i) * C; stride = 1;
+                }
+                const int64_t lab = labels[row];
+                for (int c = 0; c < (int)C; c++) {
+                    float loss, dx;
+                    FL::element(lv.logits[base + c * stride], lab == (int64_t)c, P, loss, dx);
+                    const float we = FL::weight_of(weight, weight_mode, row, C, c);
+                    acc += (double)(loss * we);
+                    if (lv.grad) lv.grad[base + c * stride] = (k0 * we) * dx;
+                }
+            }
+            part[(size_t)ch] = acc;
+        }
+    });
+    double total = 0.0;
+    for (double v : part) total += v;
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+int sph2pob_focal_loss_fwd_f32_cpu(const float* logits, const int64_t* labels, const float* weight, int weight_mode, float gamma,
+                                   float alpha, float scale, float* loss, int64_t n, int64_t num_classes, void*) {
+    if (int rc = FL::flat_check(n, num_classes, weight_mode, gamma, 0)) return rc;
+    if (n == 0) return SPH2POB_OK;
+    if (!logits || !labels || !loss || (weight_mode != 0 && !weight)) return SPH2POB_ERR_NULL;
+    const FL::Params P = FL::make_params(gamma, alpha);
+    parallel_for(n, 1 << 10, [&](int64_t lo, int64_t hi) {
+        for (int64_t row = lo; row < hi; row++)
+            for (int c = 0; c < (int)num_classes; c++) {
+                float l, dx;
+                FL::element(logits[row * num_classes + c], labels[row] == (int64_t)c, P, l, dx);
+                loss[row * num_classes + c] = (scale * FL::weight_of(weight, weight_mode, row, num_classes, c)) * l;
+            }
+    });
+    return SPH2POB_OK;
+}
+
+int sph2pob_focal_loss_bwd_f32_cpu(const float* logits, const int64_t* labels, const float* weight, int weight_mode, const float* grad_out,
+                                   int grad_stride, float gamma, float alpha, float scale, const float* avg_factor, float* grad_logits,
+                                   int64_t n, int64_t num_classes, void*) {
+    if (int rc = FL::flat_check(n, num_classes, weight_mode, gamma, grad_stride)) return rc;
+    if (n == 0) return SPH2POB_OK;
+    if (!logits || !labels || !grad_out || !grad_logits || (weight_mode != 0 && !weight)) return SPH2POB_ERR_NULL;
+    const FL::Params P = FL::make_params(gamma, alpha);
+    const float k0 = FL::effective_scale(scale, avg_factor);
+    parallel_for(n, 1 << 10, [&](int64_t lo, int64_t hi) {
+        for (int64_t row = lo; row < hi; row++)
+            for (int c = 0; c < (int)num_classes; c++) {
+                const int64_t e = row * num_classes + c;
+                float l, dx;
+                FL::element(logits[e], labels[row] == (int64_t)c, P, l, dx);
+                grad_logits[e] = grad_out[grad_stride ? e : 0] * ((k0 * FL::weight_of(weight, weight_mode, row, num_classes, c)) * dx);
+            }
+    });
+    return SPH2POB_OK;
+}
+
+int sph2pob_focal_loss_grad_scale_f32_cpu(const float* stash, const float* grad_out, float* out, int64_t total, void*) {
+    if (total < 0 || total > ((int64_t)1 << 38)) return SPH2POB_ERR_SIZE;
+    if (total == 0) return SPH2POB_OK;
+    if (!stash || !grad_out || !out) return SPH2POB_ERR_NULL;
+    const float s = grad_out[0];
+    if (out == stash && s == 1.0f) return SPH2POB_OK;
+    parallel_for(total, 1 << 16, [&](int64_t lo, int64_t hi) {
+        for (int64_t e = lo; e < hi; e++) out[e] = stash[e] * s;
     });
     return SPH2POB_OK;
 }

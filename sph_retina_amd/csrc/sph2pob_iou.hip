@@ -453,7 +453,7 @@ struct TransformLaunch {
 extern "C" {
 
 
-int sph2pob_abi_version(void) { return 1; }
+int sph2pob_abi_version(void) { return SPH2POB_ABI_VERSION; }
 const char* sph2pob_target_arch(void) { return "gfx950"; }
 
 const char* sph2pob_error_string(int code) {

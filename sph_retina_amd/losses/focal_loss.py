@@ -1,0 +1,325 @@
+"""Sigmoid focal loss — the classification half of `SphRetinaHead.loss_single` — as ONE fused pass.
+
+The reference's `FocalLoss` (mmdet/models/losses/focal_loss.py:159-244; every sph_* config: gamma=2.0, alpha=0.25) calls
+`mmcv.ops.sigmoid_focal_loss` on `cls_score.permute(0, 2, 3, 1).reshape(-1, C)` (sphdet/models/heads/sph_retina_head.py:247-248).
+Here the kernel reads the head's NCHW logits where they are, reads `labels` / `label_weights` as `sph_anchor_targets` wrote them,
+writes the gradient back in the head's layout and takes the divisor from the device:
+
+    sph_focal_loss(cls_scores, labels, label_weights, avg_factor=targets.avg_factor)   # L levels, one autograd node
+    sigmoid_focal_loss(pred, target, weight, ...) / FocalLoss                          # the reference's flat (N, C) surface
+
+Arithmetic (csrc/sph2pob_focal.hpp): the logit-stable form — z = t ? -x : x, e = exp(-|z|), q = sigmoid(z) and sigmoid(-z)
+both from e, loss = a q^gamma softplus(z) — which equals `py_sigmoid_focal_loss` (focal_loss.py:12-57) in exact arithmetic and
+differs from mmcv's kernel only where that kernel clamps `log` at FLT_MIN (logits beyond about +-16 on the wrong side); parity
+with mmcv's binary is UNPINNED, as for every third-party op here.  A label is only compared with the class index: any value
+outside [0, C) (the background label C, -1) means no class of the row is positive.
+
+The sum is deterministic (double partials per workgroup, fixed-order final pass, no float atomics); a device-tensor
+`avg_factor` goes to the kernel as a pointer, so the call neither synchronises nor allocates on the host's say-so and can be
+captured in a graph.  Difference from the reference: `avg_factor` is a count, no gradient flows into it.
+"""
+import ctypes
+import struct
+
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from .. import _torch_glue as G
+from ..registry import LOSSES, LOSSES_IS_MMDET
+
+_MAX_LEVELS = 8
+_F32_EPS = float(torch.finfo(torch.float32).eps)
+_WEIGHT_NONE, _WEIGHT_ROW, _WEIGHT_ELEM = 0, 1, 2
+
+
+def _f32(v):
+    """v rounded to fp32 (as a Python float)."""
+    return struct.unpack('f', struct.pack('f', v))[0]
+
+
+def _host_scale(loss_weight, divisor):
+    """loss_weight / (divisor + eps) with the fp32 roundings the kernel applies to a device divisor, so that a Python number and
+    the same value in a device tensor give the same bits (each double operation on fp32 operands rounds to fp32 correctly)."""
+    return _f32(_f32(loss_weight) / _f32(_f32(divisor) + _F32_EPS))
+
+
+def _f32c(t):
+    return t if t.dtype is torch.float32 and t.is_contiguous() else G.as_f32(t.detach())
+
+
+def _labels(t):
+    t = t.detach() if t.requires_grad else t
+    return t if t.dtype is torch.int64 and t.is_contiguous() else t.to(torch.int64).contiguous()
+
+
+def _avg_tensor(avg_factor, dev):
+    a = avg_factor.detach().reshape(-1)
+    if a.numel() != 1:
+        raise ValueError(f'avg_factor must hold one value, got {tuple(avg_factor.shape)}')
+    if a.device != dev:
+        raise RuntimeError(f'avg_factor is on {a.device}, the logits on {dev}: a tensor divisor must live with the logits')
+    return a if a.dtype is torch.float32 else a.float()
+
+
+def _workspace(dev, ns, hws, images, classes):
+    levels = len(ns)
+    i64s = ctypes.c_int64 * levels
+    need = _lib.lib().sph2pob_focal_loss_workspace_bytes(i64s(*ns), i64s(*hws), levels, images, classes)
+    if need <= 0:
+        raise ValueError('focal loss: these shapes are outside the limits of sph2pob_focal_loss_sum_f32 (include/sph2pob_hip.h)')
+    return G.scratch(dev, need)
+
+
+class _FocalSumFunction(torch.autograd.Function):
+    """(C, labels, weight, ..., *logits of L levels) -> scale_eff * sum of the weighted element losses; one node with L inputs.
+    When a gradient will be asked for, the one forward pass also writes the gradients for an upstream gradient of 1 (all levels
+    in one buffer, each in its own layout), and torch's backward only scales that stash
+    (`sph2pob_focal_loss_grad_scale_f32`: in place, a plain `loss.backward()` returns at once).  A second backward through a
+    retained graph recomputes: the two-pass kernel for one flat level, the fused pass into a fresh buffer otherwise."""
+
+    @staticmethod
+    def forward(ctx, classes, labels, weight, wmode, gamma, alpha, scale, avg, hws, *scores):
+        levels = len(scores)
+        xs = [_f32c(s) for s in scores]
+        dev = xs[0].device
+        images = xs[0].size(0)
+        ctx.classes = classes
+        ns = [x.numel() // (images * classes) if images else 0 for x in xs]
+        need = any(ctx.needs_input_grad[9:])
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        ptrs, i64s = ctypes.c_void_p * levels, ctypes.c_int64 * levels
+        ws = _workspace(dev, ns, hws, images, classes)
+        stash = views = None
+        if need:
+            stash, views = _FocalSumFunction._grad_buffer(xs)
+        G.call('sph2pob_focal_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if need else None,
+               i64s(*ns), i64s(*hws), levels, images, classes, G.ptr(labels), G.ptr(weight), wmode, gamma, alpha, scale, G.ptr(avg),
+               out.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
+        if need:
+            ctx.save_for_backward(stash, labels, weight, avg, *xs)
+            ctx.views = views
+            ctx.first = True
+        ctx.meta = (wmode, gamma, alpha, scale, tuple(hws), tuple(ns), [s.dtype for s in scores])
+        return out
+
+    @staticmethod
+    def _grad_buffer(xs):
+        """One buffer for the gradients of all levels (a single scaling launch in backward), each level a 16-byte aligned view."""
+        offs, total = [], 0
+        for x in xs:
+            offs.append(total)
+            total += (x.numel() + 3) // 4 * 4
+        stash = torch.empty((total,), dtype=torch.float32, device=xs[0].device)
+        return stash, [stash[o:o + x.numel()].view(x.shape) for o, x in zip(offs, xs)]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        stash, labels, weight, avg, *xs = ctx.saved_tensors
+        wmode, gamma, alpha, scale, hws, ns, dtypes = ctx.meta
+        dev = stash.device
+        g = _f32c(grad_out).reshape(1)
+        stream = G.raw_stream_of(dev)
+        levels = len(xs)
+        if ctx.first:
+            ctx.first = False
+            views = ctx.views
+            G.call('sph2pob_focal_loss_grad_scale_f32', dev, G.ptr(stash), g.data_ptr(), G.ptr(stash), stash.numel(), stream)
+        elif levels == 1 and hws[0] == 0:
+            # the stash was scaled in place and handed to autograd by the first backward: the two-pass kernel
+            views = [torch.empty_like(xs[0])]
+            G.call('sph2pob_focal_loss_bwd_f32', dev, G.ptr(xs[0]), G.ptr(labels), G.ptr(weight), wmode, g.data_ptr(), 0, gamma, alpha,
+                   scale, G.ptr(avg), G.ptr(views[0]), xs[0].numel() // ctx.classes, ctx.classes, stream)
+        else:
+            fresh, views = _FocalSumFunction._grad_buffer(xs)
+            images = xs[0].size(0)
+            ptrs, i64s = ctypes.c_void_p * levels, ctypes.c_int64 * levels
+            out, ws = torch.empty((), dtype=torch.float32, device=dev), _workspace(dev, ns, hws, images, ctx.classes)   # held over the call
+            G.call('sph2pob_focal_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]), i64s(*ns), i64s(*hws),
+                   levels, images, ctx.classes, G.ptr(labels), G.ptr(weight), wmode, gamma, alpha, scale, G.ptr(avg), out.data_ptr(), G.ptr(ws),
+                   stream)
+            G.call('sph2pob_focal_loss_grad_scale_f32', dev, G.ptr(fresh), g.data_ptr(), G.ptr(fresh), fresh.numel(), stream)
+        grads = [(v if dt is torch.float32 else v.to(dt)) if need else None
+                 for v, dt, need in zip(views, dtypes, ctx.needs_input_grad[9:])]
+        return (None,) * 9 + tuple(grads)
+
+
+class _FocalNoneFunction(torch.autograd.Function):
+    """(pred (N, C), labels, weight) -> scale * weighted element losses (N, C): reduction 'none'; the backward is the two-pass
+    kernel on a per-element upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, labels, weight, wmode, gamma, alpha, scale):
+        x = _f32c(pred)
+        n, c = x.shape
+        out = torch.empty_like(x)
+        if n:
+            G.call('sph2pob_focal_loss_fwd_f32', x.device, x.data_ptr(), labels.data_ptr(), G.ptr(weight), wmode, gamma, alpha, scale,
+                   out.data_ptr(), n, c, G.raw_stream_of(x.device))
+        ctx.save_for_backward(x, labels, weight)
+        ctx.meta = (wmode, gamma, alpha, scale, pred.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, labels, weight = ctx.saved_tensors
+        wmode, gamma, alpha, scale, dt = ctx.meta
+        n, c = x.shape
+        g = _f32c(grad_out)
+        gx = torch.empty_like(x)
+        if n:
+            G.call('sph2pob_focal_loss_bwd_f32', x.device, x.data_ptr(), labels.data_ptr(), G.ptr(weight), wmode, g.data_ptr(), 1, gamma,
+                   alpha, scale, None, gx.data_ptr(), n, c, G.raw_stream_of(x.device))
+        return (gx if dt is torch.float32 else gx.to(dt)), None, None, None, None, None, None
+
+
+def _reduce_scale(reduction, avg_factor, loss_weight, elems, dev):
+    """(host scale, device divisor | None, nan) of weight_reduce_loss (mmdet/models/losses/utils.py:30-58)."""
+    if avg_factor is not None and reduction == 'sum':
+        raise ValueError('avg_factor can not be used with reduction="sum"')
+    if reduction == 'sum':
+        return float(loss_weight), None, False
+    if avg_factor is None:
+        if elems == 0:   # torch: the mean of an empty tensor is nan
+            return float(loss_weight), None, True
+        return float(loss_weight) / elems, None, False
+    if isinstance(avg_factor, torch.Tensor):
+        return float(loss_weight), _avg_tensor(avg_factor, dev), False
+    return _host_scale(float(loss_weight), float(avg_factor)), None, False
+
+
+def _check_params(gamma, alpha):
+    gamma, alpha = float(gamma), float(alpha)
+    if not gamma >= 0:
+        raise ValueError(f'gamma must be >= 0, got {gamma}')
+    return gamma, alpha
+
+
+def sigmoid_focal_loss(pred, target, weight=None, gamma=2.0, alpha=0.25, reduction='mean', avg_factor=None, loss_weight=1.0):
+    """loss_weight * weight_reduce_loss(sigmoid focal loss of (pred, target), weight, reduction, avg_factor) — the reference's
+    `sigmoid_focal_loss` (focal_loss.py:113-156).  pred (N, C) logits; target (N,) integer labels, any value outside [0, C) is
+    background; weight (N,), (N, C) or (N * C,); 'mean' without avg_factor divides by N * C; avg_factor may be a number or a
+    device tensor (no host synchronisation)."""
+    if reduction not in ('none', 'mean', 'sum'):
+        raise ValueError(f"reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+    if pred.dim() != 2 or target.dim() != 1 or target.size(0) != pred.size(0) or pred.size(1) == 0:
+        raise ValueError(f'pred must be (N, C) with C > 0 and target (N,), got {tuple(pred.shape)}, {tuple(target.shape)}')
+    if target.dtype.is_floating_point or target.dtype is torch.bool:
+        raise ValueError(f'target must hold integer labels, got {target.dtype}')
+    gamma, alpha = _check_params(gamma, alpha)
+    n, c = pred.shape
+    tensors = [pred, target] + ([weight] if weight is not None else [])
+    G.require_hip(*tensors)
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError('sigmoid_focal_loss: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
+    wmode, w = _WEIGHT_NONE, None
+    if weight is not None:
+        if tuple(weight.shape) == (n, c) or (weight.size(0) != n and weight.numel() == n * c):
+            wmode = _WEIGHT_ELEM
+        elif weight.numel() == n and weight.size(0) == n:
+            wmode = _WEIGHT_ROW
+        else:
+            raise ValueError(f'weight must be (N,), (N, C) or (N * C,), got {tuple(weight.shape)} for pred {tuple(pred.shape)}')
+        w = G.as_f32_nograd(weight)
+    labels = _labels(target)
+    if reduction == 'none':
+        if avg_factor is not None and not isinstance(avg_factor, (int, float, torch.Tensor)):
+            raise TypeError('avg_factor must be a number or a tensor')
+        return _FocalNoneFunction.apply(pred, labels, w, wmode, gamma, alpha, float(loss_weight))
+    scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, n * c, pred.device)
+    out = _FocalSumFunction.apply(c, labels, w, wmode, gamma, alpha, scale, avg, [0], pred.reshape(1, n, c) if pred.is_contiguous() else pred.contiguous().reshape(1, n, c))
+    return out * float('nan') if nan else out
+
+
+def sph_focal_loss(cls_scores, labels, label_weights=None, *, gamma=2.0, alpha=0.25, avg_factor=None, loss_weight=1.0, reduction='mean'):
+    """The classification loss of a whole minibatch from the head's own outputs, as one scalar.
+
+    cls_scores: L <= 8 tensors, each the head's NCHW (B, A*C, H_l, W_l) — read in place — or the flattened (B, n_l, C);
+    labels (B, n) integer and label_weights (B, n) (or (B, n, C), or None) with n = sum n_l in level order, exactly as
+    `AnchorTargets` holds them.  Equals FocalLoss on cat([s.permute(0, 2, 3, 1).reshape(B, -1, C)]).reshape(-1, C) without the
+    copies; the gradient arrives at each cls_scores[l] in its own layout (one autograd node with L inputs).  `avg_factor`: a number
+    or a device tensor such as `AnchorTargets.avg_factor`; 'mean' without it divides by B n C."""
+    if reduction == 'none':
+        raise ValueError("sph_focal_loss returns the reduced scalar ('mean' | 'sum'); for element losses use sigmoid_focal_loss on "
+                         "the flat (N, C) logits")
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    cls_scores = list(cls_scores)
+    if not (1 <= len(cls_scores) <= _MAX_LEVELS):
+        raise ValueError(f'sph_focal_loss takes 1 to {_MAX_LEVELS} levels, got {len(cls_scores)}')
+    gamma, alpha = _check_params(gamma, alpha)
+    if labels.dim() != 2 or labels.dtype.is_floating_point or labels.dtype is torch.bool:
+        raise ValueError(f'labels must be (B, n) integer labels, got {tuple(labels.shape)} {labels.dtype}')
+    tensors = cls_scores + [labels] + ([label_weights] if label_weights is not None else [])
+    G.require_hip(*tensors)
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError('sph_focal_loss: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
+    images, n = labels.shape
+    if label_weights is None:
+        wmode, classes = _WEIGHT_NONE, None
+    elif tuple(label_weights.shape) == (images, n):
+        wmode, classes = _WEIGHT_ROW, None
+    elif label_weights.dim() == 3 and tuple(label_weights.shape[:2]) == (images, n):
+        wmode, classes = _WEIGHT_ELEM, label_weights.size(2)
+    else:
+        raise ValueError(f'label_weights must be (B, n) or (B, n, C) like labels {tuple(labels.shape)}, got {tuple(label_weights.shape)}')
+    hws, total = [], 0
+    for l, s in enumerate(cls_scores):
+        if s.dim() not in (3, 4) or s.size(0) != images:
+            raise ValueError(f'cls_scores[{l}]: expected (B, A * C, H, W) or (B, n_l, C) with B = {images}, got {tuple(s.shape)}')
+        hws.append(s.size(2) * s.size(3) if s.dim() == 4 else 0)
+    # the class count: from flattened levels or per-element weights where there are any; else from the anchors per position,
+    # which sum n_l = n fixes: sum_l (channels_l * hw_l) = n * C
+    flat_c = {s.size(2) for s in cls_scores if s.dim() == 3}
+    if classes is not None:
+        flat_c.add(classes)
+    if len(flat_c) > 1:
+        raise ValueError(f'the class count differs across levels / weights: {sorted(flat_c)}')
+    if flat_c:
+        classes = flat_c.pop()
+    else:
+        per_image = sum(s.size(1) * hw for s, hw in zip(cls_scores, hws))
+        if n == 0 or per_image % n != 0:
+            raise ValueError(f'the levels hold {per_image} scores per image, which {n} anchors (labels.size(1)) do not divide')
+        classes = per_image // n
+    if classes <= 0:
+        raise ValueError('the class count must be positive')
+    for l, s in enumerate(cls_scores):
+        if s.dim() == 4 and s.size(1) % classes != 0:
+            raise ValueError(f'cls_scores[{l}]: {s.size(1)} channels are not a multiple of C = {classes} (C must be equal across levels)')
+        total += s.size(1) // classes * hws[l] if s.dim() == 4 else s.size(1)
+    if total != labels.size(1):
+        raise ValueError(f'the levels hold {total} anchors per image, labels {labels.size(1)}')
+    scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n * classes, labels.device)
+    w = G.as_f32_nograd(label_weights) if label_weights is not None else None
+    out = _FocalSumFunction.apply(classes, _labels(labels), w, wmode, gamma, alpha, scale, avg, hws, *cls_scores)
+    return out * float('nan') if nan else out
+
+
+class FocalLoss(nn.Module):
+    """The reference's FocalLoss (focal_loss.py:159-244): same constructor and `forward`; sigmoid logits only, served by the fused
+    kernels on MI355X and CPU tensors alike.  `dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0)`
+    builds it through this package's registry when mmdet is absent; with mmdet importable it is registered as `SphFocalLoss`
+    and mmdet's own class keeps its name."""
+
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.25, reduction='mean', loss_weight=1.0, activated=False):
+        super().__init__()
+        assert use_sigmoid is True, 'Only sigmoid focal loss supported now.'
+        if activated:
+            raise NotImplementedError('FocalLoss(activated=True) takes probabilities (py_focal_loss_with_prob): not part of the fused '
+                                      'kernels — use the per-image torch route (binary_cross_entropy on the probabilities)')
+        self.use_sigmoid = use_sigmoid
+        self.gamma = gamma
+        self.alpha = alpha
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+        self.activated = activated
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        return sigmoid_focal_loss(pred, target, weight, gamma=self.gamma, alpha=self.alpha, reduction=reduction, avg_factor=avg_factor,
+                                  loss_weight=self.loss_weight)
+
+
+LOSSES.register_module(name='SphFocalLoss' if LOSSES_IS_MMDET else 'FocalLoss', force=True, module=FocalLoss)

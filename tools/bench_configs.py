@@ -409,6 +409,87 @@ def get_bboxes(images=8, rounds=7):
                     '= topk_hist + topk_compact, the two passes over the scores'}
 
 
+def focal(images=8, classes=37, rounds=7):
+    """The classification loss of a minibatch (sph_focal_loss) at the reference's test shape — 512 x 1024 ERP, 5 levels, 9 anchors,
+    37 classes, gamma 2, alpha 0.25, row weights, a device avg_factor — forward + backward on the head's NCHW logits: (a) eager;
+    (b) the same replayed from a graph; (c) the torch composition a user runs without the kernel (permute / reshape / cat, the
+    reference formula, sum / avg_factor; forward + backward).  Timed in alternation `rounds` times, medians and spreads reported.
+    The fused kernel's device time is set against 2 x 4 x B n C bytes (each logit read once, each gradient written once) over
+    the bandwidth of a device copy of the same tensors measured here (the method of tools/ubench/stream_floor.hip)."""
+    import torch.nn.functional as F
+    import demo_hot_path as D
+    g = torch.Generator(device='cuda').manual_seed(0)
+    cls = [(torch.randn((images, 9 * classes, h, w), generator=g, device='cuda') * 2 - 4).requires_grad_(True) for h, w in D.LEVEL_SHAPES]
+    n = sum(9 * h * w for h, w in D.LEVEL_SHAPES)
+    labels = torch.randint(0, classes, (images, n), generator=g, device='cuda')
+    labels[torch.rand((images, n), generator=g, device='cuda') > 0.01] = classes      # ~1 % positives
+    weights = (torch.rand((images, n), generator=g, device='cuda') > 0.02).float()
+    avg = labels.ne(classes).sum().float().reshape(1)
+
+    def fused():
+        loss = S.sph_focal_loss(cls, labels, weights, gamma=2.0, alpha=0.25, avg_factor=avg)
+        return (loss,) + torch.autograd.grad(loss, cls)
+
+    def composition():
+        x = torch.cat([c.permute(0, 2, 3, 1).reshape(images, -1, classes) for c in cls], 1).reshape(-1, classes)
+        t = F.one_hot(labels.reshape(-1), classes + 1)[:, :classes].type_as(x)
+        p = x.sigmoid()
+        pt = (1 - p) * t + p * (1 - t)
+        fw = (0.25 * t + 0.75 * (1 - t)) * pt.pow(2.0)
+        loss = (F.binary_cross_entropy_with_logits(x, t, reduction='none') * fw * weights.reshape(-1, 1)).sum() / (avg + 1.1920929e-07)
+        return (loss.reshape(()),) + torch.autograd.grad(loss, cls)
+    a, c = fused(), composition()
+    torch.cuda.synchronize()
+    loss_rel = abs(float(a[0]) - float(c[0])) / abs(float(c[0]))
+    grad_diff = max(float((x - y).abs().max()) for x, y in zip(a[1:], c[1:]))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fused()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        fused()
+    dst = [torch.empty_like(x) for x in cls]
+
+    def copy():
+        with torch.no_grad():
+            for x, y in zip(dst, cls):
+                x.copy_(y)
+    ta, tb, tc, tcopy = [], [], [], []
+    for _ in range(rounds):
+        ta.append(timeit(fused, reps=30) * 1e6)
+        tb.append(timeit(graph.replay, reps=30) * 1e6)
+        tc.append(timeit(composition, warm=2, reps=5, settle_s=0.0) * 1e6)
+        tcopy.append(timeit(copy, reps=30) * 1e6)
+    med = lambda v: float(np.median(v))
+    elems = images * n * classes
+    stream_bytes = 2 * 4 * elems
+    bw = stream_bytes / (med(tcopy) * 1e-6)   # a copy reads and writes each byte once: the same 2 x 4 x elems bytes
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(20):
+            fused()
+        torch.cuda.synchronize()
+    kernels = {}
+    for e in prof.key_averages():
+        t = getattr(e, 'device_time_total', None) or getattr(e, 'cuda_time_total', 0.0)
+        if t > 0:
+            kernels[e.key[:80]] = t / 20
+    k_sum = sum(v for k, v in kernels.items() if 'focal_sum' in k)
+    return {'config': 'focal: %d images x %d anchors x %d classes (512x1024 ERP, 5 NCHW levels), gamma 2, alpha 0.25, fwd + bwd' % (images, n, classes),
+            'a_fused_eager_us': med(ta), 'b_fused_graph_us': med(tb), 'c_torch_composition_us': med(tc),
+            'a_rounds_us': ta, 'b_rounds_us': tb, 'c_rounds_us': tc, 'a_spread_us': max(ta) - min(ta), 'b_spread_us': max(tb) - min(tb),
+            'c_spread_us': max(tc) - min(tc), 'a_over_c': med(ta) / med(tc), 'b_over_c': med(tb) / med(tc),
+            'elements': elems, 'stream_bytes': stream_bytes, 'copy_bandwidth_TBps': bw / 1e12, 'copy_floor_us': med(tcopy),
+            'kernel_us': kernels, 'focal_sum_kernel_us': k_sum, 'focal_sum_kernel_TBps': stream_bytes / (k_sum * 1e-6) / 1e12 if k_sum else None,
+            'focal_sum_over_copy_floor': k_sum / med(tcopy) if k_sum else None,
+            'loss_fused': float(a[0]), 'loss_composition': float(c[0]), 'loss_rel_diff': loss_rel, 'grad_max_abs_diff': grad_diff,
+            'note': 'kernel_us: average device time per kernel name over 20 eager calls (torch device-activity trace); the copy floor is a '
+                    'device copy of the five logit tensors (reads and writes 4 B per element each, the bytes the fused kernel moves)'}
+
+
 def coder(n=1_000_000):
     """§8f-2: decode (the op in front of loss_bbox) and encode on n RBFoV / BFoV boxes, via the C ABI."""
     import ctypes
@@ -544,8 +625,8 @@ def gaussian(n=1_000_000):
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch get_bboxes coder unbiased variants; none = all)
-    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, get_bboxes=get_bboxes, coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch get_bboxes focal coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, get_bboxes=get_bboxes, focal=focal, coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)

@@ -105,7 +105,8 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
-    images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) with the device avg_factor -> backward."""
+    images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
+    logits (sph_focal_loss), both with the device avg_factor -> backward."""
     dev = 'cuda'
     g = torch.Generator().manual_seed(seed)
     anchors = retina_anchors()
@@ -121,22 +122,29 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     loss_bbox = S.Sph2PobIoULoss(mode='ciou', loss_weight=1.0)
     deltas = (torch.randn((images * n, 4), generator=g) * 0.05).to(dev).requires_grad_(True)
     rois = anchors.repeat(images, 1)
+    gd = torch.Generator(device=dev).manual_seed(seed)
+    cls_scores = [(torch.randn((images, 9 * num_classes, h, w), generator=gd, device=dev) * 2 - 4).requires_grad_(True) for h, w in LEVEL_SHAPES]
 
     def step():
         deltas.grad = None
+        for c in cls_scores:
+            c.grad = None
         t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=num_classes)
         pred = coder.decode(rois, deltas)
         loss = loss_bbox(pred, t.bbox_targets.reshape(-1, 4), t.bbox_weights.reshape(-1, 4), avg_factor=t.avg_factor)
-        loss.backward()
-        return loss.detach(), t
+        # (the targets follow retina_anchors()' order, the logits the head's ((h W + w) A + a): a timing and plumbing demo)
+        loss_cls = S.sph_focal_loss(cls_scores, t.labels, t.label_weights, gamma=2.0, alpha=0.25, avg_factor=t.avg_factor)
+        (loss + loss_cls).backward()
+        return loss.detach(), loss_cls.detach(), t
     step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(reps):
-        loss, t = step()
+        loss, loss_cls, t = step()
     torch.cuda.synchronize()
     out = {'anchors': n, 'images': images, 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
-           'loss': float(loss), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()), 'backend': backend,
+           'loss': float(loss), 'loss_cls': float(loss_cls), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()),
+           'cls_grad_finite': all(bool(torch.isfinite(c.grad).all()) for c in cls_scores), 'backend': backend,
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels)
 
