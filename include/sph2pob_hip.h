@@ -67,7 +67,7 @@ enum {
 
 /* Library identification: ABI version (bumped on any signature change or new entry point; sph2pob_abi_version() returns the
  * value the library was built with) and the code-object target. */
-#define SPH2POB_ABI_VERSION 2
+#define SPH2POB_ABI_VERSION 3
 int sph2pob_abi_version(void);
 const char* sph2pob_target_arch(void);
 const char* sph2pob_error_string(int code);
@@ -521,6 +521,50 @@ int sph2pob_focal_loss_bwd_f32(const float* logits, const int64_t* labels, const
                                int grad_stride, float gamma, float alpha, float scale, const float* avg_factor, float* grad_logits,
                                int64_t n, int64_t num_classes, void* stream);
 int sph2pob_focal_loss_grad_scale_f32(const float* stash, const float* grad_out, float* out, int64_t total, void* stream);
+
+/* ---- fused box-regression loss: the regression half of SphRetinaHead.loss_single ------------------------------------------
+ * Replaces, for reg_decoded_bbox=True (sphdet/models/heads/sph_retina_head.py:252-265), the chain
+ * bbox_pred.permute(0, 2, 3, 1).reshape(-1, dim) -> cat over the levels -> DeltaXYWH(A)SphBBoxCoder.decode -> Sph2PobIoULoss ->
+ * / avg_factor and its backward by one pass that reads only the weights and, for the rows whose weight is not zero, their deltas,
+ * anchors and targets.  Per such row the arithmetic is the composition's: sph2pob_coder_decode_f32 with num_classes = 1, then the
+ * loss element and adjoint of sph2pob_loss_fwd_grad_f32, then the diagonal Jacobian of sph2pob_coder_decode_bwd_f32.
+ *
+ * sph2pob_bbox_loss_sum_f32 — level tables are HOST arrays of num_levels <= 8 entries, as for sph2pob_focal_loss_sum_f32:
+ *   bbox_preds   device pointers, level l either the head's NCHW (B, A dim, H_l, W_l), read in place, or the flattened
+ *                (B, n_l, dim); anchor i of a level is (h W + w) A + a, its component k is channel a dim + k
+ *   grads        NULL (forward only), or device pointers laid out exactly like bbox_preds that receive
+ *                scale_eff * w_i * J_decode^T dL/dbox: the gradient of out[0] for an upstream gradient of 1.  EVERY element of
+ *                every level is written, exactly once: rows of weight 0 get +0.0f
+ *   level_n      n_l = H_l W_l A anchors (>= 0);  level_hw: H_l W_l for NCHW, 0 for the flattened layout (NULL: all flattened)
+ *   anchors      (n, dim), n = sum n_l, rows in level order, shared by all images (as sph2pob_anchor_targets_f32 takes them)
+ *   targets      (B, n, dim) decoded ground-truth boxes: what sph2pob_anchor_targets_f32 writes with encode == 0
+ *   weight       NULL (all ones), (B, n) when weight_dim == 1, (B, n, dim) when weight_dim == dim: the per-box mean is taken as
+ *                OBBIoULoss takes it (sph2pob_loss_fwd_f32)
+ *   means_host, stds_host, max_ratio, coder_flags, ctr_clamp   exactly those of sph2pob_coder_decode_f32
+ *   loss_mode    SPH2POB_LOSS_* (| SPH2POB_FLAG_REFERENCE_ORDER), eps: as for sph2pob_loss_fwd_f32
+ *   scale, avg_factor   as for sph2pob_focal_loss_sum_f32: scale_eff = scale / (*avg_factor + FLT_EPSILON) with a DEVICE float
+ *   out          (1) f32 = scale_eff * sum_i w_i L(decode(anchor_i, delta_i), target_i): double partials per workgroup in
+ *                `workspace`, added in a fixed order by one workgroup — no float atomics, no counter, the same bits on every call
+ *   workspace    sph2pob_bbox_loss_workspace_bytes(level_n, level_hw, num_levels, B, box_dim) bytes (0: shapes not accepted)
+ * A row whose mean weight is exactly 0 contributes an exact zero loss and zero gradient and its deltas and targets are NEVER READ:
+ * a NaN there stays inert.  (The rule of the loss entries above is per wave of 64 rows, csrc/sph2pob_loss.hip; here it is per
+ * row.)  Two launches whatever B and the number of levels are; nothing is read back, nothing is allocated; capturable.  The
+ * gradient leaves in whole 16-byte stores along w for NCHW levels whose H W is a multiple of 4 (flattened: n_l dim a multiple of
+ * 4) and whose gradient pointer is 16-byte aligned, one element at a time with the same values otherwise.  B n == 0 writes
+ * out[0] = 0.  After the call torch's backward is sph2pob_focal_loss_grad_scale_f32 on the gradient buffer.
+ * Errors, checked in this order before anything is enqueued: loss_mode flags -> SPH2POB_ERR_OPTION; box_dim -> SPH2POB_ERR_DIM;
+ * loss mode, weight_dim (with a weight), coder_flags, max_ratio < 0 -> SPH2POB_ERR_OPTION; num_levels outside [1, 8], B outside
+ * [0, 65 535] -> SPH2POB_ERR_SIZE; a NULL level_n / bbox_preds table -> SPH2POB_ERR_NULL; n_l < 0, level_hw that does not divide
+ * n_l, B n_l dim >= 2^31 - 4096, more than 360 / dim anchors per position -> SPH2POB_ERR_SIZE; a NULL table entry of a level with
+ * rows, out, workspace, anchors or targets with rows -> SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_bbox_loss_workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                          int box_dim);
+int sph2pob_bbox_loss_sum_f32(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                              int num_levels, int64_t num_images, int box_dim, const float* anchors, const float* targets,
+                              const float* weight, int weight_dim, const float* means_host, const float* stds_host, float max_ratio,
+                              int coder_flags, float ctr_clamp, int loss_mode, float eps, float scale, const float* avg_factor,
+                              float* out, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@
 #include "sph2pob_coder.hpp"
 #include "sph2pob_get_bboxes.hpp"
 #include "sph2pob_focal.hpp"
+#include "sph2pob_bbox_loss.hpp"
 
 namespace {
 
@@ -899,6 +900,83 @@ int sph2pob_focal_loss_grad_scale_f32_cpu(const float* stash, const float* grad_
     parallel_for(total, 1 << 16, [&](int64_t lo, int64_t hi) {
         for (int64_t e = lo; e < hi; e++) out[e] = stash[e] * s;
     });
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- fused box-regression loss: the twin of sph2pob_bbox_loss.hip on decode_one + pair_loss, row by row ----
+namespace {
+namespace BL = sph2pob_bbox;
+
+// partial sums of kFocalRows rows each, added in order: the result does not move with the thread count
+template <int DIM, bool FAST>
+double bbox_loss_rows(const BL::Levels& L, int64_t B, const float* anchors, const float* targets, const float* weight, int wd,
+                      const C::Norm& nm, float max_ratio, int cflags, float ctr_clamp, int mode, float eps, float k0) {
+    const int64_t rows = L.rows, chunks = (rows + kFocalRows - 1) / kFocalRows;
+    std::vector<double> part((size_t)chunks, 0.0);
+    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
+        for (int64_t ch = lo; ch < hi; ch++) {
+            double acc = 0.0;
+            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
+                const int64_t b = row / L.n_total, j = row - b * L.n_total;
+                int l = 0;
+                for (int q = 1; q < L.num; q++) l += j >= L.lv[q].row_off ? 1 : 0;
+                const BL::Level& lv = L.lv[l];
+                int64_t stride;
+                const int64_t off = BL::delta_offset(lv, DIM, b, j - lv.row_off, &stride);
+                const float w = element_weight<DIM>(weight, wd, row);
+                if (!(w != 0.0f)) {   // never read: exact zeros
+                    if (lv.grad)
+                        for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = 0.0f;
+                    continue;
+                }
+                float p[5], d[5], t[5], box[5] = {0, 0, 0, 0, 0}, jac[5], gx[5], gy[5];
+                for (int k = 0; k < 5; k++) {
+                    p[k] = k < DIM ? anchors[j * DIM + k] : 0.0f;
+                    d[k] = k < DIM ? lv.pred[off + k * stride] : 0.0f;
+                    t[k] = k < DIM ? targets[row * DIM + k] : 0.0f;
+                }
+                C::decode_one<DIM, true>(p, d, nm, max_ratio, cflags, ctr_clamp, box, jac);
+                const float lo1 = pair_loss<DIM, true, FAST>(box, t, mode, eps, nullptr, gx, gy);
+                acc += (double)(lo1 * w);
+                if (lv.grad) {
+                    const float g = k0 * w;
+                    for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = (g * gx[k]) * jac[k];
+                }
+            }
+            part[(size_t)ch] = acc;
+        }
+    });
+    double total = 0.0;
+    for (double v : part) total += v;
+    return total;
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_bbox_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                  int num_levels, int64_t num_images, int box_dim, const float* anchors, const float* targets,
+                                  const float* weight, int weight_dim, const float* means_host, const float* stds_host, float max_ratio,
+                                  int coder_flags, float ctr_clamp, int loss_mode, float eps, float scale, const float* avg_factor,
+                                  float* out, void* workspace, void*) {
+    if (int rc = BL::check_options(box_dim, weight, weight_dim, max_ratio, coder_flags, loss_mode)) return rc;
+    BL::Levels L;
+    if (int rc = BL::make_levels(bbox_preds, grads, level_n, level_hw, num_levels, num_images, box_dim, true, &L)) return rc;
+    if (!out || !workspace || (L.rows > 0 && (!anchors || !targets))) return SPH2POB_ERR_NULL;
+    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
+    const float k0 = BL::effective_scale(scale, avg_factor);
+    const int mode = loss_mode & 0xff;
+    const bool fast = !(loss_mode & SPH2POB_FLAG_REFERENCE_ORDER);
+    double total = 0.0;
+    if (L.rows > 0) {
+#define SPH_BBOX_ROWS(D, F) bbox_loss_rows<D, F>(L, num_images, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags, ctr_clamp, mode, eps, k0)
+        if (box_dim == 4) total = fast ? SPH_BBOX_ROWS(4, true) : SPH_BBOX_ROWS(4, false);
+        else total = fast ? SPH_BBOX_ROWS(5, true) : SPH_BBOX_ROWS(5, false);
+#undef SPH_BBOX_ROWS
+    }
+    out[0] = (float)(total * (double)k0);
     return SPH2POB_OK;
 }
 

@@ -103,10 +103,13 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
                      gt=gt, bbox_targets=bbox_targets)
 
 
-def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1):
+def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
-    logits (sph_focal_loss), both with the device avg_factor -> backward."""
+    logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
+    `sph_bbox_loss` instead: loss_single as two fused calls.  The demo's deltas are one flat leaf, so they go in as ONE flattened
+    (B, n, 4) level — the plumbing, not the NCHW in-place read with 16-byte stores along w; that route is timed by
+    `tools/bench_configs.py bbox_loss`."""
     dev = 'cuda'
     g = torch.Generator().manual_seed(seed)
     anchors = retina_anchors()
@@ -130,8 +133,12 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
         for c in cls_scores:
             c.grad = None
         t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=num_classes)
-        pred = coder.decode(rois, deltas)
-        loss = loss_bbox(pred, t.bbox_targets.reshape(-1, 4), t.bbox_weights.reshape(-1, 4), avg_factor=t.avg_factor)
+        if fused_reg:
+            loss = S.sph_bbox_loss([deltas.view(images, n, 4)], anchors, t.bbox_targets, t.bbox_weights, bbox_coder=coder, mode='ciou',
+                                   avg_factor=t.avg_factor)
+        else:
+            pred = coder.decode(rois, deltas)
+            loss = loss_bbox(pred, t.bbox_targets.reshape(-1, 4), t.bbox_weights.reshape(-1, 4), avg_factor=t.avg_factor)
         # (the targets follow retina_anchors()' order, the logits the head's ((h W + w) A + a): a timing and plumbing demo)
         loss_cls = S.sph_focal_loss(cls_scores, t.labels, t.label_weights, gamma=2.0, alpha=0.25, avg_factor=t.avg_factor)
         (loss + loss_cls).backward()
@@ -144,7 +151,7 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     torch.cuda.synchronize()
     out = {'anchors': n, 'images': images, 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
            'loss': float(loss), 'loss_cls': float(loss_cls), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()),
-           'cls_grad_finite': all(bool(torch.isfinite(c.grad).all()) for c in cls_scores), 'backend': backend,
+           'cls_grad_finite': all(bool(torch.isfinite(c.grad).all()) for c in cls_scores), 'backend': backend, 'fused_reg': fused_reg,
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels)
 
