@@ -67,7 +67,7 @@ enum {
 
 /* Library identification: ABI version (bumped on any signature change or new entry point; sph2pob_abi_version() returns the
  * value the library was built with) and the code-object target. */
-#define SPH2POB_ABI_VERSION 3
+#define SPH2POB_ABI_VERSION 4
 int sph2pob_abi_version(void);
 const char* sph2pob_target_arch(void);
 const char* sph2pob_error_string(int code);
@@ -565,6 +565,44 @@ int sph2pob_bbox_loss_sum_f32(const void* const* bbox_preds, void* const* grads,
                               const float* weight, int weight_dim, const float* means_host, const float* stds_host, float max_ratio,
                               int coder_flags, float ctr_clamp, int loss_mode, float eps, float scale, const float* avg_factor,
                               float* out, void* workspace, void* stream);
+
+/* ---- fused L1 / SmoothL1 box loss on the head's ENCODED deltas: the regression half of loss_single by default -----------------
+ * Replaces, for reg_decoded_bbox=False and loss_bbox = L1Loss / SmoothL1Loss (the reference's base configs;
+ * mmdet/models/losses/smooth_l1_loss.py:10-52), the chain bbox_pred.permute(0, 2, 3, 1).reshape(-1, dim) -> cat over the levels ->
+ * |pred - target| (or its smooth form) * weight -> sum / avg_factor and its backward by one pass that reads only the weights and,
+ * for the rows with a non-zero weight, their deltas and targets.  Nothing is decoded: there are no anchors and no coder.
+ *
+ * sph2pob_delta_loss_sum_f32 — the arguments of sph2pob_bbox_loss_sum_f32 without anchors, coder and loss mode, with beta:
+ *   bbox_preds, grads, level_n, level_hw, num_levels, num_images, box_dim   exactly as for sph2pob_bbox_loss_sum_f32; grads
+ *                receive (scale_eff * w_k) * s_k per element, EVERY element of every level written exactly once
+ *   targets      (B, n, dim) ENCODED deltas: what sph2pob_anchor_targets_f32 writes with encode == 1
+ *   weight       NULL (all ones), (B, n) when weight_dim == 1, (B, n, dim) when weight_dim == dim: each element loss is
+ *                multiplied by ITS OWN weight (no row mean)
+ *   beta         0: l1_loss — element loss d = |pred - target|, s = sign(pred - target) (0 at equality);
+ *                > 0: smooth_l1_loss — ((0.5 d) d) / beta and s = (pred - target) / beta where d < beta, d - 0.5 beta and the
+ *                sign otherwise.  fp32, in this operation order
+ *   scale, avg_factor   as for sph2pob_focal_loss_sum_f32: scale_eff = scale / (*avg_factor + FLT_EPSILON) with a DEVICE float
+ *   out          (1) f32 = scale_eff * sum over elements of w_k * loss_k: double partials per workgroup in `workspace`, added
+ *                in a fixed order by one workgroup — no float atomics, the same bits on every call
+ *   workspace    sph2pob_delta_loss_workspace_bytes(level_n, level_hw, num_levels, B, box_dim) bytes (0: shapes not accepted)
+ * A row whose dim weights are ALL exactly 0 contributes an exact zero loss and +0.0f gradients and its deltas and targets are
+ * NEVER READ: a NaN there stays inert.  The test is any != 0, so (+1, -1, 0, 0) is a live row; in a live row the elements of
+ * weight 0 are evaluated and multiplied by 0, as in the composition (a NaN delta there reaches the sum).  Two launches whatever B
+ * and the number of levels are; nothing is read back, nothing is allocated; capturable.  Store widths as for
+ * sph2pob_bbox_loss_sum_f32.  B n == 0 writes out[0] = 0.  After the call torch's backward is
+ * sph2pob_focal_loss_grad_scale_f32 on the gradient buffer.
+ * Errors, checked in this order before anything is enqueued: box_dim -> SPH2POB_ERR_DIM; weight_dim (with a weight), beta < 0
+ * or NaN -> SPH2POB_ERR_OPTION; then the shape and table checks of sph2pob_bbox_loss_sum_f32 with the same codes and limits
+ * (num_levels, B -> SIZE; NULL level_n / bbox_preds table -> NULL; n_l, level_hw, B n_l dim >= 2^31 - 4096, more than
+ * 360 / dim anchors per position -> SIZE); a NULL table entry of a level with rows, out, workspace, or targets with rows ->
+ * SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_delta_loss_workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                           int box_dim);
+int sph2pob_delta_loss_sum_f32(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                               int num_levels, int64_t num_images, int box_dim, const float* targets, const float* weight,
+                               int weight_dim, float beta, float scale, const float* avg_factor, float* out, void* workspace,
+                               void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@
 #include "sph2pob_get_bboxes.hpp"
 #include "sph2pob_focal.hpp"
 #include "sph2pob_bbox_loss.hpp"
+#include "sph2pob_delta_loss.hpp"
 
 namespace {
 
@@ -976,6 +977,67 @@ int sph2pob_bbox_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* gr
         else total = fast ? SPH_BBOX_ROWS(5, true) : SPH_BBOX_ROWS(5, false);
 #undef SPH_BBOX_ROWS
     }
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- fused L1 / SmoothL1 loss on encoded deltas: the twin of sph2pob_delta_loss.hip on the same element function, row by row ----
+namespace {
+namespace DL = sph2pob_delta;
+
+template <int DIM>
+double delta_loss_rows(const DL::Levels& L, const float* targets, const float* weight, int wd, float beta, float k0) {
+    const int64_t rows = L.rows, chunks = (rows + kFocalRows - 1) / kFocalRows;
+    std::vector<double> part((size_t)chunks, 0.0);
+    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
+        for (int64_t ch = lo; ch < hi; ch++) {
+            double acc = 0.0;
+            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
+                const int64_t b = row / L.n_total, j = row - b * L.n_total;
+                int l = 0;
+                for (int q = 1; q < L.num; q++) l += j >= L.lv[q].row_off ? 1 : 0;
+                const DL::Level& lv = L.lv[l];
+                int64_t stride;
+                const int64_t off = DL::delta_offset(lv, DIM, b, j - lv.row_off, &stride);
+                float wk[DIM];
+                if (!DL::row_weights<DIM>(weight, wd, false, row, wk)) {   // never read: exact zeros
+                    if (lv.grad)
+                        for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = 0.0f;
+                    continue;
+                }
+                for (int k = 0; k < DIM; k++) {
+                    float lo1, sk;
+                    DL::element(lv.pred[off + k * stride], targets[row * DIM + k], beta, lo1, sk);
+                    acc += (double)(lo1 * wk[k]);
+                    if (lv.grad) lv.grad[off + k * stride] = (k0 * wk[k]) * sk;
+                }
+            }
+            part[(size_t)ch] = acc;
+        }
+    });
+    double total = 0.0;
+    for (double v : part) total += v;
+    return total;
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_delta_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                   int num_levels, int64_t num_images, int box_dim, const float* targets, const float* weight,
+                                   int weight_dim, float beta, float scale, const float* avg_factor, float* out, void* workspace,
+                                   void*) {
+    if (int rc = DL::check_options(box_dim, weight, weight_dim, beta)) return rc;
+    DL::Levels L;
+    if (int rc = DL::make_levels(bbox_preds, grads, level_n, level_hw, num_levels, num_images, box_dim, true, &L)) return rc;
+    if (!out || !workspace || (L.rows > 0 && !targets)) return SPH2POB_ERR_NULL;
+    const float k0 = DL::effective_scale(scale, avg_factor);
+    const int wd = weight ? weight_dim : 0;
+    double total = 0.0;
+    if (L.rows > 0)
+        total = box_dim == 4 ? delta_loss_rows<4>(L, targets, weight, wd, beta, k0) : delta_loss_rows<5>(L, targets, weight, wd, beta, k0);
     out[0] = (float)(total * (double)k0);
     return SPH2POB_OK;
 }

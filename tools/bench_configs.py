@@ -559,6 +559,71 @@ def bbox_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7
             'loss_fused': float(a[0]), 'loss_composition': float(c[0]), 'loss_rel_diff': loss_rel, 'grad_max_abs_diff': grad_diff}
 
 
+def delta_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7):
+    """The regression loss of the reference's BASE configuration (L1Loss on encoded deltas, reg_decoded_bbox=False) for a minibatch
+    at the reference's test shape — 512 x 1024 ERP, 5 NCHW levels, 9 anchors, 98 208 anchors per image, the ground-truth counts of
+    demo_hot_path.run_batch, a device avg_factor — forward + backward to the head's NCHW deltas: (a) sph_delta_loss eager, (b)
+    replayed from a graph, (c) the composition it replaces (permute / reshape / cat -> |pred - target| * weight -> sum /
+    (avg_factor + eps)) eager and (d) replayed from a graph.  Timed in alternation `rounds` times, medians and spreads reported."""
+    import demo_hot_path as D
+    images = len(images_counts)
+    g = torch.Generator().manual_seed(0)
+    anchors = torch.cat(D.retina_level_anchors())
+    gts, labels = [], []
+    for k in images_counts:
+        u = torch.rand((k, 4), generator=g)
+        gts.append(torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85], 1).cuda())
+        labels.append(torch.randint(0, classes, (k,), generator=g).cuda())
+    assigner = S.SphMaxIoUAssigner(pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1,
+                                   iou_calculator=dict(type='SphOverlaps2D', backend='sph2pob_standard_iou', box_version=4))
+    coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(1., 1., 1., 1.))
+    t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=classes, reg_decoded_bbox=False, bbox_coder=coder)
+    n = anchors.size(0)
+    eps = float(torch.finfo(torch.float32).eps)
+    gd = torch.Generator(device='cuda').manual_seed(0)
+    preds = [(torch.randn((images, 9 * 4, h, w), generator=gd, device='cuda') * 0.05).requires_grad_(True) for h, w in D.LEVEL_SHAPES]
+
+    def fused():
+        loss = S.sph_delta_loss(preds, t.bbox_targets, t.bbox_weights, avg_factor=t.avg_factor)
+        return (loss.detach(),) + torch.autograd.grad(loss, preds)
+
+    def composition():
+        flat = torch.cat([p.permute(0, 2, 3, 1).reshape(images, -1, 4) for p in preds], 1)
+        loss = ((flat - t.bbox_targets).abs() * t.bbox_weights).sum() / (t.avg_factor.reshape(()) + eps)
+        return (loss.detach().reshape(()),) + torch.autograd.grad(loss, preds)
+    # the captures come first, each after a warm-up on a side stream (see bbox_loss above)
+    graphs = []
+    for fn in (fused, composition):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fn()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            fn()
+        graphs.append(graph)
+    a, c = fused(), composition()
+    torch.cuda.synchronize()
+    loss_rel = abs(float(a[0]) - float(c[0])) / abs(float(c[0]))
+    grad_diff = max(float((x - y).abs().max()) for x, y in zip(a[1:], c[1:]))
+    ta, tb, tc, td = [], [], [], []
+    for _ in range(rounds):
+        ta.append(timeit(fused, reps=30) * 1e6)
+        tb.append(timeit(graphs[0].replay, reps=30) * 1e6)
+        tc.append(timeit(composition, reps=30) * 1e6)
+        td.append(timeit(graphs[1].replay, reps=30) * 1e6)
+    med = lambda v: float(np.median(v))
+    return {'config': 'delta_loss: %d images x %d anchors (512x1024 ERP, 5 NCHW levels), L1 on encoded deltas, device avg_factor, fwd + bwd' % (images, n),
+            'num_gt': list(images_counts), 'num_pos': t.num_pos.tolist(),
+            'a_fused_eager_us': med(ta), 'b_fused_graph_us': med(tb), 'c_composition_eager_us': med(tc), 'd_composition_graph_us': med(td),
+            'a_rounds_us': ta, 'b_rounds_us': tb, 'c_rounds_us': tc, 'd_rounds_us': td,
+            'a_spread_us': max(ta) - min(ta), 'b_spread_us': max(tb) - min(tb), 'c_spread_us': max(tc) - min(tc), 'd_spread_us': max(td) - min(td),
+            'a_over_c': med(ta) / med(tc), 'b_over_d': med(tb) / med(td),
+            'loss_fused': float(a[0]), 'loss_composition': float(c[0]), 'loss_rel_diff': loss_rel, 'grad_max_abs_diff': grad_diff}
+
+
 def coder(n=1_000_000):
     """§8f-2: decode (the op in front of loss_bbox) and encode on n RBFoV / BFoV boxes, via the C ABI."""
     import ctypes
@@ -694,8 +759,8 @@ def gaussian(n=1_000_000):
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch get_bboxes focal bbox_loss coder unbiased variants; none = all)
-    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, get_bboxes=get_bboxes, focal=focal, bbox_loss=bbox_loss, coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch get_bboxes focal bbox_loss delta_loss coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, get_bboxes=get_bboxes, focal=focal, bbox_loss=bbox_loss, delta_loss=delta_loss, coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)

@@ -103,13 +103,15 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
                      gt=gt, bbox_targets=bbox_targets)
 
 
-def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False):
+def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
     `sph_bbox_loss` instead: loss_single as two fused calls.  The demo's deltas are one flat leaf, so they go in as ONE flattened
     (B, n, 4) level — the plumbing, not the NCHW in-place read with 16-byte stores along w; that route is timed by
-    `tools/bench_configs.py bbox_loss`."""
+    `tools/bench_configs.py bbox_loss`.  `base_config=True` runs the reference's BASE configuration instead
+    (`loss_bbox=dict(type='L1Loss')`, `reg_decoded_bbox=False`): encoded targets from `sph_anchor_targets`, `sph_delta_loss` on the
+    raw deltas, nothing decoded; its NCHW route is timed by `tools/bench_configs.py delta_loss`."""
     dev = 'cuda'
     g = torch.Generator().manual_seed(seed)
     anchors = retina_anchors()
@@ -132,8 +134,11 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
         deltas.grad = None
         for c in cls_scores:
             c.grad = None
-        t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=num_classes)
-        if fused_reg:
+        t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=num_classes, reg_decoded_bbox=not base_config,
+                                 bbox_coder=coder if base_config else None)
+        if base_config:
+            loss = S.sph_delta_loss([deltas.view(images, n, 4)], t.bbox_targets, t.bbox_weights, avg_factor=t.avg_factor)
+        elif fused_reg:
             loss = S.sph_bbox_loss([deltas.view(images, n, 4)], anchors, t.bbox_targets, t.bbox_weights, bbox_coder=coder, mode='ciou',
                                    avg_factor=t.avg_factor)
         else:
@@ -152,6 +157,7 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     out = {'anchors': n, 'images': images, 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
            'loss': float(loss), 'loss_cls': float(loss_cls), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()),
            'cls_grad_finite': all(bool(torch.isfinite(c.grad).all()) for c in cls_scores), 'backend': backend, 'fused_reg': fused_reg,
+           'base_config': base_config,
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels)
 
