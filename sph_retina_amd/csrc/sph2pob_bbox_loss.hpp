@@ -8,14 +8,14 @@
 
 #include "../../include/sph2pob_hip.h"
 #include "sph2pob_coder.hpp"
-#include "sph2pob_focal.hpp"
+#include "sph2pob_head_loss.hpp"
 #include "sph2pob_loss.hpp"
 
 namespace sph2pob_bbox {
 
-using sph2pob_focal::aligned16;
-using sph2pob_focal::effective_scale;
-using sph2pob_focal::kMaxLevels;
+using sph2pob_head::aligned16;
+using sph2pob_head::effective_scale;
+using sph2pob_head::kMaxLevels;
 
 constexpr int kWaves = 4;                  // waves of a workgroup; each owns one span
 constexpr int kTile = 1440;                // floats of a wave's gradient tile in LDS: 32 positions x 9 anchors x 5 components

@@ -3,7 +3,7 @@
 //                       thread owns four consecutive positions of one (image, anchor) of an NCHW level, loads their labels and
 //                       weights once and walks the C class planes with 16-byte loads / stores at stride H W; the weighted losses
 //                       are added in double and leave one partial per workgroup
-//   focal_final_kernel  one workgroup adds the partials in a fixed order (no float atomics: the same bits on every call)
+//   head_final_kernel   (sph2pob_head_loss.hpp) adds the partials in a fixed order
 //   focal_fwd / focal_bwd / focal_grad_scale   the flat (N, C) element forms and the stash scaling of torch's backward
 // The stream is 4 bytes in and 4 bytes out per element; per element the VALU sees one expf, one log1pf and one division.
 #include "sph2pob_focal.hpp"
@@ -11,43 +11,6 @@
 namespace {
 
 using namespace sph2pob_focal;
-
-inline int launch_status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPH2POB_OK : (int)e;
-}
-
-static int cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        n = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    return n;
-}
-
-__device__ __forceinline__ double block_sum(double v) {
-    __shared__ double sm[kBlock / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < kBlock / 64; k++) r += sm[k];
-    }
-    return r;
-}
-
-// the level of a workgroup (workgroup-uniform; at most kMaxLevels entries; a level without items is skipped by the next one's
-// equal offset)
-__device__ __forceinline__ int level_of_block(const Levels& L, int block) {
-    int l = 0;
-#pragma unroll
-    for (int q = 1; q < kMaxLevels; q++) l += (q < L.num && block >= L.lv[q].block_off) ? 1 : 0;
-    return l;
-}
 
 template <int V> struct Vec;
 template <> struct Vec<4> { using type = float4; };
@@ -152,17 +115,8 @@ __global__ __launch_bounds__(kBlock) void focal_sum_kernel(Levels L, int C, cons
             default: acc = flat_item<1, GRAD>(lv, item, C, L.n_total, labels, weight, wmode, P, k0); break;
         }
     }
-    const double r = block_sum(acc);
+    const double r = block_sum_f64(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-
-// out[0] = scale_eff * (partials added in a fixed order): thread t adds partials t, t + 256, ... in turn, then the tree
-__global__ __launch_bounds__(kBlock) void focal_final_kernel(const double* __restrict__ partial, int nb, float scale,
-                                                             const float* __restrict__ avg_factor, float* __restrict__ out) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nb; i += kBlock) acc += partial[i];
-    const double r = block_sum(acc);
-    if (threadIdx.x == 0) out[0] = (float)(r * (double)effective_scale(scale, avg_factor));
 }
 
 __global__ __launch_bounds__(kBlock) void focal_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ labels,
@@ -231,8 +185,7 @@ int sph2pob_focal_loss_sum_f32(const void* const* logits, void* const* grads, co
             hipLaunchKernelGGL(focal_sum_kernel<false>, dim3(L.blocks), dim3(kBlock), 0, s, L, (int)num_classes, labels, weight, weight_mode, P,
                                scale, avg_factor, partial);
     }
-    hipLaunchKernelGGL(focal_final_kernel, dim3(1), dim3(kBlock), 0, s, partial, L.blocks, scale, avg_factor, out);
-    return launch_status();
+    return launch_final(partial, L.blocks, scale, avg_factor, out, s);
 }
 
 int sph2pob_focal_loss_fwd_f32(const float* logits, const int64_t* labels, const float* weight, int weight_mode, float gamma, float alpha,

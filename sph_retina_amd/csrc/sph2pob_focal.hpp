@@ -8,13 +8,15 @@
 #include <stdint.h>
 
 #include "../../include/sph2pob_hip.h"
+#include "sph2pob_head_loss.hpp"
 
 namespace sph2pob_focal {
 
-#define SPHF_DEV __host__ __device__ __forceinline__
+using sph2pob_head::aligned16;
+using sph2pob_head::effective_scale;
+using sph2pob_head::kBlock;
+using sph2pob_head::kMaxLevels;
 
-constexpr int kMaxLevels = 8;
-constexpr int kBlock = 256;
 constexpr int64_t kMaxLevelElems = ((int64_t)1 << 31) - 4096;   // elements of one level: 32-bit item indices inside a level
 
 // gamma split once on the host: q^gamma = q^gint * exp2(gfrac * log2 q), gint = min(floor(gamma), 8) exact multiplications (an
@@ -64,12 +66,6 @@ SPHF_DEV void element(float x, bool t, const Params& P, float& loss, float& dx) 
     dx = t ? -dz : dz;
 }
 
-// the scale every kernel applies: `scale` (loss_weight, possibly over a host divisor), over (*avg_factor + FLT_EPSILON) when the
-// divisor lives on the device (weight_reduce_loss, mmdet/models/losses/utils.py:55-57) — one IEEE division in fp32
-SPHF_DEV float effective_scale(float scale, const float* avg_factor) {
-    return avg_factor ? scale / (avg_factor[0] + FLT_EPSILON) : scale;
-}
-
 // One level of one call.  kind: how a thread's item maps onto memory
 //   0  NCHW (B, A C, H, W), four consecutive positions p = h W + w of one (b, a) per item: 16-byte accesses at stride H W over the classes
 //   1  NCHW, one position per item (H W % 4 != 0 or a base that is not 16-byte aligned)
@@ -90,8 +86,6 @@ struct Levels {
     int64_t n_total;       // anchors of one image, all levels
     int64_t elems;         // B n C
 };
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Argument checks of sph2pob_focal_loss_sum_f32 / its twin, in the documented order; fills the table.  `tables` false: shapes
 // only (the workspace size), every level counted with its scalar kind (an upper bound on the workgroups).

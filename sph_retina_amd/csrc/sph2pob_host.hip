@@ -805,6 +805,41 @@ int sph2pob_obb_l1_bwd_f32_cpu(const float* planar_pred, const float* planar_tar
 namespace {
 namespace FL = sph2pob_focal;
 constexpr int64_t kFocalRows = 1024;   // rows of one partial sum: the partials do not move with the thread count
+
+// The row walk of the three head-loss twins: f(lv, b, i, row, acc) for every row = b n_total + j of the call, lv the level of j
+// and i = j - lv.row_off the anchor inside it; f adds the row's weighted losses to acc.  One double partial per kFocalRows rows,
+// the partials added in order: the total does not move with the thread count.
+template <class Levels, class F>
+double head_rows_sum(const Levels& L, int64_t rows, F&& f) {
+    const int64_t chunks = (rows + kFocalRows - 1) / kFocalRows;
+    std::vector<double> part((size_t)chunks, 0.0);
+    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
+        for (int64_t ch = lo; ch < hi; ch++) {
+            double acc = 0.0;
+            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
+                const int64_t b = row / L.n_total, j = row - b * L.n_total;
+                int l = 0;
+                for (int q = 1; q < L.num; q++) l += j >= L.lv[q].row_off ? 1 : 0;
+                f(L.lv[l], b, j - L.lv[l].row_off, row, acc);
+            }
+            part[(size_t)ch] = acc;
+        }
+    });
+    double total = 0.0;
+    for (double v : part) total += v;
+    return total;
+}
+
+// The regression twins' row: a dead row (live false) is never read and gets DIM exact zeros at off + k * stride; a live one runs
+// eval(off, stride).
+template <int DIM, class Eval>
+inline void box_row(const sph2pob_bbox::Level& lv, int64_t b, int64_t i, bool live, Eval&& eval) {
+    int64_t stride;
+    const int64_t off = sph2pob_bbox::delta_offset(lv, DIM, b, i, &stride);
+    if (live) eval(off, stride);
+    else if (lv.grad)
+        for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = 0.0f;
+}
 }  // namespace
 
 extern "C" {
@@ -819,38 +854,23 @@ int sph2pob_focal_loss_sum_f32_cpu(const void* const* logits, void* const* grads
     const FL::Params P = FL::make_params(gamma, alpha);
     const float k0 = FL::effective_scale(scale, avg_factor);
     const int64_t rows = L.elems > 0 ? num_images * L.n_total : 0, C = num_classes;
-    const int64_t chunks = (rows + kFocalRows - 1) / kFocalRows;
-    std::vector<double> part((size_t)chunks, 0.0);
-    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
-        for (int64_t ch = lo; ch < hi; ch++) {
-            double acc = 0.0;
-            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
-                const int64_t b = row / L.n_total, j = row - b * L.n_total;
-                int l = 0;
-                for (int q = 1; q < L.num; q++) l += j >= L.lv[q].row_off ? 1 : 0;
-                const FL::Level& lv = L.lv[l];
-                const int64_t i = j - lv.row_off;
-                int64_t base, stride;   // element (row, c) = base + c * stride
-                if (lv.hw > 0) {
-                    const int64_t p = i / lv.a, a = i - p * lv.a;
-                    base = (b * lv.a + a) * C * lv.hw + p; stride = lv.hw;
-                } else {
-                    base = (b * lv.n + i) * C; stride = 1;
-                }
-                const int64_t lab = labels[row];
-                for (int c = 0; c < (int)C; c++) {
-                    float loss, dx;
-                    FL::element(lv.logits[base + c * stride], lab == (int64_t)c, P, loss, dx);
-                    const float we = FL::weight_of(weight, weight_mode, row, C, c);
-                    acc += (double)(loss * we);
-                    if (lv.grad) lv.grad[base + c * stride] = (k0 * we) * dx;
-                }
-            }
-            part[(size_t)ch] = acc;
+    const double total = head_rows_sum(L, rows, [&](const FL::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
+        int64_t base, stride;   // element (row, c) = base + c * stride
+        if (lv.hw > 0) {
+            const int64_t p = i / lv.a, a = i - p * lv.a;
+            base = (b * lv.a + a) * C * lv.hw + p; stride = lv.hw;
+        } else {
+            base = (b * lv.n + i) * C; stride = 1;
+        }
+        const int64_t lab = labels[row];
+        for (int c = 0; c < (int)C; c++) {
+            float loss, dx;
+            FL::element(lv.logits[base + c * stride], lab == (int64_t)c, P, loss, dx);
+            const float we = FL::weight_of(weight, weight_mode, row, C, c);
+            acc += (double)(loss * we);
+            if (lv.grad) lv.grad[base + c * stride] = (k0 * we) * dx;
         }
     });
-    double total = 0.0;
-    for (double v : part) total += v;
     out[0] = (float)(total * (double)k0);
     return SPH2POB_OK;
 }
@@ -910,48 +930,28 @@ int sph2pob_focal_loss_grad_scale_f32_cpu(const float* stash, const float* grad_
 namespace {
 namespace BL = sph2pob_bbox;
 
-// partial sums of kFocalRows rows each, added in order: the result does not move with the thread count
 template <int DIM, bool FAST>
-double bbox_loss_rows(const BL::Levels& L, int64_t B, const float* anchors, const float* targets, const float* weight, int wd,
-                      const C::Norm& nm, float max_ratio, int cflags, float ctr_clamp, int mode, float eps, float k0) {
-    const int64_t rows = L.rows, chunks = (rows + kFocalRows - 1) / kFocalRows;
-    std::vector<double> part((size_t)chunks, 0.0);
-    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
-        for (int64_t ch = lo; ch < hi; ch++) {
-            double acc = 0.0;
-            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
-                const int64_t b = row / L.n_total, j = row - b * L.n_total;
-                int l = 0;
-                for (int q = 1; q < L.num; q++) l += j >= L.lv[q].row_off ? 1 : 0;
-                const BL::Level& lv = L.lv[l];
-                int64_t stride;
-                const int64_t off = BL::delta_offset(lv, DIM, b, j - lv.row_off, &stride);
-                const float w = element_weight<DIM>(weight, wd, row);
-                if (!(w != 0.0f)) {   // never read: exact zeros
-                    if (lv.grad)
-                        for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = 0.0f;
-                    continue;
-                }
-                float p[5], d[5], t[5], box[5] = {0, 0, 0, 0, 0}, jac[5], gx[5], gy[5];
-                for (int k = 0; k < 5; k++) {
-                    p[k] = k < DIM ? anchors[j * DIM + k] : 0.0f;
-                    d[k] = k < DIM ? lv.pred[off + k * stride] : 0.0f;
-                    t[k] = k < DIM ? targets[row * DIM + k] : 0.0f;
-                }
-                C::decode_one<DIM, true>(p, d, nm, max_ratio, cflags, ctr_clamp, box, jac);
-                const float lo1 = pair_loss<DIM, true, FAST>(box, t, mode, eps, nullptr, gx, gy);
-                acc += (double)(lo1 * w);
-                if (lv.grad) {
-                    const float g = k0 * w;
-                    for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = (g * gx[k]) * jac[k];
-                }
+double bbox_loss_rows(const BL::Levels& L, const float* anchors, const float* targets, const float* weight, int wd, const C::Norm& nm,
+                      float max_ratio, int cflags, float ctr_clamp, int mode, float eps, float k0) {
+    return head_rows_sum(L, L.rows, [&](const BL::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
+        const float w = element_weight<DIM>(weight, wd, row);
+        box_row<DIM>(lv, b, i, w != 0.0f, [&](int64_t off, int64_t stride) {
+            const int64_t j = lv.row_off + i;
+            float p[5], d[5], t[5], box[5] = {0, 0, 0, 0, 0}, jac[5], gx[5], gy[5];
+            for (int k = 0; k < 5; k++) {
+                p[k] = k < DIM ? anchors[j * DIM + k] : 0.0f;
+                d[k] = k < DIM ? lv.pred[off + k * stride] : 0.0f;
+                t[k] = k < DIM ? targets[row * DIM + k] : 0.0f;
             }
-            part[(size_t)ch] = acc;
-        }
+            C::decode_one<DIM, true>(p, d, nm, max_ratio, cflags, ctr_clamp, box, jac);
+            const float lo1 = pair_loss<DIM, true, FAST>(box, t, mode, eps, nullptr, gx, gy);
+            acc += (double)(lo1 * w);
+            if (lv.grad) {
+                const float g = k0 * w;
+                for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = (g * gx[k]) * jac[k];
+            }
+        });
     });
-    double total = 0.0;
-    for (double v : part) total += v;
-    return total;
 }
 }  // namespace
 
@@ -972,7 +972,7 @@ int sph2pob_bbox_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* gr
     const bool fast = !(loss_mode & SPH2POB_FLAG_REFERENCE_ORDER);
     double total = 0.0;
     if (L.rows > 0) {
-#define SPH_BBOX_ROWS(D, F) bbox_loss_rows<D, F>(L, num_images, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags, ctr_clamp, mode, eps, k0)
+#define SPH_BBOX_ROWS(D, F) bbox_loss_rows<D, F>(L, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags, ctr_clamp, mode, eps, k0)
         if (box_dim == 4) total = fast ? SPH_BBOX_ROWS(4, true) : SPH_BBOX_ROWS(4, false);
         else total = fast ? SPH_BBOX_ROWS(5, true) : SPH_BBOX_ROWS(5, false);
 #undef SPH_BBOX_ROWS
@@ -989,37 +989,18 @@ namespace DL = sph2pob_delta;
 
 template <int DIM>
 double delta_loss_rows(const DL::Levels& L, const float* targets, const float* weight, int wd, float beta, float k0) {
-    const int64_t rows = L.rows, chunks = (rows + kFocalRows - 1) / kFocalRows;
-    std::vector<double> part((size_t)chunks, 0.0);
-    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
-        for (int64_t ch = lo; ch < hi; ch++) {
-            double acc = 0.0;
-            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
-                const int64_t b = row / L.n_total, j = row - b * L.n_total;
-                int l = 0;
-                for (int q = 1; q < L.num; q++) l += j >= L.lv[q].row_off ? 1 : 0;
-                const DL::Level& lv = L.lv[l];
-                int64_t stride;
-                const int64_t off = DL::delta_offset(lv, DIM, b, j - lv.row_off, &stride);
-                float wk[DIM];
-                if (!DL::row_weights<DIM>(weight, wd, false, row, wk)) {   // never read: exact zeros
-                    if (lv.grad)
-                        for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = 0.0f;
-                    continue;
-                }
-                for (int k = 0; k < DIM; k++) {
-                    float lo1, sk;
-                    DL::element(lv.pred[off + k * stride], targets[row * DIM + k], beta, lo1, sk);
-                    acc += (double)(lo1 * wk[k]);
-                    if (lv.grad) lv.grad[off + k * stride] = (k0 * wk[k]) * sk;
-                }
+    return head_rows_sum(L, L.rows, [&](const DL::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
+        float wk[DIM];
+        const bool live = DL::row_weights<DIM>(weight, wd, false, row, wk);
+        box_row<DIM>(lv, b, i, live, [&](int64_t off, int64_t stride) {
+            for (int k = 0; k < DIM; k++) {
+                float lo1, sk;
+                DL::element(lv.pred[off + k * stride], targets[row * DIM + k], beta, lo1, sk);
+                acc += (double)(lo1 * wk[k]);
+                if (lv.grad) lv.grad[off + k * stride] = (k0 * wk[k]) * sk;
             }
-            part[(size_t)ch] = acc;
-        }
+        });
     });
-    double total = 0.0;
-    for (double v : part) total += v;
-    return total;
 }
 }  // namespace
 

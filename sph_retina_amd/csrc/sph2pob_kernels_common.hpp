@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "../../include/sph2pob_hip.h"
+#include "sph2pob_head_loss.hpp"
 #include "sph2pob_device.hpp"
 #include "sph2pob_loss.hpp"
 #include "sph2pob_fast.hpp"
@@ -16,27 +17,13 @@ namespace {
 
 using namespace sph2pob;
 
-constexpr int kBlock = 256;  // 4 waves of 64 lanes
-constexpr int kCUsDefault = 256;  // MI355X in SPX mode: 8 XCDs x 32 CUs
+using sph2pob_head::kBlock;   // 4 waves of 64 lanes; launch_status() and cu_count() come from sph2pob_head_loss.hpp too
 
 // tuning / A-B knobs (environment, read once at load): SPH2POB_NO_COMPACT=1 disables the compacting kernels,
 // SPH2POB_ALIGNED_KERNEL=persistent selects the persistent form of the aligned kernel for the closed-form arithmetic
 // (the default is the one-round chunk form), SPH2POB_NO_PREFETCH=1 its register prefetch, SPH2POB_SLICES_PER_WAVE=s /
 // SPH2POB_WGS_PER_CU=k override its grid rule (s slices per wave, or exactly k workgroups per CU), SPH2POB_PW_ROWS the
 // pairwise kernel's rows per workgroup
-// CU count of the current device (a partitioned MI355X exposes fewer); queried once, no synchronisation involved
-static int cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            n = v;
-        else
-            n = kCUsDefault;
-    }
-    return n;
-}
 static bool g_no_compact = getenv("SPH2POB_NO_COMPACT") != nullptr;
 static bool g_prefetch = getenv("SPH2POB_NO_PREFETCH") == nullptr;
 static int g_pw_rows = getenv("SPH2POB_PW_ROWS") ? atoi(getenv("SPH2POB_PW_ROWS")) : 0;
@@ -89,11 +76,6 @@ inline int check_common(int box_dim, int variant_flags, int edge, int angle) {
     if (variant >= SPH2POB_VARIANT_LEGACY && variant <= SPH2POB_VARIANT_FOV_IOU && box_dim == 5)
         return SPH2POB_ERR_DIM;  // BFoV-only variants
     return SPH2POB_OK;
-}
-
-inline int launch_status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPH2POB_OK : (int)e;
 }
 
 // dispatch a (VARIANT, DIM) pair to a functor

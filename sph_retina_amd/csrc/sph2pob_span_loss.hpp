@@ -1,0 +1,113 @@
+// The span scheme of the two fused regression losses (bbox_loss_kernel, delta_loss_kernel), once.  ONE grid covers all images and
+// levels of a head: a workgroup finds its level in the table (sph2pob_bbox_loss.hpp), each of its four waves owns one span — a few
+// hundred consecutive anchors of one image and one level.  The wave scans the span 64 rows at a time and pushes the indices of the
+// rows that take part on a wave-private LDS stack (ballot / mbcnt, as the aligned chunk kernel compacts its survivors), then
+// evaluates them in dense passes of up to 64.  The span's slice of the gradient is assembled in a wave-private LDS tile laid out
+// like the head's tensor — zeros, then the live rows' values — and leaves in one sweep: every element is stored once, by one lane,
+// in whole 16-byte stores along w where the level allows it.  The weighted losses are added in double per lane, wave and workgroup:
+// one partial per workgroup.  A row that does not take part is never read: its loss and gradient are exact zeros.
+// Device units only (after sph2pob_kernels_common.hpp's rank_below / wave_lds_fence).
+#pragma once
+#include <type_traits>
+
+#include "sph2pob_kernels_common.hpp"
+#include "sph2pob_bbox_loss.hpp"
+
+namespace {
+
+static_assert(kBlock == 64 * sph2pob_bbox::kWaves, "one span per wave");
+
+// live(row) -> bool: does row `row` (of the (B, n) rows of the call) take part.
+// eval(lv, b, i, row, k0, g, acc): one live row — anchor i of level lv in image b; adds the row's weighted losses to `acc` in
+// component order and, under GRAD, leaves the DIM gradient values in g.
+template <int DIM, bool GRAD, class Live, class Eval>
+__device__ __forceinline__ void span_loss(const sph2pob_bbox::Levels& L, float scale, const float* __restrict__ avg_factor,
+                                          double* __restrict__ partial, Live live, Eval eval) {
+    namespace BL = sph2pob_bbox;
+    __shared__ __attribute__((aligned(16))) float tile_s[GRAD ? BL::kWaves * BL::kTile : 4];
+    __shared__ unsigned short stack_s[BL::kWaves * BL::kStack];
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int l = level_of_block(L, blockIdx.x);
+    const BL::Level& lv = L.lv[l];
+    const int item = ((int)blockIdx.x - lv.block_off) * BL::kWaves + wave;
+    double acc = 0.0;
+    if (item < lv.items) {   // wave-uniform
+        const int b = item / lv.spans, sp = item - b * lv.spans;
+        const int p_lo = sp * lv.ps;
+        const int cnt = min(lv.ps, lv.pos - p_lo);        // positions of this span
+        const int na = cnt * lv.a, i_lo = p_lo * lv.a;    // its anchors: [i_lo, i_lo + na) of the level, na <= kStack
+        const int64_t row0 = (int64_t)b * L.n_total + lv.row_off + i_lo;
+        float* tile = tile_s + (GRAD ? wave * BL::kTile : 0);
+        unsigned short* stack = stack_s + wave * BL::kStack;
+        if (GRAD) {   // the span's slice of the gradient: zeros first
+            const int used = lv.a * DIM * lv.ps;          // <= kTile, a multiple of 4
+            for (int e = lane * 4; e < used; e += 256) *reinterpret_cast<float4*>(tile + e) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        // the rows that take part, in anchor order
+        int top = 0;
+        for (int s0 = 0; s0 < na; s0 += 64) {
+            const int s = s0 + lane;
+            const bool on = live(row0 + (s < na ? s : 0)) && s < na;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(on);
+            if (on) stack[top + rank_below(m)] = (unsigned short)s;
+            top += __popcll(m);
+        }
+        wave_lds_fence();
+        const float k0 = GRAD ? BL::effective_scale(scale, avg_factor) : 0.0f;
+        for (int base = 0; base < top; base += 64) {
+            const int j = base + lane;
+            if (j < top) {
+                const int s = stack[j];
+                float g[DIM];
+                eval(lv, b, i_lo + s, row0 + s, k0, g, acc);
+                if (GRAD) {
+                    if (lv.hw > 0) {
+                        const int pp = s / lv.a, aa = s - pp * lv.a;
+#pragma unroll
+                        for (int k = 0; k < DIM; k++) tile[(aa * DIM + k) * lv.ps + pp] = g[k];
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < DIM; k++) tile[s * DIM + k] = g[k];
+                    }
+                }
+            }
+        }
+        if (GRAD) {
+            wave_lds_fence();
+            // the tile is `rows` rows of `len` floats: NCHW — one row per channel, the span's positions; flat — one row
+            const int rows = lv.hw > 0 ? lv.a * DIM : 1;
+            const int len = lv.hw > 0 ? cnt : cnt * DIM;
+            const int lstride = lv.hw > 0 ? lv.ps : 0;
+            const int64_t gstride = lv.hw > 0 ? lv.hw : 0;
+            float* g0 = lv.grad + (lv.hw > 0 ? (int64_t)b * lv.a * DIM * lv.hw + p_lo : ((int64_t)b * lv.n + i_lo) * DIM);
+            if (lv.vec) {   // workgroup-uniform; len, lstride, gstride and g0 are multiples of 4 floats
+                const int q4 = len >> 2, total = rows * q4;
+                for (int e = lane; e < total; e += 64) {
+                    const int r = e / q4, q = e - r * q4;
+                    *reinterpret_cast<float4*>(g0 + r * gstride + 4 * q) = *reinterpret_cast<const float4*>(tile + r * lstride + 4 * q);
+                }
+            } else {
+                const int total = rows * len;
+                for (int e = lane; e < total; e += 64) {
+                    const int r = e / len, q = e - r * len;
+                    g0[r * gstride + q] = tile[r * lstride + q];
+                }
+            }
+        }
+    }
+    const double r = block_sum_f64(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// f(integral_constant<int, DIM>, bool_constant<GRAD>) for the box_dim (4 | 5) and the gradient request of a call
+template <class F>
+void by_dim_grad(int box_dim, bool grad, F&& f) {
+    auto by_grad = [&](auto dim) {
+        if (grad) f(dim, std::true_type{});
+        else f(dim, std::false_type{});
+    };
+    if (box_dim == 4) by_grad(std::integral_constant<int, 4>{});
+    else by_grad(std::integral_constant<int, 5>{});
+}
+
+}  // namespace

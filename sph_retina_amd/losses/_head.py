@@ -1,0 +1,171 @@
+"""What the fused head losses (`sph_focal_loss`, `sph_bbox_loss`, `sph_delta_loss`) share on the Python side: the fp32 scale
+rule of `weight_reduce_loss`, the level plumbing with its checks, and the gradient-stash protocol of their autograd nodes.
+
+The stash protocol: when a gradient will be asked for, the one forward pass also writes the gradients for an upstream gradient of
+1 — all levels in one buffer, each a 16-byte aligned view in its own layout — and torch's backward only scales that stash
+(`sph2pob_focal_loss_grad_scale_f32`: in place, a plain `loss.backward()` returns at once).  A second backward through a retained
+graph finds the stash already scaled and handed to autograd, so it recomputes into a fresh buffer."""
+import ctypes
+import struct
+
+import torch
+
+from .. import _lib
+from .. import _torch_glue as G
+
+_MAX_LEVELS = 8
+_F32_EPS = float(torch.finfo(torch.float32).eps)
+
+
+def _f32(v):
+    """v rounded to fp32 (as a Python float)."""
+    return struct.unpack('f', struct.pack('f', v))[0]
+
+
+def _host_scale(loss_weight, divisor):
+    """loss_weight / (divisor + eps) with the fp32 roundings the kernel applies to a device divisor, so that a Python number and
+    the same value in a device tensor give the same bits (each double operation on fp32 operands rounds to fp32 correctly)."""
+    return _f32(_f32(loss_weight) / _f32(_f32(divisor) + _F32_EPS))
+
+
+def _f32c(t):
+    return t if t.dtype is torch.float32 and t.is_contiguous() else G.as_f32(t.detach())
+
+
+def _avg_tensor(avg_factor, dev):
+    a = avg_factor.detach().reshape(-1)
+    if a.numel() != 1:
+        raise ValueError(f'avg_factor must hold one value, got {tuple(avg_factor.shape)}')
+    if a.device != dev:
+        raise RuntimeError(f'avg_factor is on {a.device}, the logits on {dev}: a tensor divisor must live with the logits')
+    return a if a.dtype is torch.float32 else a.float()
+
+
+def _reduce_scale(reduction, avg_factor, loss_weight, elems, dev):
+    """(host scale, device divisor | None, nan) of weight_reduce_loss (mmdet/models/losses/utils.py:30-58)."""
+    if avg_factor is not None and reduction == 'sum':
+        raise ValueError('avg_factor can not be used with reduction="sum"')
+    if reduction == 'sum':
+        return float(loss_weight), None, False
+    if avg_factor is None:
+        if elems == 0:   # torch: the mean of an empty tensor is nan
+            return float(loss_weight), None, True
+        return float(loss_weight) / elems, None, False
+    if isinstance(avg_factor, torch.Tensor):
+        return float(loss_weight), _avg_tensor(avg_factor, dev), False
+    return _host_scale(float(loss_weight), float(avg_factor)), None, False
+
+
+# ---- the checks every head loss starts with; `fn` is the public function's name, so each message names its caller ----
+
+def check_reduction(fn, reduction, instead):
+    if reduction == 'none':
+        raise ValueError(f"{fn} returns the reduced scalar ('mean' | 'sum'); {instead}")
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+
+
+def check_levels(fn, levels):
+    if not (1 <= len(levels) <= _MAX_LEVELS):
+        raise ValueError(f'{fn} takes 1 to {_MAX_LEVELS} levels, got {len(levels)}')
+
+
+def check_one_device(fn, tensors):
+    G.require_hip(*tensors)
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f'{fn}: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
+
+
+def box_levels(name, bbox_preds, images, dim):
+    """(hws, anchors per image) of L regression levels, each NCHW (B, A * dim, H, W) -> H W or flattened (B, n_l, dim) -> 0."""
+    hws, total = [], 0
+    for l, p in enumerate(bbox_preds):
+        if p.dim() == 4 and p.size(0) == images and p.size(1) % dim == 0:
+            hws.append(p.size(2) * p.size(3))
+            total += p.size(1) // dim * hws[-1]
+        elif p.dim() == 3 and p.size(0) == images and p.size(2) == dim:
+            hws.append(0)
+            total += p.size(1)
+        else:
+            raise ValueError(f'{name}[{l}]: expected (B, A * {dim}, H, W) or (B, n_l, {dim}) with B = {images}, got {tuple(p.shape)}')
+    return hws, total
+
+
+def weight_dim(bbox_weights, images, n, dim, targets_shape):
+    """The kernels' weight_dim: 0 without weights, 1 for (B, n), dim for (B, n, dim)."""
+    if bbox_weights is None:
+        return 0
+    if tuple(bbox_weights.shape) == (images, n):
+        return 1
+    if tuple(bbox_weights.shape) == (images, n, dim):
+        return dim
+    raise ValueError(f'bbox_weights must be (B, n) or (B, n, dim) like bbox_targets {tuple(targets_shape)}, got {tuple(bbox_weights.shape)}')
+
+
+# ---- buffers ----
+
+def workspace(entry_name, what, dev, ns, hws, images, last):
+    """The partial-sum workspace of sph2pob_<entry_name>_sum_f32; `last` is the class count or the box dimension."""
+    levels = len(ns)
+    i64s = ctypes.c_int64 * levels
+    need = getattr(_lib.lib(), f'sph2pob_{entry_name}_workspace_bytes')(i64s(*ns), i64s(*hws), levels, images, last)
+    if need <= 0:
+        raise ValueError(f'{what}: these shapes are outside the limits of sph2pob_{entry_name}_sum_f32 (include/sph2pob_hip.h)')
+    return G.scratch(dev, need)
+
+
+def scalar(dev):
+    """The fp32 scalar an entry writes its sum to."""
+    return torch.empty((), dtype=torch.float32, device=dev)
+
+
+def grad_buffer(xs):
+    """One buffer for the gradients of all levels (a single scaling launch in backward), each level a 16-byte aligned view."""
+    offs, total = [], 0
+    for x in xs:
+        offs.append(total)
+        total += (x.numel() + 3) // 4 * 4
+    stash = torch.empty((total,), dtype=torch.float32, device=xs[0].device)
+    return stash, [stash[o:o + x.numel()].view(x.shape) for o, x in zip(offs, xs)]
+
+
+# ---- the stash protocol of the autograd nodes; `fixed` is the number of arguments in front of the levels ----
+
+def stash_forward(ctx, fixed, xs, launch, saved):
+    """Forward side: `launch(views)` runs the fused entry, with the stash's per-level views when any level needs a gradient and
+    None otherwise; `saved` are the tensors the backward needs besides the stash and the levels."""
+    need = any(ctx.needs_input_grad[fixed:])
+    stash = views = None
+    if need:
+        stash, views = grad_buffer(xs)
+    launch(views)
+    if need:
+        ctx.save_for_backward(stash, *saved, *xs)
+        ctx.views = views
+        ctx.first = True
+
+
+def stash_backward(ctx, fixed, grad_out, stash, dtypes, relaunch):
+    """Backward side: the first call scales the forward's stash in place; later calls take `relaunch(g) -> (buffer, views)` — a
+    fresh buffer to scale, or None where the views already hold the scaled gradient.  Returns backward's tuple."""
+    dev = stash.device
+    g = _f32c(grad_out).reshape(1)
+    if ctx.first:
+        ctx.first = False
+        views = ctx.views
+    else:
+        stash, views = relaunch(g)
+    if stash is not None:
+        G.call('sph2pob_focal_loss_grad_scale_f32', dev, G.ptr(stash), g.data_ptr(), G.ptr(stash), stash.numel(), G.raw_stream_of(dev))
+    grads = [(v if dt is torch.float32 else v.to(dt)) if need else None
+             for v, dt, need in zip(views, dtypes, ctx.needs_input_grad[fixed:])]
+    return (None,) * fixed + tuple(grads)
+
+
+def relaunch_fresh(xs, launch):
+    """The usual `relaunch` of stash_backward: the fused entry again, into a fresh buffer."""
+    def relaunch(_g):
+        fresh, views = grad_buffer(xs)
+        launch(views)
+        return fresh, views
+    return relaunch

@@ -19,88 +19,48 @@ import math
 
 import torch
 
-from .. import _lib
 from .. import _torch_glue as G
-from .focal_loss import _MAX_LEVELS, _f32c, _reduce_scale
+from . import _head as H
+from ._head import _f32c, _reduce_scale
 from .sph2pob_iou_loss import LOSS_MODES, _mode_code
-
-
-def _workspace(dev, ns, hws, images, dim):
-    levels = len(ns)
-    i64s = ctypes.c_int64 * levels
-    need = _lib.lib().sph2pob_bbox_loss_workspace_bytes(i64s(*ns), i64s(*hws), levels, images, dim)
-    if need <= 0:
-        raise ValueError('bbox loss: these shapes are outside the limits of sph2pob_bbox_loss_sum_f32 (include/sph2pob_hip.h)')
-    return G.scratch(dev, need)
 
 
 class _BBoxLossFunction(torch.autograd.Function):
     """(anchors, targets, weight, ..., *bbox_preds of L levels) -> scale_eff * sum of the weighted box losses; one node with L
-    inputs.  When a gradient will be asked for, the one forward pass also writes the gradients for an upstream gradient of 1 (all
-    levels in one buffer, each a 16-byte aligned view in its own layout) and torch's backward only scales that stash
-    (`sph2pob_focal_loss_grad_scale_f32`: in place, a plain `loss.backward()` returns at once).  A second backward through a
-    retained graph recomputes with the same entry into a fresh buffer."""
+    inputs and the gradient stash of `_head`.  A second backward through a retained graph recomputes with the same entry into a
+    fresh buffer."""
+
+    _FIXED = 10   # arguments in front of the levels
 
     @staticmethod
     def forward(ctx, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, hws, *preds):
-        levels = len(preds)
         xs = [_f32c(p) for p in preds]
-        dev = xs[0].device
         images, dim = targets.size(0), anchors.size(1)
         ns = [x.numel() // (images * dim) if images else 0 for x in xs]
-        need = any(ctx.needs_input_grad[10:])
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        stash = views = None
-        if need:
-            stash, views = _BBoxLossFunction._grad_buffer(xs)
-        _BBoxLossFunction._launch(dev, xs, views, ns, hws, images, dim, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out)
-        if need:
-            ctx.save_for_backward(stash, anchors, targets, weight, avg, *xs)
-            ctx.views = views
-            ctx.first = True
+        out = H.scalar(xs[0].device)
         ctx.meta = (wd, coder_cfg, mode, eps, scale, tuple(hws), tuple(ns), [p.dtype for p in preds])
+        H.stash_forward(ctx, _BBoxLossFunction._FIXED, xs,
+                        lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out),
+                        (anchors, targets, weight, avg))
         return out
 
     @staticmethod
-    def _launch(dev, xs, views, ns, hws, images, dim, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out):
-        levels = len(xs)
+    def _launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out):
+        levels, dev, images, dim = len(xs), xs[0].device, targets.size(0), anchors.size(1)
         means, stds, max_ratio, flags, ctr_clamp = coder_cfg
         ptrs, i64s, f32s = ctypes.c_void_p * levels, ctypes.c_int64 * levels, ctypes.c_float * dim
-        ws = _workspace(dev, ns, hws, images, dim)   # held over the call
+        ws = H.workspace('bbox_loss', 'bbox loss', dev, ns, hws, images, dim)   # held over the call
         G.call('sph2pob_bbox_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None,
                i64s(*ns), i64s(*hws), levels, images, dim, G.ptr(anchors), G.ptr(targets), G.ptr(weight), wd, f32s(*means), f32s(*stds),
                max_ratio, flags, ctr_clamp, mode, eps, scale, G.ptr(avg), out.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
 
     @staticmethod
-    def _grad_buffer(xs):
-        """One buffer for the gradients of all levels (a single scaling launch in backward), each level a 16-byte aligned view."""
-        offs, total = [], 0
-        for x in xs:
-            offs.append(total)
-            total += (x.numel() + 3) // 4 * 4
-        stash = torch.empty((total,), dtype=torch.float32, device=xs[0].device)
-        return stash, [stash[o:o + x.numel()].view(x.shape) for o, x in zip(offs, xs)]
-
-    @staticmethod
     def backward(ctx, grad_out):
         stash, anchors, targets, weight, avg, *xs = ctx.saved_tensors
         wd, coder_cfg, mode, eps, scale, hws, ns, dtypes = ctx.meta
-        dev = stash.device
-        g = _f32c(grad_out).reshape(1)
-        stream = G.raw_stream_of(dev)
-        if ctx.first:
-            ctx.first = False
-            views = ctx.views
-        else:
-            # the stash was scaled in place and handed to autograd by the first backward: the fused pass into a fresh buffer
-            stash, views = _BBoxLossFunction._grad_buffer(xs)
-            out = torch.empty((), dtype=torch.float32, device=dev)
-            _BBoxLossFunction._launch(dev, xs, views, ns, hws, targets.size(0), anchors.size(1), anchors, targets, weight, wd, coder_cfg,
-                                      mode, eps, scale, avg, out)
-        G.call('sph2pob_focal_loss_grad_scale_f32', dev, G.ptr(stash), g.data_ptr(), G.ptr(stash), stash.numel(), stream)
-        grads = [(v if dt is torch.float32 else v.to(dt)) if need else None
-                 for v, dt, need in zip(views, dtypes, ctx.needs_input_grad[10:])]
-        return (None,) * 10 + tuple(grads)
+        relaunch = H.relaunch_fresh(xs, lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg,
+                                                                              mode, eps, scale, avg, H.scalar(stash.device)))
+        return H.stash_backward(ctx, _BBoxLossFunction._FIXED, grad_out, stash, dtypes, relaunch)
 
 
 def _coder_cfg(bbox_coder, dim):
@@ -126,16 +86,11 @@ def sph_bbox_loss(bbox_preds, anchors, bbox_targets, bbox_weights=None, *, bbox_
     without the copies and without the work on the rows of weight 0; the gradient arrives at each bbox_preds[l] in its own layout
     (one autograd node with L inputs).  `avg_factor`: a number or a device tensor such as `AnchorTargets.avg_factor`; 'mean'
     without it divides by B n."""
-    if reduction == 'none':
-        raise ValueError("sph_bbox_loss returns the reduced scalar ('mean' | 'sum'); for the loss of every box use "
-                         "Sph2PobIoULoss(reduction='none') on bbox_coder.decode(...)")
-    if reduction not in ('mean', 'sum'):
-        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    H.check_reduction('sph_bbox_loss', reduction, "for the loss of every box use Sph2PobIoULoss(reduction='none') on bbox_coder.decode(...)")
     if mode not in LOSS_MODES:
         raise ValueError(f'mode must be one of {sorted(LOSS_MODES)}, got {mode!r}')
     bbox_preds = list(bbox_preds)
-    if not (1 <= len(bbox_preds) <= _MAX_LEVELS):
-        raise ValueError(f'sph_bbox_loss takes 1 to {_MAX_LEVELS} levels, got {len(bbox_preds)}')
+    H.check_levels('sph_bbox_loss', bbox_preds)
     if isinstance(anchors, (list, tuple)):
         anchors = torch.cat(list(anchors), 0)
     if anchors.dim() != 2 or anchors.size(1) not in (4, 5):
@@ -144,28 +99,9 @@ def sph_bbox_loss(bbox_preds, anchors, bbox_targets, bbox_weights=None, *, bbox_
     if bbox_targets.dim() != 3 or tuple(bbox_targets.shape[1:]) != (n, dim):
         raise ValueError(f'bbox_targets must be (B, n, dim) = (B, {n}, {dim}), got {tuple(bbox_targets.shape)}')
     images = bbox_targets.size(0)
-    tensors = bbox_preds + [anchors, bbox_targets] + ([bbox_weights] if bbox_weights is not None else [])
-    G.require_hip(*tensors)
-    if len({t.device for t in tensors}) != 1:
-        raise RuntimeError('sph_bbox_loss: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
-    if bbox_weights is None:
-        wd = 0
-    elif tuple(bbox_weights.shape) == (images, n):
-        wd = 1
-    elif tuple(bbox_weights.shape) == (images, n, dim):
-        wd = dim
-    else:
-        raise ValueError(f'bbox_weights must be (B, n) or (B, n, dim) like bbox_targets {tuple(bbox_targets.shape)}, got {tuple(bbox_weights.shape)}')
-    hws, total = [], 0
-    for l, p in enumerate(bbox_preds):
-        if p.dim() == 4 and p.size(0) == images and p.size(1) % dim == 0:
-            hws.append(p.size(2) * p.size(3))
-            total += p.size(1) // dim * hws[-1]
-        elif p.dim() == 3 and p.size(0) == images and p.size(2) == dim:
-            hws.append(0)
-            total += p.size(1)
-        else:
-            raise ValueError(f'bbox_preds[{l}]: expected (B, A * {dim}, H, W) or (B, n_l, {dim}) with B = {images}, got {tuple(p.shape)}')
+    H.check_one_device('sph_bbox_loss', bbox_preds + [anchors, bbox_targets] + ([bbox_weights] if bbox_weights is not None else []))
+    wd = H.weight_dim(bbox_weights, images, n, dim, bbox_targets.shape)
+    hws, total = H.box_levels('bbox_preds', bbox_preds, images, dim)
     if total != n:
         raise ValueError(f'the levels hold {total} anchors per image, anchors {n}')
     scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n, anchors.device)

@@ -19,33 +19,16 @@ The sum is deterministic (double partials per workgroup, fixed-order final pass,
 captured in a graph.  Difference from the reference: `avg_factor` is a count, no gradient flows into it.
 """
 import ctypes
-import struct
 
 import torch
 import torch.nn as nn
 
-from .. import _lib
 from .. import _torch_glue as G
 from ..registry import LOSSES, LOSSES_IS_MMDET
+from . import _head as H
+from ._head import _f32c, _reduce_scale
 
-_MAX_LEVELS = 8
-_F32_EPS = float(torch.finfo(torch.float32).eps)
 _WEIGHT_NONE, _WEIGHT_ROW, _WEIGHT_ELEM = 0, 1, 2
-
-
-def _f32(v):
-    """v rounded to fp32 (as a Python float)."""
-    return struct.unpack('f', struct.pack('f', v))[0]
-
-
-def _host_scale(loss_weight, divisor):
-    """loss_weight / (divisor + eps) with the fp32 roundings the kernel applies to a device divisor, so that a Python number and
-    the same value in a device tensor give the same bits (each double operation on fp32 operands rounds to fp32 correctly)."""
-    return _f32(_f32(loss_weight) / _f32(_f32(divisor) + _F32_EPS))
-
-
-def _f32c(t):
-    return t if t.dtype is torch.float32 and t.is_contiguous() else G.as_f32(t.detach())
 
 
 def _labels(t):
@@ -53,95 +36,50 @@ def _labels(t):
     return t if t.dtype is torch.int64 and t.is_contiguous() else t.to(torch.int64).contiguous()
 
 
-def _avg_tensor(avg_factor, dev):
-    a = avg_factor.detach().reshape(-1)
-    if a.numel() != 1:
-        raise ValueError(f'avg_factor must hold one value, got {tuple(avg_factor.shape)}')
-    if a.device != dev:
-        raise RuntimeError(f'avg_factor is on {a.device}, the logits on {dev}: a tensor divisor must live with the logits')
-    return a if a.dtype is torch.float32 else a.float()
-
-
-def _workspace(dev, ns, hws, images, classes):
-    levels = len(ns)
-    i64s = ctypes.c_int64 * levels
-    need = _lib.lib().sph2pob_focal_loss_workspace_bytes(i64s(*ns), i64s(*hws), levels, images, classes)
-    if need <= 0:
-        raise ValueError('focal loss: these shapes are outside the limits of sph2pob_focal_loss_sum_f32 (include/sph2pob_hip.h)')
-    return G.scratch(dev, need)
-
-
 class _FocalSumFunction(torch.autograd.Function):
-    """(C, labels, weight, ..., *logits of L levels) -> scale_eff * sum of the weighted element losses; one node with L inputs.
-    When a gradient will be asked for, the one forward pass also writes the gradients for an upstream gradient of 1 (all levels
-    in one buffer, each in its own layout), and torch's backward only scales that stash
-    (`sph2pob_focal_loss_grad_scale_f32`: in place, a plain `loss.backward()` returns at once).  A second backward through a
-    retained graph recomputes: the two-pass kernel for one flat level, the fused pass into a fresh buffer otherwise."""
+    """(C, labels, weight, ..., *logits of L levels) -> scale_eff * sum of the weighted element losses; one node with L inputs and
+    the gradient stash of `_head`.  A second backward through a retained graph recomputes: the two-pass kernel for one flat level,
+    the fused pass into a fresh buffer otherwise."""
+
+    _FIXED = 9   # arguments in front of the levels
 
     @staticmethod
     def forward(ctx, classes, labels, weight, wmode, gamma, alpha, scale, avg, hws, *scores):
-        levels = len(scores)
         xs = [_f32c(s) for s in scores]
-        dev = xs[0].device
         images = xs[0].size(0)
         ctx.classes = classes
         ns = [x.numel() // (images * classes) if images else 0 for x in xs]
-        need = any(ctx.needs_input_grad[9:])
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        ptrs, i64s = ctypes.c_void_p * levels, ctypes.c_int64 * levels
-        ws = _workspace(dev, ns, hws, images, classes)
-        stash = views = None
-        if need:
-            stash, views = _FocalSumFunction._grad_buffer(xs)
-        G.call('sph2pob_focal_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if need else None,
-               i64s(*ns), i64s(*hws), levels, images, classes, G.ptr(labels), G.ptr(weight), wmode, gamma, alpha, scale, G.ptr(avg),
-               out.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
-        if need:
-            ctx.save_for_backward(stash, labels, weight, avg, *xs)
-            ctx.views = views
-            ctx.first = True
+        out = H.scalar(xs[0].device)
         ctx.meta = (wmode, gamma, alpha, scale, tuple(hws), tuple(ns), [s.dtype for s in scores])
+        H.stash_forward(ctx, _FocalSumFunction._FIXED, xs,
+                        lambda views: _FocalSumFunction._launch(xs, views, ns, hws, classes, labels, weight, wmode, gamma, alpha, scale, avg, out),
+                        (labels, weight, avg))
         return out
 
     @staticmethod
-    def _grad_buffer(xs):
-        """One buffer for the gradients of all levels (a single scaling launch in backward), each level a 16-byte aligned view."""
-        offs, total = [], 0
-        for x in xs:
-            offs.append(total)
-            total += (x.numel() + 3) // 4 * 4
-        stash = torch.empty((total,), dtype=torch.float32, device=xs[0].device)
-        return stash, [stash[o:o + x.numel()].view(x.shape) for o, x in zip(offs, xs)]
+    def _launch(xs, views, ns, hws, classes, labels, weight, wmode, gamma, alpha, scale, avg, out):
+        levels, dev, images = len(xs), xs[0].device, xs[0].size(0)
+        ptrs, i64s = ctypes.c_void_p * levels, ctypes.c_int64 * levels
+        ws = H.workspace('focal_loss', 'focal loss', dev, ns, hws, images, classes)   # held over the call
+        G.call('sph2pob_focal_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None,
+               i64s(*ns), i64s(*hws), levels, images, classes, G.ptr(labels), G.ptr(weight), wmode, gamma, alpha, scale, G.ptr(avg),
+               out.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
 
     @staticmethod
     def backward(ctx, grad_out):
         stash, labels, weight, avg, *xs = ctx.saved_tensors
         wmode, gamma, alpha, scale, hws, ns, dtypes = ctx.meta
         dev = stash.device
-        g = _f32c(grad_out).reshape(1)
-        stream = G.raw_stream_of(dev)
-        levels = len(xs)
-        if ctx.first:
-            ctx.first = False
-            views = ctx.views
-            G.call('sph2pob_focal_loss_grad_scale_f32', dev, G.ptr(stash), g.data_ptr(), G.ptr(stash), stash.numel(), stream)
-        elif levels == 1 and hws[0] == 0:
-            # the stash was scaled in place and handed to autograd by the first backward: the two-pass kernel
-            views = [torch.empty_like(xs[0])]
-            G.call('sph2pob_focal_loss_bwd_f32', dev, G.ptr(xs[0]), G.ptr(labels), G.ptr(weight), wmode, g.data_ptr(), 0, gamma, alpha,
-                   scale, G.ptr(avg), G.ptr(views[0]), xs[0].numel() // ctx.classes, ctx.classes, stream)
+        if len(xs) == 1 and hws[0] == 0:
+            def relaunch(g):   # one flat level: the two-pass kernel, which takes the upstream gradient itself
+                views = [torch.empty_like(xs[0])]
+                G.call('sph2pob_focal_loss_bwd_f32', dev, G.ptr(xs[0]), G.ptr(labels), G.ptr(weight), wmode, g.data_ptr(), 0, gamma, alpha,
+                       scale, G.ptr(avg), G.ptr(views[0]), xs[0].numel() // ctx.classes, ctx.classes, G.raw_stream_of(dev))
+                return None, views
         else:
-            fresh, views = _FocalSumFunction._grad_buffer(xs)
-            images = xs[0].size(0)
-            ptrs, i64s = ctypes.c_void_p * levels, ctypes.c_int64 * levels
-            out, ws = torch.empty((), dtype=torch.float32, device=dev), _workspace(dev, ns, hws, images, ctx.classes)   # held over the call
-            G.call('sph2pob_focal_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]), i64s(*ns), i64s(*hws),
-                   levels, images, ctx.classes, G.ptr(labels), G.ptr(weight), wmode, gamma, alpha, scale, G.ptr(avg), out.data_ptr(), G.ptr(ws),
-                   stream)
-            G.call('sph2pob_focal_loss_grad_scale_f32', dev, G.ptr(fresh), g.data_ptr(), G.ptr(fresh), fresh.numel(), stream)
-        grads = [(v if dt is torch.float32 else v.to(dt)) if need else None
-                 for v, dt, need in zip(views, dtypes, ctx.needs_input_grad[9:])]
-        return (None,) * 9 + tuple(grads)
+            relaunch = H.relaunch_fresh(xs, lambda views: _FocalSumFunction._launch(xs, views, ns, hws, ctx.classes, labels, weight, wmode,
+                                                                                  gamma, alpha, scale, avg, H.scalar(stash.device)))
+        return H.stash_backward(ctx, _FocalSumFunction._FIXED, grad_out, stash, dtypes, relaunch)
 
 
 class _FocalNoneFunction(torch.autograd.Function):
@@ -173,21 +111,6 @@ class _FocalNoneFunction(torch.autograd.Function):
         return (gx if dt is torch.float32 else gx.to(dt)), None, None, None, None, None, None
 
 
-def _reduce_scale(reduction, avg_factor, loss_weight, elems, dev):
-    """(host scale, device divisor | None, nan) of weight_reduce_loss (mmdet/models/losses/utils.py:30-58)."""
-    if avg_factor is not None and reduction == 'sum':
-        raise ValueError('avg_factor can not be used with reduction="sum"')
-    if reduction == 'sum':
-        return float(loss_weight), None, False
-    if avg_factor is None:
-        if elems == 0:   # torch: the mean of an empty tensor is nan
-            return float(loss_weight), None, True
-        return float(loss_weight) / elems, None, False
-    if isinstance(avg_factor, torch.Tensor):
-        return float(loss_weight), _avg_tensor(avg_factor, dev), False
-    return _host_scale(float(loss_weight), float(avg_factor)), None, False
-
-
 def _check_params(gamma, alpha):
     gamma, alpha = float(gamma), float(alpha)
     if not gamma >= 0:
@@ -208,10 +131,7 @@ def sigmoid_focal_loss(pred, target, weight=None, gamma=2.0, alpha=0.25, reducti
         raise ValueError(f'target must hold integer labels, got {target.dtype}')
     gamma, alpha = _check_params(gamma, alpha)
     n, c = pred.shape
-    tensors = [pred, target] + ([weight] if weight is not None else [])
-    G.require_hip(*tensors)
-    if len({t.device for t in tensors}) != 1:
-        raise RuntimeError('sigmoid_focal_loss: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
+    H.check_one_device('sigmoid_focal_loss', [pred, target] + ([weight] if weight is not None else []))
     wmode, w = _WEIGHT_NONE, None
     if weight is not None:
         if tuple(weight.shape) == (n, c) or (weight.size(0) != n and weight.numel() == n * c):
@@ -239,21 +159,13 @@ def sph_focal_loss(cls_scores, labels, label_weights=None, *, gamma=2.0, alpha=0
     `AnchorTargets` holds them.  Equals FocalLoss on cat([s.permute(0, 2, 3, 1).reshape(B, -1, C)]).reshape(-1, C) without the
     copies; the gradient arrives at each cls_scores[l] in its own layout (one autograd node with L inputs).  `avg_factor`: a number
     or a device tensor such as `AnchorTargets.avg_factor`; 'mean' without it divides by B n C."""
-    if reduction == 'none':
-        raise ValueError("sph_focal_loss returns the reduced scalar ('mean' | 'sum'); for element losses use sigmoid_focal_loss on "
-                         "the flat (N, C) logits")
-    if reduction not in ('mean', 'sum'):
-        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    H.check_reduction('sph_focal_loss', reduction, 'for element losses use sigmoid_focal_loss on the flat (N, C) logits')
     cls_scores = list(cls_scores)
-    if not (1 <= len(cls_scores) <= _MAX_LEVELS):
-        raise ValueError(f'sph_focal_loss takes 1 to {_MAX_LEVELS} levels, got {len(cls_scores)}')
+    H.check_levels('sph_focal_loss', cls_scores)
     gamma, alpha = _check_params(gamma, alpha)
     if labels.dim() != 2 or labels.dtype.is_floating_point or labels.dtype is torch.bool:
         raise ValueError(f'labels must be (B, n) integer labels, got {tuple(labels.shape)} {labels.dtype}')
-    tensors = cls_scores + [labels] + ([label_weights] if label_weights is not None else [])
-    G.require_hip(*tensors)
-    if len({t.device for t in tensors}) != 1:
-        raise RuntimeError('sph_focal_loss: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
+    H.check_one_device('sph_focal_loss', cls_scores + [labels] + ([label_weights] if label_weights is not None else []))
     images, n = labels.shape
     if label_weights is None:
         wmode, classes = _WEIGHT_NONE, None

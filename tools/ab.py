@@ -18,6 +18,8 @@ Workloads (all through the C ABI, buffers allocated once, HIP events around `--l
   loss      sph2pob_loss_fwd_grad_f32 + final sum + grad_scale, 1 M nearby RBFoV pairs, CIoU (configs[2])
   nms       sph2pob_nms_segmented_f32 on 5 000 sorted boxes x 37 classes and on one class of 5 000
   bnms      sph2pob_batched_nms_f32 (unsorted input, no host work) on the same two scenes
+  head_losses  sph2pob_{focal,bbox,delta}_loss_sum_f32, each timed on its own, with gradients: 8 images x the 5 NCHW levels of the
+            512 x 1024 ERP (98 208 anchors), 37 classes, dim 4, CIoU closed-form / L1, ~1 % live rows, a device avg_factor
 Every arm's outputs are compared with the first arm's (bit equality is reported, not assumed).
 """
 import argparse
@@ -202,6 +204,41 @@ def workloads(args, torch, G):
                 ws = torch.empty(lib.sph2pob_nms_segmented_workspace_bytes(k, seg) // 8 + 8, dtype=torch.int64, device='cuda')
                 return (lambda: lib.sph2pob_nms_segmented_f32(G.ptr(bs), G.ptr(cs), k, 4, 1, 0.5, seg, G.ptr(ws), G.ptr(keep), st)), [keep]
             yield f'nms {title}', make
+    elif args.workload == 'head_losses':
+        import math
+        from tools import demo_hot_path as D
+        images, classes, levels = 8, 37, len(D.LEVEL_SHAPES)
+        anchors = torch.cat(D.retina_level_anchors())
+        n = anchors.size(0)
+        g = torch.Generator().manual_seed(6)
+        live = torch.rand((images, n), generator=g) < 0.01     # the positives of bench_configs.bbox_loss are of this order
+        weights = live[:, :, None].float().expand(images, n, 4).contiguous().cuda()
+        boxes = anchors.cpu()[None] + torch.randn((images, n, 4), generator=g) * torch.tensor([2., 2., 1., 1.])
+        boxes[..., 2:] = boxes[..., 2:].clamp(1, 179)
+        boxes, deltas_t = boxes.contiguous().cuda(), (torch.randn((images, n, 4), generator=g) * 0.1).cuda()
+        labels = torch.where(live, torch.randint(0, classes, (images, n), generator=g), torch.tensor(classes)).cuda()
+        avg = live.sum().float().reshape(1).cuda()
+        cls = [(torch.randn((images, 9 * classes, h, w), generator=g) * 2 - 4).cuda() for h, w in D.LEVEL_SHAPES]
+        box = [(torch.randn((images, 9 * 4, h, w), generator=g) * 0.05).cuda() for h, w in D.LEVEL_SHAPES]
+        ptrs, i64s, f4 = ctypes.c_void_p * levels, ctypes.c_int64 * levels, ctypes.c_float * 4
+        ns, hws = i64s(*[9 * h * w for h, w in D.LEVEL_SHAPES]), i64s(*[h * w for h, w in D.LEVEL_SHAPES])
+        means, stds, max_ratio = f4(0, 0, 0, 0), f4(1, 1, 1, 1), abs(math.log(16 / 1000))
+
+        def entry(name, xs, last, call):
+            def make(lib):
+                grads = [torch.empty_like(x) for x in xs]
+                out = torch.empty(1, device='cuda')
+                ws = torch.empty(getattr(lib, f'sph2pob_{name}_workspace_bytes')(ns, hws, levels, images, last), dtype=torch.uint8, device='cuda')
+                xp, gp = ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in grads])
+                return (lambda: call(lib, xp, gp, G.ptr(out), G.ptr(ws))), [out] + grads
+            return f'head_losses {name}_sum fwd+grad {images} x {n}', make
+        yield entry('focal_loss', cls, classes, lambda lib, xp, gp, out, ws: lib.sph2pob_focal_loss_sum_f32(
+            xp, gp, ns, hws, levels, images, classes, G.ptr(labels), None, 0, 2.0, 0.25, 1.0, G.ptr(avg), out, ws, st))
+        yield entry('bbox_loss', box, 4, lambda lib, xp, gp, out, ws: lib.sph2pob_bbox_loss_sum_f32(
+            xp, gp, ns, hws, levels, images, 4, G.ptr(anchors), G.ptr(boxes), G.ptr(weights), 4, means, stds,
+            max_ratio, 1, 32.0, 3, 1e-6, 1.0, G.ptr(avg), out, ws, st))
+        yield entry('delta_loss', box, 4, lambda lib, xp, gp, out, ws: lib.sph2pob_delta_loss_sum_f32(
+            xp, gp, ns, hws, levels, images, 4, G.ptr(deltas_t), G.ptr(weights), 4, 0.0, 1.0, G.ptr(avg), out, ws, st))
     else:
         raise SystemExit('unknown workload ' + args.workload)
 
