@@ -33,6 +33,21 @@ SPH_DEV unsigned long long sph_lane_mask(bool cond) {
 #endif
 }
 SPH_DEV unsigned float_bits(float x) { return __builtin_bit_cast(unsigned, x); }
+// A constant that only a guarded (rare) block uses, formed INSIDE that block.  Left to the compiler, every such constant
+// that an instruction cannot take as a literal (both values of a select, a select on an SGPR mask) is hoisted into a VGPR
+// in front of the finishing loop, where every wave pays its v_mov although more than 99 % of the waves run one pass and
+// few enter the block at all.  The same value, hence the same bits; on the host it is the plain constant.
+template <unsigned BITS>
+SPH_DEV float rare_const_bits() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "i"(BITS));
+    return r;
+#else
+    return __builtin_bit_cast(float, BITS);
+#endif
+}
+#define SPH_RARE_CONST(x) rare_const_bits<__builtin_bit_cast(unsigned, (float)(x))>()
 SPH_DEV unsigned max3_u32(unsigned a, unsigned b, unsigned c) {
     const unsigned m = a > b ? a : b;
     return m > c ? m : c;   // one v_max3_u32
@@ -182,9 +197,10 @@ SPH_DEV void rot(float& c, float& s, float ca, float sa) {
 // the reference's  sign * |acos(clamp(cos a))|  expressed on (cos a, sin a): floor |a| and |pi - a| at kMinAng;
 // sin a == 0 takes the negative sign (criterion `< 0` false -> -1, sph2pob_efficient.py:211-226)
 SPH_DEV void angle_floor(float& c, float& s) {
-    if (fabsf(s) < kMinAng) {
-        s = s > 0.0f ? kMinAng : -kMinAng;
-        c = c < 0.0f ? -kCosMinAng : kCosMinAng;
+    if (fabsf(s) < kMinAng) {   // (always inside a guarded block: see SPH_RARE_CONST)
+        const float m = SPH_RARE_CONST(kMinAng), cm = SPH_RARE_CONST(kCosMinAng);
+        s = s > 0.0f ? m : -m;
+        c = c < 0.0f ? -cm : cm;
     }
 }
 
@@ -583,7 +599,7 @@ SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, Pl
                 // angles are on opposite sides of the +-pi cut — their difference is ~2 pi, no decision fires — exactly
                 // when both cosines are negative and the sines differ in sign (the floors keep |sin| >= 4.88e-4)
                 const bool straddle = (ca < 0.0f) & ((sa < 0.0f) != (sb < 0.0f));
-                dang = straddle ? 6.0f : fmaf(s * s, s * (1.0f / 6.0f), s);
+                dang = straddle ? SPH_RARE_CONST(6.0f) : fmaf(s * s, s * (1.0f / 6.0f), s);
 #endif
             }
             sim |= fabsf(dang) < e;
@@ -652,7 +668,7 @@ SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode
     unsigned long long nan_wave = 0ull;   // DIM 4, wave-uniform: the lanes that carry a NaN
     float carrier = 0.0f;                 // DIM 5
     auto jitter_shift = [&](bool similar) {
-        const float sh1 = similar ? e2 : 0.0f, sh2 = similar ? e : 0.0f;  // x - 0 == x exactly
+        const float sh1 = similar ? SPH_RARE_CONST(2 * kEpsS) : 0.0f, sh2 = similar ? SPH_RARE_CONST(kEpsS) : 0.0f;  // x - 0 == x exactly
 #pragma unroll
         for (int k = 0; k < DIM; k++) { x1[k] = x1[k] - sh1; x2[k] = x2[k] + sh2; }
         if (PRE && similar) { pre1 = colat_trig(x1[1], 1); if (PRE == 1) pre2 = colat_trig(x2[1], 2); }   // the shifted colatitudes
@@ -719,7 +735,7 @@ SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode
     rb = rb * fmaf(-base, rb, 2.0f);  // one Newton step: ~0.5 ulp quotient without the IEEE divide expansion
     const float iou = fminf(fmaxf(inter * rb, 0.0f), 1.0f);
     if (DIM == 5) return carrier != carrier ? __builtin_nanf("") : iou;
-    if (__builtin_expect(nan_wave != 0ull, 0)) return nan_lane ? __builtin_nanf("") : iou;
+    if (__builtin_expect(nan_wave != 0ull, 0)) return nan_lane ? SPH_RARE_CONST(__builtin_nanf("")) : iou;
     return iou;
 }
 

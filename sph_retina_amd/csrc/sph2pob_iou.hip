@@ -217,18 +217,48 @@ __global__ __launch_bounds__(kBlock, REF ? 4 : (DIM == 4 ? 7 : 5)) void iou_alig
 //     compares: SQ_INSTS_VALU 3.62 -> 3.49 M per launch, 7.21 -> 7.05 us per 1 M pairs.  Measured on the ISA and not kept: a
 //     "clean" bit from the cull (its range tests cost the cull more than the clamps they would skip), passes peeled out
 //     of the loop (no hoisted rare-block constants, but every common one re-materialised per use: -5 v_mov, twice the code).
+//   * wave prologue and slice glue of the BFoV launches (ISA of the <0, 4, true, 2> body; bit-identical results;
+//     profiles/r09a_prologue_glue.log): 7.16 -> 6.92 us per 1 M pairs.  (i) 32-bit byte offsets from the
+//     kernel-argument pointers (OFF32): per slice v_min_i32 + v_ashrrev_i32 + v_lshlrev_b64 + 2 v_lshl_add_u64 in front of
+//     the first load become one v_lshlrev_b32 (+ v_or for the second slice; the clamp of the tail lanes only in the one
+//     wave that holds the tail: clamping in every wave 7.08 us), each store loses its v_ashrrev_i32 + v_lshl_add_u64, the
+//     stack holds the result's byte offset instead of the pair index; (ii) the wave number through v_readfirstlane: chunk
+//     base, the `base >= n` test and the LDS base (formed once, was twice) are scalar; one zero register for both stores
+//     of the culled pairs; the priority is a template parameter chosen by the launcher (was s_and + s_bitcmp + s_cselect
+//     + branch, twice).  (i) WITHOUT the scalar wave number and the shared zero register is slower than the parent (7.23
+//     us; 7.28 with hoisted constants as well), so (i) and (ii) go together; (ii) alone was not built.  (iii) the constants
+//     that only guarded blocks use are formed inside those blocks (sph2pob_fast.hpp: SPH_RARE_CONST): 15 -> 8 v_mov_b32 in
+//     front of the pass loop (the four upper clamp bounds and 3.0e38 are operands of the common path's v_med3, which takes
+//     one SGPR and no literal: they stay).  It changes nothing at 1 M (6.92 vs 6.91 us without it) or 250 k (3.86 vs 3.87);
+//     at 8 M the build without it read 47.9 us against the parent's 47.2 and 47.4 with it, so it is kept.
+//     Measured and not kept: RBFoV on the 32-bit route: 10.09 -> 9.69 us at 1 M but 62.8 -> 63.4 at 8 M, where the 64-bit
+//     instantiation of the same build read 60.0; RBFoV keeps 64-bit offsets.
+//     The BFoV chunk kernel now has three instantiations per (variant, edge) instead of one (64-bit; 32-bit with and
+//     without the priority): +0.2 MB of library (7.4 -> 7.6 MB).
 template <int DIM, int SLICES>
 struct ChunkQueue {
     float f[2 * DIM][64 * SLICES];
-    int idx[64 * SLICES];
+    int idx[64 * SLICES];   // pair index (OFF32: the byte offset of the pair's result, 4 * index)
 };
 constexpr int kChunkSlices = 2;
-template <int VARIANT, int DIM, bool ARC, int SLICES, int WAVES = kBlock / 64>
+// OFF32: every load and store of the chunk kernel is addressed by an unsigned 32-bit byte offset from its kernel-argument
+// pointer (global_load / global_store v_off, s[base:base+1]: no 64-bit address arithmetic per lane), which needs the byte
+// offset one past the last box, n * 4 * dim, to fit in 32 bits.  Above that the launcher takes the 64-bit instantiation.
+constexpr bool chunk_offsets_fit_u32(int64_t n, int dim) { return n >= 0 && n * (4 * dim) < ((int64_t)1 << 32); }
+static_assert(chunk_offsets_fit_u32(((int64_t)1 << 28) - 1, 4) && !chunk_offsets_fit_u32((int64_t)1 << 28, 4), "BFoV: n * 16 < 2^32");
+static_assert(chunk_offsets_fit_u32(214748364, 5) && !chunk_offsets_fit_u32(214748365, 5), "RBFoV: n * 20 < 2^32");
+static_assert(chunk_offsets_fit_u32(0, 4) && chunk_offsets_fit_u32(0, 5) && !chunk_offsets_fit_u32(-1, 4), "empty batch fits, a negative size never");
+__device__ __forceinline__ const float* at_byte(const float* __restrict__ p, unsigned off) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(p) + off); }
+__device__ __forceinline__ float* at_byte(float* __restrict__ p, unsigned off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(p) + off); }
+// PRIO: the load + cull phase at wave priority 1 (the launcher's choice: see below)
+template <int VARIANT, int DIM, bool ARC, int SLICES, bool OFF32, bool PRIO, int WAVES = kBlock / 64>
 __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chunk_kernel(const float* __restrict__ b1, const float* __restrict__ b2,
                                                                       float* __restrict__ out, int n, int mode, int edge_arg) {
     __shared__ ChunkQueue<DIM, SLICES> queues[WAVES];
     const int edge = ARC ? (int)EDGE_ARC : (edge_arg & 0xff);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    // the wave's number in an SGPR: its chunk, the test below and its LDS base (formed once) are scalar
+    const int wave = OFF32 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     ChunkQueue<DIM, SLICES>& q = queues[wave];
     const int base = (blockIdx.x * WAVES + wave) * (64 * SLICES);
     if (base >= n) return;   // wave-uniform; the kernel has no barrier
@@ -247,26 +277,46 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
     // 1-2.5 % instead (2.6 M: +2.8 %), and RBFoV launches lose 2.5 % at 1 M: the launcher asks for it for BFoV launches of
     // up to two rounds (profiles/r03g_ab_prio*.log).  A priority that falls (or rises) with the wave's progress through
     // its pass, to keep the waves of a SIMD in step (or to retire them one by one): 7.70 / 7.55 against 7.31 / 7.18 us.
-    const bool cull_first = (edge_arg & 0x10000) != 0;
-    if (cull_first) __builtin_amdgcn_s_setprio(1);
+    if (PRIO) __builtin_amdgcn_s_setprio(1);
     // BFoV: lanes past the end of the batch load the last pair again (never stored, never stacked): no zero fill of the
     // sixteen registers, no branch around the loads (8.31 -> 8.24 us per 1 M pairs; RBFoV's twenty dword loads were faster
     // behind the branch: 10.5 vs 10.7 us)
     float x[SLICES][5], y[SLICES][5];
+    // OFF32: byte offset of lane's first result; slice s is at + 256 s, its BFoV boxes at 4 x that
+    const unsigned o4 = (unsigned)(base + lane) * 4u;
+    static_assert(!OFF32 || DIM == 4, "the 32-bit route is BFoV's (RBFoV: measured, not kept; see above)");
+    if (OFF32) {
+        auto load4 = [&](unsigned off, int s) {
+            const float4 u = *reinterpret_cast<const float4*>(at_byte(b1, off)), v = *reinterpret_cast<const float4*>(at_byte(b2, off));
+            x[s][0] = u.x; x[s][1] = u.y; x[s][2] = u.z; x[s][3] = u.w; x[s][4] = 0.0f;
+            y[s][0] = v.x; y[s][1] = v.y; y[s][2] = v.z; y[s][3] = v.w; y[s][4] = 0.0f;
+        };
+        if (base + 64 * SLICES <= n) {   // wave-uniform: a whole chunk needs no clamp (clamping always: 7.08 vs 6.92 us)
 #pragma unroll
-    for (int s = 0; s < SLICES; s++) {
-        const int i = base + s * 64 + lane;
-        if (DIM == 4) {
-            const int il = i < n ? i : n - 1;
-            load_box<DIM>(b1, il, x[s]);
-            load_box<DIM>(b2, il, y[s]);
+            for (int s = 0; s < SLICES; s++) load4(o4 * 4u + s * 1024u, s);
         } else {
+            const unsigned last = (unsigned)(n - 1) * 16u;
 #pragma unroll
-            for (int k = 0; k < 5; k++) { x[s][k] = 0.0f; y[s][k] = 0.0f; }
-            if (i < n) { load_box<DIM>(b1, i, x[s]); load_box<DIM>(b2, i, y[s]); }
+            for (int s = 0; s < SLICES; s++) { const unsigned o = o4 * 4u + s * 1024u; load4(o < last ? o : last, s); }
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < SLICES; s++) {
+            const int i = base + s * 64 + lane;
+            if (DIM == 4) {
+                const int il = i < n ? i : n - 1;
+                load_box<DIM>(b1, il, x[s]);
+                load_box<DIM>(b2, il, y[s]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 5; k++) { x[s][k] = 0.0f; y[s][k] = 0.0f; }
+                if (i < n) { load_box<DIM>(b1, i, x[s]); load_box<DIM>(b2, i, y[s]); }
+            }
         }
     }
     int count = 0;
+    float zero = 0.0f;   // ONE register for the stores of the culled pairs (left alone, a v_mov in front of each)
+    if (OFF32) asm volatile("" : "+v"(zero));
 #pragma unroll
     for (int s = 0; s < SLICES; s++) {
         const int i = base + s * 64 + lane;
@@ -279,7 +329,7 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
         const unsigned long long cm = __builtin_amdgcn_ballot_w64(cp.in_sizes) & __builtin_amdgcn_ballot_w64(cp.in_theta) &
                                       __builtin_amdgcn_ballot_w64(cp.apart);
 #endif
-        const bool inside = i < n, surv = inside & !culled;
+        const bool inside = OFF32 ? o4 + s * 256u < (unsigned)n * 4u : i < n, surv = inside & !culled;
 #if defined(SPH_ABL_NOCULL)
         const unsigned long long m = __builtin_amdgcn_ballot_w64(surv);
 #else
@@ -287,12 +337,15 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
         // compare whose mask crosses a branch, costs two more VALU instructions; see CullParts)
         const unsigned long long m = __builtin_amdgcn_ballot_w64(inside) & ~cm;
 #endif
-        if (inside & culled) out[i] = 0.0f;   // (non-temporal stores here and below: 8.42 vs 8.30 us at 1 M, 51.4 vs 48.1 at 8 M)
+        if (inside & culled) {   // (non-temporal stores here and below: 8.42 vs 8.30 us at 1 M, 51.4 vs 48.1 at 8 M)
+            if (OFF32) *at_byte(out, o4 + s * 256u) = zero;
+            else out[i] = 0.0f;
+        }
         if (surv) {
             const int slot = count + rank_below(m);
 #pragma unroll
             for (int k = 0; k < DIM; k++) { q.f[k][slot] = x[s][k]; q.f[DIM + k][slot] = y[s][k]; }
-            q.idx[slot] = i;
+            q.idx[slot] = OFF32 ? (int)(o4 + s * 256u) : i;
         }
         count += __popcll(m);
         if (s == 0) SPH_STAMP(1);
@@ -301,7 +354,7 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
     SPH_STAMP(3);
     SPH_STAMP_VALUE((unsigned long long)count);
     wave_lds_fence();
-    if (cull_first) __builtin_amdgcn_s_setprio(0);
+    if (PRIO) __builtin_amdgcn_s_setprio(0);
     for (int b = 0; b < count; b += 64) {
         const int slot = b + lane;
         if (slot < count) {
@@ -309,10 +362,12 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
 #pragma unroll
             for (int k = 0; k < 5; k++) { u1[k] = k < DIM ? q.f[k][slot] : 0.0f; u2[k] = k < DIM ? q.f[DIM + k][slot] : 0.0f; }
 #if defined(SPH_ABL_NOFINISH)
-            out[q.idx[slot]] = u1[0] + u2[1] + u1[2] + u2[3] > 1e30f ? 1.0f : 0.5f;   // ABLATION: no finishing arithmetic
+            const float r = u1[0] + u2[1] + u1[2] + u2[3] > 1e30f ? 1.0f : 0.5f;   // ABLATION: no finishing arithmetic
 #else
-            out[q.idx[slot]] = lean_finish<VARIANT, DIM>(u1, u2, mode, edge);
+            const float r = lean_finish<VARIANT, DIM>(u1, u2, mode, edge);
 #endif
+            if (OFF32) *at_byte(out, (unsigned)q.idx[slot]) = r;
+            else out[q.idx[slot]] = r;
         }
     }
     SPH_STAMP(5);
@@ -418,10 +473,20 @@ struct AlignedLaunch {
 #define SPH_PIPE(PF, ARC, REF) hipLaunchKernelGGL((iou_aligned_compact_kernel<VV, D, PF, ARC, REF>), dim3((unsigned)wgs), dim3(kBlock), 0, s, b1, b2, out, (int)n, mode, edge_k)
             if (!ref_finish && V < 2 && !g_persistent) {   // the default: one-round chunk kernel
                 const unsigned cw = (unsigned)((n + kBlock * kChunkSlices - 1) / (kBlock * kChunkSlices));
+                const int edge_k = edge | (angle << 8);
                 // cull phase at a higher wave priority while (nearly) the whole grid is resident at once: see the kernel
-                const int edge_k = (edge | (angle << 8)) | (D == 4 && (int64_t)cw <= kCUs * 8 * 2 && !g_no_prio ? 0x10000 : 0);
-                if (edge == SPH2POB_EDGE_ARC) hipLaunchKernelGGL((iou_aligned_chunk_kernel<VV, D, true, kChunkSlices>), dim3(cw), dim3(kBlock), 0, s, b1, b2, out, (int)n, mode, edge_k);
-                else hipLaunchKernelGGL((iou_aligned_chunk_kernel<VV, D, false, kChunkSlices>), dim3(cw), dim3(kBlock), 0, s, b1, b2, out, (int)n, mode, edge_k);
+                const bool prio = D == 4 && (int64_t)cw <= kCUs * 8 * 2 && !g_no_prio;
+                const bool off32 = D == 4 && chunk_offsets_fit_u32(n, D);   // (RBFoV stays on 64-bit offsets: see the kernel)
+#define SPH_CHUNK(ARC, O32, PRIO) hipLaunchKernelGGL((iou_aligned_chunk_kernel<VV, D, ARC, kChunkSlices, O32, PRIO>), dim3(cw), dim3(kBlock), 0, s, b1, b2, out, (int)n, mode, edge_k)
+#define SPH_CHUNK_ARC(O32, PRIO) do { if (edge == SPH2POB_EDGE_ARC) SPH_CHUNK(true, O32, PRIO); else SPH_CHUNK(false, O32, PRIO); } while (0)
+                // (a launch that is large enough for 64-bit offsets is far beyond two rounds: it never asks for the priority)
+                if constexpr (D == 4) {   // (OFF32 is instantiated for BFoV only: the kernel's static_assert)
+                    if (!off32) SPH_CHUNK_ARC(false, false);
+                    else if (prio) SPH_CHUNK_ARC(true, true);
+                    else SPH_CHUNK_ARC(true, false);
+                } else SPH_CHUNK_ARC(false, false);
+#undef SPH_CHUNK_ARC
+#undef SPH_CHUNK
             } else
             if (ref_finish) { if (wgs > kCUs * 4) wgs = kCUs * 4; SPH_PIPE(true, false, true); }   // reference-order finish: 4 waves per SIMD
             else if (edge == SPH2POB_EDGE_ARC) { if (g_prefetch) SPH_PIPE(true, true, false); else SPH_PIPE(false, true, false); }
