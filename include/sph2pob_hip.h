@@ -67,7 +67,7 @@ enum {
 
 /* Library identification: ABI version (bumped on any signature change or new entry point; sph2pob_abi_version() returns the
  * value the library was built with) and the code-object target. */
-#define SPH2POB_ABI_VERSION 4
+#define SPH2POB_ABI_VERSION 5
 int sph2pob_abi_version(void);
 const char* sph2pob_target_arch(void);
 const char* sph2pob_error_string(int code);
@@ -317,6 +317,25 @@ int sph2pob_get_bboxes_f32(const void* const* cls_scores, const void* const* bbo
                            const float* means_host, const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp,
                            int variant, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
                            int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream);
+/*
+ * The same post-processing with every NMS the reference's test configurations select: `variant_flags & 0xff` is STANDARD,
+ * EFFICIENT, UNBIASED (SphNMS('unbiased_iou'): the bounding-circle cull first, the fp64 intersection area on its survivors) or
+ * NAIVE (SphNMS('naive_iou'); with SPH2POB_FLAG_NAIVE_TAN the 'sph2tan' box formator), and class_agnostic = 1 runs one greedy
+ * NMS over all candidates of an image whatever their class (PlanarNMS's default): candidates in (score descending, candidate
+ * position ascending) order, one segment; labels / prior_inds are still each detection's own.  Tables, outputs, workspace
+ * (sph2pob_get_bboxes_workspace_bytes), launch count and everything else as above; sph2pob_get_bboxes_f32 is this entry
+ * restricted to STANDARD | EFFICIENT with class_agnostic = 0.
+ * Errors, in the order above with these additions: box_dim -> SPH2POB_ERR_DIM; a variant other than STANDARD | EFFICIENT |
+ * UNBIASED | NAIVE, SPH2POB_FLAG_REFERENCE_ORDER or an unknown flag bit, SPH2POB_FLAG_NAIVE_TAN with a variant other than NAIVE,
+ * class_agnostic outside {0, 1}, activation, coder_flags, max_ratio < 0 -> SPH2POB_ERR_OPTION; then the sizes, tables and
+ * pointers exactly as for sph2pob_get_bboxes_f32.
+ */
+int sph2pob_test_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors,
+                            const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                            int64_t num_classes, int box_dim, int activation, float score_thr, int64_t nms_pre,
+                            const float* means_host, const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp,
+                            int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
+                            int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream);
 
 /*
  * MaxIoUAssigner epilogue on a (k, n) overlaps matrix (rows = GT, columns = boxes), SURVEY §8f-1.

@@ -43,7 +43,7 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_nms_segmented_f32', 'sph2pob_nms_f32', 'sph2pob_assign_f32', 'sph2pob_coder_encode_f32',
               'sph2pob_coder_decode_f32', 'sph2pob_coder_decode_bwd_f32', 'sph2pob_obb_l1_fwd_f32', 'sph2pob_obb_l1_bwd_f32',
               'sph2pob_gauss_loss_fwd_f32', 'sph2pob_gauss_loss_bwd_f32', 'sph2pob_gauss_loss_fwd_sum_f32',
-              'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32', 'sph2pob_get_bboxes_f32', 'sph2pob_focal_loss_sum_f32',
+              'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32', 'sph2pob_get_bboxes_f32', 'sph2pob_test_bboxes_f32', 'sph2pob_focal_loss_sum_f32',
               'sph2pob_focal_loss_fwd_f32', 'sph2pob_focal_loss_bwd_f32', 'sph2pob_focal_loss_grad_scale_f32', 'sph2pob_bbox_loss_sum_f32',
               'sph2pob_delta_loss_sum_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp',
@@ -129,6 +129,9 @@ SIGNATURES = {
     # coder_flags, ctr_clamp, variant, iou_threshold, max_per_img, 4 outputs, workspace, stream
     'sph2pob_get_bboxes_f32': [ctypes.c_void_p] * 5 + [_int, _i64, _i64, _int, _int, ctypes.c_float, _i64, ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_float, _int, ctypes.c_float, _int, ctypes.c_float, _i64] + [ctypes.c_void_p] * 6,
+    # the same with (variant_flags, class_agnostic) in place of variant
+    'sph2pob_test_bboxes_f32': [ctypes.c_void_p] * 5 + [_int, _i64, _i64, _int, _int, ctypes.c_float, _i64, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_float, _int, ctypes.c_float, _int, _int, ctypes.c_float, _i64] + [ctypes.c_void_p] * 6,
     'sph2pob_focal_loss_workspace_bytes': [ctypes.c_void_p, ctypes.c_void_p, _int, _i64, _i64],
     # level tables (logits, grads, n, hw), num_levels, B, C, labels, weight, weight_mode, gamma, alpha, scale, avg_factor, out,
     # workspace, stream
@@ -167,7 +170,7 @@ _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_targe
              'sph2pob_focal_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_bbox_loss_workspace_bytes': ctypes.c_int64,
              'sph2pob_delta_loss_workspace_bytes': ctypes.c_int64}
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class Sph2PobLibraryError(RuntimeError):

@@ -1,17 +1,19 @@
 """Detection post-processing for a whole minibatch in one call, without a host synchronisation.
 
-`sph_get_bboxes` is what `SphRetinaHead._get_bboxes_single` -> `_bbox_post_process` compute per image
+`sph_test_bboxes` takes the reference's `test_cfg` dict as it stands in the configs — every `iou_calculator` they select:
+`'unbiased_iou'` (PANDORA), `'naive_iou'` (360-Indoor), `'planar'` with its `box_formator` (the base model; class-agnostic as
+`PlanarNMS` is) and the two closed-form Sph2Pob calculators — and runs `sph2pob_test_bboxes_f32`.  `sph_get_bboxes` is the
+earlier, keyword-only entry for the two closed-form calculators.  Both compute what `SphRetinaHead._get_bboxes_single` -> `_bbox_post_process` compute per image
 (sphdet/models/heads/sph_retina_head.py:101-216, :22-99): per level sigmoid, `filter_scores_and_topk(score_thr, nms_pre)`
 (mmdet/core/utils/misc.py:119-165) and `bbox_coder.decode`, then cat over the levels, `SphNMS` and `[:max_per_img]` — from the
-head's raw per-level outputs for B images to padded, fixed-shape detections as ONE C-ABI call (`sph2pob_get_bboxes_f32`: ten
-launches whatever B is).  Nothing is read back and nothing is sized on the host, so inference can be captured into a hipGraph;
+head's raw per-level outputs for B images to padded, fixed-shape detections as ONE C-ABI call (ten launches whatever B is).  Nothing is read back and nothing is sized on the host, so inference can be captured into a hipGraph;
 the counts stay on the device (`num_dets`).
 
 The reference's unstable parts are pinned: the per-level order is (score descending, candidate index ascending) — a stable
 descending sort — and NMS ties go by candidate position, as `sph_batched_nms` has them here.
 
 The per-image API (`multiclass_nms`, or `filter` + `bbox_coder.decode` + `sph_batched_nms` on each image and level) keeps serving
-what this entry does not: score factors, softmax heads, `with_nms=False`, planar NMS, the unbiased / naive calculators, the
+what these entries do not: score factors, softmax heads, `with_nms=False`, the `'xinyuan'` / `kent_iou` calculators, the
 reference arithmetic and more than 16 384 candidates per image.
 """
 import ctypes
@@ -28,7 +30,7 @@ _MAX_LEVELS = 8
 
 
 class DetBBoxes:
-    """Result of `sph_get_bboxes`, B images, all tensors on the inputs' device:
+    """Result of `sph_test_bboxes` / `sph_get_bboxes`, B images, all tensors on the inputs' device:
     dets (B, max_per_img, dim + 1) f32 = (box, score), rows from num_dets[b] on are zero; labels (B, max_per_img) int64, -1
     padded; prior_inds (B, max_per_img) int64, the detection's anchor as an index into cat(mlvl_anchors), -1 padded;
     num_dets (B,) int64."""
@@ -60,33 +62,30 @@ def _level(t, name, per_anchor, n, images):
     return G.as_f32_nograd(t), hw
 
 
-def sph_get_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, score_thr=0.05, nms_pre=1000, nms=None, max_per_img=100,
-                   iou_calculator='sph2pob_efficient', box_version=4, activation='sigmoid', score_factors=None, with_nms=True,
-                   wh_ratio_clip=16 / 1000, arithmetic=None):
-    """Detections of every image of a minibatch (see the module docstring and include/sph2pob_hip.h).
-
-    cls_scores: L tensors (B, A*C, H_l, W_l) — the head's NCHW, read in place — or (B, n_l, C); bbox_preds laid out alike with
-    `box_version` values per anchor; mlvl_anchors: L tensors (n_l, box_version) shared by the images.  `bbox_coder`: a
-    DeltaXYWHSphBBoxCoder / DeltaXYWHASphBBoxCoder (its means / stds / clip flags).  `nms`: dict(type='nms', iou_threshold=...).
-    `activation`: 'sigmoid' (the inputs are logits) or 'none' (they are probabilities).  Returns `DetBBoxes`."""
+def _refuse_head_options(who, activation, score_factors, with_nms, nms):
+    """The head options neither entry serves -> NotImplementedError; returns the nms dict without its 'type'."""
     if score_factors is not None:
-        raise NotImplementedError('sph_get_bboxes does not take score factors (FCOS-style heads): ' + _PER_IMAGE)
+        raise NotImplementedError(f'{who} does not take score factors (FCOS-style heads): ' + _PER_IMAGE)
     if activation == 'softmax':
-        raise NotImplementedError('sph_get_bboxes implements sigmoid heads only (use_sigmoid_cls=True), not softmax: ' + _PER_IMAGE)
+        raise NotImplementedError(f'{who} implements sigmoid heads only (use_sigmoid_cls=True), not softmax: ' + _PER_IMAGE)
     if activation not in ('sigmoid', 'none'):
         raise ValueError(f"activation must be 'sigmoid' or 'none', got {activation!r}")
     if not with_nms:
-        raise NotImplementedError('sph_get_bboxes always runs the NMS (with_nms=True): ' + _PER_IMAGE)
+        raise NotImplementedError(f'{who} always runs the NMS (with_nms=True): ' + _PER_IMAGE)
     nms_cfg = dict(nms or {})
     if nms_cfg.pop('type', 'nms') != 'nms':
-        raise NotImplementedError("sph_get_bboxes implements nms=dict(type='nms', ...) only: " + _PER_IMAGE)
-    if iou_calculator == 'planar' or type(iou_calculator).__name__ == 'PlanarNMS':
-        raise NotImplementedError('sph_get_bboxes runs the spherical NMS only, not PlanarNMS: ' + _PER_IMAGE)
-    variant = _variant_of(iou_calculator)
-    if variant not in ('efficient', 'standard'):
-        raise NotImplementedError(f'sph_get_bboxes serves the sph2pob_efficient / sph2pob_standard calculators, not {variant}: ' + _PER_IMAGE)
+        raise NotImplementedError(f"{who} implements nms=dict(type='nms', ...) only: " + _PER_IMAGE)
+    return nms_cfg
+
+
+def _refuse_reference_arithmetic(who, arithmetic):
     if (arithmetic or G.get_arithmetic()) == 'reference':
-        raise NotImplementedError("sph_get_bboxes runs the default arithmetic only, not arithmetic='reference': " + _PER_IMAGE)
+        raise NotImplementedError(f"{who} runs the default arithmetic only, not arithmetic='reference': " + _PER_IMAGE)
+
+
+def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder, score_thr, nms_pre, iou_threshold, max_per_img, box_version,
+         activation, wh_ratio_clip):
+    """The level marshalling and the call both entries share; `nms_args`: what `symbol` takes between ctr_clamp and iou_threshold."""
     nms_pre, max_per_img = int(nms_pre), int(max_per_img)
     if nms_pre <= 0:
         raise ValueError(f'nms_pre must be positive, got {nms_pre} (the reference slices with min(-1, n); that quirk is not reproduced)')
@@ -97,11 +96,11 @@ def sph_get_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, score_th
         raise ValueError(f'box_version must be 4 or 5 and match the bbox_coder, got {box_version} and {type(bbox_coder).__name__}')
     levels = len(mlvl_anchors)
     if not (1 <= levels <= _MAX_LEVELS) or len(cls_scores) != levels or len(bbox_preds) != levels:
-        raise ValueError(f'sph_get_bboxes takes 1 to {_MAX_LEVELS} levels with one cls_scores / bbox_preds / anchors tensor each')
+        raise ValueError(f'{who} takes 1 to {_MAX_LEVELS} levels with one cls_scores / bbox_preds / anchors tensor each')
     tensors = list(cls_scores) + list(bbox_preds) + list(mlvl_anchors)
     G.require_hip(*tensors)
     if len({t.device for t in tensors}) != 1:
-        raise RuntimeError('sph_get_bboxes: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
+        raise RuntimeError(f'{who}: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
     dev = tensors[0].device
     images = cls_scores[0].size(0)
     num_classes = None
@@ -125,7 +124,7 @@ def sph_get_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, score_th
     lib = _lib.lib()
     k_cap = sum(min(nms_pre, n * num_classes) for n in ns)
     if k_cap > lib.sph2pob_batched_nms_max_boxes():
-        raise NotImplementedError(f'sph_get_bboxes holds at most {lib.sph2pob_batched_nms_max_boxes()} candidates per image (the NMS key\'s '
+        raise NotImplementedError(f'{who} holds at most {lib.sph2pob_batched_nms_max_boxes()} candidates per image (the NMS key\'s '
                                   f'index field), nms_pre={nms_pre} over {levels} levels gives {k_cap}: ' + _PER_IMAGE)
     ptrs = ctypes.c_void_p * levels
     i64s = ctypes.c_int64 * levels
@@ -137,13 +136,86 @@ def sph_get_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, score_th
     if dev.type != 'cpu':
         need = lib.sph2pob_get_bboxes_workspace_bytes(level_n, levels, images, num_classes, dim, nms_pre)
         if need <= 0:
-            raise ValueError('sph_get_bboxes: these shapes are outside the limits of sph2pob_get_bboxes_f32 (include/sph2pob_hip.h)')
+            raise ValueError(f'{who}: these shapes are outside the limits of {symbol} (include/sph2pob_hip.h)')
         ws = G.scratch(dev, need)
     means = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.means])
     stds = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.stds])
     flags = (1 if bbox_coder.clip_border else 0) | (2 if bbox_coder.add_ctr_clamp else 0)
-    G.call('sph2pob_get_bboxes_f32', dev, ptrs(*cls_p), ptrs(*box_p), ptrs(*anc_p), level_n, i64s(*hws), levels, images, num_classes, dim,
+    G.call(symbol, dev, ptrs(*cls_p), ptrs(*box_p), ptrs(*anc_p), level_n, i64s(*hws), levels, images, num_classes, dim,
            int(activation == 'sigmoid'), float(score_thr), nms_pre, means, stds, float(abs(math.log(wh_ratio_clip))), flags,
-           float(bbox_coder.ctr_clamp), G.VARIANTS[variant], float(nms_cfg.get('iou_threshold', 0.5)), max_per_img, G.ptr(out.dets),
+           float(bbox_coder.ctr_clamp), *nms_args, float(iou_threshold), max_per_img, G.ptr(out.dets),
            G.ptr(out.labels), G.ptr(out.prior_inds), out.num_dets.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
     return out
+
+
+def sph_get_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, score_thr=0.05, nms_pre=1000, nms=None, max_per_img=100,
+                   iou_calculator='sph2pob_efficient', box_version=4, activation='sigmoid', score_factors=None, with_nms=True,
+                   wh_ratio_clip=16 / 1000, arithmetic=None):
+    """Detections of every image of a minibatch with the closed-form Sph2Pob calculators (see the module docstring and
+    include/sph2pob_hip.h); `sph_test_bboxes` serves the other calculators of the reference's configurations.
+
+    cls_scores: L tensors (B, A*C, H_l, W_l) — the head's NCHW, read in place — or (B, n_l, C); bbox_preds laid out alike with
+    `box_version` values per anchor; mlvl_anchors: L tensors (n_l, box_version) shared by the images.  `bbox_coder`: a
+    DeltaXYWHSphBBoxCoder / DeltaXYWHASphBBoxCoder (its means / stds / clip flags).  `nms`: dict(type='nms', iou_threshold=...).
+    `activation`: 'sigmoid' (the inputs are logits) or 'none' (they are probabilities).  Returns `DetBBoxes`."""
+    who = 'sph_get_bboxes'
+    nms_cfg = _refuse_head_options(who, activation, score_factors, with_nms, nms)
+    if iou_calculator == 'planar' or type(iou_calculator).__name__ == 'PlanarNMS':
+        raise NotImplementedError('sph_get_bboxes runs the spherical NMS only, not PlanarNMS: ' + _PER_IMAGE)
+    variant = _variant_of(iou_calculator)
+    if variant not in ('efficient', 'standard'):
+        raise NotImplementedError(f'sph_get_bboxes serves the sph2pob_efficient / sph2pob_standard calculators, not {variant}: ' + _PER_IMAGE)
+    _refuse_reference_arithmetic(who, arithmetic)
+    return _run(who, 'sph2pob_get_bboxes_f32', (G.VARIANTS[variant],), cls_scores, bbox_preds, mlvl_anchors, bbox_coder, score_thr, nms_pre,
+                nms_cfg.get('iou_threshold', 0.5), max_per_img, box_version, activation, wh_ratio_clip)
+
+
+_TEST_CFG_KEYS = ('score_thr', 'nms_pre', 'nms', 'max_per_img', 'iou_calculator', 'box_formator', 'min_bbox_size')
+_OTHER_KEYS = ('score_factors', 'with_nms', 'wh_ratio_clip', 'arithmetic')
+
+
+def _test_variant(iou_calculator, box_formator, nms_cfg):
+    """test_cfg.iou_calculator (+ box_formator, nms.class_agnostic) -> (kernel variant name, class_agnostic), as
+    `_bbox_post_process` picks PlanarNMS / SphNMS (sph_retina_head.py:89-92)."""
+    calc = iou_calculator
+    if isinstance(calc, dict):   # dict(type='SphOverlaps2D', backend=...): the base Faster-RCNN configuration's form
+        if calc.get('type', 'SphOverlaps2D') != 'SphOverlaps2D':
+            raise TypeError(f"iou_calculator dict must have type='SphOverlaps2D', got {calc.get('type')!r}")
+        calc = calc.get('backend', 'unbiased_iou')   # SphOverlaps2D's default backend
+    elif type(calc).__name__ == 'SphOverlaps2D':
+        calc = calc.backend
+    if calc in ('xinyuan', 'kent_iou'):
+        raise NotImplementedError(f'sph_test_bboxes has no batched NMS on the {calc} calculator: ' + _PER_IMAGE)
+    if calc == 'planar' or type(calc).__name__ == 'PlanarNMS':
+        formator = calc.box_formator if type(calc).__name__ == 'PlanarNMS' else box_formator
+        if formator not in ('sph2pix', 'sph2tan'):
+            raise ValueError(f"box_formator must be 'sph2pix' or 'sph2tan', got {formator!r}")
+        return ('naive' if formator == 'sph2pix' else 'naive_tan'), bool(nms_cfg.get('class_agnostic', True))   # PlanarNMS's default
+    return _variant_of(calc), False   # SphNMS pops class_agnostic and suppresses per class whatever it says
+
+
+def sph_test_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, test_cfg=None, box_version=4, activation='sigmoid', **overrides):
+    """Detections of every image of a minibatch under the reference's `test_cfg`, taken verbatim from its configurations:
+
+        test_cfg=dict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100,
+                      iou_calculator='unbiased_iou', box_formator='sph2pix')
+
+    `iou_calculator`: a calculator name of `SphNMS` ('unbiased_iou', 'naive_iou', 'sph2pob_efficient', 'sph2pob_standard'), per
+    class; 'planar': `PlanarNMS(box_formator)` — the naive IoU, across classes unless nms['class_agnostic'] is false;
+    dict(type='SphOverlaps2D', backend=...): the backend's name.  `min_bbox_size` is accepted and ignored, as in the
+    reference's Sph head.  Keyword overrides (the `test_cfg` keys, and `score_factors`, `with_nms`, `wh_ratio_clip`, `arithmetic`
+    as `sph_get_bboxes` has them) win over `test_cfg`.  Tensors as for `sph_get_bboxes`; returns `DetBBoxes`, whose labels and
+    prior_inds are each detection's own also when the NMS ran across classes.  One C-ABI call (`sph2pob_test_bboxes_f32`, on
+    CPU tensors its twin), ten launches, no host read."""
+    who = 'sph_test_bboxes'
+    cfg = dict(test_cfg or {})
+    unknown = [k for k in cfg if k not in _TEST_CFG_KEYS] + [k for k in overrides if k not in _TEST_CFG_KEYS + _OTHER_KEYS]
+    if unknown:
+        raise TypeError(f'{who}: unknown test_cfg key / keyword {unknown} (known: {list(_TEST_CFG_KEYS + _OTHER_KEYS)})')
+    cfg.update(overrides)
+    nms_cfg = _refuse_head_options(who, activation, cfg.get('score_factors'), cfg.get('with_nms', True), cfg.get('nms'))
+    variant, class_agnostic = _test_variant(cfg.get('iou_calculator', 'sph2pob_efficient'), cfg.get('box_formator', 'sph2pix'), nms_cfg)
+    _refuse_reference_arithmetic(who, cfg.get('arithmetic'))
+    return _run(who, 'sph2pob_test_bboxes_f32', (G.VARIANTS[variant], int(class_agnostic)), cls_scores, bbox_preds, mlvl_anchors, bbox_coder,
+                cfg.get('score_thr', 0.05), cfg.get('nms_pre', 1000), nms_cfg.get('iou_threshold', 0.5), cfg.get('max_per_img', 100), box_version,
+                activation, cfg.get('wh_ratio_clip', 16 / 1000))

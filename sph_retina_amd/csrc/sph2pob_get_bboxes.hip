@@ -1,4 +1,4 @@
-// libsph2pob_hip.so — detection post-processing for a minibatch (sph2pob_get_bboxes_f32, include/sph2pob_hip.h): per (image,
+// libsph2pob_hip.so — detection post-processing for a minibatch (sph2pob_test_bboxes_f32 / sph2pob_get_bboxes_f32, include/sph2pob_hip.h): per (image,
 // level) exact top-k of the class scores above a threshold, read from the head's own layout; gather + decode of the selected
 // candidates; then the batched NMS stage of sph2pob_nms.hip.  Replaces SphRetinaHead._get_bboxes_single / _bbox_post_process
 // (sphdet/models/heads/sph_retina_head.py:101-216, :22-99) and filter_scores_and_topk (mmdet/core/utils/misc.py:119-165) for
@@ -23,8 +23,8 @@
 // the NMS stage (sph2pob_nms.hip): boxes / scores / labels of B candidate blocks of stride k_cap, live counts on the device
 extern "C" __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(
     const float* boxes, const float* scores, const int64_t* labels, const int* prior, const int* counts, int64_t num_images, int k_cap,
-    int box_dim, int variant_flags, float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets, int64_t* labels_out,
-    int64_t* prior_out, int64_t* num_dets, void* stream);
+    int box_dim, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
+    int64_t* labels_out, int64_t* prior_out, int64_t* num_dets, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim);
 
 namespace {
@@ -294,20 +294,20 @@ extern "C" {
 int64_t sph2pob_get_bboxes_workspace_bytes(const int64_t* level_n, int num_levels, int64_t num_images, int64_t num_classes, int box_dim,
                                            int64_t nms_pre) {
     Levels L;
-    if (make_level_shapes(level_n, nullptr, num_levels, num_images, num_classes, box_dim, 0, SPH2POB_VARIANT_EFFICIENT, nms_pre, 0, 0.0f, 0,
+    if (make_level_shapes(level_n, nullptr, num_levels, num_images, num_classes, box_dim, 0, SPH2POB_VARIANT_EFFICIENT, 0, nms_pre, 0, 0.0f, 0,
                           kChunk, true, &L))
         return 0;
     return make_ws(nullptr, L, num_images, box_dim).bytes;
 }
 
-int sph2pob_get_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
-                           const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
-                           float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
-                           int coder_flags, float ctr_clamp, int variant, float iou_threshold, int64_t max_per_img, float* dets,
-                           int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
+int sph2pob_test_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                            const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                            float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                            int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img,
+                            float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
     Levels L;
     if (int rc = make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                             variant, nms_pre, max_per_img, max_ratio, coder_flags, kChunk, &L))
+                             variant_flags, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, kChunk, &L))
         return rc;
     if (!num_dets || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
     hipStream_t s = (hipStream_t)stream;
@@ -330,8 +330,20 @@ int sph2pob_get_bboxes_f32(const void* const* cls_scores, const void* const* bbo
         hipLaunchKernelGGL((cand_build_kernel<5>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
                            (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
     if (int rc = launch_status()) return rc;
-    return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant, iou_threshold, max_per_img,
-                                    w.nms, dets, labels, prior_inds, num_dets, s);
+    return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant_flags, class_agnostic, iou_threshold,
+                                    max_per_img, w.nms, dets, labels, prior_inds, num_dets, s);
+}
+
+// the closed-form calculators, per class: its own variant check (after the box_dim check, as documented), then the entry above
+int sph2pob_get_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                           const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                           float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                           int coder_flags, float ctr_clamp, int variant, float iou_threshold, int64_t max_per_img, float* dets,
+                           int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
+    if ((box_dim == 4 || box_dim == 5) && !closed_form_variant(variant)) return SPH2POB_ERR_OPTION;
+    return sph2pob_test_bboxes_f32(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                                   score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, 0, iou_threshold,
+                                   max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
 }
 
 }  // extern "C"

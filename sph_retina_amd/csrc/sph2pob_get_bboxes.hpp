@@ -1,5 +1,5 @@
-// Shared by the batched detection post-processing (sph2pob_get_bboxes_f32: sph2pob_get_bboxes.hip, its NMS stage in
-// sph2pob_nms.hip) and its CPU twin (sph2pob_host.hip): the level table, the order-preserving score keys, the score
+// Shared by the batched detection post-processing (sph2pob_test_bboxes_f32 and its restricted front-end
+// sph2pob_get_bboxes_f32: sph2pob_get_bboxes.hip, the NMS stage in sph2pob_nms.hip) and the CPU twins (sph2pob_host.hip): the level table, the order-preserving score keys, the score
 // activation and the argument checks, so that a CPU tensor gets the order and the checks a device tensor gets.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -92,15 +92,22 @@ inline int64_t k_cap_of(const int64_t* level_n, int num_levels, int64_t num_clas
     return k;
 }
 
-// Argument checks of sph2pob_get_bboxes_f32 and its twin, in the documented order, in two parts: the shapes (all the workspace
+// What sph2pob_get_bboxes_f32 accepts of the variants sph2pob_test_bboxes_f32 serves (its own check, in front of the shared ones)
+inline bool closed_form_variant(int variant) {
+    const int v = variant & 0xff;
+    return (v == SPH2POB_VARIANT_STANDARD || v == SPH2POB_VARIANT_EFFICIENT) && !(variant & ~(0xff | SPH2POB_FLAG_ROBUST_PARALLEL));
+}
+
+// Argument checks of sph2pob_test_bboxes_f32 and its twin, in the documented order, in two parts: the shapes (all the workspace
 // size needs; level_hw may be NULL = flattened layout) fill the level table, then the pointer tables are checked and entered.
 inline int make_level_shapes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes,
-                             int box_dim, int activation, int variant, int64_t nms_pre, int64_t max_per_img, float max_ratio,
-                             int coder_flags, int chunk_elems, bool have_tables, Levels* out) {
+                             int box_dim, int activation, int variant, int class_agnostic, int64_t nms_pre, int64_t max_per_img,
+                             float max_ratio, int coder_flags, int chunk_elems, bool have_tables, Levels* out) {
     if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
     const int v = variant & 0xff;
-    if ((v != SPH2POB_VARIANT_STANDARD && v != SPH2POB_VARIANT_EFFICIENT) || (variant & ~(0xff | SPH2POB_FLAG_ROBUST_PARALLEL)) ||
-        activation < 0 || activation > 1 || (coder_flags & ~3) || !(max_ratio >= 0.0f))
+    if ((v != SPH2POB_VARIANT_STANDARD && v != SPH2POB_VARIANT_EFFICIENT && v != SPH2POB_VARIANT_UNBIASED && v != SPH2POB_VARIANT_NAIVE) ||
+        (variant & ~(0xff | SPH2POB_FLAG_ROBUST_PARALLEL | SPH2POB_FLAG_NAIVE_TAN)) ||
+        ((variant & SPH2POB_FLAG_NAIVE_TAN) && v != SPH2POB_VARIANT_NAIVE) || class_agnostic < 0 || class_agnostic > 1 || activation < 0 || activation > 1 || (coder_flags & ~3) || !(max_ratio >= 0.0f))
         return SPH2POB_ERR_OPTION;
     if (num_levels < 1 || num_levels > kMaxLevels || num_images < 1 || num_images > 65535 || num_classes < 1 ||
         num_classes > ((int64_t)1 << kNmsClsBits) || nms_pre <= 0 || max_per_img < 0 || max_per_img > ((int64_t)1 << 30))
@@ -130,9 +137,10 @@ inline int make_level_shapes(const int64_t* level_n, const int64_t* level_hw, in
 }
 inline int make_levels(const void* const* cls, const void* const* bbox, const void* const* anchors, const int64_t* level_n,
                        const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
-                       int variant, int64_t nms_pre, int64_t max_per_img, float max_ratio, int coder_flags, int chunk_elems, Levels* out) {
-    if (int rc = make_level_shapes(level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation, variant, nms_pre, max_per_img,
-                                   max_ratio, coder_flags, chunk_elems, cls && bbox && anchors && level_hw, out))
+                       int variant, int class_agnostic, int64_t nms_pre, int64_t max_per_img, float max_ratio, int coder_flags,
+                       int chunk_elems, Levels* out) {
+    if (int rc = make_level_shapes(level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation, variant, class_agnostic, nms_pre,
+                                   max_per_img, max_ratio, coder_flags, chunk_elems, cls && bbox && anchors && level_hw, out))
         return rc;
     for (int l = 0; l < num_levels; l++) {
         if (!cls[l] || !bbox[l] || !anchors[l]) return SPH2POB_ERR_NULL;

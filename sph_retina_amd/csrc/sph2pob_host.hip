@@ -619,18 +619,19 @@ int sph2pob_anchor_targets_f32_cpu(const float* anchors, int64_t n, const float*
     return SPH2POB_OK;
 }
 
-// ---- detection post-processing for a minibatch: sph2pob_get_bboxes_f32 (the same keys, in the same order, sorted instead of
-// selected; the NMS twin above on each image's candidates; the workspace is not used) ----
-int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
-                               const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
-                               float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
-                               int coder_flags, float ctr_clamp, int variant, float iou_threshold, int64_t max_per_img, float* dets,
-                               int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
+// ---- detection post-processing for a minibatch: sph2pob_test_bboxes_f32 / sph2pob_get_bboxes_f32 (the same keys, in the same
+// order, sorted instead of selected; the NMS twin above on each image's candidates — one segment when class-agnostic; the
+// workspace is not used) ----
+int sph2pob_test_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                                const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                                float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                                int coder_flags, float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img,
+                                float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
     (void)workspace;
     namespace GB = sph2pob_gb;
     GB::Levels L;
     if (int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                                 variant, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &L))
+                                 variant, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &L))
         return rc;
     if (!num_dets || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
     const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
@@ -669,7 +670,7 @@ int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const*
         // the batched NMS on this image: (class | descending score | position) order, the sweeps, the kept by (score | position)
         const int64_t k = (int64_t)scores.size();
         order.resize(k);
-        for (int64_t j = 0; j < k; j++) order[j] = GB::nms_class_key(cls[j], scores[j], (int)j);
+        for (int64_t j = 0; j < k; j++) order[j] = GB::nms_class_key(class_agnostic ? 0 : cls[j], scores[j], (int)j);
         std::sort(order.begin(), order.end());
         sorted.resize(k * dim); cls_sorted.resize(k); keep.assign(k, 0);
         for (int64_t r = 0; r < k; r++) {
@@ -678,7 +679,7 @@ int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const*
             cls_sorted[r] = cls[j];
         }
         if (k > 0)
-            if (int rc = sph2pob_nms_segmented_f32_cpu(sorted.data(), cls_sorted.data(), k, box_dim, variant, iou_threshold, k, nullptr, keep.data(), nullptr))
+            if (int rc = sph2pob_nms_segmented_f32_cpu(sorted.data(), class_agnostic ? nullptr : cls_sorted.data(), k, box_dim, variant, iou_threshold, k, nullptr, keep.data(), nullptr))
                 return rc;
         keys.clear();
         for (int64_t r = 0; r < k; r++) {
@@ -698,6 +699,16 @@ int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const*
         }
     }
     return SPH2POB_OK;
+}
+int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                               const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                               float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                               int coder_flags, float ctr_clamp, int variant, float iou_threshold, int64_t max_per_img, float* dets,
+                               int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
+    if ((box_dim == 4 || box_dim == 5) && !sph2pob_gb::closed_form_variant(variant)) return SPH2POB_ERR_OPTION;
+    return sph2pob_test_bboxes_f32_cpu(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                                       score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, 0, iou_threshold,
+                                       max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
 }
 
 }  // extern "C"

@@ -48,9 +48,8 @@ __device__ __forceinline__ void wave_class_segment(const int64_t* __restrict__ c
 }
 
 template <int VARIANT, int DIM, bool FAST>
-__global__ __launch_bounds__(kBlock) void nms_mask_kernel(const float* __restrict__ boxes,
-                                                         const int64_t* __restrict__ cls, int64_t k, int words,
-                                                         float thr, unsigned long long* __restrict__ mask, int edge) {
+__device__ __forceinline__ void nms_mask_body(const float* __restrict__ boxes, const int64_t* __restrict__ cls, int64_t k, int words,
+                                              float thr, unsigned long long* __restrict__ mask, int edge) {
     // one wave per row i: only the words that hold later columns of row i's own class segment are evaluated.
     // Row layout: `words` u64 per row, word r of row i covers columns 64 * ((seg_start >> 6) + r) ...: indices are
     // relative to the row's class segment, so the matrix is k x (largest segment / 64 + 2) instead of k x k / 64.
@@ -83,6 +82,24 @@ __global__ __launch_bounds__(kBlock) void nms_mask_kernel(const float* __restric
         unsigned long long bits = __builtin_amdgcn_ballot_w64(hit);
         if (lane == 0) row[r] = bits;
     }
+}
+template <int VARIANT, int DIM, bool FAST>
+__global__ __launch_bounds__(kBlock) void nms_mask_kernel(const float* __restrict__ boxes,
+                                                         const int64_t* __restrict__ cls, int64_t k, int words,
+                                                         float thr, unsigned long long* __restrict__ mask, int edge) {
+    nms_mask_body<VARIANT, DIM, FAST>(boxes, cls, k, words, thr, mask, edge);
+}
+// The batched form (sph2pob_test_bboxes_f32) for the variants without a cull (the naive IoU; `edge` as above): blockIdx.y is the
+// image, laid out as nms_mask_compact_batch_kernel below lays it out.  cls == NULL: one segment per image (class-agnostic).
+// Whole waves leave early and the body has no workgroup barrier.
+template <int VARIANT, int DIM>
+__global__ __launch_bounds__(kBlock) void nms_mask_batch_kernel(const float* __restrict__ boxes, const int64_t* __restrict__ cls,
+                                                               const int* __restrict__ counts, int k_cap, float thr,
+                                                               unsigned long long* __restrict__ mask, int64_t mask_stride, int edge) {
+    const int b = blockIdx.y, k = counts[b];
+    if ((int)blockIdx.x * (kBlock / 64) >= k) return;
+    nms_mask_body<VARIANT, DIM, false>(boxes + (int64_t)b * k_cap * DIM, cls ? cls + (int64_t)b * k_cap : nullptr, k, (k + 63) / 64, thr,
+                                       mask + b * mask_stride, edge);
 }
 
 constexpr int kNmsMaxWords = 512;  // <= 32768 boxes per class segment (the sweep's removed bit-vector lives in LDS)
@@ -169,15 +186,17 @@ __global__ __launch_bounds__(kBlock) void nms_mask_compact_kernel(const float* _
                                                                  unsigned long long* __restrict__ mask) {
     nms_mask_compact_body<VARIANT, DIM>(boxes, cls, k, words, thr, mask);
 }
-// The batched form (sph2pob_get_bboxes_f32): blockIdx.y is the image, its candidates start at b * k_cap, its live count is read
+// The batched form (sph2pob_test_bboxes_f32): blockIdx.y is the image, its candidates start at b * k_cap, its live count is read
 // from the device and its matrix is laid out for that count (rows of (k + 63) / 64 words), as the single-image call lays it out.
+// cls == NULL: one segment per image (class-agnostic).
 template <int VARIANT, int DIM>
 __global__ __launch_bounds__(kBlock) void nms_mask_compact_batch_kernel(const float* __restrict__ boxes, const int64_t* __restrict__ cls,
                                                                        const int* __restrict__ counts, int k_cap, float thr,
                                                                        unsigned long long* __restrict__ mask, int64_t mask_stride) {
     const int b = blockIdx.y, k = counts[b];
     if ((int)blockIdx.x * (kBlock / 64) >= k) return;
-    nms_mask_compact_body<VARIANT, DIM>(boxes + (int64_t)b * k_cap * DIM, cls + (int64_t)b * k_cap, k, (k + 63) / 64, thr, mask + b * mask_stride);
+    nms_mask_compact_body<VARIANT, DIM>(boxes + (int64_t)b * k_cap * DIM, cls ? cls + (int64_t)b * k_cap : nullptr, k, (k + 63) / 64, thr,
+                                        mask + b * mask_stride);
 }
 
 // Greedy sweep, one WORKGROUP per class segment (classes are independent).  Every workgroup looks at 4 candidate rows;
@@ -311,7 +330,8 @@ __global__ __launch_bounds__(kSweepBlock) void nms_sweep_batch_kernel(const unsi
                                                                       int k_cap, unsigned char* __restrict__ keep) {
     const int b = blockIdx.y, k = counts[b];
     if ((int)blockIdx.x * kSweepCands >= k) return;
-    nms_sweep_body(mask + b * mask_stride, cls + (int64_t)b * k_cap, k, (k + 63) / 64, keep + (int64_t)b * k_cap);
+    // cls == NULL (class-agnostic): row 0 heads the image's one segment [0, k); the other workgroups find no head and leave
+    nms_sweep_body(mask + b * mask_stride, cls ? cls + (int64_t)b * k_cap : nullptr, k, (k + 63) / 64, keep + (int64_t)b * k_cap);
 }
 
 // ---- batched NMS without the host (sph_batched_nms, sphdet/bbox/nms/sph_nms.py:22-60, for K <= 16 384 candidates) ----
@@ -437,7 +457,8 @@ __global__ __launch_bounds__(BS) void nms_prepare_kernel(const float* __restrict
                                                                 int* __restrict__ status) {
     nms_prepare_body<T, DIM, IPW, BS>(boxes, scores, idxs, k, boxes_sorted, cls_sorted, order, skey_sorted, status);
 }
-// (batched: T, IPW and BS are chosen for k_cap, which bounds every image's count; rows from an image's count on are never read)
+// (batched: T, IPW and BS are chosen for k_cap, which bounds every image's count; rows from an image's count on are never read;
+// idxs == NULL sorts by (descending score | position) alone: class-agnostic)
 template <int T, int DIM, int IPW, int BS>
 __global__ __launch_bounds__(BS) void nms_prepare_batch_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                                       const int64_t* __restrict__ idxs, const int* __restrict__ counts, int k_cap,
@@ -447,12 +468,12 @@ __global__ __launch_bounds__(BS) void nms_prepare_batch_kernel(const float* __re
     const int b = blockIdx.y, k = counts[b];
     const int64_t o = (int64_t)b * k_cap;
     if ((int)blockIdx.x * IPW >= k) return;
-    nms_prepare_body<T, DIM, IPW, BS>(boxes + o * DIM, scores + o, idxs + o, k, boxes_sorted + o * DIM, cls_sorted + o, order + o, skey_sorted + o,
+    nms_prepare_body<T, DIM, IPW, BS>(boxes + o * DIM, scores + o, idxs ? idxs + o : nullptr, k, boxes_sorted + o * DIM, cls_sorted + o, order + o, skey_sorted + o,
                                       status + b);
 }
 // (dets come from the SORTED boxes and the score inside the key: everything the kernel reads is indexed by the sorted position,
 // nothing by a loaded value — one round trip)
-// BATCH (sph2pob_get_bboxes_f32): the padded outputs of one image — labels / prior indices looked up through the kept
+// BATCH (sph2pob_test_bboxes_f32): the padded outputs of one image — labels / prior indices looked up through the kept
 // candidate's position, -1 and zero rows from the count on up to max_rows, the count as int64 — instead of keep_out / status.
 struct SelectBatch { const int64_t* labels_in; const int* prior_in; int64_t* labels_out; int64_t* prior_out; int64_t* num_dets; int max_rows; };
 template <int T, int DIM, int IPW, int BS, bool BATCH>
@@ -698,15 +719,18 @@ int sph2pob_batched_nms_f32(const float* boxes, const float* scores, const int64
     return launch_status();
 }
 
-// The NMS stage of sph2pob_get_bboxes_f32 (sph2pob_get_bboxes.hip): the four kernels above with the image as grid dimension y.
-// Candidate blocks have the fixed stride k_cap, every kernel reads its image's live count from `counts`; closed-form variants
-// only (the caller has checked), so the suppression matrix always comes from the compacting kernel.
+// The NMS stage of sph2pob_test_bboxes_f32 (sph2pob_get_bboxes.hip): the four kernels above with the image as grid dimension y.
+// Candidate blocks have the fixed stride k_cap, every kernel reads its image's live count from `counts`.  The caller has checked
+// the variant: the closed-form ones and the unbiased one take the compacting mask kernel (cull first, finish on the survivors), the
+// naive one the plain kernel — what sph2pob_batched_nms_f32 launches for one image.  class_agnostic: the sort is by score alone and
+// mask and sweep see one segment per image (no class array), as sph2pob_batched_nms_f32 with idxs == NULL; labels_out are still
+// the candidates' own.
 __attribute__((visibility("hidden"))) int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim) {
     return num_images * batched_nms_ws(nullptr, k_cap, box_dim).bytes + (num_images * 4 + 255) / 256 * 256;   // + one status word per image
 }
 __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(const float* boxes, const float* scores, const int64_t* labels, const int* prior,
                                                                    const int* counts, int64_t num_images, int k_cap, int box_dim, int variant_flags,
-                                                                   float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
+                                                                   int class_agnostic, float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
                                                                    int64_t* labels_out, int64_t* prior_out, int64_t* num_dets, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int64_t k = k_cap;
@@ -726,8 +750,10 @@ __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(const float* 
     w.mask = (unsigned long long*)(p + off);
     const int64_t mask_stride = k * (int64_t)one.words;
     const int variant = variant_flags & 0xff, rows = (int)max_per_img;
+    const int64_t* sort_cls = class_agnostic ? nullptr : labels;          // what the order is built on
+    const int64_t* seg_cls = class_agnostic ? nullptr : (const int64_t*)w.cls;   // the segments of the sorted order
 #define SPH_PREP(T, D, I, Bs) hipLaunchKernelGGL((nms_prepare_batch_kernel<T, D, I, Bs>), dim3((unsigned)((k + I - 1) / I), B), dim3(Bs), 0, s, boxes, scores, \
-                                                 labels, counts, k_cap, w.boxes, w.cls, w.order, w.skey, status)
+                                                 sort_cls, counts, k_cap, w.boxes, w.cls, w.order, w.skey, status)
 #define SPH_SEL(T, D, I, Bs) hipLaunchKernelGGL((nms_select_batch_kernel<T, D, I, Bs>), dim3((unsigned)((k + I - 1) / I), B), dim3(Bs), 0, s, \
                                                 (const float*)w.boxes, (const unsigned char*)w.keep, (const unsigned long long*)w.skey, counts, k_cap, rows, \
                                                 labels, prior, dets, labels_out, prior_out, num_dets)
@@ -737,14 +763,19 @@ __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(const float* 
     int rc = launch_status();
     if (rc) return rc;
     const dim3 mgrid((unsigned)((k + kBlock / 64 - 1) / (kBlock / 64)), B);
-#define SPH_MASK(V, D) hipLaunchKernelGGL((nms_mask_compact_batch_kernel<V, D>), mgrid, dim3(kBlock), 0, s, (const float*)w.boxes, (const int64_t*)w.cls, \
+#define SPH_MASK(V, D) hipLaunchKernelGGL((nms_mask_compact_batch_kernel<V, D>), mgrid, dim3(kBlock), 0, s, (const float*)w.boxes, seg_cls, \
                                           counts, k_cap, iou_threshold, w.mask, mask_stride)
+#define SPH_MASK_PLAIN(V, D) hipLaunchKernelGGL((nms_mask_batch_kernel<V, D>), mgrid, dim3(kBlock), 0, s, (const float*)w.boxes, seg_cls, counts, k_cap, \
+                                                iou_threshold, w.mask, mask_stride, \
+                                                (variant_flags & SPH2POB_FLAG_NAIVE_TAN) ? (int)EDGE_TANGENT : (int)EDGE_ARC)
     if (variant == SPH2POB_VARIANT_EFFICIENT) { if (box_dim == 4) SPH_MASK(1, 4); else SPH_MASK(1, 5); }
+    else if (variant == SPH2POB_VARIANT_UNBIASED) { if (box_dim == 4) SPH_MASK(5, 4); else SPH_MASK(5, 5); }
+    else if (variant == SPH2POB_VARIANT_NAIVE) { if (box_dim == 4) SPH_MASK_PLAIN(6, 4); else SPH_MASK_PLAIN(6, 5); }
     else { if (box_dim == 4) SPH_MASK(0, 4); else SPH_MASK(0, 5); }
     rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(nms_sweep_batch_kernel, dim3((unsigned)((k + kSweepCands - 1) / kSweepCands), B), dim3(kSweepBlock), 0, s,
-                       (const unsigned long long*)w.mask, mask_stride, (const int64_t*)w.cls, counts, k_cap, w.keep);
+                       (const unsigned long long*)w.mask, mask_stride, seg_cls, counts, k_cap, w.keep);
     rc = launch_status();
     if (rc) return rc;
     if (box_dim == 4) SPH_BY_SIZE(SPH_SEL, 4); else SPH_BY_SIZE(SPH_SEL, 5);
@@ -752,6 +783,7 @@ __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(const float* 
 #undef SPH_SEL
 #undef SPH_BY_SIZE
 #undef SPH_MASK
+#undef SPH_MASK_PLAIN
     return launch_status();
 }
 

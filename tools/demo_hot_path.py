@@ -185,14 +185,23 @@ def head_outputs(images=8, num_classes=37, dim=4, seed=0, device='cuda', sparse=
     return cls, box
 
 
-def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1):
+PANDORA_TEST_CFG = dict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100,
+                        iou_calculator='unbiased_iou', box_formator='sph2pix')   # sph_retinanet_r50_fpn_120e_pandora.py
+
+
+def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None):
     """The inference half of `run()` for a minibatch (SphRetinaHead.get_bboxes over the images): the head's per-level NCHW scores
-    and deltas -> sph_get_bboxes (per-level top-k, decode, NMS, max_per_img) -> padded detections, no synchronisation."""
+    and deltas -> sph_get_bboxes (per-level top-k, decode, NMS, max_per_img) -> padded detections, no synchronisation.  With a
+    `test_cfg` (the reference's dict, e.g. PANDORA_TEST_CFG) the step is sph_test_bboxes under that configuration."""
     anchors = retina_level_anchors()
     cls, box = head_outputs(images, num_classes, seed=seed)
     coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
+    if test_cfg is not None:
+        nms_calculator = test_cfg.get('iou_calculator', nms_calculator)
 
     def step():
+        if test_cfg is not None:
+            return S.sph_test_bboxes(cls, box, anchors, bbox_coder=coder, test_cfg=test_cfg, box_version=4, activation='none')
         return S.sph_get_bboxes(cls, box, anchors, bbox_coder=coder, score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5),
                                 max_per_img=100, iou_calculator=nms_calculator, box_version=4, activation='none')
     step()
@@ -213,3 +222,4 @@ if __name__ == '__main__':
         print(json.dumps(run(backend=backend, nms_calculator=nms, reps=5)[0]), flush=True)
     print(json.dumps(run_batch(reps=5)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5)[0]), flush=True)
+    print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG)[0]), flush=True)
