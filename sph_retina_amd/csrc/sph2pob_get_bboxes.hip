@@ -18,14 +18,7 @@
 
 #include "../../include/sph2pob_hip.h"
 #include "sph2pob_coder.hpp"
-#include "sph2pob_get_bboxes.hpp"
-
-// the NMS stage (sph2pob_nms.hip): boxes / scores / labels of B candidate blocks of stride k_cap, live counts on the device
-extern "C" __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(
-    const float* boxes, const float* scores, const int64_t* labels, const int* prior, const int* counts, int64_t num_images, int k_cap,
-    int box_dim, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
-    int64_t* labels_out, int64_t* prior_out, int64_t* num_dets, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim);
+#include "sph2pob_get_bboxes.hpp"   // (declares the NMS stage, sph2pob_nms_batch_launch)
 
 namespace {
 

@@ -1,12 +1,21 @@
 // Shared by the batched detection post-processing (sph2pob_test_bboxes_f32 and its restricted front-end
 // sph2pob_get_bboxes_f32: sph2pob_get_bboxes.hip, the NMS stage in sph2pob_nms.hip) and the CPU twins (sph2pob_host.hip): the level table, the order-preserving score keys, the score
-// activation and the argument checks, so that a CPU tensor gets the order and the checks a device tensor gets.
+// activation, the argument checks (the NMS entries' option check among them) and the declarations of the NMS stage, so that a
+// CPU tensor gets the order and the checks a device tensor gets.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/sph2pob_hip.h"
+
+// The NMS stage of sph2pob_test_bboxes_f32, defined in sph2pob_nms.hip and called from sph2pob_get_bboxes.hip (inside the library
+// only): boxes / scores / labels / prior indices of B candidate blocks of stride k_cap, live counts on the device.
+extern "C" __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(
+    const float* boxes, const float* scores, const int64_t* labels, const int* prior, const int* counts, int64_t num_images, int k_cap,
+    int box_dim, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
+    int64_t* labels_out, int64_t* prior_out, int64_t* num_dets, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim);
 
 namespace sph2pob_gb {
 
@@ -90,6 +99,20 @@ inline int64_t k_cap_of(const int64_t* level_n, int num_levels, int64_t num_clas
         k += c < nms_pre ? c : nms_pre;
     }
     return k;
+}
+
+// Option check of the NMS entries (sph2pob_nms_segmented_f32, sph2pob_nms_f32, sph2pob_batched_nms_f32) and of the host twin.  Not
+// check_common(): a BFoV-only variant with box_dim 5 is an OPTION error here, not a DIM error.
+inline int nms_check_options(int box_dim, int variant_flags) {
+    const int variant = variant_flags & 0xff;
+    // SPH2POB_FLAG_ROBUST_PARALLEL is accepted and has no effect here (a near-parallel pair is far above any threshold)
+    if (variant_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER | SPH2POB_FLAG_ROBUST_PARALLEL | SPH2POB_FLAG_NAIVE_TAN)) return SPH2POB_ERR_OPTION;
+    if ((variant_flags & SPH2POB_FLAG_NAIVE_TAN) && variant != SPH2POB_VARIANT_NAIVE) return SPH2POB_ERR_OPTION;
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    if (variant != SPH2POB_VARIANT_STANDARD && variant != SPH2POB_VARIANT_EFFICIENT && variant != SPH2POB_VARIANT_UNBIASED &&
+        variant != SPH2POB_VARIANT_NAIVE)
+        return SPH2POB_ERR_OPTION;
+    return SPH2POB_OK;
 }
 
 // What sph2pob_get_bboxes_f32 accepts of the variants sph2pob_test_bboxes_f32 serves (its own check, in front of the shared ones)

@@ -480,13 +480,7 @@ int sph2pob_transform_bwd_general_f32_cpu(const float* b1, const float* b2, cons
 int sph2pob_nms_segmented_f32_cpu(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim, int variant_flags,
                                   float iou_threshold, int64_t max_segment, void* workspace, unsigned char* keep, void*) {
     (void)max_segment; (void)workspace;   // no suppression matrix on the host: no per-class limit either
-    const int variant = variant_flags & 0xff;
-    if (variant_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER | SPH2POB_FLAG_ROBUST_PARALLEL | SPH2POB_FLAG_NAIVE_TAN)) return SPH2POB_ERR_OPTION;
-    if ((variant_flags & SPH2POB_FLAG_NAIVE_TAN) && variant != SPH2POB_VARIANT_NAIVE) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (variant != SPH2POB_VARIANT_STANDARD && variant != SPH2POB_VARIANT_EFFICIENT && variant != SPH2POB_VARIANT_UNBIASED &&
-        variant != SPH2POB_VARIANT_NAIVE)
-        return SPH2POB_ERR_OPTION;
+    if (int rc = sph2pob_gb::nms_check_options(box_dim, variant_flags)) return rc;
     if (k < 0) return SPH2POB_ERR_SIZE;
     if (k == 0) return SPH2POB_OK;
     if (!boxes_sorted || !keep) return SPH2POB_ERR_NULL;

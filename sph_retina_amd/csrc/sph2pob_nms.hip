@@ -10,10 +10,11 @@ namespace {
 // ---- NMS (replaces the python greedy loop of sph_nms_op, sphdet/bbox/nms/sph_nms.py:62-74) ----
 // Boxes arrive sorted by (class, descending score).  Kernel 1: one wave per (row i, 64-column word w) evaluates
 // IoU(box_i [role bboxes1], box_j [role bboxes2]) > thr for the 64 columns j = 64w + lane (j > i, same class)
-// and emits the 64-bit suppression word with one ballot — no LDS, no atomics.  Kernel 2: a single wave sweeps
-// the rows in order; the greedy dependency inside a 64-row block is resolved on the 64x64 diagonal block held
-// one row per lane (readlane, scalar bit ops), then the kept rows of the block are OR-ed into the running
-// "removed" bit-vector (LDS) with lanes striding over the words, so global loads are never on the serial chain.
+// and emits the 64-bit suppression word with one ballot — no LDS, no atomics.  Kernel 2, the sweep: one WORKGROUP per
+// class segment walks the segment's 64-row blocks in order; wave 0 resolves the greedy dependency inside a block on the
+// 64x64 diagonal block held one row per lane (readlane, scalar bit ops) while the other waves OR the kept rows of the
+// block before into the segment's "removed" bit-vector (LDS), one barrier per block (see nms_sweep_body).
+//
 // A row's class segment [begin, end) in the class-sorted order, found by the whole wave: 64 probes per round, both ends in
 // the same rounds — three dependent round trips for 5 000 rows where a per-lane binary search made 2 x 13 (the NMS kernels
 // of a 5 000-box call spent most of their ~12 us in those searches).  All lanes of the wave pass the same i.
@@ -583,78 +584,124 @@ __global__ __launch_bounds__(BS) void nms_select_batch_kernel(const float* __res
                                            nullptr, sb);
 }
 
+// ---- host side: the launch glue of the three entries (sorted input, one image without the host, the batched stage) ----
 
-}  // namespace
-
-extern "C" {
-
-
-int sph2pob_nms_max_boxes(void) { return kNmsMaxWords * 64 - 64; }  // per class segment (unaligned: L/64 + 2 words)
-
-static int64_t nms_row_words(int64_t k, int64_t max_segment) {
+int64_t nms_row_words(int64_t k, int64_t max_segment) {
     int64_t full = (k + 63) / 64, seg = (max_segment >> 6) + 2;  // an unaligned segment of L boxes spans <= L/64 + 2 words
     return seg < full ? seg : full;
 }
-int64_t sph2pob_nms_workspace_bytes(int64_t k) { return k * nms_row_words(k, k) * 8; }
-int64_t sph2pob_nms_segmented_workspace_bytes(int64_t k, int64_t max_segment) {
-    return k * nms_row_words(k, max_segment < 1 ? 1 : max_segment) * 8;
+int nms_edge(int variant_flags) { return (variant_flags & SPH2POB_FLAG_NAIVE_TAN) ? (int)EDGE_TANGENT : (int)EDGE_ARC; }
+
+// The size classes of the rank sort (nms_prepare_* and nms_select_*, single image and batched: the same class for the same k).
+// T keys per lane x BS threads cover the candidates, IPW boxes per workgroup, chosen so that the grid is at most 256
+// workgroups: with ~150 VGPRs per lane a CU holds ONE of these workgroups at a time, and 313 of them (16 boxes each at
+// K = 5 000) ran in two rounds — 12 us per launch where 6 144 candidates or fewer now take one round.
+// by_sort_size calls f(SortSize<T, DIM, IPW, BS>{}) for the class of k: the template arguments of the four kernels, and their grid.
+template <int T_, int D_, int IPW_, int BS_> struct SortSize {
+    static constexpr int T = T_, D = D_, IPW = IPW_, BS = BS_;
+    static dim3 grid(int64_t k, unsigned images = 1) { return dim3((unsigned)((k + IPW - 1) / IPW), images); }
+};
+template <int D, class F>
+void by_sort_size_of(int64_t k, F&& f) {
+    if (k <= 2048) f(SortSize<4, D, 16, 512>{});
+    else if (k <= 4096) f(SortSize<8, D, 16, 512>{});
+    else if (k <= 6144) f(SortSize<12, D, 24, 512>{});
+    else if (k <= 8192) f(SortSize<16, D, 32, 512>{});
+    else if (k <= 12288) f(SortSize<12, D, 48, 1024>{});
+    else f(SortSize<16, D, 64, 1024>{});
+}
+template <class F>
+void by_sort_size(int64_t k, int box_dim, F&& f) {
+    if (box_dim == 4) by_sort_size_of<4>(k, f); else by_sort_size_of<5>(k, f);
 }
 
-static int nms_check_options(int box_dim, int variant_flags) {
-    const int variant = variant_flags & 0xff;
-    // SPH2POB_FLAG_ROBUST_PARALLEL is accepted and has no effect here (a near-parallel pair is far above any threshold)
-    if (variant_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER | SPH2POB_FLAG_ROBUST_PARALLEL | SPH2POB_FLAG_NAIVE_TAN)) return SPH2POB_ERR_OPTION;
-    if ((variant_flags & SPH2POB_FLAG_NAIVE_TAN) && variant != SPH2POB_VARIANT_NAIVE) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (variant != SPH2POB_VARIANT_STANDARD && variant != SPH2POB_VARIANT_EFFICIENT && variant != SPH2POB_VARIANT_UNBIASED &&
-        variant != SPH2POB_VARIANT_NAIVE)
-        return SPH2POB_ERR_OPTION;
-    return SPH2POB_OK;
-}
-// mask + sweep on boxes sorted by (class, -score): the two launches every NMS entry point shares
-static int nms_mask_and_sweep(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim, int variant_flags,
-                              float iou_threshold, int words, unsigned long long* mask, unsigned char* keep, hipStream_t s) {
-    const int variant = variant_flags & 0xff;
-    const bool fast = !(variant_flags & SPH2POB_FLAG_REFERENCE_ORDER);
-    const int wpb = kBlock / 64;
-    dim3 grid((unsigned)((k + wpb - 1) / wpb));
-#define SPH_NMS_LAUNCH(V, D, F) \
-    hipLaunchKernelGGL((nms_mask_kernel<V, D, F>), grid, dim3(kBlock), 0, s, boxes_sorted, cls_sorted, k, words, iou_threshold, mask, \
-                       (variant_flags & SPH2POB_FLAG_NAIVE_TAN) ? (int)EDGE_TANGENT : (int)EDGE_ARC)
-#define SPH_NMS_COMPACT(V, D) \
-    hipLaunchKernelGGL((nms_mask_compact_kernel<V, D>), grid, dim3(kBlock), 0, s, boxes_sorted, cls_sorted, k, words, iou_threshold, mask)
-    const bool compact = fast && !g_no_compact && k < ((int64_t)1 << 31) - 64 &&
-                         (variant == SPH2POB_VARIANT_EFFICIENT || variant == SPH2POB_VARIANT_STANDARD || variant == SPH2POB_VARIANT_UNBIASED);
-    if (compact) {
-        if (variant == SPH2POB_VARIANT_UNBIASED) { if (box_dim == 4) SPH_NMS_COMPACT(5, 4); else SPH_NMS_COMPACT(5, 5); }
-        else if (variant == SPH2POB_VARIANT_EFFICIENT) { if (box_dim == 4) SPH_NMS_COMPACT(1, 4); else SPH_NMS_COMPACT(1, 5); }
-        else { if (box_dim == 4) SPH_NMS_COMPACT(0, 4); else SPH_NMS_COMPACT(0, 5); }
-    } else if (variant == SPH2POB_VARIANT_EFFICIENT) {
-        if (box_dim == 4) { if (fast) SPH_NMS_LAUNCH(1, 4, true); else SPH_NMS_LAUNCH(1, 4, false); }
-        else { if (fast) SPH_NMS_LAUNCH(1, 5, true); else SPH_NMS_LAUNCH(1, 5, false); }
-    } else if (variant == SPH2POB_VARIANT_UNBIASED) {  // sph_nms.py:11-12
-        if (box_dim == 4) { if (fast) SPH_NMS_LAUNCH(5, 4, true); else SPH_NMS_LAUNCH(5, 4, false); }
-        else { if (fast) SPH_NMS_LAUNCH(5, 5, true); else SPH_NMS_LAUNCH(5, 5, false); }
-    } else if (variant == SPH2POB_VARIANT_NAIVE) {     // sph_nms.py:13-14
-        if (box_dim == 4) SPH_NMS_LAUNCH(6, 4, false); else SPH_NMS_LAUNCH(6, 5, false);
-    } else {
-        if (box_dim == 4) { if (fast) SPH_NMS_LAUNCH(0, 4, true); else SPH_NMS_LAUNCH(0, 4, false); }
-        else { if (fast) SPH_NMS_LAUNCH(0, 5, true); else SPH_NMS_LAUNCH(0, 5, false); }
+// The mask launch, through dispatch().  The closed-form variants and the unbiased one have a compacting kernel (cull first, finish
+// on the survivors), the naive one only the plain kernel; the BFoV-only variants 2 - 4 have none (the option check refuses them).
+constexpr bool has_compact_mask(int v) { return v == VARIANT_STANDARD || v == VARIANT_EFFICIENT || v == VARIANT_UNBIASED; }
+struct MaskLaunch {   // one image; boxes sorted by (class, -score)
+    const float* boxes; const int64_t* cls; int64_t k; int words; float thr; unsigned long long* mask; int edge; hipStream_t s; bool fast = true;
+    template <int V, int D, bool FAST> void plain(dim3 grid) {
+        hipLaunchKernelGGL((nms_mask_kernel<V, D, FAST>), grid, dim3(kBlock), 0, s, boxes, cls, k, words, thr, mask, edge);
     }
-#undef SPH_NMS_LAUNCH
-#undef SPH_NMS_COMPACT
-    int rc = launch_status();
-    if (rc) return rc;
+    template <int V, int D> int run() {
+        if constexpr (V >= 2 && V <= 4) return SPH2POB_ERR_OPTION;
+        else {
+            const dim3 grid((unsigned)((k + kBlock / 64 - 1) / (kBlock / 64)));
+            if constexpr (has_compact_mask(V)) {
+                if (fast && !g_no_compact && k < ((int64_t)1 << 31) - 64)
+                    hipLaunchKernelGGL((nms_mask_compact_kernel<V, D>), grid, dim3(kBlock), 0, s, boxes, cls, k, words, thr, mask);
+                else if (fast) plain<V, D, true>(grid);
+                else plain<V, D, false>(grid);
+            } else plain<V, D, false>(grid);   // sph_nms.py:13-14: no closed form, no reference order
+            return launch_status();
+        }
+    }
+};
+struct MaskBatchLaunch {   // the image is grid dimension y; SPH2POB_NO_COMPACT is not consulted, make_level_shapes has refused the reference order
+    const float* boxes; const int64_t* cls; const int* counts; int k_cap; unsigned images; float thr; unsigned long long* mask;
+    int64_t mask_stride; int edge; hipStream_t s; bool fast = true;
+    template <int V, int D> int run() {
+        if constexpr (V >= 2 && V <= 4) return SPH2POB_ERR_OPTION;
+        else {
+            const dim3 grid((unsigned)((k_cap + kBlock / 64 - 1) / (kBlock / 64)), images);
+            if constexpr (has_compact_mask(V))
+                hipLaunchKernelGGL((nms_mask_compact_batch_kernel<V, D>), grid, dim3(kBlock), 0, s, boxes, cls, counts, k_cap, thr, mask, mask_stride);
+            else
+                hipLaunchKernelGGL((nms_mask_batch_kernel<V, D>), grid, dim3(kBlock), 0, s, boxes, cls, counts, k_cap, thr, mask, mask_stride, edge);
+            return launch_status();
+        }
+    }
+};
+
+// mask + sweep on boxes sorted by (class, -score): the two launches every single-image entry shares
+int nms_mask_and_sweep(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim, int variant_flags,
+                       float iou_threshold, int words, unsigned long long* mask, unsigned char* keep, hipStream_t s) {
+    if (int rc = dispatch(variant_flags, box_dim, MaskLaunch{boxes_sorted, cls_sorted, k, words, iou_threshold, mask, nms_edge(variant_flags), s}))
+        return rc;
     hipLaunchKernelGGL(nms_sweep_kernel, dim3((unsigned)((k + kSweepCands - 1) / kSweepCands)), dim3(kSweepBlock), 0, s, mask, cls_sorted, k,
                        words, keep);
     return launch_status();
 }
 
+// The workspace of the host-free forms, and its size (`bytes` is the extent laid out: the size entries return it).
+//   images == 0  one image (sph2pob_batched_nms_f32):  sorted boxes | classes | permutation | score keys | keep flags | mask matrix
+//   images  > 0  the batched stage: the same regions images-fold, image b starting b * k elements into each (b * mask_stride words
+//                into the mask), and one status word per image in front of the mask
+// Every region is 256-byte aligned.
+struct NmsWs { float* boxes; int64_t* cls; int* order; unsigned long long* skey; unsigned char* keep; int* status; unsigned long long* mask;
+               int64_t mask_stride, bytes; int words; };
+NmsWs nms_ws(void* workspace, int64_t images, int64_t k, int box_dim) {
+    const int64_t n = images ? images : 1;
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) { char* at = (char*)workspace + off; off += (bytes + 255) / 256 * 256; return at; };
+    NmsWs w;
+    w.words = (int)nms_row_words(k, k);
+    w.mask_stride = k * (int64_t)w.words;
+    w.boxes = (float*)take(n * k * box_dim * 4);
+    w.cls = (int64_t*)take(n * k * 8);
+    w.order = (int*)take(n * k * 4);
+    w.skey = (unsigned long long*)take(n * k * 8);
+    w.keep = (unsigned char*)take(n * k);
+    w.status = images ? (int*)take(images * 4) : nullptr;
+    w.mask = (unsigned long long*)take(n * w.mask_stride * 8);
+    w.bytes = off;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sph2pob_nms_max_boxes(void) { return kNmsMaxWords * 64 - 64; }  // per class segment (unaligned: L/64 + 2 words)
+int64_t sph2pob_nms_workspace_bytes(int64_t k) { return k * nms_row_words(k, k) * 8; }
+int64_t sph2pob_nms_segmented_workspace_bytes(int64_t k, int64_t max_segment) {
+    return k * nms_row_words(k, max_segment < 1 ? 1 : max_segment) * 8;
+}
+
 int sph2pob_nms_segmented_f32(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim,
                               int variant_flags, float iou_threshold, int64_t max_segment, void* workspace,
                               unsigned char* keep, void* stream) {
-    int rc = nms_check_options(box_dim, variant_flags);
-    if (rc) return rc;
+    if (int rc = sph2pob_gb::nms_check_options(box_dim, variant_flags)) return rc;
     if (k < 0 || k > ((int64_t)1 << 31) - 64 || max_segment < 0 || max_segment > sph2pob_nms_max_boxes())
         return SPH2POB_ERR_SIZE;
     if (k == 0) return SPH2POB_OK;
@@ -665,125 +712,70 @@ int sph2pob_nms_segmented_f32(const float* boxes_sorted, const int64_t* cls_sort
                               (hipStream_t)stream);
 }
 
-// workspace of the host-free form: sorted boxes | classes | permutation | keep flags | mask matrix (all 256-byte aligned)
-struct BatchedNmsWs { float* boxes; int64_t* cls; int* order; unsigned long long* skey; unsigned char* keep; unsigned long long* mask; int64_t bytes; int words; };
-static BatchedNmsWs batched_nms_ws(void* workspace, int64_t k, int box_dim) {
-    auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
-    BatchedNmsWs w;
-    char* p = (char*)workspace;
-    w.words = (int)nms_row_words(k, k);
-    int64_t off = 0;
-    w.boxes = (float*)(p + off); off += up(k * box_dim * 4);
-    w.cls = (int64_t*)(p + off); off += up(k * 8);
-    w.order = (int*)(p + off); off += up(k * 4);
-    w.skey = (unsigned long long*)(p + off); off += up(k * 8);
-    w.keep = (unsigned char*)(p + off); off += up(k);
-    w.mask = (unsigned long long*)(p + off); off += up(k * (int64_t)w.words * 8);
-    w.bytes = off;
-    return w;
-}
 int sph2pob_batched_nms_max_boxes(void) { return 1 << kNmsIdxBits; }
 int64_t sph2pob_batched_nms_workspace_bytes(int64_t k, int box_dim) {
-    return k > 0 && k <= sph2pob_batched_nms_max_boxes() ? batched_nms_ws(nullptr, k, box_dim).bytes : 0;
+    return k > 0 && k <= sph2pob_batched_nms_max_boxes() ? nms_ws(nullptr, 0, k, box_dim).bytes : 0;
 }
 int sph2pob_batched_nms_f32(const float* boxes, const float* scores, const int64_t* idxs, int64_t k, int box_dim, int variant_flags,
                             float iou_threshold, int64_t max_num, void* workspace, int64_t* keep, float* dets, int* status,
                             void* stream) {
-    int rc = nms_check_options(box_dim, variant_flags);
-    if (rc) return rc;
+    if (int rc = sph2pob_gb::nms_check_options(box_dim, variant_flags)) return rc;
     if (k < 0 || k > sph2pob_batched_nms_max_boxes() || max_num < 0) return SPH2POB_ERR_SIZE;
     if (!status) return SPH2POB_ERR_NULL;
     hipStream_t s = (hipStream_t)stream;
     if (k == 0 || max_num == 0) return hipMemsetAsync(status, 0, sizeof(int), s) == hipSuccess ? SPH2POB_OK : (int)hipGetLastError();
     if (!boxes || !scores || !workspace || !keep || !dets) return SPH2POB_ERR_NULL;
-    const BatchedNmsWs w = batched_nms_ws(workspace, k, box_dim);
+    const NmsWs w = nms_ws(workspace, 0, k, box_dim);
     const int kk = (int)k, mx = (int)(max_num < k ? max_num : k);
-    // T keys per lane x BS threads cover the candidates, IPW boxes per workgroup, chosen so that the grid is at most 256
-    // workgroups: with ~150 VGPRs per lane a CU holds ONE of these workgroups at a time, and 313 of them (16 boxes each at
-    // K = 5 000) ran in two rounds — 12 us per launch where 6 144 candidates or fewer now take one round
-#define SPH_PREP(T, D, I, B) hipLaunchKernelGGL((nms_prepare_kernel<T, D, I, B>), dim3((unsigned)((k + I - 1) / I)), dim3(B), 0, s, boxes, scores, idxs, kk, \
-                                                w.boxes, w.cls, w.order, w.skey, status)
-#define SPH_SEL(T, D, I, B) hipLaunchKernelGGL((nms_select_kernel<T, D, I, B>), dim3((unsigned)((k + I - 1) / I)), dim3(B), 0, s, (const float*)w.boxes, \
-                                               (const unsigned char*)w.keep, (const unsigned long long*)w.skey, kk, mx, keep, dets, status)
-#define SPH_BY_SIZE(M, D) do { if (k <= 2048) M(4, D, 16, 512); else if (k <= 4096) M(8, D, 16, 512); else if (k <= 6144) M(12, D, 24, 512); \
-                               else if (k <= 8192) M(16, D, 32, 512); else if (k <= 12288) M(12, D, 48, 1024); else M(16, D, 64, 1024); } while (0)
-    if (box_dim == 4) SPH_BY_SIZE(SPH_PREP, 4); else SPH_BY_SIZE(SPH_PREP, 5);
-    rc = launch_status();
-    if (rc) return rc;
-    rc = nms_mask_and_sweep(w.boxes, idxs ? w.cls : nullptr, k, box_dim, variant_flags, iou_threshold, w.words, w.mask, w.keep, s);
-    if (rc) return rc;
-    if (box_dim == 4) SPH_BY_SIZE(SPH_SEL, 4); else SPH_BY_SIZE(SPH_SEL, 5);
-#undef SPH_PREP
-#undef SPH_SEL
-#undef SPH_BY_SIZE
+    by_sort_size(k, box_dim, [&](auto size) {
+        using Z = decltype(size);
+        hipLaunchKernelGGL((nms_prepare_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k), dim3(Z::BS), 0, s, boxes, scores, idxs, kk, w.boxes, w.cls,
+                           w.order, w.skey, status);
+    });
+    if (int rc = launch_status()) return rc;
+    if (int rc = nms_mask_and_sweep(w.boxes, idxs ? w.cls : nullptr, k, box_dim, variant_flags, iou_threshold, w.words, w.mask, w.keep, s)) return rc;
+    by_sort_size(k, box_dim, [&](auto size) {
+        using Z = decltype(size);
+        hipLaunchKernelGGL((nms_select_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k), dim3(Z::BS), 0, s, w.boxes, w.keep, w.skey, kk, mx, keep, dets,
+                           status);
+    });
     return launch_status();
 }
 
-// The NMS stage of sph2pob_test_bboxes_f32 (sph2pob_get_bboxes.hip): the four kernels above with the image as grid dimension y.
-// Candidate blocks have the fixed stride k_cap, every kernel reads its image's live count from `counts`.  The caller has checked
-// the variant: the closed-form ones and the unbiased one take the compacting mask kernel (cull first, finish on the survivors), the
-// naive one the plain kernel — what sph2pob_batched_nms_f32 launches for one image.  class_agnostic: the sort is by score alone and
-// mask and sweep see one segment per image (no class array), as sph2pob_batched_nms_f32 with idxs == NULL; labels_out are still
-// the candidates' own.
-__attribute__((visibility("hidden"))) int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim) {
-    return num_images * batched_nms_ws(nullptr, k_cap, box_dim).bytes + (num_images * 4 + 255) / 256 * 256;   // + one status word per image
-}
-__attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(const float* boxes, const float* scores, const int64_t* labels, const int* prior,
-                                                                   const int* counts, int64_t num_images, int k_cap, int box_dim, int variant_flags,
-                                                                   int class_agnostic, float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
-                                                                   int64_t* labels_out, int64_t* prior_out, int64_t* num_dets, void* stream) {
+// The NMS stage of sph2pob_test_bboxes_f32 (sph2pob_get_bboxes.hip; declared in sph2pob_get_bboxes.hpp): the four kernels above with
+// the image as grid dimension y.  Candidate blocks have the fixed stride k_cap, every kernel reads its image's live count from
+// `counts`.  The caller has checked the variant; the kernels are what sph2pob_batched_nms_f32 launches for one image.
+// class_agnostic: the sort is by score alone and mask and sweep see one segment per image (no class array), as
+// sph2pob_batched_nms_f32 with idxs == NULL; labels_out are still the candidates' own.
+int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim) { return nms_ws(nullptr, num_images, k_cap, box_dim).bytes; }
+int sph2pob_nms_batch_launch(const float* boxes, const float* scores, const int64_t* labels, const int* prior, const int* counts,
+                             int64_t num_images, int k_cap, int box_dim, int variant_flags, int class_agnostic, float iou_threshold,
+                             int64_t max_per_img, void* nms_workspace, float* dets, int64_t* labels_out, int64_t* prior_out, int64_t* num_dets,
+                             void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int64_t k = k_cap;
     const unsigned B = (unsigned)num_images;
-    // one image's layout B times over: every array of image b starts b * k_cap elements into its B-fold region
-    const BatchedNmsWs one = batched_nms_ws(nullptr, k, box_dim);
-    auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
-    char* p = (char*)nms_workspace;
-    BatchedNmsWs w = one;
-    int64_t off = 0;
-    w.boxes = (float*)(p + off); off += up(num_images * k * box_dim * 4);
-    w.cls = (int64_t*)(p + off); off += up(num_images * k * 8);
-    w.order = (int*)(p + off); off += up(num_images * k * 4);
-    w.skey = (unsigned long long*)(p + off); off += up(num_images * k * 8);
-    w.keep = (unsigned char*)(p + off); off += up(num_images * k);
-    int* status = (int*)(p + off); off += up(num_images * 4);
-    w.mask = (unsigned long long*)(p + off);
-    const int64_t mask_stride = k * (int64_t)one.words;
-    const int variant = variant_flags & 0xff, rows = (int)max_per_img;
-    const int64_t* sort_cls = class_agnostic ? nullptr : labels;          // what the order is built on
-    const int64_t* seg_cls = class_agnostic ? nullptr : (const int64_t*)w.cls;   // the segments of the sorted order
-#define SPH_PREP(T, D, I, Bs) hipLaunchKernelGGL((nms_prepare_batch_kernel<T, D, I, Bs>), dim3((unsigned)((k + I - 1) / I), B), dim3(Bs), 0, s, boxes, scores, \
-                                                 sort_cls, counts, k_cap, w.boxes, w.cls, w.order, w.skey, status)
-#define SPH_SEL(T, D, I, Bs) hipLaunchKernelGGL((nms_select_batch_kernel<T, D, I, Bs>), dim3((unsigned)((k + I - 1) / I), B), dim3(Bs), 0, s, \
-                                                (const float*)w.boxes, (const unsigned char*)w.keep, (const unsigned long long*)w.skey, counts, k_cap, rows, \
-                                                labels, prior, dets, labels_out, prior_out, num_dets)
-#define SPH_BY_SIZE(M, D) do { if (k <= 2048) M(4, D, 16, 512); else if (k <= 4096) M(8, D, 16, 512); else if (k <= 6144) M(12, D, 24, 512); \
-                               else if (k <= 8192) M(16, D, 32, 512); else if (k <= 12288) M(12, D, 48, 1024); else M(16, D, 64, 1024); } while (0)
-    if (box_dim == 4) SPH_BY_SIZE(SPH_PREP, 4); else SPH_BY_SIZE(SPH_PREP, 5);
-    int rc = launch_status();
-    if (rc) return rc;
-    const dim3 mgrid((unsigned)((k + kBlock / 64 - 1) / (kBlock / 64)), B);
-#define SPH_MASK(V, D) hipLaunchKernelGGL((nms_mask_compact_batch_kernel<V, D>), mgrid, dim3(kBlock), 0, s, (const float*)w.boxes, seg_cls, \
-                                          counts, k_cap, iou_threshold, w.mask, mask_stride)
-#define SPH_MASK_PLAIN(V, D) hipLaunchKernelGGL((nms_mask_batch_kernel<V, D>), mgrid, dim3(kBlock), 0, s, (const float*)w.boxes, seg_cls, counts, k_cap, \
-                                                iou_threshold, w.mask, mask_stride, \
-                                                (variant_flags & SPH2POB_FLAG_NAIVE_TAN) ? (int)EDGE_TANGENT : (int)EDGE_ARC)
-    if (variant == SPH2POB_VARIANT_EFFICIENT) { if (box_dim == 4) SPH_MASK(1, 4); else SPH_MASK(1, 5); }
-    else if (variant == SPH2POB_VARIANT_UNBIASED) { if (box_dim == 4) SPH_MASK(5, 4); else SPH_MASK(5, 5); }
-    else if (variant == SPH2POB_VARIANT_NAIVE) { if (box_dim == 4) SPH_MASK_PLAIN(6, 4); else SPH_MASK_PLAIN(6, 5); }
-    else { if (box_dim == 4) SPH_MASK(0, 4); else SPH_MASK(0, 5); }
-    rc = launch_status();
-    if (rc) return rc;
-    hipLaunchKernelGGL(nms_sweep_batch_kernel, dim3((unsigned)((k + kSweepCands - 1) / kSweepCands), B), dim3(kSweepBlock), 0, s,
-                       (const unsigned long long*)w.mask, mask_stride, seg_cls, counts, k_cap, w.keep);
-    rc = launch_status();
-    if (rc) return rc;
-    if (box_dim == 4) SPH_BY_SIZE(SPH_SEL, 4); else SPH_BY_SIZE(SPH_SEL, 5);
-#undef SPH_PREP
-#undef SPH_SEL
-#undef SPH_BY_SIZE
-#undef SPH_MASK
-#undef SPH_MASK_PLAIN
+    const NmsWs w = nms_ws(nms_workspace, num_images, k, box_dim);
+    const int rows = (int)max_per_img;
+    const int64_t* sort_cls = class_agnostic ? nullptr : labels;   // what the order is built on
+    const int64_t* seg_cls = class_agnostic ? nullptr : w.cls;     // the segments of the sorted order
+    by_sort_size(k, box_dim, [&](auto size) {
+        using Z = decltype(size);
+        hipLaunchKernelGGL((nms_prepare_batch_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k, B), dim3(Z::BS), 0, s, boxes, scores, sort_cls, counts,
+                           k_cap, w.boxes, w.cls, w.order, w.skey, w.status);
+    });
+    if (int rc = launch_status()) return rc;
+    if (int rc = dispatch(variant_flags, box_dim,
+                          MaskBatchLaunch{w.boxes, seg_cls, counts, k_cap, B, iou_threshold, w.mask, w.mask_stride, nms_edge(variant_flags), s}))
+        return rc;
+    hipLaunchKernelGGL(nms_sweep_batch_kernel, dim3((unsigned)((k + kSweepCands - 1) / kSweepCands), B), dim3(kSweepBlock), 0, s, w.mask,
+                       w.mask_stride, seg_cls, counts, k_cap, w.keep);
+    if (int rc = launch_status()) return rc;
+    by_sort_size(k, box_dim, [&](auto size) {
+        using Z = decltype(size);
+        hipLaunchKernelGGL((nms_select_batch_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k, B), dim3(Z::BS), 0, s, w.boxes, w.keep, w.skey, counts,
+                           k_cap, rows, labels, prior, dets, labels_out, prior_out, num_dets);
+    });
     return launch_status();
 }
 

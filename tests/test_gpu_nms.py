@@ -198,7 +198,8 @@ def _general_route(N, boxes, scores, idxs, cfg, variant='efficient'):
         lib.sph2pob_batched_nms_max_boxes = real
 
 
-@pytest.mark.parametrize('k,dim,ncls', [(1, 4, 1), (63, 4, 3), (2048, 4, 37), (2049, 5, 5), (5000, 4, 37), (8192, 4, 2), (16384, 4, 80)])
+@pytest.mark.parametrize('k,dim,ncls', [(1, 4, 1), (63, 4, 3), (2048, 4, 37), (2049, 5, 5), (5000, 4, 37), (8192, 4, 2), (16384, 4, 80),
+                                          (4097, 4, 3), (6145, 5, 3), (8193, 4, 3), (12288, 4, 3), (12289, 5, 3)])   # (the other edges of the sort's size classes)
 def test_host_free_route_equals_general_route(N, oracle, k, dim, ncls):
     rng = np.random.default_rng(k + dim)
     centres = oracle.generate_boxes(max(k // 16, 1), 8, box='bfov' if dim == 4 else 'rbfov', alpha=(5, 60), beta=(5, 60))

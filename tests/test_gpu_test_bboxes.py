@@ -77,6 +77,31 @@ def test_small_scene_equals_the_per_image_composition(S, dim, variant):
     assert all(60 < int(wide.num_dets[b]) < 600 for b in (0, 2, 3)), wide.num_dets.tolist()
 
 
+@pytest.mark.parametrize('k_cap,calculator,dim', [(2048, 'sph2pob_efficient', 4), (2049, 'naive_iou', 5), (4097, 'sph2pob_efficient', 4),
+                                                 (6145, 'naive_iou', 5), (8193, 'sph2pob_efficient', 4), (12289, 'naive_iou', 5),
+                                                 (16384, 'sph2pob_efficient', 4)])
+def test_every_sort_size_class_with_a_full_and_a_sparse_image(S, k_cap, calculator, dim):
+    """The rank sort's size class is chosen for k_cap, on both sides of every edge of the class table, and serves every image's
+    own count: image 0 fills the candidate block (k_cap live candidates), image 1 has 100 — far below the class k_cap selects.
+    One flattened level, n = 4096, C = 4: class segments of about k_cap / 4 boxes.  The compacting mask kernel (efficient, BFoV)
+    and the plain one (naive, RBFoV) alternate over the sizes."""
+    n, C, thr = 4096, 4, 0.05
+    g = torch.Generator().manual_seed(k_cap)
+    u = torch.rand((256, 5), generator=g).repeat(n // 256, 1)   # 256 distinct anchors, the deltas spread them: the NMS has work to do
+    anchors = [torch.stack([u[:, 0] * 360, 40 + u[:, 1] * 100, 10 + u[:, 2] * 50, 10 + u[:, 3] * 50, u[:, 4] * 120 - 60], 1)[:, :dim].contiguous().cuda()]
+    s = torch.rand((2, n * C), generator=g) * 0.9 + 0.06                 # image 0: every score above the threshold
+    few = torch.randperm(n * C, generator=g)[:100]
+    s[1] = s[1] * 0.01                                                   # image 1: exactly 100 of them
+    s[1, few] = s[1, few] * 100
+    cls, box = [s.reshape(2, n, C).cuda()], [(torch.randn((2, n, dim), generator=g) * 0.5).cuda()]
+    assert int((cls[0][0] > thr).sum()) == n * C and int((cls[0][1] > thr).sum()) == 100
+    coder = coder_for(S, dim)
+    cfg = cfg_with(PANDORA, iou_calculator=calculator, nms_pre=k_cap, max_per_img=1000, score_thr=thr)
+    r = S.sph_test_bboxes(cls, box, anchors, bbox_coder=coder, test_cfg=cfg, box_version=dim, activation='none')
+    counts, levels = check_batch(r, cls, box, anchors, coder, cfg, dim)
+    assert levels == [[k_cap], [100]] and 0 < counts[1] <= 100 < counts[0] < k_cap, (counts, levels)
+
+
 def level_anchors(demo, dim):
     anchors = demo.retina_level_anchors()
     if dim == 5:
