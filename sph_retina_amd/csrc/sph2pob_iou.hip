@@ -1,6 +1,8 @@
 // libsph2pob_hip.so — aligned IoU (the dominant kernels), the Sph2Pob transform and its adjoint, planar IoU: kernels + C-ABI
 // launchers (include/sph2pob_hip.h).  gfx950 only.
 
+#include <type_traits>
+
 #include "sph2pob_kernels_common.hpp"
 
 namespace {
@@ -235,12 +237,43 @@ __global__ __launch_bounds__(kBlock, REF ? 4 : (DIM == 4 ? 7 : 5)) void iou_alig
 //     instantiation of the same build read 60.0; RBFoV keeps 64-bit offsets.
 //     The BFoV chunk kernel now has three instantiations per (variant, edge) instead of one (64-bit; 32-bit with and
 //     without the priority): +0.2 MB of library (7.4 -> 7.6 MB).
+//   * whole-line stores (LINES; profiles/r11a_store_floor.log, r11b_ab_lines_*.log; bit-identical results).
+//     The dword stores (two masked zero stores in the cull, one scattered store in the pass) touched every 128-byte line
+//     twice and left 4 MB dirty in the L2s for the kernel boundary.  A load-store-only kernel of this shape: dword per lane
+//     4.04 us per launch, dwordx4 from lanes 0-31 3.21, the same write-through (sc1) 2.89, dword sc1 3.83, empty 2.71.  Here:
+//     the chunk's results staged in 512 B of the wave's LDS and stored once after the pass loop.  Against the parent, 7
+//     interleaved rounds (us per launch, parent / dword body of this build / plain lines / write-through lines):
+//     250 k 4.33 / 4.37 / 4.46 / 4.45 (rounds 4.1-5.9: level), 1 M 6.75 / 6.81 / 6.90 / 6.31, 2 M 15.35 / 15.12 / 13.75 / 13.58,
+//     8 M 47.04 / 46.59 / 45.03 / 44.79; efficient 1 M 6.85 / 6.86 / 6.89 / 6.37, 8 M 46.75 / 46.92 / 45.14 / 44.30.  bench.py,
+//     three interleaved runs: 6.857 -> 6.233 us per step (spreads 0.042 / 0.171).  Write-through lines are the fastest arm
+//     at every size where the arms differ, so they are the default everywhere; plain lines gain from 2 M pairs up and
+//     nothing at 1 M (the staging's LDS traffic pays for the saved stores; the gain at 1 M is the write-through's: nothing
+//     is left to write back while no SIMD can work).  A dword per lane written through was not built for this kernel (the
+//     floor says 3.83 us against 2.89).  Four more instantiations per (variant, edge): 7.6 -> 8.2 MB of library.
+//     250 k again with 15 rounds (parent / shipped / dword body): 4.249 / 4.260 / 4.227, efficient 3.866 / 3.828 / 3.805: level.
+//     The shipped build (no knob) against the parent (profiles/r11c_*, r11d_*): iou.npy of bench.py --dump-outputs byte-identical
+//     (default, 8 M pairs, efficient); bench.py 6.777 -> 6.260 us per step (three interleaved runs each, spreads 0.155 / 0.046);
+//     --full, one run each: kernel_ms 6.84 -> 6.50, cold 10.56 -> 9.18, at_8m 48.64 -> 46.75 us; rocprofv3: traced average
+//     7.85 -> 6.88 us, WRITE_SIZE 4.287 -> 4.000 MB per launch (the algorithmic bytes), SQ_INSTS_VALU 420.1 -> 441.1 per wave
+//     (+21: the staging costs more issue than the stores it replaces), SQ_INSTS_SALU 579 k -> 634 k.
 template <int DIM, int SLICES>
 struct ChunkQueue {
     float f[2 * DIM][64 * SLICES];
     int idx[64 * SLICES];   // pair index (OFF32: the byte offset of the pair's result, 4 * index)
 };
+// LINES: the chunk's results are staged in the wave's own LDS (`res`) and written after the pass loop as whole 128-byte
+// lines.  The stack's index column holds the byte offset of the survivor's slot in `res` (< 256 SLICES) in 16 bits, so that
+// the workgroup takes 19 456 B and eight stay resident per CU (a 32-bit column: 20 480 B, exactly 160 KiB for eight).
+template <int DIM, int SLICES>
+struct alignas(16) ChunkLineQueue {
+    float f[2 * DIM][64 * SLICES];
+    float res[64 * SLICES];
+    unsigned short idx[64 * SLICES];
+};
 constexpr int kChunkSlices = 2;
+// write-through whole lines at every size: fastest arm from 1 M to 8 M pairs, level with the others at 250 k (see the kernel's header)
+constexpr int kChunkStoresDefault = CHUNK_STORES_WT;
+static_assert(256 * kChunkSlices <= 65536, "a slot's byte offset in res fits the 16-bit index column");
 // OFF32: every load and store of the chunk kernel is addressed by an unsigned 32-bit byte offset from its kernel-argument
 // pointer (global_load / global_store v_off, s[base:base+1]: no 64-bit address arithmetic per lane), which needs the byte
 // offset one past the last box, n * 4 * dim, to fit in 32 bits.  Above that the launcher takes the 64-bit instantiation.
@@ -251,15 +284,21 @@ static_assert(chunk_offsets_fit_u32(0, 4) && chunk_offsets_fit_u32(0, 5) && !chu
 __device__ __forceinline__ const float* at_byte(const float* __restrict__ p, unsigned off) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(p) + off); }
 __device__ __forceinline__ float* at_byte(float* __restrict__ p, unsigned off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(p) + off); }
 // PRIO: the load + cull phase at wave priority 1 (the launcher's choice: see below)
-template <int VARIANT, int DIM, bool ARC, int SLICES, bool OFF32, bool PRIO, int WAVES = kBlock / 64>
+// LINES (BFoV 32-bit bodies; the launcher asks for it only when `out` is 16-byte aligned): no global store in the cull or
+// the pass; see ChunkLineQueue and the end of the kernel.  WT: the line stores are write-through (sc1).
+template <int VARIANT, int DIM, bool ARC, int SLICES, bool OFF32, bool PRIO, bool LINES = false, bool WT = false, int WAVES = kBlock / 64>
 __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chunk_kernel(const float* __restrict__ b1, const float* __restrict__ b2,
                                                                       float* __restrict__ out, int n, int mode, int edge_arg) {
-    __shared__ ChunkQueue<DIM, SLICES> queues[WAVES];
+    static_assert(!LINES || (DIM == 4 && OFF32), "whole-line stores are built for the BFoV 32-bit bodies only");
+    static_assert(LINES || !WT, "write-through is a flavour of the line stores");
+    using Queue = std::conditional_t<LINES, ChunkLineQueue<DIM, SLICES>, ChunkQueue<DIM, SLICES>>;
+    __shared__ Queue queues[WAVES];
+    static_assert(!LINES || 8 * sizeof(queues) + 4096 <= 160 * 1024, "eight workgroups per CU, at least 4 KiB clear of the 160 KiB of LDS");
     const int edge = ARC ? (int)EDGE_ARC : (edge_arg & 0xff);
     const int lane = threadIdx.x & 63;
     // the wave's number in an SGPR: its chunk, the test below and its LDS base (formed once) are scalar
     const int wave = OFF32 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
-    ChunkQueue<DIM, SLICES>& q = queues[wave];
+    Queue& q = queues[wave];
     const int base = (blockIdx.x * WAVES + wave) * (64 * SLICES);
     if (base >= n) return;   // wave-uniform; the kernel has no barrier
     const int wave_global = blockIdx.x * WAVES + wave;
@@ -337,7 +376,8 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
         // compare whose mask crosses a branch, costs two more VALU instructions; see CullParts)
         const unsigned long long m = __builtin_amdgcn_ballot_w64(inside) & ~cm;
 #endif
-        if (inside & culled) {   // (non-temporal stores here and below: 8.42 vs 8.30 us at 1 M, 51.4 vs 48.1 at 8 M)
+        if constexpr (LINES) q.res[s * 64 + lane] = zero;   // every lane, no branch: a survivor's result lands on it later
+        else if (inside & culled) {   // (non-temporal stores here and below: 8.42 vs 8.30 us at 1 M, 51.4 vs 48.1 at 8 M)
             if (OFF32) *at_byte(out, o4 + s * 256u) = zero;
             else out[i] = 0.0f;
         }
@@ -345,7 +385,8 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
             const int slot = count + rank_below(m);
 #pragma unroll
             for (int k = 0; k < DIM; k++) { q.f[k][slot] = x[s][k]; q.f[DIM + k][slot] = y[s][k]; }
-            q.idx[slot] = OFF32 ? (int)(o4 + s * 256u) : i;
+            if constexpr (LINES) q.idx[slot] = (unsigned short)((s * 64 + lane) * 4);
+            else q.idx[slot] = OFF32 ? (int)(o4 + s * 256u) : i;
         }
         count += __popcll(m);
         if (s == 0) SPH_STAMP(1);
@@ -366,8 +407,32 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
 #else
             const float r = lean_finish<VARIANT, DIM>(u1, u2, mode, edge);
 #endif
-            if (OFF32) *at_byte(out, (unsigned)q.idx[slot]) = r;
+            if constexpr (LINES) *reinterpret_cast<float*>(reinterpret_cast<char*>(q.res) + q.idx[slot]) = r;   // in order behind the zero
+            else if (OFF32) *at_byte(out, (unsigned)q.idx[slot]) = r;
             else out[q.idx[slot]] = r;
+        }
+    }
+    if constexpr (LINES) {
+        // the chunk's 128 results, once: lanes 0-31 read 16 bytes of `res` each and store them with ONE instruction, so that
+        // every 128-byte line of the output is written whole.  The one wave that holds the batch's tail stores a dword per
+        // lane as before: a line store never reaches past n.
+        wave_lds_fence();
+        if (base + 64 * SLICES <= n) {   // wave-uniform
+            static_assert(SLICES == 2, "32 lanes x 16 bytes = the 128 results of two slices");
+            if (lane < 32) {
+                const float4 v = *reinterpret_cast<const float4*>(&q.res[4 * lane]);
+                const unsigned off = (unsigned)base * 4u + 16u * lane;
+                if constexpr (WT) {
+                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                    const u32x4 w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+                    // (n * 4 fits: the 32-bit route; the descriptor's range check is a second guard, not the bound)
+                    __builtin_amdgcn_raw_buffer_store_b128(w, __builtin_amdgcn_make_buffer_rsrc(out, 0, n * 4, 0x00020000), off, 0, /* sc1 */ 16);
+                } else *reinterpret_cast<float4*>(at_byte(out, off)) = v;
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < SLICES; s++)
+                if (o4 + s * 256u < (unsigned)n * 4u) *at_byte(out, o4 + s * 256u) = q.res[s * 64 + lane];
         }
     }
     SPH_STAMP(5);
@@ -477,14 +542,19 @@ struct AlignedLaunch {
                 // cull phase at a higher wave priority while (nearly) the whole grid is resident at once: see the kernel
                 const bool prio = D == 4 && (int64_t)cw <= kCUs * 8 * 2 && !g_no_prio;
                 const bool off32 = D == 4 && chunk_offsets_fit_u32(n, D);   // (RBFoV stays on 64-bit offsets: see the kernel)
-#define SPH_CHUNK(ARC, O32, PRIO) hipLaunchKernelGGL((iou_aligned_chunk_kernel<VV, D, ARC, kChunkSlices, O32, PRIO>), dim3(cw), dim3(kBlock), 0, s, b1, b2, out, (int)n, mode, edge_k)
-#define SPH_CHUNK_ARC(O32, PRIO) do { if (edge == SPH2POB_EDGE_ARC) SPH_CHUNK(true, O32, PRIO); else SPH_CHUNK(false, O32, PRIO); } while (0)
+                // whole-line stores need a 16-byte aligned output (a tensor view need not be); which form a size gets: see the kernel
+                int stores = g_chunk_stores != CHUNK_STORES_AUTO ? g_chunk_stores : kChunkStoresDefault;
+                if (!off32 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) stores = CHUNK_STORES_DWORD;
+#define SPH_CHUNK(ARC, O32, PRIO, LINES, WT) hipLaunchKernelGGL((iou_aligned_chunk_kernel<VV, D, ARC, kChunkSlices, O32, PRIO, LINES, WT>), dim3(cw), dim3(kBlock), 0, s, b1, b2, out, (int)n, mode, edge_k)
+#define SPH_CHUNK_ARC(O32, PRIO, LINES, WT) do { if (edge == SPH2POB_EDGE_ARC) SPH_CHUNK(true, O32, PRIO, LINES, WT); else SPH_CHUNK(false, O32, PRIO, LINES, WT); } while (0)
+#define SPH_CHUNK_STORES(PRIO) do { if (stores == CHUNK_STORES_WT) SPH_CHUNK_ARC(true, PRIO, true, true); else if (stores == CHUNK_STORES_LINES) SPH_CHUNK_ARC(true, PRIO, true, false); else SPH_CHUNK_ARC(true, PRIO, false, false); } while (0)
                 // (a launch that is large enough for 64-bit offsets is far beyond two rounds: it never asks for the priority)
-                if constexpr (D == 4) {   // (OFF32 is instantiated for BFoV only: the kernel's static_assert)
-                    if (!off32) SPH_CHUNK_ARC(false, false);
-                    else if (prio) SPH_CHUNK_ARC(true, true);
-                    else SPH_CHUNK_ARC(true, false);
-                } else SPH_CHUNK_ARC(false, false);
+                if constexpr (D == 4) {   // (OFF32 and LINES are instantiated for BFoV only: the kernel's static_asserts)
+                    if (!off32) SPH_CHUNK_ARC(false, false, false, false);
+                    else if (prio) SPH_CHUNK_STORES(true);
+                    else SPH_CHUNK_STORES(false);
+                } else SPH_CHUNK_ARC(false, false, false, false);
+#undef SPH_CHUNK_STORES
 #undef SPH_CHUNK_ARC
 #undef SPH_CHUNK
             } else
@@ -619,6 +689,10 @@ int sph2pob_transform_bwd_general_f32(const float* b1, const float* b2, const fl
 #undef SPH_TBWDD
     return launch_status();
 }
+
+// Not part of the ABI (tests): the store form that SPH2POB_CHUNK_STORES forced when this copy was loaded: 0 none (the launcher's
+// default), 1 dword, 2 lines, 3 write-through lines.
+int sph2pob_debug_chunk_stores(void) { return g_chunk_stores; }
 
 #if defined(SPH_STAMPS)
 int sph2pob_debug_set_stamps(void* buffer) {

@@ -30,6 +30,13 @@ static int g_pw_rows = getenv("SPH2POB_PW_ROWS") ? atoi(getenv("SPH2POB_PW_ROWS"
 static int g_slices_per_wave = getenv("SPH2POB_SLICES_PER_WAVE") ? atoi(getenv("SPH2POB_SLICES_PER_WAVE")) : 0;
 static int g_wgs_per_cu = getenv("SPH2POB_WGS_PER_CU") ? atoi(getenv("SPH2POB_WGS_PER_CU")) : 0;
 static bool g_no_prio = getenv("SPH2POB_NO_PRIO") != nullptr;   // A/B: no wave priority in the chunk kernel
+// A/B: SPH2POB_CHUNK_STORES=dword|lines|wt forces how the BFoV chunk kernel writes its results (a dword per lane; whole
+// 128-byte lines, plain; whole lines, write-through); anything else leaves the choice to the launcher
+enum { CHUNK_STORES_AUTO = 0, CHUNK_STORES_DWORD, CHUNK_STORES_LINES, CHUNK_STORES_WT };
+static int g_chunk_stores = [] {
+    const char* s = getenv("SPH2POB_CHUNK_STORES");
+    return !s ? CHUNK_STORES_AUTO : s[0] == 'd' ? CHUNK_STORES_DWORD : s[0] == 'l' ? CHUNK_STORES_LINES : s[0] == 'w' ? CHUNK_STORES_WT : CHUNK_STORES_AUTO;
+}();
 static bool g_persistent = getenv("SPH2POB_ALIGNED_KERNEL") != nullptr && getenv("SPH2POB_ALIGNED_KERNEL")[0] == 'p';   // A/B: the persistent form
 
 template <int DIM>
