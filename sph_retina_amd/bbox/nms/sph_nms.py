@@ -48,7 +48,7 @@ def _nms_sorted(boxes_sorted, cls_sorted, iou_threshold, variant):
     keep = torch.empty((k,), dtype=torch.uint8, device=dev)
     if k == 0:
         return keep
-    # the suppression matrix is k x (largest class segment / 64 + 2) words: its width needs the largest segment on the
+    # the suppression matrix is k x min(largest class segment / 64 + 2, 512) words: its width needs the largest segment on the
     # host (one sync; the caller's nonzero() syncs anyway).  multiclass_nms hands over every (box, class) candidate
     # above score_thr — far more than 32 768 rows in total, but a class segment stays small.
     # Small inputs take the full k x k/64 layout (<= 8 MB) and skip that sync.

@@ -53,7 +53,7 @@ __device__ __forceinline__ void nms_mask_body(const float* __restrict__ boxes, c
                                               float thr, unsigned long long* __restrict__ mask, int edge) {
     // one wave per row i: only the words that hold later columns of row i's own class segment are evaluated.
     // Row layout: `words` u64 per row, word r of row i covers columns 64 * ((seg_start >> 6) + r) ...: indices are
-    // relative to the row's class segment, so the matrix is k x (largest segment / 64 + 2) instead of k x k / 64.
+    // relative to the row's class segment, so the matrix is k x min(largest segment / 64 + 2, kNmsMaxWords) instead of k x k / 64.
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wave;
     if (i >= k) return;
@@ -115,7 +115,7 @@ __device__ __forceinline__ void nms_mask_compact_body(const float* __restrict__ 
                                                       int64_t k, int words, float thr,
                                                       unsigned long long* __restrict__ mask) {
     __shared__ int stack[kBlock / 64][kQCap];
-    __shared__ unsigned int bits[kBlock / 64][2 * kNmsMaxWords];
+    __shared__ unsigned int bits[kBlock / 64][2 * kNmsMaxWords];   // two dwords per row word: nms_row_words() never exceeds kNmsMaxWords
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wave;
     if (i >= k) return;   // whole waves leave: no workgroup barrier below
@@ -586,10 +586,15 @@ __global__ __launch_bounds__(BS) void nms_select_batch_kernel(const float* __res
 
 // ---- host side: the launch glue of the three entries (sorted input, one image without the host, the batched stage) ----
 
+// Words per mask row.  An unaligned segment of L boxes spans at most ceil((63 + L) / 64) <= L / 64 + 2 words, and a segment of
+// the largest size the sweep takes (kNmsMaxWords * 64 - 64 boxes) at most kNmsMaxWords of them at any offset: the width is
+// bounded by kNmsMaxWords, which is what the compacting mask kernel's LDS bitmap and the sweep's removed[] are sized for.
 int64_t nms_row_words(int64_t k, int64_t max_segment) {
-    int64_t full = (k + 63) / 64, seg = (max_segment >> 6) + 2;  // an unaligned segment of L boxes spans <= L/64 + 2 words
+    int64_t full = (k + 63) / 64, seg = (max_segment >> 6) + 2;
+    if (seg > kNmsMaxWords) seg = kNmsMaxWords;
     return seg < full ? seg : full;
 }
+static_assert((63 + (kNmsMaxWords * 64 - 64) + 63) / 64 == kNmsMaxWords, "the longest segment fits kNmsMaxWords words at any offset");
 int nms_edge(int variant_flags) { return (variant_flags & SPH2POB_FLAG_NAIVE_TAN) ? (int)EDGE_TANGENT : (int)EDGE_ARC; }
 
 // The size classes of the rank sort (nms_prepare_* and nms_select_*, single image and batched: the same class for the same k).
@@ -692,7 +697,7 @@ NmsWs nms_ws(void* workspace, int64_t images, int64_t k, int box_dim) {
 
 extern "C" {
 
-int sph2pob_nms_max_boxes(void) { return kNmsMaxWords * 64 - 64; }  // per class segment (unaligned: L/64 + 2 words)
+int sph2pob_nms_max_boxes(void) { return kNmsMaxWords * 64 - 64; }  // per class segment (unaligned: at most kNmsMaxWords words)
 int64_t sph2pob_nms_workspace_bytes(int64_t k) { return k * nms_row_words(k, k) * 8; }
 int64_t sph2pob_nms_segmented_workspace_bytes(int64_t k, int64_t max_segment) {
     return k * nms_row_words(k, max_segment < 1 ? 1 : max_segment) * 8;

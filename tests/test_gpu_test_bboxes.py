@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from nms_decisive_scenes import naive_iou_f64
 from test_bboxes_restatement import BASE_PLANAR, BASE_PLANAR_TAN, INDOOR360, PANDORA, candidates, cfg_with, check_batch
 
 pytestmark = pytest.mark.gpu
@@ -123,18 +124,6 @@ def test_real_shape_equals_the_per_image_composition(S, demo, variant, dim):
     counts, levels = check_batch(r, cls, box, anchors, coder, cfg, dim)
     assert all(0 < k <= 100 for k in counts), counts
     assert all(lv[:3] == [1000, 1000, 1000] and 0 < min(lv[3:]) and max(lv[3:]) < 1000 for lv in levels), levels
-
-
-def naive_iou_f64(a, b):
-    """The Naive IoU of BFoV boxes in float64 (the oracle evaluates it in the reference's fp32): boxes drawn in ERP pixels of the
-    512 x 1024 image (box_formator.py:76-83), then inter / max(union, 0) of the axis-aligned boxes.  Pairwise (m, n)."""
-    def xyxy(x):
-        cx, cy, w, h = x[:, 0] / 360 * 1024, x[:, 1] / 180 * 512, x[:, 2] / 360 * 1024, x[:, 3] / 180 * 512
-        return cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2
-    ax1, ay1, ax2, ay2 = [v[:, None] for v in xyxy(a)]
-    bx1, by1, bx2, by2 = [v[None, :] for v in xyxy(b)]
-    inter = np.maximum(np.minimum(ax2, bx2) - np.maximum(ax1, bx1), 0) * np.maximum(np.minimum(ay2, by2) - np.maximum(ay1, by1), 0)
-    return inter / np.maximum((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1) - inter, 0)
 
 
 def f64_keep(oracle, variant, boxes, scores, labels, thr):
