@@ -2,28 +2,37 @@
 // assigner batched over a minibatch with the anchor-target construction as its epilogue: kernels + C-ABI launchers
 // (include/sph2pob_hip.h).  gfx950 only.
 
+#include <type_traits>
+
 #include "sph2pob_kernels_common.hpp"
-#include "sph2pob_coder.hpp"
+#include "sph2pob_assign.hpp"
 
 namespace {
 
+using sph2pob_assign::Rule;
+using sph2pob_assign::threshold_index;
+static_assert(kBlock == sph2pob_assign::kTile, "one thread per column of a tile");
 
-// ---- pairwise IoU for the assigner call pattern (few rows x many columns), closed-form core ----
-// Order-preserving packed keys for max / first-argmax reductions (the assigner): (float bits mapped to an unsigned order) << 32
-// | ~index, so that the maximum key is the maximum value and, among equal values, the SMALLEST index — what torch.max(dim)
-// returns.  IoUs are >= +0 (the kernels never produce -0) or -1 for ignored columns.
-__device__ __forceinline__ unsigned long long pack_max_key(float v, int64_t j) {
-    // IoUs are >= 0 (or -1 for ignored columns): map to an order-preserving unsigned key; ties -> smallest index
-    unsigned u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned)(0xffffffffu - (unsigned)j);
+// a run-time flag as a compile-time one: the launchers pick a kernel's boolean template arguments through generic lambdas
+template <class F>
+auto with_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+
+// ---- packed keys: order-preserving, for max / first-argmax reductions with one atomic.  (float bits mapped to an unsigned order)
+// << 32 | an index that DEcreases with the position, so that the maximum key is the maximum value and, among equal values, the
+// SMALLEST index — what torch.max(dim) returns.  IoUs are >= +0 (the kernels never produce -0) or -1 for ignored columns. ----
+__device__ __forceinline__ unsigned ordered_bits(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-// the fused assigner's row keys keep bit 0 of the low word free for a "this value occurs at more than one column of the
+// the column key (and the matrix route's row key): low word = ~index
+__device__ __forceinline__ unsigned long long pack_max_key(float v, int64_t j) {
+    return ((unsigned long long)ordered_bits(v) << 32) | (unsigned)(0xffffffffu - (unsigned)j);
+}
+__device__ __forceinline__ int64_t max_key_index(unsigned long long key) { return (int64_t)(0xffffffffu - (unsigned)key); }
+// the fused assigner's row key keeps bit 0 of the low word free for a "this value occurs at more than one column of the
 // tile" flag: low = (0x7fffffff - index) << 1 | flag (indices < 2^31)
 __device__ __forceinline__ unsigned long long pack_row_key(float v, unsigned j) {
-    unsigned u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | ((0x7fffffffu - j) << 1);
+    return ((unsigned long long)ordered_bits(v) << 32) | ((0x7fffffffu - j) << 1);
 }
 __device__ __forceinline__ unsigned row_key_index(unsigned long long key) { return 0x7fffffffu - ((unsigned)key >> 1); }
 __device__ __forceinline__ float unpack_max_val(unsigned long long key) {
@@ -31,6 +40,15 @@ __device__ __forceinline__ float unpack_max_val(unsigned long long key) {
     u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
     return __uint_as_float(u);
 }
+// what a row holds when no tile contributed (no ignore mask: IoU 0 at the shard's first column)
+__device__ __forceinline__ unsigned long long row_floor(bool has_ignore, unsigned col_offset) {
+    return has_ignore ? 0ull : pack_row_key(0.0f, col_offset);
+}
+// a per-GT accumulator (the maximum of the tiles' row keys, zero when no tile contributed) -> the GT's key, tie flag cleared
+__device__ __forceinline__ unsigned long long acc_to_key(unsigned long long a, unsigned long long floor) { return (a > floor ? a : floor) & ~1ull; }
+// keys travel between ranks as SIGNED 64-bit integers (torch.distributed has no unsigned MAX): top bit flipped
+__device__ __forceinline__ long long key_to_signed(unsigned long long k) { return (long long)(k ^ 0x8000000000000000ull); }
+__device__ __forceinline__ unsigned long long key_from_signed(long long k) { return (unsigned long long)k ^ 0x8000000000000000ull; }
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -40,19 +58,53 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     return v;
 }
 
-// keys travel between ranks as SIGNED 64-bit integers (torch.distributed has no unsigned MAX): top bit flipped
-__device__ __forceinline__ long long key_to_signed(unsigned long long k) { return (long long)(k ^ 0x8000000000000000ull); }
-__device__ __forceinline__ unsigned long long key_from_signed(long long k) { return (unsigned long long)k ^ 0x8000000000000000ull; }
+// ---- one layout of the fused routes' two buffers, per image, in 64-bit words.
+// workspace: col_part[chunks][n], then row_part[k][tiles] (what pairwise_compact_tile writes; overwritten by every call).
+// state (zero between calls): one u64 accumulator per GT; the finalize pass's arrival counters; batched only, one line for the
+// image's packed (positives | negatives << 32) count; and, batched only, behind the LAST image one line: [0] images that
+// finished, [1] sum of max(positives, 1).  The batched route lays every image out for k_max rows whatever its own count; the
+// single-image route is one image without the count lines. ----
+constexpr int kAccLine = 8;        // u64 words per 64-byte line: every counter has a line of its own
+// column tiles per first-level arrival counter; one more counter takes the groups' arrivals (a single counter serialises one
+// returning atomic per workgroup: 1 535 tiles = +13 us, profiles/r05b_trace_fused_one_counter.txt)
+constexpr int kTicketGroup = 32;
+// distance of the accumulators: 256 bytes for k <= 1024, so that the GTs' atomics spread over memory channels (64 x 392 832
+// anchors: 70.2 -> 65.5 us, profiles/r05d_ab_fused_stride.log; 16 slots per GT instead made the finalize pass read 64 KB per
+// workgroup: slower, profiles/r05e_ab_fused_slots.log)
+__host__ __device__ inline int64_t acc_stride(int64_t k) { return k <= 1024 ? 32 : 1; }
+__host__ __device__ inline int64_t col_tiles(int64_t n) { return (n + kBlock - 1) / kBlock; }
+__host__ __device__ inline int64_t ticket_groups(int64_t tiles) { return (tiles + kTicketGroup - 1) / kTicketGroup; }
+struct Layout {
+    int64_t tiles, chunks;               // column tiles of kBlock anchors; row chunks col_part has room for
+    int64_t row_part, ws_words;          // workspace: col_part at 0, row_part, the image's words
+    int64_t stride, counters;            // state: accumulator i at i * stride; counters[0]: top, [(1 + g) * kAccLine]: group g
+    int64_t count, state_words;          // state: the image's count line (batched), the image's words
+};
+// k rows (k_max of the batch), n columns in `tiles` = col_tiles(n) tiles (a finalize kernel has them as its grid), `chunks` row
+// chunks (the state does not depend on them)
+__host__ __device__ inline Layout layout(int64_t k, int64_t n, int64_t tiles, int64_t chunks, bool batched) {
+    Layout l;
+    l.tiles = tiles;
+    l.chunks = chunks;
+    l.row_part = chunks * n;
+    l.ws_words = l.row_part + k * l.tiles;
+    l.stride = acc_stride(k);
+    l.counters = (k * l.stride + kAccLine - 1) / kAccLine * kAccLine;
+    l.count = l.counters + (1 + ticket_groups(l.tiles)) * kAccLine;
+    l.state_words = l.count + (batched ? kAccLine : 0);
+    return l;
+}
+__host__ __device__ inline int64_t row_chunks(int64_t k, int64_t rows_per_wg) { return k > 0 ? (k + rows_per_wg - 1) / rows_per_wg : 0; }
 
+// ---- pairwise IoU for the assigner call pattern (few rows x many columns), closed-form core ----
 // One thread owns one column box (anchor); a workgroup covers 256 columns x up to 64 rows (GT).  Per-box cull
 // quantities are hoisted: rows live in LDS (broadcast reads), the column's in registers, so a culled pair costs
 // ~15 VALU instructions + one coalesced store of 0.  Survivors are (row, column) index pairs pushed on the wave's
-// LDS stack and finished 64 at a time on fully populated waves (same scheme as iou_aligned_compact_kernel).
-constexpr int kPwRows = 64;
+// LDS stack and finished 64 at a time on fully populated waves (same scheme as iou_aligned_compact_kernel); the < 64
+// leftovers of the four waves are merged once at the end and finished on as few, as full waves as possible (with 8 rows per
+// workgroup a wave stacks ~80 survivors: one full pass and a 16-lane one without the merge).
 // ARC: rbb_edge == 'arc' folded at compile time, as in the aligned kernels (with a run-time edge the chord / tangent forms
-// made this kernel 47 KB of code at 84 VGPRs).  The < 64 leftovers of the four waves are merged once at the end and
-// finished on as few, as full waves as possible (with 8 rows per workgroup a wave stacks ~80 survivors: one full pass and
-// a 16-lane one without the merge).
+// made this kernel 47 KB of code at 84 VGPRs).
 // OUT: bit 0 = write the m x n matrix; bit 1 = the assigner's reductions (max_iou_assigner.py:171-176 without
 // the matrix) — every finished survivor with IoU > 0 goes into the tile's per-column and per-row maxima in LDS (ds_max_u64 on
 // packed keys; culled pairs and survivors that finish to 0 are covered by the initial values: exact zeros), written once per
@@ -60,23 +112,13 @@ constexpr int kPwRows = 64;
 //   col_part[chunk][j]      max over the chunk's rows of (IoU[i][j], first row)         (chunk = blockIdx row chunk)
 //   row_part[i][tile]       max over the tile's 256 columns of (IoU[i][j], first column, global index = col_offset + j),
 //                           bit 0 = the value may occur at more than one column of the tile
-//   row_acc[i]              atomic max of the row's partials over ALL tiles (zero before the launch)
+//   row_acc[i * stride]     atomic max of the row's partials over ALL tiles (zero before the launch)
 // `ignore` (optional, one byte per column): columns whose overlaps the assigner sets to -1 (max_iou_assigner.py:115-126)
 // — they take part in no row maximum, their column maximum is (-1, row 0), and the matrix, when written, holds -1.
-// Per-GT accumulators of the fused assigner (the "state" buffer, zero between calls): one u64 per GT, 256 bytes apart for
-// k <= 1024 so that the GTs' atomics spread over memory channels (64 x 392 832 anchors: 70.2 -> 65.5 us, profiles/r05d_ab_fused_stride.log;
-// 16 slots per GT instead made the finalize pass read 64 KB per workgroup: slower, profiles/r05e_ab_fused_slots.log), followed by the
-// finalize pass's arrival counters: one per group of 32 column tiles + one for the groups, each on a 64-byte line (a single
-// counter serialises one returning atomic per workgroup: 1 535 tiles = +13 us, profiles/r05b_trace_fused_one_counter.txt).
-constexpr int kAccLine = 8;        // u64 words per counter line
-constexpr int kTicketGroup = 32;   // column tiles per first-level arrival counter
-__host__ __device__ inline int64_t acc_stride(int64_t k) { return k <= 1024 ? 32 : 1; }
-__host__ __device__ inline int64_t acc_words(int64_t k) { return (k * acc_stride(k) + kAccLine - 1) / kAccLine * kAccLine; }
-__host__ __device__ inline int64_t ticket_groups(int64_t tiles) { return (tiles + kTicketGroup - 1) / kTicketGroup; }
+constexpr int kPwRows = 64;    // rows of one workgroup at most
 constexpr int kRowSlots = 4;   // LDS copies of a row's running maximum (lane & 3): a pass holds a few rows, 64 lanes on one address serialise
 // The tile's work, shared by the single-image kernel and the batched one (anchor_targets_pairwise_kernel): column tile bx of
-// `tiles`, row chunk by; `stride` = distance of the per-GT accumulators in row_acc (acc_stride of the count the state was laid
-// out for).
+// `tiles`, row chunk by; `stride` = distance of the per-GT accumulators in row_acc (Layout::stride).
 template <int VARIANT, int DIM, bool ARC, int OUT>
 __device__ __forceinline__ void pairwise_compact_tile(const float* __restrict__ b1, int m, const float* __restrict__ b2, int n,
                                                       float* __restrict__ out, int mode, int edge_arg, int rows_per_wg,
@@ -210,29 +252,29 @@ __device__ __forceinline__ void pairwise_compact_tile(const float* __restrict__ 
     }
 }
 
-template <int VARIANT, int DIM, bool ARC, int OUT = 1>
-__global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void iou_pairwise_compact_kernel(const float* __restrict__ b1, int m,
-                                                                     const float* __restrict__ b2, int n,
-                                                                     float* __restrict__ out, int mode, int edge_arg,
-                                                                     int rows_per_wg,
-                                                                     const unsigned char* __restrict__ ignore = nullptr,
-                                                                     unsigned long long* __restrict__ col_part = nullptr,
-                                                                     unsigned long long* __restrict__ row_part = nullptr,
-                                                                     unsigned col_offset = 0,
-                                                                     unsigned long long* __restrict__ row_acc = nullptr) {
-    // dispatch order = LAST column tile first, all of its row chunks, then the tile before it: anchor grids end with their
-    // coarsest level (mmdet's AnchorGenerator walks the strides upwards) and their tiles grow heavier towards the end —
-    // the coarsest anchors survive the cull against nearly every GT and carry the longest serial chains of passes —, and
-    // the grid is larger than what is resident at once: dispatched last, the heaviest tiles started last.  Heaviest first:
-    // 64 x 98 208 anchors 21.7 -> 18.5 us, 64 x 392 832 47.2 -> 41.3 us with the rows-per-workgroup rule retuned for it
-    // (profiles/r03y_ab_pairwise*.log, r03z_ab_pairwise.log); tiles taken from both ends inwards instead: 20.2 / 42.1 us.
-    // A caller that lists the coarse level first gets the previous behaviour.  (tiles x chunks <= m n / 1024 + ..., and the
-    // m x n matrix has to fit the device: the linear id stays far below 2^32.  The same order from a transposed grid —
-    // chunks on x, tiles on y, no division — measured 1 % slower at 392 832 anchors: r04b_ab_pairwise_transposed.log.)
+// Dispatch order of the tiles = LAST column tile first, all of its row chunks, then the tile before it: anchor grids end with their
+// coarsest level (mmdet's AnchorGenerator walks the strides upwards) and their tiles grow heavier towards the end —
+// the coarsest anchors survive the cull against nearly every GT and carry the longest serial chains of passes —, and
+// the grid is larger than what is resident at once: dispatched last, the heaviest tiles started last.  Heaviest first:
+// 64 x 98 208 anchors 21.7 -> 18.5 us, 64 x 392 832 47.2 -> 41.3 us with the rows-per-workgroup rule retuned for it
+// (profiles/r03y_ab_pairwise*.log, r03z_ab_pairwise.log); tiles taken from both ends inwards instead: 20.2 / 42.1 us.
+// A caller that lists the coarse level first gets the previous behaviour.  (tiles x chunks <= m n / 1024 + ..., and the
+// m x n matrix has to fit the device: the linear id stays far below 2^32.  The same order from a transposed grid —
+// chunks on x, tiles on y, no division — measured 1 % slower at 392 832 anchors: r04b_ab_pairwise_transposed.log.)
+struct TileId { int bx, by; };   // column tile, row chunk
+__device__ __forceinline__ TileId tail_first_tile() {   // grid (tiles, chunks[, images])
     const unsigned lid = blockIdx.y * gridDim.x + blockIdx.x;
-    const int bx = (int)(gridDim.x - 1 - lid / gridDim.y), by = (int)(lid % gridDim.y);
+    return TileId{(int)(gridDim.x - 1 - lid / gridDim.y), (int)(lid % gridDim.y)};
+}
+
+template <int VARIANT, int DIM, bool ARC, int OUT>
+__global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void iou_pairwise_compact_kernel(const float* __restrict__ b1, int m,
+        const float* __restrict__ b2, int n, float* __restrict__ out, int mode, int edge_arg, int rows_per_wg,
+        const unsigned char* __restrict__ ignore, unsigned long long* __restrict__ col_part, unsigned long long* __restrict__ row_part,
+        unsigned col_offset, unsigned long long* __restrict__ row_acc) {
+    const TileId t = tail_first_tile();
     pairwise_compact_tile<VARIANT, DIM, ARC, OUT>(b1, m, b2, n, out, mode, edge_arg, rows_per_wg, ignore, col_part, row_part, col_offset,
-                                                  row_acc, bx, by, (int)gridDim.x, acc_stride(m));
+                                                  row_acc, t.bx, t.by, (int)gridDim.x, acc_stride(m));
 }
 
 // out[i*n + j]: consecutive lanes walk j (coalesced stores, b2 loads coalesced, b1 row is a broadcast).
@@ -332,30 +374,23 @@ __global__ __launch_bounds__(kBlock) void assign_rows_kernel(const unsigned long
 #pragma unroll
         for (int w = 1; w < kBlock / 64; w++) best = sm[w] > best ? sm[w] : best;
         gt_max[i] = unpack_max_val(best);
-        gt_argmax[i] = (int64_t)(0xffffffffu - (unsigned)best);
+        gt_argmax[i] = max_key_index(best);
     }
 }
 // C: thresholds + low-quality matching, one thread per column; later GTs overwrite earlier ones like the python loop
 __global__ __launch_bounds__(kBlock) void assign_finalize_kernel(const float* __restrict__ ov, int k, int64_t n,
-                                                                const float* __restrict__ max_ov,
-                                                                const int64_t* __restrict__ argmax_ov,
-                                                                const float* __restrict__ gt_max,
-                                                                const int64_t* __restrict__ gt_argmax, float pos_thr,
-                                                                float neg_lo, float neg_hi, float min_pos,
-                                                                int low_quality, int assign_all,
-                                                                const int64_t* __restrict__ gt_labels,
-                                                                int64_t* __restrict__ gt_inds,
-                                                                int64_t* __restrict__ labels) {
+        const float* __restrict__ max_ov, const int64_t* __restrict__ argmax_ov, const float* __restrict__ gt_max,
+        const int64_t* __restrict__ gt_argmax, float pos_thr, float neg_lo, float neg_hi, float min_pos, int low_quality, int assign_all,
+        const int64_t* __restrict__ gt_labels, int64_t* __restrict__ gt_inds, int64_t* __restrict__ labels) {
+    const Rule rule{pos_thr, neg_lo, neg_hi, min_pos, low_quality, assign_all};
     const int64_t jraw = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = jraw < n;
     const int64_t j = valid ? jraw : n - 1;   // lanes past the end stay in the wave (v_readlane below reads lanes 0..31) and store nothing
     const float m = max_ov[j];
     const int64_t am = argmax_ov[j];   // unconditional: one round trip for both, not two
-    int64_t a = -1;
-    if (m >= neg_lo && m < neg_hi) a = 0;
-    if (m >= pos_thr) a = am + 1;
-    if (low_quality) {
-        if (assign_all) {   // the column is re-read, 32 rows at a time: unconditional (clamped) loads, all issued before the first wait
+    int64_t a = threshold_index(m, am, rule);
+    if (rule.low_quality) {
+        if (rule.assign_all) {   // the column is re-read, 32 rows at a time: unconditional (clamped) loads, all issued before the first wait
             for (int r0 = 0; r0 < k; r0 += kAssignRows) {
                 float raw[kAssignRows];
 #pragma unroll
@@ -364,7 +399,7 @@ __global__ __launch_bounds__(kBlock) void assign_finalize_kernel(const float* __
                 // a row past k or below min_pos becomes NaN, which equals nothing
                 const int il = r0 + (int)(threadIdx.x & (kAssignRows - 1));
                 const float gl = gt_max[il < k ? il : k - 1];
-                const int gbits = __float_as_int((il < k && gl >= min_pos) ? gl : __builtin_nanf(""));
+                const int gbits = __float_as_int((il < k && gl >= rule.min_pos) ? gl : __builtin_nanf(""));
 #pragma unroll
                 for (int t = 0; t < kAssignRows; t++) {
                     const float g = __int_as_float(__builtin_amdgcn_readlane(gbits, t));
@@ -373,7 +408,7 @@ __global__ __launch_bounds__(kBlock) void assign_finalize_kernel(const float* __
             }
         } else {
             for (int i = 0; i < k; i++)
-                if (gt_max[i] >= min_pos && gt_argmax[i] == j) a = i + 1;
+                if (gt_max[i] >= rule.min_pos && gt_argmax[i] == j) a = i + 1;
         }
     }
     if (!valid) return;
@@ -382,17 +417,12 @@ __global__ __launch_bounds__(kBlock) void assign_finalize_kernel(const float* __
 }
 
 // ---- fused assigner (no k x n matrix): phase 2 and 3 behind iou_pairwise_compact_kernel<.., OUT & 2> ----
-// the rows' floor: what a row holds when no tile contributed (no ignore mask: IoU 0 at the shard's first column)
-__device__ __forceinline__ unsigned long long row_floor(bool has_ignore, unsigned col_offset) {
-    return has_ignore ? 0ull : pack_row_key(0.0f, col_offset);
-}
 // B' (the sharded form only): accumulators -> signed-order keys for the all-reduce; leaves the accumulators zero
 __global__ __launch_bounds__(kBlock) void assign_keys_from_acc_kernel(unsigned long long* __restrict__ row_acc, int k, bool has_ignore,
                                                                      unsigned col_offset, long long* __restrict__ gt_keys) {
     const unsigned long long fl = row_floor(has_ignore, col_offset);
     for (int i = threadIdx.x; i < k; i += kBlock) {
-        const unsigned long long a = row_acc[i * acc_stride(k)];
-        gt_keys[i] = key_to_signed((a > fl ? a : fl) & ~1ull);
+        gt_keys[i] = key_to_signed(acc_to_key(row_acc[i * acc_stride(k)], fl));
         row_acc[i * acc_stride(k)] = 0ull;
     }
 }
@@ -409,16 +439,13 @@ __global__ __launch_bounds__(kBlock) void assign_keys_from_acc_kernel(unsigned l
 // counter for the next call.  Otherwise they are `gt_keys` (all-reduced by the caller).
 // The column's share of C', common to the single-image kernel and the batched one (anchor_targets_finalize_kernel): returns
 // the assigned index (-1 / 0 / GT + 1) of column `tile * 256 + threadIdx.x` (clamped to n - 1 past the end) and its maximum
-// (m, am).  `stride`: distance of the per-GT accumulators (acc_stride of the count the state was laid out for).
+// (m, am).  `stride`: distance of the per-GT accumulators (Layout::stride).
 template <int VARIANT, int DIM, bool ARC, bool FROM_ACC>
-__device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict__ b1, int k, const float* __restrict__ b2, int n, int edge_arg,
-                                                         const unsigned long long* __restrict__ col_part, int chunks,
-                                                         const unsigned long long* __restrict__ row_part,
-                                                         const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc,
-                                                         const int64_t stride, bool has_ignore, unsigned col_offset, float pos_thr,
-                                                         float neg_lo, float neg_hi, float min_pos, int low_quality, int assign_all,
-                                                         float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax, const int tile,
-                                                         const int tiles, float& m_out, int64_t& am_out) {
+__device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict__ b1, int k, const float* __restrict__ b2, int n,
+        int edge_arg, const unsigned long long* __restrict__ col_part, int chunks, const unsigned long long* __restrict__ row_part,
+        const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc, const int64_t stride, bool has_ignore,
+        unsigned col_offset, const Rule& rule, float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax, const int tile, const int tiles,
+        float& m_out, int64_t& am_out) {
     const int edge = ARC ? (int)EDGE_ARC : edge_arg;
     const int lane = threadIdx.x & 63;
     const int jraw = tile * kBlock + threadIdx.x;
@@ -426,7 +453,7 @@ __device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict
     const int j = valid ? jraw : n - 1;
     const unsigned long long fl = row_floor(has_ignore, col_offset);
     auto row_key_of = [&](int i) -> unsigned long long {
-        if (FROM_ACC) { const unsigned long long a = row_acc[i * stride]; return (a > fl ? a : fl) & ~1ull; }
+        if (FROM_ACC) return acc_to_key(row_acc[i * stride], fl);
         return key_from_signed(gt_keys[i]);
     };
     if (tile == 0 && gt_max) {   // the per-GT results, decoded once
@@ -445,17 +472,15 @@ __device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict
         for (int t = 0; t < 8; t++) ck = v[t] > ck ? v[t] : ck;
     }
     const float m = unpack_max_val(ck);
-    const int64_t am = (int64_t)(0xffffffffu - (unsigned)ck);
+    const int64_t am = max_key_index(ck);
     const bool ign = m < 0.0f;   // only an ignored column has a negative maximum
-    int64_t a = -1;
-    if (m >= neg_lo && m < neg_hi) a = 0;
-    if (m >= pos_thr) a = am + 1;
-    if (low_quality) {
+    int64_t a = threshold_index(m, am, rule);
+    if (rule.low_quality) {
         int best = -1;
-        if (!assign_all) {
+        if (!rule.assign_all) {
             for (int i = 0; i < k; i++) {
                 const unsigned long long key = row_key_of(i);
-                if (unpack_max_val(key) >= min_pos && row_key_index(key) == col_offset + (unsigned)j) best = i;
+                if (unpack_max_val(key) >= rule.min_pos && row_key_index(key) == col_offset + (unsigned)j) best = i;
             }
         } else {
             float a5[5] = {0.0f, 0.0f, 1.0f, 1.0f, 0.0f};
@@ -466,7 +491,7 @@ __device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict
                 const int il = r0 + lane, ic = il < k ? il : k - 1;
                 const unsigned long long gk = row_key_of(ic);
                 const float g = unpack_max_val(gk);
-                const bool on = il < k && g >= min_pos;
+                const bool on = il < k && g >= rule.min_pos;
                 const unsigned long long zero = __builtin_amdgcn_ballot_w64(on && g == 0.0f);
                 const unsigned long long neg = __builtin_amdgcn_ballot_w64(on && g == -1.0f);
                 const unsigned long long pk = row_part[(int64_t)ic * tiles + tile];
@@ -525,60 +550,41 @@ __device__ __forceinline__ bool finalize_arrive(unsigned long long* __restrict__
     __syncthreads();
     return ticket != 0;
 }
+// what the last arrival does for the next call: the image's accumulators (the k rows it used) and every counter back to zero
+__device__ __forceinline__ void reset_image_state(unsigned long long* __restrict__ acc, int k, const Layout& l) {
+    for (int i = threadIdx.x; i < k; i += kBlock) acc[i * l.stride] = 0ull;
+    for (int i = threadIdx.x; i <= (int)ticket_groups(l.tiles); i += kBlock) acc[l.counters + (int64_t)i * kAccLine] = 0ull;
+}
 template <int VARIANT, int DIM, bool ARC, bool FROM_ACC>
-__global__ __launch_bounds__(kBlock) void assign_fused_finalize_kernel(const float* __restrict__ b1, int k, const float* __restrict__ b2, int n,
-                                                                      int edge_arg, const unsigned long long* __restrict__ col_part, int chunks,
-                                                                      const unsigned long long* __restrict__ row_part,
-                                                                      const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc,
-                                                                      bool has_ignore, unsigned col_offset,
-                                                                      float pos_thr, float neg_lo, float neg_hi, float min_pos,
-                                                                      int low_quality, int assign_all,
-                                                                      const int64_t* __restrict__ gt_labels,
-                                                                      float* __restrict__ max_ov, int64_t* __restrict__ argmax_ov,
-                                                                      float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax,
-                                                                      int64_t* __restrict__ gt_inds, int64_t* __restrict__ labels) {
+__global__ __launch_bounds__(kBlock) void assign_fused_finalize_kernel(const float* __restrict__ b1, int k, const float* __restrict__ b2,
+        int n, int edge_arg, const unsigned long long* __restrict__ col_part, int chunks, const unsigned long long* __restrict__ row_part,
+        const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc, bool has_ignore, unsigned col_offset,
+        float pos_thr, float neg_lo, float neg_hi, float min_pos, int low_quality, int assign_all, const int64_t* __restrict__ gt_labels,
+        float* __restrict__ max_ov, int64_t* __restrict__ argmax_ov, float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax,
+        int64_t* __restrict__ gt_inds, int64_t* __restrict__ labels) {
+    const Rule rule{pos_thr, neg_lo, neg_hi, min_pos, low_quality, assign_all};
     const int tile = blockIdx.x, tiles = gridDim.x;
     const int j = tile * kBlock + threadIdx.x;
+    const Layout l = layout(k, n, tiles, chunks, false);
     float m;
     int64_t am;
     const int64_t a = fused_finalize_column<VARIANT, DIM, ARC, FROM_ACC>(b1, k, b2, n, edge_arg, col_part, chunks, row_part, gt_keys, row_acc,
-                                                                         acc_stride(k), has_ignore, col_offset, pos_thr, neg_lo, neg_hi, min_pos,
-                                                                         low_quality, assign_all, gt_max, gt_argmax, tile, tiles, m, am);
+                                                                         l.stride, has_ignore, col_offset, rule, gt_max, gt_argmax, tile, tiles, m, am);
     if (j < n) {
         max_ov[j] = m;
         if (argmax_ov) argmax_ov[j] = am;
         gt_inds[j] = a;
         if (labels) labels[j] = a > 0 ? gt_labels[a - 1] : -1;
     }
-    if (FROM_ACC) {   // every read of the accumulators above has returned (its value was used); the last arrival zeroes them and
-        // every counter for the next call
-        unsigned long long* counters = row_acc + acc_words(k);
-        if (finalize_arrive(counters, tile, tiles)) {
-            for (int i = threadIdx.x; i < k; i += kBlock) row_acc[i * acc_stride(k)] = 0ull;
-            for (int i = threadIdx.x; i <= (int)ticket_groups(tiles); i += kBlock) counters[(int64_t)i * kAccLine] = 0ull;
-        }
-    }
+    // every read of the accumulators above has returned (its value was used)
+    if (FROM_ACC && finalize_arrive(row_acc + l.counters, tile, tiles)) reset_image_state(row_acc, k, l);
 }
 
 
 // ---- anchor targets for a minibatch (sph2pob_anchor_targets_f32): the fused assigner with the image as a grid dimension and
 // the target construction of mmdet's AnchorHead._get_targets_single (anchor_head.py:254-285, PseudoSampler) as the finalize
 // pass's epilogue.  Two launches for B images; every image owns a slice of the workspace and of the state, laid out for k_max
-// rows whatever its own count. ----
-// per-image workspace: col_part[chunks_max][n] then row_part[k_max][tiles]; per-image state: the single-image layout for k_max
-// rows (accumulators, 1 + groups arrival counters) + one line for the packed (positives | negatives << 32) count; behind the
-// last image one line: [0] images that finished, [1] sum of max(positives, 1)
-struct BatchLayout { int64_t ws_words, col_words, state_words, acc, chunks_max, tiles; };
-__host__ __device__ inline BatchLayout batch_layout(int64_t k_max, int64_t n, int64_t rpw) {
-    BatchLayout l;
-    l.tiles = (n + kBlock - 1) / kBlock;
-    l.chunks_max = k_max > 0 ? (k_max + rpw - 1) / rpw : 0;
-    l.col_words = l.chunks_max * n;
-    l.ws_words = l.col_words + k_max * l.tiles;
-    l.acc = acc_words(k_max);
-    l.state_words = l.acc + (2 + ticket_groups(l.tiles)) * kAccLine;
-    return l;
-}
+// rows whatever its own count (Layout). ----
 // rows of image b in the concatenated GT: offsets clamped to [0, K], the count to [0, k_max] (later rows are not assigned)
 struct ImageRows { int64_t lo; int k; };
 __device__ __forceinline__ ImageRows image_rows(const int64_t* __restrict__ gt_offsets, int b, int64_t K, int k_max) {
@@ -594,47 +600,40 @@ __device__ __forceinline__ int image_chunks(int k, int rows_per_wg) { return (k 
 // grid (tiles, chunks_max, B): per image the tail-first order of iou_pairwise_compact_kernel; workgroups past the image's own
 // chunks (all of them for an image without GT) exit at once
 template <int VARIANT, int DIM, bool ARC>
-__global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void anchor_targets_pairwise_kernel(const float* __restrict__ gt, const int64_t* __restrict__ gt_offsets,
-                                                                                  int64_t K, int k_max, const float* __restrict__ anchors, int n,
-                                                                                  int edge_arg, int rows_per_wg,
-                                                                                  unsigned long long* __restrict__ workspace,
-                                                                                  unsigned long long* __restrict__ state) {
+__global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void anchor_targets_pairwise_kernel(const float* __restrict__ gt,
+        const int64_t* __restrict__ gt_offsets, int64_t K, int k_max, const float* __restrict__ anchors, int n, int edge_arg,
+        int rows_per_wg, unsigned long long* __restrict__ workspace, unsigned long long* __restrict__ state) {
     const int b = blockIdx.z;
-    const unsigned lid = blockIdx.y * gridDim.x + blockIdx.x;
-    const int bx = (int)(gridDim.x - 1 - lid / gridDim.y), by = (int)(lid % gridDim.y);
+    const TileId t = tail_first_tile();
     const ImageRows im = image_rows(gt_offsets, b, K, k_max);
     const int chunks = image_chunks(im.k, rows_per_wg);
-    if (by >= chunks) return;
-    const BatchLayout l = batch_layout(k_max, n, rows_per_wg);
+    if (t.by >= chunks) return;
+    const Layout l = layout(k_max, n, col_tiles(n), row_chunks(k_max, rows_per_wg), true);
     unsigned long long* col_part = workspace + b * l.ws_words;
     pairwise_compact_tile<VARIANT, DIM, ARC, 2>(gt + im.lo * DIM, im.k, anchors, n, nullptr, (int)MODE_IOU, edge_arg, (im.k + chunks - 1) / chunks,
-                                                nullptr, col_part, col_part + l.col_words, 0u, state + b * l.state_words, bx, by, (int)l.tiles,
-                                                acc_stride(k_max));
+                                                nullptr, col_part, col_part + l.row_part, 0u, state + b * l.state_words, t.bx, t.by, (int)l.tiles,
+                                                l.stride);
 }
 
 struct TargetOut {
     int64_t* gt_inds; float* max_ov; int64_t* assigned_labels; int64_t* labels; float* label_weights; float* bbox_targets;
     float* bbox_weights; int64_t* num_pos; int64_t* num_neg; float* avg_factor;
 };
-// grid (tiles, B).  The targets of column j of image b from its assigned index a (g > 0 positive, 0 negative, -1 neither):
-//   labels gt_labels[a - 1] (0 without labels) | num_classes; label_weights 1 (pos_weight on positives when > 0) | 0 for -1;
-//   bbox_targets the GT box, or its deltas w.r.t. the anchor (ENCODE: sph2pob_coder::encode_one, the coder kernel's function)
-//   | 0; bbox_weights 1 | 0.
+// grid (tiles, B).  The targets of column j of image b from its assigned index: sph2pob_assign::target_row, stored here.
 // Counts: one ballot per wave into LDS, one packed atomic per workgroup into the image's state line; the image's last
 // workgroup writes num_pos / num_neg and adds max(num_pos, 1) to the batch's sum, the batch's last image writes avg_factor.
 // Each of these atomics returns before the arrival that publishes it is issued (finalize_arrive's `extra`).
 template <int VARIANT, int DIM, bool ARC, bool ENCODE>
-__global__ __launch_bounds__(kBlock) void anchor_targets_finalize_kernel(const float* __restrict__ gt, const int64_t* __restrict__ gt_labels,
-                                                                        const int64_t* __restrict__ gt_offsets, int64_t K, int k_max,
-                                                                        const float* __restrict__ anchors, int n, int edge_arg, int rows_per_wg,
-                                                                        unsigned long long* __restrict__ workspace,
-                                                                        unsigned long long* __restrict__ state, float pos_thr, float neg_lo,
-                                                                        float neg_hi, float min_pos, int low_quality, int assign_all,
-                                                                        int64_t num_classes, float pos_weight, sph2pob_coder::Norm nm, TargetOut o) {
+__global__ __launch_bounds__(kBlock) void anchor_targets_finalize_kernel(const float* __restrict__ gt,
+        const int64_t* __restrict__ gt_labels, const int64_t* __restrict__ gt_offsets, int64_t K, int k_max,
+        const float* __restrict__ anchors, int n, int edge_arg, int rows_per_wg, unsigned long long* __restrict__ workspace,
+        unsigned long long* __restrict__ state, float pos_thr, float neg_lo, float neg_hi, float min_pos, int low_quality, int assign_all,
+        int64_t num_classes, float pos_weight, sph2pob_coder::Norm nm, TargetOut o) {
     __shared__ unsigned wg_count[2];
+    const Rule rule{pos_thr, neg_lo, neg_hi, min_pos, low_quality, assign_all};
     const int tile = blockIdx.x, tiles = gridDim.x, b = blockIdx.y, images = gridDim.y;
     const ImageRows im = image_rows(gt_offsets, b, K, k_max);
-    const BatchLayout l = batch_layout(k_max, n, rows_per_wg);
+    const Layout l = layout(k_max, n, tiles, row_chunks(k_max, rows_per_wg), true);
     const float* gt_b = gt + im.lo * DIM;
     unsigned long long* acc = state + b * l.state_words;
     if (threadIdx.x < 2) wg_count[threadIdx.x] = 0u;
@@ -643,39 +642,32 @@ __global__ __launch_bounds__(kBlock) void anchor_targets_finalize_kernel(const f
     if (im.k > 0) {
         const unsigned long long* col_part = workspace + b * l.ws_words;
         a = fused_finalize_column<VARIANT, DIM, ARC, true>(gt_b, im.k, anchors, n, edge_arg, col_part, image_chunks(im.k, rows_per_wg),
-                                                           col_part + l.col_words, nullptr, acc, acc_stride(k_max), false, 0u, pos_thr, neg_lo,
-                                                           neg_hi, min_pos, low_quality, assign_all, nullptr, nullptr, tile, tiles, m, am);
+                                                           col_part + l.row_part, nullptr, acc, l.stride, false, 0u, rule, nullptr, nullptr, tile,
+                                                           tiles, m, am);
     }
     const int j = tile * kBlock + threadIdx.x;
     const bool valid = j < n, pos = valid && a > 0, neg = valid && a == 0;
     if (valid) {
         const int64_t e = (int64_t)b * n + j;
-        const int64_t lab = (pos && gt_labels) ? gt_labels[im.lo + a - 1] : 0;
+        float g[5], p[5];
+        if (pos) {
+            load_box<DIM>(gt_b, a - 1, g);
+            if constexpr (ENCODE) load_box<DIM>(anchors, j, p);
+        }
+        const sph2pob_assign::TargetRow r = sph2pob_assign::target_row<DIM, ENCODE>(a, p, g, gt_labels ? gt_labels + im.lo : nullptr, num_classes,
+                                                                                    pos_weight, nm);
         o.gt_inds[e] = a;
         o.max_ov[e] = m;
-        if (o.assigned_labels) o.assigned_labels[e] = pos ? lab : -1;
-        o.labels[e] = pos ? lab : num_classes;
-        o.label_weights[e] = pos ? (pos_weight <= 0.0f ? 1.0f : pos_weight) : (neg ? 1.0f : 0.0f);
-        float t[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (pos) {
-            float g[5];
-            load_box<DIM>(gt_b, a - 1, g);
-            if constexpr (ENCODE) {
-                float p[5];
-                load_box<DIM>(anchors, j, p);
-                sph2pob_coder::encode_one<DIM>(p, g, nm, t);
-            } else {
-#pragma unroll
-                for (int c = 0; c < DIM; c++) t[c] = g[c];
-            }
-        }
-        const float w = pos ? 1.0f : 0.0f;
+        if (o.assigned_labels) o.assigned_labels[e] = pos ? r.label : -1;
+        o.labels[e] = r.label;
+        o.label_weights[e] = r.label_weight;
+        const float w = r.box_weight;
         if constexpr (DIM == 4) {   // one 16-byte store per row
-            reinterpret_cast<float4*>(o.bbox_targets)[e] = make_float4(t[0], t[1], t[2], t[3]);
+            reinterpret_cast<float4*>(o.bbox_targets)[e] = make_float4(r.t[0], r.t[1], r.t[2], r.t[3]);
             reinterpret_cast<float4*>(o.bbox_weights)[e] = make_float4(w, w, w, w);
         } else {
 #pragma unroll
-            for (int c = 0; c < DIM; c++) { o.bbox_targets[e * DIM + c] = t[c]; o.bbox_weights[e * DIM + c] = w; }
+            for (int c = 0; c < DIM; c++) { o.bbox_targets[e * DIM + c] = r.t[c]; o.bbox_weights[e * DIM + c] = w; }
         }
     }
     __syncthreads();   // wg_count is zero
@@ -685,17 +677,15 @@ __global__ __launch_bounds__(kBlock) void anchor_targets_finalize_kernel(const f
         if (mn) atomicAdd(&wg_count[1], (unsigned)__popcll(mn));
     }
     __syncthreads();
-    unsigned long long* counters = acc + l.acc;
-    unsigned long long* count = counters + (1 + ticket_groups(tiles)) * kAccLine;
+    unsigned long long* count = acc + l.count;
     unsigned dep = 0u;
     if (threadIdx.x == 0) {
         const unsigned long long prev = __hip_atomic_fetch_add(count, (unsigned long long)wg_count[0] | ((unsigned long long)wg_count[1] << 32),
                                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("" : "+v"(dep) : "v"(prev));   // dep stays 0, and is not known before the count's atomic has returned
     }
-    if (finalize_arrive(counters, tile, tiles, dep)) {   // the image's last workgroup: its state back to zero, its counts out
-        for (int i = threadIdx.x; i < im.k; i += kBlock) acc[i * acc_stride(k_max)] = 0ull;
-        for (int i = threadIdx.x; i <= (int)ticket_groups(tiles); i += kBlock) counters[(int64_t)i * kAccLine] = 0ull;
+    if (finalize_arrive(acc + l.counters, tile, tiles, dep)) {   // the image's last workgroup: its state back to zero, its counts out
+        reset_image_state(acc, im.k, l);
         if (threadIdx.x == 0) {
             const unsigned long long c = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(count, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -724,8 +714,7 @@ __global__ __launch_bounds__(kBlock) void anchor_targets_finalize_kernel(const f
 // anchors 49.1 us at 8, 47.0 at 12, 42.6 at 16, 41.1 at 22, 42.0 at 32 => about 4 096 workgroups, at least 8 rows, chunks of
 // equal size
 static int64_t pairwise_rows_per_wg(int64_t m, int64_t n) {
-    const int64_t col_tiles = (n + kBlock - 1) / kBlock;
-    int64_t rpw = g_pw_rows > 0 ? g_pw_rows : (m * col_tiles) / 4096;
+    int64_t rpw = g_pw_rows > 0 ? g_pw_rows : (m * col_tiles(n)) / 4096;
     if (rpw < 8 && g_pw_rows <= 0) rpw = 8;
     if (rpw < 4) rpw = 4;
     if (rpw > kPwRows) rpw = kPwRows;
@@ -733,131 +722,117 @@ static int64_t pairwise_rows_per_wg(int64_t m, int64_t n) {
     if (g_pw_rows <= 0) rpw = (m + (m + rpw - 1) / rpw - 1) / ((m + rpw - 1) / rpw);   // 64 rows: 23 -> 3 chunks of 22 / 22 / 20
     return rpw;
 }
-struct PairwiseLaunch {
-    const float* b1; int64_t m; const float* b2; int64_t n; float* out; int mode, edge, angle; hipStream_t s; bool fast = true;
-    template <int V, int D> int run() {
-        if (fast && V < 2 && angle == SPH2POB_ANGLE_EQUATOR && n < ((int64_t)1 << 31) - kBlock && m <= (int64_t)65535 * 4 &&
-            !g_no_compact) {
-            const int64_t col_tiles = (n + kBlock - 1) / kBlock;
-            const int64_t rpw = pairwise_rows_per_wg(m, n);
-            dim3 grid((unsigned)col_tiles, (unsigned)((m + rpw - 1) / rpw));
-            if (edge == SPH2POB_EDGE_ARC)
-                hipLaunchKernelGGL((iou_pairwise_compact_kernel<V >= 2 ? 0 : V, D, true, 1>), grid, dim3(kBlock), 0, s, b1, (int)m, b2, (int)n,
-                                   out, mode, edge, (int)rpw, (const unsigned char*)nullptr, (unsigned long long*)nullptr,
-                                   (unsigned long long*)nullptr, 0u, (unsigned long long*)nullptr);
-            else
-                hipLaunchKernelGGL((iou_pairwise_compact_kernel<V >= 2 ? 0 : V, D, false, 1>), grid, dim3(kBlock), 0, s, b1, (int)m, b2, (int)n,
-                                   out, mode, edge, (int)rpw, (const unsigned char*)nullptr, (unsigned long long*)nullptr,
-                                   (unsigned long long*)nullptr, 0u, (unsigned long long*)nullptr);
-            return launch_status();
-        }
-        // grid.y is limited to 65535 rows per launch: walk the rows in slabs
-        const int64_t kMaxRows = 65535;
-        for (int64_t r0 = 0; r0 < m; r0 += kMaxRows) {
-            int64_t rows = m - r0 < kMaxRows ? m - r0 : kMaxRows;
-            dim3 grid((unsigned)((n + kBlock - 1) / kBlock), (unsigned)rows);
-            if (fast && V < 2 && angle == SPH2POB_ANGLE_EQUATOR)
-                hipLaunchKernelGGL((iou_pairwise_kernel<V >= 2 ? 0 : V, D, true>), grid, dim3(kBlock), 0, s, b1 + r0 * D, rows,
-                                   b2, n, out + r0 * n, mode, edge, angle);
-            else if (V >= 5 && fast)
-                hipLaunchKernelGGL((iou_pairwise_kernel<V >= 5 ? V : 5, D, true>), grid, dim3(kBlock), 0, s, b1 + r0 * D, rows,
-                                   b2, n, out + r0 * n, mode, edge, angle);
-            else
-                hipLaunchKernelGGL((iou_pairwise_kernel<V, D, false>), grid, dim3(kBlock), 0, s, b1 + r0 * D, rows, b2, n,
-                                   out + r0 * n, mode, edge, angle);
-            int rc = launch_status();
-            if (rc) return rc;
-        }
-        return SPH2POB_OK;
-    }
-};
-// the fused assigner's two halves (closed-form standard / efficient only: the kernels that carry the reductions)
-struct AssignWs { unsigned long long *row_acc, *col_part, *row_part; int64_t chunks, tiles; };
-static AssignWs assign_ws(void* workspace, void* state, int64_t k, int64_t n) {
-    AssignWs w;
-    w.tiles = (n + kBlock - 1) / kBlock;
-    const int64_t rpw = pairwise_rows_per_wg(k, n);
-    w.chunks = (k + rpw - 1) / rpw;
-    w.row_acc = (unsigned long long*)state;   // k accumulators + the arrival counter: zero between calls
-    w.col_part = (unsigned long long*)workspace;
-    w.row_part = w.col_part + w.chunks * n;
-    return w;
-}
 // the batched form: rows per workgroup from the rows the whole batch can hold (an image has at most k_max, the batch K)
 static int64_t batch_rows_per_wg(int64_t images, int64_t K, int64_t k_max, int64_t n) {
     const int64_t total = images * k_max < K ? images * k_max : K;
     int64_t rpw = pairwise_rows_per_wg(total, n);
     return rpw > k_max ? k_max : rpw;
 }
-struct AnchorTargetsLaunch {
-    const float* anchors; int64_t n; const float* gt; const int64_t* gt_labels; const int64_t* gt_offsets; int64_t images, K, k_max; int edge;
-    float pos, neg_lo, neg_hi, min_pos; int low_quality, assign_all; int64_t num_classes; float pos_weight; bool encode; sph2pob_coder::Norm nm;
-    TargetOut o; void* workspace; void* state; hipStream_t s; bool fast = true;
+// the single-image fused route's buffers for rpw = pairwise_rows_per_wg(k, n)
+static Layout fused_layout(int64_t k, int64_t n, int64_t rpw) { return layout(k, n, col_tiles(n), row_chunks(k, rpw), false); }
+
+// iou_pairwise_compact_kernel in its three forms: the matrix alone (`red` == nullptr: the pairwise entry), the reductions, or both
+struct Reductions { const unsigned char* ignore; unsigned long long *col_part, *row_part; unsigned col_offset; unsigned long long* row_acc; };
+template <int V, int D>
+static void launch_compact(const float* b1, int64_t m, const float* b2, int64_t n, float* out, int mode, int edge, int64_t rpw,
+                           const Reductions* red, hipStream_t s) {
+    const dim3 grid((unsigned)col_tiles(n), (unsigned)row_chunks(m, rpw));
+    const Reductions r = red ? *red : Reductions{};
+    with_flag(edge == SPH2POB_EDGE_ARC, [&](auto arc) {
+        auto go = [&](auto out_bits) {
+            hipLaunchKernelGGL((iou_pairwise_compact_kernel<V, D, decltype(arc)::value, decltype(out_bits)::value>), grid, dim3(kBlock), 0, s, b1,
+                               (int)m, b2, (int)n, out, mode, edge, (int)rpw, r.ignore, r.col_part, r.row_part, r.col_offset, r.row_acc);
+        };
+        if (!red) go(std::integral_constant<int, 1>{});
+        else if (out) go(std::integral_constant<int, 3>{});
+        else go(std::integral_constant<int, 2>{});
+    });
+}
+// standard / efficient as they are, every other variant as 0: a launcher that does not serve the others (the entry points'
+// checks refuse them) names its kernels with this and instantiates nothing for them
+constexpr int closed_form(int v) { return v >= 2 ? 0 : v; }
+struct PairwiseLaunch {
+    const float* b1; int64_t m; const float* b2; int64_t n; float* out; int mode, edge, angle; hipStream_t s; bool fast = true;
     template <int V, int D> int run() {
-        if constexpr (V >= 2) return SPH2POB_ERR_OPTION;
-        else {
-            if (!fast) return SPH2POB_ERR_OPTION;
-            const int64_t rpw = k_max > 0 ? batch_rows_per_wg(images, K, k_max, n) : 1;
-            const BatchLayout l = batch_layout(k_max, n, rpw);
-            unsigned long long *ws = (unsigned long long*)workspace, *st = (unsigned long long*)state;
-            const bool arc = edge == SPH2POB_EDGE_ARC;
-            if (k_max > 0) {
-                dim3 grid((unsigned)l.tiles, (unsigned)l.chunks_max, (unsigned)images);
-#define SPH_AT(ARC) hipLaunchKernelGGL((anchor_targets_pairwise_kernel<V, D, ARC>), grid, dim3(kBlock), 0, s, gt, gt_offsets, K, (int)k_max, anchors, \
-                                       (int)n, edge, (int)rpw, ws, st)
-                if (arc) SPH_AT(true); else SPH_AT(false);
-#undef SPH_AT
-            }
-            dim3 grid((unsigned)l.tiles, (unsigned)images);
-#define SPH_AT(ARC, ENC) hipLaunchKernelGGL((anchor_targets_finalize_kernel<V, D, ARC, ENC>), grid, dim3(kBlock), 0, s, gt, gt_labels, gt_offsets, K, \
-                                            (int)k_max, anchors, (int)n, edge, (int)rpw, ws, st, pos, neg_lo, neg_hi, min_pos, low_quality, assign_all,  \
-                                            num_classes, pos_weight, nm, o)
-            if (arc) { if (encode) SPH_AT(true, true); else SPH_AT(true, false); }
-            else { if (encode) SPH_AT(false, true); else SPH_AT(false, false); }
-#undef SPH_AT
+        const bool closed = fast && V < 2 && angle == SPH2POB_ANGLE_EQUATOR;
+        if (closed && n < ((int64_t)1 << 31) - kBlock && m <= (int64_t)65535 * 4 && !g_no_compact) {
+            launch_compact<closed_form(V), D>(b1, m, b2, n, out, mode, edge, pairwise_rows_per_wg(m, n), nullptr, s);
             return launch_status();
         }
+        // grid.y is limited to 65535 rows per launch: walk the rows in slabs
+        const int64_t kMaxRows = 65535;
+        for (int64_t r0 = 0; r0 < m; r0 += kMaxRows) {
+            int64_t rows = m - r0 < kMaxRows ? m - r0 : kMaxRows;
+            auto go = [&](auto variant, auto fast_core) {
+                hipLaunchKernelGGL((iou_pairwise_kernel<decltype(variant)::value, D, decltype(fast_core)::value>), dim3((unsigned)col_tiles(n), (unsigned)rows),
+                                   dim3(kBlock), 0, s, b1 + r0 * D, rows, b2, n, out + r0 * n, mode, edge, angle);
+            };
+            if (closed) go(std::integral_constant<int, closed_form(V)>{}, std::true_type{});
+            else if (V >= 5 && fast) go(std::integral_constant<int, (V >= 5 ? V : 5)>{}, std::true_type{});
+            else go(std::integral_constant<int, V>{}, std::false_type{});
+            int rc = launch_status();
+            if (rc) return rc;
+        }
+        return SPH2POB_OK;
     }
 };
+// the fused assigner's two halves and the batched route: closed-form standard / efficient only (the kernels that carry the reductions)
 struct AssignReduceLaunch {
     const float* b1; int64_t m; const float* b2; int64_t n; float* out; int edge; const unsigned char* ignore; unsigned col_offset;
     long long* gt_keys /* NULL: leave the keys in the accumulators */; void* workspace; void* state; hipStream_t s; bool fast = true;
     template <int V, int D> int run() {
-        if constexpr (V >= 2) return SPH2POB_ERR_OPTION;
-        else {
-            if (!fast) return SPH2POB_ERR_OPTION;
-            const AssignWs w = assign_ws(workspace, state, m, n);
-            const int64_t rpw = pairwise_rows_per_wg(m, n);
-            dim3 grid((unsigned)w.tiles, (unsigned)w.chunks);
-#define SPH_AR(ARC, OUT) hipLaunchKernelGGL((iou_pairwise_compact_kernel<V, D, ARC, OUT>), grid, dim3(kBlock), 0, s, b1, (int)m, b2, (int)n, out, \
-                                           (int)MODE_IOU, edge, (int)rpw, ignore, w.col_part, w.row_part, col_offset, w.row_acc)
-            if (edge == SPH2POB_EDGE_ARC) { if (out) SPH_AR(true, 3); else SPH_AR(true, 2); }
-            else { if (out) SPH_AR(false, 3); else SPH_AR(false, 2); }
-#undef SPH_AR
-            if (gt_keys)
-                hipLaunchKernelGGL(assign_keys_from_acc_kernel, dim3(1), dim3(kBlock), 0, s, w.row_acc, (int)m, ignore != nullptr, col_offset, gt_keys);
-            return launch_status();
-        }
+        if (V >= 2 || !fast) return SPH2POB_ERR_OPTION;
+        const int64_t rpw = pairwise_rows_per_wg(m, n);
+        const Layout l = fused_layout(m, n, rpw);
+        unsigned long long *ws = (unsigned long long*)workspace, *acc = (unsigned long long*)state;
+        const Reductions red{ignore, ws, ws + l.row_part, col_offset, acc};
+        launch_compact<closed_form(V), D>(b1, m, b2, n, out, (int)MODE_IOU, edge, rpw, &red, s);
+        if (gt_keys)
+            hipLaunchKernelGGL(assign_keys_from_acc_kernel, dim3(1), dim3(kBlock), 0, s, acc, (int)m, ignore != nullptr, col_offset, gt_keys);
+        return launch_status();
     }
 };
 struct AssignFinalizeLaunch {
     const float* b1; int64_t m; const float* b2; int64_t n; int edge; unsigned col_offset; const long long* gt_keys /* NULL: the accumulators */;
-    bool has_ignore;
-    float pos, neg_lo, neg_hi, min_pos; int low_quality, assign_all; const int64_t* gt_labels; float* max_ov; int64_t* argmax_ov;
+    bool has_ignore; Rule rule; const int64_t* gt_labels; float* max_ov; int64_t* argmax_ov;
     float* gt_max; int64_t* gt_argmax; int64_t* gt_inds; int64_t* labels; void* workspace; void* state; hipStream_t s; bool fast = true;
     template <int V, int D> int run() {
-        if constexpr (V >= 2) return SPH2POB_ERR_OPTION;
-        else {
-            if (!fast) return SPH2POB_ERR_OPTION;
-            const AssignWs w = assign_ws(workspace, state, m, n);
-#define SPH_AF(ARC, ACC) hipLaunchKernelGGL((assign_fused_finalize_kernel<V, D, ARC, ACC>), dim3((unsigned)w.tiles), dim3(kBlock), 0, s, b1, (int)m, b2, \
-                                           (int)n, edge, w.col_part, (int)w.chunks, w.row_part, gt_keys, w.row_acc, has_ignore, col_offset, pos, neg_lo,  \
-                                           neg_hi, min_pos, low_quality, assign_all, gt_labels, max_ov, argmax_ov, gt_max, gt_argmax, gt_inds, labels)
-            if (edge == SPH2POB_EDGE_ARC) { if (gt_keys) SPH_AF(true, false); else SPH_AF(true, true); }
-            else { if (gt_keys) SPH_AF(false, false); else SPH_AF(false, true); }
-#undef SPH_AF
-            return launch_status();
-        }
+        if (V >= 2 || !fast) return SPH2POB_ERR_OPTION;
+        const Layout l = fused_layout(m, n, pairwise_rows_per_wg(m, n));
+        const unsigned long long* ws = (const unsigned long long*)workspace;
+        with_flag(edge == SPH2POB_EDGE_ARC, [&](auto arc) {
+            with_flag(gt_keys == nullptr, [&](auto from_acc) {
+                hipLaunchKernelGGL((assign_fused_finalize_kernel<closed_form(V), D, decltype(arc)::value, decltype(from_acc)::value>),
+                                   dim3((unsigned)l.tiles), dim3(kBlock), 0, s, b1, (int)m, b2, (int)n, edge, ws, (int)l.chunks, ws + l.row_part, gt_keys,
+                                   (unsigned long long*)state, has_ignore, col_offset, rule.pos_thr, rule.neg_lo, rule.neg_hi, rule.min_pos,
+                                   rule.low_quality, rule.assign_all, gt_labels, max_ov, argmax_ov, gt_max, gt_argmax, gt_inds, labels);
+            });
+        });
+        return launch_status();
+    }
+};
+struct AnchorTargetsLaunch {
+    const float* anchors; int64_t n; const float* gt; const int64_t* gt_labels; const int64_t* gt_offsets; int64_t images, K, k_max; int edge;
+    Rule rule; int64_t num_classes; float pos_weight; bool encode; sph2pob_coder::Norm nm;
+    TargetOut o; void* workspace; void* state; hipStream_t s; bool fast = true;
+    template <int V, int D> int run() {
+        if (V >= 2 || !fast) return SPH2POB_ERR_OPTION;
+        const int64_t rpw = k_max > 0 ? batch_rows_per_wg(images, K, k_max, n) : 1;
+        const Layout l = layout(k_max, n, col_tiles(n), row_chunks(k_max, rpw), true);
+        unsigned long long *ws = (unsigned long long*)workspace, *st = (unsigned long long*)state;
+        with_flag(edge == SPH2POB_EDGE_ARC, [&](auto arc) {
+            if (k_max > 0)
+                hipLaunchKernelGGL((anchor_targets_pairwise_kernel<closed_form(V), D, decltype(arc)::value>),
+                                   dim3((unsigned)l.tiles, (unsigned)l.chunks, (unsigned)images), dim3(kBlock), 0, s, gt, gt_offsets, K, (int)k_max,
+                                   anchors, (int)n, edge, (int)rpw, ws, st);
+            with_flag(encode, [&](auto enc) {
+                hipLaunchKernelGGL((anchor_targets_finalize_kernel<closed_form(V), D, decltype(arc)::value, decltype(enc)::value>),
+                                   dim3((unsigned)l.tiles, (unsigned)images), dim3(kBlock), 0, s, gt, gt_labels, gt_offsets, K, (int)k_max, anchors,
+                                   (int)n, edge, (int)rpw, ws, st, rule.pos_thr, rule.neg_lo, rule.neg_hi, rule.min_pos, rule.low_quality,
+                                   rule.assign_all, num_classes, pos_weight, nm, o);
+            });
+        });
+        return launch_status();
     }
 };
 
@@ -879,10 +854,8 @@ int sph2pob_iou_pairwise_f32(const float* b1, int64_t m, const float* b2, int64_
 }
 
 
-int64_t sph2pob_assign_workspace_bytes(int64_t k, int64_t n) {
-    int64_t nparts = ((n + kBlock - 1) / kBlock) * (kBlock / 64);
-    return k * nparts * 8;
-}
+// the matrix epilogue's workspace: one partial per row and wave of assign_cols_kernel
+int64_t sph2pob_assign_workspace_bytes(int64_t k, int64_t n) { return k * (col_tiles(n) * (kBlock / 64)) * 8; }
 
 int sph2pob_assign_f32(const float* overlaps, int64_t k, int64_t n, float pos_iou_thr, float neg_iou_lo,
                        float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
@@ -894,7 +867,7 @@ int sph2pob_assign_f32(const float* overlaps, int64_t k, int64_t n, float pos_io
         !workspace || (assigned_labels && !gt_labels))
         return SPH2POB_ERR_NULL;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
+    const unsigned blocks = (unsigned)col_tiles(n);
     const int nparts = (int)(blocks * (kBlock / 64));
     unsigned long long* partial = (unsigned long long*)workspace;
     hipLaunchKernelGGL(assign_cols_kernel, dim3(blocks), dim3(kBlock), 0, s, overlaps, (int)k, n, max_overlaps,
@@ -908,28 +881,16 @@ int sph2pob_assign_f32(const float* overlaps, int64_t k, int64_t n, float pos_io
 }
 
 int64_t sph2pob_iou_assign_workspace_bytes(int64_t k, int64_t n) {
-    if (k <= 0 || n <= 0) return 0;
-    const AssignWs w = assign_ws(nullptr, nullptr, k, n);
-    return (w.chunks * n + k * w.tiles) * 8;
+    return k > 0 && n > 0 ? fused_layout(k, n, pairwise_rows_per_wg(k, n)).ws_words * 8 : 0;
 }
 int64_t sph2pob_iou_assign_state_bytes(int64_t k, int64_t n) {
-    return k > 0 && n > 0 ? (acc_words(k) + (1 + ticket_groups((n + kBlock - 1) / kBlock)) * kAccLine) * 8 : 0;
-}
-
-static int assign_fused_check(int64_t k, int64_t n, int box_dim, int variant, int edge, int64_t col_offset) {
-    int rc = check_common(box_dim, variant, edge, 0);
-    if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT || (variant & SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (k <= 0 || n <= 0 || n >= ((int64_t)1 << 31) - kBlock || k > (int64_t)65535 * 4 || col_offset < 0 ||
-        col_offset + n > (int64_t)0x7ffffffe)
-        return SPH2POB_ERR_SIZE;
-    return SPH2POB_OK;
+    return k > 0 && n > 0 ? layout(k, n, col_tiles(n), 0, false).state_words * 8 : 0;
 }
 
 int sph2pob_iou_assign_reduce_f32(const float* gt, int64_t k, const float* boxes, int64_t n, int box_dim, int variant, int edge,
                                   const unsigned char* ignore, int64_t col_offset, float* overlaps, int64_t* gt_keys,
                                   void* workspace, void* state, void* stream) {
-    int rc = assign_fused_check(k, n, box_dim, variant, edge, col_offset);
+    int rc = sph2pob_assign::assign_fused_check(check_common(box_dim, variant, edge, 0), k, n, variant, col_offset);
     if (rc) return rc;
     if (!gt || !boxes || !gt_keys || !workspace || !state) return SPH2POB_ERR_NULL;
     return dispatch(variant, box_dim, AssignReduceLaunch{gt, k, boxes, n, overlaps, edge, ignore, (unsigned)col_offset,
@@ -942,13 +903,13 @@ int sph2pob_iou_assign_finalize_f32(const float* gt, int64_t k, const float* box
                                     const int64_t* gt_labels, float* max_overlaps, int64_t* argmax_overlaps,
                                     float* gt_max_overlaps, int64_t* gt_argmax_overlaps, int64_t* assigned_gt_inds,
                                     int64_t* assigned_labels, void* workspace, void* stream) {
-    int rc = assign_fused_check(k, n, box_dim, variant, edge, col_offset);
+    int rc = sph2pob_assign::assign_fused_check(check_common(box_dim, variant, edge, 0), k, n, variant, col_offset);
     if (rc) return rc;
     if (!gt || !boxes || !gt_keys || !workspace || !max_overlaps || !assigned_gt_inds || (assigned_labels && !gt_labels))
         return SPH2POB_ERR_NULL;
     return dispatch(variant, box_dim,
-                    AssignFinalizeLaunch{gt, k, boxes, n, edge, (unsigned)col_offset, (const long long*)gt_keys, false, pos_iou_thr,
-                                         neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all, gt_labels,
+                    AssignFinalizeLaunch{gt, k, boxes, n, edge, (unsigned)col_offset, (const long long*)gt_keys, false,
+                                         Rule{pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all}, gt_labels,
                                          max_overlaps, argmax_overlaps, gt_max_overlaps, gt_argmax_overlaps, assigned_gt_inds,
                                          assigned_labels, workspace, nullptr, (hipStream_t)stream});
 }
@@ -958,26 +919,26 @@ int sph2pob_iou_assign_f32(const float* gt, int64_t k, const float* boxes, int64
                            float min_pos_iou, int match_low_quality, int gt_max_assign_all, const int64_t* gt_labels,
                            float* max_overlaps, int64_t* argmax_overlaps, float* gt_max_overlaps, int64_t* gt_argmax_overlaps,
                            int64_t* assigned_gt_inds, int64_t* assigned_labels, void* workspace, void* state, void* stream) {
-    int rc = assign_fused_check(k, n, box_dim, variant, edge, 0);
+    int rc = sph2pob_assign::assign_fused_check(check_common(box_dim, variant, edge, 0), k, n, variant, 0);
     if (rc) return rc;
     if (!gt || !boxes || !workspace || !state || !max_overlaps || !assigned_gt_inds || (assigned_labels && !gt_labels)) return SPH2POB_ERR_NULL;
     // two launches: the per-GT keys stay in the workspace's accumulators, the finalize pass reads and clears them
     rc = dispatch(variant, box_dim, AssignReduceLaunch{gt, k, boxes, n, overlaps, edge, ignore, 0u, nullptr, workspace, state, (hipStream_t)stream});
     if (rc) return rc;
     return dispatch(variant, box_dim,
-                    AssignFinalizeLaunch{gt, k, boxes, n, edge, 0u, nullptr, ignore != nullptr, pos_iou_thr, neg_iou_lo, neg_iou_hi,
-                                         min_pos_iou, match_low_quality, gt_max_assign_all, gt_labels, max_overlaps, argmax_overlaps,
-                                         gt_max_overlaps, gt_argmax_overlaps, assigned_gt_inds, assigned_labels, workspace, state,
-                                         (hipStream_t)stream});
+                    AssignFinalizeLaunch{gt, k, boxes, n, edge, 0u, nullptr, ignore != nullptr,
+                                         Rule{pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all}, gt_labels,
+                                         max_overlaps, argmax_overlaps, gt_max_overlaps, gt_argmax_overlaps, assigned_gt_inds, assigned_labels,
+                                         workspace, state, (hipStream_t)stream});
 }
 
 int64_t sph2pob_anchor_targets_workspace_bytes(int64_t num_images, int64_t num_gt, int64_t k_max, int64_t n) {
     if (num_images <= 0 || num_gt <= 0 || k_max <= 0 || n <= 0) return 0;
-    return num_images * batch_layout(k_max, n, batch_rows_per_wg(num_images, num_gt, k_max, n)).ws_words * 8;
+    return num_images * layout(k_max, n, col_tiles(n), row_chunks(k_max, batch_rows_per_wg(num_images, num_gt, k_max, n)), true).ws_words * 8;
 }
 int64_t sph2pob_anchor_targets_state_bytes(int64_t num_images, int64_t k_max, int64_t n) {
     if (num_images <= 0 || k_max < 0 || n <= 0) return 0;
-    return (num_images * batch_layout(k_max, n, 1).state_words + kAccLine) * 8;
+    return (num_images * layout(k_max, n, col_tiles(n), 0, true).state_words + kAccLine) * 8;   // + the batch's line behind the last image
 }
 
 int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
@@ -987,20 +948,16 @@ int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt,
                                int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
                                float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
                                float* avg_factor, void* workspace, void* state, void* stream) {
-    int rc = check_common(box_dim, variant, edge, 0);
+    int rc = sph2pob_assign::anchor_targets_check(check_common(box_dim, variant, edge, 0), anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt,
+                                                  k_max, variant, assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets,
+                                                  bbox_weights, num_pos, num_neg, avg_factor, true, workspace, state);
     if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT || (variant & SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (num_images <= 0 || num_images > 65535 || num_gt < 0 || k_max < 0 || k_max > num_gt || k_max > (int64_t)65535 * 4 || n <= 0 ||
-        n >= ((int64_t)1 << 31) - kBlock || num_gt > kMaxElems)
-        return SPH2POB_ERR_SIZE;
-    if (!anchors || !gt_offsets || (num_gt > 0 && !gt) || (k_max > 0 && !workspace) || !state || !assigned_gt_inds || !max_overlaps ||
-        (assigned_labels && !gt_labels && num_gt > 0) || !labels || !label_weights || !bbox_targets || !bbox_weights || !num_pos || !num_neg || !avg_factor)
-        return SPH2POB_ERR_NULL;
     const TargetOut o{assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg, avg_factor};
     return dispatch(variant, box_dim,
-                    AnchorTargetsLaunch{anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt, k_max, edge, pos_iou_thr, neg_iou_lo, neg_iou_hi,
-                                        min_pos_iou, match_low_quality, gt_max_assign_all, num_classes, pos_weight, encode != 0,
-                                        sph2pob_coder::make_norm(means_host, stds_host, box_dim), o, workspace, state, (hipStream_t)stream});
+                    AnchorTargetsLaunch{anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt, k_max, edge,
+                                        Rule{pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all}, num_classes,
+                                        pos_weight, encode != 0, sph2pob_coder::make_norm(means_host, stds_host, box_dim), o, workspace, state,
+                                        (hipStream_t)stream});
 }
 
 

@@ -25,6 +25,7 @@
 #include "sph2pob_unbiased.hpp"
 #include "sph2pob_coder.hpp"
 #include "sph2pob_get_bboxes.hpp"
+#include "sph2pob_assign.hpp"
 #include "sph2pob_focal.hpp"
 #include "sph2pob_bbox_loss.hpp"
 #include "sph2pob_delta_loss.hpp"
@@ -502,6 +503,7 @@ int sph2pob_assign_f32_cpu(const float* ov, int64_t k, int64_t n, float pos_iou_
     if (!ov || !max_overlaps || !argmax_overlaps || !gt_max_overlaps || !gt_argmax_overlaps || !assigned_gt_inds ||
         (assigned_labels && !gt_labels))
         return SPH2POB_ERR_NULL;
+    const sph2pob_assign::Rule rule{pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all};
     parallel_for(n, 4096, [&](int64_t lo, int64_t hi) {   // columns: max / first argmax over the rows, thresholds
         for (int64_t j = lo; j < hi; j++) {
             float best = ov[j];
@@ -512,10 +514,7 @@ int sph2pob_assign_f32_cpu(const float* ov, int64_t k, int64_t n, float pos_iou_
             }
             max_overlaps[j] = best;
             argmax_overlaps[j] = bi;
-            int64_t a = -1;
-            if (best >= neg_iou_lo && best < neg_iou_hi) a = 0;
-            if (best >= pos_iou_thr) a = bi + 1;
-            assigned_gt_inds[j] = a;
+            assigned_gt_inds[j] = sph2pob_assign::threshold_index(best, bi, rule);
         }
     });
     parallel_for(k, 1, [&](int64_t lo, int64_t hi) {      // rows: max / first argmax over the columns
@@ -557,18 +556,14 @@ int sph2pob_anchor_targets_f32_cpu(const float* anchors, int64_t n, const float*
                                    int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
                                    float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
                                    float* avg_factor, void* workspace, void* state, void*) {
-    (void)workspace; (void)state;
-    int rc = check_common(box_dim, variant, edge, 0);
+    int rc = sph2pob_assign::anchor_targets_check(check_common(box_dim, variant, edge, 0), anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt,
+                                                  k_max, variant, assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets,
+                                                  bbox_weights, num_pos, num_neg, avg_factor, false, workspace, state);
     if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT || (variant & SPH2POB_FLAG_REFERENCE_ORDER)) return SPH2POB_ERR_OPTION;
-    if (num_images <= 0 || num_images > 65535 || num_gt < 0 || k_max < 0 || k_max > num_gt || k_max > (int64_t)65535 * 4 || n <= 0 ||
-        n >= ((int64_t)1 << 31) - 256 || num_gt > kMaxElems)
-        return SPH2POB_ERR_SIZE;
-    if (!anchors || !gt_offsets || (num_gt > 0 && !gt) || !assigned_gt_inds || !max_overlaps || (assigned_labels && !gt_labels && num_gt > 0) || !labels ||
-        !label_weights || !bbox_targets || !bbox_weights || !num_pos || !num_neg || !avg_factor)
-        return SPH2POB_ERR_NULL;
     const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
     const int dim = box_dim;
+    namespace A = sph2pob_assign;   // the kernel's element function, for this call's (dim, encode)
+    const auto row = dim == 4 ? (encode ? A::target_row<4, true> : A::target_row<4, false>) : (encode ? A::target_row<5, true> : A::target_row<5, false>);
     std::vector<float> ov, gt_max;
     std::vector<int64_t> argmax(n), gt_argmax;
     int64_t total = 0;
@@ -593,18 +588,12 @@ int sph2pob_anchor_targets_f32_cpu(const float* anchors, int64_t n, const float*
         int64_t np = 0, nn = 0;
         for (int64_t j = 0; j < n; j++) {
             const int64_t a = gi[j], e = b * n + j;
-            const bool pos = a > 0;
-            np += pos; nn += a == 0;
-            labels[e] = pos ? (gt_labels ? gt_labels[lo + a - 1] : 0) : num_classes;
-            label_weights[e] = pos ? (pos_weight <= 0.0f ? 1.0f : pos_weight) : (a == 0 ? 1.0f : 0.0f);
-            float t[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            if (pos) {
-                const float* g = gt_b + (a - 1) * dim;
-                if (!encode) for (int c = 0; c < dim; c++) t[c] = g[c];
-                else if (dim == 4) sph2pob_coder::encode_one<4>(anchors + j * 4, g, nm, t);
-                else sph2pob_coder::encode_one<5>(anchors + j * 5, g, nm, t);
-            }
-            for (int c = 0; c < dim; c++) { bbox_targets[e * dim + c] = t[c]; bbox_weights[e * dim + c] = pos ? 1.0f : 0.0f; }
+            np += a > 0; nn += a == 0;
+            const A::TargetRow r = row(a, anchors + j * dim, a > 0 ? gt_b + (a - 1) * dim : nullptr, gt_labels ? gt_labels + lo : nullptr,
+                                       num_classes, pos_weight, nm);
+            labels[e] = r.label;
+            label_weights[e] = r.label_weight;
+            for (int c = 0; c < dim; c++) { bbox_targets[e * dim + c] = r.t[c]; bbox_weights[e * dim + c] = r.box_weight; }
         }
         num_pos[b] = np; num_neg[b] = nn;
         total += std::max<int64_t>(np, 1);

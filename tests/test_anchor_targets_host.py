@@ -3,6 +3,8 @@ per-image SphMaxIoUAssigner.assign + a torch transcription of _get_targets_singl
 inputs), against the reference's recorded assignment for the full scene (tests/golden/assign.npz part b), and the argument
 checks of the C ABI without a GPU."""
 import ctypes
+import os
+import shutil
 
 import numpy as np
 import pytest
@@ -155,6 +157,124 @@ def test_argument_validation_without_gpu(twin):
     assert lib.sph2pob_anchor_targets_workspace_bytes(0, 8, 8, 100) == 0 and lib.sph2pob_anchor_targets_state_bytes(2, 8, 0) == 0
     assert lib.sph2pob_anchor_targets_workspace_bytes(8, 512, 64, 98208) >= 8 * (98208 + 64 * 384) * 8
     assert lib.sph2pob_anchor_targets_state_bytes(8, 64, 98208) >= 8 * 64 * 8
+    # The device entry and the twin answer every bad call alike.  A value just inside a bound is shown to pass the size check by
+    # the NULL error of a missing `anchors` behind it (nothing is dereferenced); the value just outside fails with the size error.
+    dev, host = _lib.lib().sph2pob_anchor_targets_f32, _lib.host_lib().sph2pob_anchor_targets_f32_cpu
+    big, most = (1 << 31) - 256, 65535 * 4
+    grid = [(dict(images=1, null=(0,)), -1), (dict(images=0, null=(0,)), -4), (dict(images=65535, null=(0,)), -1),
+            (dict(images=65536, null=(0,)), -4),
+            (dict(num_gt=0, k_max=0, null=(0,)), -1), (dict(num_gt=-1, k_max=0, null=(0,)), -4), (dict(num_gt=-1, k_max=-1, null=(0,)), -4),
+            (dict(k_max=0, null=(0,)), -1), (dict(k_max=-1, null=(0,)), -4), (dict(k_max=8, null=(0,)), -1), (dict(k_max=9, null=(0,)), -4),
+            (dict(num_gt=most, k_max=most, null=(0,)), -1), (dict(num_gt=most + 1, k_max=most + 1, null=(0,)), -4),
+            (dict(num_gt=most + 1, k_max=most, null=(0,)), -1),
+            (dict(n=1, null=(0,)), -1), (dict(n=0, null=(0,)), -4), (dict(n=-1, null=(0,)), -4),
+            (dict(n=big - 1, null=(0,)), -1), (dict(n=big, null=(0,)), -4),          # the bound leaves room for one tile of 256 columns
+            (dict(num_gt=1 << 38, null=(0,)), -1), (dict(num_gt=(1 << 38) + 1, null=(0,)), -4)]
+    grid += [(dict(null=(i,)), -1) for i in (0, 2, 4, 22, 23, 25, 26, 27, 28, 29, 30, 31)]        # each required pointer in turn
+    grid += [(dict(null=(3,)), -1), (dict(null=(3, 24, 0)), -1), (dict(num_gt=0, k_max=0, null=(2, 3, 0)), -1)]
+    # both unsupported kinds of variant (past the closed forms; reference order), and what is answered first: dim, option, size, NULL
+    grid += [(dict(variant=v), -3) for v in (2, 3, 4, 5, 6, 7, 0x100, 0x101, 0x300, 0x400, 0x800)]
+    grid += [(dict(variant=v, box_dim=5), -2) for v in (2, 3, 4)] + [(dict(variant=v, box_dim=5), -3) for v in (5, 6, 0x100, 0x101)]
+    grid += [(dict(variant=5, images=0, null=(0,)), -3), (dict(variant=0x100, n=0), -3), (dict(box_dim=3, variant=5, images=0), -2),
+             (dict(box_dim=6, variant=0x100), -2), (dict(edge=-1, images=0), -3), (dict(edge=3, null=(0,)), -3), (dict(edge=2, null=(0,)), -1),
+             (dict(variant=1, null=(0,)), -1), (dict(variant=0x201, null=(0,)), -1), (dict(variant=1, box_dim=5, n=0), -4), (dict(images=0, null=(0, 2, 4)), -4)]
+    for kw, want in grid:
+        assert dev(*_args(ptr, **kw)) == host(*_args(ptr, **kw)) == want, kw
+    for i in (32, 33):      # workspace / state: required by the device entry alone (the twin would run, so it is not called)
+        assert dev(*_args(ptr, null=(i,))) == -1
+
+
+# (k, n, sph2pob_assign_workspace_bytes, sph2pob_iou_assign_workspace_bytes, sph2pob_iou_assign_state_bytes) and
+# (B, K, k_max, n, sph2pob_anchor_targets_workspace_bytes, sph2pob_anchor_targets_state_bytes), recorded from the build before
+# the assigner's buffers got one layout function: callers cache these buffers across both routes, so every size stays what it was
+SINGLE_SIZES = (
+    (1, 1, 32, 16, 384),
+    (1, 256, 32, 2056, 384),
+    (1, 257, 64, 2072, 384),
+    (1, 8192, 1024, 65792, 384),
+    (1, 8193, 1056, 65808, 448),
+    (1, 98208, 12288, 788736, 1088),
+    (1, 392832, 49120, 3154936, 3392),
+    (8, 1, 256, 72, 2176),
+    (8, 256, 256, 2112, 2176),
+    (8, 257, 512, 2184, 2176),
+    (8, 8192, 8192, 67584, 2176),
+    (8, 8193, 8448, 67656, 2240),
+    (8, 98208, 98304, 810240, 2880),
+    (8, 392832, 392960, 3240896, 5184),
+    (64, 1, 2048, 576, 16512),
+    (64, 256, 2048, 16896, 16512),
+    (64, 257, 4096, 17472, 16512),
+    (64, 8192, 65536, 540672, 16512),
+    (64, 8193, 67584, 541248, 16576),
+    (64, 98208, 786432, 6481920, 17216),
+    (64, 392832, 3143680, 10213888, 19520),
+    (1024, 1, 32768, 9216, 262272),
+    (1024, 256, 32768, 270336, 262272),
+    (1024, 257, 65536, 279552, 262272),
+    (1024, 8192, 1048576, 8650752, 262272),
+    (1024, 8193, 1081344, 8659968, 262336),
+    (1024, 98208, 12582912, 15716352, 262976),
+    (1024, 392832, 50298880, 62857216, 265280),
+    (1025, 1, 32800, 9232, 8384),
+    (1025, 256, 32800, 272392, 8384),
+    (1025, 257, 65600, 281624, 8384),
+    (1025, 8192, 1049600, 8716544, 8384),
+    (1025, 8193, 1082400, 8725776, 8448),
+    (1025, 98208, 12595200, 16505088, 9088),
+    (1025, 392832, 50348000, 66012152, 11392),
+    (262140, 1, 8388480, 2130408, 2097280),
+    (262140, 256, 8388480, 10618848, 2097280),
+    (262140, 257, 16776960, 12615616, 2097280),
+    (262140, 8192, 268431360, 335543296, 2097280),
+    (262140, 8193, 276819840, 337673184, 2097344),
+    (262140, 98208, 3221176320, 4023373824, 2097984),
+    (262140, 392832, 12876316800, 16091398176, 2100288),
+    (0, 100, 0, 0, 0),
+    (5, 0, 0, 0, 0),
+    (0, 0, 0, 0, 0),
+    (-1, 100, -32, 0, 0),
+    (5, -3, 0, 0, 0),
+    (-2, -2, 0, 0, 0),
+)
+BATCHED_SIZES = (
+    (1, 1, 1, 1, 16, 512),
+    (1, 64, 64, 256, 16896, 16640),
+    (2, 1025, 1025, 300, 652000, 16960),
+    (2, 2049, 1025, 257, 563248, 16960),
+    (8, 512, 64, 98208, 14143488, 138304),
+    (8, 100, 64, 98208, 51855360, 138304),
+    (8, 512, 64, 392832, 31428608, 156736),
+    (8, 64, 8, 8192, 540672, 17984),
+    (8, 64, 8, 8193, 541248, 18496),
+    (4, 4096, 1024, 8193, 9470976, 1049664),
+    (3, 262140, 262140, 257, 37846848, 6292096),
+    (65535, 8, 1, 1, 1048560, 29359744),
+    (2, 8, 0, 100, 0, 448),
+    (0, 8, 8, 100, 0, 0),
+    (2, 0, 0, 100, 0, 448),
+    (2, 8, 8, 0, 0, 0),
+    (-1, 8, 8, 100, 0, 0),
+    (2, -8, 8, 100, 0, 4544),
+    (2, 8, -1, 100, 0, 0),
+    (2, 8, 8, -100, 0, 0),
+)
+
+
+def test_size_entries_return_the_recorded_bytes(tmp_path, monkeypatch):
+    lib = _lib.lib()
+    if 'SPH2POB_PW_ROWS' in os.environ:    # the rows-per-workgroup knob (read once at load) changes the workspace: a copy loaded without it
+        monkeypatch.delenv('SPH2POB_PW_ROWS')
+        lib = ctypes.CDLL(shutil.copy(_lib.LIB_PATH, str(tmp_path / 'libsph2pob_default_rows.so')))
+        for name in ('sph2pob_assign_workspace_bytes', 'sph2pob_iou_assign_workspace_bytes', 'sph2pob_iou_assign_state_bytes',
+                     'sph2pob_anchor_targets_workspace_bytes', 'sph2pob_anchor_targets_state_bytes'):
+            getattr(lib, name).argtypes, getattr(lib, name).restype = _lib.SIGNATURES[name], ctypes.c_int64
+    for k, n, matrix_ws, fused_ws, fused_state in SINGLE_SIZES:
+        got = (lib.sph2pob_assign_workspace_bytes(k, n), lib.sph2pob_iou_assign_workspace_bytes(k, n), lib.sph2pob_iou_assign_state_bytes(k, n))
+        assert got == (matrix_ws, fused_ws, fused_state), (k, n, got)
+    for b, kk, k_max, n, ws, state in BATCHED_SIZES:
+        got = (lib.sph2pob_anchor_targets_workspace_bytes(b, kk, k_max, n), lib.sph2pob_anchor_targets_state_bytes(b, k_max, n))
+        assert got == (ws, state), (b, kk, k_max, n, got)
 
 
 def test_unsupported_options_name_the_per_image_api():

@@ -102,6 +102,23 @@ def test_ties_and_a_gt_that_overlaps_nothing(S, dim):
     assert int((out.gt_inds[0] == 4).sum()) > 100   # the zero path: the GT that overlaps nothing takes the anchors no later GT claims
 
 
+def test_more_gt_than_the_accumulator_stride_switch_beside_an_empty_image(S):
+    """k_max = 1 025: the per-GT accumulators lie one word apart (256 bytes apart up to 1 024); image 1 has no GT."""
+    from sph_retina_amd import _torch_glue as G
+    gts, labs = draw_gt([1025, 0], 4, seed=21)
+    g = torch.Generator().manual_seed(22)
+    v = torch.rand((300, 4), generator=g)
+    anchors = torch.stack([v[:, 0] * 360, 20 + v[:, 1] * 140, 5 + v[:, 2] * 85, 5 + v[:, 3] * 85], 1).cuda()
+    a = make_assigner(S, 'sph2pob_standard_iou', 4)
+    off = torch.tensor([0, 1025, 1025], dtype=torch.int64).cuda()
+    out = S.sph_anchor_targets(anchors, torch.cat(gts), torch.cat(labs), off, assigner=a, num_classes=37, k_max=1025)
+    _, state = G.assign_workspace(anchors.device, 0, 0)
+    assert not state.any(), 'the state buffer must read all-zero after a call'
+    check_batch(out, a, anchors, gts, labs, 37)
+    assert int(out.num_pos[0]) > 0 and int(out.num_pos[1]) == 0 and int(out.num_neg[1]) == 300
+    assert not state.any()
+
+
 def test_state_is_left_zero_and_workspace_reuse(S, anchors4):
     from sph_retina_amd import _lib, _torch_glue as G
     lib = _lib.lib()

@@ -142,10 +142,14 @@ def _scene(k, n, dim, seed):
 
 
 @pytest.mark.parametrize('k,n,dim', [(1, 1, 4), (3, 70, 4), (64, 1000, 4), (17, 4099, 5), (200, 333, 4), (33, 65, 5),
-                                     (65, 2000, 4), (9, 256, 4), (8, 513, 4)])
+                                     (65, 2000, 4), (9, 256, 4), (8, 513, 4),
+                                     # either side of the per-GT accumulators' stride switch (k = 1 024); 32 and 33 column
+                                     # tiles: one full group of arrival counters, and one full group plus a group of one
+                                     (1024, 300, 4), (1025, 300, 5), (3, 8192, 4), (3, 8193, 5)])
 @pytest.mark.parametrize('variant', ['standard', 'efficient'])
 def test_fused_equals_matrix_route_bit_for_bit(A, k, n, dim, variant):
     import sph_retina_amd as S
+    from sph_retina_amd import _torch_glue as G
     gt, boxes, labels = _scene(k, n, dim, 1000 * k + n)
     ign = (torch.rand(n, generator=torch.Generator().manual_seed(n)) < 0.1).cuda()
     for ignore in (None, ign, torch.ones_like(ign)):
@@ -156,6 +160,13 @@ def test_fused_equals_matrix_route_bit_for_bit(A, k, n, dim, variant):
             res3, ov3, ex3 = A.fused_assign(gt, boxes, labels, variant, ignore_mask=ignore, return_overlaps=True,
                                             return_extras=True, **kw)
             _same(res, ex, res3, ex3, ov, ov3)
+    if k >= 1024 or n >= 8192:   # the same buffers twice: equal results, and the cached state reads all-zero after a call
+        first = A.fused_assign(gt, boxes, labels, variant, return_extras=True, **CFGS[0])
+        _, state = G.assign_workspace(boxes.device, 0, 0)
+        assert not state.any(), 'the state buffer must read all-zero after a call'
+        again = A.fused_assign(gt, boxes, labels, variant, return_extras=True, **CFGS[0])
+        _same(*first, *again)
+        assert G.assign_workspace(boxes.device, 0, 0)[1] is state and not state.any()
     if k > 3 and n > 600:   # the scene holds what it claims
         ov, res, ex = _matrix_route(A, S, gt, boxes, labels, variant, None, **CFGS[0])
         assert float(ov[3].max()) == 0.0 and int((res.gt_inds == 4).sum()) > n // 2   # zero-overlap GT takes every free box

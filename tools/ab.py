@@ -15,6 +15,7 @@ Workloads (all through the C ABI, buffers allocated once, HIP events around `--l
   pairwise  sph2pob_iou_pairwise_f32 on configs[3] (64 GT x the ERP anchor grids)
   assign    pairwise + sph2pob_assign_f32 (the matrix route) on the same
   fused     sph2pob_iou_assign_f32 (no matrix) on the same
+  anchor_targets  sph2pob_anchor_targets_f32 (the batched route): 8 images x 64 GT x the 98 208 anchors of the 512 x 1024 ERP
   loss      sph2pob_loss_fwd_grad_f32 + final sum + grad_scale, 1 M nearby RBFoV pairs, CIoU (configs[2])
   nms       sph2pob_nms_segmented_f32 on 5 000 sorted boxes x 37 classes and on one class of 5 000
   bnms      sph2pob_batched_nms_f32 (unsorted input, no host work) on the same two scenes
@@ -86,9 +87,9 @@ def load_arms(specs, tmp):
     return arms
 
 
-def _gt64(torch):
+def _gt64(torch, k=64):
     g = torch.Generator().manual_seed(0)
-    u = torch.rand((64, 4), generator=g)
+    u = torch.rand((k, 4), generator=g)
     return torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85], 1).cuda()
 
 
@@ -147,6 +148,23 @@ def workloads(args, torch, G):
                     return rc
                 return launch, ([ov] if args.workload == 'pairwise' else [ov, mo, amo, gm, gam, gi, lab])
             yield f'{args.workload} 64 x {n}', make
+    elif args.workload == 'anchor_targets':
+        from tools.bench_configs import retina_anchors
+        anchors, B, km = retina_anchors(512, 1024), 8, 64
+        n, K = anchors.size(0), B * km
+        gt, labels = _gt64(torch, K), (torch.arange(K) % 37).cuda()
+        off = (torch.arange(B + 1) * km).cuda()
+
+        def make(lib):
+            i64, f32 = dict(dtype=torch.int64, device='cuda'), dict(dtype=torch.float32, device='cuda')
+            o = [torch.empty((B, n), **i64), torch.empty((B, n), **f32), torch.empty((B, n), **i64), torch.empty((B, n), **i64),
+                 torch.empty((B, n), **f32), torch.empty((B, n, 4), **f32), torch.empty((B, n, 4), **f32), torch.empty(B, **i64),
+                 torch.empty(B, **i64), torch.empty(1, **f32)]
+            ws = torch.empty(lib.sph2pob_anchor_targets_workspace_bytes(B, K, km, n) // 8, **i64)
+            state = torch.zeros(lib.sph2pob_anchor_targets_state_bytes(B, km, n) // 8, **i64)
+            return (lambda: lib.sph2pob_anchor_targets_f32(G.ptr(anchors), n, G.ptr(gt), G.ptr(labels), G.ptr(off), B, K, km, 4, 0, 0, 0.5, 0.0, 0.4, 0.0,
+                                                           1, 1, 37, -1.0, 0, None, None, *[G.ptr(t) for t in o], G.ptr(ws), G.ptr(state), st)), o
+        yield f'anchor_targets {B} x {km} x {n}', make
     elif args.workload == 'loss':
       for n in ([int(v) for v in args.pairs.split(',')] if args.pairs != '1000000' else [1_000_000]):
           g = torch.Generator().manual_seed(2)
