@@ -349,8 +349,24 @@ SPH_DEV CullParts fast_cull_parts(const float (&g)[5], const float (&p)[5], int 
     // bound — with 2 v_max3_u32 + 2 v_max_u32 + 2 compares for the eight coordinates.  A pair with a coordinate out of
     // range (or NaN) is never culled: the finishing stage clamps it exactly like the reference does.  (Round 1 clamped
     // all eight values here instead, NaN-propagating: 12 v_minimum3 / v_maximum3.)
-    const unsigned mg = max3_u32(float_bits(g[1]), float_bits(g[2]), float_bits(g[3]));
-    const unsigned mp = max3_u32(float_bits(p[1]), float_bits(p[2]), float_bits(p[3]));
+    // ARC edges (not CHORD): the four extents are NOT tested (`in_sizes` is the test of the two colatitudes alone: 1 v_max_u32 +
+    // 1 compare, as for theta).  An extent enters the cull only through d = w^2 + h^2 in R^2 below, and the bound decreases in
+    // R^2, so a raw extent may stand in for the one the finishing stage uses (jitter_spherical's clamp into [e, 180 - e]
+    // degrees, e <= 2.5e-4) whenever its square is not smaller, or smaller by no more than the margin already allows:
+    //   * above 180: the clamp lowers it, the raw square is the larger one (from 4 * 180 degrees on R^2 > 8.9: never culled);
+    //   * negative, -0, or inside [0, e): the clamp raises it to e; the raw square is >= 0, so the radius is short by at most
+    //     e = 4.4e-6 rad — what an extent inside [0, e) already did, and inside the 1.5e-3 rad margin by a factor of 300;
+    //   * +-inf, or finite with an infinite square: d = +inf, and prod * rsq(prod) = inf * 0 (or prod = inf * 0 for a
+    //     degenerate partner) = NaN: R^2 is NaN, the bound is NaN, `apart` is false;
+    //   * finite and huge: R^2 is huge or +inf, the bound's polynomial (all its terms then negative) is hugely negative or
+    //     -inf, never NaN: `apart` is false;
+    //   * NaN: d, R^2 and the bound are NaN: `apart` is false.
+    // So a pair with an extent out of range is culled only where its clamped form is culled as well.  Chord / tangent edges
+    // and CHORD keep the test of all eight values: edge_length is not monotonic past 180 degrees.
+    const bool arc_only = edge == EDGE_ARC && !CHORD;
+    const unsigned mphi = float_bits(g[1]) > float_bits(p[1]) ? float_bits(g[1]) : float_bits(p[1]);
+    const unsigned mg = arc_only ? mphi : max3_u32(float_bits(g[1]), float_bits(g[2]), float_bits(g[3]));
+    const unsigned mp = arc_only ? mphi : max3_u32(float_bits(p[1]), float_bits(p[2]), float_bits(p[3]));
     const unsigned mth = float_bits(g[0]) > float_bits(p[0]) ? float_bits(g[0]) : float_bits(p[0]);
     const bool in_sizes = (mg > mp ? mg : mp) <= 0x43340000u, in_theta = mth <= 0x43b40000u;   // 180.0f, 360.0f
     // (r_g + r_p)^2 with r = half the diagonal: (d_g + d_p + 2 sqrt(d_g d_p)) / 4, d = w^2 + h^2.  For arc edges the
@@ -400,6 +416,7 @@ struct FastTrig { float sg, cg, sp, cp, sD, cD; };
 // reference is active) — only filled in when lean_front is asked for them.
 struct PlanarPair {
     float dx, dy, ca, sa, cb, sb, wg, hg, wp, hp, c, s;
+    float pax, pay, pbx, pby;   // BFoV: the centres in each other's frame (see lean_front's rotated jitter)
     bool g_A, g_ag, g_ap, g_wg, g_hg, g_wp, g_hp;
 };
 
@@ -498,7 +515,10 @@ SPH_DEV ColatTrig colat_trig(float phi_deg, int role) {
 
 // PRE = 1: the colatitude trig of the two boxes is handed in (`pre1`, `pre2`: exactly what the function would compute);
 // PRE = 2: that of the first box only (one box against many: an NMS row)
-template <int VARIANT, int DIM, bool GATES, bool CLAMPED = true, int PRE = 0>
+// ABS_PINS: fix where sg * sp is formed and cut `s` loose from the |s| of the candidate test, so that three absolute values become
+// source modifiers (below).  The same bits either way; a kernel asks for what measured faster for it (the aligned chunk kernel's
+// dword-store body: 6.69 us per 1 M pairs without them, 6.81 with; its whole-line body 6.13 without, 6.04 with).
+template <int VARIANT, int DIM, bool GATES, bool CLAMPED = true, int PRE = 0, bool ABS_PINS = true>
 SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, PlanarPair& o, FastTrig* trig = nullptr,
                         ColatTrig pre1 = ColatTrig{0.0f, 1.0f}, ColatTrig pre2 = ColatTrig{0.0f, 1.0f}) {
     const float e = (float)kEpsS, ea = (float)kEpsA;
@@ -521,7 +541,13 @@ SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, Pl
         sD = t + t;
         h2 = 2.0f * sh * sh;
     }
-    const float spcg = sp * cg, sgcp = sg * cp, sgsp = sg * sp;
+    const float spcg = sp * cg, sgcp = sg * cp;
+    float sgsp = sg * sp;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // formed HERE, in front of the guard of the floors: only C uses it, and C is formed behind that guard, where the two sines
+    // (absolute values: sincos_colat) arrive as v_and 0x7fffffff each instead of as |x| modifiers of this product
+    if (ABS_PINS) asm volatile("" : "+v"(sgsp));
+#endif
     const float q = spcg - sgcp;                     // sin(phi_p - phi_g)
     const float N = fmaf(-spcg, h2, q), D = -sp * sD;
     const float Np = fmaf(sgcp, h2, q), Dp = -sg * sD;
@@ -581,7 +607,32 @@ SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, Pl
     // by 4e = 4.94e-4 (`sim`), i.e. |a_g - a_p| < 1.729e-3 — and 0.54 % of the benchmark's survivors are within 2e-3 (the
     // two bearings of a pair are correlated), which sends every third 64-lane pass through this block
     const bool cand_s = fabsf(s) < 1.75e-3f, cand = (c > 0.5f) & cand_s;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (from here on `s` is a value of its own to the compiler: left alone, |s| of the test above is kept in a register — one
+    // v_and 0x7fffffff — for lean_finish's near-parallel test behind the guard below, which takes it as an |s| modifier)
+    if (ABS_PINS) asm volatile("" : "+v"(s));
+#endif
     float dx = A, dy = 0.0f;
+    // The centre of each box in the other's frame (stage 2's pax ... pby), BFoV.  dy is 0 unless the block below runs, so the
+    // common path forms them from dx alone, 4 products, and the block forms them again in full for its whole wave (8 + the v_mov
+    // of dy on every pass before).  Both forms give stage 2 the same t2, whichever wave a pair shares:
+    //   -fma(dx, cb, +0 * sb), fma(dx, sb, -(+0 * cb)), fma(dx, ca, +0 * sa), fma(+0, ca, -(dx * sa))
+    // add an exact zero to a product.  The four directions are finite or the lane is a NaN lane (S2 > 1e-30 or the coincident
+    // fix; iS < 1e15).  A product that is not exactly zero — rounded to zero or not — is rounded the same with the zero added:
+    // the same bits.  An exactly zero product needs a zero direction (dx = A >= Amin > 0).  The sines never are: the floors
+    // above leave |sa|, |sb| >= kMinAng.  The cosines are, together, exactly when sD is (ca = -sp sD iS, cb = -sg sD iS with
+    // sp, sg >= sin e and |sD| = 0 or > 1e-14: no underflow; the floors move a cosine only where the sine is small, which it is
+    // not here: |sa|, |sb| ~ 1) — two boxes on one meridian — or after the coincident fix.  Then pax and pbx are zeros whose SIGN may differ between the forms,
+    // s = fma(sa, cb, -(ca * sb)) is a zero too, |c| ~ 1, and lean_finish replaces t2 by near_parallel_inter(pax, pay, c, s, ..):
+    // pbx reaches nothing, and pax enters that function as px in  l0 = px - a / c,  r0 = px + a / c  (a / c != 0)  and in
+    // (xl - px) t, (xr - px) t  with xl = max(-X, l0) < 0 < xr = min(X, r0): a zero px of either sign gives the same bits.
+    // (RBFoV rotates the directions by gamma behind the floors, where any of them may vanish: it keeps the full form.)
+    float pax = -(dx * cb), pay = dx * sb, pbx = dx * ca, pby = -(dx * sa);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (formed HERE: left alone the four products sink into an else-branch of the guard below, and the common path pays six
+    // register copies for the join)
+    if (DIM == 4) asm volatile("" : "+v"(pax), "+v"(pay), "+v"(pbx), "+v"(pby));
+#endif
     // ONE guard for the decisions and the adjustments (the wave-level test of the candidates is on the sine alone: a
     // single compare's mask, see SPH_ANY_LANE)
     if (SPH_SITE(2) (SPH_ANY_LANE2(cand_s, sim_size) || SPH_ANY_LANE(sim_dist))) {
@@ -620,6 +671,8 @@ SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, Pl
         if (sim | close) {   // only the lanes whose angles moved: the others keep their bits whatever the wave holds
             c = fmaf(ca, cb, sa * sb);
             s = fmaf(sa, cb, -(ca * sb));
+            pax = -fmaf(dx, cb, dy * sb); pay = fmaf(dx, sb, -(dy * cb));
+            pbx = fmaf(dx, ca, dy * sa);  pby = fmaf(dy, ca, -(dx * sa));
         }
     }
     if (GATES) {
@@ -645,12 +698,13 @@ SPH_DEV void lean_front(const float (&x1)[5], const float (&x2)[5], int edge, Pl
     }
     o.dx = dx; o.dy = dy; o.ca = ca; o.sa = sa; o.cb = cb; o.sb = sb; o.c = c; o.s = s;
     o.wg = wg; o.hg = hg; o.wp = wp; o.hp = hp;
+    o.pax = pax; o.pay = pay; o.pbx = pbx; o.pby = pby;
 }
 
 // Spherical jitter + stages 1 + 2 for one pair that survived the cull: clamp(IoU, 0, 1).  The spherical jitter's shift
 // and the near-parallel safeguard are guarded like lean_front's rare branches.  A NaN coordinate gives NaN, as the
 // reference's torch.clamp chain does (sph_iou_api.py:86, :244-260).
-template <int VARIANT, int DIM, int PRE = 0>
+template <int VARIANT, int DIM, int PRE = 0, bool ABS_PINS = true>
 SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode, int edge, ColatTrig pre1 = ColatTrig{0.0f, 1.0f},
                           ColatTrig pre2 = ColatTrig{0.0f, 1.0f}) {
     const float e = (float)kEpsS, e2 = (float)(2 * kEpsS);
@@ -710,15 +764,16 @@ SPH_DEV float lean_finish(const float (&in1)[5], const float (&in2)[5], int mode
     }
     if (DIM == 5) x2[4] = clampf(x2[4], (float)(-360.0 + 2 * kEpsS), (float)(360.0 - 2 * kEpsS));  // the two clamps of :256-258
     PlanarPair q;
-    lean_front<VARIANT, DIM, false, true, PRE>(x1, x2, edge, q, nullptr, pre1, pre2);
+    lean_front<VARIANT, DIM, false, true, PRE, ABS_PINS>(x1, x2, edge, q, nullptr, pre1, pre2);
     // ---- stage 2: boundary integral of the two rectangles (P at the origin, T at (dx, dy)) ----
     // (no clamp of the reciprocals: where |c| or |s| < kNearParallel — 1 / 2.5e-4 = 4e3 bounds them everywhere else — the
     // near-parallel block below replaces t2, whatever inf or NaN the slabs made of it)
     const float ic = fast_rcp(q.c), is = fast_rcp(q.s);
     const float aic = fabsf(ic), ais = fabsf(is);
     const float hwa = 0.5f * q.wg, hha = 0.5f * q.hg, hwb = 0.5f * q.wp, hhb = 0.5f * q.hp;
-    const float pax = -fmaf(q.dx, q.cb, q.dy * q.sb), pay = fmaf(q.dx, q.sb, -(q.dy * q.cb));
-    const float pbx = fmaf(q.dx, q.ca, q.dy * q.sa), pby = fmaf(q.dy, q.ca, -(q.dx * q.sa));
+    // (BFoV: lean_front's own, formed without dy on the common path; RBFoV: behind the gamma clamp, in full)
+    const float pax = DIM == 4 ? q.pax : -fmaf(q.dx, q.cb, q.dy * q.sb), pay = DIM == 4 ? q.pay : fmaf(q.dx, q.sb, -(q.dy * q.cb));
+    const float pbx = DIM == 4 ? q.pbx : fmaf(q.dx, q.ca, q.dy * q.sa), pby = DIM == 4 ? q.pby : fmaf(q.dy, q.ca, -(q.dx * q.sa));
     float t2 = edges_inside3(pax, pay, q.c, q.s, ic, is, aic, ais, hwa, hha, hwb, hhb, q.wg, q.hg, true) +
                edges_inside3(pbx, pby, q.c, -q.s, ic, -is, aic, ais, hwb, hhb, hwa, hha, q.wp, q.hp, false);
     // the two jitter steps cancelled: DESIGN.md §9.  (Two compares and a scalar OR of their masks; written as one

@@ -256,6 +256,23 @@ __global__ __launch_bounds__(kBlock, REF ? 4 : (DIM == 4 ? 7 : 5)) void iou_alig
 //     --full, one run each: kernel_ms 6.84 -> 6.50, cold 10.56 -> 9.18, at_8m 48.64 -> 46.75 us; rocprofv3: traced average
 //     7.85 -> 6.88 us, WRITE_SIZE 4.287 -> 4.000 MB per launch (the algorithmic bytes), SQ_INSTS_VALU 420.1 -> 441.1 per wave
 //     (+21: the staging costs more issue than the stores it replaces), SQ_INSTS_SALU 579 k -> 634 k.
+//   * instruction diet of the LINES bodies (ISA of the benched <0, 4, true, 2, true, true, true, true> body; bit-identical results;
+//     profiles/r12_diet_*.log): SQ_INSTS_VALU 441.1 -> 415.3 per wave, SQ_INSTS_SALU 81.1 -> 79.6, 49 -> 48 VGPRs.
+//     (i) one survivor mask per slice: the push branches on the scalar mask of the rank and the count (inverse ballot) instead of
+//     on `!culled` rebuilt from the other sense of each compare: 3 compares per slice.  (ii) arc edges: the range test of the
+//     cull covers theta and phi only (fast_cull_parts: why no extent can be culled wrongly): 2 v_max3_u32 per slice.  (iii) the
+//     index column holds the result slot's offset from the start of `queues`, which is also the zero stores' address register;
+//     the column's address is one v_lshl_add_u32 from a scalar base (count folded in); the slice's 256 s comes off the scalar
+//     side of the `inside` compare; the pass forms its two addresses from the slot, not from registers set up in front of the
+//     loop, and reads the index with the record: 6 -> 4 and 8 -> 5 VALU in the two pushes, 11 -> 8 in front of the pass loop,
+//     one v_add fewer behind each pass.  (iv) lean_front / lean_finish: the centres without dy on the common path, the three
+//     |x| as source modifiers: 8 per pass.  Not kept: `surv` from the failing senses of the same compares (the compiler merges
+//     the two range tests into 2 v_cndmask + v_or + v_cmp: +2 per slice); the four centre products left to sink (six register
+//     copies on the common path).  Times move less than the counts say, and not by the count alone: at 1 M pairs, 9 interleaved
+//     rounds, parent / this build / without the |x| pins / centres as before / neither: 6.263 / 6.038 / 6.134 / 6.162 / 6.323 us;
+//     the dword body, 5 VALU shorter (cull and finish only), read 6.753 -> 6.805 us with the |x| pins and 6.691 without: the
+//     BFoV dword-store bodies ask lean_finish for none (ABS_PINS; 6.896 -> 6.781 us, r12_diet_ab_pins.log).  2 M 13.68 -> 13.42, 8 M 44.75 -> 43.10, nearby 1 M 12.63 -> 12.35,
+//     RBFoV 1 M 10.14 -> 10.00 us.
 template <int DIM, int SLICES>
 struct ChunkQueue {
     float f[2 * DIM][64 * SLICES];
@@ -294,6 +311,7 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
     using Queue = std::conditional_t<LINES, ChunkLineQueue<DIM, SLICES>, ChunkQueue<DIM, SLICES>>;
     __shared__ Queue queues[WAVES];
     static_assert(!LINES || 8 * sizeof(queues) + 4096 <= 160 * 1024, "eight workgroups per CU, at least 4 KiB clear of the 160 KiB of LDS");
+    static_assert(!LINES || sizeof(queues) <= 65536, "a result slot's byte offset in `queues` fits the 16-bit index column");
     const int edge = ARC ? (int)EDGE_ARC : (edge_arg & 0xff);
     const int lane = threadIdx.x & 63;
     // the wave's number in an SGPR: its chunk, the test below and its LDS base (formed once) are scalar
@@ -356,6 +374,15 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
     int count = 0;
     float zero = 0.0f;   // ONE register for the stores of the culled pairs (left alone, a v_mov in front of each)
     if (OFF32) asm volatile("" : "+v"(zero));
+    // LINES: the byte offset of lane's slot of slice 0 in `res`, from the start of `queues`, in ONE register: the address of the
+    // zero stores (slice s at + 256 s) and, as it stands, the value of the index column — the pass stores through it without
+    // adding the wave's base (left alone: the wave's base | 4 lane for the stores and a second form of it for each push)
+    unsigned roff = 0;
+    if constexpr (LINES) {
+        roff = (unsigned)(reinterpret_cast<char*>(&q.res[lane]) - reinterpret_cast<char*>(queues));
+        asm volatile("" : "+v"(roff));
+    }
+    auto res_at = [&](unsigned off) -> float& { return *reinterpret_cast<float*>(reinterpret_cast<char*>(queues) + off); };
 #pragma unroll
     for (int s = 0; s < SLICES; s++) {
         const int i = base + s * 64 + lane;
@@ -368,25 +395,41 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
         const unsigned long long cm = __builtin_amdgcn_ballot_w64(cp.in_sizes) & __builtin_amdgcn_ballot_w64(cp.in_theta) &
                                       __builtin_amdgcn_ballot_w64(cp.apart);
 #endif
-        const bool inside = OFF32 ? o4 + s * 256u < (unsigned)n * 4u : i < n, surv = inside & !culled;
+        // (OFF32: 4 n < 2^30, so the slice's 256 s comes off the scalar side of a signed compare: no v_or per slice)
+        const bool inside = OFF32 ? (int)o4 < (int)((unsigned)n * 4u) - s * 256 : i < n;
 #if defined(SPH_ABL_NOCULL)
+        const bool surv = inside & !culled;
         const unsigned long long m = __builtin_amdgcn_ballot_w64(surv);
 #else
         // (the mask from the ballots of single compares, taken before the branch of the store: the ballot of `surv`, or of a
         // compare whose mask crosses a branch, costs two more VALU instructions; see CullParts)
         const unsigned long long m = __builtin_amdgcn_ballot_w64(inside) & ~cm;
+        // LINES: nothing but the push reads the cull, so its branch takes the scalar mask of the rank and the count as it is (one
+        // s_and_saveexec).  Built from `!culled` next to that mask, every condition was compared twice, once per sense: 6 VALU
+        // instructions per chunk; built from the failing senses of the same compares, the two range tests were merged into
+        // 2 v_cndmask + v_or + v_cmp.  The dword bodies keep the lane's own `culled` for the zero store.
+        const bool surv = LINES ? __builtin_amdgcn_inverse_ballot_w64(m) : inside & !culled;
 #endif
-        if constexpr (LINES) q.res[s * 64 + lane] = zero;   // every lane, no branch: a survivor's result lands on it later
+        if constexpr (LINES) res_at(roff + s * 256u) = zero;   // every lane, no branch: a survivor's result lands on it later
         else if (inside & culled) {   // (non-temporal stores here and below: 8.42 vs 8.30 us at 1 M, 51.4 vs 48.1 at 8 M)
             if (OFF32) *at_byte(out, o4 + s * 256u) = zero;
             else out[i] = 0.0f;
         }
         if (surv) {
-            const int slot = count + rank_below(m);
+            const int rank = rank_below(m), slot = count + rank;
 #pragma unroll
-            for (int k = 0; k < DIM; k++) { q.f[k][slot] = x[s][k]; q.f[DIM + k][slot] = y[s][k]; }
-            if constexpr (LINES) q.idx[slot] = (unsigned short)((s * 64 + lane) * 4);
-            else q.idx[slot] = OFF32 ? (int)(o4 + s * 256u) : i;
+            for (int k = 0; k < DIM; k++) {   // (count, a scalar, goes to the base: no v_add per slice)
+                if constexpr (LINES) { (&q.f[k][count])[rank] = x[s][k]; (&q.f[DIM + k][count])[rank] = y[s][k]; }
+                else { q.f[k][slot] = x[s][k]; q.f[DIM + k][slot] = y[s][k]; }
+            }
+            if constexpr (LINES) {
+                // (the 16-bit column's address from a copy of the rank the compiler cannot relate to the records' address: ONE
+                // v_lshl_add_u32 from the column's base + 2 count, a scalar; left alone it is (4 slot + base) - 2 slot, a shift
+                // and a subtraction more)
+                int rank16 = rank;
+                asm volatile("" : "+v"(rank16));
+                (&q.idx[count])[rank16] = (unsigned short)(roff + s * 256u);
+            } else q.idx[slot] = OFF32 ? (int)(o4 + s * 256u) : i;
         }
         count += __popcll(m);
         if (s == 0) SPH_STAMP(1);
@@ -397,17 +440,31 @@ __global__ __launch_bounds__(64 * WAVES, DIM == 4 ? 8 : 7) void iou_aligned_chun
     wave_lds_fence();
     if (PRIO) __builtin_amdgcn_s_setprio(0);
     for (int b = 0; b < count; b += 64) {
-        const int slot = b + lane;
+        int slot = b + lane;
+        // (LINES: a value the loop optimiser cannot turn into two address registers that are set up in front of the loop and
+        // advanced in it: more than 99 % of the waves run one pass, which pays 3 VALU instructions for that set-up)
+        if constexpr (LINES) asm volatile("" : "+v"(slot));
         if (slot < count) {
             float u1[5], u2[5];
 #pragma unroll
             for (int k = 0; k < 5; k++) { u1[k] = k < DIM ? q.f[k][slot] : 0.0f; u2[k] = k < DIM ? q.f[DIM + k][slot] : 0.0f; }
+            // LINES: the survivor's slot in `res`, read HERE with the record (one wait for both) and held in a register through the
+            // pass: read behind it, the slot and the records' address stay live instead, and the column's address is formed from
+            // both (see the push)
+            unsigned rslot = 0;
+            if constexpr (LINES) {
+                int slot16 = slot;
+                asm volatile("" : "+v"(slot16));
+                rslot = q.idx[slot16];
+                asm volatile("" : "+v"(rslot));
+            }
 #if defined(SPH_ABL_NOFINISH)
             const float r = u1[0] + u2[1] + u1[2] + u2[3] > 1e30f ? 1.0f : 0.5f;   // ABLATION: no finishing arithmetic
 #else
-            const float r = lean_finish<VARIANT, DIM>(u1, u2, mode, edge);
+            // (the BFoV dword-store bodies without lean_front's |x| pins: see there)
+            const float r = lean_finish<VARIANT, DIM, 0, LINES || DIM != 4>(u1, u2, mode, edge);
 #endif
-            if constexpr (LINES) *reinterpret_cast<float*>(reinterpret_cast<char*>(q.res) + q.idx[slot]) = r;   // in order behind the zero
+            if constexpr (LINES) res_at(rslot) = r;   // in order behind the zero
             else if (OFF32) *at_byte(out, (unsigned)q.idx[slot]) = r;
             else out[q.idx[slot]] = r;
         }
