@@ -67,7 +67,7 @@ enum {
 
 /* Library identification: ABI version (bumped on any signature change or new entry point; sph2pob_abi_version() returns the
  * value the library was built with) and the code-object target. */
-#define SPH2POB_ABI_VERSION 5
+#define SPH2POB_ABI_VERSION 6
 int sph2pob_abi_version(void);
 const char* sph2pob_target_arch(void);
 const char* sph2pob_error_string(int code);
@@ -441,6 +441,29 @@ int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt,
                                int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
                                float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
                                float* avg_factor, void* workspace, void* state, void* stream);
+
+/*
+ * The same call for the calculators without a closed form: LEGACY, SPH_IOU, FOV_IOU (box_dim 4 only), UNBIASED and NAIVE
+ * (box_dim 4 or 5; NAIVE with or without SPH2POB_FLAG_NAIVE_TAN).  Two launches for the batch, no (k, n) matrix, nothing read
+ * back: phase 1 runs the variant's per-pair function — the one sph2pob_iou_pairwise_f32 runs for it with mode IOU, the given
+ * edge and angle EQUATOR in the default arithmetic — on every (GT, anchor) pair (no cull) and keeps the per-anchor and per-GT
+ * maxima; phase 2 is the finalize pass of sph2pob_anchor_targets_f32 with that function in its re-evaluation.  Arguments,
+ * outputs, limits and the target table are those of sph2pob_anchor_targets_f32, and so are workspace and state: the same two
+ * size entries, the same layout, the same zero-before / zero-after contract, so one zeroed state buffer serves both entries
+ * alternately.  For image b the outputs are exactly what sph2pob_iou_pairwise_f32 + sph2pob_assign_f32 give for that image alone
+ * (same function, same inputs, same bits), provided its overlaps are +0 or positive (no NaN): what every variant returns for
+ * valid boxes.
+ * Errors, in the order of sph2pob_anchor_targets_f32: box_dim (LEGACY / SPH_IOU / FOV_IOU with box_dim 5 included, as the
+ * pairwise entry answers) -> SPH2POB_ERR_DIM; STANDARD | EFFICIENT (they have their own entry), SPH2POB_FLAG_REFERENCE_ORDER, a
+ * bad edge -> SPH2POB_ERR_OPTION; then the sizes and the NULL checks.
+ */
+int sph2pob_anchor_targets_any_f32(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
+                                   int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
+                                   float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
+                                   int64_t num_classes, float pos_weight, int encode, const float* means_host, const float* stds_host,
+                                   int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
+                                   float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
+                                   float* avg_factor, void* workspace, void* state, void* stream);
 
 /* ---- box coder: the step immediately in front of the loss when reg_decoded_bbox=True --------------
  * Replaces sphdet/bbox/coder/delta_xywh_sph_bbox_coder.py:116-161 (bbox2delta), :164-263 (delta2bbox) for box_dim 4

@@ -43,7 +43,7 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_nms_segmented_f32', 'sph2pob_nms_f32', 'sph2pob_assign_f32', 'sph2pob_coder_encode_f32',
               'sph2pob_coder_decode_f32', 'sph2pob_coder_decode_bwd_f32', 'sph2pob_obb_l1_fwd_f32', 'sph2pob_obb_l1_bwd_f32',
               'sph2pob_gauss_loss_fwd_f32', 'sph2pob_gauss_loss_bwd_f32', 'sph2pob_gauss_loss_fwd_sum_f32',
-              'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32', 'sph2pob_get_bboxes_f32', 'sph2pob_test_bboxes_f32', 'sph2pob_focal_loss_sum_f32',
+              'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32', 'sph2pob_anchor_targets_any_f32', 'sph2pob_get_bboxes_f32', 'sph2pob_test_bboxes_f32', 'sph2pob_focal_loss_sum_f32',
               'sph2pob_focal_loss_fwd_f32', 'sph2pob_focal_loss_bwd_f32', 'sph2pob_focal_loss_grad_scale_f32', 'sph2pob_bbox_loss_sum_f32',
               'sph2pob_delta_loss_sum_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp',
@@ -114,6 +114,9 @@ SIGNATURES = {
     # pos_weight, encode, means, stds, 10 outputs, workspace, state, stream
     'sph2pob_anchor_targets_f32': [_c_f32p, _i64, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, _int, _int, _int] +
                                   [ctypes.c_float] * 4 + [_int, _int, _i64, ctypes.c_float, _int] + [ctypes.c_void_p] * 15,
+    # the same arguments, for the variants without a closed form
+    'sph2pob_anchor_targets_any_f32': [_c_f32p, _i64, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, _int, _int, _int] +
+                                      [ctypes.c_float] * 4 + [_int, _int, _i64, ctypes.c_float, _int] + [ctypes.c_void_p] * 15,
     'sph2pob_nms_max_boxes': [],
     'sph2pob_nms_workspace_bytes': [_i64],
     'sph2pob_nms_f32': [_c_f32p, ctypes.c_void_p, _i64, _int, _int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
@@ -170,7 +173,7 @@ _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_targe
              'sph2pob_focal_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_bbox_loss_workspace_bytes': ctypes.c_int64,
              'sph2pob_delta_loss_workspace_bytes': ctypes.c_int64}
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class Sph2PobLibraryError(RuntimeError):

@@ -10,7 +10,8 @@ the image as a grid dimension and the target construction as its epilogue).  The
 
 The per-image API (`SphMaxIoUAssigner.assign`, then the few torch lines of `_get_targets_single`) keeps serving what this
 entry does not: `gt_bboxes_ignore`, per-image valid flags (`allowed_border >= 0`), samplers that draw on the host,
-`gpu_assign_thr`, and IoU backends other than the closed-form `sph2pob_standard_iou` / `sph2pob_efficient_iou`.
+`gpu_assign_thr`, and IoU backends other than the closed-form `sph2pob_standard_iou` / `sph2pob_efficient_iou` — the other
+backends have a batched entry of their own, `sph_train_targets` (train_targets.py), which shares this module's call path.
 """
 import ctypes
 
@@ -103,13 +104,21 @@ def sph_anchor_targets(anchors, gt_bboxes, gt_labels=None, gt_offsets=None, *, a
         raise NotImplementedError('sph_anchor_targets needs an SphMaxIoUAssigner(fused=True) with the sph2pob_standard_iou or '
                                   'sph2pob_efficient_iou backend in the default arithmetic and (n, 4|5) anchors, n > 0; otherwise '
                                   + _PER_IMAGE)
+    return _batched_call('sph_anchor_targets', 'sph2pob_anchor_targets_f32', variant, anchors, gt_bboxes, gt_labels, gt_offsets, assigner,
+                         num_classes, pos_weight, reg_decoded_bbox, bbox_coder, k_max, with_assigned_labels)
+
+
+def _batched_call(who, symbol, variant, anchors, gt_bboxes, gt_labels, gt_offsets, assigner, num_classes, pos_weight, reg_decoded_bbox,
+                  bbox_coder, k_max, with_assigned_labels):
+    """The GT in either form -> one call of `symbol` (`sph2pob_anchor_targets_f32` or `sph2pob_anchor_targets_any_f32`: the same
+    arguments, buffers and outputs) with the assigner's rule and the kernel variant `variant`."""
     dim = assigner.iou_calculator.box_version
     counts = None
     if isinstance(gt_bboxes, (list, tuple)):
         if gt_offsets is not None:
             raise ValueError('gt_offsets goes with concatenated gt_bboxes, not with a list')
         if len(gt_bboxes) == 0:
-            raise ValueError('sph_anchor_targets needs at least one image')
+            raise ValueError(f'{who} needs at least one image')
         gt, gl, gt_offsets, counts = _concat(gt_bboxes, gt_labels, anchors.device, dim)
         k_max = max(counts)
     else:
@@ -121,7 +130,7 @@ def sph_anchor_targets(anchors, gt_bboxes, gt_labels=None, gt_offsets=None, *, a
     tensors = [anchors, gt, gt_offsets] + ([gl] if gl is not None else [])
     G.require_hip(*tensors)
     if len({t.device for t in tensors}) != 1:
-        raise RuntimeError('sph_anchor_targets: anchors, gt_bboxes, gt_labels and gt_offsets must be on one device, got '
+        raise RuntimeError(f'{who}: anchors, gt_bboxes, gt_labels and gt_offsets must be on one device, got '
                            + ', '.join(sorted({str(t.device) for t in tensors})))
     bx, gt = G.as_f32_nograd(anchors[..., :dim]), G.as_f32_nograd(gt)
     gt_offsets = gt_offsets.contiguous()
@@ -153,7 +162,7 @@ def sph_anchor_targets(anchors, gt_bboxes, gt_labels=None, gt_offsets=None, *, a
         ws, state = G.assign_workspace(dev, lib.sph2pob_anchor_targets_workspace_bytes(images, num_gt, k_max, n),
                                        lib.sph2pob_anchor_targets_state_bytes(images, k_max, n))
     try:
-        G.call('sph2pob_anchor_targets_f32', dev, G.ptr(bx), n, G.ptr(gt), G.ptr(gl), G.ptr(gt_offsets), images, num_gt, k_max, dim,
+        G.call(symbol, dev, G.ptr(bx), n, G.ptr(gt), G.ptr(gl), G.ptr(gt_offsets), images, num_gt, k_max, dim,
                G.VARIANTS[variant], G.EDGES['arc'], assigner.pos_iou_thr, neg_lo, neg_hi, assigner.min_pos_iou,
                int(bool(assigner.match_low_quality)), int(bool(assigner.gt_max_assign_all)), int(num_classes), float(pos_weight),
                int(not reg_decoded_bbox), means, stds, G.ptr(out.gt_inds), G.ptr(out.max_overlaps), G.ptr(out.assigned_labels),

@@ -1,5 +1,6 @@
 // libsph2pob_hip.so — pairwise IoU (the assigner call pattern), the MaxIoUAssigner epilogues, matrix and fused, and the fused
-// assigner batched over a minibatch with the anchor-target construction as its epilogue: kernels + C-ABI launchers
+// assigner batched over a minibatch with the anchor-target construction as its epilogue — on the closed-form cull / compact /
+// finish, or on any variant's per-pair function evaluated for every pair —: kernels + C-ABI launchers
 // (include/sph2pob_hip.h).  gfx950 only.
 
 #include <type_traits>
@@ -53,6 +54,14 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         unsigned long long w = __shfl_xor(v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned w = __shfl_xor(v, o, 64);
         v = w > v ? w : v;
     }
     return v;
@@ -426,6 +435,58 @@ __global__ __launch_bounds__(kBlock) void assign_keys_from_acc_kernel(unsigned l
         row_acc[i * acc_stride(k)] = 0ull;
     }
 }
+// ---- the per-pair function of C's re-evaluation (below), phase 1's by construction: `column` takes the lane's column once (j
+// clamped to n - 1 past the end), `row` gives that column's IoU with GT row i. ----
+// standard / efficient in the closed form: the cull and the finishing pass of pairwise_compact_tile
+template <int VARIANT, int DIM, bool ARC>
+struct ClosedFormPair {
+    int edge;
+    float a5[5] = {0.0f, 0.0f, 1.0f, 1.0f, 0.0f};
+    bool have_column = false;
+    CullBox ca{};
+    ColatTrig ct{};
+    __device__ __forceinline__ explicit ClosedFormPair(int edge_arg) : edge(ARC ? (int)EDGE_ARC : edge_arg) {}
+    __device__ __forceinline__ void column(const float* __restrict__ b2, int j, bool valid) {
+        if (valid) load_box<DIM>(b2, j, a5);
+        ca = cull_box(a5, edge);
+        ct = colat_trig(a5[1], 2);
+        have_column = true;
+    }
+    __device__ __forceinline__ float row(const float* __restrict__ b1, int i) const {
+        float g5[5];
+        load_box<DIM>(b1, i, g5);
+        const CullBox cg = cull_box(g5, edge);
+        float v = 0.0f;
+        if (!cull_pair(cg, ca)) v = lean_finish<VARIANT, DIM, 1>(g5, a5, MODE_IOU, edge, colat_trig(g5[1], 1), ct);
+        return v;
+    }
+};
+// every other variant: the function iou_pairwise_kernel runs for it in the default arithmetic with rbb_angle='equator' (`edge`
+// carries SPH2POB_FLAG_NAIVE_TAN as EDGE_TANGENT, as in the pairwise entry) — the reference-order core for legacy / Sph-IoU /
+// FoV-IoU, which have no other, the fast selection for the unbiased and the naive IoU
+template <int VARIANT, int DIM>
+__device__ __forceinline__ float per_pair_iou(const float (&g)[5], const float (&a)[5], int edge) {
+    return pair_iou_sel<VARIANT, DIM, (VARIANT >= VARIANT_UNBIASED)>(g, a, (int)MODE_IOU, edge, (int)ANGLE_EQUATOR);
+}
+template <int VARIANT, int DIM>
+struct PerPairFunction {
+    int edge;
+    float a5[5];
+    bool have_column = false;
+    __device__ __forceinline__ explicit PerPairFunction(int edge_arg) : edge(edge_arg) {}
+    __device__ __forceinline__ void column(const float* __restrict__ b2, int j, bool) {
+        load_box<DIM>(b2, j, a5);
+        have_column = true;
+    }
+    __device__ __forceinline__ float row(const float* __restrict__ b1, int i) const {
+        float g5[5];
+        load_box<DIM>(b1, i, g5);
+        return per_pair_iou<VARIANT, DIM>(g5, a5, edge);
+    }
+};
+template <int VARIANT, int DIM, bool ARC>
+using PairOf = std::conditional_t<(VARIANT < VARIANT_LEGACY), ClosedFormPair<(VARIANT < VARIANT_LEGACY ? VARIANT : 0), DIM, ARC>, PerPairFunction<VARIANT, DIM>>;
+
 // C': one workgroup per column tile (the tiles of phase 1).  Column maxima from the row chunks' partials, thresholds, and
 // the low-quality step (max_iou_assigner.py:192-207) without the matrix: `overlaps[i, :] == gt_max[i]` can hold in this tile
 //   * for gt_max[i] == 0 on every column that is not ignored (nothing overlaps GT i: every live IoU of the row is 0);
@@ -446,7 +507,6 @@ __device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict
         const long long* __restrict__ gt_keys, unsigned long long* __restrict__ row_acc, const int64_t stride, bool has_ignore,
         unsigned col_offset, const Rule& rule, float* __restrict__ gt_max, int64_t* __restrict__ gt_argmax, const int tile, const int tiles,
         float& m_out, int64_t& am_out) {
-    const int edge = ARC ? (int)EDGE_ARC : edge_arg;
     const int lane = threadIdx.x & 63;
     const int jraw = tile * kBlock + threadIdx.x;
     const bool valid = jraw < n;
@@ -483,10 +543,7 @@ __device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict
                 if (unpack_max_val(key) >= rule.min_pos && row_key_index(key) == col_offset + (unsigned)j) best = i;
             }
         } else {
-            float a5[5] = {0.0f, 0.0f, 1.0f, 1.0f, 0.0f};
-            bool have_box = false;
-            CullBox ca{};
-            ColatTrig ct{};
+            PairOf<VARIANT, DIM, ARC> pair(edge_arg);
             for (int r0 = 0; r0 < k; r0 += 64) {
                 const int il = r0 + lane, ic = il < k ? il : k - 1;
                 const unsigned long long gk = row_key_of(ic);
@@ -509,17 +566,8 @@ __device__ __forceinline__ int64_t fused_finalize_column(const float* __restrict
                 while (rec) {   // wave-uniform: rows whose maximum lives in this tile
                     const int t = __builtin_ctzll(rec);
                     rec &= rec - 1;
-                    if (!have_box) {
-                        if (valid) load_box<DIM>(b2, j, a5);
-                        ca = cull_box(a5, edge);
-                        ct = colat_trig(a5[1], 2);
-                        have_box = true;
-                    }
-                    float g5[5];
-                    load_box<DIM>(b1, r0 + t, g5);
-                    const CullBox cg = cull_box(g5, edge);
-                    float v = 0.0f;
-                    if (!cull_pair(cg, ca)) v = lean_finish<VARIANT, DIM, 1>(g5, a5, MODE_IOU, edge, colat_trig(g5[1], 1), ct);
+                    if (!pair.have_column) pair.column(b2, j, valid);
+                    const float v = pair.row(b1, r0 + t);
                     const float gm = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(g), t));
                     if (!ign && v == gm && r0 + t > best) best = r0 + t;
                 }
@@ -613,6 +661,77 @@ __global__ __launch_bounds__(kBlock, ARC ? 8 : 4) void anchor_targets_pairwise_k
     pairwise_compact_tile<VARIANT, DIM, ARC, 2>(gt + im.lo * DIM, im.k, anchors, n, nullptr, (int)MODE_IOU, edge_arg, (im.k + chunks - 1) / chunks,
                                                 nullptr, col_part, col_part + l.row_part, 0u, state + b * l.state_words, t.bx, t.by, (int)l.tiles,
                                                 l.stride);
+}
+
+// Phase 1 of the batched route for the variants without a closed form (sph2pob_anchor_targets_any_f32): the grid, the image
+// slices, the chunk rule and the three outputs of anchor_targets_pairwise_kernel, with per_pair_iou on EVERY pair of the tile in
+// place of cull / compact / finish.  One thread owns one anchor (a lane past n works on anchor n - 1 and contributes nothing)
+// and walks the chunk's rows from LDS: the column's key is a running maximum in registers (equal values keep the first row);
+// per row the wave reduces the value's ordered bits, a ballot names the first lane that holds the maximum and tells whether a
+// second one does, and lane 0 takes the packed row key into the tile's LDS with one ds_max_rtn_u64 — an equal value already
+// there is the same value at a column of another wave: the "second column" flag either way (conservative, as in
+// pairwise_compact_tile).  Every tile has a live column, so every row of the chunk gets a key: no tile base is needed.
+// A -0 would sort below +0 in the keys while torch.max treats them alike: zeros are taken as +0.
+template <int VARIANT, int DIM>
+__global__ __launch_bounds__(kBlock) void anchor_targets_pairwise_any_kernel(const float* __restrict__ gt,
+        const int64_t* __restrict__ gt_offsets, int64_t K, int k_max, const float* __restrict__ anchors, int n, int edge, int rows_per_wg,
+        unsigned long long* __restrict__ workspace, unsigned long long* __restrict__ state) {
+    __shared__ float row_raw[kPwRows][5];
+    __shared__ unsigned long long row_key[kPwRows];
+    __shared__ int row_tie[kPwRows];
+    const int b = blockIdx.z;
+    const TileId t = tail_first_tile();
+    const ImageRows im = image_rows(gt_offsets, b, K, k_max);
+    const int chunks = image_chunks(im.k, rows_per_wg);
+    if (t.by >= chunks) return;
+    const Layout l = layout(k_max, n, col_tiles(n), row_chunks(k_max, rows_per_wg), true);
+    unsigned long long* col_part = workspace + b * l.ws_words;
+    unsigned long long* row_part = col_part + l.row_part;
+    unsigned long long* row_acc = state + b * l.state_words;
+    const float* gt_b = gt + im.lo * DIM;
+    const int rpw = (im.k + chunks - 1) / chunks;
+    const int r0 = t.by * rpw, rows = (im.k - r0 < rpw) ? im.k - r0 : rpw;
+    const int lane = threadIdx.x & 63;
+    if ((int)threadIdx.x < rows) {
+        float g[5];
+        load_box<DIM>(gt_b, r0 + threadIdx.x, g);
+#pragma unroll
+        for (int c = 0; c < 5; c++) row_raw[threadIdx.x][c] = g[c];
+        row_key[threadIdx.x] = 0ull;
+        row_tie[threadIdx.x] = 0;
+    }
+    const int jraw = t.bx * kBlock + threadIdx.x;
+    const bool valid = jraw < n;
+    float a[5];
+    load_box<DIM>(anchors, valid ? jraw : n - 1, a);
+    __syncthreads();
+    unsigned long long ck = 0ull;
+    for (int i = 0; i < rows; i++) {
+        float g[5];
+#pragma unroll
+        for (int c = 0; c < 5; c++) g[c] = row_raw[i][c];
+        float v = per_pair_iou<VARIANT, DIM>(g, a, edge);
+        v = v == 0.0f ? 0.0f : v;
+        const unsigned long long key = pack_max_key(v, r0 + i);
+        ck = key > ck ? key : ck;
+        const unsigned ob = valid ? ordered_bits(v) : 0u;
+        const unsigned wm = wave_max_u32(ob);
+        const unsigned long long eq = __builtin_amdgcn_ballot_w64(ob == wm);
+        if (lane == 0 && wm != 0u) {   // wm == 0: a wave past n
+            const unsigned col = (unsigned)(jraw + __builtin_ctzll(eq));
+            const unsigned long long old = atomicMax(&row_key[i], ((unsigned long long)wm << 32) | ((0x7fffffffu - col) << 1));
+            if (__popcll(eq) > 1 || (unsigned)(old >> 32) == wm) row_tie[i] = 1;
+        }
+    }
+    __syncthreads();
+    if (valid) col_part[(int64_t)t.by * n + jraw] = ck;
+    if ((int)threadIdx.x < rows) {
+        const unsigned long long best = row_key[threadIdx.x] | (unsigned long long)row_tie[threadIdx.x];
+        row_part[(int64_t)(r0 + threadIdx.x) * l.tiles + t.bx] = best;
+        // as in pairwise_compact_tile: only tiles that hold something above the rows' common floor (0 at column 0)
+        if ((unsigned)(best >> 32) > 0x80000000u)
+            __hip_atomic_fetch_max(row_acc + (r0 + threadIdx.x) * l.stride, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 struct TargetOut {
@@ -835,6 +954,29 @@ struct AnchorTargetsLaunch {
         return launch_status();
     }
 };
+// the same two launches, buffers and sizes for the variants that run their per-pair function on every pair (legacy, Sph-IoU,
+// FoV-IoU, unbiased, naive); `edge` carries SPH2POB_FLAG_NAIVE_TAN
+struct AnchorTargetsAnyLaunch : AnchorTargetsLaunch {
+    template <int V, int D> int run() {
+        if constexpr (V < 2) return SPH2POB_ERR_OPTION;
+        else {
+            if (!fast) return SPH2POB_ERR_OPTION;
+            const int64_t rpw = k_max > 0 ? batch_rows_per_wg(images, K, k_max, n) : 1;
+            const Layout l = layout(k_max, n, col_tiles(n), row_chunks(k_max, rpw), true);
+            unsigned long long *ws = (unsigned long long*)workspace, *st = (unsigned long long*)state;
+            if (k_max > 0)
+                hipLaunchKernelGGL((anchor_targets_pairwise_any_kernel<V, D>), dim3((unsigned)l.tiles, (unsigned)l.chunks, (unsigned)images),
+                                   dim3(kBlock), 0, s, gt, gt_offsets, K, (int)k_max, anchors, (int)n, edge, (int)rpw, ws, st);
+            with_flag(encode, [&](auto enc) {
+                hipLaunchKernelGGL((anchor_targets_finalize_kernel<V, D, false, decltype(enc)::value>), dim3((unsigned)l.tiles, (unsigned)images),
+                                   dim3(kBlock), 0, s, gt, gt_labels, gt_offsets, K, (int)k_max, anchors, (int)n, edge, (int)rpw, ws, st,
+                                   rule.pos_thr, rule.neg_lo, rule.neg_hi, rule.min_pos, rule.low_quality, rule.assign_all, num_classes,
+                                   pos_weight, nm, o);
+            });
+            return launch_status();
+        }
+    }
+};
 
 }  // namespace
 
@@ -948,9 +1090,9 @@ int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt,
                                int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
                                float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
                                float* avg_factor, void* workspace, void* state, void* stream) {
-    int rc = sph2pob_assign::anchor_targets_check(check_common(box_dim, variant, edge, 0), anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt,
-                                                  k_max, variant, assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets,
-                                                  bbox_weights, num_pos, num_neg, avg_factor, true, workspace, state);
+    int rc = sph2pob_assign::anchor_targets_check(sph2pob_assign::closed_form_only(check_common(box_dim, variant, edge, 0), variant), anchors, n, gt,
+                                                  gt_labels, gt_offsets, num_images, num_gt, k_max, assigned_gt_inds, max_overlaps, assigned_labels,
+                                                  labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg, avg_factor, true, workspace, state);
     if (rc) return rc;
     const TargetOut o{assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg, avg_factor};
     return dispatch(variant, box_dim,
@@ -958,6 +1100,26 @@ int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt,
                                         Rule{pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all}, num_classes,
                                         pos_weight, encode != 0, sph2pob_coder::make_norm(means_host, stds_host, box_dim), o, workspace, state,
                                         (hipStream_t)stream});
+}
+
+int sph2pob_anchor_targets_any_f32(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
+                                   int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
+                                   float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
+                                   int64_t num_classes, float pos_weight, int encode, const float* means_host, const float* stds_host,
+                                   int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
+                                   float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
+                                   float* avg_factor, void* workspace, void* state, void* stream) {
+    int rc = sph2pob_assign::anchor_targets_check(sph2pob_assign::per_pair_only(check_common(box_dim, variant, edge, 0), variant), anchors, n, gt,
+                                                  gt_labels, gt_offsets, num_images, num_gt, k_max, assigned_gt_inds, max_overlaps, assigned_labels,
+                                                  labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg, avg_factor, true, workspace, state);
+    if (rc) return rc;
+    if (variant & SPH2POB_FLAG_NAIVE_TAN) edge = SPH2POB_EDGE_TANGENT;   // as the pairwise entry hands it to naive_iou
+    const TargetOut o{assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg, avg_factor};
+    return dispatch(variant, box_dim,
+                    AnchorTargetsAnyLaunch{{anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt, k_max, edge,
+                                            Rule{pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all}, num_classes,
+                                            pos_weight, encode != 0, sph2pob_coder::make_norm(means_host, stds_host, box_dim), o, workspace, state,
+                                            (hipStream_t)stream}});
 }
 
 

@@ -66,13 +66,19 @@ inline int assign_fused_check(int rc, int64_t k, int64_t n, int variant, int64_t
         return SPH2POB_ERR_SIZE;
     return SPH2POB_OK;
 }
-// sph2pob_anchor_targets_f32 and its twin; `need_buffers`: workspace (for k_max > 0) and state are required — the twin uses neither
+// the batched route that carries the per-pair functions: every variant the closed-form entry does not serve
+inline int per_pair_only(int rc, int variant) {
+    if (rc) return rc;
+    return ((variant & 0xff) < SPH2POB_VARIANT_LEGACY || (variant & SPH2POB_FLAG_REFERENCE_ORDER)) ? SPH2POB_ERR_OPTION : SPH2POB_OK;
+}
+// sph2pob_anchor_targets_f32 / sph2pob_anchor_targets_any_f32 and their twins; `rc`: what the entry's variant rule
+// (closed_form_only / per_pair_only) answered; `need_buffers`: workspace (for k_max > 0) and state are required — the twins use neither
 inline int anchor_targets_check(int rc, const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
-                                int64_t num_images, int64_t num_gt, int64_t k_max, int variant, const int64_t* assigned_gt_inds,
+                                int64_t num_images, int64_t num_gt, int64_t k_max, const int64_t* assigned_gt_inds,
                                 const float* max_overlaps, const int64_t* assigned_labels, const int64_t* labels, const float* label_weights,
                                 const float* bbox_targets, const float* bbox_weights, const int64_t* num_pos, const int64_t* num_neg,
                                 const float* avg_factor, bool need_buffers, const void* workspace, const void* state) {
-    if ((rc = closed_form_only(rc, variant))) return rc;
+    if (rc) return rc;
     if (num_images <= 0 || num_images > 65535 || num_gt < 0 || k_max < 0 || k_max > num_gt || k_max > (int64_t)65535 * 4 || n <= 0 ||
         n >= ((int64_t)1 << 31) - kTile || num_gt > sph2pob::kMaxElems)
         return SPH2POB_ERR_SIZE;

@@ -547,19 +547,19 @@ int sph2pob_assign_f32_cpu(const float* ov, int64_t k, int64_t n, float pos_iou_
 }
 
 
-// ---- anchor targets for a minibatch: sph2pob_anchor_targets_f32 (a loop over the images on the two twins above, then the
-// target table of include/sph2pob_hip.h; workspace and state are not used) ----
-int sph2pob_anchor_targets_f32_cpu(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
-                                   int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
-                                   float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
-                                   int64_t num_classes, float pos_weight, int encode, const float* means_host, const float* stds_host,
-                                   int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels, int64_t* labels,
-                                   float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
-                                   float* avg_factor, void* workspace, void* state, void*) {
-    int rc = sph2pob_assign::anchor_targets_check(check_common(box_dim, variant, edge, 0), anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt,
-                                                  k_max, variant, assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets,
-                                                  bbox_weights, num_pos, num_neg, avg_factor, false, workspace, state);
-    if (rc) return rc;
+}  // extern "C"
+
+// ---- anchor targets for a minibatch: sph2pob_anchor_targets_f32 / sph2pob_anchor_targets_any_f32 after their checks (a loop over
+// the images on the two twins above — the pairwise twin runs the variant's per-pair function —, then the target table of
+// include/sph2pob_hip.h; workspace and state are not used) ----
+namespace {
+int anchor_targets_cpu(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets, int64_t num_images,
+                       int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr, float neg_iou_lo, float neg_iou_hi,
+                       float min_pos_iou, int match_low_quality, int gt_max_assign_all, int64_t num_classes, float pos_weight, int encode,
+                       const float* means_host, const float* stds_host, int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels,
+                       int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,
+                       float* avg_factor) {
+    int rc = SPH2POB_OK;
     const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
     const int dim = box_dim;
     namespace A = sph2pob_assign;   // the kernel's element function, for this call's (dim, encode)
@@ -601,6 +601,30 @@ int sph2pob_anchor_targets_f32_cpu(const float* anchors, int64_t n, const float*
     *avg_factor = (float)total;
     return SPH2POB_OK;
 }
+}  // namespace
+
+extern "C" {
+
+#define SPH2POB_ANCHOR_TARGETS_TWIN(NAME, VARIANT_RULE)                                                                                          \
+    int NAME(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets, int64_t num_images,          \
+             int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr, float neg_iou_lo, float neg_iou_hi,           \
+             float min_pos_iou, int match_low_quality, int gt_max_assign_all, int64_t num_classes, float pos_weight, int encode,                 \
+             const float* means_host, const float* stds_host, int64_t* assigned_gt_inds, float* max_overlaps, int64_t* assigned_labels,          \
+             int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* num_pos, int64_t* num_neg,                \
+             float* avg_factor, void* workspace, void* state, void*) {                                                                           \
+        int rc = sph2pob_assign::anchor_targets_check(sph2pob_assign::VARIANT_RULE(check_common(box_dim, variant, edge, 0), variant), anchors, n, \
+                                                      gt, gt_labels, gt_offsets, num_images, num_gt, k_max, assigned_gt_inds, max_overlaps,      \
+                                                      assigned_labels, labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg,      \
+                                                      avg_factor, false, workspace, state);                                                      \
+        if (rc) return rc;                                                                                                                       \
+        return anchor_targets_cpu(anchors, n, gt, gt_labels, gt_offsets, num_images, num_gt, k_max, box_dim, variant, edge, pos_iou_thr,         \
+                                  neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all, num_classes, pos_weight, encode,    \
+                                  means_host, stds_host, assigned_gt_inds, max_overlaps, assigned_labels, labels, label_weights, bbox_targets,   \
+                                  bbox_weights, num_pos, num_neg, avg_factor);                                                                   \
+    }
+SPH2POB_ANCHOR_TARGETS_TWIN(sph2pob_anchor_targets_f32_cpu, closed_form_only)
+SPH2POB_ANCHOR_TARGETS_TWIN(sph2pob_anchor_targets_any_f32_cpu, per_pair_only)
+#undef SPH2POB_ANCHOR_TARGETS_TWIN
 
 // ---- detection post-processing for a minibatch: sph2pob_test_bboxes_f32 / sph2pob_get_bboxes_f32 (the same keys, in the same
 // order, sorted instead of selected; the NMS twin above on each image's candidates — one segment when class-agnostic; the

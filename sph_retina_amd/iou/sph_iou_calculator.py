@@ -21,9 +21,10 @@ _HIP_BACKENDS = {'sph2pob_standard_iou': sph2pob_standard_iou, 'sph2pob_legacy_i
 class SphOverlaps2D(object):
     """2D Overlaps calculator for spherical boxes (reference: sph_iou_calculator.py:8-56)."""
 
-    def __init__(self, backend='unbiased_iou', box_version=4):
+    def __init__(self, backend='unbiased_iou', box_version=4, box_formator='sph2pix'):
         self.backend = backend
         self.box_version = box_version
+        self.box_formator = box_formator   # naive_iou only: Sph2PlanarBoxTransform's 'sph2pix' | 'sph2tan' (the reference's default: 'sph2pix')
 
     def __call__(self, bboxes1, bboxes2, mode='iou', is_aligned=False):
         assert bboxes1.size(-1) in [0, 4, 5, 6]
@@ -31,14 +32,14 @@ class SphOverlaps2D(object):
         bboxes1 = bboxes1[..., :self.box_version]  # drops a trailing score column
         bboxes2 = bboxes2[..., :self.box_version]
         with torch.no_grad():
-            return sph_overlaps(bboxes1, bboxes2, mode, is_aligned, self.backend)
+            return sph_overlaps(bboxes1, bboxes2, mode, is_aligned, self.backend, self.box_formator)
 
     def __repr__(self):
         return self.__class__.__name__ + '()'
 
 
-def sph_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False, backend='unbiased_iou'):
-    """Backend switch (reference: sph_iou_calculator.py:58-113); rows = bboxes1."""
+def sph_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False, backend='unbiased_iou', box_formator='sph2pix'):
+    """Backend switch (reference: sph_iou_calculator.py:58-113); rows = bboxes1.  `box_formator`: naive_iou's."""
     assert mode in ['iou', 'iof']
     assert backend in _ALL_BACKENDS
     rows = bboxes1.size(0)
@@ -50,4 +51,6 @@ def sph_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False, backend='unbias
         raise NotImplementedError(
             f"backend '{backend}' (Kent distributions) is outside the Sph2Pob hot path served by sph_retina_amd; "
             "use one of " + ', '.join(sorted(_HIP_BACKENDS)))
+    if backend == 'naive_iou' and box_formator != 'sph2pix':
+        return fn(bboxes1, bboxes2, mode, is_aligned, box_formator=box_formator)
     return fn(bboxes1, bboxes2, mode, is_aligned)

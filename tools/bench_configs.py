@@ -321,6 +321,72 @@ def config4_batch(images=8, num_gt=64, h=512, w=1024, rounds=7):
             'note': '(a) also writes labels, label_weights, bbox_targets, bbox_weights and the counts, which (b) does not'}
 
 
+def train_targets(images=8, num_gt=64, h=512, w=1024, rounds=5, backends=None):
+    """`sph_train_targets` on the backends without a closed form (sph2pob_anchor_targets_any_f32: two launches for the batch)
+    against the per-image API it replaces — `SphMaxIoUAssigner.assign` on each image (the pairwise kernel into a (k, n) matrix,
+    then the three launches of the matrix epilogue) plus the torch target lines of `_get_targets_single` with their `nonzero`
+    synchronisations — both through the Python API, timed in alternation `rounds` times in this one process.  One JSON record per
+    backend; `loop_spread_us` over the rounds is the yardstick for the ratio.  No cull on either side: every pair is evaluated."""
+    import sph_retina_amd as S
+    anchors = retina_anchors(h, w)
+    n, K = anchors.size(0), images * num_gt
+    g = torch.Generator().manual_seed(0)
+    u = torch.rand((K, 5), generator=g)
+    gt5 = torch.stack([u[:, 0] * 300 + 30, 50 + u[:, 1] * 80, 10 + u[:, 2] * 35, 10 + u[:, 3] * 35, -40 + 80 * u[:, 4]], 1).cuda()
+    labels = torch.randint(0, 37, (K,), generator=g).cuda()
+    anchors5 = torch.cat([anchors, ((torch.arange(n, device='cuda') % 7) - 3.0).unsqueeze(1) * 10], 1).contiguous()
+    off = (torch.arange(images + 1) * num_gt).cuda()
+    out = []
+    for backend, dim in (backends or (('sph2pob_legacy_iou', 4), ('sph_iou', 4), ('fov_iou', 4), ('naive_iou', 4), ('naive_iou', 5),
+                                      ('unbiased_iou', 4), ('unbiased_iou', 5))):
+        cfg = dict(assigner=dict(type='MaxIoUAssigner', pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1,
+                                 iou_calculator=dict(type='SphOverlaps2D', backend=backend, box_version=dim)),
+                   allowed_border=-1, pos_weight=-1, debug=False)
+        a = S.SphMaxIoUAssigner(**{k: v for k, v in cfg['assigner'].items() if k != 'type'})
+        bx, gt = (anchors, gt5[:, :4].contiguous()) if dim == 4 else (anchors5, gt5)
+
+        def batched():
+            return S.sph_train_targets(bx, gt, labels, off, train_cfg=cfg, num_classes=37, k_max=num_gt)
+
+        def loop():
+            total, res = 0, []
+            for b in range(images):
+                gb, lb = gt[b * num_gt:(b + 1) * num_gt], labels[b * num_gt:(b + 1) * num_gt]
+                r = a.assign(bx, gb, gt_labels=lb)
+                pos = torch.nonzero(r.gt_inds > 0, as_tuple=False).squeeze(-1)
+                neg = torch.nonzero(r.gt_inds == 0, as_tuple=False).squeeze(-1)
+                bbox_targets, bbox_weights = torch.zeros_like(bx), torch.zeros_like(bx)
+                lab, lw = bx.new_full((n,), 37, dtype=torch.long), bx.new_zeros(n)
+                if len(pos) > 0:
+                    bbox_targets[pos] = gb[r.gt_inds[pos] - 1]
+                    bbox_weights[pos] = 1.0
+                    lab[pos] = lb[r.gt_inds[pos] - 1]
+                    lw[pos] = 1.0
+                if len(neg) > 0:
+                    lw[neg] = 1.0
+                total += max(len(pos), 1)
+                res.append((r.gt_inds, lab, bbox_targets))
+            return total, res
+        t = batched()
+        total, res = loop()
+        torch.cuda.synchronize()
+        equal = float(t.avg_factor) == float(total) and all(torch.equal(t.gt_inds[b], r[0]) and torch.equal(t.labels[b], r[1]) and
+                                                           torch.equal(t.bbox_targets[b], r[2]) for b, r in enumerate(res))
+        one = timeit(batched, warm=1, reps=1, settle_s=0.0)
+        reps = max(3, min(100, int(0.2 / max(one, 1e-6))))
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(timeit(batched, warm=2, reps=reps) * 1e6)
+            tb.append(timeit(loop, warm=2, reps=max(3, reps // 4)) * 1e6)
+        med = lambda v: float(np.median(v))   # noqa: E731
+        out.append({'config': 'train targets: %s dim %d, %d images x %d GT x %d anchors, Python API' % (backend, dim, images, num_gt, n),
+                    'batched_us': med(ta), 'loop_us': med(tb), 'batched_rounds_us': ta, 'loop_rounds_us': tb,
+                    'batched_spread_us': max(ta) - min(ta), 'loop_spread_us': max(tb) - min(tb), 'batched_over_loop': med(ta) / med(tb),
+                    'equal_to_loop': bool(equal), 'num_pos': t.num_pos.tolist()})
+        print(json.dumps(out[-1]), flush=True)
+    return {'config': 'train targets', 'backends': len(out)}
+
+
 def get_bboxes(images=8, rounds=7):
     """Detection post-processing for a minibatch (sph_get_bboxes) at the reference's test shape — 512 x 1024 ERP, 5 levels, 9
     anchors, 37 classes, nms_pre 1000, max_per_img 100 — on the head's NCHW outputs: (a) one eager call for the batch; (b) the
@@ -759,8 +825,8 @@ def gaussian(n=1_000_000):
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch get_bboxes focal bbox_loss delta_loss coder unbiased variants; none = all)
-    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, get_bboxes=get_bboxes, focal=focal, bbox_loss=bbox_loss, delta_loss=delta_loss, coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch train_targets get_bboxes focal bbox_loss delta_loss coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, train_targets=train_targets, get_bboxes=get_bboxes, focal=focal, bbox_loss=bbox_loss, delta_loss=delta_loss, coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)

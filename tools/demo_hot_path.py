@@ -103,7 +103,8 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
                      gt=gt, bbox_targets=bbox_targets)
 
 
-def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False):
+def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
+              train_cfg=None):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -111,7 +112,9 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     (B, n, 4) level — the plumbing, not the NCHW in-place read with 16-byte stores along w; that route is timed by
     `tools/bench_configs.py bbox_loss`.  `base_config=True` runs the reference's BASE configuration instead
     (`loss_bbox=dict(type='L1Loss')`, `reg_decoded_bbox=False`): encoded targets from `sph_anchor_targets`, `sph_delta_loss` on the
-    raw deltas, nothing decoded; its NCHW route is timed by `tools/bench_configs.py delta_loss`."""
+    raw deltas, nothing decoded; its NCHW route is timed by `tools/bench_configs.py delta_loss`.  With a `train_cfg` (the
+    reference's dict: its assigner with any SphOverlaps2D backend, pos_weight) the targets come from `sph_train_targets` under
+    that configuration, still one call and no synchronisation."""
     dev = 'cuda'
     g = torch.Generator().manual_seed(seed)
     anchors = retina_anchors()
@@ -121,6 +124,10 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
         u = torch.rand((k, 4), generator=g)
         gts.append(torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85], 1).to(dev))
         labels.append(torch.randint(0, num_classes, (k,), generator=g).to(dev))
+    if train_cfg is not None:   # reported below: the calculator the configuration names
+        a = train_cfg['assigner']
+        c = a['iou_calculator'] if isinstance(a, dict) else a.iou_calculator
+        backend = c.get('backend', 'unbiased_iou') if isinstance(c, dict) else c.backend
     assigner = S.SphMaxIoUAssigner(pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1,
                                    iou_calculator=dict(type='SphOverlaps2D', backend=backend, box_version=4))
     coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(1., 1., 1., 1.))
@@ -134,8 +141,12 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
         deltas.grad = None
         for c in cls_scores:
             c.grad = None
-        t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=num_classes, reg_decoded_bbox=not base_config,
-                                 bbox_coder=coder if base_config else None)
+        if train_cfg is not None:
+            t = S.sph_train_targets(anchors, gts, labels, train_cfg=train_cfg, num_classes=num_classes, reg_decoded_bbox=not base_config,
+                                    bbox_coder=coder if base_config else None)
+        else:
+            t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=num_classes, reg_decoded_bbox=not base_config,
+                                     bbox_coder=coder if base_config else None)
         if base_config:
             loss = S.sph_delta_loss([deltas.view(images, n, 4)], t.bbox_targets, t.bbox_weights, avg_factor=t.avg_factor)
         elif fused_reg:
