@@ -463,10 +463,10 @@ struct ClosedFormPair {
 };
 // every other variant: the function iou_pairwise_kernel runs for it in the default arithmetic with rbb_angle='equator' (`edge`
 // carries SPH2POB_FLAG_NAIVE_TAN as EDGE_TANGENT, as in the pairwise entry) — the reference-order core for legacy / Sph-IoU /
-// FoV-IoU, which have no other, the fast selection for the unbiased and the naive IoU
+// FoV-IoU, which have no other, the fast selection for the unbiased and the naive IoU (pair_sel_fast, sph2pob_iou_entry.hpp)
 template <int VARIANT, int DIM>
 __device__ __forceinline__ float per_pair_iou(const float (&g)[5], const float (&a)[5], int edge) {
-    return pair_iou_sel<VARIANT, DIM, (VARIANT >= VARIANT_UNBIASED)>(g, a, (int)MODE_IOU, edge, (int)ANGLE_EQUATOR);
+    return pair_iou_sel<VARIANT, DIM, pair_sel_fast(VARIANT, true, ANGLE_EQUATOR)>(g, a, (int)MODE_IOU, edge, (int)ANGLE_EQUATOR);
 }
 template <int VARIANT, int DIM>
 struct PerPairFunction {
@@ -882,13 +882,10 @@ struct PairwiseLaunch {
         const int64_t kMaxRows = 65535;
         for (int64_t r0 = 0; r0 < m; r0 += kMaxRows) {
             int64_t rows = m - r0 < kMaxRows ? m - r0 : kMaxRows;
-            auto go = [&](auto variant, auto fast_core) {
+            with_pair_sel<V>(fast, angle, [&](auto variant, auto fast_core) {
                 hipLaunchKernelGGL((iou_pairwise_kernel<decltype(variant)::value, D, decltype(fast_core)::value>), dim3((unsigned)col_tiles(n), (unsigned)rows),
                                    dim3(kBlock), 0, s, b1 + r0 * D, rows, b2, n, out + r0 * n, mode, edge, angle);
-            };
-            if (closed) go(std::integral_constant<int, closed_form(V)>{}, std::true_type{});
-            else if (V >= 5 && fast) go(std::integral_constant<int, (V >= 5 ? V : 5)>{}, std::true_type{});
-            else go(std::integral_constant<int, V>{}, std::false_type{});
+            });
             int rc = launch_status();
             if (rc) return rc;
         }
@@ -985,14 +982,9 @@ extern "C" {
 
 int sph2pob_iou_pairwise_f32(const float* b1, int64_t m, const float* b2, int64_t n, float* out, int box_dim,
                              int variant, int mode, int edge, int angle, void* stream) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    if (mode < 0 || mode > 1 || ((variant & 0xff) >= SPH2POB_VARIANT_UNBIASED && mode != SPH2POB_MODE_IOU)) return SPH2POB_ERR_OPTION;
-    if (m < 0 || n < 0 || n > kMaxElems || m > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (m == 0 || n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !out) return SPH2POB_ERR_NULL;
-    if (variant & SPH2POB_FLAG_NAIVE_TAN) edge = SPH2POB_EDGE_TANGENT;
-    return dispatch(variant, box_dim, PairwiseLaunch{b1, m, b2, n, out, mode, edge, angle, (hipStream_t)stream});
+    const int rc = check_iou(box_dim, variant, mode, edge, angle, m, n, {b1, b2, out});
+    if (rc || m == 0 || n == 0) return rc;
+    return dispatch(variant, box_dim, PairwiseLaunch{b1, m, b2, n, out, mode, naive_edge(variant, edge), angle, (hipStream_t)stream});
 }
 
 

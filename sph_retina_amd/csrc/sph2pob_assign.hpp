@@ -53,8 +53,8 @@ SPHA_DEV TargetRow target_row(int64_t a, const float* anchor, const float* g, co
     return r;
 }
 
-// ---- argument checks, in the documented order.  `rc` is what the library's check_common(box_dim, variant, edge, 0) answered (each
-// library has its own copy next to its dispatch()). ----
+// ---- argument checks, in the documented order.  `rc` is what check_common(box_dim, variant, edge, 0) answered
+// (sph2pob_iou_entry.hpp, next to dispatch()). ----
 inline int closed_form_only(int rc, int variant) {   // the kernels that carry the reductions: standard / efficient, closed form
     if (rc) return rc;
     return ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT || (variant & SPH2POB_FLAG_REFERENCE_ORDER)) ? SPH2POB_ERR_OPTION : SPH2POB_OK;

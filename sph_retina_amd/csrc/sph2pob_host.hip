@@ -23,6 +23,7 @@
 #include "sph2pob_loss.hpp"
 #include "sph2pob_fast.hpp"
 #include "sph2pob_unbiased.hpp"
+#include "sph2pob_iou_entry.hpp"
 #include "sph2pob_coder.hpp"
 #include "sph2pob_get_bboxes.hpp"
 #include "sph2pob_assign.hpp"
@@ -70,90 +71,53 @@ inline void load_box(const float* p, int64_t i, float (&b)[5]) {
     for (int k = 0; k < 5; k++) b[k] = k < DIM ? p[i * DIM + k] : 0.0f;
 }
 
-// the selection the kernels make (sph2pob_kernels_common.hpp: pair_iou_sel; sph2pob_iou.hip: the launch rules of AlignedLaunch)
-template <int V, int DIM>
-inline float pair_iou_any(const float (&x)[5], const float (&y)[5], bool fast, int mode, int edge, int angle) {
-    if constexpr (V == VARIANT_UNBIASED) return fast ? unbiased_pair_iou<DIM, false>(x, y) : unbiased_pair_iou<DIM, true>(x, y);
-    else if constexpr (V == VARIANT_NAIVE) return naive_iou<DIM>(x, y, edge == EDGE_TANGENT);
-    else if constexpr (V < 2) return (fast && angle == ANGLE_EQUATOR) ? pair_iou_fast<V, DIM>(x, y, mode, edge) : pair_iou<V, DIM>(x, y, mode, edge, angle);
-    else return pair_iou<V, DIM>(x, y, mode, edge, angle);
-}
-
-template <class F>
-int dispatch(int variant_flags, int box_dim, F&& f) {
-    const int v = variant_flags & 0xff;
-    f.fast = !(variant_flags & SPH2POB_FLAG_REFERENCE_ORDER);
-    switch (v) {
-        case SPH2POB_VARIANT_STANDARD: return box_dim == 4 ? f.template run<0, 4>() : f.template run<0, 5>();
-        case SPH2POB_VARIANT_EFFICIENT: return box_dim == 4 ? f.template run<1, 4>() : f.template run<1, 5>();
-        case SPH2POB_VARIANT_SPH_IOU: return f.template run<3, 4>();
-        case SPH2POB_VARIANT_FOV_IOU: return f.template run<4, 4>();
-        case SPH2POB_VARIANT_UNBIASED: return box_dim == 4 ? f.template run<5, 4>() : f.template run<5, 5>();
-        case SPH2POB_VARIANT_NAIVE: return box_dim == 4 ? f.template run<6, 4>() : f.template run<6, 5>();
-        default: return f.template run<2, 4>();
-    }
-}
-
-int check_common(int box_dim, int variant_flags, int edge, int angle) {
-    const int variant = variant_flags & 0xff;
-    if (variant_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER | SPH2POB_FLAG_ROBUST_PARALLEL | SPH2POB_FLAG_NAIVE_TAN)) return SPH2POB_ERR_OPTION;
-    if ((variant_flags & SPH2POB_FLAG_NAIVE_TAN) && variant != SPH2POB_VARIANT_NAIVE) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (variant < 0 || variant > SPH2POB_VARIANT_NAIVE || edge < 0 || edge > 2 || angle < 0 || angle > 1) return SPH2POB_ERR_OPTION;
-    if (variant >= SPH2POB_VARIANT_LEGACY && variant <= SPH2POB_VARIANT_FOV_IOU && box_dim == 5) return SPH2POB_ERR_DIM;
+// ---- the IoU / transform family: checks, dispatch(), the per-pair selection and the row bodies are sph2pob_iou_entry.hpp's, as
+// the kernels'; here are the loops.  row(e) for every e of [0, total) ----
+template <class Row>
+int for_rows(int64_t total, int64_t grain, Row&& row) {
+    parallel_for(total, grain, [&](int64_t lo, int64_t hi) {
+        for (int64_t e = lo; e < hi; e++) row(e);
+    });
     return SPH2POB_OK;
 }
-
-struct Aligned {
-    const float *b1, *b2; float* out; int64_t n; int mode, edge, angle; bool fast = true;
+// aligned (n == 0: out[e] of pair e) or pairwise (out[e] of row e / n and column e % n); the selection is made once per call
+struct PairIou {
+    const float *b1, *b2; float* out; int64_t total, n; int mode, edge, angle; bool fast = true;
     template <int V, int D> int run() {
-        parallel_for(n, 2048, [&](int64_t lo, int64_t hi) {
-            for (int64_t i = lo; i < hi; i++) {
+        return with_pair_sel<V>(fast, angle, [&](auto variant, auto fast_core) {
+            return for_rows(total, 2048, [&](int64_t e) {
                 float x[5], y[5];
-                load_box<D>(b1, i, x);
-                load_box<D>(b2, i, y);
-                out[i] = pair_iou_any<V, D>(x, y, fast, mode, edge, angle);
-            }
+                load_box<D>(b1, n ? e / n : e, x);
+                load_box<D>(b2, n ? e % n : e, y);
+                out[e] = pair_iou_sel<decltype(variant)::value, D, decltype(fast_core)::value>(x, y, mode, edge, angle);
+            });
         });
-        return SPH2POB_OK;
-    }
-};
-struct Pairwise {
-    const float* b1; int64_t m; const float* b2; int64_t n; float* out; int mode, edge, angle; bool fast = true;
-    template <int V, int D> int run() {
-        parallel_for(m * n, 2048, [&](int64_t lo, int64_t hi) {
-            for (int64_t e = lo; e < hi; e++) {
-                float x[5], y[5];
-                load_box<D>(b1, e / n, x);
-                load_box<D>(b2, e % n, y);
-                out[e] = pair_iou_any<V, D>(x, y, fast, mode, edge, angle);
-            }
-        });
-        return SPH2POB_OK;
     }
 };
 struct Transform {
     const float *b1, *b2; float *o1, *o2; int64_t n; int edge, angle, jitter; bool fast = true;
     template <int V, int D> int run() {
-        if constexpr (V > 2) return SPH2POB_ERR_OPTION;
-        else {
-            parallel_for(n, 2048, [&](int64_t lo, int64_t hi) {
-                for (int64_t i = lo; i < hi; i++) {
-                    float x[5], y[5];
-                    load_box<D>(b1, i, x);
-                    load_box<D>(b2, i, y);
-                    if (jitter) jitter_spherical<D>(x, y);
-                    PBox p1, p2;
-                    transform<V, D>(x, y, edge, angle, p1, p2);
-                    if (jitter) jitter_rotated(p1, p2);
-                    float* q1 = o1 + i * 5;
-                    float* q2 = o2 + i * 5;
-                    q1[0] = p1.x; q1[1] = p1.y; q1[2] = p1.w; q1[3] = p1.h; q1[4] = p1.a;
-                    q2[0] = p2.x; q2[1] = p2.y; q2[2] = p2.w; q2[3] = p2.h; q2[4] = p2.a;
-                }
-            });
-            return SPH2POB_OK;
-        }
+        if constexpr (V > VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
+        else return for_rows(n, 2048, [&](int64_t i) {
+            float x[5], y[5];
+            load_box<D>(b1, i, x);
+            load_box<D>(b2, i, y);
+            transform_row<V, D>(x, y, edge, angle, jitter, o1 + i * 5, o2 + i * 5);
+        });
+    }
+};
+// the two adjoints (sph2pob_transform_bwd_f32 / _general_f32): the closed form or, DUAL, the dual-number one
+template <bool DUAL>
+struct TransformBwd {
+    const float *b1, *b2, *g1, *g2; float *gb1, *gb2; int64_t n; int edge, angle, jitter; bool fast = true;
+    template <int V, int D> int run() {
+        if constexpr (V > (DUAL ? VARIANT_LEGACY : VARIANT_EFFICIENT)) return SPH2POB_ERR_OPTION;
+        else return for_rows(n, DUAL ? 512 : 1024, [&](int64_t i) {
+            float x[5], y[5];
+            load_box<D>(b1, i, x);
+            load_box<D>(b2, i, y);
+            transform_bwd_row<V, D, DUAL>(x, y, g1 + i * 5, g2 + i * 5, edge, angle, jitter, gb1 + i * D, gb2 + i * D);
+        });
     }
 };
 
@@ -256,8 +220,8 @@ struct NmsRun {
                 if (i == 0 || (cls && cls[i] != cls[i - 1])) starts.push_back(i);
             starts.push_back(k);
             const int64_t segs = (int64_t)starts.size() - 1;
-            parallel_for(segs, 1, [&](int64_t lo, int64_t hi) {
-                for (int64_t s = lo; s < hi; s++) {
+            return with_pair_sel<V>(fast, ANGLE_EQUATOR, [&](auto variant, auto fast_core) {
+                return for_rows(segs, 1, [&](int64_t s) {
                     const int64_t a = starts[(size_t)s], b = starts[(size_t)s + 1];
                     std::vector<unsigned char> removed((size_t)(b - a), 0);
                     for (int64_t i = a; i < b; i++) {
@@ -269,12 +233,12 @@ struct NmsRun {
                             if (removed[(size_t)(j - a)]) continue;
                             float y[5];
                             load_box<D>(boxes, j, y);
-                            if (!(pair_iou_any<V, D>(x, y, fast, MODE_IOU, edge, ANGLE_EQUATOR) <= thr)) removed[(size_t)(j - a)] = 1;
+                            if (!(pair_iou_sel<decltype(variant)::value, D, decltype(fast_core)::value>(x, y, MODE_IOU, edge, ANGLE_EQUATOR) <= thr))
+                                removed[(size_t)(j - a)] = 1;
                         }
                     }
-                }
+                });
             });
-            return SPH2POB_OK;
         }
     }
 };
@@ -288,53 +252,31 @@ int sph2pob_host_threads(void) { return cpu_threads(); }
 
 int sph2pob_iou_aligned_f32_cpu(const float* b1, const float* b2, float* out, int64_t n, int box_dim, int variant, int mode, int edge,
                                 int angle, void*) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    if (mode < 0 || mode > 1 || ((variant & 0xff) >= SPH2POB_VARIANT_UNBIASED && mode != SPH2POB_MODE_IOU)) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !out) return SPH2POB_ERR_NULL;
-    if (variant & SPH2POB_FLAG_NAIVE_TAN) edge = SPH2POB_EDGE_TANGENT;
-    return dispatch(variant, box_dim, Aligned{b1, b2, out, n, mode, edge, angle});
+    const int rc = check_iou(box_dim, variant, mode, edge, angle, n, n, {b1, b2, out});
+    if (rc || n == 0) return rc;
+    return dispatch(variant, box_dim, PairIou{b1, b2, out, n, 0, mode, naive_edge(variant, edge), angle});
 }
 
 int sph2pob_iou_pairwise_f32_cpu(const float* b1, int64_t m, const float* b2, int64_t n, float* out, int box_dim, int variant, int mode,
                                  int edge, int angle, void*) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    if (mode < 0 || mode > 1 || ((variant & 0xff) >= SPH2POB_VARIANT_UNBIASED && mode != SPH2POB_MODE_IOU)) return SPH2POB_ERR_OPTION;
-    if (m < 0 || n < 0 || n > kMaxElems || m > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (m == 0 || n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !out) return SPH2POB_ERR_NULL;
-    if (variant & SPH2POB_FLAG_NAIVE_TAN) edge = SPH2POB_EDGE_TANGENT;
-    return dispatch(variant, box_dim, Pairwise{b1, m, b2, n, out, mode, edge, angle});
+    const int rc = check_iou(box_dim, variant, mode, edge, angle, m, n, {b1, b2, out});
+    if (rc || m == 0 || n == 0) return rc;
+    return dispatch(variant, box_dim, PairIou{b1, b2, out, m * n, n, mode, naive_edge(variant, edge), angle});
 }
 
 int sph2pob_transform_f32_cpu(const float* b1, const float* b2, float* planar1, float* planar2, int64_t n, int box_dim, int variant,
                               int edge, int angle, int jitter, void*) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !planar1 || !planar2) return SPH2POB_ERR_NULL;
+    const int rc = check_transform(box_dim, variant, SPH2POB_VARIANT_LEGACY, edge, angle, n, {b1, b2, planar1, planar2});
+    if (rc || n == 0) return rc;
     return dispatch(variant, box_dim, Transform{b1, b2, planar1, planar2, n, edge, angle, jitter});
 }
 
 int sph2pob_planar_iou_f32_cpu(const float* p1, int64_t m, const float* p2, int64_t n, float* out, int aligned, int mode, void*) {
-    if (mode < 0 || mode > 1) return SPH2POB_ERR_OPTION;
-    if (m < 0 || n < 0 || m > kMaxElems || n > kMaxElems || (aligned && m != n)) return SPH2POB_ERR_SIZE;
-    if (m == 0 || n == 0) return SPH2POB_OK;
-    if (!p1 || !p2 || !out) return SPH2POB_ERR_NULL;
-    const int64_t total = aligned ? n : m * n;
-    parallel_for(total, 4096, [&](int64_t lo, int64_t hi) {
-        for (int64_t e = lo; e < hi; e++) {
-            const float* a = p1 + (aligned ? e : e / n) * 5;
-            const float* b = p2 + (aligned ? e : e % n) * 5;
-            out[e] = planar_iou_given(PBox{a[0], a[1], a[2], a[3], a[4]}, PBox{b[0], b[1], b[2], b[3], b[4]}, mode);
-        }
+    const int rc = check_planar_iou(p1, m, p2, n, out, aligned, mode);
+    if (rc || m == 0 || n == 0) return rc;
+    return for_rows(aligned ? n : m * n, 4096, [&](int64_t e) {
+        out[e] = planar_pair(p1 + (aligned ? e : e / n) * 5, p2 + (aligned ? e : e % n) * 5, mode);
     });
-    return SPH2POB_OK;
 }
 
 int sph2pob_loss_fwd_f32_cpu(const float* pred, const float* target, const float* weight, int weight_dim, float scale, float* loss,
@@ -418,63 +360,18 @@ int sph2pob_sum_f32_cpu(const float* x, int64_t n, float scale, float* out, floa
     return SPH2POB_OK;
 }
 
-// adjoint of the transforms (sph2pob_transform_bwd_f32 / _general_f32)
 int sph2pob_transform_bwd_f32_cpu(const float* b1, const float* b2, const float* g1, const float* g2, float* gb1, float* gb2, int64_t n,
                                   int box_dim, int variant, int edge, int jitter, void*) {
-    int rc = check_common(box_dim, variant, edge, 0);
-    if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !g1 || !g2 || !gb1 || !gb2) return SPH2POB_ERR_NULL;
-    auto body = [&](auto vtag, auto dtag) {
-        constexpr int V = decltype(vtag)::value, D = decltype(dtag)::value;
-        parallel_for(n, 1024, [&](int64_t lo, int64_t hi) {
-            for (int64_t i = lo; i < hi; i++) {
-                float x[5], y[5], p[5], q[5], gx[5], gy[5];
-                load_box<D>(b1, i, x);
-                load_box<D>(b2, i, y);
-                for (int k = 0; k < 5; k++) { p[k] = g1[i * 5 + k]; q[k] = g2[i * 5 + k]; }
-                pair_transform_bwd<V, D>(x, y, p, q, edge, jitter != 0, gx, gy);
-                for (int k = 0; k < D; k++) { gb1[i * D + k] = gx[k]; gb2[i * D + k] = gy[k]; }
-            }
-        });
-    };
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-    using I4 = std::integral_constant<int, 4>; using I5 = std::integral_constant<int, 5>;
-    if ((variant & 0xff) == 0) { if (box_dim == 4) body(I0{}, I4{}); else body(I0{}, I5{}); }
-    else { if (box_dim == 4) body(I1{}, I4{}); else body(I1{}, I5{}); }
-    return SPH2POB_OK;
+    const int rc = check_transform(box_dim, variant, SPH2POB_VARIANT_EFFICIENT, edge, 0, n, {b1, b2, g1, g2, gb1, gb2});
+    if (rc || n == 0) return rc;
+    return dispatch(variant, box_dim, TransformBwd<false>{b1, b2, g1, g2, gb1, gb2, n, edge, 0, jitter});
 }
 
 int sph2pob_transform_bwd_general_f32_cpu(const float* b1, const float* b2, const float* g1, const float* g2, float* gb1, float* gb2,
                                           int64_t n, int box_dim, int variant, int edge, int angle, int jitter, void*) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !g1 || !g2 || !gb1 || !gb2) return SPH2POB_ERR_NULL;
-    auto body = [&](auto vtag, auto dtag) {
-        constexpr int V = decltype(vtag)::value, D = decltype(dtag)::value;
-        parallel_for(n, 512, [&](int64_t lo, int64_t hi) {
-            for (int64_t i = lo; i < hi; i++) {
-                float x[5], y[5], p[5], q[5], gx[5], gy[5];
-                load_box<D>(b1, i, x);
-                load_box<D>(b2, i, y);
-                for (int k = 0; k < 5; k++) { p[k] = g1[i * 5 + k]; q[k] = g2[i * 5 + k]; }
-                transform_bwd_dual<V, D>(x, y, p, q, edge, angle, jitter != 0, gx, gy);
-                for (int k = 0; k < D; k++) { gb1[i * D + k] = gx[k]; gb2[i * D + k] = gy[k]; }
-            }
-        });
-    };
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-    using I4 = std::integral_constant<int, 4>; using I5 = std::integral_constant<int, 5>;
-    const int v = variant & 0xff;
-    if (v == 0) { if (box_dim == 4) body(I0{}, I4{}); else body(I0{}, I5{}); }
-    else if (v == 1) { if (box_dim == 4) body(I1{}, I4{}); else body(I1{}, I5{}); }
-    else body(I2{}, I4{});
-    return SPH2POB_OK;
+    const int rc = check_transform(box_dim, variant, SPH2POB_VARIANT_LEGACY, edge, angle, n, {b1, b2, g1, g2, gb1, gb2});
+    if (rc || n == 0) return rc;
+    return dispatch(variant, box_dim, TransformBwd<true>{b1, b2, g1, g2, gb1, gb2, n, edge, angle, jitter});
 }
 
 // ---- NMS on boxes sorted by (class, -score): sph2pob_nms_segmented_f32 / sph2pob_nms_f32 ----
@@ -485,8 +382,7 @@ int sph2pob_nms_segmented_f32_cpu(const float* boxes_sorted, const int64_t* cls_
     if (k < 0) return SPH2POB_ERR_SIZE;
     if (k == 0) return SPH2POB_OK;
     if (!boxes_sorted || !keep) return SPH2POB_ERR_NULL;
-    return dispatch(variant_flags, box_dim, NmsRun{boxes_sorted, cls_sorted, k, iou_threshold, keep,
-                                                   (variant_flags & SPH2POB_FLAG_NAIVE_TAN) ? (int)EDGE_TANGENT : (int)EDGE_ARC});
+    return dispatch(variant_flags, box_dim, NmsRun{boxes_sorted, cls_sorted, k, iou_threshold, keep, naive_edge(variant_flags, EDGE_ARC)});
 }
 int sph2pob_nms_f32_cpu(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim, int variant_flags, float iou_threshold,
                         void* workspace, unsigned char* keep, void* stream) {

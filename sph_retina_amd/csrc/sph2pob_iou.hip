@@ -509,29 +509,17 @@ __global__ __launch_bounds__(kBlock) void transform_kernel(const float* __restri
     float x[5], y[5];
     load_box<DIM>(b1, i, x);
     load_box<DIM>(b2, i, y);
-    if (jitter) jitter_spherical<DIM>(x, y);
-    PBox p1, p2;
-    transform<VARIANT, DIM>(x, y, edge, angle, p1, p2);
-    if (jitter) jitter_rotated(p1, p2);
-    float* q1 = o1 + i * 5;
-    float* q2 = o2 + i * 5;
-    q1[0] = p1.x; q1[1] = p1.y; q1[2] = p1.w; q1[3] = p1.h; q1[4] = p1.a;
-    q2[0] = p2.x; q2[1] = p2.y; q2[2] = p2.w; q2[3] = p2.h; q2[4] = p2.a;
+    transform_row<VARIANT, DIM>(x, y, edge, angle, jitter, o1 + i * 5, o2 + i * 5);
 }
 
 
 // ---- planar rotated IoU on given planar boxes (mmcv box_iou_rotated / diff_iou_rotated_2d values) ----
-// planar_iou_given, not planar_iou: no jitter runs in front of this entry, so coincident and near-parallel edges are its
-// everyday input (sph2pob_device.hpp)
 __global__ __launch_bounds__(kBlock) void planar_iou_kernel(const float* __restrict__ p1, int64_t m, const float* __restrict__ p2,
                                                            int64_t n, float* __restrict__ out, int aligned, int mode) {
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int64_t i = aligned ? j : (int64_t)blockIdx.y;
     if (j >= n) return;
-    const float* a = p1 + i * 5;
-    const float* b = p2 + j * 5;
-    const PBox A{a[0], a[1], a[2], a[3], a[4]}, B{b[0], b[1], b[2], b[3], b[4]};
-    out[aligned ? j : i * n + j] = planar_iou_given(A, B, mode);
+    out[aligned ? j : i * n + j] = planar_pair(p1 + i * 5, p2 + j * 5, mode);
 }
 
 // ---- adjoint of the Sph2Pob transform: gradients of the planar boxes -> gradients of the spherical boxes ----
@@ -542,14 +530,10 @@ __global__ __launch_bounds__(kBlock) void transform_bwd_kernel(const float* __re
                                                               int edge, int jitter) {
     int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    float x[5], y[5], gx[5], gy[5], p[5], q[5];
+    float x[5], y[5];
     load_box<DIM>(b1, i, x);
     load_box<DIM>(b2, i, y);
-#pragma unroll
-    for (int k = 0; k < 5; k++) { p[k] = g1[i * 5 + k]; q[k] = g2[i * 5 + k]; }
-    pair_transform_bwd<VARIANT, DIM>(x, y, p, q, edge, jitter != 0, gx, gy);
-#pragma unroll
-    for (int k = 0; k < DIM; k++) { gb1[i * DIM + k] = gx[k]; gb2[i * DIM + k] = gy[k]; }
+    transform_bwd_row<VARIANT, DIM, false>(x, y, g1 + i * 5, g2 + i * 5, edge, 0, jitter, gb1 + i * DIM, gb2 + i * DIM);
 }
 
 // adjoint of the reference-order transforms by forward-mode differentiation (legacy, rbb_angle='project')
@@ -560,14 +544,10 @@ __global__ __launch_bounds__(kBlock) void transform_bwd_dual_kernel(const float*
                                                                    int edge, int angle, int jitter) {
     int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    float x[5], y[5], gx[5], gy[5], p[5], q[5];
+    float x[5], y[5];
     load_box<DIM>(b1, i, x);
     load_box<DIM>(b2, i, y);
-#pragma unroll
-    for (int k = 0; k < 5; k++) { p[k] = g1[i * 5 + k]; q[k] = g2[i * 5 + k]; }
-    transform_bwd_dual<VARIANT, DIM>(x, y, p, q, edge, angle, jitter != 0, gx, gy);
-#pragma unroll
-    for (int k = 0; k < DIM; k++) { gb1[i * DIM + k] = gx[k]; gb2[i * DIM + k] = gy[k]; }
+    transform_bwd_row<VARIANT, DIM, true>(x, y, g1 + i * 5, g2 + i * 5, edge, angle, jitter, gb1 + i * DIM, gb2 + i * DIM);
 }
 
 struct AlignedLaunch {
@@ -619,12 +599,11 @@ struct AlignedLaunch {
             else if (edge == SPH2POB_EDGE_ARC) { if (g_prefetch) SPH_PIPE(true, true, false); else SPH_PIPE(false, true, false); }
             else { if (g_prefetch) SPH_PIPE(true, false, false); else SPH_PIPE(false, false, false); }
 #undef SPH_PIPE
-        } else if (fast && V < 2 && angle == SPH2POB_ANGLE_EQUATOR)
-            hipLaunchKernelGGL((iou_aligned_kernel<V >= 2 ? 0 : V, D, true>), grid, dim3(kBlock), 0, s, b1, b2, out, n, mode, edge, angle);
-        else if (V >= 5 && fast)  // unbiased / naive: `fast` selects the default (double) arithmetic of the unbiased IoU
-            hipLaunchKernelGGL((iou_aligned_kernel<V >= 5 ? V : 5, D, true>), grid, dim3(kBlock), 0, s, b1, b2, out, n, mode, edge, angle);
-        else
-            hipLaunchKernelGGL((iou_aligned_kernel<V, D, false>), grid, dim3(kBlock), 0, s, b1, b2, out, n, mode, edge, angle);
+        } else
+            with_pair_sel<V>(fast, angle, [&](auto variant, auto fast_core) {
+                hipLaunchKernelGGL((iou_aligned_kernel<decltype(variant)::value, D, decltype(fast_core)::value>), grid, dim3(kBlock), 0, s, b1, b2,
+                                   out, n, mode, edge, angle);
+            });
         return launch_status();
     }
 };
@@ -635,6 +614,20 @@ struct TransformLaunch {
         else {
             dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
             hipLaunchKernelGGL((transform_kernel<V, D>), grid, dim3(kBlock), 0, s, b1, b2, o1, o2, n, edge, angle, jitter);
+            return launch_status();
+        }
+    }
+};
+// the two adjoints: the closed form (standard / efficient) or, DUAL, the dual-number one (legacy too)
+template <bool DUAL>
+struct TransformBwdLaunch {
+    const float *b1, *b2, *g1, *g2; float *gb1, *gb2; int64_t n; int edge, angle, jitter; hipStream_t s; bool fast = true;
+    template <int V, int D> int run() {
+        if constexpr (V > (DUAL ? VARIANT_LEGACY : VARIANT_EFFICIENT)) return SPH2POB_ERR_OPTION;
+        else {
+            dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+            if constexpr (DUAL) hipLaunchKernelGGL((transform_bwd_dual_kernel<V, D>), grid, dim3(kBlock), 0, s, b1, b2, g1, g2, gb1, gb2, n, edge, angle, jitter);
+            else hipLaunchKernelGGL((transform_bwd_kernel<V, D>), grid, dim3(kBlock), 0, s, b1, b2, g1, g2, gb1, gb2, n, edge, jitter);
             return launch_status();
         }
     }
@@ -661,35 +654,23 @@ const char* sph2pob_error_string(int code) {
 
 int sph2pob_iou_aligned_f32(const float* b1, const float* b2, float* out, int64_t n, int box_dim, int variant,
                             int mode, int edge, int angle, void* stream) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    if (mode < 0 || mode > 1 || ((variant & 0xff) >= SPH2POB_VARIANT_UNBIASED && mode != SPH2POB_MODE_IOU)) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !out) return SPH2POB_ERR_NULL;
-    if (variant & SPH2POB_FLAG_NAIVE_TAN) edge = SPH2POB_EDGE_TANGENT;
-    return dispatch(variant, box_dim, AlignedLaunch{b1, b2, out, n, mode, edge, angle, (hipStream_t)stream});
+    const int rc = check_iou(box_dim, variant, mode, edge, angle, n, n, {b1, b2, out});
+    if (rc || n == 0) return rc;
+    return dispatch(variant, box_dim, AlignedLaunch{b1, b2, out, n, mode, naive_edge(variant, edge), angle, (hipStream_t)stream});
 }
-
 
 int sph2pob_transform_f32(const float* b1, const float* b2, float* planar1, float* planar2, int64_t n,
                           int box_dim, int variant, int edge, int angle, int jitter, void* stream) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !planar1 || !planar2) return SPH2POB_ERR_NULL;
+    const int rc = check_transform(box_dim, variant, SPH2POB_VARIANT_LEGACY, edge, angle, n, {b1, b2, planar1, planar2});
+    if (rc || n == 0) return rc;
     return dispatch(variant, box_dim,
                     TransformLaunch{b1, b2, planar1, planar2, n, edge, angle, jitter, (hipStream_t)stream});
 }
 
 int sph2pob_planar_iou_f32(const float* p1, int64_t m, const float* p2, int64_t n, float* out, int aligned, int mode,
                            void* stream) {
-    if (mode < 0 || mode > 1) return SPH2POB_ERR_OPTION;
-    if (m < 0 || n < 0 || m > kMaxElems || n > kMaxElems || (aligned && m != n)) return SPH2POB_ERR_SIZE;
-    if (m == 0 || n == 0) return SPH2POB_OK;
-    if (!p1 || !p2 || !out) return SPH2POB_ERR_NULL;
+    const int rc = check_planar_iou(p1, m, p2, n, out, aligned, mode);
+    if (rc || m == 0 || n == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
     const unsigned bx = (unsigned)((n + kBlock - 1) / kBlock);
     if (aligned) {
@@ -701,8 +682,7 @@ int sph2pob_planar_iou_f32(const float* p1, int64_t m, const float* p2, int64_t 
         const int64_t rows = m - r0 < kMaxRows ? m - r0 : kMaxRows;
         hipLaunchKernelGGL(planar_iou_kernel, dim3(bx, (unsigned)rows), dim3(kBlock), 0, s, p1 + r0 * 5, rows, p2, n,
                            out + r0 * n, 0, mode);
-        const int rc = launch_status();
-        if (rc) return rc;
+        if (const int launched = launch_status()) return launched;
     }
     return SPH2POB_OK;
 }
@@ -710,41 +690,19 @@ int sph2pob_planar_iou_f32(const float* p1, int64_t m, const float* p2, int64_t 
 int sph2pob_transform_bwd_f32(const float* b1, const float* b2, const float* grad_planar1, const float* grad_planar2,
                               float* grad_b1, float* grad_b2, int64_t n, int box_dim, int variant, int edge, int jitter,
                               void* stream) {
-    int rc = check_common(box_dim, variant, edge, 0);
-    if (rc) return rc;
-    if ((variant & 0xff) > SPH2POB_VARIANT_EFFICIENT) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !grad_planar1 || !grad_planar2 || !grad_b1 || !grad_b2) return SPH2POB_ERR_NULL;
-    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    hipStream_t s = (hipStream_t)stream;
-#define SPH_TBWD(V, D) \
-    hipLaunchKernelGGL((transform_bwd_kernel<V, D>), grid, dim3(kBlock), 0, s, b1, b2, grad_planar1, grad_planar2, grad_b1, grad_b2, n, edge, jitter)
-    if ((variant & 0xff) == SPH2POB_VARIANT_STANDARD) { if (box_dim == 4) SPH_TBWD(0, 4); else SPH_TBWD(0, 5); }
-    else { if (box_dim == 4) SPH_TBWD(1, 4); else SPH_TBWD(1, 5); }
-#undef SPH_TBWD
-    return launch_status();
+    const int rc = check_transform(box_dim, variant, SPH2POB_VARIANT_EFFICIENT, edge, 0, n, {b1, b2, grad_planar1, grad_planar2, grad_b1, grad_b2});
+    if (rc || n == 0) return rc;
+    return dispatch(variant, box_dim,
+                    TransformBwdLaunch<false>{b1, b2, grad_planar1, grad_planar2, grad_b1, grad_b2, n, edge, 0, jitter, (hipStream_t)stream});
 }
 
 int sph2pob_transform_bwd_general_f32(const float* b1, const float* b2, const float* grad_planar1,
                                       const float* grad_planar2, float* grad_b1, float* grad_b2, int64_t n, int box_dim,
                                       int variant, int edge, int angle, int jitter, void* stream) {
-    int rc = check_common(box_dim, variant, edge, angle);
-    if (rc) return rc;
-    const int v = variant & 0xff;
-    if (v > SPH2POB_VARIANT_LEGACY) return SPH2POB_ERR_OPTION;
-    if (n < 0 || n > kMaxElems) return SPH2POB_ERR_SIZE;
-    if (n == 0) return SPH2POB_OK;
-    if (!b1 || !b2 || !grad_planar1 || !grad_planar2 || !grad_b1 || !grad_b2) return SPH2POB_ERR_NULL;
-    dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    hipStream_t s = (hipStream_t)stream;
-#define SPH_TBWDD(V, D) \
-    hipLaunchKernelGGL((transform_bwd_dual_kernel<V, D>), grid, dim3(kBlock), 0, s, b1, b2, grad_planar1, grad_planar2, grad_b1, grad_b2, n, edge, angle, jitter)
-    if (v == SPH2POB_VARIANT_LEGACY) SPH_TBWDD(2, 4);
-    else if (v == SPH2POB_VARIANT_STANDARD) { if (box_dim == 4) SPH_TBWDD(0, 4); else SPH_TBWDD(0, 5); }
-    else { if (box_dim == 4) SPH_TBWDD(1, 4); else SPH_TBWDD(1, 5); }
-#undef SPH_TBWDD
-    return launch_status();
+    const int rc = check_transform(box_dim, variant, SPH2POB_VARIANT_LEGACY, edge, angle, n, {b1, b2, grad_planar1, grad_planar2, grad_b1, grad_b2});
+    if (rc || n == 0) return rc;
+    return dispatch(variant, box_dim,
+                    TransformBwdLaunch<true>{b1, b2, grad_planar1, grad_planar2, grad_b1, grad_b2, n, edge, angle, jitter, (hipStream_t)stream});
 }
 
 // Not part of the ABI (tests): the store form that SPH2POB_CHUNK_STORES forced when this copy was loaded: 0 none (the launcher's

@@ -1,6 +1,6 @@
-// Shared by the translation units of libsph2pob_hip.so (sph2pob_{iou,assign,loss,nms}.hip): constants, launch knobs, box loads,
-// the (VARIANT, DIM) dispatch and the argument checks every entry point starts with (the kMaxElems bound is sph2pob_loss.hpp's,
-// shared with the host twins).  Internal: include/sph2pob_hip.h is the ABI.
+// Shared by the translation units of libsph2pob_hip.so (sph2pob_{iou,assign,loss,nms}.hip): constants, launch knobs, box loads and
+// wave helpers.  The (VARIANT, DIM) dispatch, the argument checks every entry point starts with and the choice of a pair's IoU
+// function are sph2pob_iou_entry.hpp's, shared with the host twins.  Internal: include/sph2pob_hip.h is the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,6 +12,7 @@
 #include "sph2pob_loss.hpp"
 #include "sph2pob_fast.hpp"
 #include "sph2pob_unbiased.hpp"
+#include "sph2pob_iou_entry.hpp"
 
 namespace {
 
@@ -52,16 +53,6 @@ __device__ __forceinline__ void load_box(const float* __restrict__ p, int64_t i,
     }
 }
 
-// FAST: the closed-form core of sph2pob_fast.hpp (standard / efficient with rbb_angle='equator'); otherwise the
-// reference-order path of sph2pob_device.hpp (legacy, rbb_angle='project').
-template <int VARIANT, int DIM, bool FAST>
-__device__ __forceinline__ float pair_iou_sel(const float (&x)[5], const float (&y)[5], int mode, int edge, int angle) {
-    if constexpr (VARIANT == VARIANT_UNBIASED) return unbiased_pair_iou<DIM, !FAST>(x, y);
-    else if constexpr (VARIANT == VARIANT_NAIVE) return naive_iou<DIM>(x, y, edge == EDGE_TANGENT);   // (edge carries SPH2POB_FLAG_NAIVE_TAN)
-    else if constexpr (FAST) return pair_iou_fast<VARIANT, DIM>(x, y, mode, edge);
-    else return pair_iou<VARIANT, DIM>(x, y, mode, edge, angle);
-}
-
 constexpr int kQCap = 128;                    // per-wave survivor stack capacity (<= 63 carried + 64 pushed)
 
 // number of set bits of a wave mask below this lane: v_mbcnt_lo + v_mbcnt_hi (the 64-bit shift / and / popcount form
@@ -72,31 +63,6 @@ __device__ __forceinline__ int rank_below(unsigned long long m) {
 __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-}
-
-inline int check_common(int box_dim, int variant_flags, int edge, int angle) {
-    const int variant = variant_flags & 0xff;
-    if (variant_flags & ~(0xff | SPH2POB_FLAG_REFERENCE_ORDER | SPH2POB_FLAG_ROBUST_PARALLEL | SPH2POB_FLAG_NAIVE_TAN)) return SPH2POB_ERR_OPTION;
-    if ((variant_flags & SPH2POB_FLAG_NAIVE_TAN) && variant != SPH2POB_VARIANT_NAIVE) return SPH2POB_ERR_OPTION;
-    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
-    if (variant < 0 || variant > SPH2POB_VARIANT_NAIVE || edge < 0 || edge > 2 || angle < 0 || angle > 1) return SPH2POB_ERR_OPTION;
-    if (variant >= SPH2POB_VARIANT_LEGACY && variant <= SPH2POB_VARIANT_FOV_IOU && box_dim == 5)
-        return SPH2POB_ERR_DIM;  // BFoV-only variants
-    return SPH2POB_OK;
-}
-
-// dispatch a (VARIANT, DIM) pair to a functor
-template <typename F>
-int dispatch(int variant_flags, int box_dim, F&& f) {
-    const int variant = variant_flags & 0xff;
-    f.fast = !(variant_flags & SPH2POB_FLAG_REFERENCE_ORDER);   // SPH2POB_FLAG_ROBUST_PARALLEL: accepted, always on now
-    if (variant == SPH2POB_VARIANT_STANDARD) return box_dim == 4 ? f.template run<0, 4>() : f.template run<0, 5>();
-    if (variant == SPH2POB_VARIANT_EFFICIENT) return box_dim == 4 ? f.template run<1, 4>() : f.template run<1, 5>();
-    if (variant == SPH2POB_VARIANT_SPH_IOU) return f.template run<3, 4>();
-    if (variant == SPH2POB_VARIANT_FOV_IOU) return f.template run<4, 4>();
-    if (variant == SPH2POB_VARIANT_UNBIASED) return box_dim == 4 ? f.template run<5, 4>() : f.template run<5, 5>();
-    if (variant == SPH2POB_VARIANT_NAIVE) return box_dim == 4 ? f.template run<6, 4>() : f.template run<6, 5>();
-    return f.template run<2, 4>();
 }
 
 }  // namespace

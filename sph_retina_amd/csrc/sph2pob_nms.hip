@@ -595,7 +595,7 @@ int64_t nms_row_words(int64_t k, int64_t max_segment) {
     return seg < full ? seg : full;
 }
 static_assert((63 + (kNmsMaxWords * 64 - 64) + 63) / 64 == kNmsMaxWords, "the longest segment fits kNmsMaxWords words at any offset");
-int nms_edge(int variant_flags) { return (variant_flags & SPH2POB_FLAG_NAIVE_TAN) ? (int)EDGE_TANGENT : (int)EDGE_ARC; }
+int nms_edge(int variant_flags) { return naive_edge(variant_flags, EDGE_ARC); }   // the NMS entries take no edge: arc
 
 // The size classes of the rank sort (nms_prepare_* and nms_select_*, single image and batched: the same class for the same k).
 // T keys per lane x BS threads cover the candidates, IPW boxes per workgroup, chosen so that the grid is at most 256

@@ -345,3 +345,32 @@ def test_gpu_unbiased_nms_compaction_never_changes_a_decision(dim, thr):
     if dim == 4 and thr > 0:   # ... including near-degenerate boxes that touch nothing (the far value alone removed them)
         tiny = set(range(0, k, 25)) - set(range(7, k, 90))
         assert len(tiny - set(want)) > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dim', [4, 5])
+@pytest.mark.parametrize('tan', [0, 0x400])
+def test_gpu_naive_has_one_kernel_whatever_the_reference_order_flag(dim, tan):
+    """The naive IoU has one arithmetic: SPH2POB_FLAG_REFERENCE_ORDER selects the same kernel (pair_sel_fast,
+    csrc/sph2pob_iou_entry.hpp), so the aligned and the pairwise entry give the same bits with and without it, with and without
+    SPH2POB_FLAG_NAIVE_TAN, and agree with the CPU twin as closely as the formator test above asks (2e-6).  n = 300: one full
+    256-thread block and a tail."""
+    from sph_retina_amd import _lib, _torch_glue as G
+    g = load_golden('naive')
+    n, m, variant = 300, 3, 6 | tan
+    h1, h2 = (torch.from_numpy(np.ascontiguousarray(g[k][:n, :dim])) for k in ('b1', 'b2'))
+    d1, d2 = h1.cuda(), h2.cuda()
+    st = G.raw_stream_of(d1.device)
+    dev, host = _lib.lib(), _lib.host_lib()
+    want_al, want_pw = torch.empty(n), torch.empty((m, n))
+    assert host.sph2pob_iou_aligned_f32_cpu(G.ptr(h1), G.ptr(h2), G.ptr(want_al), n, dim, variant, 0, 0, 0, None) == 0
+    assert host.sph2pob_iou_pairwise_f32_cpu(G.ptr(h1), m, G.ptr(h2), n, G.ptr(want_pw), dim, variant, 0, 0, 0, None) == 0
+    got = {}
+    for ref_order in (0, 0x100):
+        al, pw = torch.full((n,), -1.0, device='cuda'), torch.full((m, n), -1.0, device='cuda')
+        assert dev.sph2pob_iou_aligned_f32(G.ptr(d1), G.ptr(d2), G.ptr(al), n, dim, variant | ref_order, 0, 0, 0, st) == 0
+        assert dev.sph2pob_iou_pairwise_f32(G.ptr(d1), m, G.ptr(d2), n, G.ptr(pw), dim, variant | ref_order, 0, 0, 0, st) == 0
+        got[ref_order] = (al.cpu(), pw.cpu())
+    assert torch.equal(got[0][0], got[0x100][0]) and torch.equal(got[0][1], got[0x100][1])
+    assert (got[0][0] - want_al).abs().max() < 2e-6 and (got[0][1] - want_pw).abs().max() < 2e-6
+    assert (got[0][0] >= 0).all() and (got[0][1] >= 0).all()

@@ -21,6 +21,7 @@ Workloads (all through the C ABI, buffers allocated once, HIP events around `--l
   bnms      sph2pob_batched_nms_f32 (unsorted input, no host work) on the same two scenes
   head_losses  sph2pob_{focal,bbox,delta}_loss_sum_f32, each timed on its own, with gradients: 8 images x the 5 NCHW levels of the
             512 x 1024 ERP (98 208 anchors), 37 classes, dim 4, CIoU closed-form / L1, ~1 % live rows, a device avg_factor
+  adjoint   sph2pob_transform_bwd_f32 / _general_f32, every instantiated (variant, dim) x edge x angle x jitter, --pairs N
 Every arm's outputs are compared with the first arm's (bit equality is reported, not assumed).
 """
 import argparse
@@ -257,6 +258,25 @@ def workloads(args, torch, G):
             max_ratio, 1, 32.0, 3, 1e-6, 1.0, G.ptr(avg), out, ws, st))
         yield entry('delta_loss', box, 4, lambda lib, xp, gp, out, ws: lib.sph2pob_delta_loss_sum_f32(
             xp, gp, ns, hws, levels, images, 4, G.ptr(deltas_t), G.ptr(weights), 4, 0.0, 1.0, G.ptr(avg), out, ws, st))
+    elif args.workload == 'adjoint':
+        n = int(args.pairs.split(',')[0])
+        g = torch.Generator().manual_seed(7)
+        u = torch.rand((n, 5), generator=g)
+        b1 = torch.stack([u[:, 0] * 360, u[:, 1] * 180, u[:, 2] * 99 + 1, u[:, 3] * 99 + 1, u[:, 4] * 180 - 90], 1)
+        b2 = b1 + torch.randn((n, 5), generator=g) * torch.tensor([8., 8., 6., 6., 10.])   # a third nearby, a third equal, the rest unrelated
+        b2[n // 3:2 * n // 3] = b1[n // 3:2 * n // 3]
+        b2[2 * n // 3:] = b1[torch.randperm(n, generator=g)[2 * n // 3:]]
+        g1, g2 = torch.randn((n, 5), generator=g).cuda(), torch.randn((n, 5), generator=g).cuda()
+        for general, variant, dim in [(gen, v, d) for gen in (0, 1) for v, d in ((0, 4), (0, 5), (1, 4), (1, 5), (2, 4)) if gen or v < 2]:
+            x, y = b1[:, :dim].contiguous().cuda(), b2[:, :dim].contiguous().cuda()
+            for edge, angle, jitter in [(e, a, j) for e in (0, 1, 2) for a in ((0, 1) if general else (0,)) for j in (0, 1)]:
+                def make(lib, x=x, y=y, variant=variant, dim=dim, edge=edge, angle=angle, jitter=jitter, general=general):
+                    o = [torch.empty((n, dim), device='cuda'), torch.empty((n, dim), device='cuda')]
+                    p = [G.ptr(t) for t in (x, y, g1, g2, *o)]
+                    if general:
+                        return (lambda: lib.sph2pob_transform_bwd_general_f32(*p, n, dim, variant, edge, angle, jitter, st)), o
+                    return (lambda: lib.sph2pob_transform_bwd_f32(*p, n, dim, variant, edge, jitter, st)), o
+                yield f'adjoint {"dual" if general else "closed"} variant {variant} dim {dim} edge {edge} angle {angle} jitter {jitter} pairs {n}', make
     else:
         raise SystemExit('unknown workload ' + args.workload)
 
