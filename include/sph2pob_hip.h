@@ -65,8 +65,9 @@ enum {
     SPH2POB_ERR_SIZE = -4     /* negative count or a product that overflows the launch geometry */
 };
 
-/* Library identification: ABI version (bumped on any signature change or new entry point; sph2pob_abi_version() returns the
- * value the library was built with) and the code-object target. */
+/* Library identification: ABI version (bumped when the signature or the meaning of an existing entry point changes; purely
+ * additive entry points — the _h16 family below — do not bump it: a caller detects them by symbol.  sph2pob_abi_version() returns
+ * the value the library was built with) and the code-object target. */
 #define SPH2POB_ABI_VERSION 6
 int sph2pob_abi_version(void);
 const char* sph2pob_target_arch(void);
@@ -645,6 +646,61 @@ int sph2pob_delta_loss_sum_f32(const void* const* bbox_preds, void* const* grads
                                int num_levels, int64_t num_images, int box_dim, const float* targets, const float* weight,
                                int weight_dim, float beta, float scale, const float* avg_factor, float* out, void* workspace,
                                void* stream);
+
+/* ---- 16-bit head outputs: the five multi-level entries on float16 / bfloat16 level tensors, read where they are -----------------
+ * Under mixed precision (torch.autocast; mmdet's fp16 = dict(...), whose force_fp32 is the cast these entries remove) the head's
+ * outputs are 16-bit.  Each entry below takes the arguments of its _f32 sibling, in its order, and before `stream`
+ *   dtype        SPH2POB_DTYPE_F16 | SPH2POB_DTYPE_BF16: the element type of every LEVEL pointer (logits / bbox_preds /
+ *                cls_scores) and, for the losses, of the `grads` pointers.  Anchors, targets, weights, labels, avg_factor, out
+ *                and every result stay fp32 / int64.
+ * A level value is widened to fp32 on load (exact) and all arithmetic is the sibling's, in fp32 / double, unchanged: the item and
+ * span geometry, the partial order and the layouts do not depend on dtype — a thread's four consecutive elements are one 8-byte
+ * access, so the vector kinds need 8-byte alignment where fp32 needs 16.  Hence, for levels that qualify for the same kinds as
+ * their fp32 copies (every tensor from an allocator does), the loss scalar and the four inference outputs have the BITS the
+ * sibling gives on the levels converted to fp32.
+ *
+ * The three loss entries also take, between `workspace` and `dtype`,
+ *   grad_out     NULL (an upstream gradient of 1), or a DEVICE float g: grads receive RNE(g * s), s being the fp32 value the
+ *                sibling writes — one fp32 product, then ONE round-to-nearest-even narrowing (never a 16-bit value scaled
+ *                afterwards: small fp16 gradients under a loss scale survive).  Ignored without grads
+ *   skip_if_one  with grad_out: every workgroup returns at once when g == 1.0f exactly — `grads` then already hold the gradient
+ *                of an earlier call with grad_out NULL (a device-side test, no host read; capturable)
+ * and `out` may be NULL (then `workspace` may be too): no partials are written and no final pass is launched — the gradient-only
+ * call of torch's backward.  With out, workspace is required as for the sibling.  out and grads both NULL: nothing is enqueued.
+ * The protocol of an autograd node: forward with grads = a 16-bit stash and grad_out NULL; the first backward is the same call
+ * with grad_out = g, skip_if_one = 1, out = NULL on the stash (in place: the levels are read, not the stash); a later backward
+ * through a retained graph is that call into a fresh buffer with skip_if_one = 0.  No fp32 copy of a level or of a gradient
+ * exists at any point.
+ * Errors: a dtype outside the enum -> SPH2POB_ERR_OPTION, first; then the sibling's checks with its codes and in its order (out /
+ * workspace as above), all before anything is enqueued.  There are no CPU twins: CPU tensors of a 16-bit dtype are converted by
+ * the caller and take the _f32 twins.
+ */
+enum { SPH2POB_DTYPE_F16 = 1, SPH2POB_DTYPE_BF16 = 2 };
+int sph2pob_focal_loss_sum_h16(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                               int num_levels, int64_t num_images, int64_t num_classes, const int64_t* labels, const float* weight,
+                               int weight_mode, float gamma, float alpha, float scale, const float* avg_factor, float* out,
+                               void* workspace, const float* grad_out, int skip_if_one, int dtype, void* stream);
+int sph2pob_bbox_loss_sum_h16(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                              int num_levels, int64_t num_images, int box_dim, const float* anchors, const float* targets,
+                              const float* weight, int weight_dim, const float* means_host, const float* stds_host, float max_ratio,
+                              int coder_flags, float ctr_clamp, int loss_mode, float eps, float scale, const float* avg_factor,
+                              float* out, void* workspace, const float* grad_out, int skip_if_one, int dtype, void* stream);
+int sph2pob_delta_loss_sum_h16(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                               int num_levels, int64_t num_images, int box_dim, const float* targets, const float* weight,
+                               int weight_dim, float beta, float scale, const float* avg_factor, float* out, void* workspace,
+                               const float* grad_out, int skip_if_one, int dtype, void* stream);
+int sph2pob_get_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors,
+                           const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes,
+                           int box_dim, int activation, float score_thr, int64_t nms_pre, const float* means_host,
+                           const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp, int variant,
+                           float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds,
+                           int64_t* num_dets, void* workspace, int dtype, void* stream);
+int sph2pob_test_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors,
+                            const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes,
+                            int box_dim, int activation, float score_thr, int64_t nms_pre, const float* means_host,
+                            const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp, int variant_flags,
+                            int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
+                            int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

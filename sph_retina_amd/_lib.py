@@ -165,6 +165,13 @@ SIGNATURES = {
     'sph2pob_obb_l1_bwd_f32': [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_float, _c_f32p, _c_f32p, _i64, _int,
                                ctypes.c_void_p],
 }
+# The 16-bit level entries (SPH2POB_DTYPE_*; no CPU twins): the arguments of the _f32 sibling with `dtype` in front of the stream,
+# and for the losses (grad_out, skip_if_one) in front of that
+H16_DTYPES = {'float16': 1, 'bfloat16': 2}
+for _name in ('focal_loss_sum', 'bbox_loss_sum', 'delta_loss_sum'):
+    SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_c_f32p, _int, _int, ctypes.c_void_p]
+for _name in ('get_bboxes', 'test_bboxes'):
+    SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_int, ctypes.c_void_p]
 _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_target_arch': ctypes.c_char_p, 'sph2pob_error_string': ctypes.c_char_p,
              'sph2pob_nms_workspace_bytes': ctypes.c_int64, 'sph2pob_nms_segmented_workspace_bytes': ctypes.c_int64, 'sph2pob_assign_workspace_bytes': ctypes.c_int64,
              'sph2pob_iou_assign_workspace_bytes': ctypes.c_int64, 'sph2pob_iou_assign_state_bytes': ctypes.c_int64,

@@ -70,6 +70,18 @@ def as_f32_nograd(t):
     return as_f32(t.detach() if t.requires_grad else t)
 
 
+def h16_dtype_code(levels):
+    """SPH2POB_DTYPE_* when the head outputs of a call are read where they are by the *_h16 entries — all on the GPU, contiguous
+    and of ONE dtype in {float16, bfloat16} — and 0 otherwise: mixed dtypes, non-contiguous levels, CPU tensors and fp32 keep
+    the fp32 route (a converted copy where one is needed)."""
+    dt = levels[0].dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        return 0
+    if any(t.dtype is not dt or t.device.type != 'cuda' or not t.is_contiguous() for t in levels):
+        return 0
+    return _lib.H16_DTYPES[str(dt).split('.')[-1]]
+
+
 def ptr(t):
     """Device address as a plain integer (None = NULL): the launchers' argtypes are declared, so ctypes converts it
     without a c_void_p object being built for every argument of every call."""

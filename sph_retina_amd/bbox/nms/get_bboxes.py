@@ -47,7 +47,7 @@ class DetBBoxes:
         return [(self.dets[b, :k], self.labels[b, :k]) for b, k in enumerate(self.num_dets.tolist())]
 
 
-def _level(t, name, per_anchor, n, images):
+def _level(t, name, per_anchor, n, images, native=False):
     """(tensor, hw) of one level: hw = H W for the head's NCHW (B, A per_anchor, H, W), 0 for the flattened (B, n, per_anchor)."""
     if t.dim() == 4:
         hw = t.size(2) * t.size(3)
@@ -59,6 +59,8 @@ def _level(t, name, per_anchor, n, images):
             raise ValueError(f'{name}: expected ({images}, {n}, {per_anchor}), got {tuple(t.shape)}')
     else:
         raise ValueError(f'{name}: expected (B, A * {per_anchor}, H, W) or (B, n, {per_anchor}), got {tuple(t.shape)}')
+    if native:
+        return (t.detach() if t.requires_grad else t), hw
     return G.as_f32_nograd(t), hw
 
 
@@ -104,6 +106,7 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
     dev = tensors[0].device
     images = cls_scores[0].size(0)
     num_classes = None
+    code = G.h16_dtype_code(list(cls_scores) + list(bbox_preds))   # 16-bit GPU levels: read where they are, one dtype for both
     held, cls_p, box_p, anc_p, ns, hws = [], [], [], [], [], []   # held: converted copies stay alive until the call is enqueued
     for l in range(levels):
         anc = G.as_f32_nograd(mlvl_anchors[l][..., :dim])
@@ -115,8 +118,8 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
             num_classes = c
         if c != num_classes or c == 0:
             raise ValueError(f'level {l}: {c} classes, level 0 has {num_classes}')
-        cs, hw = _level(cls_scores[l], f'cls_scores[{l}]', c, n, images)
-        bp, hw_b = _level(bbox_preds[l], f'bbox_preds[{l}]', dim, n, images)
+        cs, hw = _level(cls_scores[l], f'cls_scores[{l}]', c, n, images, bool(code))
+        bp, hw_b = _level(bbox_preds[l], f'bbox_preds[{l}]', dim, n, images, bool(code))
         if hw != hw_b:
             raise ValueError(f'level {l}: cls_scores and bbox_preds must use the same layout')
         held += [cs, bp, anc]
@@ -141,10 +144,14 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
     means = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.means])
     stds = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.stds])
     flags = (1 if bbox_coder.clip_border else 0) | (2 if bbox_coder.add_ctr_clamp else 0)
+    if code:   # the _h16 sibling: the same arguments with the levels' dtype in front of the stream
+        symbol, tail = symbol[:-len('_f32')] + '_h16', (code,)
+    else:
+        tail = ()
     G.call(symbol, dev, ptrs(*cls_p), ptrs(*box_p), ptrs(*anc_p), level_n, i64s(*hws), levels, images, num_classes, dim,
            int(activation == 'sigmoid'), float(score_thr), nms_pre, means, stds, float(abs(math.log(wh_ratio_clip))), flags,
            float(bbox_coder.ctr_clamp), *nms_args, float(iou_threshold), max_per_img, G.ptr(out.dets),
-           G.ptr(out.labels), G.ptr(out.prior_inds), out.num_dets.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
+           G.ptr(out.labels), G.ptr(out.prior_inds), out.num_dets.data_ptr(), G.ptr(ws), *tail, G.raw_stream_of(dev))
     return out
 
 

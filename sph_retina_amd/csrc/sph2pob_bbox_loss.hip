@@ -14,14 +14,14 @@ namespace CD = sph2pob_coder;
 // 26 KiB per workgroup) would admit six workgroups per CU
 constexpr int kBboxWaves = 3;
 
-template <int DIM, bool FAST, bool GRAD>
-__global__ __launch_bounds__(kBlock, kBboxWaves) void bbox_loss_kernel(BL::Levels L, const float* __restrict__ anchors,
-                                                                       const float* __restrict__ targets, const float* __restrict__ weight,
-                                                                       int wd, CD::Norm nm, float max_ratio, int cflags, float ctr_clamp,
-                                                                       int loss_mode, float eps, float scale,
-                                                                       const float* __restrict__ avg_factor, double* __restrict__ partial) {
-    span_loss<DIM, GRAD>(
-        L, scale, avg_factor, partial,
+// T: the element type of the levels (float, or the 16-bit types of sph2pob_bbox_loss_sum_h16); gs: the upstream gradient (16-bit T)
+template <class T, int DIM, bool FAST, bool GRAD>
+__device__ __forceinline__ void bbox_loss_body(const BL::Levels& L, const float* __restrict__ anchors, const float* __restrict__ targets,
+                                               const float* __restrict__ weight, int wd, const CD::Norm& nm, float max_ratio, int cflags,
+                                               float ctr_clamp, int loss_mode, float eps, float scale, const float* __restrict__ avg_factor,
+                                               float gs, double* __restrict__ partial) {
+    span_loss<T, DIM, GRAD>(
+        L, scale, avg_factor, gs, partial,
         [&](int64_t row) { return sph2pob::element_weight<DIM>(weight, wd, row) != 0.0f; },
         [&](const BL::Level& lv, int b, int i, int64_t row, float k0, float (&g)[DIM], double& acc) {
             const float w = sph2pob::element_weight<DIM>(weight, wd, row);
@@ -30,10 +30,11 @@ __global__ __launch_bounds__(kBlock, kBboxWaves) void bbox_loss_kernel(BL::Level
             const int64_t off = BL::delta_offset(lv, DIM, b, i, &stride);
             const float* ap = anchors + (lv.row_off + i) * DIM;
             const float* tp = targets + row * DIM;
+            const T* dp = level_ptr<T>(lv.pred);
 #pragma unroll
             for (int k = 0; k < 5; k++) {
                 p[k] = k < DIM ? ap[k] : 0.0f;
-                d[k] = k < DIM ? lv.pred[off + k * stride] : 0.0f;
+                d[k] = k < DIM ? (float)dp[off + k * stride] : 0.0f;
                 t[k] = k < DIM ? tp[k] : 0.0f;
                 box[k] = 0.0f;
             }
@@ -46,6 +47,31 @@ __global__ __launch_bounds__(kBlock, kBboxWaves) void bbox_loss_kernel(BL::Level
                 for (int k = 0; k < DIM; k++) g[k] = (gw * gx[k]) * jac[k];
             }
         });
+}
+
+template <int DIM, bool FAST, bool GRAD>
+__global__ __launch_bounds__(kBlock, kBboxWaves) void bbox_loss_kernel(BL::Levels L, const float* __restrict__ anchors,
+                                                                       const float* __restrict__ targets, const float* __restrict__ weight,
+                                                                       int wd, CD::Norm nm, float max_ratio, int cflags, float ctr_clamp,
+                                                                       int loss_mode, float eps, float scale,
+                                                                       const float* __restrict__ avg_factor, double* __restrict__ partial) {
+    bbox_loss_body<float, DIM, FAST, GRAD>(L, anchors, targets, weight, wd, nm, max_ratio, cflags, ctr_clamp, loss_mode, eps, scale, avg_factor,
+                                           1.0f, partial);
+}
+
+// 16-bit levels: the gradient leaves as RNE_T(g ((gw gx) jac)); partial NULL: a gradient-only call, no sum
+template <class T, int DIM, bool FAST, bool GRAD>
+__global__ __launch_bounds__(kBlock, kBboxWaves) void bbox_loss_h16_kernel(BL::Levels L, const float* __restrict__ anchors,
+                                                                           const float* __restrict__ targets, const float* __restrict__ weight,
+                                                                           int wd, CD::Norm nm, float max_ratio, int cflags, float ctr_clamp,
+                                                                           int loss_mode, float eps, float scale,
+                                                                           const float* __restrict__ avg_factor, const float* __restrict__ grad_out,
+                                                                           int skip_if_one, double* __restrict__ partial) {
+    bool done;
+    const float gs = upstream_gradient(grad_out, skip_if_one, done);
+    if (done) return;   // kernel-uniform
+    bbox_loss_body<T, DIM, FAST, GRAD>(L, anchors, targets, weight, wd, nm, max_ratio, cflags, ctr_clamp, loss_mode, eps, scale, avg_factor, gs,
+                                       partial);
 }
 
 }  // namespace
@@ -83,6 +109,39 @@ int sph2pob_bbox_loss_sum_f32(const void* const* bbox_preds, void* const* grads,
             else go(bbox_loss_kernel<D, false, G>);
         });
     }
+    return launch_final(partial, L.blocks, scale, avg_factor, out, s);
+}
+
+int sph2pob_bbox_loss_sum_h16(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                              int num_levels, int64_t num_images, int box_dim, const float* anchors, const float* targets,
+                              const float* weight, int weight_dim, const float* means_host, const float* stds_host, float max_ratio,
+                              int coder_flags, float ctr_clamp, int loss_mode, float eps, float scale, const float* avg_factor,
+                              float* out, void* workspace, const float* grad_out, int skip_if_one, int dtype, void* stream) {
+    if (!sph2pob_head::h16_dtype_ok(dtype)) return SPH2POB_ERR_OPTION;
+    if (int rc = BL::check_options(box_dim, weight, weight_dim, max_ratio, coder_flags, loss_mode)) return rc;
+    BL::Levels L;
+    if (int rc = BL::make_levels(bbox_preds, grads, level_n, level_hw, num_levels, num_images, box_dim, true, &L, 8)) return rc;
+    if ((out && !workspace) || (L.rows > 0 && (!anchors || !targets))) return SPH2POB_ERR_NULL;
+    if (!out && !grads) return SPH2POB_OK;   // neither the sum nor the gradient is asked for
+    hipStream_t s = (hipStream_t)stream;
+    const CD::Norm nm = CD::make_norm(means_host, stds_host, box_dim);
+    double* partial = out ? (double*)workspace : nullptr;
+    const int mode = loss_mode & 0xff;
+    if (L.blocks > 0) {
+        const bool fast = !(loss_mode & SPH2POB_FLAG_REFERENCE_ORDER);
+        by_dtype_dim_grad(dtype, box_dim, grads != nullptr, [&](auto t, auto dim, auto gr) {
+            using T = decltype(t);
+            constexpr int D = decltype(dim)::value;
+            constexpr bool G = decltype(gr)::value;
+            auto go = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(kBlock), 0, s, L, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags,
+                                   ctr_clamp, mode, eps, scale, avg_factor, grads ? grad_out : nullptr, skip_if_one, partial);
+            };
+            if (fast) go(bbox_loss_h16_kernel<T, D, true, G>);
+            else go(bbox_loss_h16_kernel<T, D, false, G>);
+        });
+    }
+    if (!out) return L.blocks > 0 ? launch_status() : SPH2POB_OK;
     return launch_final(partial, L.blocks, scale, avg_factor, out, s);
 }
 

@@ -53,9 +53,11 @@ inline int check_options(int box_dim, const float* weight, int weight_dim, float
     return SPH2POB_OK;
 }
 
-// Shape checks in the documented order; fills the table.  `tables` false: shapes only (the workspace size).
+// Shape checks in the documented order; fills the table.  `tables` false: shapes only (the workspace size).  `vec_bytes`: the
+// alignment a four-element store needs — 16 for fp32 levels, 8 for the 16-bit levels of the _h16 entries, whose pointers the table
+// keeps as float* all the same (sph2pob_head_loss.hpp, level_ptr).
 inline int make_levels(const void* const* preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw, int num_levels,
-                       int64_t B, int dim, bool tables, Levels* out) {
+                       int64_t B, int dim, bool tables, Levels* out, int vec_bytes = 16) {
     if (dim != 4 && dim != 5) return SPH2POB_ERR_DIM;
     if (num_levels < 1 || num_levels > kMaxLevels || B < 0 || B > 65535) return SPH2POB_ERR_SIZE;
     if (!level_n || (tables && !preds)) return SPH2POB_ERR_NULL;
@@ -78,7 +80,7 @@ inline int make_levels(const void* const* preds, void* const* grads, const int64
         d.pred = tables ? (const float*)preds[l] : nullptr;
         d.grad = tables && grads ? (float*)grads[l] : nullptr;
         if (tables && B * n > 0 && (!d.pred || (grads && !d.grad))) return SPH2POB_ERR_NULL;
-        d.vec = d.grad && aligned16(d.grad) && (hw > 0 ? hw % 4 == 0 : (n * dim) % 4 == 0);
+        d.vec = d.grad && sph2pob_head::aligned_to(d.grad, vec_bytes) && (hw > 0 ? hw % 4 == 0 : (n * dim) % 4 == 0);
         d.block_off = (int)blocks;
         d.row_off = rows;
         blocks += (d.items + kWaves - 1) / kWaves;

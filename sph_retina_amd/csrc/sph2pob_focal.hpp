@@ -12,7 +12,7 @@
 
 namespace sph2pob_focal {
 
-using sph2pob_head::aligned16;
+using sph2pob_head::aligned_to;
 using sph2pob_head::effective_scale;
 using sph2pob_head::kBlock;
 using sph2pob_head::kMaxLevels;
@@ -88,9 +88,11 @@ struct Levels {
 };
 
 // Argument checks of sph2pob_focal_loss_sum_f32 / its twin, in the documented order; fills the table.  `tables` false: shapes
-// only (the workspace size), every level counted with its scalar kind (an upper bound on the workgroups).
+// only (the workspace size), every level counted with its scalar kind (an upper bound on the workgroups).  `vec_bytes`: the
+// alignment the vector kinds need — four elements: 16 for fp32 levels, 8 for the 16-bit levels of sph2pob_focal_loss_sum_h16,
+// whose pointers the table keeps as float* all the same (sph2pob_head_loss.hpp, level_ptr).
 inline int make_levels(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw, int num_levels,
-                       int64_t B, int64_t C, int weight_mode, float gamma, bool tables, Levels* out) {
+                       int64_t B, int64_t C, int weight_mode, float gamma, bool tables, Levels* out, int vec_bytes = 16) {
     if (!(gamma >= 0.0f) || weight_mode < 0 || weight_mode > 2) return SPH2POB_ERR_OPTION;
     if (num_levels < 1 || num_levels > kMaxLevels || B < 0 || B > 65535 || C <= 0 || C > ((int64_t)1 << 24)) return SPH2POB_ERR_SIZE;
     if (!level_n || (tables && !logits)) return SPH2POB_ERR_NULL;
@@ -106,7 +108,7 @@ inline int make_levels(const void* const* logits, void* const* grads, const int6
         d.logits = tables ? (const float*)logits[l] : nullptr;
         d.grad = tables && grads ? (float*)grads[l] : nullptr;
         if (tables && elems > 0 && (!d.logits || (grads && !d.grad))) return SPH2POB_ERR_NULL;
-        const bool al = tables && aligned16(d.logits) && aligned16(d.grad);
+        const bool al = tables && aligned_to(d.logits, vec_bytes) && aligned_to(d.grad, vec_bytes);
         int64_t items;
         if (hw > 0) {
             d.kind = al && hw % 4 == 0 ? KIND_NCHW4 : KIND_NCHW1;

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/sph2pob_hip.h"
 #include "sph2pob_coder.hpp"
 #include "sph2pob_get_bboxes.hpp"   // (declares the NMS stage, sph2pob_nms_batch_launch)
@@ -44,22 +46,30 @@ __device__ __forceinline__ int level_of_chunk(const Levels& L, int chunk) {
 
 // Streams one chunk of one image's level in memory order, four consecutive scores per lane and step (one 16-byte load when the
 // image's base is aligned), and hands every score above the threshold to f(descending key, flat index, valid): f is called by
-// all lanes of a wave together, four times per step.
-template <class F>
+// all lanes of a wave together, four times per step.  T: the element type of the scores — float, or a 16-bit type of the _h16
+// entries: then the four scores are one 8-byte load, widened to fp32 here; everything after the load is fp32 either way.
+template <class T, class F>
 __device__ __forceinline__ void stream_chunk(const Level& lv, int64_t b, int chunk, int activation, float thr, F&& f) {
-    const float* base = lv.cls + b * (int64_t)lv.count;
-    const bool vec = (lv.count & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
+    const T* base = reinterpret_cast<const T*>(lv.cls) + b * (int64_t)lv.count;
+    const bool vec = (lv.count & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & (4 * sizeof(T) - 1)) == 0;
     const int m_begin = chunk * kChunk;
     for (int it = 0; it < kSelIters; it++) {
         const int m0 = m_begin + (it * kSelBlock + (int)threadIdx.x) * 4;
         if (m_begin + it * kSelBlock * 4 >= lv.count) break;   // workgroup-uniform
         float x[4];
         if (vec && m0 + 3 < lv.count) {
-            const float4 v = *reinterpret_cast<const float4*>(base + m0);
-            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+            if constexpr (std::is_same<T, float>::value) {
+                const float4 v = *reinterpret_cast<const float4*>(base + m0);
+                x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+            } else {
+                struct alignas(4 * sizeof(T)) Quad { T v[4]; };
+                const Quad q = *reinterpret_cast<const Quad*>(base + m0);
+#pragma unroll
+                for (int e = 0; e < 4; e++) x[e] = (float)q.v[e];
+            }
         } else {
 #pragma unroll
-            for (int e = 0; e < 4; e++) x[e] = m0 + e < lv.count ? base[m0 + e] : 0.0f;
+            for (int e = 0; e < 4; e++) x[e] = m0 + e < lv.count ? (float)base[m0 + e] : 0.0f;
         }
         const int mc = m0 < lv.count ? m0 : 0;
         int ch = mc / lv.hw, p = mc - ch * lv.hw;
@@ -73,6 +83,7 @@ __device__ __forceinline__ void stream_chunk(const Level& lv, int64_t b, int chu
     }
 }
 
+template <class T>
 __global__ __launch_bounds__(kSelBlock) void topk_hist_kernel(Levels L, int activation, float thr, int* __restrict__ hist) {
     __shared__ int h[kBins];
     const int b = blockIdx.y, l = level_of_chunk(L, blockIdx.x);
@@ -80,7 +91,7 @@ __global__ __launch_bounds__(kSelBlock) void topk_hist_kernel(Levels L, int acti
     for (int i = threadIdx.x; i < kBins; i += kSelBlock) h[i] = 0;
     __syncthreads();
     int any = 0;
-    stream_chunk(lv, b, blockIdx.x - lv.chunk_off, activation, thr, [&](unsigned dkey, unsigned, bool valid) {
+    stream_chunk<T>(lv, b, blockIdx.x - lv.chunk_off, activation, thr, [&](unsigned dkey, unsigned, bool valid) {
         if (valid) { atomicAdd(&h[score_bin(dkey)], 1); any = 1; }
     });
     if (!__syncthreads_or(any)) return;   // (a detector's scores are mostly below the threshold: most chunks stop here)
@@ -120,6 +131,7 @@ __global__ __launch_bounds__(kResBlock) void topk_cut_kernel(Levels L, int nms_p
     }
 }
 
+template <class T>
 __global__ __launch_bounds__(kSelBlock) void topk_compact_kernel(Levels L, int activation, float thr, Meta* __restrict__ meta,
                                                                 unsigned long long* __restrict__ buf) {
     const int b = blockIdx.y, l = level_of_chunk(L, blockIdx.x);
@@ -128,7 +140,7 @@ __global__ __launch_bounds__(kSelBlock) void topk_compact_kernel(Levels L, int a
     const int cut = m->cut;
     if (cut < 0) return;
     unsigned long long* out = buf + b * L.total + lv.buf_off;
-    stream_chunk(lv, b, blockIdx.x - lv.chunk_off, activation, thr, [&](unsigned dkey, unsigned flat, bool valid) {
+    stream_chunk<T>(lv, b, blockIdx.x - lv.chunk_off, activation, thr, [&](unsigned dkey, unsigned flat, bool valid) {
         const bool take = valid && score_bin(dkey) <= cut;
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(take);
         if (mask == 0ull) return;   // wave-uniform
@@ -207,7 +219,7 @@ __global__ __launch_bounds__(kResBlock) void topk_resolve_kernel(Levels L, const
 
 // One lane per selected key: its rank among the level's selection (tiles of the selection in LDS), then gather + decode.
 constexpr int kBuildBlock = 256;
-template <int DIM>
+template <int DIM, class T>
 __global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const Meta* __restrict__ meta, const unsigned long long* __restrict__ sel,
                                                                int num_classes, C::Norm nm, float max_ratio, int coder_flags, float ctr_clamp,
                                                                float* __restrict__ boxes, float* __restrict__ scores, int64_t* __restrict__ labels,
@@ -242,7 +254,7 @@ __global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const
     float p[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, d[5], box[5];
 #pragma unroll
     for (int k = 0; k < DIM; k++) p[k] = lv.anchors[(int64_t)ai * DIM + k];
-    gather_deltas<DIM>(lv, b, ai, d);
+    gather_deltas<DIM, T>(lv, b, ai, d);
     C::decode_one<DIM, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr);
     const int64_t at = (int64_t)b * L.k_cap + off + rank;
 #pragma unroll
@@ -280,6 +292,42 @@ int launch_status() {
     return e == hipSuccess ? SPH2POB_OK : (int)e;
 }
 
+// T: the element type of cls_scores and bbox_preds (anchors and every output are fp32 / int64 whatever T is)
+template <class T>
+int test_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img,
+                float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
+    Levels L;
+    if (int rc = make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                             variant_flags, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, kChunk, &L))
+        return rc;
+    if (!num_dets || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = (int)num_images;
+    const Ws w = make_ws(workspace, L, B, box_dim);
+    const int pre = (int)(nms_pre < ((int64_t)1 << 30) ? nms_pre : ((int64_t)1 << 30));
+    if (hipMemsetAsync(w.hist, 0, (size_t)w.zero_bytes, s) != hipSuccess) return (int)hipGetLastError();
+    hipLaunchKernelGGL(topk_hist_kernel<T>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.hist);
+    hipLaunchKernelGGL(topk_cut_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, pre, (const int*)w.hist, w.meta);
+    hipLaunchKernelGGL(topk_compact_kernel<T>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.meta, w.buf);
+    hipLaunchKernelGGL(topk_resolve_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.buf, w.sel);
+    int max_cap = 0;
+    for (int l = 0; l < L.num; l++) max_cap = L.lv[l].cap > max_cap ? L.lv[l].cap : max_cap;
+    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
+    const dim3 bgrid((max_cap + kBuildBlock - 1) / kBuildBlock, L.num, B);
+    if (box_dim == 4)
+        hipLaunchKernelGGL((cand_build_kernel<4, T>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+                           (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
+    else
+        hipLaunchKernelGGL((cand_build_kernel<5, T>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+                           (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
+    if (int rc = launch_status()) return rc;
+    return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant_flags, class_agnostic, iou_threshold,
+                                    max_per_img, w.nms, dets, labels, prior_inds, num_dets, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -298,33 +346,23 @@ int sph2pob_test_bboxes_f32(const void* const* cls_scores, const void* const* bb
                             float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
                             int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img,
                             float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
-    Levels L;
-    if (int rc = make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                             variant_flags, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, kChunk, &L))
-        return rc;
-    if (!num_dets || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
-    hipStream_t s = (hipStream_t)stream;
-    const int B = (int)num_images;
-    const Ws w = make_ws(workspace, L, B, box_dim);
-    const int pre = (int)(nms_pre < ((int64_t)1 << 30) ? nms_pre : ((int64_t)1 << 30));
-    if (hipMemsetAsync(w.hist, 0, (size_t)w.zero_bytes, s) != hipSuccess) return (int)hipGetLastError();
-    hipLaunchKernelGGL(topk_hist_kernel, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.hist);
-    hipLaunchKernelGGL(topk_cut_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, pre, (const int*)w.hist, w.meta);
-    hipLaunchKernelGGL(topk_compact_kernel, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.meta, w.buf);
-    hipLaunchKernelGGL(topk_resolve_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.buf, w.sel);
-    int max_cap = 0;
-    for (int l = 0; l < L.num; l++) max_cap = L.lv[l].cap > max_cap ? L.lv[l].cap : max_cap;
-    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
-    const dim3 bgrid((max_cap + kBuildBlock - 1) / kBuildBlock, L.num, B);
-    if (box_dim == 4)
-        hipLaunchKernelGGL((cand_build_kernel<4>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                           (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
-    else
-        hipLaunchKernelGGL((cand_build_kernel<5>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                           (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
-    if (int rc = launch_status()) return rc;
-    return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant_flags, class_agnostic, iou_threshold,
-                                    max_per_img, w.nms, dets, labels, prior_inds, num_dets, s);
+    return test_bboxes<float>(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation, score_thr,
+                              nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags, class_agnostic, iou_threshold,
+                              max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+}
+
+int sph2pob_test_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                            const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                            float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                            int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img,
+                            float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream) {
+    if (dtype != SPH2POB_DTYPE_F16 && dtype != SPH2POB_DTYPE_BF16) return SPH2POB_ERR_OPTION;
+    auto run = [&](auto t) {
+        return test_bboxes<decltype(t)>(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                                        score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags, class_agnostic,
+                                        iou_threshold, max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+    };
+    return dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
 }
 
 // the closed-form calculators, per class: its own variant check (after the box_dim check, as documented), then the entry above
@@ -337,6 +375,18 @@ int sph2pob_get_bboxes_f32(const void* const* cls_scores, const void* const* bbo
     return sph2pob_test_bboxes_f32(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
                                    score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, 0, iou_threshold,
                                    max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+}
+
+int sph2pob_get_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                           const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                           float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                           int coder_flags, float ctr_clamp, int variant, float iou_threshold, int64_t max_per_img, float* dets,
+                           int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream) {
+    if (dtype != SPH2POB_DTYPE_F16 && dtype != SPH2POB_DTYPE_BF16) return SPH2POB_ERR_OPTION;
+    if ((box_dim == 4 || box_dim == 5) && !closed_form_variant(variant)) return SPH2POB_ERR_OPTION;
+    return sph2pob_test_bboxes_h16(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                                   score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, 0, iou_threshold,
+                                   max_per_img, dets, labels, prior_inds, num_dets, workspace, dtype, stream);
 }
 
 }  // extern "C"

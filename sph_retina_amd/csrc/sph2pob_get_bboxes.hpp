@@ -29,8 +29,8 @@ constexpr int kNmsIdxBits = 14, kNmsClsBits = 18;   // the composite NMS key: K 
 //   NCHW (B, A C, H, W):  m = ch * hw + p  ->  f = p * (A C) + ch      (hw = H W, ac = A C)
 //   flat (B, n, C):       m = f                                        (hw = count, ac = 1: the same formula)
 struct Level {
-    const float* cls;      // scores or logits
-    const float* bbox;     // deltas, laid out like cls
+    const float* cls;      // scores or logits; the _h16 entries keep their 16-bit pointers here too and read them as T
+    const float* bbox;     // deltas, laid out like cls (and of its element type)
     const float* anchors;  // (n, dim)
     int n;                 // anchors of the level
     int count;             // n * C candidates per image
@@ -172,18 +172,19 @@ inline int make_levels(const void* const* cls, const void* const* bbox, const vo
     return SPH2POB_OK;
 }
 
-// the deltas of anchor `ai` of image b, from the head layout
-template <int DIM>
+// the deltas of anchor `ai` of image b, from the head layout, widened to fp32; T: the element type of the level tensors
+template <int DIM, class T = float>
 SPHG_DEV void gather_deltas(const Level& lv, int64_t b, int ai, float* d) {
+    const T* bbox = reinterpret_cast<const T*>(lv.bbox);
     if (lv.sp > 0) {
         const int p = ai / lv.a, a = ai - p * lv.a;
-        const float* q = lv.bbox + (b * lv.a + a) * (int64_t)DIM * lv.sp + p;
+        const T* q = bbox + (b * lv.a + a) * (int64_t)DIM * lv.sp + p;
 #pragma unroll
-        for (int k = 0; k < DIM; k++) d[k] = q[(int64_t)k * lv.sp];
+        for (int k = 0; k < DIM; k++) d[k] = (float)q[(int64_t)k * lv.sp];
     } else {
-        const float* q = lv.bbox + (b * lv.n + ai) * (int64_t)DIM;
+        const T* q = bbox + (b * lv.n + ai) * (int64_t)DIM;
 #pragma unroll
-        for (int k = 0; k < DIM; k++) d[k] = q[k];
+        for (int k = 0; k < DIM; k++) d[k] = (float)q[k];
     }
 }
 

@@ -16,6 +16,10 @@ constexpr int kMaxLevels = 8;
 constexpr int kBlock = 256;   // 4 waves of 64 lanes
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// `bytes` (a power of two): what a thread's four consecutive elements need — 16 for fp32 levels, 8 for the 16-bit levels of the
+// _h16 entries
+inline bool aligned_to(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+inline bool h16_dtype_ok(int dtype) { return dtype == SPH2POB_DTYPE_F16 || dtype == SPH2POB_DTYPE_BF16; }
 
 // the scale every kernel applies: `scale` (loss_weight, possibly over a host divisor), over (*avg_factor + FLT_EPSILON) when the
 // divisor lives on the device (weight_reduce_loss, mmdet/models/losses/utils.py:55-57) — one IEEE division in fp32
@@ -26,6 +30,7 @@ SPHF_DEV float effective_scale(float scale, const float* avg_factor) {
 }  // namespace sph2pob_head
 
 #if defined(__HIPCC__)
+#include <type_traits>
 // Internal linkage: the library is linked from separately compiled units and each instantiates its own copy of the final kernel.
 namespace {
 
@@ -43,6 +48,53 @@ static int cu_count() {
         n = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
     }
     return n;
+}
+
+// ---- the level element type T of a kernel: float, or the 16-bit types of the _h16 entries.  T reaches the load and store sites
+// only: a value is widened to fp32 on load (exact) and narrowed once on store, by the compiler's own conversion (round to nearest
+// even; on gfx950 the packed v_cvt_pk_f16_f32 and v_cvt_pk_bf16_f32).  A level table keeps its pointers as float*: level_ptr<T>
+// reads them as what the entry's dtype says they are.
+using f16_t = _Float16;
+using bf16_t = __bf16;
+template <class T> struct alignas(4 * sizeof(T)) Quad { T v[4]; };   // four consecutive elements: one 16- or 8-byte access
+
+template <class T> __device__ __forceinline__ const T* level_ptr(const float* p) { return reinterpret_cast<const T*>(p); }
+template <class T> __device__ __forceinline__ T* level_ptr(float* p) { return reinterpret_cast<T*>(p); }
+
+// The one narrowing of a ROUNDED fp32 value.  The empty asm pins the fp32 value in a register first: without it the compiler
+// folds a preceding fp32 multiply into the conversion (v_fma_mixlo_f16 d, g, s, 0 — seen in the scalar kinds of the fp16 focal
+// kernel), which rounds the exact product once instead of RNE_T(fl32(g s)) and turns g * -0 into +0.
+template <class T> __device__ __forceinline__ T narrow(float v) {
+    if constexpr (!std::is_same<T, float>::value) asm("" : "+v"(v));
+    return (T)v;
+}
+template <class T> __device__ __forceinline__ float load1(const T* p) { return (float)p[0]; }
+template <class T> __device__ __forceinline__ void store1(T* p, float v) { p[0] = narrow<T>(v); }
+template <class T> __device__ __forceinline__ void load4(const T* p, float (&x)[4]) {
+    const Quad<T> q = *reinterpret_cast<const Quad<T>*>(p);
+#pragma unroll
+    for (int k = 0; k < 4; k++) x[k] = (float)q.v[k];
+}
+template <class T> __device__ __forceinline__ void store4(T* p, float x0, float x1, float x2, float x3) {
+    Quad<T> q;
+    q.v[0] = narrow<T>(x0); q.v[1] = narrow<T>(x1); q.v[2] = narrow<T>(x2); q.v[3] = narrow<T>(x3);
+    *reinterpret_cast<Quad<T>*>(p) = q;
+}
+
+// The upstream gradient of an _h16 loss kernel (include/sph2pob_hip.h): 1 without grad_out, else grad_out[0]; `done` when the
+// workgroup has nothing to do — skip_if_one and the value is exactly 1: `grads` already hold the gradient (the device-side test of
+// focal_grad_scale_kernel: no host read)
+__device__ __forceinline__ float upstream_gradient(const float* __restrict__ grad_out, int skip_if_one, bool& done) {
+    const float g = grad_out ? grad_out[0] : 1.0f;
+    done = grad_out && skip_if_one && g == 1.0f;
+    return g;
+}
+
+// f(T{}) for the level element type of a checked SPH2POB_DTYPE_* code
+template <class F>
+void by_h16_dtype(int dtype, F&& f) {
+    if (dtype == SPH2POB_DTYPE_F16) f(f16_t{});
+    else f(bf16_t{});
 }
 
 // the sum of a workgroup's values in thread 0 (0 elsewhere): shuffle tree per wave, then the four waves in order

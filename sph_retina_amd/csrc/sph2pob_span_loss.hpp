@@ -20,9 +20,13 @@ static_assert(kBlock == 64 * sph2pob_bbox::kWaves, "one span per wave");
 // live(row) -> bool: does row `row` (of the (B, n) rows of the call) take part.
 // eval(lv, b, i, row, k0, g, acc): one live row — anchor i of level lv in image b; adds the row's weighted losses to `acc` in
 // component order and, under GRAD, leaves the DIM gradient values in g.
-template <int DIM, bool GRAD, class Live, class Eval>
-__device__ __forceinline__ void span_loss(const sph2pob_bbox::Levels& L, float scale, const float* __restrict__ avg_factor,
+// T: the element type of the levels (eval reads lv.pred through level_ptr<T>).  The tile, the stack and the span geometry do not
+// depend on it: a 16-bit T is narrowed in the stream-out, four values per 8-byte store, after the upstream gradient `gs` has been
+// folded in on the way into the tile (fp32 levels leave gs to torch's backward).  16-bit T only: partial NULL — no sum is kept.
+template <class T, int DIM, bool GRAD, class Live, class Eval>
+__device__ __forceinline__ void span_loss(const sph2pob_bbox::Levels& L, float scale, const float* __restrict__ avg_factor, float gs,
                                           double* __restrict__ partial, Live live, Eval eval) {
+    constexpr bool F32 = std::is_same<T, float>::value;
     namespace BL = sph2pob_bbox;
     __shared__ __attribute__((aligned(16))) float tile_s[GRAD ? BL::kWaves * BL::kTile : 4];
     __shared__ unsigned short stack_s[BL::kWaves * BL::kStack];
@@ -61,6 +65,10 @@ __device__ __forceinline__ void span_loss(const sph2pob_bbox::Levels& L, float s
                 float g[DIM];
                 eval(lv, b, i_lo + s, row0 + s, k0, g, acc);
                 if (GRAD) {
+                    if constexpr (!F32) {
+#pragma unroll
+                        for (int k = 0; k < DIM; k++) g[k] = gs * g[k];
+                    }
                     if (lv.hw > 0) {
                         const int pp = s / lv.a, aa = s - pp * lv.a;
 #pragma unroll
@@ -79,26 +87,31 @@ __device__ __forceinline__ void span_loss(const sph2pob_bbox::Levels& L, float s
             const int len = lv.hw > 0 ? cnt : cnt * DIM;
             const int lstride = lv.hw > 0 ? lv.ps : 0;
             const int64_t gstride = lv.hw > 0 ? lv.hw : 0;
-            float* g0 = lv.grad + (lv.hw > 0 ? (int64_t)b * lv.a * DIM * lv.hw + p_lo : ((int64_t)b * lv.n + i_lo) * DIM);
-            if (lv.vec) {   // workgroup-uniform; len, lstride, gstride and g0 are multiples of 4 floats
+            T* g0 = level_ptr<T>(lv.grad) + (lv.hw > 0 ? (int64_t)b * lv.a * DIM * lv.hw + p_lo : ((int64_t)b * lv.n + i_lo) * DIM);
+            if (lv.vec) {   // workgroup-uniform; len, lstride, gstride and g0 are multiples of 4 elements
                 const int q4 = len >> 2, total = rows * q4;
                 for (int e = lane; e < total; e += 64) {
                     const int r = e / q4, q = e - r * q4;
-                    *reinterpret_cast<float4*>(g0 + r * gstride + 4 * q) = *reinterpret_cast<const float4*>(tile + r * lstride + 4 * q);
+                    if constexpr (F32) {
+                        *reinterpret_cast<float4*>(g0 + r * gstride + 4 * q) = *reinterpret_cast<const float4*>(tile + r * lstride + 4 * q);
+                    } else {
+                        const float4 v = *reinterpret_cast<const float4*>(tile + r * lstride + 4 * q);
+                        store4(g0 + r * gstride + 4 * q, v.x, v.y, v.z, v.w);
+                    }
                 }
             } else {
                 const int total = rows * len;
                 for (int e = lane; e < total; e += 64) {
                     const int r = e / len, q = e - r * len;
-                    g0[r * gstride + q] = tile[r * lstride + q];
+                    g0[r * gstride + q] = narrow<T>(tile[r * lstride + q]);
                 }
             }
         }
     }
+    if (!F32 && !partial) return;   // kernel-uniform
     const double r = block_sum_f64(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
-
 // f(integral_constant<int, DIM>, bool_constant<GRAD>) for the box_dim (4 | 5) and the gradient request of a call
 template <class F>
 void by_dim_grad(int box_dim, bool grad, F&& f) {
@@ -108,6 +121,12 @@ void by_dim_grad(int box_dim, bool grad, F&& f) {
     };
     if (box_dim == 4) by_grad(std::integral_constant<int, 4>{});
     else by_grad(std::integral_constant<int, 5>{});
+}
+
+// f(T{}, integral_constant<int, DIM>, bool_constant<GRAD>) for the checked dtype of an _h16 entry
+template <class F>
+void by_dtype_dim_grad(int dtype, int box_dim, bool grad, F&& f) {
+    by_h16_dtype(dtype, [&](auto t) { by_dim_grad(box_dim, grad, [&](auto dim, auto gr) { f(t, dim, gr); }); });
 }
 
 }  // namespace

@@ -4,7 +4,12 @@ rule of `weight_reduce_loss`, the level plumbing with its checks, and the gradie
 The stash protocol: when a gradient will be asked for, the one forward pass also writes the gradients for an upstream gradient of
 1 — all levels in one buffer, each a 16-byte aligned view in its own layout — and torch's backward only scales that stash
 (`sph2pob_focal_loss_grad_scale_f32`: in place, a plain `loss.backward()` returns at once).  A second backward through a retained
-graph finds the stash already scaled and handed to autograd, so it recomputes into a fresh buffer."""
+graph finds the stash already scaled and handed to autograd, so it recomputes into a fresh buffer.
+
+16-bit levels (float16 / bfloat16, all on the GPU, contiguous, one dtype: `level_inputs`) are read where they are by the `*_h16`
+entries: the stash has the levels' dtype, and backward reruns the entry for the gradients alone with the upstream gradient folded
+in before the one narrowing (`native_backward`) — no fp32 copy of a level, no fp32 stash, nothing scaled in 16 bits.  CPU tensors,
+mixed dtypes and non-contiguous levels keep the fp32 route."""
 import ctypes
 import struct
 
@@ -114,35 +119,82 @@ def workspace(entry_name, what, dev, ns, hws, images, last):
     return G.scratch(dev, need)
 
 
+def call_sum(entry_name, what, code, dev, ns, hws, images, last, args, out, g=None, skip=0):
+    """sph2pob_<entry_name>_sum_f32(*args, out, workspace, stream) or, for native 16-bit levels (`code` = SPH2POB_DTYPE_*), the
+    _h16 entry with (grad_out, skip_if_one, dtype) in front of the stream; there `out` None asks for the gradients alone: no
+    workspace, no sum."""
+    ws = workspace(entry_name, what, dev, ns, hws, images, last) if out is not None else None   # held over the call
+    if code:
+        G.call(f'sph2pob_{entry_name}_sum_h16', dev, *args, G.ptr(out), G.ptr(ws), G.ptr(g), skip, code, G.raw_stream_of(dev))
+    else:
+        G.call(f'sph2pob_{entry_name}_sum_f32', dev, *args, out.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
+
+
 def scalar(dev):
     """The fp32 scalar an entry writes its sum to."""
     return torch.empty((), dtype=torch.float32, device=dev)
 
 
-def grad_buffer(xs):
-    """One buffer for the gradients of all levels (a single scaling launch in backward), each level a 16-byte aligned view."""
+def grad_buffer(xs, dtype=torch.float32):
+    """One buffer of `dtype` for the gradients of all levels (a single scaling launch in backward), each level a 16-byte aligned
+    view."""
+    per16 = 16 // torch.empty((), dtype=dtype).element_size()
     offs, total = [], 0
     for x in xs:
         offs.append(total)
-        total += (x.numel() + 3) // 4 * 4
-    stash = torch.empty((total,), dtype=torch.float32, device=xs[0].device)
+        total += (x.numel() + per16 - 1) // per16 * per16
+    stash = torch.empty((total,), dtype=dtype, device=xs[0].device)
     return stash, [stash[o:o + x.numel()].view(x.shape) for o, x in zip(offs, xs)]
+
+
+# ---- 16-bit levels: the native route of the *_h16 entries (include/sph2pob_hip.h) ----
+
+def forward_only(levels):
+    """The levels as the autograd node should see them: under torch.no_grad() detached, so that the node allocates no gradient
+    stash (a custom Function's needs_input_grad reports the inputs' requires_grad whatever the grad mode is)."""
+    if torch.is_grad_enabled():
+        return levels
+    return [t.detach() if t.requires_grad else t for t in levels]
+
+
+def level_inputs(levels):
+    """(SPH2POB_DTYPE_* or 0, the tensors the entry reads): the levels themselves on the native 16-bit route
+    (`_torch_glue.h16_dtype_code`), fp32 contiguous ones otherwise."""
+    code = G.h16_dtype_code(levels)
+    return code, (list(levels) if code else [_f32c(t) for t in levels])
 
 
 # ---- the stash protocol of the autograd nodes; `fixed` is the number of arguments in front of the levels ----
 
-def stash_forward(ctx, fixed, xs, launch, saved):
+def stash_forward(ctx, fixed, xs, launch, saved, code=0):
     """Forward side: `launch(views)` runs the fused entry, with the stash's per-level views when any level needs a gradient and
-    None otherwise; `saved` are the tensors the backward needs besides the stash and the levels."""
+    None otherwise; `saved` are the tensors the backward needs besides the stash and the levels.  `code` != 0 (native 16-bit
+    levels): the stash has the levels' dtype and is valid for an upstream gradient of 1."""
     need = any(ctx.needs_input_grad[fixed:])
     stash = views = None
     if need:
-        stash, views = grad_buffer(xs)
+        stash, views = grad_buffer(xs, xs[0].dtype if code else torch.float32)
     launch(views)
     if need:
         ctx.save_for_backward(stash, *saved, *xs)
         ctx.views = views
         ctx.first = True
+
+
+def native_backward(ctx, fixed, grad_out, xs, regrad):
+    """Backward side of native 16-bit levels; `regrad(views, g, skip_if_one)` runs the *_h16 entry for the gradients alone (no
+    sum) with the upstream gradient g folded in before the one narrowing.  The first call recomputes into the forward's stash —
+    every workgroup returns at once when g is exactly 1, a device-side test — later calls (a retained graph) into a fresh buffer.
+    Nothing is ever scaled in 16 bits and no fp32 copy of a gradient exists."""
+    g = _f32c(grad_out).reshape(1)
+    if ctx.first:
+        ctx.first = False
+        views = ctx.views
+        regrad(views, g, 1)
+    else:
+        _fresh, views = grad_buffer(xs, xs[0].dtype)
+        regrad(views, g, 0)
+    return (None,) * fixed + tuple(v if need else None for v, need in zip(views, ctx.needs_input_grad[fixed:]))
 
 
 def stash_backward(ctx, fixed, grad_out, stash, dtypes, relaunch):

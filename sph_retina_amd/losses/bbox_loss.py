@@ -21,7 +21,7 @@ import torch
 
 from .. import _torch_glue as G
 from . import _head as H
-from ._head import _f32c, _reduce_scale
+from ._head import _reduce_scale
 from .sph2pob_iou_loss import LOSS_MODES, _mode_code
 
 
@@ -34,30 +34,33 @@ class _BBoxLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, hws, *preds):
-        xs = [_f32c(p) for p in preds]
+        code, xs = H.level_inputs(preds)   # 16-bit GPU levels are read where they are (sph2pob_bbox_loss_sum_h16)
         images, dim = targets.size(0), anchors.size(1)
         ns = [x.numel() // (images * dim) if images else 0 for x in xs]
         out = H.scalar(xs[0].device)
-        ctx.meta = (wd, coder_cfg, mode, eps, scale, tuple(hws), tuple(ns), [p.dtype for p in preds])
+        ctx.meta = (wd, coder_cfg, mode, eps, scale, tuple(hws), tuple(ns), [p.dtype for p in preds], code)
         H.stash_forward(ctx, _BBoxLossFunction._FIXED, xs,
-                        lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out),
-                        (anchors, targets, weight, avg))
+                        lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out, code),
+                        (anchors, targets, weight, avg), code)
         return out
 
     @staticmethod
-    def _launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out):
+    def _launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out, code=0, g=None, skip=0):
         levels, dev, images, dim = len(xs), xs[0].device, targets.size(0), anchors.size(1)
         means, stds, max_ratio, flags, ctr_clamp = coder_cfg
         ptrs, i64s, f32s = ctypes.c_void_p * levels, ctypes.c_int64 * levels, ctypes.c_float * dim
-        ws = H.workspace('bbox_loss', 'bbox loss', dev, ns, hws, images, dim)   # held over the call
-        G.call('sph2pob_bbox_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None,
-               i64s(*ns), i64s(*hws), levels, images, dim, G.ptr(anchors), G.ptr(targets), G.ptr(weight), wd, f32s(*means), f32s(*stds),
-               max_ratio, flags, ctr_clamp, mode, eps, scale, G.ptr(avg), out.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
+        H.call_sum('bbox_loss', 'bbox loss', code, dev, ns, hws, images, dim,
+                   (ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None, i64s(*ns), i64s(*hws), levels,
+                    images, dim, G.ptr(anchors), G.ptr(targets), G.ptr(weight), wd, f32s(*means), f32s(*stds), max_ratio, flags, ctr_clamp, mode,
+                    eps, scale, G.ptr(avg)), out, g, skip)
 
     @staticmethod
     def backward(ctx, grad_out):
         stash, anchors, targets, weight, avg, *xs = ctx.saved_tensors
-        wd, coder_cfg, mode, eps, scale, hws, ns, dtypes = ctx.meta
+        wd, coder_cfg, mode, eps, scale, hws, ns, dtypes, code = ctx.meta
+        if code:
+            return H.native_backward(ctx, _BBoxLossFunction._FIXED, grad_out, xs, lambda views, g, skip: _BBoxLossFunction._launch(
+                xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, None, code, g, skip))
         relaunch = H.relaunch_fresh(xs, lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg,
                                                                               mode, eps, scale, avg, H.scalar(stash.device)))
         return H.stash_backward(ctx, _BBoxLossFunction._FIXED, grad_out, stash, dtypes, relaunch)
@@ -107,5 +110,5 @@ def sph_bbox_loss(bbox_preds, anchors, bbox_targets, bbox_weights=None, *, bbox_
     scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n, anchors.device)
     w = G.as_f32_nograd(bbox_weights) if bbox_weights is not None else None
     out = _BBoxLossFunction.apply(G.as_f32_nograd(anchors), G.as_f32_nograd(bbox_targets), w, wd, _coder_cfg(bbox_coder, dim), _mode_code(mode),
-                                  float(eps), scale, avg, hws, *bbox_preds)
+                                  float(eps), scale, avg, hws, *H.forward_only(bbox_preds))
     return out * float('nan') if nan else out

@@ -24,7 +24,7 @@ import torch.nn as nn
 from .. import _torch_glue as G
 from ..registry import LOSSES, LOSSES_IS_MMDET
 from . import _head as H
-from ._head import _f32c, _reduce_scale
+from ._head import _reduce_scale
 
 
 class _DeltaLossFunction(torch.autograd.Function):
@@ -36,29 +36,31 @@ class _DeltaLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, targets, weight, wd, beta, scale, avg, hws, *preds):
-        xs = [_f32c(p) for p in preds]
+        code, xs = H.level_inputs(preds)   # 16-bit GPU levels are read where they are (sph2pob_delta_loss_sum_h16)
         images, dim = targets.size(0), targets.size(2)
         ns = [x.numel() // (images * dim) if images else 0 for x in xs]
         out = H.scalar(xs[0].device)
-        ctx.meta = (wd, beta, scale, tuple(hws), tuple(ns), [p.dtype for p in preds])
+        ctx.meta = (wd, beta, scale, tuple(hws), tuple(ns), [p.dtype for p in preds], code)
         H.stash_forward(ctx, _DeltaLossFunction._FIXED, xs,
-                        lambda views: _DeltaLossFunction._launch(xs, views, ns, hws, targets, weight, wd, beta, scale, avg, out),
-                        (targets, weight, avg))
+                        lambda views: _DeltaLossFunction._launch(xs, views, ns, hws, targets, weight, wd, beta, scale, avg, out, code),
+                        (targets, weight, avg), code)
         return out
 
     @staticmethod
-    def _launch(xs, views, ns, hws, targets, weight, wd, beta, scale, avg, out):
+    def _launch(xs, views, ns, hws, targets, weight, wd, beta, scale, avg, out, code=0, g=None, skip=0):
         levels, dev, images, dim = len(xs), xs[0].device, targets.size(0), targets.size(2)
         ptrs, i64s = ctypes.c_void_p * levels, ctypes.c_int64 * levels
-        ws = H.workspace('delta_loss', 'delta loss', dev, ns, hws, images, dim)   # held over the call
-        G.call('sph2pob_delta_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None,
-               i64s(*ns), i64s(*hws), levels, images, dim, G.ptr(targets), G.ptr(weight), wd, beta, scale, G.ptr(avg), out.data_ptr(),
-               G.ptr(ws), G.raw_stream_of(dev))
+        H.call_sum('delta_loss', 'delta loss', code, dev, ns, hws, images, dim,
+                   (ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None, i64s(*ns), i64s(*hws), levels,
+                    images, dim, G.ptr(targets), G.ptr(weight), wd, beta, scale, G.ptr(avg)), out, g, skip)
 
     @staticmethod
     def backward(ctx, grad_out):
         stash, targets, weight, avg, *xs = ctx.saved_tensors
-        wd, beta, scale, hws, ns, dtypes = ctx.meta
+        wd, beta, scale, hws, ns, dtypes, code = ctx.meta
+        if code:
+            return H.native_backward(ctx, _DeltaLossFunction._FIXED, grad_out, xs, lambda views, g, skip: _DeltaLossFunction._launch(
+                xs, views, ns, hws, targets, weight, wd, beta, scale, avg, None, code, g, skip))
         relaunch = H.relaunch_fresh(xs, lambda views: _DeltaLossFunction._launch(xs, views, ns, hws, targets, weight, wd, beta, scale, avg, H.scalar(stash.device)))
         return H.stash_backward(ctx, _DeltaLossFunction._FIXED, grad_out, stash, dtypes, relaunch)
 
@@ -96,7 +98,7 @@ def sph_delta_loss(bbox_preds, bbox_targets, bbox_weights=None, *, beta=0.0, avg
         raise ValueError(f'the levels hold {total} anchors per image, bbox_targets {n}')
     scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n * dim, bbox_targets.device)
     w = G.as_f32_nograd(bbox_weights) if bbox_weights is not None else None
-    out = _DeltaLossFunction.apply(G.as_f32_nograd(bbox_targets), w, wd, beta, scale, avg, hws, *bbox_preds)
+    out = _DeltaLossFunction.apply(G.as_f32_nograd(bbox_targets), w, wd, beta, scale, avg, hws, *H.forward_only(bbox_preds))
     return out * float('nan') if nan else out
 
 

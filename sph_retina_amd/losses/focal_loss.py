@@ -45,31 +45,33 @@ class _FocalSumFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, classes, labels, weight, wmode, gamma, alpha, scale, avg, hws, *scores):
-        xs = [_f32c(s) for s in scores]
+        code, xs = H.level_inputs(scores)   # 16-bit GPU levels are read where they are (sph2pob_focal_loss_sum_h16)
         images = xs[0].size(0)
         ctx.classes = classes
         ns = [x.numel() // (images * classes) if images else 0 for x in xs]
         out = H.scalar(xs[0].device)
-        ctx.meta = (wmode, gamma, alpha, scale, tuple(hws), tuple(ns), [s.dtype for s in scores])
+        ctx.meta = (wmode, gamma, alpha, scale, tuple(hws), tuple(ns), [s.dtype for s in scores], code)
         H.stash_forward(ctx, _FocalSumFunction._FIXED, xs,
-                        lambda views: _FocalSumFunction._launch(xs, views, ns, hws, classes, labels, weight, wmode, gamma, alpha, scale, avg, out),
-                        (labels, weight, avg))
+                        lambda views: _FocalSumFunction._launch(xs, views, ns, hws, classes, labels, weight, wmode, gamma, alpha, scale, avg, out, code),
+                        (labels, weight, avg), code)
         return out
 
     @staticmethod
-    def _launch(xs, views, ns, hws, classes, labels, weight, wmode, gamma, alpha, scale, avg, out):
+    def _launch(xs, views, ns, hws, classes, labels, weight, wmode, gamma, alpha, scale, avg, out, code=0, g=None, skip=0):
         levels, dev, images = len(xs), xs[0].device, xs[0].size(0)
         ptrs, i64s = ctypes.c_void_p * levels, ctypes.c_int64 * levels
-        ws = H.workspace('focal_loss', 'focal loss', dev, ns, hws, images, classes)   # held over the call
-        G.call('sph2pob_focal_loss_sum_f32', dev, ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None,
-               i64s(*ns), i64s(*hws), levels, images, classes, G.ptr(labels), G.ptr(weight), wmode, gamma, alpha, scale, G.ptr(avg),
-               out.data_ptr(), G.ptr(ws), G.raw_stream_of(dev))
+        H.call_sum('focal_loss', 'focal loss', code, dev, ns, hws, images, classes,
+                   (ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None, i64s(*ns), i64s(*hws), levels,
+                    images, classes, G.ptr(labels), G.ptr(weight), wmode, gamma, alpha, scale, G.ptr(avg)), out, g, skip)
 
     @staticmethod
     def backward(ctx, grad_out):
         stash, labels, weight, avg, *xs = ctx.saved_tensors
-        wmode, gamma, alpha, scale, hws, ns, dtypes = ctx.meta
+        wmode, gamma, alpha, scale, hws, ns, dtypes, code = ctx.meta
         dev = stash.device
+        if code:
+            return H.native_backward(ctx, _FocalSumFunction._FIXED, grad_out, xs, lambda views, g, skip: _FocalSumFunction._launch(
+                xs, views, ns, hws, ctx.classes, labels, weight, wmode, gamma, alpha, scale, avg, None, code, g, skip))
         if len(xs) == 1 and hws[0] == 0:
             def relaunch(g):   # one flat level: the two-pass kernel, which takes the upstream gradient itself
                 views = [torch.empty_like(xs[0])]
@@ -204,7 +206,7 @@ def sph_focal_loss(cls_scores, labels, label_weights=None, *, gamma=2.0, alpha=0
         raise ValueError(f'the levels hold {total} anchors per image, labels {labels.size(1)}')
     scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n * classes, labels.device)
     w = G.as_f32_nograd(label_weights) if label_weights is not None else None
-    out = _FocalSumFunction.apply(classes, _labels(labels), w, wmode, gamma, alpha, scale, avg, hws, *cls_scores)
+    out = _FocalSumFunction.apply(classes, _labels(labels), w, wmode, gamma, alpha, scale, avg, hws, *H.forward_only(cls_scores))
     return out * float('nan') if nan else out
 
 

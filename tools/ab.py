@@ -20,7 +20,10 @@ Workloads (all through the C ABI, buffers allocated once, HIP events around `--l
   nms       sph2pob_nms_segmented_f32 on 5 000 sorted boxes x 37 classes and on one class of 5 000
   bnms      sph2pob_batched_nms_f32 (unsorted input, no host work) on the same two scenes
   head_losses  sph2pob_{focal,bbox,delta}_loss_sum_f32, each timed on its own, with gradients: 8 images x the 5 NCHW levels of the
-            512 x 1024 ERP (98 208 anchors), 37 classes, dim 4, CIoU closed-form / L1, ~1 % live rows, a device avg_factor
+            512 x 1024 ERP (98 208 anchors), 37 classes, dim 4, CIoU closed-form / L1, ~1 % live rows, a device avg_factor; then the
+            same on bf16 levels, forward + first backward with g = 1 and g = 0.5: sph2pob_*_sum_h16 where the arm's library has
+            them, the cast route (.float(), the _f32 entry, the stash scaling, .to(bfloat16)) where it has not (the parent build)
+  test_bboxes_h16  sph2pob_test_bboxes on bf16 levels at that shape (PANDORA's test_cfg): the _h16 entry, or .float() + the _f32 entry
   adjoint   sph2pob_transform_bwd_f32 / _general_f32, every instantiated (variant, dim) x edge x angle x jitter, --pairs N
 Every arm's outputs are compared with the first arm's (bit equality is reported, not assumed).
 """
@@ -258,6 +261,80 @@ def workloads(args, torch, G):
             max_ratio, 1, 32.0, 3, 1e-6, 1.0, G.ptr(avg), out, ws, st))
         yield entry('delta_loss', box, 4, lambda lib, xp, gp, out, ws: lib.sph2pob_delta_loss_sum_f32(
             xp, gp, ns, hws, levels, images, 4, G.ptr(deltas_t), G.ptr(weights), 4, 0.0, 1.0, G.ptr(avg), out, ws, st))
+
+        # bf16 levels, forward + first backward with an upstream gradient g.  An arm whose library has the _h16 entries takes the
+        # native route (the entry with a bf16 stash, then the gradient-only call with grad_out = g, skip_if_one = 1); an arm
+        # without them (the parent build) takes what a bf16 caller got there: .float() of the levels, the _f32 entry with
+        # gradients, the stash scaling, .to(bfloat16) of the gradients.  The outputs compared are the loss and the bf16 gradients.
+        bf = torch.bfloat16
+        cls16, box16 = [x.to(bf) for x in cls], [x.to(bf) for x in box]
+
+        def entry16(name, xs, last, args, gval):
+            def make(lib):
+                out = torch.empty(1, device='cuda')
+                ws = torch.empty(getattr(lib, f'sph2pob_{name}_workspace_bytes')(ns, hws, levels, images, last), dtype=torch.uint8, device='cuda')
+                g = torch.full((1,), gval, device='cuda')
+                h16 = getattr(lib, f'sph2pob_{name}_sum_h16', None)
+                held = {}
+                if h16 is not None:
+                    grads = [torch.empty_like(x) for x in xs]
+                    xp, gp = ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in grads])
+
+                    def launch():
+                        rc = h16(xp, gp, ns, hws, levels, images, last, *args, G.ptr(out), G.ptr(ws), None, 0, 2, st)
+                        return rc | h16(xp, gp, ns, hws, levels, images, last, *args, None, None, G.ptr(g), 1, 2, st)
+                    return launch, [out] + grads
+                f32 = getattr(lib, f'sph2pob_{name}_sum_f32')
+                grads = [torch.empty_like(x) for x in xs]   # the bf16 gradients the caller ends up with
+
+                def launch():
+                    fs = [x.float() for x in xs]
+                    stash = [torch.empty_like(f) for f in fs]
+                    rc = f32(ptrs(*[G.ptr(f) for f in fs]), ptrs(*[G.ptr(v) for v in stash]), ns, hws, levels, images, last, *args, G.ptr(out),
+                             G.ptr(ws), st)
+                    for v, o in zip(stash, grads):
+                        rc |= lib.sph2pob_focal_loss_grad_scale_f32(G.ptr(v), G.ptr(g), G.ptr(v), v.numel(), st)
+                        o.copy_(v)   # the narrowing cast
+                    held['last'] = (fs, stash)
+                    return rc
+                return launch, [out] + grads
+            return f'head_losses bf16 {name} fwd+bwd g={gval} {images} x {n}', make
+        for gval in (1.0, 0.5):
+            yield entry16('focal_loss', cls16, classes, (G.ptr(labels), None, 0, 2.0, 0.25, 1.0, G.ptr(avg)), gval)
+            yield entry16('bbox_loss', box16, 4, (G.ptr(anchors), G.ptr(boxes), G.ptr(weights), 4, means, stds, max_ratio, 1, 32.0, 3, 1e-6,
+                                                  1.0, G.ptr(avg)), gval)
+            yield entry16('delta_loss', box16, 4, (G.ptr(deltas_t), G.ptr(weights), 4, 0.0, 1.0, G.ptr(avg)), gval)
+    elif args.workload == 'test_bboxes_h16':
+        # sph2pob_test_bboxes on bf16 levels (PANDORA's test_cfg, 8 images x the 5 NCHW levels, 37 classes): the _h16 entry where the
+        # arm's library has it, the parent's route (.float() of every level, then the _f32 entry) where it has not
+        import math
+        from tools import demo_hot_path as D
+        images, classes, levels = 8, 37, len(D.LEVEL_SHAPES)
+        anchors = D.retina_level_anchors()
+        cls, box = D.head_outputs(images, classes)
+        cls, box = [x.to(torch.bfloat16) for x in cls], [x.to(torch.bfloat16) for x in box]
+        ptrs, i64s, f4 = ctypes.c_void_p * levels, ctypes.c_int64 * levels, ctypes.c_float * 4
+        ns, hws = i64s(*[9 * h * w for h, w in D.LEVEL_SHAPES]), i64s(*[h * w for h, w in D.LEVEL_SHAPES])
+        means, stds, max_ratio = f4(0, 0, 0, 0), f4(0.1, 0.1, 0.2, 0.2), abs(math.log(16 / 1000))
+        ap = ptrs(*[G.ptr(a) for a in anchors])
+
+        def make(lib):
+            f32, i64 = dict(dtype=torch.float32, device='cuda'), dict(dtype=torch.int64, device='cuda')
+            o = [torch.empty((images, 100, 5), **f32), torch.empty((images, 100), **i64), torch.empty((images, 100), **i64), torch.empty((images,), **i64)]
+            ws = torch.empty(lib.sph2pob_get_bboxes_workspace_bytes(ns, levels, images, classes, 4, 1000), dtype=torch.uint8, device='cuda')
+            mid = (ns, hws, levels, images, classes, 4, 0, 0.05, 1000, means, stds, max_ratio, 1, 32.0, 5, 0, 0.5, 100, *[G.ptr(t) for t in o], G.ptr(ws))
+            h16 = getattr(lib, 'sph2pob_test_bboxes_h16', None)
+            if h16 is not None:
+                cp, bp = ptrs(*[G.ptr(x) for x in cls]), ptrs(*[G.ptr(x) for x in box])
+                return (lambda: h16(cp, bp, ap, *mid, 2, st)), o
+            held = {}
+
+            def launch():
+                cf, bf32 = [x.float() for x in cls], [x.float() for x in box]
+                held['last'] = (cf, bf32)
+                return lib.sph2pob_test_bboxes_f32(ptrs(*[G.ptr(x) for x in cf]), ptrs(*[G.ptr(x) for x in bf32]), ap, *mid, st)
+            return launch, o
+        yield f'test_bboxes bf16 unbiased {images} x {sum(a.size(0) for a in anchors)}', make
     elif args.workload == 'adjoint':
         n = int(args.pairs.split(',')[0])
         g = torch.Generator().manual_seed(7)
@@ -314,7 +391,8 @@ def run(args):
                 torch.cuda.synchronize()
                 times[k].append(e0.elapsed_time(e1) / args.launches * 1e3)
         for (label, _), t in zip(arms, times):
-            say(f'{title}: {label:24s} median {statistics.median(t):8.3f} us  min {min(t):8.3f}  all {" ".join("%.2f" % x for x in t)}')
+            say(f'{title}: {label:24s} median {statistics.median(t):8.3f} us  min {min(t):8.3f}  max-min {max(t) - min(t):7.3f}  '
+                f'all {" ".join("%.2f" % x for x in t)}')
     shutil.rmtree(tmp, ignore_errors=True)
     if args.tag:
         os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
