@@ -702,6 +702,46 @@ int sph2pob_test_bboxes_h16(const void* const* cls_scores, const void* const* bb
                             int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
                             int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream);
 
+/* ---- fused Gaussian box-regression loss: loss_single's regression half with Sph2PobGDLoss / Sph2PobKFLoss -------------------------
+ * sph2pob_bbox_loss_sum_f32 with the Gaussian body of the sph2pob_gauss_loss_* launchers in place of the IoU family: per row whose
+ * mean weight is not zero, sph2pob_coder_decode_f32 with num_classes = 1, then the loss element and adjoint of
+ * sph2pob_gauss_loss_fwd_grad_f32, then the diagonal Jacobian of sph2pob_coder_decode_bwd_f32; grads receive
+ * ((scale_eff * w_i) * dL/dbox_k) * J_k.
+ *
+ * sph2pob_gauss_bbox_loss_sum_f32 — the arguments of sph2pob_bbox_loss_sum_f32 up to and including ctr_clamp, with their meaning,
+ * layouts, limits, store widths and zero-weight rule (a row of mean weight exactly 0 is NEVER READ and gets an exact zero loss and
+ * +0.0f gradients); then, in place of (loss_mode, eps),
+ *   type_flags, fun, tau, alpha, opts, beta, eps   exactly the trailing parameters of sph2pob_gauss_loss_fwd_f32 (type_flags:
+ *                SPH2POB_GAUSS_* | SPH2POB_FLAG_REFERENCE_ORDER)
+ * then scale, avg_factor, out, workspace, stream as for sph2pob_bbox_loss_sum_f32, with
+ *   workspace    sph2pob_gauss_bbox_loss_workspace_bytes(level_n, level_hw, num_levels, B, box_dim) bytes (0: shapes not accepted)
+ * Two launches whatever B and the number of levels are; nothing is read back, nothing is allocated; capturable.  B n == 0 writes
+ * out[0] = 0.  After the call torch's backward is sph2pob_focal_loss_grad_scale_f32 on the gradient buffer.
+ * Errors, checked in this order before anything is enqueued: type_flags flags -> SPH2POB_ERR_OPTION; box_dim -> SPH2POB_ERR_DIM;
+ * loss type, a post-map the type does not accept, opts bits, weight_dim (with a weight), coder_flags, max_ratio < 0 ->
+ * SPH2POB_ERR_OPTION; then the shape and table checks of sph2pob_bbox_loss_sum_f32 with the same codes and limits (num_levels, B ->
+ * SIZE; NULL level_n / bbox_preds table -> NULL; n_l, level_hw, B n_l dim >= 2^31 - 4096, more than 360 / dim anchors per position
+ * -> SIZE); a NULL table entry of a level with rows, out, workspace, anchors or targets with rows -> SPH2POB_ERR_NULL.
+ *
+ * sph2pob_gauss_bbox_loss_sum_h16 — float16 / bfloat16 levels read where they are: differs from the _f32 entry exactly as
+ * sph2pob_bbox_loss_sum_h16 differs from sph2pob_bbox_loss_sum_f32 (grad_out, skip_if_one, dtype in front of stream; out and
+ * workspace may be NULL; the dtype is checked first).  No CPU twin.
+ */
+int64_t sph2pob_gauss_bbox_loss_workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                                int box_dim);
+int sph2pob_gauss_bbox_loss_sum_f32(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                    int num_levels, int64_t num_images, int box_dim, const float* anchors, const float* targets,
+                                    const float* weight, int weight_dim, const float* means_host, const float* stds_host,
+                                    float max_ratio, int coder_flags, float ctr_clamp, int type_flags, int fun, float tau, float alpha,
+                                    int opts, float beta, float eps, float scale, const float* avg_factor, float* out,
+                                    void* workspace, void* stream);
+int sph2pob_gauss_bbox_loss_sum_h16(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                    int num_levels, int64_t num_images, int box_dim, const float* anchors, const float* targets,
+                                    const float* weight, int weight_dim, const float* means_host, const float* stds_host,
+                                    float max_ratio, int coder_flags, float ctr_clamp, int type_flags, int fun, float tau, float alpha,
+                                    int opts, float beta, float eps, float scale, const float* avg_factor, float* out,
+                                    void* workspace, const float* grad_out, int skip_if_one, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ LIB_DIR = os.path.join(_HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_hip.so')
 HOST_LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_host.so')
 SOURCES = ['sph2pob_iou.hip', 'sph2pob_assign.hip', 'sph2pob_loss.hip', 'sph2pob_nms.hip', 'sph2pob_coder.hip', 'sph2pob_get_bboxes.hip',
-           'sph2pob_focal.hip', 'sph2pob_bbox_loss.hip', 'sph2pob_delta_loss.hip']
+           'sph2pob_focal.hip', 'sph2pob_bbox_loss.hip', 'sph2pob_delta_loss.hip', 'sph2pob_gauss_bbox_loss.hip']
 HOST_SOURCES = ['sph2pob_host.hip']
 HOST_FLAGS = ['--offload-arch=gfx950', '--cuda-host-only', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-pthread']
 
@@ -45,8 +45,8 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_gauss_loss_fwd_f32', 'sph2pob_gauss_loss_bwd_f32', 'sph2pob_gauss_loss_fwd_sum_f32',
               'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32', 'sph2pob_anchor_targets_any_f32', 'sph2pob_get_bboxes_f32', 'sph2pob_test_bboxes_f32', 'sph2pob_focal_loss_sum_f32',
               'sph2pob_focal_loss_fwd_f32', 'sph2pob_focal_loss_bwd_f32', 'sph2pob_focal_loss_grad_scale_f32', 'sph2pob_bbox_loss_sum_f32',
-              'sph2pob_delta_loss_sum_f32']
-HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp',
+              'sph2pob_delta_loss_sum_f32', 'sph2pob_gauss_bbox_loss_sum_f32']
+HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp', 'sph2pob_gauss_bbox_loss.hpp',
            'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
 # half the rate of plain VALU on gfx950 (tools/ubench/valu_rate2.hip), measured 12 % slower on the dominant kernel
@@ -150,6 +150,12 @@ SIGNATURES = {
     'sph2pob_bbox_loss_sum_f32': [ctypes.c_void_p] * 4 + [_int, _i64, _int, _c_f32p, _c_f32p, _c_f32p, _int, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_float, _int, ctypes.c_float, _int, ctypes.c_float, ctypes.c_float, _c_f32p, _c_f32p,
                                   ctypes.c_void_p, ctypes.c_void_p],
+    'sph2pob_gauss_bbox_loss_workspace_bytes': [ctypes.c_void_p, ctypes.c_void_p, _int, _i64, _int],
+    # the arguments of sph2pob_bbox_loss_sum_f32 up to ctr_clamp, the Gaussian tail (type_flags, fun, tau, alpha, opts, beta, eps),
+    # then scale, avg_factor, out, workspace, stream
+    'sph2pob_gauss_bbox_loss_sum_f32': [ctypes.c_void_p] * 4 + [_int, _i64, _int, _c_f32p, _c_f32p, _c_f32p, _int, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_float, _int, ctypes.c_float] + _GAUSS_TAIL[:-1] +
+                                       [ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p],
     'sph2pob_delta_loss_workspace_bytes': [ctypes.c_void_p, ctypes.c_void_p, _int, _i64, _int],
     # level tables (bbox_preds, grads, n, hw), num_levels, B, box_dim, targets, weight, weight_dim, beta, scale, avg_factor, out,
     # workspace, stream
@@ -168,7 +174,7 @@ SIGNATURES = {
 # The 16-bit level entries (SPH2POB_DTYPE_*; no CPU twins): the arguments of the _f32 sibling with `dtype` in front of the stream,
 # and for the losses (grad_out, skip_if_one) in front of that
 H16_DTYPES = {'float16': 1, 'bfloat16': 2}
-for _name in ('focal_loss_sum', 'bbox_loss_sum', 'delta_loss_sum'):
+for _name in ('focal_loss_sum', 'bbox_loss_sum', 'delta_loss_sum', 'gauss_bbox_loss_sum'):
     SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_c_f32p, _int, _int, ctypes.c_void_p]
 for _name in ('get_bboxes', 'test_bboxes'):
     SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_int, ctypes.c_void_p]
@@ -178,7 +184,7 @@ _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_targe
              'sph2pob_anchor_targets_workspace_bytes': ctypes.c_int64, 'sph2pob_anchor_targets_state_bytes': ctypes.c_int64,
              'sph2pob_batched_nms_workspace_bytes': ctypes.c_int64, 'sph2pob_get_bboxes_workspace_bytes': ctypes.c_int64,
              'sph2pob_focal_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_bbox_loss_workspace_bytes': ctypes.c_int64,
-             'sph2pob_delta_loss_workspace_bytes': ctypes.c_int64}
+             'sph2pob_delta_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_gauss_bbox_loss_workspace_bytes': ctypes.c_int64}
 
 ABI_VERSION = 6
 

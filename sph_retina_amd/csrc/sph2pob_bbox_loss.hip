@@ -1,6 +1,7 @@
 // Fused box-regression loss kernels (level table and checks: sph2pob_bbox_loss.hpp; the span scheme: sph2pob_span_loss.hpp).
-//   bbox_loss_kernel   a row takes part when its mean weight is not zero; a live row runs gather -> decode -> loss + adjoint ->
-//                      decode adjoint.  (The loss kernels of sph2pob_loss.hip skip per wave of 64 rows; here the rule is per row.)
+//   bbox_loss_kernel   decoded_span_loss with pair_loss: a row takes part when its mean weight is not zero; a live row runs
+//                      gather -> decode -> loss + adjoint -> decode adjoint.  (The loss kernels of sph2pob_loss.hip skip per wave
+//                      of 64 rows; here the rule is per row.)
 //   head_final_kernel  (sph2pob_head_loss.hpp) adds the partials in a fixed order
 #include "sph2pob_span_loss.hpp"
 
@@ -20,33 +21,10 @@ __device__ __forceinline__ void bbox_loss_body(const BL::Levels& L, const float*
                                                const float* __restrict__ weight, int wd, const CD::Norm& nm, float max_ratio, int cflags,
                                                float ctr_clamp, int loss_mode, float eps, float scale, const float* __restrict__ avg_factor,
                                                float gs, double* __restrict__ partial) {
-    span_loss<T, DIM, GRAD>(
-        L, scale, avg_factor, gs, partial,
-        [&](int64_t row) { return sph2pob::element_weight<DIM>(weight, wd, row) != 0.0f; },
-        [&](const BL::Level& lv, int b, int i, int64_t row, float k0, float (&g)[DIM], double& acc) {
-            const float w = sph2pob::element_weight<DIM>(weight, wd, row);
-            float p[5], d[5], t[5], box[5], jac[5], gx[5], gy[5];
-            int64_t stride;
-            const int64_t off = BL::delta_offset(lv, DIM, b, i, &stride);
-            const float* ap = anchors + (lv.row_off + i) * DIM;
-            const float* tp = targets + row * DIM;
-            const T* dp = level_ptr<T>(lv.pred);
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                p[k] = k < DIM ? ap[k] : 0.0f;
-                d[k] = k < DIM ? (float)dp[off + k * stride] : 0.0f;
-                t[k] = k < DIM ? tp[k] : 0.0f;
-                box[k] = 0.0f;
-            }
-            CD::decode_one<DIM, GRAD>(p, d, nm, max_ratio, cflags, ctr_clamp, box, GRAD ? jac : nullptr);
-            const float lo = sph2pob::pair_loss<DIM, GRAD, FAST>(box, t, loss_mode, eps, nullptr, gx, gy);
-            acc += (double)(lo * w);
-            if (GRAD) {
-                const float gw = k0 * w;
-#pragma unroll
-                for (int k = 0; k < DIM; k++) g[k] = (gw * gx[k]) * jac[k];
-            }
-        });
+    decoded_span_loss<T, DIM, GRAD>(L, anchors, targets, weight, wd, nm, max_ratio, cflags, ctr_clamp, scale, avg_factor, gs, partial,
+                                    [&](const float (&box)[5], const float (&t)[5], float (&gx)[5], float (&gy)[5]) {
+                                        return sph2pob::pair_loss<DIM, GRAD, FAST>(box, t, loss_mode, eps, nullptr, gx, gy);
+                                    });
 }
 
 template <int DIM, bool FAST, bool GRAD>

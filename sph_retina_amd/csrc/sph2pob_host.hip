@@ -29,6 +29,7 @@
 #include "sph2pob_assign.hpp"
 #include "sph2pob_focal.hpp"
 #include "sph2pob_bbox_loss.hpp"
+#include "sph2pob_gauss_bbox_loss.hpp"
 #include "sph2pob_delta_loss.hpp"
 
 namespace {
@@ -840,13 +841,14 @@ int sph2pob_focal_loss_grad_scale_f32_cpu(const float* stash, const float* grad_
 
 }  // extern "C"
 
-// ---- fused box-regression loss: the twin of sph2pob_bbox_loss.hip on decode_one + pair_loss, row by row ----
+// ---- fused box-regression losses: the twins of sph2pob_bbox_loss.hip and sph2pob_gauss_bbox_loss.hip on decode_one + the
+// per-pair body (IouBody: pair_loss; GaussBody: pair_gauss_loss), row by row ----
 namespace {
 namespace BL = sph2pob_bbox;
 
-template <int DIM, bool FAST>
+template <int DIM, bool FAST, class Body>
 double bbox_loss_rows(const BL::Levels& L, const float* anchors, const float* targets, const float* weight, int wd, const C::Norm& nm,
-                      float max_ratio, int cflags, float ctr_clamp, int mode, float eps, float k0) {
+                      float max_ratio, int cflags, float ctr_clamp, const Body& body, float k0) {
     return head_rows_sum(L, L.rows, [&](const BL::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
         const float w = element_weight<DIM>(weight, wd, row);
         box_row<DIM>(lv, b, i, w != 0.0f, [&](int64_t off, int64_t stride) {
@@ -858,7 +860,7 @@ double bbox_loss_rows(const BL::Levels& L, const float* anchors, const float* ta
                 t[k] = k < DIM ? targets[row * DIM + k] : 0.0f;
             }
             C::decode_one<DIM, true>(p, d, nm, max_ratio, cflags, ctr_clamp, box, jac);
-            const float lo1 = pair_loss<DIM, true, FAST>(box, t, mode, eps, nullptr, gx, gy);
+            const float lo1 = body.template eval<DIM, true, FAST>(box, t, nullptr, gx, gy);
             acc += (double)(lo1 * w);
             if (lv.grad) {
                 const float g = k0 * w;
@@ -866,6 +868,16 @@ double bbox_loss_rows(const BL::Levels& L, const float* anchors, const float* ta
             }
         });
     });
+}
+
+// the sum of the rows for the box_dim and the arithmetic of a call
+template <class Body>
+double bbox_loss_total(int box_dim, bool fast, const BL::Levels& L, const float* anchors, const float* targets, const float* weight, int wd,
+                       const C::Norm& nm, float max_ratio, int cflags, float ctr_clamp, const Body& body, float k0) {
+#define SPH_BBOX_ROWS(D, F) bbox_loss_rows<D, F>(L, anchors, targets, weight, wd, nm, max_ratio, cflags, ctr_clamp, body, k0)
+    if (box_dim == 4) return fast ? SPH_BBOX_ROWS(4, true) : SPH_BBOX_ROWS(4, false);
+    return fast ? SPH_BBOX_ROWS(5, true) : SPH_BBOX_ROWS(5, false);
+#undef SPH_BBOX_ROWS
 }
 }  // namespace
 
@@ -882,15 +894,32 @@ int sph2pob_bbox_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* gr
     if (!out || !workspace || (L.rows > 0 && (!anchors || !targets))) return SPH2POB_ERR_NULL;
     const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
     const float k0 = BL::effective_scale(scale, avg_factor);
-    const int mode = loss_mode & 0xff;
     const bool fast = !(loss_mode & SPH2POB_FLAG_REFERENCE_ORDER);
     double total = 0.0;
-    if (L.rows > 0) {
-#define SPH_BBOX_ROWS(D, F) bbox_loss_rows<D, F>(L, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags, ctr_clamp, mode, eps, k0)
-        if (box_dim == 4) total = fast ? SPH_BBOX_ROWS(4, true) : SPH_BBOX_ROWS(4, false);
-        else total = fast ? SPH_BBOX_ROWS(5, true) : SPH_BBOX_ROWS(5, false);
-#undef SPH_BBOX_ROWS
-    }
+    if (L.rows > 0)
+        total = bbox_loss_total(box_dim, fast, L, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags, ctr_clamp,
+                                IouBody{loss_mode & 0xff, eps}, k0);
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+int sph2pob_gauss_bbox_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                        int num_levels, int64_t num_images, int box_dim, const float* anchors, const float* targets,
+                                        const float* weight, int weight_dim, const float* means_host, const float* stds_host,
+                                        float max_ratio, int coder_flags, float ctr_clamp, int type_flags, int fun, float tau,
+                                        float alpha, int opts, float beta, float eps, float scale, const float* avg_factor, float* out,
+                                        void* workspace, void*) {
+    if (int rc = sph2pob_gauss_bbox::check_options(box_dim, weight, weight_dim, max_ratio, coder_flags, type_flags, fun, opts)) return rc;
+    BL::Levels L;
+    if (int rc = BL::make_levels(bbox_preds, grads, level_n, level_hw, num_levels, num_images, box_dim, true, &L)) return rc;
+    if (!out || !workspace || (L.rows > 0 && (!anchors || !targets))) return SPH2POB_ERR_NULL;
+    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
+    const float k0 = BL::effective_scale(scale, avg_factor);
+    const bool fast = !(type_flags & SPH2POB_FLAG_REFERENCE_ORDER);
+    double total = 0.0;
+    if (L.rows > 0)
+        total = bbox_loss_total(box_dim, fast, L, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags, ctr_clamp,
+                                sph2pob_gauss_bbox::make_body(type_flags, fun, tau, alpha, opts, beta, eps), k0);
     out[0] = (float)(total * (double)k0);
     return SPH2POB_OK;
 }

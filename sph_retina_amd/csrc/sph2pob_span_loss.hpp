@@ -112,6 +112,45 @@ __device__ __forceinline__ void span_loss(const sph2pob_bbox::Levels& L, float s
     const double r = block_sum_f64(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
+
+// span_loss for a loss on DECODED boxes (bbox_loss_kernel, gauss_bbox_loss_kernel): a row takes part when its mean weight is not
+// zero; a live row runs gather -> decode_one -> pair(box, target, gx, gy) -> decode Jacobian.  pair returns the row's loss and,
+// under GRAD, leaves d loss / d box in gx.  The gradient is ((k0 w) gx[k]) jac[k], the composition's product order.
+template <class T, int DIM, bool GRAD, class Pair>
+__device__ __forceinline__ void decoded_span_loss(const sph2pob_bbox::Levels& L, const float* __restrict__ anchors,
+                                                  const float* __restrict__ targets, const float* __restrict__ weight, int wd,
+                                                  const sph2pob_coder::Norm& nm, float max_ratio, int cflags, float ctr_clamp, float scale,
+                                                  const float* __restrict__ avg_factor, float gs, double* __restrict__ partial, Pair pair) {
+    namespace BL = sph2pob_bbox;
+    span_loss<T, DIM, GRAD>(
+        L, scale, avg_factor, gs, partial,
+        [&](int64_t row) { return sph2pob::element_weight<DIM>(weight, wd, row) != 0.0f; },
+        [&](const BL::Level& lv, int b, int i, int64_t row, float k0, float (&g)[DIM], double& acc) {
+            const float w = sph2pob::element_weight<DIM>(weight, wd, row);
+            float p[5], d[5], t[5], box[5], jac[5], gx[5], gy[5];
+            int64_t stride;
+            const int64_t off = BL::delta_offset(lv, DIM, b, i, &stride);
+            const float* ap = anchors + (lv.row_off + i) * DIM;
+            const float* tp = targets + row * DIM;
+            const T* dp = level_ptr<T>(lv.pred);
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                p[k] = k < DIM ? ap[k] : 0.0f;
+                d[k] = k < DIM ? (float)dp[off + k * stride] : 0.0f;
+                t[k] = k < DIM ? tp[k] : 0.0f;
+                box[k] = 0.0f;
+            }
+            sph2pob_coder::decode_one<DIM, GRAD>(p, d, nm, max_ratio, cflags, ctr_clamp, box, GRAD ? jac : nullptr);
+            const float lo = pair(box, t, gx, gy);
+            acc += (double)(lo * w);
+            if (GRAD) {
+                const float gw = k0 * w;
+#pragma unroll
+                for (int k = 0; k < DIM; k++) g[k] = (gw * gx[k]) * jac[k];
+            }
+        });
+}
+
 // f(integral_constant<int, DIM>, bool_constant<GRAD>) for the box_dim (4 | 5) and the gradient request of a call
 template <class F>
 void by_dim_grad(int box_dim, bool grad, F&& f) {

@@ -27,42 +27,43 @@ from .sph2pob_iou_loss import LOSS_MODES, _mode_code
 
 class _BBoxLossFunction(torch.autograd.Function):
     """(anchors, targets, weight, ..., *bbox_preds of L levels) -> scale_eff * sum of the weighted box losses; one node with L
-    inputs and the gradient stash of `_head`.  A second backward through a retained graph recomputes with the same entry into a
-    fresh buffer."""
+    inputs and the gradient stash of `_head`.  `entry` names the C entry (sph2pob_<entry>_sum_f32 / _h16) and `tail` holds its
+    arguments between ctr_clamp and scale: ('bbox_loss', (loss_mode, eps)) here, the Gaussian tail for `sph_gauss_bbox_loss`.
+    A second backward through a retained graph recomputes with the same entry into a fresh buffer."""
 
     _FIXED = 10   # arguments in front of the levels
 
     @staticmethod
-    def forward(ctx, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, hws, *preds):
+    def forward(ctx, anchors, targets, weight, wd, coder_cfg, entry, tail, scale, avg, hws, *preds):
         code, xs = H.level_inputs(preds)   # 16-bit GPU levels are read where they are (sph2pob_bbox_loss_sum_h16)
         images, dim = targets.size(0), anchors.size(1)
         ns = [x.numel() // (images * dim) if images else 0 for x in xs]
         out = H.scalar(xs[0].device)
-        ctx.meta = (wd, coder_cfg, mode, eps, scale, tuple(hws), tuple(ns), [p.dtype for p in preds], code)
+        ctx.meta = (wd, coder_cfg, entry, tail, scale, tuple(hws), tuple(ns), [p.dtype for p in preds], code)
         H.stash_forward(ctx, _BBoxLossFunction._FIXED, xs,
-                        lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out, code),
+                        lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, entry, tail, scale, avg, out, code),
                         (anchors, targets, weight, avg), code)
         return out
 
     @staticmethod
-    def _launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, out, code=0, g=None, skip=0):
+    def _launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, entry, tail, scale, avg, out, code=0, g=None, skip=0):
         levels, dev, images, dim = len(xs), xs[0].device, targets.size(0), anchors.size(1)
         means, stds, max_ratio, flags, ctr_clamp = coder_cfg
         ptrs, i64s, f32s = ctypes.c_void_p * levels, ctypes.c_int64 * levels, ctypes.c_float * dim
-        H.call_sum('bbox_loss', 'bbox loss', code, dev, ns, hws, images, dim,
+        H.call_sum(entry, entry.replace('_', ' '), code, dev, ns, hws, images, dim,
                    (ptrs(*[G.ptr(x) for x in xs]), ptrs(*[G.ptr(v) for v in views]) if views is not None else None, i64s(*ns), i64s(*hws), levels,
-                    images, dim, G.ptr(anchors), G.ptr(targets), G.ptr(weight), wd, f32s(*means), f32s(*stds), max_ratio, flags, ctr_clamp, mode,
-                    eps, scale, G.ptr(avg)), out, g, skip)
+                    images, dim, G.ptr(anchors), G.ptr(targets), G.ptr(weight), wd, f32s(*means), f32s(*stds), max_ratio, flags, ctr_clamp, *tail,
+                    scale, G.ptr(avg)), out, g, skip)
 
     @staticmethod
     def backward(ctx, grad_out):
         stash, anchors, targets, weight, avg, *xs = ctx.saved_tensors
-        wd, coder_cfg, mode, eps, scale, hws, ns, dtypes, code = ctx.meta
+        wd, coder_cfg, entry, tail, scale, hws, ns, dtypes, code = ctx.meta
         if code:
             return H.native_backward(ctx, _BBoxLossFunction._FIXED, grad_out, xs, lambda views, g, skip: _BBoxLossFunction._launch(
-                xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, mode, eps, scale, avg, None, code, g, skip))
+                xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg, entry, tail, scale, avg, None, code, g, skip))
         relaunch = H.relaunch_fresh(xs, lambda views: _BBoxLossFunction._launch(xs, views, ns, hws, anchors, targets, weight, wd, coder_cfg,
-                                                                              mode, eps, scale, avg, H.scalar(stash.device)))
+                                                                              entry, tail, scale, avg, H.scalar(stash.device)))
         return H.stash_backward(ctx, _BBoxLossFunction._FIXED, grad_out, stash, dtypes, relaunch)
 
 
@@ -74,6 +75,31 @@ def _coder_cfg(bbox_coder, dim):
     flags = (1 if bbox_coder.clip_border else 0) | (2 if bbox_coder.add_ctr_clamp else 0)
     max_ratio = abs(math.log(getattr(bbox_coder, 'wh_ratio_clip', 16 / 1000)))
     return means, stds, float(max_ratio), flags, float(bbox_coder.ctr_clamp)
+
+
+def decoded_loss_apply(fn, entry, tail, bbox_preds, anchors, bbox_targets, bbox_weights, bbox_coder, reduction, avg_factor, loss_weight):
+    """The shape checks, the scale rule and the autograd node shared by `sph_bbox_loss` and `sph_gauss_bbox_loss`; `fn` is the
+    public function's name, (entry, tail) as for `_BBoxLossFunction`."""
+    bbox_preds = list(bbox_preds)
+    H.check_levels(fn, bbox_preds)
+    if isinstance(anchors, (list, tuple)):
+        anchors = torch.cat(list(anchors), 0)
+    if anchors.dim() != 2 or anchors.size(1) not in (4, 5):
+        raise ValueError(f'anchors must be (n, 4) or (n, 5), got {tuple(anchors.shape)}')
+    n, dim = anchors.shape
+    if bbox_targets.dim() != 3 or tuple(bbox_targets.shape[1:]) != (n, dim):
+        raise ValueError(f'bbox_targets must be (B, n, dim) = (B, {n}, {dim}), got {tuple(bbox_targets.shape)}')
+    images = bbox_targets.size(0)
+    H.check_one_device(fn, bbox_preds + [anchors, bbox_targets] + ([bbox_weights] if bbox_weights is not None else []))
+    wd = H.weight_dim(bbox_weights, images, n, dim, bbox_targets.shape)
+    hws, total = H.box_levels('bbox_preds', bbox_preds, images, dim)
+    if total != n:
+        raise ValueError(f'the levels hold {total} anchors per image, anchors {n}')
+    scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n, anchors.device)
+    w = G.as_f32_nograd(bbox_weights) if bbox_weights is not None else None
+    out = _BBoxLossFunction.apply(G.as_f32_nograd(anchors), G.as_f32_nograd(bbox_targets), w, wd, _coder_cfg(bbox_coder, dim), entry, tail,
+                                  scale, avg, hws, *H.forward_only(bbox_preds))
+    return out * float('nan') if nan else out
 
 
 def sph_bbox_loss(bbox_preds, anchors, bbox_targets, bbox_weights=None, *, bbox_coder, mode='ciou', eps=1e-6, avg_factor=None,
@@ -92,23 +118,5 @@ def sph_bbox_loss(bbox_preds, anchors, bbox_targets, bbox_weights=None, *, bbox_
     H.check_reduction('sph_bbox_loss', reduction, "for the loss of every box use Sph2PobIoULoss(reduction='none') on bbox_coder.decode(...)")
     if mode not in LOSS_MODES:
         raise ValueError(f'mode must be one of {sorted(LOSS_MODES)}, got {mode!r}')
-    bbox_preds = list(bbox_preds)
-    H.check_levels('sph_bbox_loss', bbox_preds)
-    if isinstance(anchors, (list, tuple)):
-        anchors = torch.cat(list(anchors), 0)
-    if anchors.dim() != 2 or anchors.size(1) not in (4, 5):
-        raise ValueError(f'anchors must be (n, 4) or (n, 5), got {tuple(anchors.shape)}')
-    n, dim = anchors.shape
-    if bbox_targets.dim() != 3 or tuple(bbox_targets.shape[1:]) != (n, dim):
-        raise ValueError(f'bbox_targets must be (B, n, dim) = (B, {n}, {dim}), got {tuple(bbox_targets.shape)}')
-    images = bbox_targets.size(0)
-    H.check_one_device('sph_bbox_loss', bbox_preds + [anchors, bbox_targets] + ([bbox_weights] if bbox_weights is not None else []))
-    wd = H.weight_dim(bbox_weights, images, n, dim, bbox_targets.shape)
-    hws, total = H.box_levels('bbox_preds', bbox_preds, images, dim)
-    if total != n:
-        raise ValueError(f'the levels hold {total} anchors per image, anchors {n}')
-    scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n, anchors.device)
-    w = G.as_f32_nograd(bbox_weights) if bbox_weights is not None else None
-    out = _BBoxLossFunction.apply(G.as_f32_nograd(anchors), G.as_f32_nograd(bbox_targets), w, wd, _coder_cfg(bbox_coder, dim), _mode_code(mode),
-                                  float(eps), scale, avg, hws, *H.forward_only(bbox_preds))
-    return out * float('nan') if nan else out
+    return decoded_loss_apply('sph_bbox_loss', 'bbox_loss', (_mode_code(mode), float(eps)), bbox_preds, anchors, bbox_targets, bbox_weights,
+                              bbox_coder, reduction, avg_factor, loss_weight)

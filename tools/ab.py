@@ -20,7 +20,9 @@ Workloads (all through the C ABI, buffers allocated once, HIP events around `--l
   nms       sph2pob_nms_segmented_f32 on 5 000 sorted boxes x 37 classes and on one class of 5 000
   bnms      sph2pob_batched_nms_f32 (unsorted input, no host work) on the same two scenes
   head_losses  sph2pob_{focal,bbox,delta}_loss_sum_f32, each timed on its own, with gradients: 8 images x the 5 NCHW levels of the
-            512 x 1024 ERP (98 208 anchors), 37 classes, dim 4, CIoU closed-form / L1, ~1 % live rows, a device avg_factor; then the
+            512 x 1024 ERP (98 208 anchors), 37 classes, dim 4, CIoU closed-form / L1, ~1 % live rows, a device avg_factor; then
+            sph2pob_gauss_bbox_loss_sum_f32 (kld) on the same, or on an arm without it the composition through that library's
+            decode, Gaussian loss and decode-adjoint entries; then the
             same on bf16 levels, forward + first backward with g = 1 and g = 0.5: sph2pob_*_sum_h16 where the arm's library has
             them, the cast route (.float(), the _f32 entry, the stash scaling, .to(bfloat16)) where it has not (the parent build)
   test_bboxes_h16  sph2pob_test_bboxes on bf16 levels at that shape (PANDORA's test_cfg): the _h16 entry, or .float() + the _f32 entry
@@ -261,6 +263,50 @@ def workloads(args, torch, G):
             max_ratio, 1, 32.0, 3, 1e-6, 1.0, G.ptr(avg), out, ws, st))
         yield entry('delta_loss', box, 4, lambda lib, xp, gp, out, ws: lib.sph2pob_delta_loss_sum_f32(
             xp, gp, ns, hws, levels, images, 4, G.ptr(deltas_t), G.ptr(weights), 4, 0.0, 1.0, G.ptr(avg), out, ws, st))
+
+        # The Gaussian regression loss (kld, log1p, tau 1).  An arm whose library has sph2pob_gauss_bbox_loss_sum_f32 takes it; an arm
+        # without it (the parent build) takes the composition a head ran there, through that library's own entries: permute /
+        # reshape / cat of the levels, sph2pob_coder_decode_f32 over all B n rows, sph2pob_gauss_loss_fwd_grad_f32 over all B n
+        # rows, the division by the device avg_factor, sph2pob_coder_decode_bwd_f32, split + permute back.  Its figure therefore
+        # includes the torch copies a head makes around the entries (five permute copies in, two scalings, five permute copies
+        # out: thirteen torch launches beside the three entries); the B n x 4 buffers are allocated once, outside the timing.  Outputs: the
+        # loss and the NCHW gradients (the two routes scale in a different order: equal values, not equal bits).
+        gauss = (1, 1, 1.0, 1.0, 1, 0.0, 0.0)   # SPH2POB_GAUSS_KLD, log1p, tau, alpha, sqrt, beta, eps
+        rois = anchors.repeat(images, 1).contiguous()
+        total = images * n
+        eps32 = float(torch.finfo(torch.float32).eps)
+
+        def gauss_entry():
+            def make(lib):
+                fused = getattr(lib, 'sph2pob_gauss_bbox_loss_sum_f32', None)
+                grads = [torch.empty_like(x) for x in box]
+                out = torch.empty(1, device='cuda')
+                if fused is not None:
+                    ws = torch.empty(lib.sph2pob_gauss_bbox_loss_workspace_bytes(ns, hws, levels, images, 4), dtype=torch.uint8, device='cuda')
+                    xp, gp = ptrs(*[G.ptr(x) for x in box]), ptrs(*[G.ptr(v) for v in grads])
+                    return (lambda: fused(xp, gp, ns, hws, levels, images, 4, G.ptr(anchors), G.ptr(boxes), G.ptr(weights), 4, means, stds,
+                                          max_ratio, 1, 32.0, *gauss, 1.0, G.ptr(avg), G.ptr(out), G.ptr(ws), st)), [out] + grads
+                ws = torch.empty(lib.sph2pob_loss_sum_workspace_floats(total), device='cuda')
+                flat, dec, gbox, gflat = (torch.empty((total, 4), device='cuda') for _ in range(4))   # allocated once, outside the timing
+                sizes = [9 * h * w for h, w in D.LEVEL_SHAPES]
+
+                def launch():
+                    for fl, x in zip(flat.view(images, n, 4).split(sizes, 1), box):   # the permute + cat copies of the head
+                        fl.copy_(x.permute(0, 2, 3, 1).reshape(images, -1, 4))
+                    rc = lib.sph2pob_coder_decode_f32(G.ptr(rois), G.ptr(flat), means, stds, G.ptr(dec), total, 1, 4, max_ratio, 1, 32.0, st)
+                    rc |= lib.sph2pob_gauss_loss_fwd_grad_f32(G.ptr(dec), G.ptr(boxes), G.ptr(weights), 4, 1.0, None, G.ptr(out), G.ptr(ws),
+                                                              G.ptr(gbox), None, total, 4, *gauss, st)
+                    k = 1.0 / (avg + eps32)
+                    out.mul_(k)
+                    gbox.mul_(k)
+                    rc |= lib.sph2pob_coder_decode_bwd_f32(G.ptr(rois), G.ptr(flat), G.ptr(gbox), means, stds, G.ptr(gflat), total, 1, 4, max_ratio,
+                                                           1, 32.0, st)
+                    for gl, v, (h, w) in zip(gflat.view(images, n, 4).split(sizes, 1), grads, D.LEVEL_SHAPES):
+                        v.copy_(gl.reshape(images, h, w, 9 * 4).permute(0, 3, 1, 2))
+                    return rc
+                return launch, [out] + grads
+            return f'head_losses gauss_bbox_loss_sum kld fwd+grad {images} x {n}', make
+        yield gauss_entry()
 
         # bf16 levels, forward + first backward with an upstream gradient g.  An arm whose library has the _h16 entries takes the
         # native route (the entry with a bf16 stash, then the gradient-only call with grad_out = g, skip_if_one = 1); an arm

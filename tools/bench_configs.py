@@ -556,12 +556,9 @@ def focal(images=8, classes=37, rounds=7):
                     'device copy of the five logit tensors (reads and writes 4 B per element each, the bytes the fused kernel moves)'}
 
 
-def bbox_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7):
-    """The regression loss of a minibatch at the reference's test shape — 512 x 1024 ERP, 5 NCHW levels, 9 anchors, 98 208 anchors
-    per image, the ground-truth counts of demo_hot_path.run_batch, CIoU, a device avg_factor — forward + backward to the head's
-    NCHW deltas: (a) sph_bbox_loss eager, (b) replayed from a graph, (c) the composition it replaces (permute / reshape / cat ->
-    coder.decode -> Sph2PobIoULoss -> / avg_factor) eager and (d) replayed from a graph.  Timed in alternation `rounds` times,
-    medians and spreads reported."""
+def _decoded_loss(name, what, fused_loss, module, images_counts, classes, rounds):
+    """The scene and the four timings shared by bbox_loss and gauss_bbox_loss: `fused_loss(preds, anchors, t, coder)` is the fused
+    call, `module` the loss module of the composition."""
     import demo_hot_path as D
     images = len(images_counts)
     g = torch.Generator().manual_seed(0)
@@ -574,7 +571,6 @@ def bbox_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7
     assigner = S.SphMaxIoUAssigner(pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1,
                                    iou_calculator=dict(type='SphOverlaps2D', backend='sph2pob_standard_iou', box_version=4))
     coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(1., 1., 1., 1.))
-    loss_mod = Sph2PobIoULoss(mode='ciou', loss_weight=1.0)
     t = S.sph_anchor_targets(anchors, gts, labels, assigner=assigner, num_classes=classes)
     n = anchors.size(0)
     rois = anchors.repeat(images, 1)
@@ -583,12 +579,12 @@ def bbox_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7
     preds = [(torch.randn((images, 9 * 4, h, w), generator=gd, device='cuda') * 0.05).requires_grad_(True) for h, w in D.LEVEL_SHAPES]
 
     def fused():
-        loss = S.sph_bbox_loss(preds, anchors, t.bbox_targets, t.bbox_weights, bbox_coder=coder, mode='ciou', avg_factor=t.avg_factor)
+        loss = fused_loss(preds, anchors, t, coder)
         return (loss.detach(),) + torch.autograd.grad(loss, preds)
 
     def composition():
         flat = torch.cat([p.permute(0, 2, 3, 1).reshape(images, -1, 4) for p in preds], 1).reshape(-1, 4)
-        loss = loss_mod(coder.decode(rois, flat), targets2, weights2, avg_factor=t.avg_factor)
+        loss = module(coder.decode(rois, flat), targets2, weights2, avg_factor=t.avg_factor)
         return (loss.detach().reshape(()),) + torch.autograd.grad(loss, preds)
     # The captures come first, each after a warm-up on a side stream, and nothing returned keeps an autograd graph alive: a
     # gradient edge of `preds` created by an eager call on the default stream and still alive at capture time makes autograd
@@ -616,13 +612,34 @@ def bbox_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7
         tc.append(timeit(composition, reps=30) * 1e6)
         td.append(timeit(graphs[1].replay, reps=30) * 1e6)
     med = lambda v: float(np.median(v))
-    return {'config': 'bbox_loss: %d images x %d anchors (512x1024 ERP, 5 NCHW levels), CIoU, device avg_factor, fwd + bwd' % (images, n),
+    return {'config': '%s: %d images x %d anchors (512x1024 ERP, 5 NCHW levels), %s, device avg_factor, fwd + bwd' % (name, images, n, what),
             'num_gt': list(images_counts), 'num_pos': t.num_pos.tolist(),
             'a_fused_eager_us': med(ta), 'b_fused_graph_us': med(tb), 'c_composition_eager_us': med(tc), 'd_composition_graph_us': med(td),
             'a_rounds_us': ta, 'b_rounds_us': tb, 'c_rounds_us': tc, 'd_rounds_us': td,
             'a_spread_us': max(ta) - min(ta), 'b_spread_us': max(tb) - min(tb), 'c_spread_us': max(tc) - min(tc), 'd_spread_us': max(td) - min(td),
             'a_over_c': med(ta) / med(tc), 'b_over_d': med(tb) / med(td),
             'loss_fused': float(a[0]), 'loss_composition': float(c[0]), 'loss_rel_diff': loss_rel, 'grad_max_abs_diff': grad_diff}
+
+
+def bbox_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7):
+    """The regression loss of a minibatch at the reference's test shape — 512 x 1024 ERP, 5 NCHW levels, 9 anchors, 98 208 anchors
+    per image, the ground-truth counts of demo_hot_path.run_batch, CIoU, a device avg_factor — forward + backward to the head's
+    NCHW deltas: (a) sph_bbox_loss eager, (b) replayed from a graph, (c) the composition it replaces (permute / reshape / cat ->
+    coder.decode -> Sph2PobIoULoss -> / avg_factor) eager and (d) replayed from a graph.  Timed in alternation `rounds` times,
+    medians and spreads reported."""
+    return _decoded_loss('bbox_loss', 'CIoU', lambda preds, anchors, t, coder: S.sph_bbox_loss(
+        preds, anchors, t.bbox_targets, t.bbox_weights, bbox_coder=coder, mode='ciou', avg_factor=t.avg_factor),
+        Sph2PobIoULoss(mode='ciou', loss_weight=1.0), images_counts, classes, rounds)
+
+
+def gauss_bbox_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7):
+    """bbox_loss with loss_bbox = Sph2PobGDLoss(kld): (a) sph_gauss_bbox_loss eager, (b) replayed from a graph, (c) the composition
+    it replaces (permute / reshape / cat -> coder.decode -> Sph2PobGDLoss -> / avg_factor) eager and (d) replayed from a graph."""
+    from sph_retina_amd.losses.sph2pob_gaussian_loss import Sph2PobGDLoss
+    module = Sph2PobGDLoss(loss_type='kld', loss_weight=1.0)
+    return _decoded_loss('gauss_bbox_loss', 'Sph2PobGDLoss kld', lambda preds, anchors, t, coder: S.sph_gauss_bbox_loss(
+        preds, anchors, t.bbox_targets, t.bbox_weights, bbox_coder=coder, loss=module, avg_factor=t.avg_factor),
+        module, images_counts, classes, rounds)
 
 
 def delta_loss(images_counts=(64, 1, 0, 17, 64, 3, 128, 33), classes=37, rounds=7):
@@ -825,8 +842,8 @@ def gaussian(n=1_000_000):
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch train_targets get_bboxes focal bbox_loss delta_loss coder unbiased variants; none = all)
-    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, train_targets=train_targets, get_bboxes=get_bboxes, focal=focal, bbox_loss=bbox_loss, delta_loss=delta_loss, coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch train_targets get_bboxes focal bbox_loss gauss_bbox_loss delta_loss coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, train_targets=train_targets, get_bboxes=get_bboxes, focal=focal, bbox_loss=bbox_loss, gauss_bbox_loss=gauss_bbox_loss, delta_loss=delta_loss, coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)

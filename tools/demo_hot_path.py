@@ -104,7 +104,7 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
-              train_cfg=None):
+              train_cfg=None, loss_bbox=None):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -114,8 +114,12 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     (`loss_bbox=dict(type='L1Loss')`, `reg_decoded_bbox=False`): encoded targets from `sph_anchor_targets`, `sph_delta_loss` on the
     raw deltas, nothing decoded; its NCHW route is timed by `tools/bench_configs.py delta_loss`.  With a `train_cfg` (the
     reference's dict: its assigner with any SphOverlaps2D backend, pos_weight) the targets come from `sph_train_targets` under
-    that configuration, still one call and no synchronisation."""
+    that configuration, still one call and no synchronisation.  `loss_bbox`: a Gaussian loss cfg such as
+    dict(type='Sph2PobGDLoss', loss_type='kld', fun='log1p', tau=1.0) or dict(type='Sph2PobKFLoss') in place of CIoU; the regression
+    half then goes through `sph_gauss_bbox_loss` (its NCHW route is timed by `tools/bench_configs.py gauss_bbox_loss`)."""
     dev = 'cuda'
+    if loss_bbox is not None and base_config:
+        raise ValueError('base_config runs L1 on encoded deltas: no loss_bbox')
     g = torch.Generator().manual_seed(seed)
     anchors = retina_anchors()
     n, images = anchors.size(0), len(counts)
@@ -131,7 +135,7 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     assigner = S.SphMaxIoUAssigner(pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1,
                                    iou_calculator=dict(type='SphOverlaps2D', backend=backend, box_version=4))
     coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(1., 1., 1., 1.))
-    loss_bbox = S.Sph2PobIoULoss(mode='ciou', loss_weight=1.0)
+    loss_iou = S.Sph2PobIoULoss(mode='ciou', loss_weight=1.0)
     deltas = (torch.randn((images * n, 4), generator=g) * 0.05).to(dev).requires_grad_(True)
     rois = anchors.repeat(images, 1)
     gd = torch.Generator(device=dev).manual_seed(seed)
@@ -149,12 +153,15 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
                                      bbox_coder=coder if base_config else None)
         if base_config:
             loss = S.sph_delta_loss([deltas.view(images, n, 4)], t.bbox_targets, t.bbox_weights, avg_factor=t.avg_factor)
+        elif loss_bbox is not None:
+            loss = S.sph_gauss_bbox_loss([deltas.view(images, n, 4)], anchors, t.bbox_targets, t.bbox_weights, bbox_coder=coder, loss=loss_bbox,
+                                         avg_factor=t.avg_factor)
         elif fused_reg:
             loss = S.sph_bbox_loss([deltas.view(images, n, 4)], anchors, t.bbox_targets, t.bbox_weights, bbox_coder=coder, mode='ciou',
                                    avg_factor=t.avg_factor)
         else:
             pred = coder.decode(rois, deltas)
-            loss = loss_bbox(pred, t.bbox_targets.reshape(-1, 4), t.bbox_weights.reshape(-1, 4), avg_factor=t.avg_factor)
+            loss = loss_iou(pred, t.bbox_targets.reshape(-1, 4), t.bbox_weights.reshape(-1, 4), avg_factor=t.avg_factor)
         # (the targets follow retina_anchors()' order, the logits the head's ((h W + w) A + a): a timing and plumbing demo)
         loss_cls = S.sph_focal_loss(cls_scores, t.labels, t.label_weights, gamma=2.0, alpha=0.25, avg_factor=t.avg_factor)
         (loss + loss_cls).backward()
@@ -168,7 +175,7 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     out = {'anchors': n, 'images': images, 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
            'loss': float(loss), 'loss_cls': float(loss_cls), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()),
            'cls_grad_finite': all(bool(torch.isfinite(c.grad).all()) for c in cls_scores), 'backend': backend, 'fused_reg': fused_reg,
-           'base_config': base_config,
+           'base_config': base_config, 'loss_bbox': loss_bbox['type'] if loss_bbox is not None else 'Sph2PobIoULoss',
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels)
 
