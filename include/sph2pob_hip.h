@@ -565,6 +565,55 @@ int sph2pob_focal_loss_bwd_f32(const float* logits, const int64_t* labels, const
                                int64_t n, int64_t num_classes, void* stream);
 int sph2pob_focal_loss_grad_scale_f32(const float* stash, const float* grad_out, float* out, int64_t total, void* stream);
 
+/* ---- softmax cross-entropy, plain and with hard-negative mining: the classification half of SphSSDHead.loss_single -----------
+ * Replaces, for softmax heads (use_sigmoid=False), the chain cls_score.permute(0, 2, 3, 1).reshape(B, -1, K) -> cat over the
+ * levels -> F.cross_entropy(reduction='none') * label_weights -> per image nonzero() twice and topk(min(r P_b, N_b))
+ * (sphdet/models/heads/sph_ssd_head.py:96-161), and mmdet's cross_entropy + weight_reduce_loss in plain mode.
+ * K = score channels per anchor (C + 1, background last); channel a K + c of an NCHW level is class c of anchor a.  Per row i of
+ * image b, with label t:
+ *     valid  = 0 <= t < K and t != ignore_index; an invalid row has loss 0, gradient 0 and is neither positive nor negative
+ *              (F.cross_entropy raises on an out-of-range label instead)
+ *     l_i    = CE(x_i, t) * class_weight[t] * weight[b, i]
+ *     plain  (neg_pos_ratio == -1): out = scale_eff * sum of l_i over the valid rows
+ *     mining (neg_pos_ratio = r >= 0): positives = valid rows with t != background_label, negatives = rows with
+ *              t == background_label, k_b = min(r P_b, N_b) from the labels on the device; the mined negatives of an image are the
+ *              first k_b in the order (l_i descending, row index ascending), a NaN above +inf as torch.topk has it;
+ *              out = scale_eff * sum_b (sum of l_i over positives + mined): ONE scalar, the sum of the reference's B values
+ *     grad   = scale_eff * weight * class_weight[t] * (softmax(x_i)_j - [j == t]) on positive / mined (plain: valid) rows, an exact
+ *              0.0 on every other element; every element of every level is written exactly once
+ * Arithmetic (csrc/sph2pob_softmax.hpp): m = max_j x_j, e_j = expf(x_j - m), class sums in double without the maximum's own
+ * term; CE = log1p(sum_{j != t} e_j) when the target is the maximum, else (m - x_t) + log1p(S - 1); the target's gradient
+ * component is -(sum_{j != t} e_j) / S, never p_t - 1.  The tie rule (lowest row index first) is where the mined SET may differ
+ * from torch.topk, whose choice among equal values is unspecified; the loss value does not depend on it.  The reference divides by
+ * num_total_samples without the FLT_EPSILON of scale_eff.
+ *
+ * sph2pob_softmax_loss_sum_f32 — level tables, labels, weight (per row, or NULL), scale, avg_factor, out as for
+ * sph2pob_focal_loss_sum_f32; class_weight NULL or (K,) device floats; workspace of
+ * sph2pob_softmax_loss_workspace_bytes(level_n, level_hw, num_levels, B, K, mining) bytes (0: shapes not accepted), no
+ * initialisation.  Launches: plain 2; mining 4 (rows -> keys, one workgroup per image for the cut, rows -> gradient, final), 3
+ * without grads.  No float atomics, nothing read back: the same bits on every call.
+ * Errors, in this order before anything is enqueued: neg_pos_ratio < -1 (or > 2^30) -> SPH2POB_ERR_OPTION; num_levels outside
+ * [1, 8], B outside [0, 65 535], K outside [2, 4096] -> SPH2POB_ERR_SIZE; a NULL level_n / logits table -> SPH2POB_ERR_NULL;
+ * n_l < 0, level_hw that does not divide n_l, B n_l K >= 2^31 - 4096 -> SPH2POB_ERR_SIZE; a NULL table entry of a level with
+ * elements, out, workspace, or labels with rows -> SPH2POB_ERR_NULL.  B n == 0 writes out[0] = 0.
+ *
+ * sph2pob_softmax_loss_fwd_f32: loss[i] = scale * l_i on a flat (n, K) input (reduction 'none').
+ * sph2pob_softmax_loss_bwd_f32: grad_logits[i, j] = grad_out[i * grad_stride] * scale_eff * weight * class_weight[t] * dCE/dx_j
+ * (grad_stride 0: one device scalar, 1: per row).  grad_stride -> SPH2POB_ERR_OPTION; n < 0, K outside [2, 4096], n K > 2^38 ->
+ * SPH2POB_ERR_SIZE; n == 0 is a no-op; a NULL pointer with work to do -> SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_softmax_loss_workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                             int64_t num_channels, int mining);
+int sph2pob_softmax_loss_sum_f32(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                 int num_levels, int64_t num_images, int64_t num_channels, const int64_t* labels, const float* weight,
+                                 const float* class_weight, int64_t ignore_index, int64_t background_label, int64_t neg_pos_ratio,
+                                 float scale, const float* avg_factor, float* out, void* workspace, void* stream);
+int sph2pob_softmax_loss_fwd_f32(const float* logits, const int64_t* labels, const float* weight, const float* class_weight,
+                                 int64_t ignore_index, float scale, float* loss, int64_t n, int64_t num_channels, void* stream);
+int sph2pob_softmax_loss_bwd_f32(const float* logits, const int64_t* labels, const float* weight, const float* class_weight,
+                                 int64_t ignore_index, const float* grad_out, int grad_stride, float scale, const float* avg_factor,
+                                 float* grad_logits, int64_t n, int64_t num_channels, void* stream);
+
 /* ---- fused box-regression loss: the regression half of SphRetinaHead.loss_single ------------------------------------------
  * Replaces, for reg_decoded_bbox=True (sphdet/models/heads/sph_retina_head.py:252-265), the chain
  * bbox_pred.permute(0, 2, 3, 1).reshape(-1, dim) -> cat over the levels -> DeltaXYWH(A)SphBBoxCoder.decode -> Sph2PobIoULoss ->

@@ -18,7 +18,7 @@ LIB_DIR = os.path.join(_HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_hip.so')
 HOST_LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_host.so')
 SOURCES = ['sph2pob_iou.hip', 'sph2pob_assign.hip', 'sph2pob_loss.hip', 'sph2pob_nms.hip', 'sph2pob_coder.hip', 'sph2pob_get_bboxes.hip',
-           'sph2pob_focal.hip', 'sph2pob_bbox_loss.hip', 'sph2pob_delta_loss.hip', 'sph2pob_gauss_bbox_loss.hip']
+           'sph2pob_focal.hip', 'sph2pob_bbox_loss.hip', 'sph2pob_delta_loss.hip', 'sph2pob_gauss_bbox_loss.hip', 'sph2pob_softmax.hip']
 HOST_SOURCES = ['sph2pob_host.hip']
 HOST_FLAGS = ['--offload-arch=gfx950', '--cuda-host-only', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-pthread']
 
@@ -45,8 +45,9 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_gauss_loss_fwd_f32', 'sph2pob_gauss_loss_bwd_f32', 'sph2pob_gauss_loss_fwd_sum_f32',
               'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32', 'sph2pob_anchor_targets_any_f32', 'sph2pob_get_bboxes_f32', 'sph2pob_test_bboxes_f32', 'sph2pob_focal_loss_sum_f32',
               'sph2pob_focal_loss_fwd_f32', 'sph2pob_focal_loss_bwd_f32', 'sph2pob_focal_loss_grad_scale_f32', 'sph2pob_bbox_loss_sum_f32',
-              'sph2pob_delta_loss_sum_f32', 'sph2pob_gauss_bbox_loss_sum_f32']
-HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp', 'sph2pob_gauss_bbox_loss.hpp',
+              'sph2pob_delta_loss_sum_f32', 'sph2pob_gauss_bbox_loss_sum_f32', 'sph2pob_softmax_loss_sum_f32',
+              'sph2pob_softmax_loss_fwd_f32', 'sph2pob_softmax_loss_bwd_f32']
+HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp', 'sph2pob_gauss_bbox_loss.hpp', 'sph2pob_softmax.hpp',
            'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
 # half the rate of plain VALU on gfx950 (tools/ubench/valu_rate2.hip), measured 12 % slower on the dominant kernel
@@ -161,6 +162,14 @@ SIGNATURES = {
     # workspace, stream
     'sph2pob_delta_loss_sum_f32': [ctypes.c_void_p] * 4 + [_int, _i64, _int, _c_f32p, _c_f32p, _int, ctypes.c_float, ctypes.c_float,
                                    _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p],
+    'sph2pob_softmax_loss_workspace_bytes': [ctypes.c_void_p, ctypes.c_void_p, _int, _i64, _i64, _int],
+    # level tables (logits, grads, n, hw), num_levels, B, K, labels, weight, class_weight, ignore_index, background_label,
+    # neg_pos_ratio (-1: plain), scale, avg_factor, out, workspace, stream
+    'sph2pob_softmax_loss_sum_f32': [ctypes.c_void_p] * 4 + [_int, _i64, _i64, ctypes.c_void_p, _c_f32p, _c_f32p, _i64, _i64, _i64,
+                                    ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p],
+    'sph2pob_softmax_loss_fwd_f32': [_c_f32p, ctypes.c_void_p, _c_f32p, _c_f32p, _i64, ctypes.c_float, _c_f32p, _i64, _i64, ctypes.c_void_p],
+    'sph2pob_softmax_loss_bwd_f32': [_c_f32p, ctypes.c_void_p, _c_f32p, _c_f32p, _i64, _c_f32p, _int, ctypes.c_float, _c_f32p, _c_f32p,
+                                    _i64, _i64, ctypes.c_void_p],
     'sph2pob_coder_encode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int,
                                  ctypes.c_void_p],
     'sph2pob_coder_decode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int, _int,
@@ -184,7 +193,8 @@ _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_targe
              'sph2pob_anchor_targets_workspace_bytes': ctypes.c_int64, 'sph2pob_anchor_targets_state_bytes': ctypes.c_int64,
              'sph2pob_batched_nms_workspace_bytes': ctypes.c_int64, 'sph2pob_get_bboxes_workspace_bytes': ctypes.c_int64,
              'sph2pob_focal_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_bbox_loss_workspace_bytes': ctypes.c_int64,
-             'sph2pob_delta_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_gauss_bbox_loss_workspace_bytes': ctypes.c_int64}
+             'sph2pob_delta_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_gauss_bbox_loss_workspace_bytes': ctypes.c_int64,
+             'sph2pob_softmax_loss_workspace_bytes': ctypes.c_int64}
 
 ABI_VERSION = 6
 

@@ -31,6 +31,7 @@
 #include "sph2pob_bbox_loss.hpp"
 #include "sph2pob_gauss_bbox_loss.hpp"
 #include "sph2pob_delta_loss.hpp"
+#include "sph2pob_softmax.hpp"
 
 namespace {
 
@@ -963,6 +964,151 @@ int sph2pob_delta_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* g
     if (L.rows > 0)
         total = box_dim == 4 ? delta_loss_rows<4>(L, targets, weight, wd, beta, k0) : delta_loss_rows<5>(L, targets, weight, wd, beta, k0);
     out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- softmax cross-entropy, plain and mined: the twins of sph2pob_softmax.hip on the Row, the keys and the cut of sph2pob_softmax.hpp ----
+namespace {
+namespace SM = sph2pob_softmax;
+
+// element (row, c) of a level = base + c * stride
+inline void softmax_row_span(const SM::Level& lv, int64_t K, int64_t b, int64_t i, int64_t* base, int64_t* stride) {
+    if (lv.hw > 0) {
+        const int64_t p = i / lv.a, a = i - p * lv.a;
+        *base = (b * lv.a + a) * K * lv.hw + p; *stride = lv.hw;
+    } else {
+        *base = (b * lv.n + i) * K; *stride = 1;
+    }
+}
+// the three walks of one valid row: its cross-entropy, and (g != NULL) g[c * stride] = kw * d CE / d x_c
+inline float softmax_row(const float* x, float* g, int64_t stride, int K, int64_t lab, float kw) {
+    SM::Row r;
+    r.begin((int)lab);
+    for (int c = 0; c < K; c++) r.see_max(c, x[c * stride]);
+    r.close_max();
+    for (int c = 0; c < K; c++) r.see_sum(c, x[c * stride]);
+    const float ce = r.close_sum();
+    if (g)
+        for (int c = 0; c < K; c++) g[c * stride] = kw * r.grad(c, x[c * stride]);
+    return ce;
+}
+inline void softmax_zero_row(float* g, int64_t stride, int K) {
+    for (int c = 0; c < K; c++) g[c * stride] = 0.0f;
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_softmax_loss_sum_f32_cpu(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                     int num_levels, int64_t num_images, int64_t num_channels, const int64_t* labels, const float* weight,
+                                     const float* class_weight, int64_t ignore_index, int64_t background_label, int64_t neg_pos_ratio,
+                                     float scale, const float* avg_factor, float* out, void* workspace, void*) {
+    SM::Levels L;
+    if (int rc = SM::make_levels(logits, grads, level_n, level_hw, num_levels, num_images, num_channels, neg_pos_ratio, true, &L)) return rc;
+    if (!out || !workspace || (L.rows > 0 && !labels)) return SPH2POB_ERR_NULL;
+    const float k0 = SM::effective_scale(scale, avg_factor);
+    const int K = (int)num_channels;
+    const bool mining = neg_pos_ratio >= 0;
+    const int64_t n = L.n_total;
+    std::vector<unsigned> keys(mining ? (size_t)L.rows : 0);
+    // first pass: plain — losses and gradients; mining — keys and the positives' losses
+    double total = head_rows_sum(L, L.rows, [&](const SM::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
+        int64_t base, stride;
+        softmax_row_span(lv, K, b, i, &base, &stride);
+        const int64_t lab = labels[row];
+        float* g = !mining && lv.grad ? lv.grad + base : nullptr;
+        if (!SM::valid_label(lab, K, ignore_index)) {
+            if (mining) keys[(size_t)row] = SM::kKeyNone;
+            if (g) softmax_zero_row(g, stride, K);
+            return;
+        }
+        const float cwl = SM::class_factor(class_weight, lab), w = SM::row_weight(weight, row);
+        const float l = SM::row_loss(softmax_row(lv.logits + base, g, stride, K, lab, k0 * (cwl * w)), cwl, w);
+        if (!mining) acc += (double)l;
+        else if (lab != background_label) { keys[(size_t)row] = SM::kKeyPos; acc += (double)l; }
+        else keys[(size_t)row] = SM::loss_key(l);
+    });
+    if (mining) {
+        // the cut of every image: the k_b-th largest negative key, the rows tied at it taken in index order
+        std::vector<SM::Cut> cuts((size_t)num_images);
+        for (int64_t b = 0; b < (L.rows > 0 ? num_images : 0); b++) {
+            const unsigned* kb = keys.data() + b * n;
+            std::vector<unsigned> neg;
+            int64_t pos = 0;
+            for (int64_t j = 0; j < n; j++) {
+                if (kb[j] == SM::kKeyPos) pos++;
+                else if (kb[j] >= 2u) neg.push_back(kb[j]);
+            }
+            const int64_t k = SM::mined_count(neg_pos_ratio, pos, (int64_t)neg.size());
+            SM::Cut c{SM::kKeyNaN, 0};
+            double sum = 0.0;
+            if (k > 0) {
+                std::nth_element(neg.begin(), neg.begin() + (k - 1), neg.end(), [](unsigned x, unsigned y) { return x > y; });
+                c.key = neg[(size_t)(k - 1)];
+                int64_t above = 0;
+                for (int64_t j = 0; j < n; j++)
+                    if (kb[j] >= 2u && kb[j] > c.key) { above++; sum += (double)SM::key_loss(kb[j]); }
+                const int64_t take = k - above;
+                int64_t seen = 0;
+                for (int64_t j = 0; j < n && seen < take; j++)
+                    if (kb[j] == c.key && ++seen == take) c.upto = (int)(j + 1);
+                sum += (double)take * (double)SM::key_loss(c.key);
+            }
+            cuts[(size_t)b] = c;
+            total += sum;
+        }
+        if (grads)
+            head_rows_sum(L, L.rows, [&](const SM::Level& lv, int64_t b, int64_t i, int64_t row, double&) {
+                int64_t base, stride;
+                softmax_row_span(lv, K, b, i, &base, &stride);
+                const unsigned key = keys[(size_t)row];
+                if (key == SM::kKeyPos || SM::mined(key, (int)(row - b * n), cuts[(size_t)b])) {
+                    const int64_t lab = labels[row];
+                    softmax_row(lv.logits + base, lv.grad + base, stride, K, lab, k0 * (SM::class_factor(class_weight, lab) * SM::row_weight(weight, row)));
+                } else {
+                    softmax_zero_row(lv.grad + base, stride, K);
+                }
+            });
+    }
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+int sph2pob_softmax_loss_fwd_f32_cpu(const float* logits, const int64_t* labels, const float* weight, const float* class_weight,
+                                     int64_t ignore_index, float scale, float* loss, int64_t n, int64_t num_channels, void*) {
+    if (int rc = SM::flat_check(n, num_channels, 0)) return rc;
+    if (n == 0) return SPH2POB_OK;
+    if (!logits || !labels || !loss) return SPH2POB_ERR_NULL;
+    const int K = (int)num_channels;
+    parallel_for(n, 1 << 10, [&](int64_t lo, int64_t hi) {
+        for (int64_t row = lo; row < hi; row++) {
+            const int64_t lab = labels[row];
+            if (!SM::valid_label(lab, K, ignore_index)) { loss[row] = 0.0f; continue; }
+            const float cwl = SM::class_factor(class_weight, lab), w = SM::row_weight(weight, row);
+            loss[row] = scale * SM::row_loss(softmax_row(logits + row * K, nullptr, 1, K, lab, 0.0f), cwl, w);
+        }
+    });
+    return SPH2POB_OK;
+}
+
+int sph2pob_softmax_loss_bwd_f32_cpu(const float* logits, const int64_t* labels, const float* weight, const float* class_weight,
+                                     int64_t ignore_index, const float* grad_out, int grad_stride, float scale, const float* avg_factor,
+                                     float* grad_logits, int64_t n, int64_t num_channels, void*) {
+    if (int rc = SM::flat_check(n, num_channels, grad_stride)) return rc;
+    if (n == 0) return SPH2POB_OK;
+    if (!logits || !labels || !grad_out || !grad_logits) return SPH2POB_ERR_NULL;
+    const int K = (int)num_channels;
+    const float k0 = SM::effective_scale(scale, avg_factor);
+    parallel_for(n, 1 << 10, [&](int64_t lo, int64_t hi) {
+        for (int64_t row = lo; row < hi; row++) {
+            const int64_t lab = labels[row];
+            if (!SM::valid_label(lab, K, ignore_index)) { softmax_zero_row(grad_logits + row * K, 1, K); continue; }
+            const float cwl = SM::class_factor(class_weight, lab), w = SM::row_weight(weight, row);
+            softmax_row(logits + row * K, grad_logits + row * K, 1, K, lab, grad_out[grad_stride ? row : 0] * (k0 * (cwl * w)));
+        }
+    });
     return SPH2POB_OK;
 }
 

@@ -1,0 +1,200 @@
+// Softmax cross-entropy with optional hard-negative mining (SphSSDHead.loss_single, sphdet/models/heads/sph_ssd_head.py:96-161;
+// mmdet's cross_entropy + weight_reduce_loss in plain mode): the row arithmetic, the order-preserving loss keys, the level table
+// and the argument checks, shared by the kernels (sph2pob_softmax.hip) and their CPU twins (sph2pob_host.hip) so that a CPU tensor
+// gets the arithmetic, the mined set and the checks a device tensor gets.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/sph2pob_hip.h"
+#include "sph2pob_head_loss.hpp"
+
+namespace sph2pob_softmax {
+
+using sph2pob_head::aligned_to;
+using sph2pob_head::effective_scale;
+using sph2pob_head::kBlock;
+using sph2pob_head::kMaxLevels;
+
+constexpr int64_t kMaxLevelElems = ((int64_t)1 << 31) - 4096;   // elements of one level: 32-bit indices inside a level
+constexpr int kMinK = 2, kMaxK = 4096;
+constexpr int kCutBlock = 1024;   // threads of the per-image cut workgroup
+
+// ---- one row, cancellation free ----------------------------------------------------------------------------------------------
+// m = max_j x_j; e_j = expf(x_j - m), the difference taken in fp32: a correctly rounded fp32 subtraction IS the double difference
+// narrowed to fp32.  jx is the one class whose term (exactly 1) is left out of the sums: the target when x_t == m, else the first
+// maximum.  q = sum of e_j over j not in {t, jx}, in double.  Then, with et = e_t:
+//     t == jx:  R = q        CE = log1p(R)                  sum_{j != t} e_j = q
+//     else:     R = q + et   CE = (m - x_t) + log1p(R)      sum_{j != t} e_j = 1 + q
+// S = 1 + R;  p_j = e_j / S;  d CE / d x_t = -(sum_{j != t} e_j) / S (never p_t - 1);  d CE / d x_j = p_j.
+// The walk over the classes belongs to the caller (NCHW planes, a flat row, the twins' strided loop): pass 1 calls see_max for
+// every class, then close_max; pass 2 calls see_sum for every class, then close_sum; pass 3 asks grad(c, x) per class.
+struct Row {
+    float m, xt, et;
+    int t, jm, jx;
+    double q, inv, nt;   // nt: sum_{j != t} e_j
+
+    SPHF_DEV void begin(int target) { m = -INFINITY; xt = 0.0f; et = 1.0f; t = target; jm = 0; jx = 0; q = 0.0; inv = 0.0; nt = 0.0; }
+    SPHF_DEV void see_max(int c, float x) {
+        if (x > m) { m = x; jm = c; }
+        if (c == t) xt = x;
+    }
+    SPHF_DEV void close_max() {
+        jx = xt == m ? t : jm;
+        et = jx == t ? 1.0f : expf(xt - m);
+    }
+    SPHF_DEV void see_sum(int c, float x) {
+        if (c != t && c != jx) q += (double)expf(x - m);
+    }
+    // the row's cross-entropy, rounded to fp32 once
+    SPHF_DEV float close_sum() {
+        const bool top = jx == t;
+        const double r = top ? q : q + (double)et;
+        nt = top ? q : 1.0 + q;
+        inv = 1.0 / (1.0 + r);
+        return (float)((top ? 0.0 : (double)m - (double)xt) + log1p(r));
+    }
+    SPHF_DEV float grad(int c, float x) const {
+        return c == t ? -(float)(nt * inv) : (float)((double)expf(x - m) * inv);
+    }
+};
+
+// valid: 0 <= label < K and label != ignore_index; anything else has loss 0, gradient 0 and is neither positive nor negative
+SPHF_DEV bool valid_label(int64_t lab, int K, int64_t ignore_index) { return lab >= 0 && lab < (int64_t)K && lab != ignore_index; }
+// the row factor cw[label] * w of a valid row; the row loss is (CE * cw) * w and the gradient factor k0 * (cw * w)
+SPHF_DEV float class_factor(const float* cw, int64_t lab) { return cw ? cw[lab] : 1.0f; }
+SPHF_DEV float row_weight(const float* w, int64_t row) { return w ? w[row] : 1.0f; }
+SPHF_DEV float row_loss(float ce, float cwl, float w) { return (ce * cwl) * w; }
+
+// ---- keys: one 32-bit word per row between the passes -------------------------------------------------------------------------
+// 0: the row takes no part (invalid label; in mining mode nothing else is 0);  1: a positive;  >= 2: a negative, the ascending
+// image of its loss — a larger loss has a larger key, -inf maps to 0x007fffff, every NaN to 0xffffffff (above +inf, as torch.topk
+// orders it).  The loss of a mined row is read back from its key: exact, except that -0 comes back as +0 and a NaN as the quiet one.
+constexpr unsigned kKeyNone = 0u, kKeyPos = 1u, kKeyNaN = 0xffffffffu;
+SPHF_DEV unsigned float_bits(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float_as_uint(v);
+#else
+    unsigned u; __builtin_memcpy(&u, &v, 4); return u;
+#endif
+}
+SPHF_DEV float bits_float(unsigned u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float(u);
+#else
+    float v; __builtin_memcpy(&v, &u, 4); return v;
+#endif
+}
+SPHF_DEV unsigned loss_key(float l) {
+    if (l != l) return kKeyNaN;
+    const unsigned u = float_bits(l + 0.0f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+SPHF_DEV float key_loss(unsigned k) {
+    if (k == kKeyNaN) return bits_float(0x7fc00000u);
+    return bits_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// the cut of one image: the k-th largest negative key and the row index below which rows with exactly that key are taken.  Nothing
+// mined: key = kKeyNaN, upto = 0
+struct Cut { unsigned key; int upto; };
+SPHF_DEV bool mined(unsigned key, int i, const Cut& c) { return key >= 2u && (key > c.key || (key == c.key && i < c.upto)); }
+// k_b = min(r P_b, N_b)
+SPHF_DEV int64_t mined_count(int64_t ratio, int64_t pos, int64_t neg) { const int64_t k = ratio * pos; return k < neg ? k : neg; }
+
+// ---- levels ---------------------------------------------------------------------------------------------------------------------
+// kind: how a thread's item maps onto memory
+//   0  NCHW (B, A K, H, W), four consecutive positions p = h W + w of one (b, a) per item: 16-byte accesses at stride H W over the classes
+//   1  NCHW, one position per item (H W % 4 != 0 or a base that is not 16-byte aligned)
+//   2  flat (B, n_l, K), one row per item walked with 16-byte accesses (K % 4 == 0 and an aligned base)
+//   3  flat, one row per item, one element at a time
+enum { KIND_NCHW4 = 0, KIND_NCHW1 = 1, KIND_FLAT4 = 2, KIND_FLAT1 = 3 };
+struct Level {
+    const float* logits;
+    float* grad;           // laid out like logits; NULL in a forward-only call
+    int n, hw, a, kind;    // anchors of the level; H W (0: flat); anchors per position
+    int items;             // work items of the level
+    int block_off;         // first workgroup of the level
+    int64_t row_off;       // index of the level's first anchor inside an image's n rows
+};
+struct Levels {
+    Level lv[kMaxLevels];
+    int num, blocks;       // levels; workgroups of a row pass
+    int64_t n_total;       // anchors of one image, all levels
+    int64_t n_pad;         // n_total rounded up to 4: the stride of one image's keys
+    int64_t rows;          // B n
+};
+
+// Argument checks of sph2pob_softmax_loss_sum_f32 / its twin, in the documented order; fills the table.  `tables` false: shapes
+// only (the workspace size), every level counted with its scalar kind (an upper bound on the workgroups).
+inline int make_levels(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw, int num_levels,
+                       int64_t B, int64_t K, int64_t neg_pos_ratio, bool tables, Levels* out) {
+    if (neg_pos_ratio < -1 || neg_pos_ratio > ((int64_t)1 << 30)) return SPH2POB_ERR_OPTION;
+    if (num_levels < 1 || num_levels > kMaxLevels || B < 0 || B > 65535 || K < kMinK || K > kMaxK) return SPH2POB_ERR_SIZE;
+    if (!level_n || (tables && !logits)) return SPH2POB_ERR_NULL;
+    Levels L{};
+    L.num = num_levels;
+    int64_t blocks = 0, rows = 0;
+    for (int l = 0; l < num_levels; l++) {
+        const int64_t n = level_n[l], hw = level_hw ? level_hw[l] : 0;
+        if (n < 0 || hw < 0 || (hw > 0 && n % hw != 0) || n > kMaxLevelElems / K || (B > 0 && n * K > kMaxLevelElems / B)) return SPH2POB_ERR_SIZE;
+        const int64_t elems = B * n * K;
+        Level& d = L.lv[l];
+        d.n = (int)n; d.hw = (int)hw; d.a = hw > 0 ? (int)(n / hw) : 1;
+        d.logits = tables ? (const float*)logits[l] : nullptr;
+        d.grad = tables && grads ? (float*)grads[l] : nullptr;
+        if (tables && elems > 0 && (!d.logits || (grads && !d.grad))) return SPH2POB_ERR_NULL;
+        const bool al = tables && aligned_to(d.logits, 16) && aligned_to(d.grad, 16);
+        if (hw > 0) d.kind = al && hw % 4 == 0 ? KIND_NCHW4 : KIND_NCHW1;
+        else d.kind = al && K % 4 == 0 ? KIND_FLAT4 : KIND_FLAT1;
+        const int64_t items = d.kind == KIND_NCHW4 ? B * n / 4 : B * n;
+        d.items = (int)items;
+        d.block_off = (int)blocks;
+        d.row_off = rows;
+        blocks += (items + kBlock - 1) / kBlock;
+        rows += n;
+        if (blocks >= ((int64_t)1 << 31) - 1 || rows >= ((int64_t)1 << 31) - 8) return SPH2POB_ERR_SIZE;
+    }
+    L.blocks = (int)blocks; L.n_total = rows; L.n_pad = (rows + 3) / 4 * 4; L.rows = B * rows;
+    *out = L;
+    return SPH2POB_OK;
+}
+
+// The workspace: doubles [0, blocks) the row pass's partials, [blocks, blocks + B) the mined sums of the images (mining), one
+// spare; then (mining) B cuts and B n_pad keys
+struct Workspace {
+    double* partial;
+    Cut* cut;
+    unsigned* keys;
+};
+inline int64_t partial_doubles(int64_t blocks, int64_t B) { return (blocks + B + 1 + 1) / 2 * 2; }   // keeps what follows 16-byte aligned
+inline int64_t workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t B, int64_t K, int mining) {
+    Levels L;
+    if (make_levels(nullptr, nullptr, level_n, level_hw, num_levels, B, K, -1, false, &L) != SPH2POB_OK) return 0;
+    int64_t bytes = 8 * partial_doubles(L.blocks, B);
+    if (mining) bytes += ((int64_t)sizeof(Cut) * B + 15) / 16 * 16 + 4 * B * L.n_pad;
+    return bytes + 16;
+}
+// `blocks`: the upper bound workspace_bytes used (the scalar kinds), so that the carve does not move with the alignment of a call
+inline Workspace carve(void* workspace, const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t B, int64_t K) {
+    Levels U;
+    make_levels(nullptr, nullptr, level_n, level_hw, num_levels, B, K, -1, false, &U);
+    uintptr_t p = (reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15;
+    Workspace w;
+    w.partial = reinterpret_cast<double*>(p);
+    p += 8 * (uintptr_t)partial_doubles(U.blocks, B);
+    w.cut = reinterpret_cast<Cut*>(p);
+    p += ((uintptr_t)sizeof(Cut) * (uintptr_t)B + 15) / 16 * 16;
+    w.keys = reinterpret_cast<unsigned*>(p);
+    return w;
+}
+
+// flat (N, K) entries: grad_stride -> OPTION; n < 0, K outside [2, 4096], N K too large -> SIZE
+inline int flat_check(int64_t n, int64_t K, int grad_stride) {
+    if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
+    if (n < 0 || K < kMinK || K > kMaxK || n > ((int64_t)1 << 38) / K) return SPH2POB_ERR_SIZE;
+    return SPH2POB_OK;
+}
+
+}  // namespace sph2pob_softmax

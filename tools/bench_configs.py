@@ -556,6 +556,85 @@ def focal(images=8, classes=37, rounds=7):
                     'device copy of the five logit tensors (reads and writes 4 B per element each, the bytes the fused kernel moves)'}
 
 
+SSD300_LEVELS = ((4, 38, 38), (6, 19, 19), (6, 10, 10), (6, 5, 5), (4, 3, 3), (4, 1, 1))   # (A, H, W): 8 732 anchors
+
+
+def softmax_mining(images=8, channels=38, rounds=7):
+    """The softmax classification loss with hard-negative mining (sph_softmax_loss, neg_pos_ratio=3, row weights, a device
+    avg_factor), forward + backward on the head's NCHW scores, at two shapes: the project's head (512 x 1024 ERP, 5 levels, 9
+    anchors: 98 208 anchors) and SSD300's 8 732 anchors in 6 levels; K = 38 score channels at both.  Per shape: (a) eager; (b) the
+    same replayed from a graph; (c) the torch composition of SphSSDHead.loss's classification half in this process — permute /
+    reshape / cat, F.cross_entropy(reduction='none') * weights, then per image nonzero() twice, a host k and topk — forward +
+    backward.  Timed in alternation `rounds` times, medians and spreads reported."""
+    import torch.nn.functional as F
+    import demo_hot_path as D
+    shapes = (('head 512x1024 ERP, 5 levels', [(9, h, w) for h, w in D.LEVEL_SHAPES]), ('SSD300, 6 levels', list(SSD300_LEVELS)))
+    med = lambda v: float(np.median(v))
+    out = {'config': 'softmax_mining: %d images, K = %d, neg_pos_ratio 3, fwd + bwd' % (images, channels), 'shapes': []}
+    for what, levels in shapes:
+        g = torch.Generator(device='cuda').manual_seed(0)
+        cls = [(torch.randn((images, a * channels, h, w), generator=g, device='cuda') * 2).requires_grad_(True) for a, h, w in levels]
+        n = sum(a * h * w for a, h, w in levels)
+        bg = channels - 1
+        labels = torch.randint(0, bg, (images, n), generator=g, device='cuda')
+        labels[torch.rand((images, n), generator=g, device='cuda') > 0.01] = bg      # ~1 % positives
+        weights = (torch.rand((images, n), generator=g, device='cuda') > 0.02).float()
+        avg = labels.ne(bg).sum().float().reshape(1)
+
+        def fused():
+            loss = S.sph_softmax_loss(cls, labels, weights, neg_pos_ratio=3, avg_factor=avg)
+            return (loss.detach(),) + torch.autograd.grad(loss, cls)
+
+        def forward_only():
+            with torch.no_grad():
+                return S.sph_softmax_loss(cls, labels, weights, neg_pos_ratio=3, avg_factor=avg)
+
+        def composition():
+            x = torch.cat([c.permute(0, 2, 3, 1).reshape(images, -1, channels) for c in cls], 1)
+            total = x.new_zeros(())
+            for b in range(images):
+                loss_all = F.cross_entropy(x[b], labels[b], reduction='none') * weights[b]
+                pos = ((labels[b] >= 0) & (labels[b] < bg)).nonzero(as_tuple=False).reshape(-1)
+                neg = (labels[b] == bg).nonzero(as_tuple=False).reshape(-1)
+                k = min(3 * pos.size(0), neg.size(0))
+                top, _ = loss_all[neg].topk(k)
+                total = total + loss_all[pos].sum() + top.sum()
+            loss = total / (avg + 1.1920929e-07)
+            return (loss.detach().reshape(()),) + torch.autograd.grad(loss, cls)
+        # The capture comes first, after a warm-up on a side stream, and nothing returned keeps an autograd graph alive (see
+        # _decoded_loss: a gradient edge of `cls` left by an eager call on the default stream invalidates the capture).
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fused()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            fused()
+        a, c = fused(), composition()
+        torch.cuda.synchronize()
+        loss_rel = abs(float(a[0]) - float(c[0])) / abs(float(c[0]))
+        grad_diff = max(float((x - y).abs().max()) for x, y in zip(a[1:], c[1:]))
+        ta, tb, tc, tf = [], [], [], []
+        for _ in range(rounds):
+            ta.append(timeit(fused, reps=30) * 1e6)
+            tb.append(timeit(graph.replay, reps=30) * 1e6)
+            tc.append(timeit(composition, warm=2, reps=5, settle_s=0.0) * 1e6)
+            tf.append(timeit(forward_only, reps=30) * 1e6)
+        out['shapes'].append({
+            'shape': '%s: %d anchors' % (what, n), 'a_fused_eager_us': med(ta), 'b_fused_graph_us': med(tb), 'c_torch_composition_us': med(tc),
+            'f_fused_forward_only_us': med(tf),
+            'a_rounds_us': ta, 'b_rounds_us': tb, 'c_rounds_us': tc, 'f_rounds_us': tf, 'a_spread_us': max(ta) - min(ta),
+            'b_spread_us': max(tb) - min(tb), 'c_spread_us': max(tc) - min(tc), 'f_spread_us': max(tf) - min(tf),
+            'a_over_c': med(ta) / med(tc), 'b_over_c': med(tb) / med(tc), 'logit_bytes': 4 * images * n * channels,
+            'loss_fused': float(a[0]), 'loss_composition': float(c[0]), 'loss_rel_diff': loss_rel, 'grad_max_abs_diff': grad_diff})
+        del graph
+    out['note'] = ('f: the forward alone under no_grad (rows -> keys, cut, final: no gradient pass).  The composition synchronises with '
+                   'the host twice per image (nonzero) and cannot be captured.')
+    return out
+
+
 def _decoded_loss(name, what, fused_loss, module, images_counts, classes, rounds):
     """The scene and the four timings shared by bbox_loss and gauss_bbox_loss: `fused_loss(preds, anchors, t, coder)` is the fused
     call, `module` the loss module of the composition."""
@@ -842,8 +921,8 @@ def gaussian(n=1_000_000):
 if __name__ == '__main__':
     # config4 twice: the reference's default 512 x 1024 ERP (98 208 anchors: the "~100k" of BASELINE configs[3]) and the
     # literal 1024 x 2048 grid (392 832 anchors, SURVEY §8d "secondary")
-    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch train_targets get_bboxes focal bbox_loss gauss_bbox_loss delta_loss coder unbiased variants; none = all)
-    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, train_targets=train_targets, get_bboxes=get_bboxes, focal=focal, bbox_loss=bbox_loss, gauss_bbox_loss=gauss_bbox_loss, delta_loss=delta_loss, coder=coder, unbiased=unbiased,
+    # (arguments select configurations by name: config3 gaussian config4 config4b config4_batch train_targets get_bboxes focal softmax_mining bbox_loss gauss_bbox_loss delta_loss coder unbiased variants; none = all)
+    table = dict(config3=config3, gaussian=gaussian, config4=config4, config4b=lambda: config4(1024, 2048), config4_batch=config4_batch, train_targets=train_targets, get_bboxes=get_bboxes, focal=focal, softmax_mining=softmax_mining, bbox_loss=bbox_loss, gauss_bbox_loss=gauss_bbox_loss, delta_loss=delta_loss, coder=coder, unbiased=unbiased,
                  variants=variants)
     for name in (sys.argv[1:] or list(table)):
         print(json.dumps(table[name]()), flush=True)
