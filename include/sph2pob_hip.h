@@ -791,6 +791,66 @@ int sph2pob_gauss_bbox_loss_sum_h16(const void* const* bbox_preds, void* const* 
                                     int opts, float beta, float eps, float scale, const float* avg_factor, float* out,
                                     void* workspace, const float* grad_out, int skip_if_one, int dtype, void* stream);
 
+/* ---- inference for softmax heads (use_sigmoid_cls=False: SphSSDHead, the two-channel SphRPNHead) ---------------------------------
+ * The reference's `cls_score.softmax(-1)[:, :-1]` in front of filter_scores_and_topk (sphdet/models/heads/sph_ssd_head.py:330-347;
+ * sph_rpn_head.py:52-57, softmax(dim=1)[:, 0], is K = 2), for B images, read from the head's own layout.  Every anchor has
+ * K = num_classes + 1 logits, the background LAST inside the anchor's group of K: NCHW (B, A K, H_l, W_l), channel a K + j, or
+ * flat (B, n_l, K).
+ * The probability, pinned as the sigmoid of sph2pob_test_bboxes_f32 is (csrc/sph2pob_softmax.hpp, Prob): per anchor m = max_j x_j;
+ * e_j = expf(x_j - m), the difference taken in fp32; S = sum_j e_j in double, in ascending class order; p_c = (float)((double)e_c
+ * / S) for c < C = num_classes.  These are the e_j and the S of the loss (sph2pob_softmax_loss_sum_f32's Row), whose gradient
+ * e_j * (1 / S) differs from e_j / S in the last bit of a double at most: a model infers with the probabilities it was trained
+ * with.  A -inf logit has probability exactly 0.  A row with a NaN or a +inf (or without a finite logit) is NaN in all its
+ * classes and so yields no candidate (score > score_thr is false); other rows are not touched.
+ *
+ * sph2pob_softmax_scores_f32 — the probabilities alone, one launch, nothing read back:
+ *   logits       HOST table of num_levels <= 8 device pointers, laid out as above, read in place
+ *   level_n      n_l anchors;  level_hw: H_l W_l for the NCHW layout, 0 for the flat one (NULL: every level flat)
+ *   out          HOST table of device pointers: level l receives fp32 (B, A C, H_l, W_l) resp. (B, n_l, C) — the layout of the
+ *                logits without the background channel, what sph2pob_test_bboxes_f32 takes with activation = 0
+ * Errors, in this order, before anything is enqueued: num_levels outside [1, 8], B outside [0, 65 535], K = num_classes + 1
+ * outside [2, 4096] -> SPH2POB_ERR_SIZE; a NULL level_n / logits / out table -> SPH2POB_ERR_NULL; per level n_l < 0, level_hw that
+ * does not divide n_l, B n_l K >= 2^31 - 4096 -> SPH2POB_ERR_SIZE, a NULL entry of a level with B n_l > 0 -> SPH2POB_ERR_NULL.
+ * B n_l == 0 everywhere: nothing is enqueued.
+ * sph2pob_softmax_scores_h16 — float16 / bfloat16 logits read where they are (dtype: SPH2POB_DTYPE_*, checked first ->
+ * SPH2POB_ERR_OPTION), widened on load; out stays fp32 and has the bits the _f32 entry gives on the widened logits.
+ *
+ * sph2pob_softmax_bboxes_f32 — sph2pob_test_bboxes_f32 for a softmax head in one call, eleven launches whatever B is, nothing
+ * read back, nothing allocated, capturable.  The arguments of sph2pob_test_bboxes_f32 without `activation`; cls_scores are
+ * the logits (K per anchor), num_classes = C = K - 1.  Stage 0 writes the probabilities above into the workspace, in the head's
+ * layout without the background channel; from there on everything is what sph2pob_test_bboxes_f32 documents with activation = 0:
+ * a candidate is (anchor, c) with index anchor C + c, valid iff p > score_thr, the selection, decode, NMS and outputs as there —
+ * the result has the BITS of sph2pob_test_bboxes_f32 on the output of sph2pob_softmax_scores_f32.  labels lie in [0, C).
+ *   workspace    sph2pob_softmax_bboxes_workspace_bytes(level_n, num_levels, B, C, box_dim, nms_pre) bytes, no initialisation
+ *                (0 = the shapes are not accepted): that of sph2pob_test_bboxes_f32 plus 4 B n_l C bytes per level
+ * Errors, in the order of sph2pob_test_bboxes_f32: box_dim -> SPH2POB_ERR_DIM; variant, flags, class_agnostic, coder_flags,
+ * max_ratio < 0 -> SPH2POB_ERR_OPTION; num_levels outside [1, 8], B outside [1, 65 535], C < 1 or K = C + 1 > 4096, nms_pre <= 0,
+ * max_per_img < 0 -> SPH2POB_ERR_SIZE; a NULL table -> SPH2POB_ERR_NULL; n_l < 1, n_l C >= 2^31 - 2^17, level_hw that does not
+ * divide n_l, K_cap > sph2pob_batched_nms_max_boxes() -> SPH2POB_ERR_SIZE; a NULL table entry, output or workspace ->
+ * SPH2POB_ERR_NULL; then B n_l K >= 2^31 - 4096 -> SPH2POB_ERR_SIZE.
+ * sph2pob_softmax_bboxes_h16 — float16 / bfloat16 logits AND deltas read where they are (dtype checked first ->
+ * SPH2POB_ERR_OPTION); no fp32 copy of either exists, only the C foreground probabilities are written, in fp32; the outputs have
+ * the bits of the _f32 entry on the widened levels.  The _f32 entries have CPU twins, the _h16 ones do not.
+ */
+int sph2pob_softmax_scores_f32(const void* const* logits, const int64_t* level_n, const int64_t* level_hw, int num_levels,
+                               int64_t num_images, int64_t num_classes, void* const* out, void* stream);
+int sph2pob_softmax_scores_h16(const void* const* logits, const int64_t* level_n, const int64_t* level_hw, int num_levels,
+                               int64_t num_images, int64_t num_classes, void* const* out, int dtype, void* stream);
+int64_t sph2pob_softmax_bboxes_workspace_bytes(const int64_t* level_n, int num_levels, int64_t num_images, int64_t num_classes,
+                                               int box_dim, int64_t nms_pre);
+int sph2pob_softmax_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors,
+                               const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                               int64_t num_classes, int box_dim, float score_thr, int64_t nms_pre, const float* means_host,
+                               const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp, int variant_flags,
+                               int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
+                               int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream);
+int sph2pob_softmax_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors,
+                               const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                               int64_t num_classes, int box_dim, float score_thr, int64_t nms_pre, const float* means_host,
+                               const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp, int variant_flags,
+                               int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
+                               int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ LIB_DIR = os.path.join(_HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_hip.so')
 HOST_LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_host.so')
 SOURCES = ['sph2pob_iou.hip', 'sph2pob_assign.hip', 'sph2pob_loss.hip', 'sph2pob_nms.hip', 'sph2pob_coder.hip', 'sph2pob_get_bboxes.hip',
-           'sph2pob_focal.hip', 'sph2pob_bbox_loss.hip', 'sph2pob_delta_loss.hip', 'sph2pob_gauss_bbox_loss.hip', 'sph2pob_softmax.hip']
+           'sph2pob_focal.hip', 'sph2pob_bbox_loss.hip', 'sph2pob_delta_loss.hip', 'sph2pob_gauss_bbox_loss.hip', 'sph2pob_softmax.hip', 'sph2pob_softmax_bboxes.hip']
 HOST_SOURCES = ['sph2pob_host.hip']
 HOST_FLAGS = ['--offload-arch=gfx950', '--cuda-host-only', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-pthread']
 
@@ -46,7 +46,7 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_gauss_loss_fwd_grad_f32', 'sph2pob_anchor_targets_f32', 'sph2pob_anchor_targets_any_f32', 'sph2pob_get_bboxes_f32', 'sph2pob_test_bboxes_f32', 'sph2pob_focal_loss_sum_f32',
               'sph2pob_focal_loss_fwd_f32', 'sph2pob_focal_loss_bwd_f32', 'sph2pob_focal_loss_grad_scale_f32', 'sph2pob_bbox_loss_sum_f32',
               'sph2pob_delta_loss_sum_f32', 'sph2pob_gauss_bbox_loss_sum_f32', 'sph2pob_softmax_loss_sum_f32',
-              'sph2pob_softmax_loss_fwd_f32', 'sph2pob_softmax_loss_bwd_f32']
+              'sph2pob_softmax_loss_fwd_f32', 'sph2pob_softmax_loss_bwd_f32', 'sph2pob_softmax_scores_f32', 'sph2pob_softmax_bboxes_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp', 'sph2pob_gauss_bbox_loss.hpp', 'sph2pob_softmax.hpp',
            'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
@@ -170,6 +170,12 @@ SIGNATURES = {
     'sph2pob_softmax_loss_fwd_f32': [_c_f32p, ctypes.c_void_p, _c_f32p, _c_f32p, _i64, ctypes.c_float, _c_f32p, _i64, _i64, ctypes.c_void_p],
     'sph2pob_softmax_loss_bwd_f32': [_c_f32p, ctypes.c_void_p, _c_f32p, _c_f32p, _i64, _c_f32p, _int, ctypes.c_float, _c_f32p, _c_f32p,
                                     _i64, _i64, ctypes.c_void_p],
+    # level tables (logits, n, hw), num_levels, B, C, output table, stream
+    'sph2pob_softmax_scores_f32': [ctypes.c_void_p] * 3 + [_int, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p],
+    'sph2pob_softmax_bboxes_workspace_bytes': [ctypes.c_void_p, _int, _i64, _i64, _int, _i64],
+    # sph2pob_test_bboxes_f32 without `activation`
+    'sph2pob_softmax_bboxes_f32': [ctypes.c_void_p] * 5 + [_int, _i64, _i64, _int, ctypes.c_float, _i64, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_float, _int, ctypes.c_float, _int, _int, ctypes.c_float, _i64] + [ctypes.c_void_p] * 6,
     'sph2pob_coder_encode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int,
                                  ctypes.c_void_p],
     'sph2pob_coder_decode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int, _int,
@@ -185,7 +191,7 @@ SIGNATURES = {
 H16_DTYPES = {'float16': 1, 'bfloat16': 2}
 for _name in ('focal_loss_sum', 'bbox_loss_sum', 'delta_loss_sum', 'gauss_bbox_loss_sum'):
     SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_c_f32p, _int, _int, ctypes.c_void_p]
-for _name in ('get_bboxes', 'test_bboxes'):
+for _name in ('get_bboxes', 'test_bboxes', 'softmax_scores', 'softmax_bboxes'):
     SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_int, ctypes.c_void_p]
 _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_target_arch': ctypes.c_char_p, 'sph2pob_error_string': ctypes.c_char_p,
              'sph2pob_nms_workspace_bytes': ctypes.c_int64, 'sph2pob_nms_segmented_workspace_bytes': ctypes.c_int64, 'sph2pob_assign_workspace_bytes': ctypes.c_int64,
@@ -194,7 +200,7 @@ _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_targe
              'sph2pob_batched_nms_workspace_bytes': ctypes.c_int64, 'sph2pob_get_bboxes_workspace_bytes': ctypes.c_int64,
              'sph2pob_focal_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_bbox_loss_workspace_bytes': ctypes.c_int64,
              'sph2pob_delta_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_gauss_bbox_loss_workspace_bytes': ctypes.c_int64,
-             'sph2pob_softmax_loss_workspace_bytes': ctypes.c_int64}
+             'sph2pob_softmax_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_softmax_bboxes_workspace_bytes': ctypes.c_int64}
 
 ABI_VERSION = 6
 

@@ -12,9 +12,13 @@ the counts stay on the device (`num_dets`).
 The reference's unstable parts are pinned: the per-level order is (score descending, candidate index ascending) — a stable
 descending sort — and NMS ties go by candidate position, as `sph_batched_nms` has them here.
 
+Softmax heads (`use_sigmoid_cls=False`: SphSSDHead, the two-channel SphRPNHead) have entries of their own in
+`softmax_bboxes.py`: `sph_softmax_bboxes` is `sph_test_bboxes` on K = C + 1 logits per anchor, `sph_softmax_scores` the
+probabilities alone.  Both entries here keep refusing `activation='softmax'`.
+
 The per-image API (`multiclass_nms`, or `filter` + `bbox_coder.decode` + `sph_batched_nms` on each image and level) keeps serving
-what these entries do not: score factors, softmax heads, `with_nms=False`, the `'xinyuan'` / `kent_iou` calculators, the
-reference arithmetic and more than 16 384 candidates per image.
+what none of these entries does: score factors, `with_nms=False`, the `'xinyuan'` / `kent_iou` calculators, the reference
+arithmetic and more than 16 384 candidates per image.
 """
 import ctypes
 import math
@@ -27,6 +31,7 @@ from .sph_nms import _variant_of
 
 _PER_IMAGE = 'use the per-image API (per level: score filter, top-k and bbox_coder.decode; then sph_batched_nms / multiclass_nms on each image)'
 _MAX_LEVELS = 8
+_SOFTMAX_MAX_K = 4096   # kMaxK of csrc/sph2pob_softmax.hpp: the softmax loss and the softmax inference share it
 
 
 class DetBBoxes:
@@ -69,7 +74,8 @@ def _refuse_head_options(who, activation, score_factors, with_nms, nms):
     if score_factors is not None:
         raise NotImplementedError(f'{who} does not take score factors (FCOS-style heads): ' + _PER_IMAGE)
     if activation == 'softmax':
-        raise NotImplementedError(f'{who} implements sigmoid heads only (use_sigmoid_cls=True), not softmax: ' + _PER_IMAGE)
+        raise NotImplementedError(f'{who} implements sigmoid heads only (use_sigmoid_cls=True), not softmax: sph_softmax_bboxes is the batched '
+                                  'entry for softmax heads; or ' + _PER_IMAGE)
     if activation not in ('sigmoid', 'none'):
         raise ValueError(f"activation must be 'sigmoid' or 'none', got {activation!r}")
     if not with_nms:
@@ -87,7 +93,10 @@ def _refuse_reference_arithmetic(who, arithmetic):
 
 def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder, score_thr, nms_pre, iou_threshold, max_per_img, box_version,
          activation, wh_ratio_clip):
-    """The level marshalling and the call both entries share; `nms_args`: what `symbol` takes between ctr_clamp and iou_threshold."""
+    """The level marshalling and the call the entries share; `nms_args`: what `symbol` takes between ctr_clamp and iou_threshold.
+    `activation='softmax'` (sph_softmax_bboxes only): cls_scores hold K = C + 1 logits per anchor, `symbol` has no activation argument
+    and sizes its workspace itself."""
+    softmax = activation == 'softmax'
     nms_pre, max_per_img = int(nms_pre), int(max_per_img)
     if nms_pre <= 0:
         raise ValueError(f'nms_pre must be positive, got {nms_pre} (the reference slices with min(-1, n); that quirk is not reproduced)')
@@ -118,12 +127,16 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
             num_classes = c
         if c != num_classes or c == 0:
             raise ValueError(f'level {l}: {c} classes, level 0 has {num_classes}')
+        if softmax and not 2 <= c <= _SOFTMAX_MAX_K:
+            raise ValueError(f'{who}: {c} logits per anchor; a softmax head has K = num_classes + 1 in [2, {_SOFTMAX_MAX_K}], the background last')
         cs, hw = _level(cls_scores[l], f'cls_scores[{l}]', c, n, images, bool(code))
         bp, hw_b = _level(bbox_preds[l], f'bbox_preds[{l}]', dim, n, images, bool(code))
         if hw != hw_b:
             raise ValueError(f'level {l}: cls_scores and bbox_preds must use the same layout')
         held += [cs, bp, anc]
         cls_p.append(cs.data_ptr()); box_p.append(bp.data_ptr()); anc_p.append(anc.data_ptr()); ns.append(n); hws.append(hw)
+    if softmax:
+        num_classes -= 1
     lib = _lib.lib()
     k_cap = sum(min(nms_pre, n * num_classes) for n in ns)
     if k_cap > lib.sph2pob_batched_nms_max_boxes():
@@ -137,7 +150,7 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
                     prior_inds=torch.empty((images, max_per_img), **i64), num_dets=torch.empty((images,), **i64))
     ws = None
     if dev.type != 'cpu':
-        need = lib.sph2pob_get_bboxes_workspace_bytes(level_n, levels, images, num_classes, dim, nms_pre)
+        need = (lib.sph2pob_softmax_bboxes_workspace_bytes if softmax else lib.sph2pob_get_bboxes_workspace_bytes)(level_n, levels, images, num_classes, dim, nms_pre)
         if need <= 0:
             raise ValueError(f'{who}: these shapes are outside the limits of {symbol} (include/sph2pob_hip.h)')
         ws = G.scratch(dev, need)
@@ -149,7 +162,7 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
     else:
         tail = ()
     G.call(symbol, dev, ptrs(*cls_p), ptrs(*box_p), ptrs(*anc_p), level_n, i64s(*hws), levels, images, num_classes, dim,
-           int(activation == 'sigmoid'), float(score_thr), nms_pre, means, stds, float(abs(math.log(wh_ratio_clip))), flags,
+           *(() if softmax else (int(activation == 'sigmoid'),)), float(score_thr), nms_pre, means, stds, float(abs(math.log(wh_ratio_clip))), flags,
            float(bbox_coder.ctr_clamp), *nms_args, float(iou_threshold), max_per_img, G.ptr(out.dets),
            G.ptr(out.labels), G.ptr(out.prior_inds), out.num_dets.data_ptr(), G.ptr(ws), *tail, G.raw_stream_of(dev))
     return out
@@ -181,7 +194,7 @@ _TEST_CFG_KEYS = ('score_thr', 'nms_pre', 'nms', 'max_per_img', 'iou_calculator'
 _OTHER_KEYS = ('score_factors', 'with_nms', 'wh_ratio_clip', 'arithmetic')
 
 
-def _test_variant(iou_calculator, box_formator, nms_cfg):
+def _test_variant(iou_calculator, box_formator, nms_cfg, who='sph_test_bboxes'):
     """test_cfg.iou_calculator (+ box_formator, nms.class_agnostic) -> (kernel variant name, class_agnostic), as
     `_bbox_post_process` picks PlanarNMS / SphNMS (sph_retina_head.py:89-92)."""
     calc = iou_calculator
@@ -192,7 +205,7 @@ def _test_variant(iou_calculator, box_formator, nms_cfg):
     elif type(calc).__name__ == 'SphOverlaps2D':
         calc = calc.backend
     if calc in ('xinyuan', 'kent_iou'):
-        raise NotImplementedError(f'sph_test_bboxes has no batched NMS on the {calc} calculator: ' + _PER_IMAGE)
+        raise NotImplementedError(f'{who} has no batched NMS on the {calc} calculator: ' + _PER_IMAGE)
     if calc == 'planar' or type(calc).__name__ == 'PlanarNMS':
         formator = calc.box_formator if type(calc).__name__ == 'PlanarNMS' else box_formator
         if formator not in ('sph2pix', 'sph2tan'):

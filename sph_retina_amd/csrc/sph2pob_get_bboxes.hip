@@ -292,8 +292,9 @@ int launch_status() {
     return e == hipSuccess ? SPH2POB_OK : (int)e;
 }
 
-// T: the element type of cls_scores and bbox_preds (anchors and every output are fp32 / int64 whatever T is)
-template <class T>
+// TS: the element type of cls_scores, TD: of bbox_preds (anchors and every output are fp32 / int64 whatever they are).  The public
+// entries read both as one type; the softmax entries select on fp32 probabilities and gather the head's own deltas
+template <class TS, class TD = TS>
 int test_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
                 const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
                 float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
@@ -309,19 +310,19 @@ int test_bboxes(const void* const* cls_scores, const void* const* bbox_preds, co
     const Ws w = make_ws(workspace, L, B, box_dim);
     const int pre = (int)(nms_pre < ((int64_t)1 << 30) ? nms_pre : ((int64_t)1 << 30));
     if (hipMemsetAsync(w.hist, 0, (size_t)w.zero_bytes, s) != hipSuccess) return (int)hipGetLastError();
-    hipLaunchKernelGGL(topk_hist_kernel<T>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.hist);
+    hipLaunchKernelGGL(topk_hist_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.hist);
     hipLaunchKernelGGL(topk_cut_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, pre, (const int*)w.hist, w.meta);
-    hipLaunchKernelGGL(topk_compact_kernel<T>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.meta, w.buf);
+    hipLaunchKernelGGL(topk_compact_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.meta, w.buf);
     hipLaunchKernelGGL(topk_resolve_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.buf, w.sel);
     int max_cap = 0;
     for (int l = 0; l < L.num; l++) max_cap = L.lv[l].cap > max_cap ? L.lv[l].cap : max_cap;
     const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
     const dim3 bgrid((max_cap + kBuildBlock - 1) / kBuildBlock, L.num, B);
     if (box_dim == 4)
-        hipLaunchKernelGGL((cand_build_kernel<4, T>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+        hipLaunchKernelGGL((cand_build_kernel<4, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
                            (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
     else
-        hipLaunchKernelGGL((cand_build_kernel<5, T>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+        hipLaunchKernelGGL((cand_build_kernel<5, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
                            (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
     if (int rc = launch_status()) return rc;
     return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant_flags, class_agnostic, iou_threshold,
@@ -363,6 +364,21 @@ int sph2pob_test_bboxes_h16(const void* const* cls_scores, const void* const* bb
                                         iou_threshold, max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
     };
     return dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
+}
+
+// Stages 1-10 on fp32 probabilities with the deltas of the head's own type (delta_dtype 0: fp32, else SPH2POB_DTYPE_*): the pipeline
+// behind sph2pob_softmax_bboxes_f32 / _h16 (sph2pob_softmax_bboxes.hip), whose stage 0 wrote `probs`.  Inside the library only
+int sph2pob_test_bboxes_on_probs(const void* const* probs, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                                 const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
+                                 int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
+                                 float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
+                                 int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, int delta_dtype, void* stream) {
+    auto run = [&](auto t) {
+        return test_bboxes<float, decltype(t)>(probs, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0,
+                                               score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags,
+                                               class_agnostic, iou_threshold, max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+    };
+    return delta_dtype == 0 ? run(float{}) : delta_dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
 }
 
 // the closed-form calculators, per class: its own variant check (after the box_dim check, as documented), then the entry above

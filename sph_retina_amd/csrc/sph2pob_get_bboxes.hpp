@@ -16,6 +16,13 @@ extern "C" __attribute__((visibility("hidden"))) int sph2pob_nms_batch_launch(
     int box_dim, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, void* nms_workspace, float* dets,
     int64_t* labels_out, int64_t* prior_out, int64_t* num_dets, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim);
+// Stages 1-10 of sph2pob_test_bboxes_f32 (activation 0) on fp32 scores with deltas of their own element type (delta_dtype 0: fp32,
+// else SPH2POB_DTYPE_*), defined in sph2pob_get_bboxes.hip and called from sph2pob_softmax_bboxes.hip (inside the library only)
+extern "C" __attribute__((visibility("hidden"))) int sph2pob_test_bboxes_on_probs(
+    const void* const* probs, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n, const int64_t* level_hw,
+    int num_levels, int64_t num_images, int64_t num_classes, int box_dim, float score_thr, int64_t nms_pre, const float* means_host,
+    const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold,
+    int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, int delta_dtype, void* stream);
 
 namespace sph2pob_gb {
 

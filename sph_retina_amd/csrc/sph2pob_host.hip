@@ -1113,3 +1113,72 @@ int sph2pob_softmax_loss_bwd_f32_cpu(const float* logits, const int64_t* labels,
 }
 
 }  // extern "C"
+
+// ---- inference for softmax heads: the twins of sph2pob_softmax_bboxes.hip on the Prob and the level table of sph2pob_softmax.hpp ----
+namespace {
+// every row of every level: the three walks of Prob, the probabilities written without the background channel
+void softmax_prob_rows(const SM::ProbLevels& L, const int64_t* level_n, int64_t B, int K) {
+    for (int l = 0; l < L.num; l++) {
+        const SM::ProbLevel& lv = L.lv[l];
+        const float* x = (const float*)lv.logits;
+        const int64_t n = level_n[l];
+        parallel_for(B * n, 1 << 10, [&](int64_t lo, int64_t hi) {
+            for (int64_t row = lo; row < hi; row++) {
+                int64_t in = row * K, out = row * (K - 1), stride = 1;
+                if (lv.hw > 0) {
+                    const int64_t b = row / n, i = row - b * n, p = i / lv.a, a = i - p * lv.a;
+                    SM::prob_nchw_span(b * lv.a + a, p, lv.hw, K, &in, &out);
+                    stride = lv.hw;
+                }
+                SM::Prob r;
+                r.begin();
+                for (int j = 0; j < K; j++) r.see_max(x[in + j * stride]);
+                for (int j = 0; j < K; j++) r.see_sum(x[in + j * stride]);
+                for (int j = 0; j < K - 1; j++) lv.out[out + j * stride] = r.p(x[in + j * stride]);
+            }
+        });
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_softmax_scores_f32_cpu(const void* const* logits, const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                   int64_t num_classes, void* const* out, void*) {
+    SM::ProbLevels L;
+    if (int rc = SM::make_prob_levels(logits, out, level_n, level_hw, num_levels, num_images, num_classes, 4, &L)) return rc;
+    softmax_prob_rows(L, level_n, num_images, (int)num_classes + 1);
+    return SPH2POB_OK;
+}
+
+// stage 0 into buffers of its own, then the twin of the pipeline on them (the workspace is not used)
+int sph2pob_softmax_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                                   const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
+                                   int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
+                                   float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
+                                   int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
+    namespace GB = sph2pob_gb;
+    GB::Levels G;
+    const int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0, variant,
+                                   class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &G);
+    if (rc == SPH2POB_ERR_DIM || rc == SPH2POB_ERR_OPTION) return rc;
+    if (num_classes > SM::kMaxK - 1) return SPH2POB_ERR_SIZE;
+    if (rc) return rc;
+    if (!num_dets || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    SM::ProbLevels L;
+    std::vector<std::vector<float>> probs(num_levels);
+    const void* in[GB::kMaxLevels];
+    void* out[GB::kMaxLevels];
+    for (int l = 0; l < num_levels; l++) out[l] = const_cast<void*>(cls_scores[l]);   // (shapes first: nothing is sized before the checks)
+    if (int rc2 = SM::make_prob_levels(cls_scores, out, level_n, level_hw, num_levels, num_images, num_classes, 4, &L)) return rc2;
+    for (int l = 0; l < num_levels; l++) {
+        probs[l].resize((size_t)(num_images * level_n[l] * num_classes));
+        in[l] = L.lv[l].out = probs[l].data();
+    }
+    softmax_prob_rows(L, level_n, num_images, (int)num_classes + 1);
+    return sph2pob_test_bboxes_f32_cpu(in, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0, score_thr,
+                                       nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, class_agnostic, iou_threshold,
+                                       max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+}
+
+}  // extern "C"

@@ -61,6 +61,26 @@ struct Row {
     }
 };
 
+// ---- one row without a target: the probabilities an inference call selects on and reports (sph2pob_softmax_scores_f32,
+// sph2pob_softmax_bboxes_f32 and their twins) ------------------------------------------------------------------------------------
+// Row's m and e_j; S = sum_j (double)e_j over ALL classes in ascending class order (the maximum's own term is expf(0) = 1 exactly,
+// the 1 Row adds by hand); p_c = (float)((double)e_c / S).  This is Row's p_j = e_j * inv up to the last bit of the double
+// quotient (a divide here, Row's product with the reciprocal there) — far below the fp32 narrowing.  A -inf logit: e = 0, p = 0
+// exactly.  A NaN or +inf in the row (or no finite logit at all): x - m is NaN for it, S is NaN, every class of the row is NaN.
+// The walk belongs to the caller as for Row: see_max for every class, then see_sum for every class, then p(x) per class.
+struct Prob {
+    float m;
+    double s;
+    SPHF_DEV void begin() { m = -INFINITY; s = 0.0; }
+    SPHF_DEV void see_max(float x) { if (x > m) m = x; }
+    SPHF_DEV float e(float x) const { return expf(x - m); }
+    SPHF_DEV void add(float ej) { s += (double)ej; }
+    SPHF_DEV float of(float ej) const { return (float)((double)ej / s); }
+    // a caller that cannot keep e_j between the walks computes it twice (the same bits)
+    SPHF_DEV void see_sum(float x) { add(e(x)); }
+    SPHF_DEV float p(float x) const { return of(e(x)); }
+};
+
 // valid: 0 <= label < K and label != ignore_index; anything else has loss 0, gradient 0 and is neither positive nor negative
 SPHF_DEV bool valid_label(int64_t lab, int K, int64_t ignore_index) { return lab >= 0 && lab < (int64_t)K && lab != ignore_index; }
 // the row factor cw[label] * w of a valid row; the row loss is (CE * cw) * w and the gradient factor k0 * (cw * w)
@@ -195,6 +215,60 @@ inline int flat_check(int64_t n, int64_t K, int grad_stride) {
     if (grad_stride != 0 && grad_stride != 1) return SPH2POB_ERR_OPTION;
     if (n < 0 || K < kMinK || K > kMaxK || n > ((int64_t)1 << 38) / K) return SPH2POB_ERR_SIZE;
     return SPH2POB_OK;
+}
+
+// ---- the probability pass of inference: the level table of sph2pob_softmax_scores_f32 and of stage 0 of
+// sph2pob_softmax_bboxes_f32 --------------------------------------------------------------------------------------------------------
+// Input (B, A K, H, W) or (B, n, K), background last in each anchor's K; output fp32 in the same layout without it: (B, A C, H, W)
+// or (B, n, C), C = K - 1.  kind: how a thread's item maps onto memory
+//   PROB_NCHW4  four consecutive positions of one (b, a) per item: one vector access per class plane (H W % 4 == 0, aligned bases)
+//   PROB_NCHW1  one position per item
+//   PROB_FLAT   one row per item; K <= kHoldK: a workgroup's kBlock rows are one contiguous span, staged through LDS with
+//               coalesced loads and stores; above it every lane walks its own row in memory
+// K <= kHoldK: a row's logits are read once and held (registers, or the LDS stage); above it the three walks read them again.
+// The arithmetic is Prob's on either path: the same bits.
+constexpr int kHoldK = 40;
+enum { PROB_NCHW4 = 0, PROB_NCHW1 = 1, PROB_FLAT = 2 };
+struct ProbLevel {
+    const void* logits;    // float, or the 16-bit type of the _h16 entries
+    float* out;
+    int64_t items;         // work items of the level
+    int hw, a, kind;       // H W (0: flat); anchors per position
+    int block_off;         // first workgroup of the level
+};
+struct ProbLevels {
+    ProbLevel lv[kMaxLevels];
+    int num, blocks;
+};
+// Argument checks of sph2pob_softmax_scores_f32 / its twin, in the documented order; fills the table.  elem_bytes: 4, or 2 for
+// the 16-bit entries (a vector access of four logits is then 8 bytes)
+inline int make_prob_levels(const void* const* logits, void* const* out, const int64_t* level_n, const int64_t* level_hw, int num_levels,
+                            int64_t B, int64_t C, int elem_bytes, ProbLevels* res) {
+    const int64_t K = C + 1;
+    if (num_levels < 1 || num_levels > kMaxLevels || B < 0 || B > 65535 || C < kMinK - 1 || C > kMaxK - 1) return SPH2POB_ERR_SIZE;
+    if (!level_n || !logits || !out) return SPH2POB_ERR_NULL;
+    ProbLevels L{};
+    L.num = num_levels;
+    int64_t blocks = 0;
+    for (int l = 0; l < num_levels; l++) {
+        const int64_t n = level_n[l], hw = level_hw ? level_hw[l] : 0;
+        if (n < 0 || hw < 0 || (hw > 0 && n % hw != 0) || n > kMaxLevelElems / K || (B > 0 && n * K > kMaxLevelElems / B)) return SPH2POB_ERR_SIZE;
+        ProbLevel& d = L.lv[l];
+        d.logits = logits[l]; d.out = (float*)out[l];
+        if (B * n > 0 && (!d.logits || !d.out)) return SPH2POB_ERR_NULL;
+        d.hw = (int)hw; d.a = hw > 0 ? (int)(n / hw) : 1;
+        d.kind = hw == 0 ? PROB_FLAT : (hw % 4 == 0 && aligned_to(d.logits, 4 * elem_bytes) && aligned_to(d.out, 16)) ? PROB_NCHW4 : PROB_NCHW1;
+        d.items = d.kind == PROB_NCHW4 ? B * n / 4 : B * n;
+        d.block_off = (int)blocks;
+        blocks += (d.items + kBlock - 1) / kBlock;
+    }
+    L.blocks = (int)blocks;   // (every level holds fewer than 2^31 elements: fewer than 2^26 workgroups in all)
+    *res = L;
+    return SPH2POB_OK;
+}
+// the first logit of an NCHW item and of the probabilities it writes: position p of anchor (b, a) — class j lies j * hw further on
+SPHF_DEV void prob_nchw_span(int64_t ba, int64_t p, int hw, int K, int64_t* in, int64_t* out) {
+    *in = ba * K * hw + p; *out = ba * (K - 1) * hw + p;
 }
 
 }  // namespace sph2pob_softmax

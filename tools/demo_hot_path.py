@@ -13,7 +13,8 @@ Prints one JSON line with the stage times; `run()` is also used by tests/test_gp
 `sph_anchor_targets`: one call from the boxes to the loss's targets and a device `avg_factor`, no synchronisation — the
 sync-free one, and the one that captures into a hipGraph (tests/test_gpu_anchor_targets.py).  `run_batch_infer()` is the
 minibatch inference step built on `sph_get_bboxes`, from the head's NCHW outputs to padded detections, equally sync-free
-(tests/test_gpu_get_bboxes.py).
+(tests/test_gpu_get_bboxes.py); with `softmax_head=True` the head is a softmax one and the step is `sph_softmax_bboxes`
+(tests/test_gpu_softmax_bboxes.py).
 """
 import json
 import math
@@ -104,7 +105,7 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
-              train_cfg=None, loss_bbox=None):
+              train_cfg=None, loss_bbox=None, softmax_head=False):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -116,7 +117,9 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     reference's dict: its assigner with any SphOverlaps2D backend, pos_weight) the targets come from `sph_train_targets` under
     that configuration, still one call and no synchronisation.  `loss_bbox`: a Gaussian loss cfg such as
     dict(type='Sph2PobGDLoss', loss_type='kld', fun='log1p', tau=1.0) or dict(type='Sph2PobKFLoss') in place of CIoU; the regression
-    half then goes through `sph_gauss_bbox_loss` (its NCHW route is timed by `tools/bench_configs.py gauss_bbox_loss`)."""
+    half then goes through `sph_gauss_bbox_loss` (its NCHW route is timed by `tools/bench_configs.py gauss_bbox_loss`).
+    `softmax_head=True`: the head is a softmax one (`SphSSDHead`: K = num_classes + 1 logits per anchor, the background last) and
+    the classification loss is `sph_softmax_loss` with hard-negative mining (`neg_pos_ratio=3`) instead of the focal loss."""
     dev = 'cuda'
     if loss_bbox is not None and base_config:
         raise ValueError('base_config runs L1 on encoded deltas: no loss_bbox')
@@ -139,7 +142,8 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     deltas = (torch.randn((images * n, 4), generator=g) * 0.05).to(dev).requires_grad_(True)
     rois = anchors.repeat(images, 1)
     gd = torch.Generator(device=dev).manual_seed(seed)
-    cls_scores = [(torch.randn((images, 9 * num_classes, h, w), generator=gd, device=dev) * 2 - 4).requires_grad_(True) for h, w in LEVEL_SHAPES]
+    channels = num_classes + 1 if softmax_head else num_classes
+    cls_scores = [(torch.randn((images, 9 * channels, h, w), generator=gd, device=dev) * 2 - 4).requires_grad_(True) for h, w in LEVEL_SHAPES]
 
     def step():
         deltas.grad = None
@@ -163,7 +167,10 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
             pred = coder.decode(rois, deltas)
             loss = loss_iou(pred, t.bbox_targets.reshape(-1, 4), t.bbox_weights.reshape(-1, 4), avg_factor=t.avg_factor)
         # (the targets follow retina_anchors()' order, the logits the head's ((h W + w) A + a): a timing and plumbing demo)
-        loss_cls = S.sph_focal_loss(cls_scores, t.labels, t.label_weights, gamma=2.0, alpha=0.25, avg_factor=t.avg_factor)
+        if softmax_head:
+            loss_cls = S.sph_softmax_loss(cls_scores, t.labels, t.label_weights, neg_pos_ratio=3, avg_factor=t.avg_factor)
+        else:
+            loss_cls = S.sph_focal_loss(cls_scores, t.labels, t.label_weights, gamma=2.0, alpha=0.25, avg_factor=t.avg_factor)
         (loss + loss_cls).backward()
         return loss.detach(), loss_cls.detach(), t
     step()
@@ -175,9 +182,9 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     out = {'anchors': n, 'images': images, 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
            'loss': float(loss), 'loss_cls': float(loss_cls), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()),
            'cls_grad_finite': all(bool(torch.isfinite(c.grad).all()) for c in cls_scores), 'backend': backend, 'fused_reg': fused_reg,
-           'base_config': base_config, 'loss_bbox': loss_bbox['type'] if loss_bbox is not None else 'Sph2PobIoULoss',
+           'base_config': base_config, 'softmax_head': softmax_head, 'loss_bbox': loss_bbox['type'] if loss_bbox is not None else 'Sph2PobIoULoss',
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
-    return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels)
+    return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels, cls_scores=cls_scores)
 
 
 LEVEL_SHAPES = ((64, 128), (32, 64), (16, 32), (8, 16), (4, 8))   # the 512 x 1024 ERP at strides 8 ... 128
@@ -203,21 +210,59 @@ def head_outputs(images=8, num_classes=37, dim=4, seed=0, device='cuda', sparse=
     return cls, box
 
 
+def softmax_head_outputs(images=8, num_classes=37, dim=4, seed=0, device='cuda', shapes=LEVEL_SHAPES, anchors_per_position=9, dtype=torch.float32):
+    """Synthetic outputs of a softmax head (use_sigmoid_cls=False) in the head's NCHW: K = num_classes + 1 logits per anchor, the
+    background last at 0, the foreground N(-3, 2) (a few percent of the probabilities above 0.05: far more than nms_pre on the
+    large levels), every anchor's logits shifted together by up to +-60 as an unnormalised head's are; small deltas.
+    `anchors_per_position`: one number, or one per level."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    K = num_classes + 1
+    per = anchors_per_position if isinstance(anchors_per_position, (tuple, list)) else (anchors_per_position,) * len(shapes)
+    cls, box = [], []
+    for (h, w), a in zip(shapes, per):
+        x = torch.randn((images, a, K, h, w), generator=g, device=device) * 2 - 3
+        x[:, :, -1] = 0
+        x += (torch.rand((images, a, 1, h, w), generator=g, device=device) * 2 - 1) * 60
+        cls.append(x.reshape(images, a * K, h, w).to(dtype))
+        box.append((torch.randn((images, a * dim, h, w), generator=g, device=device) * 0.5).to(dtype))
+    return cls, box
+
+
+SSD300_SHAPES = ((38, 38), (19, 19), (10, 10), (5, 5), (3, 3), (1, 1))   # SSD300's six feature maps
+SSD300_ANCHORS = (4, 6, 6, 6, 4, 4)                                      # 8 732 anchors in all
+
+
+def ssd300_level_anchors(device='cuda', seed=0):
+    """8 732 BFoV anchors in SSD300's level shapes, spread over the sphere (a timing and plumbing scene, not SSD's own grid)."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for (h, w), a in zip(SSD300_SHAPES, SSD300_ANCHORS):
+        u = torch.rand((h * w * a, 4), generator=g)
+        out.append(torch.stack([u[:, 0] * 360, 40 + u[:, 1] * 100, 10 + u[:, 2] * 50, 10 + u[:, 3] * 50], 1).contiguous().to(device))
+    return out
+
+
 PANDORA_TEST_CFG = dict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100,
                         iou_calculator='unbiased_iou', box_formator='sph2pix')   # sph_retinanet_r50_fpn_120e_pandora.py
 
 
-def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None):
+def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None, softmax_head=False):
     """The inference half of `run()` for a minibatch (SphRetinaHead.get_bboxes over the images): the head's per-level NCHW scores
     and deltas -> sph_get_bboxes (per-level top-k, decode, NMS, max_per_img) -> padded detections, no synchronisation.  With a
-    `test_cfg` (the reference's dict, e.g. PANDORA_TEST_CFG) the step is sph_test_bboxes under that configuration."""
+    `test_cfg` (the reference's dict, e.g. PANDORA_TEST_CFG) the step is sph_test_bboxes under that configuration.
+    `softmax_head=True`: the head is a softmax one (K = num_classes + 1 logits per anchor, the background last) and the step is
+    sph_softmax_bboxes under `test_cfg` (the default configuration without one)."""
     anchors = retina_level_anchors()
-    cls, box = head_outputs(images, num_classes, seed=seed)
+    cls, box = softmax_head_outputs(images, num_classes, seed=seed) if softmax_head else head_outputs(images, num_classes, seed=seed)
     coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
     if test_cfg is not None:
         nms_calculator = test_cfg.get('iou_calculator', nms_calculator)
 
     def step():
+        if softmax_head:
+            cfg = test_cfg if test_cfg is not None else dict(score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100,
+                                                             iou_calculator=nms_calculator)
+            return S.sph_softmax_bboxes(cls, box, anchors, bbox_coder=coder, test_cfg=cfg, box_version=4)
         if test_cfg is not None:
             return S.sph_test_bboxes(cls, box, anchors, bbox_coder=coder, test_cfg=test_cfg, box_version=4, activation='none')
         return S.sph_get_bboxes(cls, box, anchors, bbox_coder=coder, score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5),
@@ -229,7 +274,7 @@ def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient'
         r = step()
     torch.cuda.synchronize()
     out = {'anchors': sum(a.size(0) for a in anchors), 'images': images, 'num_dets': r.num_dets.tolist(), 'dets': tuple(r.dets.shape),
-           'nms': nms_calculator, 'get_bboxes_ms': (time.perf_counter() - t0) / reps * 1e3}
+           'nms': nms_calculator, 'softmax_head': softmax_head, 'get_bboxes_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(result=r, cls_scores=cls, bbox_preds=box, anchors=anchors, coder=coder)
 
 
@@ -241,3 +286,4 @@ if __name__ == '__main__':
     print(json.dumps(run_batch(reps=5)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG)[0]), flush=True)
+    print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, softmax_head=True)[0]), flush=True)
