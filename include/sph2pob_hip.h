@@ -851,6 +851,47 @@ int sph2pob_softmax_bboxes_h16(const void* const* cls_scores, const void* const*
                                int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
                                int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream);
 
+/*
+ * sph2pob_sample_targets_f32 — random sampling of the anchor targets of a minibatch: mmdet's RandomSampler as the reference's
+ * SphRandomSampler calls it (sphdet/bbox/sampler/sph_random_sampler.py:34-46 over mmdet/core/bbox/samplers/random_sampler.py,
+ * add_gt_as_proposals=False) and the target lines of AnchorHead._get_targets_single with a real sampler (anchor_head.py:254-299),
+ * applied to what sph2pob_anchor_targets_f32 wrote.  Two launches whatever B is, nothing read back to the host.
+ *   assigned_gt_inds (B, n) int64     > 0 positive, == 0 negative, < 0 ignored, as sph2pob_anchor_targets_f32 writes it
+ *   labels_in, label_weights_in (B, n), bbox_targets_in, bbox_weights_in (B, n, box_dim): the targets of the same call
+ *   num_expected_pos = (int)(num * pos_fraction), computed by the caller; num; neg_pos_ub (< 0: none)
+ * Per image b, with P_b / N_b the positive / negative rows, COUNTED by the kernel from assigned_gt_inds:
+ *   k_pos = min(P_b, num_expected_pos);  k_neg = min(N_b, num - k_pos), and with neg_pos_ub >= 0 additionally at most
+ *   (int64)(neg_pos_ub * (double)max(1, k_pos))
+ *   rank(b, i) = word 0 of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with key
+ *   (seed & 0xffffffff, seed >> 32) and counter (i, b, 0, 0); an all-zero counter and key give 6627e8d5 e169c58d bc57ac4c
+ *   9b00dbd8, all-ones give 408f276d 41c83b0e a20bc7c6 6d5451fd.  `ranks` (B, n) uint32, when non-NULL, replaces the generator
+ *   (only the words of positive and negative rows are read)
+ *   the sampled positives are the k_pos positive rows with the smallest (rank, i) — ties by ascending row index — and the sampled
+ *   negatives the k_neg negative rows chosen likewise: a uniform k-subset up to rank ties (two of m rows tie with probability
+ *   ~m^2 / 2^33), NOT the stream of torch.randperm, which no device implementation reproduces
+ *   seed         a host int64, or — when seed_device is non-NULL, which then wins — one int64 ON THE DEVICE read by the kernels: a
+ *                captured graph draws a fresh sample on every replay once the caller changes that word
+ * Outputs (the four target pointers may EQUAL their inputs: the in-place form, which writes only the rows that leave the sample;
+ * an output that overlaps an input in any other way is not supported):
+ *   labels / label_weights / bbox_targets / bbox_weights   a sampled or ignored row keeps its input; a positive or negative row
+ *                                     that is not sampled gets labels = num_classes, label_weights = 0, bbox_targets = 0, bbox_weights = 0
+ *   sample_flags  (B, n) uint8        0: not sampled, 1: sampled positive, 2: sampled negative
+ *   num_pos, num_neg (B) int64        k_pos, k_neg
+ *   avg_factor      (1) f32           sum_b max(k_pos, 1) + sum_b max(k_neg, 1): mmdet's num_total_samples of a sampling head
+ *   avg_factor_pos  (1) f32           sum_b max(k_pos, 1)
+ *   workspace     sph2pob_sample_targets_workspace_bytes(num_images, n) bytes of scratch, no initialisation (0 for sizes the entry refuses)
+ * Errors, checked in this order before anything is enqueued: box_dim -> SPH2POB_ERR_DIM; a NaN neg_pos_ub -> SPH2POB_ERR_OPTION;
+ * num_images outside [1, 65 535], n outside [1, 2^31), num < 1, num_expected_pos outside [0, num] -> SPH2POB_ERR_SIZE; a NULL
+ * input, output or workspace (seed_device and ranks may be NULL) -> SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_sample_targets_workspace_bytes(int64_t num_images, int64_t n);
+int sph2pob_sample_targets_f32(const int64_t* assigned_gt_inds, int64_t num_images, int64_t n, int box_dim, const int64_t* labels_in,
+                               const float* label_weights_in, const float* bbox_targets_in, const float* bbox_weights_in,
+                               int64_t num_classes, int64_t num_expected_pos, int64_t num, double neg_pos_ub, int64_t seed,
+                               const int64_t* seed_device, const uint32_t* ranks, int64_t* labels, float* label_weights,
+                               float* bbox_targets, float* bbox_weights, unsigned char* sample_flags, int64_t* num_pos, int64_t* num_neg,
+                               float* avg_factor, float* avg_factor_pos, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ from ... import _torch_glue as G
 from .max_iou_assigner import AssignResult, _thresholds
 
 _PER_IMAGE = 'use the per-image API (SphMaxIoUAssigner.assign on each image, then the target lines of _get_targets_single)'
+_OR_SAMPLE = '; for RandomSampler with add_gt_as_proposals=False, sph_rpn_targets / sph_sample_targets sample these targets on the device'
 
 
 class AnchorTargets:
@@ -96,7 +97,7 @@ def sph_anchor_targets(anchors, gt_bboxes, gt_labels=None, gt_offsets=None, *, a
     sampler_type = sampler.get('type') if isinstance(sampler, dict) else (None if sampler is None else type(sampler).__name__)
     if sampler_type not in (None, 'PseudoSampler'):
         raise NotImplementedError(f'sph_anchor_targets implements PseudoSampler only, not {sampler_type} (it draws on the host): '
-                                  + _PER_IMAGE)
+                                  + _PER_IMAGE + _OR_SAMPLE)
     if getattr(assigner, 'gpu_assign_thr', -1) > 0:
         raise NotImplementedError('sph_anchor_targets does not move assignments to the CPU (gpu_assign_thr): ' + _PER_IMAGE)
     variant = batched_variant(assigner, anchors)

@@ -14,7 +14,7 @@ function the pairwise kernel runs for it, so each image's result equals `SphMaxI
 `_get_targets_single` on that image bit for bit.  CPU tensors go to the host twin.
 """
 from ... import _torch_glue as G
-from .anchor_targets import _PER_IMAGE, _batched_call, sph_anchor_targets
+from .anchor_targets import _OR_SAMPLE, _PER_IMAGE, _batched_call, sph_anchor_targets
 from .max_iou_assigner import _FUSED_BACKENDS, SphMaxIoUAssigner
 
 _TRAIN_CFG_KEYS = ('assigner', 'sampler', 'allowed_border', 'pos_weight', 'debug')
@@ -102,7 +102,7 @@ def sph_train_targets(anchors, gt_bboxes, gt_labels=None, gt_offsets=None, *, tr
     sampler = cfg.get('sampler')
     sampler_type = sampler.get('type') if isinstance(sampler, dict) else (None if sampler is None else type(sampler).__name__)
     if sampler_type not in (None, 'PseudoSampler'):
-        raise NotImplementedError(f'{_WHO} implements PseudoSampler only, not {sampler_type} (it draws on the host): ' + _PER_IMAGE)
+        raise NotImplementedError(f'{_WHO} implements PseudoSampler only, not {sampler_type} (it draws on the host): ' + _PER_IMAGE + _OR_SAMPLE)
     if assigner.gpu_assign_thr > 0:
         raise NotImplementedError(f'{_WHO} does not move assignments to the CPU (gpu_assign_thr): ' + _PER_IMAGE)
     if calc.backend not in _PER_PAIR_BACKENDS:

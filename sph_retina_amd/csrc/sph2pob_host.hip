@@ -32,6 +32,7 @@
 #include "sph2pob_gauss_bbox_loss.hpp"
 #include "sph2pob_delta_loss.hpp"
 #include "sph2pob_softmax.hpp"
+#include "sph2pob_sample.hpp"
 
 namespace {
 
@@ -1179,6 +1180,75 @@ int sph2pob_softmax_bboxes_f32_cpu(const void* const* cls_scores, const void* co
     return sph2pob_test_bboxes_f32_cpu(in, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0, score_thr,
                                        nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, class_agnostic, iou_threshold,
                                        max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+}
+
+}  // extern "C"
+
+// ---- random sampling of anchor targets: the rank, the sizes and the selection rule of the kernels (sph2pob_sample.hpp); the k-th
+// smallest (rank, row) by std::nth_element instead of the radix select (the workspace is not used) ----
+extern "C" {
+
+int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, int64_t n, int box_dim, const int64_t* labels_in,
+                                   const float* label_weights_in, const float* bbox_targets_in, const float* bbox_weights_in,
+                                   int64_t num_classes, int64_t num_expected_pos, int64_t num, double neg_pos_ub, int64_t seed,
+                                   const int64_t* seed_device, const uint32_t* ranks, int64_t* labels, float* label_weights,
+                                   float* bbox_targets, float* bbox_weights, unsigned char* sample_flags, int64_t* num_pos, int64_t* num_neg,
+                                   float* avg_factor, float* avg_factor_pos, void*, void*) {
+    namespace SA = sph2pob_sample;
+    if (int rc = SA::check_shape(num_images, n, box_dim, num_expected_pos, num, neg_pos_ub)) return rc;
+    if (!gt_inds || !labels_in || !label_weights_in || !bbox_targets_in || !bbox_weights_in || !labels || !label_weights || !bbox_targets ||
+        !bbox_weights || !sample_flags || !num_pos || !num_neg || !avg_factor || !avg_factor_pos) return SPH2POB_ERR_NULL;
+    const uint64_t sd = (uint64_t)(seed_device ? seed_device[0] : seed);
+    parallel_for(num_images, 1, [&](int64_t lo, int64_t hi) {
+        std::vector<uint32_t> rank((size_t)n);
+        std::vector<uint64_t> order;   // (rank, row) of one side's rows
+        for (int64_t b = lo; b < hi; b++) {
+            const int64_t* g = gt_inds + b * n;
+            int64_t count[2] = {0, 0}, k[2];
+            for (int64_t i = 0; i < n; i++) {
+                const int c = SA::side_of(g[i]);
+                if (c == SA::IGNORED) continue;
+                count[c]++;
+                rank[(size_t)i] = ranks ? ranks[b * n + i] : SA::row_rank(sd, (uint32_t)b, (uint32_t)i);
+            }
+            SA::sample_sizes(count[SA::POS], count[SA::NEG], num_expected_pos, num, neg_pos_ub, &k[SA::POS], &k[SA::NEG]);
+            SA::Pick pick[2];
+            for (int side = 0; side < 2; side++) {
+                pick[side] = SA::Pick{0u, 0, k[side]};
+                if (k[side] == 0) continue;
+                order.clear();
+                for (int64_t i = 0; i < n; i++) if (SA::side_of(g[i]) == side) order.push_back((uint64_t)rank[(size_t)i] << 32 | (uint64_t)i);
+                std::nth_element(order.begin(), order.begin() + (k[side] - 1), order.end());
+                const uint64_t kth = order[(size_t)(k[side] - 1)];
+                pick[side].key = (uint32_t)(kth >> 32);
+                pick[side].upto = (int32_t)((kth & 0xffffffffu) + 1);
+            }
+            num_pos[b] = k[SA::POS]; num_neg[b] = k[SA::NEG];
+            for (int64_t i = 0; i < n; i++) {
+                const int64_t r = b * n + i;
+                const int c = SA::side_of(g[i]);
+                const bool in = c != SA::IGNORED && SA::sampled(rank[(size_t)i], i, pick[c]);
+                sample_flags[r] = in ? (unsigned char)(c + 1) : (unsigned char)0;
+                if (in || c == SA::IGNORED) {   // the row keeps its targets
+                    if (labels != labels_in) labels[r] = labels_in[r];
+                    if (label_weights != label_weights_in) label_weights[r] = label_weights_in[r];
+                    for (int d = 0; d < box_dim; d++) {
+                        if (bbox_targets != bbox_targets_in) bbox_targets[r * box_dim + d] = bbox_targets_in[r * box_dim + d];
+                        if (bbox_weights != bbox_weights_in) bbox_weights[r * box_dim + d] = bbox_weights_in[r * box_dim + d];
+                    }
+                } else {
+                    labels[r] = num_classes;
+                    label_weights[r] = 0.0f;
+                    for (int d = 0; d < box_dim; d++) { bbox_targets[r * box_dim + d] = 0.0f; bbox_weights[r * box_dim + d] = 0.0f; }
+                }
+            }
+        }
+    });
+    int64_t sp = 0, sn = 0;
+    for (int64_t b = 0; b < num_images; b++) { sp += std::max<int64_t>(num_pos[b], 1); sn += std::max<int64_t>(num_neg[b], 1); }
+    avg_factor[0] = (float)(sp + sn);
+    avg_factor_pos[0] = (float)sp;
+    return SPH2POB_OK;
 }
 
 }  // extern "C"

@@ -105,7 +105,7 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
-              train_cfg=None, loss_bbox=None, softmax_head=False):
+              train_cfg=None, loss_bbox=None, softmax_head=False, rpn_cfg=None, rpn_seed=0):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -119,10 +119,18 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     dict(type='Sph2PobGDLoss', loss_type='kld', fun='log1p', tau=1.0) or dict(type='Sph2PobKFLoss') in place of CIoU; the regression
     half then goes through `sph_gauss_bbox_loss` (its NCHW route is timed by `tools/bench_configs.py gauss_bbox_loss`).
     `softmax_head=True`: the head is a softmax one (`SphSSDHead`: K = num_classes + 1 logits per anchor, the background last) and
-    the classification loss is `sph_softmax_loss` with hard-negative mining (`neg_pos_ratio=3`) instead of the focal loss."""
+    the classification loss is `sph_softmax_loss` with hard-negative mining (`neg_pos_ratio=3`) instead of the focal loss.
+    `rpn_cfg`: an RPN `train_cfg` with its RandomSampler (and nothing else of the above); the step is then an RPN training step,
+    `sph_rpn_targets` (assignment + sampling on the device, `rpn_seed` a Python int or a () int64 device tensor) -> `sph_softmax_loss`
+    on K = 2 logits per anchor without mining and `sph_delta_loss` on the encoded targets: the sampled `label_weights` and the device
+    `avg_factor` (the sampled count) feed the fused losses as they stand."""
     dev = 'cuda'
     if loss_bbox is not None and base_config:
         raise ValueError('base_config runs L1 on encoded deltas: no loss_bbox')
+    if rpn_cfg is not None:
+        if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head:
+            raise ValueError('rpn_cfg is a step of its own: sph_rpn_targets + sph_softmax_loss (K = 2) + sph_delta_loss')
+        train_cfg, num_classes = rpn_cfg, 1
     g = torch.Generator().manual_seed(seed)
     anchors = retina_anchors()
     n, images = anchors.size(0), len(counts)
@@ -142,13 +150,19 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     deltas = (torch.randn((images * n, 4), generator=g) * 0.05).to(dev).requires_grad_(True)
     rois = anchors.repeat(images, 1)
     gd = torch.Generator(device=dev).manual_seed(seed)
-    channels = num_classes + 1 if softmax_head else num_classes
+    channels = num_classes + 1 if softmax_head or rpn_cfg is not None else num_classes
     cls_scores = [(torch.randn((images, 9 * channels, h, w), generator=gd, device=dev) * 2 - 4).requires_grad_(True) for h, w in LEVEL_SHAPES]
 
     def step():
         deltas.grad = None
         for c in cls_scores:
             c.grad = None
+        if rpn_cfg is not None:
+            t = S.sph_rpn_targets(anchors, gts, train_cfg=rpn_cfg, num_classes=1, seed=rpn_seed, reg_decoded_bbox=False, bbox_coder=coder)
+            loss = S.sph_delta_loss([deltas.view(images, n, 4)], t.bbox_targets, t.bbox_weights, avg_factor=t.avg_factor)
+            loss_cls = S.sph_softmax_loss(cls_scores, t.labels, t.label_weights, avg_factor=t.avg_factor)
+            (loss + loss_cls).backward()
+            return loss.detach(), loss_cls.detach(), t
         if train_cfg is not None:
             t = S.sph_train_targets(anchors, gts, labels, train_cfg=train_cfg, num_classes=num_classes, reg_decoded_bbox=not base_config,
                                     bbox_coder=coder if base_config else None)
@@ -182,7 +196,7 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     out = {'anchors': n, 'images': images, 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
            'loss': float(loss), 'loss_cls': float(loss_cls), 'grad_nonzero_rows': int((deltas.grad.abs().sum(1) > 0).sum()),
            'cls_grad_finite': all(bool(torch.isfinite(c.grad).all()) for c in cls_scores), 'backend': backend, 'fused_reg': fused_reg,
-           'base_config': base_config, 'softmax_head': softmax_head, 'loss_bbox': loss_bbox['type'] if loss_bbox is not None else 'Sph2PobIoULoss',
+           'base_config': base_config, 'softmax_head': softmax_head, 'rpn': rpn_cfg is not None, 'num_neg': t.num_neg.tolist(), 'loss_bbox': loss_bbox['type'] if loss_bbox is not None else 'L1Loss' if rpn_cfg is not None else 'Sph2PobIoULoss',
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(targets=t, deltas=deltas, anchors=anchors, gts=gts, labels=labels, cls_scores=cls_scores)
 
