@@ -49,7 +49,7 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_softmax_loss_fwd_f32', 'sph2pob_softmax_loss_bwd_f32', 'sph2pob_softmax_scores_f32', 'sph2pob_softmax_bboxes_f32',
               'sph2pob_sample_targets_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp', 'sph2pob_gauss_bbox_loss.hpp', 'sph2pob_softmax.hpp', 'sph2pob_sample.hpp',
-           'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
+           'sph2pob_class_levels.hpp', 'sph2pob_select.hpp', 'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
 # half the rate of plain VALU on gfx950 (tools/ubench/valu_rate2.hip), measured 12 % slower on the dominant kernel
 # -amdgpu-kernarg-preload-count: gfx950 hands the first kernel arguments to a wave in SGPRs at launch instead of making

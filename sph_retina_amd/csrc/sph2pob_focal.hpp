@@ -1,6 +1,7 @@
 // Sigmoid focal loss (mmdet/models/losses/focal_loss.py:12-57, the op the reference takes from mmcv.ops.sigmoid_focal_loss): the
-// per-element arithmetic, the level table and the argument checks, shared by the kernels (sph2pob_focal.hip) and their CPU twins
-// (sph2pob_host.hip) so that a CPU tensor gets the arithmetic and the checks a device tensor gets.
+// per-element arithmetic and the argument checks (the level table: sph2pob_class_levels.hpp), shared by the kernels
+// (sph2pob_focal.hip) and their CPU twins (sph2pob_host.hip) so that a CPU tensor gets the arithmetic and the checks a device
+// tensor gets.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -8,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/sph2pob_hip.h"
+#include "sph2pob_class_levels.hpp"
 #include "sph2pob_head_loss.hpp"
 
 namespace sph2pob_focal {
@@ -16,8 +18,6 @@ using sph2pob_head::aligned_to;
 using sph2pob_head::effective_scale;
 using sph2pob_head::kBlock;
 using sph2pob_head::kMaxLevels;
-
-constexpr int64_t kMaxLevelElems = ((int64_t)1 << 31) - 4096;   // elements of one level: 32-bit item indices inside a level
 
 // gamma split once on the host: q^gamma = q^gint * exp2(gfrac * log2 q), gint = min(floor(gamma), 8) exact multiplications (an
 // integer gamma never meets log2 / exp2, whose absolute error in the exponent grows with gamma * |log2 q|).  mode: 2 and 0 are
@@ -66,68 +66,15 @@ SPHF_DEV void element(float x, bool t, const Params& P, float& loss, float& dx) 
     dx = t ? -dz : dz;
 }
 
-// One level of one call.  kind: how a thread's item maps onto memory
-//   0  NCHW (B, A C, H, W), four consecutive positions p = h W + w of one (b, a) per item: 16-byte accesses at stride H W over the classes
-//   1  NCHW, one position per item (H W % 4 != 0 or a base that is not 16-byte aligned)
-//   2  flat (B, n_l, C), four consecutive elements per item
-//   3  flat, one element per item
-enum { KIND_NCHW4 = 0, KIND_NCHW1 = 1, KIND_FLAT4 = 2, KIND_FLAT1 = 3 };
-struct Level {
-    const float* logits;
-    float* grad;           // laid out like logits; NULL in a forward-only call
-    int n, hw, a, kind;    // anchors of the level; H W (0: flat); anchors per position
-    int items;             // work items of the level
-    int block_off;         // first workgroup of the level
-    int64_t row_off;       // index of the level's first anchor inside an image's n rows
-};
-struct Levels {
-    Level lv[kMaxLevels];
-    int num, blocks;       // levels; workgroups of the whole call
-    int64_t n_total;       // anchors of one image, all levels
-    int64_t elems;         // B n C
-};
-
-// Argument checks of sph2pob_focal_loss_sum_f32 / its twin, in the documented order; fills the table.  `tables` false: shapes
-// only (the workspace size), every level counted with its scalar kind (an upper bound on the workgroups).  `vec_bytes`: the
-// alignment the vector kinds need — four elements: 16 for fp32 levels, 8 for the 16-bit levels of sph2pob_focal_loss_sum_h16,
-// whose pointers the table keeps as float* all the same (sph2pob_head_loss.hpp, level_ptr).
+// The level table: Level, Levels and the KIND_* of sph2pob_class_levels.hpp; a FLAT4 item is four consecutive elements, a FLAT1
+// item one element.  Argument checks of sph2pob_focal_loss_sum_f32 / its twin, in the documented order: the options here, sizes
+// and pointers in the shared walk, which fills the table (`tables`, `vec_bytes`: there)
+using namespace sph2pob_class;
+constexpr Family kFamily{1, (int64_t)1 << 24, false, INT64_MAX};
 inline int make_levels(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw, int num_levels,
                        int64_t B, int64_t C, int weight_mode, float gamma, bool tables, Levels* out, int vec_bytes = 16) {
     if (!(gamma >= 0.0f) || weight_mode < 0 || weight_mode > 2) return SPH2POB_ERR_OPTION;
-    if (num_levels < 1 || num_levels > kMaxLevels || B < 0 || B > 65535 || C <= 0 || C > ((int64_t)1 << 24)) return SPH2POB_ERR_SIZE;
-    if (!level_n || (tables && !logits)) return SPH2POB_ERR_NULL;
-    Levels L{};
-    L.num = num_levels;
-    int64_t blocks = 0, rows = 0;
-    for (int l = 0; l < num_levels; l++) {
-        const int64_t n = level_n[l], hw = level_hw ? level_hw[l] : 0;
-        if (n < 0 || hw < 0 || (hw > 0 && n % hw != 0) || n > kMaxLevelElems / C || (B > 0 && n * C > kMaxLevelElems / B)) return SPH2POB_ERR_SIZE;
-        const int64_t elems = B * n * C;
-        Level& d = L.lv[l];
-        d.n = (int)n; d.hw = (int)hw; d.a = hw > 0 ? (int)(n / hw) : 1;
-        d.logits = tables ? (const float*)logits[l] : nullptr;
-        d.grad = tables && grads ? (float*)grads[l] : nullptr;
-        if (tables && elems > 0 && (!d.logits || (grads && !d.grad))) return SPH2POB_ERR_NULL;
-        const bool al = tables && aligned_to(d.logits, vec_bytes) && aligned_to(d.grad, vec_bytes);
-        int64_t items;
-        if (hw > 0) {
-            d.kind = al && hw % 4 == 0 ? KIND_NCHW4 : KIND_NCHW1;
-            items = d.kind == KIND_NCHW4 ? B * n / 4 : B * n;
-        } else {
-            d.kind = al && elems % 4 == 0 ? KIND_FLAT4 : KIND_FLAT1;
-            items = d.kind == KIND_FLAT4 ? elems / 4 : elems;
-        }
-        d.items = (int)items;
-        d.block_off = (int)blocks;
-        d.row_off = rows;
-        blocks += (items + kBlock - 1) / kBlock;
-        rows += n;
-        L.elems += elems;
-        if (blocks >= ((int64_t)1 << 31) - 1) return SPH2POB_ERR_SIZE;
-    }
-    L.blocks = (int)blocks; L.n_total = rows;
-    *out = L;
-    return SPH2POB_OK;
+    return walk_levels(kFamily, logits, grads, level_n, level_hw, num_levels, B, C, tables, vec_bytes, out);
 }
 
 // flat (N, C) entries: weight_mode, gamma, grad_stride -> OPTION; n < 0, C <= 0, N C too large -> SIZE

@@ -773,12 +773,7 @@ int sph2pob_focal_loss_sum_f32_cpu(const void* const* logits, void* const* grads
     const int64_t rows = L.elems > 0 ? num_images * L.n_total : 0, C = num_classes;
     const double total = head_rows_sum(L, rows, [&](const FL::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
         int64_t base, stride;   // element (row, c) = base + c * stride
-        if (lv.hw > 0) {
-            const int64_t p = i / lv.a, a = i - p * lv.a;
-            base = (b * lv.a + a) * C * lv.hw + p; stride = lv.hw;
-        } else {
-            base = (b * lv.n + i) * C; stride = 1;
-        }
+        sph2pob_class::class_row_span(lv, C, b, i, &base, &stride);
         const int64_t lab = labels[row];
         for (int c = 0; c < (int)C; c++) {
             float loss, dx;
@@ -970,19 +965,11 @@ int sph2pob_delta_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* g
 
 }  // extern "C"
 
-// ---- softmax cross-entropy, plain and mined: the twins of sph2pob_softmax.hip on the Row, the keys and the cut of sph2pob_softmax.hpp ----
+// ---- softmax cross-entropy, plain and mined: the twins of sph2pob_softmax.hip on the Row and the keys of sph2pob_softmax.hpp; the
+// cut of an image by sph2pob_select.hpp's host_cut ----
 namespace {
 namespace SM = sph2pob_softmax;
 
-// element (row, c) of a level = base + c * stride
-inline void softmax_row_span(const SM::Level& lv, int64_t K, int64_t b, int64_t i, int64_t* base, int64_t* stride) {
-    if (lv.hw > 0) {
-        const int64_t p = i / lv.a, a = i - p * lv.a;
-        *base = (b * lv.a + a) * K * lv.hw + p; *stride = lv.hw;
-    } else {
-        *base = (b * lv.n + i) * K; *stride = 1;
-    }
-}
 // the three walks of one valid row: its cross-entropy, and (g != NULL) g[c * stride] = kw * d CE / d x_c
 inline float softmax_row(const float* x, float* g, int64_t stride, int K, int64_t lab, float kw) {
     SM::Row r;
@@ -1017,7 +1004,7 @@ int sph2pob_softmax_loss_sum_f32_cpu(const void* const* logits, void* const* gra
     // first pass: plain — losses and gradients; mining — keys and the positives' losses
     double total = head_rows_sum(L, L.rows, [&](const SM::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
         int64_t base, stride;
-        softmax_row_span(lv, K, b, i, &base, &stride);
+        sph2pob_class::class_row_span(lv, K, b, i, &base, &stride);
         const int64_t lab = labels[row];
         float* g = !mining && lv.grad ? lv.grad + base : nullptr;
         if (!SM::valid_label(lab, K, ignore_index)) {
@@ -1034,27 +1021,18 @@ int sph2pob_softmax_loss_sum_f32_cpu(const void* const* logits, void* const* gra
     if (mining) {
         // the cut of every image: the k_b-th largest negative key, the rows tied at it taken in index order
         std::vector<SM::Cut> cuts((size_t)num_images);
+        std::vector<uint32_t> scratch;
         for (int64_t b = 0; b < (L.rows > 0 ? num_images : 0); b++) {
             const unsigned* kb = keys.data() + b * n;
-            std::vector<unsigned> neg;
-            int64_t pos = 0;
-            for (int64_t j = 0; j < n; j++) {
-                if (kb[j] == SM::kKeyPos) pos++;
-                else if (kb[j] >= 2u) neg.push_back(kb[j]);
-            }
-            const int64_t k = SM::mined_count(neg_pos_ratio, pos, (int64_t)neg.size());
+            int64_t pos = 0, neg = 0;
+            for (int64_t j = 0; j < n; j++) { pos += kb[j] == SM::kKeyPos; neg += kb[j] >= 2u; }
+            const int64_t k = SM::mined_count(neg_pos_ratio, pos, neg);
             SM::Cut c{SM::kKeyNaN, 0};
             double sum = 0.0;
             if (k > 0) {
-                std::nth_element(neg.begin(), neg.begin() + (k - 1), neg.end(), [](unsigned x, unsigned y) { return x > y; });
-                c.key = neg[(size_t)(k - 1)];
-                int64_t above = 0;
+                const int64_t take = sph2pob_select::host_cut<true>(n, k, [&](int64_t j, uint32_t* key) { *key = kb[j]; return kb[j] >= 2u; }, scratch, &c);
                 for (int64_t j = 0; j < n; j++)
-                    if (kb[j] >= 2u && kb[j] > c.key) { above++; sum += (double)SM::key_loss(kb[j]); }
-                const int64_t take = k - above;
-                int64_t seen = 0;
-                for (int64_t j = 0; j < n && seen < take; j++)
-                    if (kb[j] == c.key && ++seen == take) c.upto = (int)(j + 1);
+                    if (kb[j] >= 2u && kb[j] > c.key) sum += (double)SM::key_loss(kb[j]);
                 sum += (double)take * (double)SM::key_loss(c.key);
             }
             cuts[(size_t)b] = c;
@@ -1063,7 +1041,7 @@ int sph2pob_softmax_loss_sum_f32_cpu(const void* const* logits, void* const* gra
         if (grads)
             head_rows_sum(L, L.rows, [&](const SM::Level& lv, int64_t b, int64_t i, int64_t row, double&) {
                 int64_t base, stride;
-                softmax_row_span(lv, K, b, i, &base, &stride);
+                sph2pob_class::class_row_span(lv, K, b, i, &base, &stride);
                 const unsigned key = keys[(size_t)row];
                 if (key == SM::kKeyPos || SM::mined(key, (int)(row - b * n), cuts[(size_t)b])) {
                     const int64_t lab = labels[row];
@@ -1184,8 +1162,8 @@ int sph2pob_softmax_bboxes_f32_cpu(const void* const* cls_scores, const void* co
 
 }  // extern "C"
 
-// ---- random sampling of anchor targets: the rank, the sizes and the selection rule of the kernels (sph2pob_sample.hpp); the k-th
-// smallest (rank, row) by std::nth_element instead of the radix select (the workspace is not used) ----
+// ---- random sampling of anchor targets: the rank and the sizes of the kernels (sph2pob_sample.hpp); the cut of a side by
+// sph2pob_select.hpp's host_cut instead of the radix select (the workspace is not used) ----
 extern "C" {
 
 int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, int64_t n, int box_dim, const int64_t* labels_in,
@@ -1201,7 +1179,7 @@ int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, i
     const uint64_t sd = (uint64_t)(seed_device ? seed_device[0] : seed);
     parallel_for(num_images, 1, [&](int64_t lo, int64_t hi) {
         std::vector<uint32_t> rank((size_t)n);
-        std::vector<uint64_t> order;   // (rank, row) of one side's rows
+        std::vector<uint32_t> scratch;
         for (int64_t b = lo; b < hi; b++) {
             const int64_t* g = gt_inds + b * n;
             int64_t count[2] = {0, 0}, k[2];
@@ -1214,14 +1192,9 @@ int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, i
             SA::sample_sizes(count[SA::POS], count[SA::NEG], num_expected_pos, num, neg_pos_ub, &k[SA::POS], &k[SA::NEG]);
             SA::Pick pick[2];
             for (int side = 0; side < 2; side++) {
-                pick[side] = SA::Pick{0u, 0, k[side]};
-                if (k[side] == 0) continue;
-                order.clear();
-                for (int64_t i = 0; i < n; i++) if (SA::side_of(g[i]) == side) order.push_back((uint64_t)rank[(size_t)i] << 32 | (uint64_t)i);
-                std::nth_element(order.begin(), order.begin() + (k[side] - 1), order.end());
-                const uint64_t kth = order[(size_t)(k[side] - 1)];
-                pick[side].key = (uint32_t)(kth >> 32);
-                pick[side].upto = (int32_t)((kth & 0xffffffffu) + 1);
+                pick[side] = SA::Pick{{0u, 0}, k[side]};
+                sph2pob_select::host_cut<false>(n, k[side], [&](int64_t i, uint32_t* key) { *key = rank[(size_t)i]; return SA::side_of(g[i]) == side; },
+                                                scratch, &pick[side].cut);
             }
             num_pos[b] = k[SA::POS]; num_neg[b] = k[SA::NEG];
             for (int64_t i = 0; i < n; i++) {

@@ -6,7 +6,7 @@
 //                         it is evaluated once and the later passes and the apply pass read the word back.  Then the k-th smallest
 //                         rank by a four-digit radix select (LDS histogram, integer atomics; random ranks spread over the bins, so
 //                         the atomics seldom meet) and, only when the rows tied at that rank are not all taken, one in-order walk
-//                         for the row index up to which they are.  The shape is softmax_cut_kernel's (sph2pob_softmax.hip), ascending.
+//                         for the row index up to which they are.  Digit decision and tie scan: sph2pob_select.hpp, ascending.
 //   sample_apply_kernel   a streaming pass over (B, n): a row that stays in the sample, or is ignored, keeps its targets (copied
 //                         when the output is another buffer, untouched when it is the input); a row that leaves gets the background
 //                         label and zeros.  Four rows per thread with 16-byte accesses when n % 4 == 0 and the bases allow.  Its
@@ -97,33 +97,9 @@ __global__ __launch_bounds__(kSelectBlock) void sample_select_kernel(const int64
             sample_sizes((int64_t)s_count[POS], (int64_t)s_count[NEG], D.num_expected_pos, D.num, D.neg_pos_ub, &kp, &kn);
             k = side == POS ? kp : kn;   // <= the side's rows < 2^31
         }
-        // prefix sums of the 256 bins by the first four waves: below[t] = rows in bins < t; the digit is the one bin with
-        // below < rem <= below + hist
-        unsigned mine = 0u, incl = 0u;
-        if (tid < 256) {
-            mine = hist[tid];
-            incl = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned up = __shfl_up(incl, o, 64);
-                if ((tid & 63) >= o) incl += up;
-            }
-            if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
-        }
-        __syncthreads();
-        if (tid < 256) {
-            unsigned before = 0u;
-#pragma unroll
-            for (int wv = 0; wv < 3; wv++) before += wv < (tid >> 6) ? s_wave[wv] : 0u;
-            const unsigned rem = d == 0 ? (unsigned)k : rem_in;
-            const unsigned below = before + incl - mine;
-            if (rem > 0u && below < rem && rem <= below + mine) {   // one thread
-                s_prefix = prefix | ((unsigned)tid << shift);
-                s_rem = rem - below;
-                if (d == 3) s_ties = mine;
-            }
-        }
-        __syncthreads();
+        // the digit: the one bin that holds the rem-th smallest rank
+        sph2pob_select::digit_decision<false>(hist, s_wave, &s_prefix, &s_rem, &s_ties, prefix, shift,
+                                              [&](unsigned) { return d == 0 ? (unsigned)k : rem_in; });
     }
     const unsigned take = s_rem;          // rows tied at the k-th rank that are taken (>= 1 when anything is)
     const unsigned cut = s_prefix;
@@ -138,24 +114,16 @@ __global__ __launch_bounds__(kSelectBlock) void sample_select_kernel(const int64
             const bool tie = i < n && side_of(gb[i]) == side && kb[i] == cut;
             const unsigned long long m = __ballot(tie);
             const unsigned in_wave = (unsigned)__popcll(m & ((1ull << (tid & 63)) - 1ull));
-            if ((tid & 63) == 0) s_wave[tid >> 6] = (unsigned)__popcll(m);
-            __syncthreads();
-            unsigned before = running, total = 0u;
-#pragma unroll
-            for (int wv = 0; wv < kWaves; wv++) {
-                if (wv < (tid >> 6)) before += s_wave[wv];
-                total += s_wave[wv];
-            }
-            if (tie && before + in_wave + 1u == take) s_upto = (int)(i + 1);   // one thread of one iteration
-            running += total;
+            const unsigned before = sph2pob_select::tie_scan<kWaves>(in_wave, (unsigned)__popcll(m), s_wave, running);
+            if (tie && before + 1u == take) s_upto = (int)(i + 1);   // one thread of one iteration
             __syncthreads();
             if (running >= take) break;   // workgroup-uniform
         }
     }
     if (tid == 0) {
         Pick p;
-        p.key = take > 0u ? cut : 0u;
-        p.upto = take > 0u ? (walk ? s_upto : n) : 0;
+        p.cut.key = take > 0u ? cut : 0u;
+        p.cut.upto = take > 0u ? (walk ? s_upto : n) : 0;
         p.k = k;
         picks[2 * b + side] = p;
     }

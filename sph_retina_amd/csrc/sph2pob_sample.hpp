@@ -1,7 +1,7 @@
 // Random sampling of anchor targets (mmdet's RandomSampler as the reference's SphRandomSampler calls it,
 // sphdet/bbox/sampler/sph_random_sampler.py:34-46, followed by the target lines of AnchorHead._get_targets_single with a real
-// sampler, anchor_head.py:254-299): the rank of a row, the sample sizes, the selection rule, the argument checks and the workspace,
-// shared by the kernels (sph2pob_sample.hip) and their CPU twin (sph2pob_host.hip) so that a CPU tensor gets the sample a device
+// sampler, anchor_head.py:254-299): the rank of a row, the sample sizes, the argument checks and the workspace (the selection rule:
+// sph2pob_select.hpp), shared by the kernels (sph2pob_sample.hip) and their CPU twin (sph2pob_host.hip) so that a CPU tensor gets the sample a device
 // tensor gets, bit for bit (everything here is integer arithmetic).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 
 #include "../../include/sph2pob_hip.h"
 #include "sph2pob_head_loss.hpp"
+#include "sph2pob_select.hpp"
 
 namespace sph2pob_sample {
 
@@ -52,10 +53,10 @@ SPHF_DEV void sample_sizes(int64_t P, int64_t N, int64_t num_expected_pos, int64
     *k_neg = N < kn ? N : kn;
 }
 
-// What the select pass leaves for one (image, side): the k-th smallest rank of the side's rows, the row index below which rows
-// with exactly that rank are taken, and k.  Nothing taken: key 0, upto 0
-struct Pick { uint32_t key; int32_t upto; int64_t k; };
-SPHF_DEV bool sampled(uint32_t rank, int64_t i, const Pick& p) { return rank < p.key || (rank == p.key && i < (int64_t)p.upto); }
+// What the select pass leaves for one (image, side): the cut (sph2pob_select.hpp, ascending) — the k-th smallest rank of the side's
+// rows and the row index below which rows with exactly that rank are taken — and k.  Nothing taken: key 0, upto 0
+struct Pick { sph2pob_select::Cut cut; int64_t k; };
+SPHF_DEV bool sampled(uint32_t rank, int64_t i, const Pick& p) { return sph2pob_select::taken<false>(rank, i, p.cut); }
 
 // ---- arguments and workspace ----------------------------------------------------------------------------------------------------
 // box_dim -> DIM; a NaN neg_pos_ub -> OPTION; B outside [1, 65 535], n outside [1, 2^31), num < 1, num_expected_pos outside

@@ -7,8 +7,8 @@
 //                         positives' partial.  MINED (mining, last pass): a row is live when its key says positive or mined(key,
 //                         index, the image's cut); live rows re-read their logits, the others get exact zeros and read nothing.
 //   softmax_cut_kernel    one workgroup per image: P_b and N_b from the keys, k_b = min(r P_b, N_b), the k_b-th largest key by a
-//                         four-digit radix select (LDS histogram, integer atomics), then one in-order walk that adds the mined
-//                         losses in double and finds the row index up to which rows tied at the cut are taken
+//                         four-digit radix select (LDS histogram, integer atomics; digit decision and tie scan: sph2pob_select.hpp),
+//                         then one in-order walk: the mined losses added in double, the row index up to which ties at the cut are taken
 //   head_final_kernel     (sph2pob_head_loss.hpp) adds the workgroups' and the images' partials in a fixed order
 // No float atomics and no global counters: the same bits on every call.  One stream, no host read.
 #include "sph2pob_softmax.hpp"
@@ -273,33 +273,10 @@ __global__ __launch_bounds__(kCutBlock) void softmax_cut_kernel(const unsigned* 
             if (d == 0 && npos) atomicAdd(&s_pos, npos);
         }
         __syncthreads();
-        // suffix sums of the 256 bins by the first four waves: above[t] = keys in bins > t; the digit is the one bin with
-        // above < rem <= above + hist
-        unsigned mine = 0u, incl = 0u;
-        if (tid < 256) {
-            mine = hist[tid];
-            incl = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned dn = __shfl_down(incl, o, 64);
-                if ((tid & 63) + o < 64) incl += dn;
-            }
-            if ((tid & 63) == 0) s_wave[tid >> 6] = incl;
-        }
-        __syncthreads();
-        if (tid < 256) {
-            unsigned after = 0u;
-#pragma unroll
-            for (int wv = 1; wv < 4; wv++) after += wv > (tid >> 6) ? s_wave[wv] : 0u;
-            const unsigned total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-            const unsigned rem = d == 0 ? (unsigned)mined_count(ratio, (int64_t)s_pos, (int64_t)total) : rem_in;
-            const unsigned above = incl + after - mine;
-            if (rem > 0u && above < rem && rem <= above + mine) {   // one thread
-                s_prefix = prefix | ((unsigned)tid << shift);
-                s_rem = rem - above;
-            }
-        }
-        __syncthreads();
+        // the digit: the one bin that holds the rem-th largest key; in the first round rem is k_b, from the negatives the bins hold
+        sph2pob_select::digit_decision<true>(hist, s_wave, &s_prefix, &s_rem, nullptr, prefix, shift, [&](unsigned total) {
+            return d == 0 ? (unsigned)mined_count(ratio, (int64_t)s_pos, (int64_t)total) : rem_in;
+        });
     }
     const unsigned take = s_rem;                          // rows tied at the cut key that are mined (>= 1 when anything is)
     const unsigned cut_key = take > 0u ? s_prefix : kKeyNaN;
@@ -322,26 +299,12 @@ __global__ __launch_bounds__(kCutBlock) void softmax_cut_kernel(const unsigned* 
             if (take > 0u && kv[e] >= 2u && kv[e] > cut_key) acc += (double)key_loss(kv[e]);
             if (take > 0u && kv[e] == cut_key) ties++;
         }
-        unsigned incl = ties;   // inclusive scan inside the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned up = __shfl_up(incl, o, 64);
-            if ((tid & 63) >= o) incl += up;
-        }
-        if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
-        __syncthreads();
-        unsigned before = running, total = 0u;
-#pragma unroll
-        for (int wv = 0; wv < kWaves; wv++) {
-            if (wv < (tid >> 6)) before += s_wave[wv];
-            total += s_wave[wv];
-        }
-        unsigned seen = before + incl - ties;
+        const unsigned incl = sph2pob_select::wave_prefix(ties);
+        unsigned seen = sph2pob_select::tie_scan<kWaves>(incl - ties, incl, s_wave, running);
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             if (take > 0u && kv[e] == cut_key && ++seen == take) s_upto = 4 * q + e + 1;   // one thread of one iteration
         }
-        running += total;
         __syncthreads();
     }
 #pragma unroll

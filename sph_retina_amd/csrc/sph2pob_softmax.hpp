@@ -1,7 +1,8 @@
 // Softmax cross-entropy with optional hard-negative mining (SphSSDHead.loss_single, sphdet/models/heads/sph_ssd_head.py:96-161;
-// mmdet's cross_entropy + weight_reduce_loss in plain mode): the row arithmetic, the order-preserving loss keys, the level table
-// and the argument checks, shared by the kernels (sph2pob_softmax.hip) and their CPU twins (sph2pob_host.hip) so that a CPU tensor
-// gets the arithmetic, the mined set and the checks a device tensor gets.
+// mmdet's cross_entropy + weight_reduce_loss in plain mode): the row arithmetic, the order-preserving loss keys and the argument
+// checks, shared by the kernels (sph2pob_softmax.hip) and their CPU twins (sph2pob_host.hip) so that a CPU tensor gets the
+// arithmetic, the mined set and the checks a device tensor gets.  The level table is sph2pob_class_levels.hpp's, the cut of an image
+// sph2pob_select.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -9,7 +10,9 @@
 #include <stdint.h>
 
 #include "../../include/sph2pob_hip.h"
+#include "sph2pob_class_levels.hpp"
 #include "sph2pob_head_loss.hpp"
+#include "sph2pob_select.hpp"
 
 namespace sph2pob_softmax {
 
@@ -18,7 +21,6 @@ using sph2pob_head::effective_scale;
 using sph2pob_head::kBlock;
 using sph2pob_head::kMaxLevels;
 
-constexpr int64_t kMaxLevelElems = ((int64_t)1 << 31) - 4096;   // elements of one level: 32-bit indices inside a level
 constexpr int kMinK = 2, kMaxK = 4096;
 constexpr int kCutBlock = 1024;   // threads of the per-image cut workgroup
 
@@ -116,69 +118,24 @@ SPHF_DEV float key_loss(unsigned k) {
     if (k == kKeyNaN) return bits_float(0x7fc00000u);
     return bits_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
-// the cut of one image: the k-th largest negative key and the row index below which rows with exactly that key are taken.  Nothing
-// mined: key = kKeyNaN, upto = 0
-struct Cut { unsigned key; int upto; };
-SPHF_DEV bool mined(unsigned key, int i, const Cut& c) { return key >= 2u && (key > c.key || (key == c.key && i < c.upto)); }
+// the cut of one image (sph2pob_select.hpp, descending): the k-th largest negative key and the row index below which rows with
+// exactly that key are taken.  Nothing mined: key = kKeyNaN, upto = 0
+using sph2pob_select::Cut;
+SPHF_DEV bool mined(unsigned key, int i, const Cut& c) { return key >= 2u && sph2pob_select::taken<true>(key, i, c); }
 // k_b = min(r P_b, N_b)
 SPHF_DEV int64_t mined_count(int64_t ratio, int64_t pos, int64_t neg) { const int64_t k = ratio * pos; return k < neg ? k : neg; }
 
 // ---- levels ---------------------------------------------------------------------------------------------------------------------
-// kind: how a thread's item maps onto memory
-//   0  NCHW (B, A K, H, W), four consecutive positions p = h W + w of one (b, a) per item: 16-byte accesses at stride H W over the classes
-//   1  NCHW, one position per item (H W % 4 != 0 or a base that is not 16-byte aligned)
-//   2  flat (B, n_l, K), one row per item walked with 16-byte accesses (K % 4 == 0 and an aligned base)
-//   3  flat, one row per item, one element at a time
-enum { KIND_NCHW4 = 0, KIND_NCHW1 = 1, KIND_FLAT4 = 2, KIND_FLAT1 = 3 };
-struct Level {
-    const float* logits;
-    float* grad;           // laid out like logits; NULL in a forward-only call
-    int n, hw, a, kind;    // anchors of the level; H W (0: flat); anchors per position
-    int items;             // work items of the level
-    int block_off;         // first workgroup of the level
-    int64_t row_off;       // index of the level's first anchor inside an image's n rows
-};
-struct Levels {
-    Level lv[kMaxLevels];
-    int num, blocks;       // levels; workgroups of a row pass
-    int64_t n_total;       // anchors of one image, all levels
-    int64_t n_pad;         // n_total rounded up to 4: the stride of one image's keys
-    int64_t rows;          // B n
-};
-
-// Argument checks of sph2pob_softmax_loss_sum_f32 / its twin, in the documented order; fills the table.  `tables` false: shapes
-// only (the workspace size), every level counted with its scalar kind (an upper bound on the workgroups).
+// The level table: Level, Levels and the KIND_* of sph2pob_class_levels.hpp; a flat level's item is one row, walked with 16-byte
+// accesses (FLAT4: K % 4 == 0 and aligned bases) or one element at a time (FLAT1); n_pad is the stride of one image's keys.
+// Argument checks of sph2pob_softmax_loss_sum_f32 / its twin, in the documented order: the option here, sizes and pointers in the
+// shared walk, which fills the table (`tables`: there)
+using namespace sph2pob_class;
+constexpr Family kFamily{kMinK, kMaxK, true, ((int64_t)1 << 31) - 8};
 inline int make_levels(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw, int num_levels,
                        int64_t B, int64_t K, int64_t neg_pos_ratio, bool tables, Levels* out) {
     if (neg_pos_ratio < -1 || neg_pos_ratio > ((int64_t)1 << 30)) return SPH2POB_ERR_OPTION;
-    if (num_levels < 1 || num_levels > kMaxLevels || B < 0 || B > 65535 || K < kMinK || K > kMaxK) return SPH2POB_ERR_SIZE;
-    if (!level_n || (tables && !logits)) return SPH2POB_ERR_NULL;
-    Levels L{};
-    L.num = num_levels;
-    int64_t blocks = 0, rows = 0;
-    for (int l = 0; l < num_levels; l++) {
-        const int64_t n = level_n[l], hw = level_hw ? level_hw[l] : 0;
-        if (n < 0 || hw < 0 || (hw > 0 && n % hw != 0) || n > kMaxLevelElems / K || (B > 0 && n * K > kMaxLevelElems / B)) return SPH2POB_ERR_SIZE;
-        const int64_t elems = B * n * K;
-        Level& d = L.lv[l];
-        d.n = (int)n; d.hw = (int)hw; d.a = hw > 0 ? (int)(n / hw) : 1;
-        d.logits = tables ? (const float*)logits[l] : nullptr;
-        d.grad = tables && grads ? (float*)grads[l] : nullptr;
-        if (tables && elems > 0 && (!d.logits || (grads && !d.grad))) return SPH2POB_ERR_NULL;
-        const bool al = tables && aligned_to(d.logits, 16) && aligned_to(d.grad, 16);
-        if (hw > 0) d.kind = al && hw % 4 == 0 ? KIND_NCHW4 : KIND_NCHW1;
-        else d.kind = al && K % 4 == 0 ? KIND_FLAT4 : KIND_FLAT1;
-        const int64_t items = d.kind == KIND_NCHW4 ? B * n / 4 : B * n;
-        d.items = (int)items;
-        d.block_off = (int)blocks;
-        d.row_off = rows;
-        blocks += (items + kBlock - 1) / kBlock;
-        rows += n;
-        if (blocks >= ((int64_t)1 << 31) - 1 || rows >= ((int64_t)1 << 31) - 8) return SPH2POB_ERR_SIZE;
-    }
-    L.blocks = (int)blocks; L.n_total = rows; L.n_pad = (rows + 3) / 4 * 4; L.rows = B * rows;
-    *out = L;
-    return SPH2POB_OK;
+    return walk_levels(kFamily, logits, grads, level_n, level_hw, num_levels, B, K, tables, 16, out);
 }
 
 // The workspace: doubles [0, blocks) the row pass's partials, [blocks, blocks + B) the mined sums of the images (mining), one

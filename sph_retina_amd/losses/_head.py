@@ -37,6 +37,11 @@ def _f32c(t):
     return t if t.dtype is torch.float32 and t.is_contiguous() else G.as_f32(t.detach())
 
 
+def _labels(t):
+    t = t.detach() if t.requires_grad else t
+    return t if t.dtype is torch.int64 and t.is_contiguous() else t.to(torch.int64).contiguous()
+
+
 def _avg_tensor(avg_factor, dev):
     a = avg_factor.detach().reshape(-1)
     if a.numel() != 1:
@@ -94,6 +99,39 @@ def box_levels(name, bbox_preds, images, dim):
         else:
             raise ValueError(f'{name}[{l}]: expected (B, A * {dim}, H, W) or (B, n_l, {dim}) with B = {images}, got {tuple(p.shape)}')
     return hws, total
+
+
+def class_levels(fn, name, cls_scores, images, n, known_channels=None):
+    """(hws, channels per anchor) of L classification levels, each NCHW (B, A * channels, H, W) -> H W or flattened
+    (B, n_l, channels) -> 0, for `n` anchors per image; `name`: the caller `fn`'s letter for the channel count (C classes, K scores).
+    The count comes from flattened levels or `known_channels` (per-element weights) where there are any; else from the anchors
+    per position, which sum n_l = n fixes: sum_l (channels_l * hw_l) = n * channels."""
+    hws, total = [], 0
+    for l, s in enumerate(cls_scores):
+        if s.dim() not in (3, 4) or s.size(0) != images:
+            raise ValueError(f'cls_scores[{l}]: expected (B, A * {name}, H, W) or (B, n_l, {name}) with B = {images}, got {tuple(s.shape)}')
+        hws.append(s.size(2) * s.size(3) if s.dim() == 4 else 0)
+    flat = {s.size(2) for s in cls_scores if s.dim() == 3}
+    if known_channels is not None:
+        flat.add(known_channels)
+    if len(flat) > 1:
+        raise ValueError(f'the class count differs across levels / weights: {sorted(flat)}')
+    if flat:
+        channels = flat.pop()
+    else:
+        per_image = sum(s.size(1) * hw for s, hw in zip(cls_scores, hws))
+        if n == 0 or per_image % n != 0:
+            raise ValueError(f'the levels hold {per_image} scores per image, which {n} anchors (labels.size(1)) do not divide')
+        channels = per_image // n
+    if channels <= 0:
+        raise ValueError('the class count must be positive')
+    for l, s in enumerate(cls_scores):
+        if s.dim() == 4 and s.size(1) % channels != 0:
+            raise ValueError(f'cls_scores[{l}]: {s.size(1)} channels are not a multiple of {name} = {channels} ({name} must be equal across levels)')
+        total += s.size(1) // channels * hws[l] if s.dim() == 4 else s.size(1)
+    if total != n:
+        raise ValueError(f'the levels hold {total} anchors per image, labels {n}')
+    return hws, channels
 
 
 def weight_dim(bbox_weights, images, n, dim, targets_shape):

@@ -26,14 +26,9 @@ import torch.nn as nn
 from .. import _torch_glue as G
 from ..registry import LOSSES, LOSSES_IS_MMDET
 from . import _head as H
-from ._head import _f32c, _reduce_scale
+from ._head import _f32c, _labels, _reduce_scale
 
 _WEIGHT_NONE, _WEIGHT_ROW, _WEIGHT_ELEM = 0, 1, 2
-
-
-def _labels(t):
-    t = t.detach() if t.requires_grad else t
-    return t if t.dtype is torch.int64 and t.is_contiguous() else t.to(torch.int64).contiguous()
 
 
 class _FocalSumFunction(torch.autograd.Function):
@@ -177,33 +172,7 @@ def sph_focal_loss(cls_scores, labels, label_weights=None, *, gamma=2.0, alpha=0
         wmode, classes = _WEIGHT_ELEM, label_weights.size(2)
     else:
         raise ValueError(f'label_weights must be (B, n) or (B, n, C) like labels {tuple(labels.shape)}, got {tuple(label_weights.shape)}')
-    hws, total = [], 0
-    for l, s in enumerate(cls_scores):
-        if s.dim() not in (3, 4) or s.size(0) != images:
-            raise ValueError(f'cls_scores[{l}]: expected (B, A * C, H, W) or (B, n_l, C) with B = {images}, got {tuple(s.shape)}')
-        hws.append(s.size(2) * s.size(3) if s.dim() == 4 else 0)
-    # the class count: from flattened levels or per-element weights where there are any; else from the anchors per position,
-    # which sum n_l = n fixes: sum_l (channels_l * hw_l) = n * C
-    flat_c = {s.size(2) for s in cls_scores if s.dim() == 3}
-    if classes is not None:
-        flat_c.add(classes)
-    if len(flat_c) > 1:
-        raise ValueError(f'the class count differs across levels / weights: {sorted(flat_c)}')
-    if flat_c:
-        classes = flat_c.pop()
-    else:
-        per_image = sum(s.size(1) * hw for s, hw in zip(cls_scores, hws))
-        if n == 0 or per_image % n != 0:
-            raise ValueError(f'the levels hold {per_image} scores per image, which {n} anchors (labels.size(1)) do not divide')
-        classes = per_image // n
-    if classes <= 0:
-        raise ValueError('the class count must be positive')
-    for l, s in enumerate(cls_scores):
-        if s.dim() == 4 and s.size(1) % classes != 0:
-            raise ValueError(f'cls_scores[{l}]: {s.size(1)} channels are not a multiple of C = {classes} (C must be equal across levels)')
-        total += s.size(1) // classes * hws[l] if s.dim() == 4 else s.size(1)
-    if total != labels.size(1):
-        raise ValueError(f'the levels hold {total} anchors per image, labels {labels.size(1)}')
+    hws, classes = H.class_levels('sph_focal_loss', 'C', cls_scores, images, n, known_channels=classes)
     scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n * classes, labels.device)
     w = G.as_f32_nograd(label_weights) if label_weights is not None else None
     out = _FocalSumFunction.apply(classes, _labels(labels), w, wmode, gamma, alpha, scale, avg, hws, *H.forward_only(cls_scores))

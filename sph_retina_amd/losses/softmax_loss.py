@@ -34,8 +34,7 @@ from .. import _lib
 from .. import _torch_glue as G
 from ..registry import LOSSES, LOSSES_IS_MMDET
 from . import _head as H
-from ._head import _f32c, _reduce_scale
-from .focal_loss import _labels
+from ._head import _f32c, _labels, _reduce_scale
 
 _PLAIN = -1
 
@@ -194,30 +193,7 @@ def sph_softmax_loss(cls_scores, labels, label_weights=None, *, neg_pos_ratio=No
     images, n = labels.shape
     if label_weights is not None and tuple(label_weights.shape) != (images, n):
         raise ValueError(f'label_weights must be (B, n) like labels {tuple(labels.shape)}, got {tuple(label_weights.shape)}')
-    hws, total = [], 0
-    for l, s in enumerate(cls_scores):
-        if s.dim() not in (3, 4) or s.size(0) != images:
-            raise ValueError(f'cls_scores[{l}]: expected (B, A * K, H, W) or (B, n_l, K) with B = {images}, got {tuple(s.shape)}')
-        hws.append(s.size(2) * s.size(3) if s.dim() == 4 else 0)
-    # the channel count: from flattened levels where there are any; else from the anchors per position, which sum n_l = n fixes
-    flat_k = {s.size(2) for s in cls_scores if s.dim() == 3}
-    if len(flat_k) > 1:
-        raise ValueError(f'the class count differs across levels / weights: {sorted(flat_k)}')
-    if flat_k:
-        channels = flat_k.pop()
-    else:
-        per_image = sum(s.size(1) * hw for s, hw in zip(cls_scores, hws))
-        if n == 0 or per_image % n != 0:
-            raise ValueError(f'the levels hold {per_image} scores per image, which {n} anchors (labels.size(1)) do not divide')
-        channels = per_image // n
-    if channels <= 0:
-        raise ValueError('the class count must be positive')
-    for l, s in enumerate(cls_scores):
-        if s.dim() == 4 and s.size(1) % channels != 0:
-            raise ValueError(f'cls_scores[{l}]: {s.size(1)} channels are not a multiple of K = {channels} (K must be equal across levels)')
-        total += s.size(1) // channels * hws[l] if s.dim() == 4 else s.size(1)
-    if total != labels.size(1):
-        raise ValueError(f'the levels hold {total} anchors per image, labels {labels.size(1)}')
+    hws, channels = H.class_levels('sph_softmax_loss', 'K', cls_scores, images, n)
     background = channels - 1 if background_label is None else int(background_label)
     scale, avg, nan = _reduce_scale(reduction, avg_factor, loss_weight, images * n, labels.device)
     w = G.as_f32_nograd(label_weights) if label_weights is not None else None

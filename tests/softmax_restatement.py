@@ -338,6 +338,67 @@ def check_ties(S, device):
     assert torch.equal(support(gc.cpu()), support(truth[2]))
 
 
+def assert_tied_selection(S, device, levels, labels, ratio):
+    """Constant logits on `levels` (every loss is the same fp32 value log K) with `labels` (B, n): the support of the gradient is
+    the positives plus the first k_b = min(ratio P_b, N_b) negatives by row index, the sum (P + k) log K.  Returns the per-image
+    (k, negatives' row indices)."""
+    B, n = labels.shape
+    const = [torch.full((B, A * K, H, W), 0.25).to(device).requires_grad_(True) for A, H, W in levels]
+    total, rows = run_levels(S, const, labels.to(device), None, neg_pos_ratio=ratio, reduction='sum')
+    sup = support(rows.cpu()).reshape(B, n)
+    want_total, info = 0.0, []
+    for b in range(B):
+        valid = labels[b] >= 0
+        pos = valid & (labels[b] != K - 1)
+        neg = torch.nonzero(valid & (labels[b] == K - 1)).reshape(-1)
+        k = min(ratio * int(pos.sum()), int(neg.numel()))
+        want = pos.clone()
+        want[neg[:k]] = True
+        assert torch.equal(sup[b], want), f'constant logits, ratio {ratio}, image {b}'
+        want_total += (int(pos.sum()) + k) * float(np.log(np.float64(K)))
+        info.append((k, neg))
+    assert abs(float(total) - want_total) <= 1e-6 * want_total, (float(total), want_total)
+    return info
+
+
+def check_ties_over_several_chunks(S, device):
+    """BIG_LEVELS: n = 4608 is more than the 4096 rows of one iteration of the cut's in-order walk.  Image 2 (40 positives) mines
+    4400 of its 4568 negatives, all tied: the row index that ends the tied rows lies in the second iteration."""
+    _, labels, _ = scene(BIG_LEVELS, seed=BIG_SEED)
+    info = assert_tied_selection(S, device, BIG_LEVELS, labels, 110)
+    k, neg = info[2]
+    assert 0 < k < neg.numel() and int(neg[k - 1]) >= 4096, (k, neg.numel())
+
+
+def check_ties_in_the_padded_tail(S, device):
+    """SCENE_LEVELS: n = 127 rows, so the last quad of an image's keys has one word of padding.  Images 0 and 2 have 42 positives and
+    85 negatives, all tied; image 0's last row is a negative.  Ratio 3: k = 85, every tied row is taken; ratio 2: k = 84, all but
+    the last one in row order — row 126 for image 0.  Image 1 has no positive, image 3 no negative."""
+    n = sum(A * H * W for A, H, W in SCENE_LEVELS)
+    assert n == 127 and n % 4 != 0
+    labels = torch.full((4, n), K - 1, dtype=torch.int64)
+    labels[0, 1:126:3] = 2
+    labels[2, -42:] = 0
+    labels[3] = 1
+    assert int((labels[0] != K - 1).sum()) == 42 and int(labels[0, 126]) == K - 1
+    for ratio, k in ((3, 85), (2, 84)):
+        info = assert_tied_selection(S, device, SCENE_LEVELS, labels, ratio)
+        assert [i[0] for i in info] == [k, 0, k, 0]
+
+
+def check_nan_loss_is_mined_first(S, device):
+    """A NaN loss has the key 0xffffffff, the first in the descending order: it is mined and reaches the sum."""
+    scores, labels, _ = scene()
+    rows = to_rows(scores).clone()
+    neg = torch.nonzero(labels[0] == K - 1).reshape(-1)
+    rows[0, neg[-1], 0] = float('nan')
+    x = rows.to(device).requires_grad_(True)
+    loss = S.sph_softmax_loss([x], labels.to(device), neg_pos_ratio=RATIO, reduction='sum')
+    assert torch.isnan(loss)
+    g, = torch.autograd.grad(loss, x)
+    assert bool(torch.isnan(g[0, neg[-1]]).any()) and bool(torch.isfinite(g[1:]).all())
+
+
 def check_plain_and_module(S, device):
     scores, labels, weights = scene()
     B, n = labels.shape

@@ -44,6 +44,18 @@ def test_ties_take_the_lowest_rows(S):
     R.check_ties(S, 'cuda')
 
 
+def test_ties_over_several_chunks_of_the_walk(S):
+    R.check_ties_over_several_chunks(S, 'cuda')
+
+
+def test_ties_in_the_padded_tail_all_taken_and_all_but_one(S):
+    R.check_ties_in_the_padded_tail(S, 'cuda')
+
+
+def test_nan_loss_is_mined_first_and_reaches_the_sum(S):
+    R.check_nan_loss_is_mined_first(S, 'cuda')
+
+
 def test_plain_mode_function_and_module(S):
     R.check_plain_and_module(S, 'cuda')
 

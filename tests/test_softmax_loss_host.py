@@ -49,16 +49,50 @@ def test_two_calls_give_the_same_bits(S, levels, seed):
     R.check_determinism(S, 'cpu', levels, seed)
 
 
+def test_ties_over_several_chunks_of_the_walk(S):
+    R.check_ties_over_several_chunks(S, 'cpu')
+
+
+def test_ties_in_the_padded_tail_all_taken_and_all_but_one(S):
+    R.check_ties_in_the_padded_tail(S, 'cpu')
+
+
 def test_nan_loss_is_mined_first_and_reaches_the_sum(S):
-    scores, labels, _ = R.scene()
-    rows = R.to_rows(scores).clone()
-    neg = torch.nonzero(labels[0] == R.K - 1).reshape(-1)
-    rows[0, neg[-1], 0] = float('nan')
-    x = rows.requires_grad_(True)
-    loss = S.sph_softmax_loss([x], labels, neg_pos_ratio=R.RATIO, reduction='sum')
-    assert torch.isnan(loss)
-    g, = torch.autograd.grad(loss, x)
-    assert bool(torch.isnan(g[0, neg[-1]]).any()) and bool(torch.isfinite(g[1:]).all())
+    R.check_nan_loss_is_mined_first(S, 'cpu')
+
+
+def test_class_levels_parses_nchw_flat_and_mixed_levels():
+    """losses/_head.class_levels, which sph_focal_loss and sph_softmax_loss share: (H W per level, channels per anchor)."""
+    from sph_retina_amd.losses import _head as H
+    z = torch.zeros
+    nchw = [z(2, 3 * 6, 4, 8), z(2, 2 * 6, 3, 5), z(2, 6, 1, 1)]            # n = 96 + 30 + 1
+    flat = [z(2, 96, 6), z(2, 30, 6), z(2, 1, 6)]
+    assert H.class_levels('f', 'K', nchw, 2, 127) == ([32, 15, 1], 6)
+    assert H.class_levels('f', 'K', flat, 2, 127) == ([0, 0, 0], 6)
+    assert H.class_levels('f', 'C', [nchw[0], flat[1], nchw[2]], 2, 127) == ([32, 0, 1], 6)
+    assert H.class_levels('f', 'C', nchw, 2, 127, known_channels=6) == ([32, 15, 1], 6)
+    # 18 channels x 32 positions: 6 channels for 96 anchors, or — told so by per-element weights — 9 for 64
+    assert H.class_levels('f', 'C', nchw[:1], 2, 64, known_channels=9) == ([32], 9)
+    with pytest.raises(ValueError, match=r'cls_scores\[1\]: expected \(B, A \* K, H, W\) or \(B, n_l, K\) with B = 2, got \(3, 12, 3, 5\)'):
+        H.class_levels('f', 'K', [nchw[0], z(3, 12, 3, 5)], 2, 126)
+    with pytest.raises(ValueError, match=r'cls_scores\[0\]: expected \(B, A \* C, H, W\) or \(B, n_l, C\) with B = 2, got \(2, 6\)'):
+        H.class_levels('f', 'C', [z(2, 6)], 2, 1)
+    with pytest.raises(ValueError, match=r'the class count differs across levels / weights: \[6, 7\]'):
+        H.class_levels('f', 'K', [flat[0], z(2, 30, 7)], 2, 126)
+    with pytest.raises(ValueError, match=r'the class count differs across levels / weights: \[5, 6\]'):
+        H.class_levels('f', 'C', flat, 2, 127, known_channels=5)
+    with pytest.raises(ValueError, match=r'the levels hold 756 scores per image, which 125 anchors \(labels.size\(1\)\) do not divide'):
+        H.class_levels('f', 'K', nchw[:2], 2, 125)
+    with pytest.raises(ValueError, match=r'the levels hold 756 scores per image, which 0 anchors'):
+        H.class_levels('f', 'K', nchw[:2], 2, 0)
+    with pytest.raises(ValueError, match='the class count must be positive'):
+        H.class_levels('f', 'K', [z(2, 5, 0)], 2, 5)
+    with pytest.raises(ValueError, match=r'cls_scores\[1\]: 12 channels are not a multiple of K = 7 \(K must be equal across levels\)'):
+        H.class_levels('f', 'K', [z(2, 14, 4, 8), nchw[1], z(2, 4, 7)], 2, 130)
+    with pytest.raises(ValueError, match=r'cls_scores\[0\]: 18 channels are not a multiple of C = 7 \(C must be equal across levels\)'):
+        H.class_levels('f', 'C', nchw[:2], 2, 108)       # 756 = 108 x 7
+    with pytest.raises(ValueError, match='the levels hold 126 anchors per image, labels 127'):
+        H.class_levels('f', 'K', flat[:2], 2, 127)
 
 
 def test_module_and_argument_errors(S):

@@ -494,7 +494,7 @@ def focal(images=8, classes=37, rounds=7):
 
     def fused():
         loss = S.sph_focal_loss(cls, labels, weights, gamma=2.0, alpha=0.25, avg_factor=avg)
-        return (loss,) + torch.autograd.grad(loss, cls)
+        return (loss.detach(),) + torch.autograd.grad(loss, cls)
 
     def composition():
         x = torch.cat([c.permute(0, 2, 3, 1).reshape(images, -1, classes) for c in cls], 1).reshape(-1, classes)
@@ -503,11 +503,8 @@ def focal(images=8, classes=37, rounds=7):
         pt = (1 - p) * t + p * (1 - t)
         fw = (0.25 * t + 0.75 * (1 - t)) * pt.pow(2.0)
         loss = (F.binary_cross_entropy_with_logits(x, t, reduction='none') * fw * weights.reshape(-1, 1)).sum() / (avg + 1.1920929e-07)
-        return (loss.reshape(()),) + torch.autograd.grad(loss, cls)
-    a, c = fused(), composition()
-    torch.cuda.synchronize()
-    loss_rel = abs(float(a[0]) - float(c[0])) / abs(float(c[0]))
-    grad_diff = max(float((x - y).abs().max()) for x, y in zip(a[1:], c[1:]))
+        return (loss.detach().reshape(()),) + torch.autograd.grad(loss, cls)
+    # the capture comes first, after a warm-up on a side stream, and nothing returned keeps an autograd graph alive (see bbox_loss)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -517,6 +514,10 @@ def focal(images=8, classes=37, rounds=7):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         fused()
+    a, c = fused(), composition()
+    torch.cuda.synchronize()
+    loss_rel = abs(float(a[0]) - float(c[0])) / abs(float(c[0]))
+    grad_diff = max(float((x - y).abs().max()) for x, y in zip(a[1:], c[1:]))
     dst = [torch.empty_like(x) for x in cls]
 
     def copy():
