@@ -892,6 +892,74 @@ int sph2pob_sample_targets_f32(const int64_t* assigned_gt_inds, int64_t num_imag
                                float* bbox_targets, float* bbox_weights, unsigned char* sample_flags, int64_t* num_pos, int64_t* num_neg,
                                float* avg_factor, float* avg_factor_pos, void* workspace, void* stream);
 
+/*
+ * sph2pob_point_targets_f32 — the targets of an anchor-free (FCOS) head for a whole minibatch: what FCOSHead.get_targets and
+ * centerness_target (mmdet/models/dense_heads/fcos_head.py:270-329, :415-434) compute through the reference's
+ * SphFCOSHead._get_target_single (sphdet/models/heads/sph_fcos_head.py:107-203), per image and with (P, k) temporaries, and the two
+ * normalisers that SphFCOSHead.loss obtains with nonzero() and len() (:68-82).  Two launches whatever B is, nothing read back.
+ *   points (P, 2) f32, level-major: (x, y) of every location, level l owning the next level_n[l] rows
+ *   the level table, HOST arrays of num_levels <= 8 entries, copied by value:
+ *     level_n        points of the level (sum = P)
+ *     range_lo/_hi   regress_ranges[l], as fp32
+ *     sample_extent  strides[l] * center_sample_radius, rounded to fp32 by the caller (read with SPH2POB_POINT_CENTER_SAMPLING only)
+ *     norm_stride    strides[l] (read with SPH2POB_POINT_NORM_ON_BBOX only)
+ *   gt (num_gt, box_dim), gt_labels (num_gt) int64, gt_offsets (B + 1) int64: image b owns rows gt_offsets[b] : gt_offsets[b + 1],
+ *   of which the first k_max are used (rows outside the tensor are never read, whatever the offsets say)
+ *   img_h, img_w   the ERP image, 1 .. 2^24;  num_classes: the background label;  flags: SPH2POB_POINT_*
+ * Per (image, point), in fp32 and in the reference's operation order (the library is built without contraction, so every float
+ * output has the bits of the torch composition on the CPU):
+ *   a GT goes to pixels as _sph2pix_box_transform then xywh2xyxy do it: x = (theta / 360) W, y = (phi / 180) H, w = (alpha / 360) W,
+ *   h = (beta / 180) H, x1 = x - w / 2, ..., area = (x2 - x1) (y2 - y1);  l = x - x1, t = y - y1, r = x2 - x, b = y2 - y
+ *   the GT is a candidate when min(l, t, r, b) > 0 — with centre sampling the same test on the centre box of :149-182, the GT's
+ *   centre +- sample_extent cut to the GT with where and strict > — and range_lo <= max(l, t, r, b) <= range_hi, both ends included;
+ *   a comparison with a NaN is false
+ *   the candidate with the smallest area wins, the lowest index among equal areas (what areas.min(dim=1) returns on the CPU); an
+ *   area >= 1e8 (the reference's INF) never wins
+ * Outputs, every element written once:
+ *   labels       (B, P) int64     the winner's label, num_classes without one
+ *   gt_inds      (B, P) int64     1 + the winner's index inside the image, 0 without one
+ *   bbox_targets (B, P, box_dim)  (l, t, r, b[, gamma]) of the winner, every component over norm_stride with NORM_ON_BBOX (the angle
+ *                                 too: fcos_head.py:326-327 divides the reference's whole tensor); EXACT ZEROS without a winner — the
+ *                                 reference leaves the distances to the image's GT 0 there and never reads them
+ *   centerness   (B, P) f32       sqrt((min(l, r) / max(l, r)) (min(t, b) / max(t, b))) of the row as written; 0 without a winner
+ *   num_pos      (B) int64        winners of the image
+ *   avg_factor        (1) f32     max(sum_b num_pos, 1)
+ *   centerness_denorm (1) f32     max(sum of centerness, 1e-6): the sum in double, per workgroup and then in one fixed order, rounded
+ *                                 once (the reference's fp32 .sum() has no defined order)
+ *   workspace    sph2pob_point_targets_workspace_bytes(B, P) bytes of scratch, no initialisation (0 for sizes the entry refuses)
+ * B P == 0 is not an error: the two normalisers (1 and 1e-6) and num_pos are still written.
+ * Errors, checked in this order before anything is enqueued: box_dim -> SPH2POB_ERR_DIM; num_levels outside [1, 8], B outside
+ * [0, 65 535], P outside [0, 2^31 - 256), num_gt < 0 or >= 2^31, k_max < 0 or > num_gt, num_classes < 0, img_h / img_w outside
+ * [1, 2^24], n_l < 0, sum n_l != P -> SPH2POB_ERR_SIZE (a NULL level_n -> SPH2POB_ERR_NULL); a NULL table the flags ask for, output,
+ * input with rows or workspace -> SPH2POB_ERR_NULL; unknown flags, a NaN range, a sample_extent < 0 or NaN, a norm_stride <= 0 or NaN
+ * -> SPH2POB_ERR_OPTION.
+ *
+ * sph2pob_point_coder_{encode,decode,decode_bwd}_f32 — bbox2distance and distance2bbox of the reference's
+ * DistancePointSphBBoxCoder (sphdet/bbox/coder/distance_point_sph_bbox_coder.py:131-163, :71-128), one row per lane, in its fp32
+ * operation order.  points (n, 2); rows of box_dim floats.
+ *   encode      gt (n, box_dim) degrees -> distances (l, t, r, b[, gamma]); clamp = 1: each of the four clamped to
+ *               [0, (float)(max_dis - eps)] as torch.clamp does (a NaN stays)
+ *   decode      x1 = x - l, y1 = y - t, x2 = x + r, y2 = y + b; x clipped to [0, max_w] and y to [0, max_h] (a negative bound: that
+ *               axis is not clipped); then xyxy2xywh and _pix2sph_box_transform: theta = (((x1 + x2) / 2) / W) 360, ...; gamma passes
+ *   decode_bwd  grad_distances for grad_boxes, as torch's autograd delivers it through that composition: the clamp passes the
+ *               gradient where the corner lies inside the closed interval; nothing flows to the points
+ * Errors, in this order: box_dim -> SPH2POB_ERR_DIM; n < 0 or >= 2^31 - 256, img_h / img_w outside [1, 2^24] -> SPH2POB_ERR_SIZE;
+ * a NULL tensor with n > 0 -> SPH2POB_ERR_NULL; a NaN bound, clamp outside {0, 1} -> SPH2POB_ERR_OPTION.  n == 0 is a no-op.
+ */
+enum { SPH2POB_POINT_CENTER_SAMPLING = 1, SPH2POB_POINT_NORM_ON_BBOX = 2 };
+int64_t sph2pob_point_targets_workspace_bytes(int64_t num_images, int64_t num_points);
+int sph2pob_point_targets_f32(const float* points, int64_t num_points, const int64_t* level_n, const float* range_lo, const float* range_hi,
+                              const float* sample_extent, const float* norm_stride, int num_levels, const float* gt, const int64_t* gt_labels,
+                              const int64_t* gt_offsets, int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int64_t img_h,
+                              int64_t img_w, int64_t num_classes, int flags, int64_t* labels, int64_t* gt_inds, float* bbox_targets,
+                              float* centerness, int64_t* num_pos, float* avg_factor, float* centerness_denorm, void* workspace, void* stream);
+int sph2pob_point_coder_encode_f32(const float* points, const float* gt, float* distances, int64_t n, int box_dim, int64_t img_h, int64_t img_w,
+                                   int clamp, double max_dis, double eps, void* stream);
+int sph2pob_point_coder_decode_f32(const float* points, const float* distances, float* boxes, int64_t n, int box_dim, int64_t img_h, int64_t img_w,
+                                   float max_h, float max_w, void* stream);
+int sph2pob_point_coder_decode_bwd_f32(const float* points, const float* distances, const float* grad_boxes, float* grad_distances, int64_t n,
+                                       int box_dim, int64_t img_h, int64_t img_w, float max_h, float max_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,8 +9,8 @@ from .losses import (CrossEntropyLoss, FocalLoss, L1Loss, SmoothL1Loss, Sph2PobI
                      sigmoid_focal_loss, sph_bbox_loss, sph_delta_loss, sph_focal_loss, sph_gauss_bbox_loss, sph_softmax_loss)
 from .bbox.nms import (DetBBoxes, SphNMS, multiclass_nms, sph_get_bboxes, sph_softmax_bboxes, sph_softmax_scores,  # noqa: F401,E402
                        sph_test_bboxes)
-from .bbox.assigners import (AnchorTargets, SphMaxIoUAssigner, sph_anchor_targets, sph_rpn_targets, sph_sample_targets,  # noqa: F401,E402
-                             sph_train_targets)
-from .bbox.coder import DeltaXYWHASphBBoxCoder, DeltaXYWHSphBBoxCoder  # noqa: F401,E402
+from .bbox.assigners import (AnchorTargets, PointTargets, SphMaxIoUAssigner, sph_anchor_targets, sph_fcos_points,  # noqa: F401,E402
+                             sph_fcos_targets, sph_rpn_targets, sph_sample_targets, sph_train_targets)
+from .bbox.coder import DeltaXYWHASphBBoxCoder, DeltaXYWHSphBBoxCoder, DistancePointSphBBoxCoder  # noqa: F401,E402
 
 __version__ = '0.1.0'

@@ -33,6 +33,7 @@
 #include "sph2pob_delta_loss.hpp"
 #include "sph2pob_softmax.hpp"
 #include "sph2pob_sample.hpp"
+#include "sph2pob_point_targets.hpp"
 
 namespace {
 
@@ -1221,6 +1222,121 @@ int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, i
     for (int64_t b = 0; b < num_images; b++) { sp += std::max<int64_t>(num_pos[b], 1); sn += std::max<int64_t>(num_neg[b], 1); }
     avg_factor[0] = (float)(sp + sn);
     avg_factor_pos[0] = (float)sp;
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- point (FCOS) targets and the distance-point coder: the rows of sph2pob_point_targets.hpp, the kernels' arithmetic.  The
+// centerness sum is taken in double per image and then over the images in order (the workspace is not used) ----
+extern "C" {
+
+int sph2pob_point_targets_f32_cpu(const float* points, int64_t num_points, const int64_t* level_n, const float* range_lo, const float* range_hi,
+                                  const float* sample_extent, const float* norm_stride, int num_levels, const float* gt, const int64_t* gt_labels,
+                                  const int64_t* gt_offsets, int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int64_t img_h,
+                                  int64_t img_w, int64_t num_classes, int flags, int64_t* labels, int64_t* gt_inds, float* bbox_targets,
+                                  float* centerness, int64_t* num_pos, float* avg_factor, float* centerness_denorm, void*, void*) {
+    namespace PT = sph2pob_point;
+    if (int rc = PT::check_shape(num_points, level_n, num_levels, num_images, num_gt, k_max, box_dim, img_h, img_w, num_classes)) return rc;
+    const int64_t rows = num_images * num_points;
+    if (!range_lo || !range_hi || ((flags & SPH2POB_POINT_CENTER_SAMPLING) && !sample_extent) || ((flags & SPH2POB_POINT_NORM_ON_BBOX) && !norm_stride) ||
+        !avg_factor || !centerness_denorm || (num_images > 0 && (!gt_offsets || !num_pos)) ||
+        (rows > 0 && (!points || !labels || !gt_inds || !bbox_targets || !centerness)) ||
+        (rows > 0 && k_max > 0 && (!gt || !gt_labels))) return SPH2POB_ERR_NULL;
+    PT::Levels L;
+    if (int rc = PT::make_levels(level_n, range_lo, range_hi, sample_extent, norm_stride, num_levels, flags, &L)) return rc;
+    const bool center = (flags & SPH2POB_POINT_CENTER_SAMPLING) != 0;
+    const float W = (float)img_w, H = (float)img_h;
+    std::vector<double> sums((size_t)num_images, 0.0);
+    parallel_for(num_images, 1, [&](int64_t lo, int64_t hi) {
+        std::vector<PT::Gt> g;
+        for (int64_t b = lo; b < hi; b++) {
+            const int64_t off = gt_offsets[b];
+            const int k = PT::image_rows(off, gt_offsets[b + 1], num_gt, k_max);
+            g.resize((size_t)k);
+            for (int j = 0; j < k; j++) g[(size_t)j] = PT::gt_pixels(gt + (off + j) * box_dim, box_dim, W, H);
+            int64_t pos = 0;
+            double sum = 0.0;
+            for (int64_t p = 0; p < num_points; p++) {
+                const PT::LevelRow lv = PT::level_of_point(L, (int)p);
+                const float x = points[2 * p], y = points[2 * p + 1];
+                PT::Best best = PT::no_best();
+                for (int j = 0; j < k; j++) {
+                    const bool cand = center ? PT::candidate<true>(g[(size_t)j], x, y, lv.lo, lv.hi, lv.extent)
+                                             : PT::candidate<false>(g[(size_t)j], x, y, lv.lo, lv.hi, lv.extent);
+                    PT::offer(best, g[(size_t)j], j, cand);
+                }
+                float t[5];
+                const float cent = box_dim == 4 ? PT::target_row<4>(best, x, y, lv.norm, t) : PT::target_row<5>(best, x, y, lv.norm, t);
+                const int64_t r = b * num_points + p;
+                labels[r] = best.idx >= 0 ? gt_labels[off + best.idx] : num_classes;
+                gt_inds[r] = best.idx + 1;
+                centerness[r] = cent;
+                for (int c = 0; c < box_dim; c++) bbox_targets[r * box_dim + c] = t[c];
+                pos += best.idx >= 0;
+                sum += (double)cent;
+            }
+            num_pos[b] = pos;
+            sums[(size_t)b] = sum;
+        }
+    });
+    int64_t tot = 0;
+    double sum = 0.0;
+    for (int64_t b = 0; b < num_images; b++) { tot += num_pos[b]; sum += sums[(size_t)b]; }
+    PT::normalisers(tot, sum, avg_factor, centerness_denorm);
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// MODE as in the kernel: 0 encode, 1 decode, 2 decode backward
+template <int DIM, int MODE>
+void point_coder_rows(const float* points, const float* a, const float* g, float* out, int64_t n, const sph2pob_point::Image& im, bool clamp, float clamp_hi) {
+    namespace PT = sph2pob_point;
+    parallel_for(n, 1 << 12, [&](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; i++) {
+            float r[5];
+            if (MODE == 0) PT::encode_row<DIM>(points + 2 * i, a + i * DIM, im, clamp, clamp_hi, r);
+            else if (MODE == 1) PT::decode_row<DIM, false>(points + 2 * i, a + i * DIM, nullptr, im, r);
+            else PT::decode_row<DIM, true>(points + 2 * i, a + i * DIM, g + i * DIM, im, r);
+            for (int c = 0; c < DIM; c++) out[i * DIM + c] = r[c];
+        }
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_point_coder_encode_f32_cpu(const float* points, const float* gt, float* distances, int64_t n, int box_dim, int64_t img_h, int64_t img_w,
+                                       int clamp, double max_dis, double eps, void*) {
+    namespace PT = sph2pob_point;
+    const float hi = clamp ? (float)(max_dis - eps) : 0.0f;
+    if (int rc = PT::check_coder(points, gt, gt, distances, n, box_dim, img_h, img_w, hi, 0.0f)) return rc;
+    if (clamp != 0 && clamp != 1) return SPH2POB_ERR_OPTION;
+    const PT::Image im{(float)img_w, (float)img_h, -1.0f, -1.0f};
+    if (box_dim == 4) point_coder_rows<4, 0>(points, gt, nullptr, distances, n, im, clamp != 0, hi);
+    else point_coder_rows<5, 0>(points, gt, nullptr, distances, n, im, clamp != 0, hi);
+    return SPH2POB_OK;
+}
+
+int sph2pob_point_coder_decode_f32_cpu(const float* points, const float* distances, float* boxes, int64_t n, int box_dim, int64_t img_h,
+                                       int64_t img_w, float max_h, float max_w, void*) {
+    namespace PT = sph2pob_point;
+    if (int rc = PT::check_coder(points, distances, distances, boxes, n, box_dim, img_h, img_w, max_h, max_w)) return rc;
+    const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
+    if (box_dim == 4) point_coder_rows<4, 1>(points, distances, nullptr, boxes, n, im, false, 0.0f);
+    else point_coder_rows<5, 1>(points, distances, nullptr, boxes, n, im, false, 0.0f);
+    return SPH2POB_OK;
+}
+
+int sph2pob_point_coder_decode_bwd_f32_cpu(const float* points, const float* distances, const float* grad_boxes, float* grad_distances, int64_t n,
+                                           int box_dim, int64_t img_h, int64_t img_w, float max_h, float max_w, void*) {
+    namespace PT = sph2pob_point;
+    if (int rc = PT::check_coder(points, distances, grad_boxes, grad_distances, n, box_dim, img_h, img_w, max_h, max_w)) return rc;
+    const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
+    if (box_dim == 4) point_coder_rows<4, 2>(points, distances, grad_boxes, grad_distances, n, im, false, 0.0f);
+    else point_coder_rows<5, 2>(points, distances, grad_boxes, grad_distances, n, im, false, 0.0f);
     return SPH2POB_OK;
 }
 

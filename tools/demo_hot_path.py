@@ -105,7 +105,7 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
-              train_cfg=None, loss_bbox=None, softmax_head=False, rpn_cfg=None, rpn_seed=0):
+              train_cfg=None, loss_bbox=None, softmax_head=False, rpn_cfg=None, rpn_seed=0, fcos_cfg=None):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -123,8 +123,15 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     `rpn_cfg`: an RPN `train_cfg` with its RandomSampler (and nothing else of the above); the step is then an RPN training step,
     `sph_rpn_targets` (assignment + sampling on the device, `rpn_seed` a Python int or a () int64 device tensor) -> `sph_softmax_loss`
     on K = 2 logits per anchor without mining and `sph_delta_loss` on the encoded targets: the sampled `label_weights` and the device
-    `avg_factor` (the sampled count) feed the fused losses as they stand."""
+    `avg_factor` (the sampled count) feed the fused losses as they stand.
+    `fcos_cfg`: the step of an anchor-free head instead (`run_fcos_batch`, and nothing else of the above): a dict with the arguments
+    of `sph_fcos_targets` (`regress_ranges`, `strides`, optionally `center_sampling`, `center_sample_radius`, `norm_on_bbox`,
+    `box_version`)."""
     dev = 'cuda'
+    if fcos_cfg is not None:
+        if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None:
+            raise ValueError('fcos_cfg is a step of its own: sph_fcos_targets + sph_focal_loss + Sph2PobIoULoss on the point decode + BCE')
+        return run_fcos_batch(counts, num_classes, seed, reps, fcos_cfg, dev)
     if loss_bbox is not None and base_config:
         raise ValueError('base_config runs L1 on encoded deltas: no loss_bbox')
     if rpn_cfg is not None:
@@ -202,6 +209,77 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
 
 
 LEVEL_SHAPES = ((64, 128), (32, 64), (16, 32), (8, 16), (4, 8))   # the 512 x 1024 ERP at strides 8 ... 128
+
+FCOS_CFG = dict(regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8)), strides=(8, 16, 32, 64, 128))
+
+
+def fcos_step(points, gt, gt_labels, gt_offsets, cls_scores, bbox_preds, centernesses, *, num_classes, coder, loss_iou, img_shape=(512, 1024),
+              **fcos_cfg):
+    """SphFCOSHead.loss (sphdet/models/heads/sph_fcos_head.py:24-105) without its nonzero() / len(pos_inds): the targets of the
+    minibatch from `sph_fcos_targets`; classification `sph_focal_loss` on `labels` over the device `avg_factor`; regression
+    `Sph2PobIoULoss` on `coder.decode` of ALL flattened predictions and targets, weighted by the centerness targets (0 on the
+    background) over `centerness_denorm`; centerness torch's BCE-with-logits weighted by `labels < num_classes` over `avg_factor`
+    (weight_reduce_loss's `+ eps`).  GT as lists (gt_offsets None) or concatenated.  -> (loss_cls, loss_bbox, loss_centerness, targets)."""
+    t = S.sph_fcos_targets(points, gt, gt_labels, gt_offsets, num_classes=num_classes, img_shape=img_shape, **fcos_cfg)
+    images, dim = t.labels.size(0), t.bbox_targets.size(-1)
+    loss_cls = S.sph_focal_loss(cls_scores, t.labels, gamma=2.0, alpha=0.25, avg_factor=t.avg_factor)
+    flat_preds = torch.cat([p.permute(0, 2, 3, 1).reshape(images, -1, dim) for p in bbox_preds], dim=1)
+    flat_ctr = torch.cat([c.permute(0, 2, 3, 1).reshape(images, -1) for c in centernesses], dim=1)
+    pts = torch.cat(list(points)) if isinstance(points, (list, tuple)) else points
+    pred = coder.decode(pts, flat_preds, img_shape=img_shape)
+    target = coder.decode(pts, t.bbox_targets, img_shape=img_shape)
+    loss_bbox = loss_iou(pred.reshape(-1, dim), target.reshape(-1, dim), t.centerness_targets.reshape(-1), avg_factor=t.centerness_denorm)
+    pos = (t.labels < num_classes).to(flat_ctr.dtype)
+    bce = torch.nn.functional.binary_cross_entropy_with_logits(flat_ctr, t.centerness_targets, reduction='none')
+    loss_ctr = (bce * pos).sum() / (t.avg_factor + torch.finfo(torch.float32).eps)
+    return loss_cls, loss_bbox, loss_ctr, t
+
+
+def fcos_head_outputs(images, num_classes, dim=4, seed=0, device='cuda', shapes=LEVEL_SHAPES, strides=FCOS_CFG['strides'], norm_on_bbox=False):
+    """Synthetic outputs of an FCOS head in the head's NCHW, leaves: class logits N(-4, 2), positive distances (a few strides; in
+    strides with `norm_on_bbox`, as the head predicts them then) and centerness logits."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    cls = [(torch.randn((images, num_classes, h, w), generator=g, device=device) * 2 - 4).requires_grad_(True) for h, w in shapes]
+    box = [(torch.rand((images, dim, h, w), generator=g, device=device) * 4 * (1 if norm_on_bbox else s) + 0.5).requires_grad_(True)
+           for (h, w), s in zip(shapes, strides)]
+    ctr = [torch.randn((images, 1, h, w), generator=g, device=device).requires_grad_(True) for h, w in shapes]
+    return cls, box, ctr
+
+
+def run_fcos_batch(counts, num_classes, seed, reps, fcos_cfg, dev='cuda'):
+    """`run_batch(fcos_cfg=...)`: the FCOS training step on the 512 x 1024 ERP (10 912 points), `fcos_step` + backward."""
+    cfg = dict(FCOS_CFG, **fcos_cfg)
+    dim = cfg.get('box_version', 4)
+    g = torch.Generator().manual_seed(seed)
+    gts, labels = [], []
+    for k in counts:
+        u = torch.rand((k, 5), generator=g)
+        gts.append(torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85, u[:, 4] * 90], 1)[:, :dim].to(dev))
+        labels.append(torch.randint(0, num_classes, (k,), generator=g).to(dev))
+    points = S.sph_fcos_points(LEVEL_SHAPES, cfg['strides'], device=dev)
+    cls_scores, bbox_preds, centernesses = fcos_head_outputs(len(counts), num_classes, dim, seed, dev, norm_on_bbox=cfg.get('norm_on_bbox', False))
+    coder = S.DistancePointSphBBoxCoder(clip_border=True, box_version=dim)
+    loss_iou = S.Sph2PobIoULoss(mode='iou', loss_weight=1.0)
+    leaves = cls_scores + bbox_preds + centernesses
+
+    def step():
+        for x in leaves:
+            x.grad = None
+        loss_cls, loss_bbox, loss_ctr, t = fcos_step(points, gts, labels, None, cls_scores, bbox_preds, centernesses, num_classes=num_classes,
+                                                     coder=coder, loss_iou=loss_iou, **cfg)
+        (loss_cls + loss_bbox + loss_ctr).backward()
+        return loss_cls.detach(), loss_bbox.detach(), loss_ctr.detach(), t
+    step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        loss_cls, loss_bbox, loss_ctr, t = step()
+    torch.cuda.synchronize()
+    out = {'points': t.labels.size(1), 'images': len(counts), 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
+           'centerness_denorm': float(t.centerness_denorm), 'loss_cls': float(loss_cls), 'loss_bbox': float(loss_bbox),
+           'loss_centerness': float(loss_ctr), 'grads_finite': all(bool(torch.isfinite(x.grad).all()) for x in leaves), 'fcos': True,
+           'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
+    return out, dict(targets=t, points=points, gts=gts, labels=labels, cls_scores=cls_scores, bbox_preds=bbox_preds, centernesses=centernesses)
 
 
 def retina_level_anchors(device='cuda'):
