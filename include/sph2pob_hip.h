@@ -960,6 +960,54 @@ int sph2pob_point_coder_decode_f32(const float* points, const float* distances, 
 int sph2pob_point_coder_decode_bwd_f32(const float* points, const float* distances, const float* grad_boxes, float* grad_distances, int64_t n,
                                        int box_dim, int64_t img_h, int64_t img_w, float max_h, float max_w, void* stream);
 
+/* ---- batched inference for FCOS heads: class score x centerness, the point coder ---------------------------------------------------
+ * sph2pob_fcos_bboxes_f32 — what SphFCOSHead._get_bboxes_single / _bbox_post_process (sphdet/models/heads/sph_fcos_head.py:246-323,
+ * :205-244) compute per image and level, for B images: sph2pob_test_bboxes_f32 with a score factor and the distance-point coder.
+ * Ten launches whatever B is (the selection and the NMS kernels of sph2pob_test_bboxes_f32, one candidate-build kernel of its own),
+ * nothing read back, nothing allocated, capturable.  The arguments of sph2pob_test_bboxes_f32, with the anchor table and the delta
+ * coder's block (means_host ... ctr_clamp) replaced:
+ *   points        host array of L device pointers, (n_l, 2) fp32 pixel coordinates, 8-byte aligned, shared by the images
+ *   bbox_preds    the distances (l, t, r, b[, gamma]) in pixels, laid out like cls_scores with box_dim channels per point
+ *   centernesses  host array of L device pointers, laid out like cls_scores with ONE channel per point: NCHW (B, A, H_l, W_l) —
+ *                 point ai = p A + a of image b is element (b A + a) H_l W_l + p — or flat (B, n_l)
+ *   img_h, img_w  the coder's image (the ERP the pixels refer to); max_h, max_w: the clip bounds, a negative bound = that axis is
+ *                 not clipped — all four as sph2pob_point_coder_decode_f32 has them
+ *   activation    applies to BOTH cls_scores and centernesses: 1 = both are logits (the head's case), 0 = both are probabilities;
+ *                 the sigmoid is the one pinned for sph2pob_test_bboxes_f32
+ * Per image and level the candidates are selected on the CLASS SCORES ALONE, exactly as sph2pob_test_bboxes_f32 selects them
+ * (score > score_thr, the first nms_pre in (class score descending, candidate index ascending) order): threshold and top-k never
+ * see the centerness.  Each selected (point, class) then gets score = class score * factor, factor = the activated centerness of
+ * its point, ONE fp32 multiply, and the box sph2pob_point_coder_decode_f32 gives for its point and distances.  The NMS runs on the
+ * products (its order: product descending, ties by candidate position in the image's block, the levels concatenated, each in its
+ * selection order), the first max_per_img survive, and dets carries the product.  A product below score_thr stays a candidate.
+ * Special values: a centerness logit of -inf gives the factor +0 and the candidate is kept with the score +0; +inf gives 1.  A
+ * NaN centerness gives a NaN product, which is not filtered: it is made the quiet NaN with the sign bit clear (0x7fc00000), which the
+ * NMS key — it orders scores by their bit pattern — puts in front of every finite score, so such a candidate is kept, suppresses what
+ * overlaps it in its class, and is reported first with a NaN score.
+ *   prior_inds    the detection's point as an index into the concatenated levels
+ *   workspace     sph2pob_get_bboxes_workspace_bytes(level_n, num_levels, B, C, box_dim, nms_pre) bytes: the pipeline and its
+ *                 workspace are those of sph2pob_test_bboxes_f32
+ * Errors, checked in this order before anything is enqueued: box_dim -> SPH2POB_ERR_DIM; the variant, flags, class_agnostic and
+ * activation rules of sph2pob_test_bboxes_f32 -> SPH2POB_ERR_OPTION; num_levels, B, C, nms_pre, max_per_img as there ->
+ * SPH2POB_ERR_SIZE; a NULL table (centernesses included) -> SPH2POB_ERR_NULL; n_l, level_hw, K_cap as there -> SPH2POB_ERR_SIZE;
+ * img_h / img_w outside [1, 2^24] -> SPH2POB_ERR_SIZE; a NaN max_h / max_w -> SPH2POB_ERR_OPTION; a NULL table entry (a centerness
+ * pointer included), output or workspace -> SPH2POB_ERR_NULL.
+ * sph2pob_fcos_bboxes_h16: cls_scores, bbox_preds and centernesses of ONE 16-bit type (dtype: SPH2POB_DTYPE_*, checked first ->
+ * SPH2POB_ERR_OPTION), read in place; everything after the loads is fp32: the result has the bits of the _f32 call on fp32 copies.
+ */
+int sph2pob_fcos_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points,
+                            const void* const* centernesses, const int64_t* level_n, const int64_t* level_hw, int num_levels,
+                            int64_t num_images, int64_t num_classes, int box_dim, int activation, float score_thr, int64_t nms_pre,
+                            int64_t img_h, int64_t img_w, float max_h, float max_w, int variant_flags, int class_agnostic,
+                            float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds,
+                            int64_t* num_dets, void* workspace, void* stream);
+int sph2pob_fcos_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points,
+                            const void* const* centernesses, const int64_t* level_n, const int64_t* level_hw, int num_levels,
+                            int64_t num_images, int64_t num_classes, int box_dim, int activation, float score_thr, int64_t nms_pre,
+                            int64_t img_h, int64_t img_w, float max_h, float max_w, int variant_flags, int class_agnostic,
+                            float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds,
+                            int64_t* num_dets, void* workspace, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

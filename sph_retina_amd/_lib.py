@@ -49,7 +49,7 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_delta_loss_sum_f32', 'sph2pob_gauss_bbox_loss_sum_f32', 'sph2pob_softmax_loss_sum_f32',
               'sph2pob_softmax_loss_fwd_f32', 'sph2pob_softmax_loss_bwd_f32', 'sph2pob_softmax_scores_f32', 'sph2pob_softmax_bboxes_f32',
               'sph2pob_sample_targets_f32', 'sph2pob_point_targets_f32', 'sph2pob_point_coder_encode_f32', 'sph2pob_point_coder_decode_f32',
-              'sph2pob_point_coder_decode_bwd_f32']
+              'sph2pob_point_coder_decode_bwd_f32', 'sph2pob_fcos_bboxes_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp', 'sph2pob_gauss_bbox_loss.hpp', 'sph2pob_softmax.hpp', 'sph2pob_sample.hpp',
            'sph2pob_point_targets.hpp', 'sph2pob_class_levels.hpp', 'sph2pob_select.hpp', 'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
@@ -194,6 +194,10 @@ SIGNATURES = {
     # points, distances, [grad_boxes,] out, n, box_dim, img_h, img_w, max_h, max_w, stream
     'sph2pob_point_coder_decode_f32': [_c_f32p, _c_f32p, _c_f32p, _i64, _int, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
     'sph2pob_point_coder_decode_bwd_f32': [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _int, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
+    # level tables (cls, bbox, points, centernesses, n, hw), num_levels, B, C, box_dim, activation, score_thr, nms_pre, img_h, img_w, max_h,
+    # max_w, variant_flags, class_agnostic, iou_threshold, max_per_img, 4 outputs, workspace, stream
+    'sph2pob_fcos_bboxes_f32': [ctypes.c_void_p] * 6 + [_int, _i64, _i64, _int, _int, ctypes.c_float, _i64, _i64, _i64, ctypes.c_float,
+                                ctypes.c_float, _int, _int, ctypes.c_float, _i64] + [ctypes.c_void_p] * 6,
     'sph2pob_coder_encode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int,
                                  ctypes.c_void_p],
     'sph2pob_coder_decode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int, _int,
@@ -209,7 +213,7 @@ SIGNATURES = {
 H16_DTYPES = {'float16': 1, 'bfloat16': 2}
 for _name in ('focal_loss_sum', 'bbox_loss_sum', 'delta_loss_sum', 'gauss_bbox_loss_sum'):
     SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_c_f32p, _int, _int, ctypes.c_void_p]
-for _name in ('get_bboxes', 'test_bboxes', 'softmax_scores', 'softmax_bboxes'):
+for _name in ('get_bboxes', 'test_bboxes', 'softmax_scores', 'softmax_bboxes', 'fcos_bboxes'):
     SIGNATURES[f'sph2pob_{_name}_h16'] = SIGNATURES[f'sph2pob_{_name}_f32'][:-1] + [_int, ctypes.c_void_p]
 _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_target_arch': ctypes.c_char_p, 'sph2pob_error_string': ctypes.c_char_p,
              'sph2pob_nms_workspace_bytes': ctypes.c_int64, 'sph2pob_nms_segmented_workspace_bytes': ctypes.c_int64, 'sph2pob_assign_workspace_bytes': ctypes.c_int64,

@@ -16,8 +16,10 @@ Softmax heads (`use_sigmoid_cls=False`: SphSSDHead, the two-channel SphRPNHead) 
 `softmax_bboxes.py`: `sph_softmax_bboxes` is `sph_test_bboxes` on K = C + 1 logits per anchor, `sph_softmax_scores` the
 probabilities alone.  Both entries here keep refusing `activation='softmax'`.
 
+FCOS heads (a centerness per point as the score factor, the distance-point coder) have `sph_fcos_bboxes` in `fcos_bboxes.py`.
+
 The per-image API (`multiclass_nms`, or `filter` + `bbox_coder.decode` + `sph_batched_nms` on each image and level) keeps serving
-what none of these entries does: score factors, `with_nms=False`, the `'xinyuan'` / `kent_iou` calculators, the reference
+what none of these entries does: score factors of anchor-based heads, `with_nms=False`, the `'xinyuan'` / `kent_iou` calculators, the reference
 arithmetic and more than 16 384 candidates per image.
 """
 import ctypes
@@ -72,7 +74,8 @@ def _level(t, name, per_anchor, n, images, native=False):
 def _refuse_head_options(who, activation, score_factors, with_nms, nms):
     """The head options neither entry serves -> NotImplementedError; returns the nms dict without its 'type'."""
     if score_factors is not None:
-        raise NotImplementedError(f'{who} does not take score factors (FCOS-style heads): ' + _PER_IMAGE)
+        raise NotImplementedError(f'{who} does not take score factors (FCOS-style heads): sph_fcos_bboxes is the batched entry for a '
+                                  'centerness per point; or ' + _PER_IMAGE)
     if activation == 'softmax':
         raise NotImplementedError(f'{who} implements sigmoid heads only (use_sigmoid_cls=True), not softmax: sph_softmax_bboxes is the batched '
                                   'entry for softmax heads; or ' + _PER_IMAGE)
@@ -91,11 +94,46 @@ def _refuse_reference_arithmetic(who, arithmetic):
         raise NotImplementedError(f"{who} runs the default arithmetic only, not arithmetic='reference': " + _PER_IMAGE)
 
 
-def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder, score_thr, nms_pre, iou_threshold, max_per_img, box_version,
-         activation, wh_ratio_clip):
-    """The level marshalling and the call the entries share; `nms_args`: what `symbol` takes between ctr_clamp and iou_threshold.
+def _delta_block(bbox_coder, wh_ratio_clip):
+    """The coder block of the delta-coder entries, as a function of the checked box dimension:
+    (means, stds, max_ratio, coder_flags, ctr_clamp)."""
+    def block(dim):
+        means = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.means])
+        stds = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.stds])
+        flags = (1 if bbox_coder.clip_border else 0) | (2 if bbox_coder.add_ctr_clamp else 0)
+        return means, stds, float(abs(math.log(wh_ratio_clip))), flags, float(bbox_coder.ctr_clamp)
+    return block
+
+
+def _priors_level(t, l, dim, points):
+    """A level's priors as contiguous fp32: (n, dim) anchors, or (n, 2) points on an 8-byte boundary (the kernel reads a point as
+    one 8-byte load)."""
+    prior = G.as_f32_nograd(t[..., :2 if points else dim])
+    if points:
+        if prior.dim() != 2 or prior.size(1) != 2:
+            raise ValueError(f'level {l}: points must be (n, 2), got {tuple(t.shape)}')
+        if prior.data_ptr() % 8:
+            prior = prior.clone()
+    return prior
+
+
+def _factor_level(t, l, n, images, native, hw):
+    """A level's score factors, (B, A, H, W), (B, n) or (B, n, 1), in the layout kind `hw` of its cls_scores."""
+    t, hw_f = _level(t.unsqueeze(-1) if t.dim() == 2 else t, f'centernesses[{l}]', 1, n, images, native)
+    if hw != hw_f:
+        raise ValueError(f'level {l}: cls_scores and centernesses must use the same layout')
+    return t
+
+
+def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_priors, bbox_coder, score_thr, nms_pre, iou_threshold, max_per_img, box_version,
+         activation, coder_block, factors=None):
+    """The level marshalling and the call the entries share.  `coder_block(dim)`: what `symbol` takes between nms_pre and
+    `nms_args` (`_delta_block` for the delta coders); `nms_args`: what it takes from there to iou_threshold.
     `activation='softmax'` (sph_softmax_bboxes only): cls_scores hold K = C + 1 logits per anchor, `symbol` has no activation argument
-    and sizes its workspace itself."""
+    and sizes its workspace itself.  `factors` (sph_fcos_bboxes only): one score factor per point and level, laid out like
+    cls_scores; `mlvl_priors` are then the levels' (n, 2) points instead of (n, dim) anchors and `symbol` takes the factor table
+    behind them."""
+    points = factors is not None
     softmax = activation == 'softmax'
     nms_pre, max_per_img = int(nms_pre), int(max_per_img)
     if nms_pre <= 0:
@@ -105,23 +143,25 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
     dim = int(box_version)
     if dim not in (4, 5) or getattr(bbox_coder, 'box_dim', None) != dim:
         raise ValueError(f'box_version must be 4 or 5 and match the bbox_coder, got {box_version} and {type(bbox_coder).__name__}')
-    levels = len(mlvl_anchors)
-    if not (1 <= levels <= _MAX_LEVELS) or len(cls_scores) != levels or len(bbox_preds) != levels:
-        raise ValueError(f'{who} takes 1 to {_MAX_LEVELS} levels with one cls_scores / bbox_preds / anchors tensor each')
-    tensors = list(cls_scores) + list(bbox_preds) + list(mlvl_anchors)
+    levels = len(mlvl_priors)
+    if not (1 <= levels <= _MAX_LEVELS) or len(cls_scores) != levels or len(bbox_preds) != levels or (points and len(factors) != levels):
+        raise ValueError(f'{who} takes 1 to {_MAX_LEVELS} levels with one cls_scores / bbox_preds / ' +
+                         ('centernesses / points' if points else 'anchors') + ' tensor each')
+    heads = list(cls_scores) + list(bbox_preds) + (list(factors) if points else [])
+    tensors = heads + list(mlvl_priors)
     G.require_hip(*tensors)
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f'{who}: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in tensors})))
     dev = tensors[0].device
     images = cls_scores[0].size(0)
     num_classes = None
-    code = G.h16_dtype_code(list(cls_scores) + list(bbox_preds))   # 16-bit GPU levels: read where they are, one dtype for both
-    held, cls_p, box_p, anc_p, ns, hws = [], [], [], [], [], []   # held: converted copies stay alive until the call is enqueued
+    code = G.h16_dtype_code(heads)   # 16-bit GPU levels: read where they are, one dtype for all of them
+    held, cls_p, box_p, anc_p, ctr_p, ns, hws = [], [], [], [], [], [], []   # held: converted copies stay alive until the call is enqueued
     for l in range(levels):
-        anc = G.as_f32_nograd(mlvl_anchors[l][..., :dim])
+        anc = _priors_level(mlvl_priors[l], l, dim, points)
         n = anc.size(0)
         if anc.dim() != 2 or n == 0 or cls_scores[l].numel() % (images * n) != 0:
-            raise ValueError(f'level {l}: anchors {tuple(mlvl_anchors[l].shape)} do not match cls_scores {tuple(cls_scores[l].shape)}')
+            raise ValueError(f'level {l}: anchors {tuple(mlvl_priors[l].shape)} do not match cls_scores {tuple(cls_scores[l].shape)}')
         c = cls_scores[l].numel() // (images * n)
         if num_classes is None:
             num_classes = c
@@ -133,6 +173,10 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
         bp, hw_b = _level(bbox_preds[l], f'bbox_preds[{l}]', dim, n, images, bool(code))
         if hw != hw_b:
             raise ValueError(f'level {l}: cls_scores and bbox_preds must use the same layout')
+        if points:
+            ct = _factor_level(factors[l], l, n, images, bool(code), hw)
+            held.append(ct)
+            ctr_p.append(ct.data_ptr())
         held += [cs, bp, anc]
         cls_p.append(cs.data_ptr()); box_p.append(bp.data_ptr()); anc_p.append(anc.data_ptr()); ns.append(n); hws.append(hw)
     if softmax:
@@ -154,16 +198,14 @@ def _run(who, symbol, nms_args, cls_scores, bbox_preds, mlvl_anchors, bbox_coder
         if need <= 0:
             raise ValueError(f'{who}: these shapes are outside the limits of {symbol} (include/sph2pob_hip.h)')
         ws = G.scratch(dev, need)
-    means = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.means])
-    stds = (ctypes.c_float * dim)(*[float(v) for v in bbox_coder.stds])
-    flags = (1 if bbox_coder.clip_border else 0) | (2 if bbox_coder.add_ctr_clamp else 0)
+    coder_args = coder_block(dim)
     if code:   # the _h16 sibling: the same arguments with the levels' dtype in front of the stream
         symbol, tail = symbol[:-len('_f32')] + '_h16', (code,)
     else:
         tail = ()
-    G.call(symbol, dev, ptrs(*cls_p), ptrs(*box_p), ptrs(*anc_p), level_n, i64s(*hws), levels, images, num_classes, dim,
-           *(() if softmax else (int(activation == 'sigmoid'),)), float(score_thr), nms_pre, means, stds, float(abs(math.log(wh_ratio_clip))), flags,
-           float(bbox_coder.ctr_clamp), *nms_args, float(iou_threshold), max_per_img, G.ptr(out.dets),
+    G.call(symbol, dev, ptrs(*cls_p), ptrs(*box_p), ptrs(*anc_p), *((ptrs(*ctr_p),) if points else ()), level_n, i64s(*hws), levels, images,
+           num_classes, dim, *(() if softmax else (int(activation == 'sigmoid'),)), float(score_thr), nms_pre, *coder_args, *nms_args,
+           float(iou_threshold), max_per_img, G.ptr(out.dets),
            G.ptr(out.labels), G.ptr(out.prior_inds), out.num_dets.data_ptr(), G.ptr(ws), *tail, G.raw_stream_of(dev))
     return out
 
@@ -187,7 +229,7 @@ def sph_get_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, score_th
         raise NotImplementedError(f'sph_get_bboxes serves the sph2pob_efficient / sph2pob_standard calculators, not {variant}: ' + _PER_IMAGE)
     _refuse_reference_arithmetic(who, arithmetic)
     return _run(who, 'sph2pob_get_bboxes_f32', (G.VARIANTS[variant],), cls_scores, bbox_preds, mlvl_anchors, bbox_coder, score_thr, nms_pre,
-                nms_cfg.get('iou_threshold', 0.5), max_per_img, box_version, activation, wh_ratio_clip)
+                nms_cfg.get('iou_threshold', 0.5), max_per_img, box_version, activation, _delta_block(bbox_coder, wh_ratio_clip))
 
 
 _TEST_CFG_KEYS = ('score_thr', 'nms_pre', 'nms', 'max_per_img', 'iou_calculator', 'box_formator', 'min_bbox_size')
@@ -238,4 +280,4 @@ def sph_test_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, test_cf
     _refuse_reference_arithmetic(who, cfg.get('arithmetic'))
     return _run(who, 'sph2pob_test_bboxes_f32', (G.VARIANTS[variant], int(class_agnostic)), cls_scores, bbox_preds, mlvl_anchors, bbox_coder,
                 cfg.get('score_thr', 0.05), cfg.get('nms_pre', 1000), nms_cfg.get('iou_threshold', 0.5), cfg.get('max_per_img', 100), box_version,
-                activation, cfg.get('wh_ratio_clip', 16 / 1000))
+                activation, _delta_block(bbox_coder, cfg.get('wh_ratio_clip', 16 / 1000)))

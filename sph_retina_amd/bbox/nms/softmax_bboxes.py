@@ -18,7 +18,7 @@ import ctypes
 import torch
 
 from ... import _torch_glue as G
-from .get_bboxes import _MAX_LEVELS, _OTHER_KEYS, _SOFTMAX_MAX_K, _TEST_CFG_KEYS, _refuse_head_options, _refuse_reference_arithmetic, _run, _test_variant
+from .get_bboxes import _MAX_LEVELS, _OTHER_KEYS, _SOFTMAX_MAX_K, _TEST_CFG_KEYS, _delta_block, _refuse_head_options, _refuse_reference_arithmetic, _run, _test_variant
 
 
 def sph_softmax_scores(cls_scores, *, num_classes):
@@ -84,4 +84,4 @@ def sph_softmax_bboxes(cls_scores, bbox_preds, mlvl_anchors, *, bbox_coder, test
     _refuse_reference_arithmetic(who, cfg.get('arithmetic'))
     return _run(who, 'sph2pob_softmax_bboxes_f32', (G.VARIANTS[variant], int(class_agnostic)), cls_scores, bbox_preds, mlvl_anchors, bbox_coder,
                 cfg.get('score_thr', 0.05), cfg.get('nms_pre', 1000), nms_cfg.get('iou_threshold', 0.5), cfg.get('max_per_img', 100), box_version,
-                'softmax', cfg.get('wh_ratio_clip', 16 / 1000))
+                'softmax', _delta_block(bbox_coder, cfg.get('wh_ratio_clip', 16 / 1000)))

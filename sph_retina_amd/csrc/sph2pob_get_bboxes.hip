@@ -2,9 +2,12 @@
 // level) exact top-k of the class scores above a threshold, read from the head's own layout; gather + decode of the selected
 // candidates; then the batched NMS stage of sph2pob_nms.hip.  Replaces SphRetinaHead._get_bboxes_single / _bbox_post_process
 // (sphdet/models/heads/sph_retina_head.py:101-216, :22-99) and filter_scores_and_topk (mmdet/core/utils/misc.py:119-165) for
-// B images with a number of launches that does not depend on B, and without a host read.  gfx950 only.
+// B images with a number of launches that does not depend on B, and without a host read.  gfx950 only.  sph2pob_fcos_bboxes_f32 is
+// the same pipeline for SphFCOSHead (sph_fcos_head.py:246-323, :205-244): the selection on the class scores alone, then a cand_build
+// of its own that decodes from points and multiplies the class score by the point's centerness.
 //
 // Selection, per (image, level), on the unique 64-bit keys (descending score bits << 32 | flat index):
+//   zero          the histograms and the per-(image, level) records
 //   topk_hist     stream 1: scores above the threshold -> a histogram of score_bin() (LDS per workgroup, integer atomics into the
 //                 level's global histogram: the totals do not depend on the order of arrival)
 //   topk_cut      the bin in which the nms_pre-th key falls, how many keys are wanted and how many lie in the bins up to it
@@ -21,11 +24,13 @@
 #include "../../include/sph2pob_hip.h"
 #include "sph2pob_coder.hpp"
 #include "sph2pob_get_bboxes.hpp"   // (declares the NMS stage, sph2pob_nms_batch_launch)
+#include "sph2pob_point_targets.hpp"   // (the point coder's decode_row)
 
 namespace {
 
 using namespace sph2pob_gb;
 namespace C = sph2pob_coder;
+namespace PT = sph2pob_point;
 
 constexpr int kSelBlock = 256, kSelIters = 16, kChunk = kSelBlock * 4 * kSelIters;   // 16 384 scores per workgroup
 constexpr int kResBlock = 1024, kRadixBits = 11, kRadix = 1 << kRadixBits;
@@ -81,6 +86,21 @@ __device__ __forceinline__ void stream_chunk(const Level& lv, int64_t b, int chu
             if (++p == lv.hw) { p = 0; ch++; }
         }
     }
+}
+
+// Launch 1: the histograms and the per-(image, level) records start every call at zero.  A kernel on the call's stream, not a memset
+// node: a captured call is then kernels only (a graph of this pipeline faulted on its second replay while launch 1
+// was hipMemsetAsync).  V: int4 — 16-byte stores, the zeroed prefix is a multiple of 256 bytes — or int for a workspace whose base
+// is not 16-byte aligned
+constexpr int kZeroBlock = 256, kZeroGridMax = 1024;
+template <class V>
+__global__ __launch_bounds__(kZeroBlock) void zero_kernel(V* __restrict__ p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * kZeroBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kZeroBlock) p[i] = V{};
+}
+template <class V>
+void launch_zero(void* p, int64_t bytes, hipStream_t s) {
+    const int64_t n = bytes / (int64_t)sizeof(V), blocks = (n + kZeroBlock - 1) / kZeroBlock;
+    hipLaunchKernelGGL(zero_kernel<V>, dim3((unsigned)(blocks < kZeroGridMax ? blocks : kZeroGridMax)), dim3(kZeroBlock), 0, s, (V*)p, n);
 }
 
 template <class T>
@@ -217,14 +237,11 @@ __global__ __launch_bounds__(kResBlock) void topk_resolve_kernel(Levels L, const
     }
 }
 
-// One lane per selected key: its rank among the level's selection (tiles of the selection in LDS), then gather + decode.
+// One lane per selected key: its rank among the level's selection (tiles of the selection in LDS).  The part of cand_build the coders
+// share: false for a lane (or a whole workgroup) without a key; else `mine` is the lane's key and `at` its row of the candidate block
 constexpr int kBuildBlock = 256;
-template <int DIM, class T>
-__global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const Meta* __restrict__ meta, const unsigned long long* __restrict__ sel,
-                                                               int num_classes, C::Norm nm, float max_ratio, int coder_flags, float ctr_clamp,
-                                                               float* __restrict__ boxes, float* __restrict__ scores, int64_t* __restrict__ labels,
-                                                               int* __restrict__ prior, int* __restrict__ counts) {
-    __shared__ unsigned long long tile[kBuildBlock];
+__device__ __forceinline__ bool cand_place(const Levels& L, const Meta* __restrict__ meta, const unsigned long long* __restrict__ sel,
+                                           int* __restrict__ counts, unsigned long long (&tile)[kBuildBlock], unsigned long long& mine, int64_t& at) {
     const int l = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
     const Meta* mb = meta + (int64_t)b * L.num;
     int off = 0, cap_off = 0, all = 0;
@@ -235,10 +252,10 @@ __global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const
     }
     if (blockIdx.x == 0 && l == 0 && t == 0) counts[b] = all;
     const int want = mb[l].want;
-    if ((int)blockIdx.x * kBuildBlock >= want) return;   // workgroup-uniform
+    if ((int)blockIdx.x * kBuildBlock >= want) return false;   // workgroup-uniform
     const unsigned long long* in = sel + (int64_t)b * L.k_cap + cap_off;
     const int i = blockIdx.x * kBuildBlock + t;
-    const unsigned long long mine = i < want ? in[i] : ~0ull;
+    mine = i < want ? in[i] : ~0ull;
     int rank = 0;
     for (int j0 = 0; j0 < want; j0 += kBuildBlock) {
         __syncthreads();
@@ -247,7 +264,21 @@ __global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const
 #pragma unroll 8
         for (int j = 0; j < kBuildBlock; j++) rank += tile[j] < mine ? 1 : 0;
     }
-    if (i >= want) return;
+    at = (int64_t)b * L.k_cap + off + rank;
+    return i < want;
+}
+
+// the delta coders: anchor and deltas gathered from the head layout, decode_one()
+template <int DIM, class T>
+__global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const Meta* __restrict__ meta, const unsigned long long* __restrict__ sel,
+                                                               int num_classes, C::Norm nm, float max_ratio, int coder_flags, float ctr_clamp,
+                                                               float* __restrict__ boxes, float* __restrict__ scores, int64_t* __restrict__ labels,
+                                                               int* __restrict__ prior, int* __restrict__ counts) {
+    __shared__ unsigned long long tile[kBuildBlock];
+    unsigned long long mine;
+    int64_t at;
+    if (!cand_place(L, meta, sel, counts, tile, mine, at)) return;
+    const int l = blockIdx.y, b = blockIdx.z;
     const Level& lv = L.lv[l];
     const unsigned flat = (unsigned)mine;
     const int ai = (int)(flat / (unsigned)num_classes), c = (int)(flat - (unsigned)ai * (unsigned)num_classes);
@@ -256,10 +287,40 @@ __global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const
     for (int k = 0; k < DIM; k++) p[k] = lv.anchors[(int64_t)ai * DIM + k];
     gather_deltas<DIM, T>(lv, b, ai, d);
     C::decode_one<DIM, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr);
-    const int64_t at = (int64_t)b * L.k_cap + off + rank;
 #pragma unroll
     for (int k = 0; k < DIM; k++) boxes[at * DIM + k] = box[k];
     scores[at] = score_of_desc_bits((unsigned)(mine >> 32));
+    labels[at] = c;
+    prior[at] = lv.prior_off + ai;
+}
+
+// The point coder with a score factor (FCOS heads, sph2pob_fcos_bboxes_f32): Level::anchors holds the level's (n, 2) points, the
+// distances are gathered like deltas, the centerness like a one-channel score; the candidate's score is the class score the key
+// carries times activate(centerness), one fp32 multiply.  The centerness pointers come as a table of their own (the level table
+// keeps its size for the other kernels), read with the workgroup-uniform level index
+template <int DIM, class T>
+__global__ __launch_bounds__(kBuildBlock) void cand_build_points_kernel(Levels L, Factors F, const Meta* __restrict__ meta,
+                                                                      const unsigned long long* __restrict__ sel, int num_classes, int activation,
+                                                                      PT::Image im, float* __restrict__ boxes, float* __restrict__ scores,
+                                                                      int64_t* __restrict__ labels, int* __restrict__ prior, int* __restrict__ counts) {
+    __shared__ unsigned long long tile[kBuildBlock];
+    unsigned long long mine;
+    int64_t at;
+    if (!cand_place(L, meta, sel, counts, tile, mine, at)) return;
+    const int l = blockIdx.y, b = blockIdx.z;
+    const Level& lv = L.lv[l];
+    const unsigned flat = (unsigned)mine;
+    const int ai = (int)(flat / (unsigned)num_classes), c = (int)(flat - (unsigned)ai * (unsigned)num_classes);
+    if (flat >= (unsigned)lv.count) return;   // a guard only: every selected key carries an index of its level
+    const float2 xy = reinterpret_cast<const float2*>(lv.anchors)[ai];
+    const float pt[2] = {xy.x, xy.y};
+    float d[5], box[5];
+    gather_deltas<DIM, T>(lv, b, ai, d);
+    const float factor = activate(gather_factor<T>(lv, F.p[l], b, ai), activation);
+    PT::decode_row<DIM, false>(pt, d, nullptr, im, box);
+#pragma unroll
+    for (int k = 0; k < DIM; k++) boxes[at * DIM + k] = box[k];
+    scores[at] = factor_score(score_of_desc_bits((unsigned)(mine >> 32)), factor);
     labels[at] = c;
     prior[at] = lv.prior_off + ai;
 }
@@ -287,13 +348,33 @@ Ws make_ws(void* workspace, const Levels& L, int64_t B, int box_dim) {
     return w;
 }
 
-int launch_status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPH2POB_OK : (int)e;
-}
-
 // TS: the element type of cls_scores, TD: of bbox_preds (anchors and every output are fp32 / int64 whatever they are).  The public
 // entries read both as one type; the softmax entries select on fp32 probabilities and gather the head's own deltas
+// The ten launches on a checked level table: the selection on the class scores, `build(w, grid, s)` — the launch of the coder's
+// cand_build — and the NMS stage
+template <class TS, class Build>
+int pipeline(const Levels& L, int64_t num_images, int box_dim, int activation, float score_thr, int64_t nms_pre, int variant_flags,
+             int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets,
+             void* workspace, void* stream, Build&& build) {
+    if (!num_dets || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = (int)num_images;
+    const Ws w = make_ws(workspace, L, B, box_dim);
+    const int pre = (int)(nms_pre < ((int64_t)1 << 30) ? nms_pre : ((int64_t)1 << 30));
+    if ((reinterpret_cast<uintptr_t>(w.hist) & 15) == 0) launch_zero<int4>(w.hist, w.zero_bytes, s);
+    else launch_zero<int>(w.hist, w.zero_bytes, s);
+    hipLaunchKernelGGL(topk_hist_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.hist);
+    hipLaunchKernelGGL(topk_cut_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, pre, (const int*)w.hist, w.meta);
+    hipLaunchKernelGGL(topk_compact_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.meta, w.buf);
+    hipLaunchKernelGGL(topk_resolve_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.buf, w.sel);
+    int max_cap = 0;
+    for (int l = 0; l < L.num; l++) max_cap = L.lv[l].cap > max_cap ? L.lv[l].cap : max_cap;
+    build(w, dim3((max_cap + kBuildBlock - 1) / kBuildBlock, L.num, B), s);
+    if (int rc = launch_status()) return rc;
+    return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant_flags, class_agnostic, iou_threshold,
+                                    max_per_img, w.nms, dets, labels, prior_inds, num_dets, s);
+}
+
 template <class TS, class TD = TS>
 int test_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
                 const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
@@ -304,29 +385,40 @@ int test_bboxes(const void* const* cls_scores, const void* const* bbox_preds, co
     if (int rc = make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
                              variant_flags, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, kChunk, &L))
         return rc;
-    if (!num_dets || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
-    hipStream_t s = (hipStream_t)stream;
-    const int B = (int)num_images;
-    const Ws w = make_ws(workspace, L, B, box_dim);
-    const int pre = (int)(nms_pre < ((int64_t)1 << 30) ? nms_pre : ((int64_t)1 << 30));
-    if (hipMemsetAsync(w.hist, 0, (size_t)w.zero_bytes, s) != hipSuccess) return (int)hipGetLastError();
-    hipLaunchKernelGGL(topk_hist_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.hist);
-    hipLaunchKernelGGL(topk_cut_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, pre, (const int*)w.hist, w.meta);
-    hipLaunchKernelGGL(topk_compact_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.meta, w.buf);
-    hipLaunchKernelGGL(topk_resolve_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.buf, w.sel);
-    int max_cap = 0;
-    for (int l = 0; l < L.num; l++) max_cap = L.lv[l].cap > max_cap ? L.lv[l].cap : max_cap;
     const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
-    const dim3 bgrid((max_cap + kBuildBlock - 1) / kBuildBlock, L.num, B);
-    if (box_dim == 4)
-        hipLaunchKernelGGL((cand_build_kernel<4, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                           (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
-    else
-        hipLaunchKernelGGL((cand_build_kernel<5, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                           (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
-    if (int rc = launch_status()) return rc;
-    return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant_flags, class_agnostic, iou_threshold,
-                                    max_per_img, w.nms, dets, labels, prior_inds, num_dets, s);
+    return pipeline<TS>(L, num_images, box_dim, activation, score_thr, nms_pre, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
+                        prior_inds, num_dets, workspace, stream, [&](const Ws& w, dim3 bgrid, hipStream_t s) {
+        if (box_dim == 4)
+            hipLaunchKernelGGL((cand_build_kernel<4, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+                               (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
+        else
+            hipLaunchKernelGGL((cand_build_kernel<5, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+                               (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
+    });
+}
+
+// T: the element type of cls_scores, bbox_preds and centernesses (points and every output are fp32 / int64)
+template <class T>
+int fcos_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points, const void* const* centernesses,
+                const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                float score_thr, int64_t nms_pre, int64_t img_h, int64_t img_w, float max_h, float max_w, int variant_flags, int class_agnostic,
+                float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace,
+                void* stream) {
+    Levels L;
+    Factors F;
+    if (int rc = make_point_levels(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim,
+                                   activation, variant_flags, class_agnostic, nms_pre, max_per_img, img_h, img_w, max_h, max_w, kChunk, &L, &F))
+        return rc;
+    const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
+    return pipeline<T>(L, num_images, box_dim, activation, score_thr, nms_pre, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
+                       prior_inds, num_dets, workspace, stream, [&](const Ws& w, dim3 bgrid, hipStream_t s) {
+        if (box_dim == 4)
+            hipLaunchKernelGGL((cand_build_points_kernel<4, T>), bgrid, dim3(kBuildBlock), 0, s, L, F, (const Meta*)w.meta,
+                               (const unsigned long long*)w.sel, (int)num_classes, activation, im, w.boxes, w.scores, w.labels, w.prior, w.counts);
+        else
+            hipLaunchKernelGGL((cand_build_points_kernel<5, T>), bgrid, dim3(kBuildBlock), 0, s, L, F, (const Meta*)w.meta,
+                               (const unsigned long long*)w.sel, (int)num_classes, activation, im, w.boxes, w.scores, w.labels, w.prior, w.counts);
+    });
 }
 
 }  // namespace
@@ -403,6 +495,31 @@ int sph2pob_get_bboxes_h16(const void* const* cls_scores, const void* const* bbo
     return sph2pob_test_bboxes_h16(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
                                    score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, 0, iou_threshold,
                                    max_per_img, dets, labels, prior_inds, num_dets, workspace, dtype, stream);
+}
+
+// FCOS heads: the selection on the class scores alone, the point coder, score = class score * centerness
+int sph2pob_fcos_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points, const void* const* centernesses,
+                            const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim,
+                            int activation, float score_thr, int64_t nms_pre, int64_t img_h, int64_t img_w, float max_h, float max_w,
+                            int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
+                            int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
+    return fcos_bboxes<float>(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                              score_thr, nms_pre, img_h, img_w, max_h, max_w, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
+                              prior_inds, num_dets, workspace, stream);
+}
+
+int sph2pob_fcos_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points, const void* const* centernesses,
+                            const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim,
+                            int activation, float score_thr, int64_t nms_pre, int64_t img_h, int64_t img_w, float max_h, float max_w,
+                            int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
+                            int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream) {
+    if (dtype != SPH2POB_DTYPE_F16 && dtype != SPH2POB_DTYPE_BF16) return SPH2POB_ERR_OPTION;
+    auto run = [&](auto t) {
+        return fcos_bboxes<decltype(t)>(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim,
+                                        activation, score_thr, nms_pre, img_h, img_w, max_h, max_w, variant_flags, class_agnostic, iou_threshold,
+                                        max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+    };
+    return dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
 }
 
 }  // extern "C"

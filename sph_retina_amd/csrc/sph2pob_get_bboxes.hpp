@@ -195,4 +195,48 @@ SPHG_DEV void gather_deltas(const Level& lv, int64_t b, int ai, float* d) {
     }
 }
 
+// ---- score factors (FCOS heads: sph2pob_fcos_bboxes_f32) ----
+// The centerness tensors of the levels, one channel per point, laid out like cls_scores: NCHW (B, A, H, W) or flat (B, n).  A table
+// of its own, so that Level keeps its size for the entries without a factor
+struct Factors { const void* p[kMaxLevels]; };
+
+// the factor of point `ai` of image b, widened to fp32: element (b A + a) HW + p of the NCHW layout (ai = p A + a), b n + ai of the flat one
+template <class T = float>
+SPHG_DEV float gather_factor(const Level& lv, const void* factors, int64_t b, int ai) {
+    const T* f = reinterpret_cast<const T*>(factors);
+    if (lv.sp > 0) {
+        const int p = ai / lv.a, a = ai - p * lv.a;
+        return (float)f[(b * lv.a + a) * (int64_t)lv.sp + p];
+    }
+    return (float)f[b * lv.n + ai];
+}
+
+// the score a candidate goes into the NMS with and is reported with: one fp32 multiply.  A NaN product (a NaN centerness) becomes the
+// quiet NaN with the sign bit clear, whatever sign the library's expf left it: the NMS key orders scores by their bits, and the kernel
+// and its twin must order alike
+SPHG_DEV float factor_score(float class_score, float factor) {
+    const float s = class_score * factor;
+    return s != s ? float_of(0x7fc00000u) : s;
+}
+
+// Argument checks of sph2pob_fcos_bboxes_f32 and its twin, in the documented order: the shapes as make_level_shapes has them, the
+// coder's image (check_coder's rules: the size, then a NaN bound), then every level pointer.  Level::anchors holds the points
+inline int make_point_levels(const void* const* cls, const void* const* bbox, const void* const* points, const void* const* factors,
+                             const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim,
+                             int activation, int variant, int class_agnostic, int64_t nms_pre, int64_t max_per_img, int64_t img_h, int64_t img_w,
+                             float max_h, float max_w, int chunk_elems, Levels* out, Factors* fac) {
+    if (int rc = make_level_shapes(level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation, variant, class_agnostic, nms_pre,
+                                   max_per_img, 0.0f, 0, chunk_elems, cls && bbox && points && factors && level_hw, out))
+        return rc;
+    if (img_h < 1 || img_w < 1 || img_h > (1 << 24) || img_w > (1 << 24)) return SPH2POB_ERR_SIZE;
+    if (max_h != max_h || max_w != max_w) return SPH2POB_ERR_OPTION;
+    *fac = Factors{};
+    for (int l = 0; l < num_levels; l++) {
+        if (!cls[l] || !bbox[l] || !points[l] || !factors[l]) return SPH2POB_ERR_NULL;
+        out->lv[l].cls = (const float*)cls[l]; out->lv[l].bbox = (const float*)bbox[l]; out->lv[l].anchors = (const float*)points[l];
+        fac->p[l] = factors[l];
+    }
+    return SPH2POB_OK;
+}
+
 }  // namespace sph2pob_gb

@@ -528,20 +528,17 @@ SPH2POB_ANCHOR_TARGETS_TWIN(sph2pob_anchor_targets_any_f32_cpu, per_pair_only)
 
 // ---- detection post-processing for a minibatch: sph2pob_test_bboxes_f32 / sph2pob_get_bboxes_f32 (the same keys, in the same
 // order, sorted instead of selected; the NMS twin above on each image's candidates — one segment when class-agnostic; the
-// workspace is not used) ----
-int sph2pob_test_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
-                                const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
-                                float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
-                                int coder_flags, float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img,
-                                float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
-    (void)workspace;
+// workspace is not used).  `candidate(lv, l, b, ai, class score, box)` is the coder's part of cand_build: it decodes the box of anchor
+// or point `ai` and returns the score the candidate goes on with ----
+}  // extern "C"
+
+namespace {
+template <class Candidate>
+int bboxes_cpu(const sph2pob_gb::Levels& L, int64_t num_images, int64_t num_classes, int box_dim, int activation, float score_thr, int variant,
+               int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets,
+               Candidate&& candidate) {
     namespace GB = sph2pob_gb;
-    GB::Levels L;
-    if (int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                                 variant, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &L))
-        return rc;
     if (!num_dets || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
-    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
     const int dim = box_dim;
     std::vector<unsigned long long> keys, order;
     std::vector<float> boxes, scores, sorted;
@@ -564,12 +561,10 @@ int sph2pob_test_bboxes_f32_cpu(const void* const* cls_scores, const void* const
             for (size_t i = 0; i < want; i++) {
                 const unsigned flat = (unsigned)keys[i];
                 const int ai = (int)(flat / (unsigned)num_classes);
-                float p[5] = {0, 0, 0, 0, 0}, d[5], box[5];
-                for (int k = 0; k < dim; k++) p[k] = lv.anchors[(int64_t)ai * dim + k];
-                if (dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); sph2pob_coder::decode_one<4, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
-                else { GB::gather_deltas<5>(lv, b, ai, d); sph2pob_coder::decode_one<5, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
+                float box[5];
+                const float score = candidate(lv, l, b, ai, GB::score_of_desc_bits((unsigned)(keys[i] >> 32)), box);
                 boxes.insert(boxes.end(), box, box + dim);
-                scores.push_back(GB::score_of_desc_bits((unsigned)(keys[i] >> 32)));
+                scores.push_back(score);
                 cls.push_back((int64_t)(flat - (unsigned)ai * (unsigned)num_classes));
                 prior.push_back(lv.prior_off + ai);
             }
@@ -606,6 +601,56 @@ int sph2pob_test_bboxes_f32_cpu(const void* const* cls_scores, const void* const
         }
     }
     return SPH2POB_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_test_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
+                                const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
+                                float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
+                                int coder_flags, float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img,
+                                float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
+    (void)workspace;
+    namespace GB = sph2pob_gb;
+    GB::Levels L;
+    if (int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
+                                 variant, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &L))
+        return rc;
+    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
+    const int dim = box_dim;
+    return bboxes_cpu(L, num_images, num_classes, box_dim, activation, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels,
+                      prior_inds, num_dets, [&](const GB::Level& lv, int, int64_t b, int ai, float score, float* box) {
+        float p[5] = {0, 0, 0, 0, 0}, d[5];
+        for (int k = 0; k < dim; k++) p[k] = lv.anchors[(int64_t)ai * dim + k];
+        if (dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); sph2pob_coder::decode_one<4, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
+        else { GB::gather_deltas<5>(lv, b, ai, d); sph2pob_coder::decode_one<5, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
+        return score;
+    });
+}
+// FCOS heads: the point coder's decode_row, score = class score * activate(centerness), one fp32 multiply (the kernel's)
+int sph2pob_fcos_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points,
+                                const void* const* centernesses, const int64_t* level_n, const int64_t* level_hw, int num_levels,
+                                int64_t num_images, int64_t num_classes, int box_dim, int activation, float score_thr, int64_t nms_pre,
+                                int64_t img_h, int64_t img_w, float max_h, float max_w, int variant, int class_agnostic, float iou_threshold,
+                                int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
+    (void)workspace;
+    namespace GB = sph2pob_gb;
+    namespace PT = sph2pob_point;
+    GB::Levels L;
+    GB::Factors F;
+    if (int rc = GB::make_point_levels(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim,
+                                       activation, variant, class_agnostic, nms_pre, max_per_img, img_h, img_w, max_h, max_w, 1 << 14, &L, &F))
+        return rc;
+    const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
+    return bboxes_cpu(L, num_images, num_classes, box_dim, activation, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels,
+                      prior_inds, num_dets, [&](const GB::Level& lv, int l, int64_t b, int ai, float score, float* box) {
+        float d[5], out[5];
+        if (box_dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); PT::decode_row<4, false>(lv.anchors + 2 * (int64_t)ai, d, nullptr, im, out); }
+        else { GB::gather_deltas<5>(lv, b, ai, d); PT::decode_row<5, false>(lv.anchors + 2 * (int64_t)ai, d, nullptr, im, out); }
+        for (int k = 0; k < box_dim; k++) box[k] = out[k];
+        return GB::factor_score(score, GB::activate(GB::gather_factor<float>(lv, F.p[l], b, ai), activation));
+    });
 }
 int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
                                const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,

@@ -338,23 +338,40 @@ PANDORA_TEST_CFG = dict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(
                         iou_calculator='unbiased_iou', box_formator='sph2pix')   # sph_retinanet_r50_fpn_120e_pandora.py
 
 
-def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None, softmax_head=False):
+def fcos_infer_outputs(images=8, num_classes=37, dim=4, seed=0, device='cuda', dtype=torch.float32):
+    """`fcos_head_outputs` at the real shape (strides 8 ... 128 on 512 x 1024: 10 912 points) as an inference step sees them:
+    detached class logits, pixel distances and centerness logits in the head's NCHW, in `dtype`."""
+    cls, box, ctr = fcos_head_outputs(images, num_classes, dim, seed, device)
+    return tuple([t.detach().to(dtype) for t in level] for level in (cls, box, ctr))
+
+
+def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None, softmax_head=False, fcos_head=False):
     """The inference half of `run()` for a minibatch (SphRetinaHead.get_bboxes over the images): the head's per-level NCHW scores
     and deltas -> sph_get_bboxes (per-level top-k, decode, NMS, max_per_img) -> padded detections, no synchronisation.  With a
     `test_cfg` (the reference's dict, e.g. PANDORA_TEST_CFG) the step is sph_test_bboxes under that configuration.
     `softmax_head=True`: the head is a softmax one (K = num_classes + 1 logits per anchor, the background last) and the step is
-    sph_softmax_bboxes under `test_cfg` (the default configuration without one)."""
-    anchors = retina_level_anchors()
-    cls, box = softmax_head_outputs(images, num_classes, seed=seed) if softmax_head else head_outputs(images, num_classes, seed=seed)
-    coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
+    sph_softmax_bboxes under `test_cfg` (the default configuration without one).  `fcos_head=True`: SphFCOSHead.get_bboxes — the
+    levels are the points of `sph_fcos_points` (10 912), the head gives class logits, pixel distances and centerness logits, and
+    the step is sph_fcos_bboxes under `test_cfg` with `max_shape` = the image; 'anchors' then counts and holds the points."""
     if test_cfg is not None:
         nms_calculator = test_cfg.get('iou_calculator', nms_calculator)
+    default_cfg = dict(score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100, iou_calculator=nms_calculator)
+    ctr = None
+    if fcos_head:
+        anchors = S.sph_fcos_points(LEVEL_SHAPES, FCOS_CFG['strides'], device='cuda')
+        cls, box, ctr = fcos_infer_outputs(images, num_classes, seed=seed)
+        coder = S.DistancePointSphBBoxCoder(clip_border=True, box_version=4)
+    else:
+        anchors = retina_level_anchors()
+        cls, box = softmax_head_outputs(images, num_classes, seed=seed) if softmax_head else head_outputs(images, num_classes, seed=seed)
+        coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
 
     def step():
+        if fcos_head:
+            return S.sph_fcos_bboxes(cls, box, ctr, anchors, bbox_coder=coder, test_cfg=test_cfg if test_cfg is not None else default_cfg,
+                                     box_version=4, max_shape=(512, 1024))
         if softmax_head:
-            cfg = test_cfg if test_cfg is not None else dict(score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100,
-                                                             iou_calculator=nms_calculator)
-            return S.sph_softmax_bboxes(cls, box, anchors, bbox_coder=coder, test_cfg=cfg, box_version=4)
+            return S.sph_softmax_bboxes(cls, box, anchors, bbox_coder=coder, test_cfg=test_cfg if test_cfg is not None else default_cfg, box_version=4)
         if test_cfg is not None:
             return S.sph_test_bboxes(cls, box, anchors, bbox_coder=coder, test_cfg=test_cfg, box_version=4, activation='none')
         return S.sph_get_bboxes(cls, box, anchors, bbox_coder=coder, score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5),
@@ -366,8 +383,8 @@ def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient'
         r = step()
     torch.cuda.synchronize()
     out = {'anchors': sum(a.size(0) for a in anchors), 'images': images, 'num_dets': r.num_dets.tolist(), 'dets': tuple(r.dets.shape),
-           'nms': nms_calculator, 'softmax_head': softmax_head, 'get_bboxes_ms': (time.perf_counter() - t0) / reps * 1e3}
-    return out, dict(result=r, cls_scores=cls, bbox_preds=box, anchors=anchors, coder=coder)
+           'nms': nms_calculator, 'softmax_head': softmax_head, 'fcos_head': fcos_head, 'get_bboxes_ms': (time.perf_counter() - t0) / reps * 1e3}
+    return out, dict(result=r, cls_scores=cls, bbox_preds=box, centernesses=ctr, anchors=anchors, coder=coder)
 
 
 if __name__ == '__main__':
@@ -379,3 +396,4 @@ if __name__ == '__main__':
     print(json.dumps(run_batch_infer(reps=5)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, softmax_head=True)[0]), flush=True)
+    print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, fcos_head=True)[0]), flush=True)
