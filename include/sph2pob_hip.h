@@ -1008,6 +1008,73 @@ int sph2pob_fcos_bboxes_h16(const void* const* cls_scores, const void* const* bb
                             float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds,
                             int64_t* num_dets, void* workspace, int dtype, void* stream);
 
+/* ---- fused box-regression loss of a point (FCOS) head: the regression half of SphFCOSHead.loss -------------------------------------
+ * Replaces (sphdet/models/heads/sph_fcos_head.py:76-100) the chain bbox_pred.permute(0, 2, 3, 1).reshape(-1, dim) -> cat over the
+ * levels -> a broadcast copy of the points -> DistancePointSphBBoxCoder.decode of all B n predictions and of all B n targets ->
+ * Sph2PobIoULoss -> / avg_factor and its backward by one pass that reads only the weights and, for the rows whose weight is not zero,
+ * their point, distances and target.  It is sph2pob_bbox_loss_sum_f32 with the point coder in place of the delta coder: per live row
+ * sph2pob_point_coder_decode_f32 on the prediction and on the target with the same point, the loss element and adjoint of
+ * sph2pob_loss_fwd_grad_f32, then sph2pob_point_coder_decode_bwd_f32 (the clip's gate included).
+ *
+ * sph2pob_point_bbox_loss_sum_f32 — bbox_preds, grads, level_n, level_hw, num_levels, num_images, box_dim, weight, weight_dim, loss_mode,
+ * eps, scale, avg_factor, out, workspace, stream exactly as for sph2pob_bbox_loss_sum_f32 (a point head has A = 1 "anchor" per
+ * position; the table takes any A), with
+ *   bbox_preds   the distances (l, t, r, b[, gamma]) in pixels as the head produces them, NCHW (B, A dim, H_l, W_l) or flat (B, n_l, dim)
+ *   points       (n, 2) fp32 pixel coordinates, n = sum n_l, rows in level order, shared by the images
+ *   targets      (B, n, dim) target DISTANCES, as sph2pob_point_targets_f32 writes bbox_targets: they are decoded with the row's point
+ *   img_h, img_w, max_h, max_w   the coder's image and the clip bounds (a negative bound: that axis is not clipped, the reference's
+ *                loss), as sph2pob_point_coder_decode_f32 has them; the clip applies to prediction and target alike
+ *   workspace    sph2pob_point_bbox_loss_workspace_bytes(level_n, level_hw, num_levels, B, box_dim) bytes (0: shapes not accepted)
+ * Nothing flows to the points, the targets or the weights.  The row rule, the store rule, the two launches and B n == 0 are those of
+ * sph2pob_bbox_loss_sum_f32: a row whose mean weight is exactly 0 is NEVER READ, its loss is an exact zero and its gradients +0.0f.
+ * fp32 levels only: there is no _h16 sibling.
+ * Errors, checked in this order before anything is enqueued: loss_mode flags -> SPH2POB_ERR_OPTION; box_dim -> SPH2POB_ERR_DIM; loss
+ * mode, weight_dim (with a weight) -> SPH2POB_ERR_OPTION; the shape and table checks of sph2pob_bbox_loss_sum_f32 with the same codes
+ * and limits (num_levels, B -> SIZE; a NULL level_n / bbox_preds table -> NULL; n_l, level_hw, B n_l dim, anchors per position -> SIZE;
+ * a NULL table entry of a level with rows -> NULL); img_h / img_w outside [1, 2^24] -> SPH2POB_ERR_SIZE; a NULL out, workspace, or
+ * points / targets with rows -> SPH2POB_ERR_NULL; a NaN max_h / max_w -> SPH2POB_ERR_OPTION.
+ */
+int64_t sph2pob_point_bbox_loss_workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                                int box_dim);
+int sph2pob_point_bbox_loss_sum_f32(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                    int num_levels, int64_t num_images, int box_dim, const float* points, const float* targets,
+                                    const float* weight, int weight_dim, int64_t img_h, int64_t img_w, float max_h, float max_w,
+                                    int loss_mode, float eps, float scale, const float* avg_factor, float* out, void* workspace,
+                                    void* stream);
+
+/* ---- fused sigmoid binary cross-entropy on the head's NCHW logits --------------------------------------------------------------------
+ * mmdet's binary_cross_entropy (mmdet/models/losses/cross_entropy_loss.py:64-143) without class_weight — FCOS' loss_centerness (soft
+ * targets, one channel) and the RPN's stock loss_cls (hard labels, one channel, background label 1) — for all levels of a head at
+ * once, with its backward: replaces the permute / reshape / cat of the levels, binary_cross_entropy_with_logits, the mask product,
+ * the sum and the divide.
+ *
+ * sph2pob_bce_loss_sum_f32 — logits, grads, level_n, level_hw, num_levels, num_images, scale, avg_factor, out, workspace, stream
+ * exactly as for sph2pob_focal_loss_sum_f32, num_channels = C in its place of num_classes, with
+ *   targets      soft targets (B, n, C) f32, or NULL
+ *   labels       hard labels (B, n) int64, or NULL.  Exactly one of the two is given.
+ *   weight       NULL (weight_mode 0), (B, n) (1) or (B, n, C) (2)
+ *   ignore_index mmdet's (default -100)
+ * Hard labels (_expand_onehot_labels): the target of channel c is label == c; a label >= C gives an all-zero row (the RPN's
+ * background label 1 with C = 1); a label < 0 or == ignore_index gives the row the weight 0.  Soft targets: the element's weight is
+ * multiplied by (t >= 0) & (t != ignore_index).  Element: e = expf(-|x|), r = 1 / (1 + e), sigmoid(x) = x >= 0 ? r : e r,
+ * loss = (float)((double)max(x, 0) - (double)x (double)t + (double)log1pf(e)) — one rounding —, dx = sigmoid(x) - t; the gradient
+ * is (scale_eff w) dx.  EVERY element is evaluated and multiplied by its weight: an element of weight 0 is read (a NaN there gives
+ * a NaN), as in sph2pob_focal_loss_sum_f32.  out[0] = scale_eff * sum w loss, added in double, one partial per workgroup, the
+ * partials in a fixed order: the same bits on every call.  Two launches; nothing is read back or allocated; B n C == 0 writes 0.
+ *   workspace    sph2pob_bce_loss_workspace_bytes(level_n, level_hw, num_levels, B, C) bytes (0: shapes not accepted)
+ * Errors, checked in this order before anything is enqueued: weight_mode -> SPH2POB_ERR_OPTION; then the size and table checks of
+ * sph2pob_focal_loss_sum_f32 with the same codes and limits (num_levels, B, C -> SIZE; a NULL level_n / logits table -> NULL; n_l,
+ * level_hw, B n_l C -> SIZE; a NULL table entry of a level with elements -> NULL); targets AND labels given -> SPH2POB_ERR_NULL; a
+ * NULL out or workspace, neither targets nor labels with elements, a NULL weight that weight_mode asks for with elements ->
+ * SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_bce_loss_workspace_bytes(const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
+                                         int64_t num_channels);
+int sph2pob_bce_loss_sum_f32(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                             int num_levels, int64_t num_images, int64_t num_channels, const float* targets, const int64_t* labels,
+                             const float* weight, int weight_mode, int64_t ignore_index, float scale, const float* avg_factor, float* out,
+                             void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

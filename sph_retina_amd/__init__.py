@@ -5,8 +5,9 @@ from ._torch_glue import get_arithmetic, set_arithmetic  # noqa: F401
 from .iou import (SphOverlaps2D, sph2pob_efficient_iou, sph2pob_legacy_iou, sph2pob_standard_iou,  # noqa: F401
                   sph_overlaps)
 
-from .losses import (CrossEntropyLoss, FocalLoss, L1Loss, SmoothL1Loss, Sph2PobIoULoss, SphIoULoss, cross_entropy,  # noqa: F401,E402
-                     sigmoid_focal_loss, sph_bbox_loss, sph_delta_loss, sph_focal_loss, sph_gauss_bbox_loss, sph_softmax_loss)
+from .losses import (CrossEntropyLoss, FocalLoss, L1Loss, SmoothL1Loss, Sph2PobIoULoss, SphIoULoss, binary_cross_entropy, cross_entropy,  # noqa: F401,E402
+                     sigmoid_focal_loss, sph_bbox_loss, sph_delta_loss, sph_focal_loss, sph_bce_loss, sph_gauss_bbox_loss,
+                     sph_point_bbox_loss, sph_softmax_loss)
 from .bbox.nms import (DetBBoxes, SphNMS, multiclass_nms, sph_fcos_bboxes, sph_get_bboxes, sph_softmax_bboxes,  # noqa: F401,E402
                        sph_softmax_scores, sph_test_bboxes)
 from .bbox.assigners import (AnchorTargets, PointTargets, SphMaxIoUAssigner, sph_anchor_targets, sph_fcos_points,  # noqa: F401,E402

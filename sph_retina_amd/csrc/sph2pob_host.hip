@@ -34,6 +34,8 @@
 #include "sph2pob_softmax.hpp"
 #include "sph2pob_sample.hpp"
 #include "sph2pob_point_targets.hpp"
+#include "sph2pob_point_bbox_loss.hpp"
+#include "sph2pob_bce_loss.hpp"
 
 namespace {
 
@@ -884,6 +886,44 @@ int sph2pob_focal_loss_grad_scale_f32_cpu(const float* stash, const float* grad_
 
 }  // extern "C"
 
+// ---- sigmoid binary cross-entropy: the twin of sph2pob_bce_loss.hip on the element and target functions of sph2pob_bce_loss.hpp ----
+namespace {
+template <bool HARD>
+double bce_rows(const sph2pob_bce::Levels& L, int64_t rows, int64_t C, const sph2pob_bce::Targets& T, float k0) {
+    return head_rows_sum(L, rows, [&](const sph2pob_bce::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
+        int64_t base, stride;   // element (row, c) = base + c * stride
+        sph2pob_class::class_row_span(lv, C, b, i, &base, &stride);
+        for (int c = 0; c < (int)C; c++) {
+            float t, we, loss, dx;
+            sph2pob_bce::target_weight<HARD>(T, row, C, c, t, we);
+            sph2pob_bce::element(lv.logits[base + c * stride], t, loss, dx);
+            acc += (double)(loss * we);
+            if (lv.grad) lv.grad[base + c * stride] = (k0 * we) * dx;
+        }
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_bce_loss_sum_f32_cpu(const void* const* logits, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                 int num_levels, int64_t num_images, int64_t num_channels, const float* targets, const int64_t* labels,
+                                 const float* weight, int weight_mode, int64_t ignore_index, float scale, const float* avg_factor,
+                                 float* out, void* workspace, void*) {
+    namespace BC = sph2pob_bce;
+    BC::Levels L;
+    if (int rc = BC::make_levels(logits, grads, level_n, level_hw, num_levels, num_images, num_channels, weight_mode, true, &L)) return rc;
+    if (int rc = BC::check_tensors(L, targets, labels, weight, weight_mode, out, workspace)) return rc;
+    const BC::Targets T{targets, labels, weight, weight_mode, ignore_index};
+    const float k0 = BC::effective_scale(scale, avg_factor);
+    const int64_t rows = L.elems > 0 ? num_images * L.n_total : 0;
+    const double total = labels ? bce_rows<true>(L, rows, num_channels, T, k0) : bce_rows<false>(L, rows, num_channels, T, k0);
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
 // ---- fused box-regression losses: the twins of sph2pob_bbox_loss.hip and sph2pob_gauss_bbox_loss.hip on decode_one + the
 // per-pair body (IouBody: pair_loss; GaussBody: pair_gauss_loss), row by row ----
 namespace {
@@ -963,6 +1003,59 @@ int sph2pob_gauss_bbox_loss_sum_f32_cpu(const void* const* bbox_preds, void* con
     if (L.rows > 0)
         total = bbox_loss_total(box_dim, fast, L, anchors, targets, weight, weight_dim, nm, max_ratio, coder_flags, ctr_clamp,
                                 sph2pob_gauss_bbox::make_body(type_flags, fun, tau, alpha, opts, beta, eps), k0);
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- fused box-regression loss of a point head: the twin of sph2pob_point_bbox_loss.hip on the same row function ----
+namespace {
+template <int DIM, bool FAST>
+double point_bbox_loss_rows(const BL::Levels& L, const float* points, const float* targets, const float* weight, int wd,
+                            const sph2pob_point::Image& im, int mode, float eps, float k0) {
+    return head_rows_sum(L, L.rows, [&](const BL::Level& lv, int64_t b, int64_t i, int64_t row, double& acc) {
+        const float w = element_weight<DIM>(weight, wd, row);
+        box_row<DIM>(lv, b, i, w != 0.0f, [&](int64_t off, int64_t stride) {
+            const int64_t j = lv.row_off + i;
+            const float pt[2] = {points[2 * j], points[2 * j + 1]};
+            float d[5], t[5], g[5];
+            for (int k = 0; k < 5; k++) {
+                d[k] = k < DIM ? lv.pred[off + k * stride] : 0.0f;
+                t[k] = k < DIM ? targets[row * DIM + k] : 0.0f;
+            }
+            const float lo1 = sph2pob_point_bbox::row_loss<DIM, true, FAST>(pt, d, t, im, mode, eps, k0 * w, g);
+            acc += (double)(lo1 * w);
+            if (lv.grad)
+                for (int k = 0; k < DIM; k++) lv.grad[off + k * stride] = g[k];
+        });
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_point_bbox_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* grads, const int64_t* level_n, const int64_t* level_hw,
+                                        int num_levels, int64_t num_images, int box_dim, const float* points, const float* targets,
+                                        const float* weight, int weight_dim, int64_t img_h, int64_t img_w, float max_h, float max_w,
+                                        int loss_mode, float eps, float scale, const float* avg_factor, float* out, void* workspace, void*) {
+    BL::Levels L;
+    if (int rc = sph2pob_point_bbox::check_and_levels(bbox_preds, grads, level_n, level_hw, num_levels, num_images, box_dim, weight, weight_dim,
+                                                      img_h, img_w, loss_mode, &L))
+        return rc;
+    if (!out || !workspace || (L.rows > 0 && (!points || !targets))) return SPH2POB_ERR_NULL;
+    if (int rc = sph2pob_point_bbox::check_bounds(max_h, max_w)) return rc;
+    const sph2pob_point::Image im{(float)img_w, (float)img_h, max_w, max_h};
+    const float k0 = BL::effective_scale(scale, avg_factor);
+    const bool fast = !(loss_mode & SPH2POB_FLAG_REFERENCE_ORDER);
+    const int mode = loss_mode & 0xff;
+    double total = 0.0;
+    if (L.rows > 0) {
+#define SPH_POINT_ROWS(D, F) point_bbox_loss_rows<D, F>(L, points, targets, weight, weight_dim, im, mode, eps, k0)
+        if (box_dim == 4) total = fast ? SPH_POINT_ROWS(4, true) : SPH_POINT_ROWS(4, false);
+        else total = fast ? SPH_POINT_ROWS(5, true) : SPH_POINT_ROWS(5, false);
+#undef SPH_POINT_ROWS
+    }
     out[0] = (float)(total * (double)k0);
     return SPH2POB_OK;
 }

@@ -125,8 +125,8 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     on K = 2 logits per anchor without mining and `sph_delta_loss` on the encoded targets: the sampled `label_weights` and the device
     `avg_factor` (the sampled count) feed the fused losses as they stand.
     `fcos_cfg`: the step of an anchor-free head instead (`run_fcos_batch`, and nothing else of the above): a dict with the arguments
-    of `sph_fcos_targets` (`regress_ranges`, `strides`, optionally `center_sampling`, `center_sample_radius`, `norm_on_bbox`,
-    `box_version`)."""
+    of `fcos_step` (`fused_losses=True`: the fused regression and centerness losses) and of `sph_fcos_targets` (`regress_ranges`,
+    `strides`, optionally `center_sampling`, `center_sample_radius`, `norm_on_bbox`, `box_version`)."""
     dev = 'cuda'
     if fcos_cfg is not None:
         if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None:
@@ -214,15 +214,22 @@ FCOS_CFG = dict(regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (51
 
 
 def fcos_step(points, gt, gt_labels, gt_offsets, cls_scores, bbox_preds, centernesses, *, num_classes, coder, loss_iou, img_shape=(512, 1024),
-              **fcos_cfg):
+              fused_losses=False, **fcos_cfg):
     """SphFCOSHead.loss (sphdet/models/heads/sph_fcos_head.py:24-105) without its nonzero() / len(pos_inds): the targets of the
     minibatch from `sph_fcos_targets`; classification `sph_focal_loss` on `labels` over the device `avg_factor`; regression
     `Sph2PobIoULoss` on `coder.decode` of ALL flattened predictions and targets, weighted by the centerness targets (0 on the
     background) over `centerness_denorm`; centerness torch's BCE-with-logits weighted by `labels < num_classes` over `avg_factor`
-    (weight_reduce_loss's `+ eps`).  GT as lists (gt_offsets None) or concatenated.  -> (loss_cls, loss_bbox, loss_centerness, targets)."""
+    (weight_reduce_loss's `+ eps`).  GT as lists (gt_offsets None) or concatenated.  -> (loss_cls, loss_bbox, loss_centerness, targets).
+    `fused_losses=True`: the regression and centerness halves as `sph_point_bbox_loss` and `sph_bce_loss` on the head's NCHW outputs
+    — the step is then sph_fcos_targets + three fused loss calls + one elementwise op for the positives' mask, no copy of a level."""
     t = S.sph_fcos_targets(points, gt, gt_labels, gt_offsets, num_classes=num_classes, img_shape=img_shape, **fcos_cfg)
     images, dim = t.labels.size(0), t.bbox_targets.size(-1)
     loss_cls = S.sph_focal_loss(cls_scores, t.labels, gamma=2.0, alpha=0.25, avg_factor=t.avg_factor)
+    if fused_losses:
+        loss_bbox = S.sph_point_bbox_loss(bbox_preds, points, t.bbox_targets, t.bbox_weights, bbox_coder=coder, mode=loss_iou.mode, eps=loss_iou.eps,
+                                          img_shape=img_shape, avg_factor=t.centerness_denorm, loss_weight=loss_iou.loss_weight)
+        loss_ctr = S.sph_bce_loss(centernesses, t.centerness_targets, (t.labels < num_classes).float(), avg_factor=t.avg_factor)
+        return loss_cls, loss_bbox, loss_ctr, t
     flat_preds = torch.cat([p.permute(0, 2, 3, 1).reshape(images, -1, dim) for p in bbox_preds], dim=1)
     flat_ctr = torch.cat([c.permute(0, 2, 3, 1).reshape(images, -1) for c in centernesses], dim=1)
     pts = torch.cat(list(points)) if isinstance(points, (list, tuple)) else points
@@ -278,6 +285,7 @@ def run_fcos_batch(counts, num_classes, seed, reps, fcos_cfg, dev='cuda'):
     out = {'points': t.labels.size(1), 'images': len(counts), 'num_gt': list(counts), 'num_pos': t.num_pos.tolist(), 'avg_factor': float(t.avg_factor),
            'centerness_denorm': float(t.centerness_denorm), 'loss_cls': float(loss_cls), 'loss_bbox': float(loss_bbox),
            'loss_centerness': float(loss_ctr), 'grads_finite': all(bool(torch.isfinite(x.grad).all()) for x in leaves), 'fcos': True,
+           'fused_losses': bool(cfg.get('fused_losses', False)),
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(targets=t, points=points, gts=gts, labels=labels, cls_scores=cls_scores, bbox_preds=bbox_preds, centernesses=centernesses)
 
