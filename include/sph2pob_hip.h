@@ -1075,6 +1075,70 @@ int sph2pob_bce_loss_sum_f32(const void* const* logits, void* const* grads, cons
                              const float* weight, int weight_mode, int64_t ignore_index, float scale, const float* avg_factor, float* out,
                              void* workspace, void* stream);
 
+/*
+ * sph2pob_rcnn_targets_f32 — the targets of the second stage of a two-stage detector for a whole minibatch, on per-image
+ * proposals: per image MaxIoUAssigner.assign(proposals_b, gt_b), the reference's SphRandomSampler.sample(...,
+ * add_gt_as_proposals) (sphdet/bbox/sampler/sph_random_sampler.py:24-52 over mmdet/core/bbox/samplers/random_sampler.py),
+ * bbox2roi and SphShared2FCBBoxHead.get_targets (sphdet/models/heads/sph_rcnn_head.py:30-66), as one compact table of
+ * S = num_images * num rows.  Four launches whatever B is; nothing is read back, allocated or kept between calls; no atomics on
+ * floats: the same bits on every call; graph-capturable (a device seed is re-read on every replay).
+ *   proposals      (B, M, row_stride) f32: only the first box_dim floats of a row are read, row_stride >= box_dim, so the `dets`
+ *                  (B, max_per_img, box_dim + 1) of the batched inference entries are read in place with their score column
+ *   num_proposals  (B) int64 ON THE DEVICE, each clamped to [0, M] before use (the `num_dets` of those entries); NULL: every
+ *                  image has M proposals
+ *   gt, gt_labels, gt_offsets, num_gt, k_max: the forms and the clamping rules of sph2pob_anchor_targets_f32 (gt_labels NULL:
+ *                  label 0)
+ *   variant        every variant the two anchor-target entries serve between them: STANDARD, EFFICIENT, LEGACY, SPH_IOU, FOV_IOU
+ *                  (box_dim 4 only), UNBIASED, NAIVE (with or without SPH2POB_FLAG_NAIVE_TAN), in the default arithmetic; edge,
+ *                  the four thresholds, match_low_quality, gt_max_assign_all as there
+ * Assignment.  For image b with k_b GT rows and n_b proposals, assigned index g of proposal j = what sph2pob_iou_pairwise_f32 (mode
+ * IOU, angle EQUATOR) + sph2pob_assign_f32 give on that image's first n_b proposals alone (the same per-pair function on the same
+ * inputs: the same bits; all 0 for an image without GT), provided the overlaps are +0 or positive (no NaN): what every variant
+ * returns for valid boxes.
+ * Candidates.  With add_gt != 0 and k_b > 0, candidate c < k_b is GT row c with g = c + 1, max overlap 1, its own label and
+ * is_gt = 1 (AssignResult.add_gt_), and candidate c >= k_b is proposal c - k_b; otherwise candidate c is proposal c.
+ * Sampling: sph2pob_sample_targets_f32's, over the candidates — P_b / N_b the candidates with g > 0 / g == 0, k_pos and k_neg by its
+ * formulas from num, num_expected_pos, neg_pos_ub; the sample of a side is its k candidates with the smallest (rank, c), rank(b, c)
+ * = word 0 of Philox4x32-10 with the seed as key and counter (c, b, 0, 0); `ranks` (B, k_max + M) uint32, indexed by c, replace
+ * the generator when non-NULL; seed / seed_device as there.
+ * Outputs.  Image b owns rows [b num, (b + 1) num): its k_pos sampled positives in ascending c, then its k_neg sampled negatives
+ * in ascending c (mmdet's unique()-sorted pos_inds then neg_inds: SamplingResult.bboxes), then padding:
+ *                                        sampled positive                       sampled negative   padding
+ *   rois           (S, 1 + box_dim) f32  (b, box)                               (b, box)           (b, 180, 90, 1, 1[, 0])
+ *   labels         (S) int64             gt_labels[g - 1]                       num_classes        num_classes
+ *   label_weights  (S) f32               1, or pos_weight when > 0              1                  0
+ *   bbox_targets   (S, box_dim) f32      the GT box (encode == 0) or its deltas 0                  0
+ *                                        w.r.t. the roi (sph2pob_coder_encode_f32's arithmetic with means_host / stds_host)
+ *   bbox_weights   (S, box_dim) f32      1                                      0                  0
+ *   pos_assigned_gt_inds (S) int64       g - 1, image-local                     -1                 -1
+ *   sample_inds    (S) int64             c                                      c                  -1
+ *   is_gt          (S) uint8             1 for a GT candidate, else 0           0                  0
+ * The padding roi is a valid 1 x 1 degree box on the equator: a caller that decodes deltas against every row meets no zero-width
+ * box, and its weights of 0 keep it out of every loss.
+ *   num_pos, num_neg (B) int64           k_pos, k_neg
+ *   avg_factor     (1) f32               max(sum_b (k_pos + k_neg), 1): the head's max(sum(label_weights > 0), 1)
+ *   num_samples    (1) f32               sum_b (k_pos + k_neg): the bbox_targets.size(0) the head hands loss_bbox as avg_factor
+ *   workspace      sph2pob_rcnn_targets_workspace_bytes(num_images, m, k_max) bytes of scratch, no initialisation (0 for sizes
+ *                  the entry refuses)
+ * Limits: num_images <= 65 535, k_max <= 262 140, m + k_max < 2^31, row_stride <= 4096, num <= 65 535 (the compaction scan
+ * carries both sides' counts in the halves of one word).  Errors, checked in this order before anything is enqueued: box_dim
+ * (LEGACY / SPH_IOU / FOV_IOU with box_dim 5 included) -> SPH2POB_ERR_DIM; a bad variant or edge, SPH2POB_FLAG_REFERENCE_ORDER, a
+ * NaN neg_pos_ub, add_gt or encode outside {0, 1} -> SPH2POB_ERR_OPTION; num_images outside [1, 65 535], m < 1, num_gt < 0,
+ * k_max < 0 or > num_gt, row_stride < box_dim, num < 1, num_expected_pos outside [0, num], a limit exceeded -> SPH2POB_ERR_SIZE; a
+ * NULL proposals, gt_offsets, gt (with num_gt > 0), output or workspace -> SPH2POB_ERR_NULL (num_proposals, gt_labels,
+ * seed_device, ranks, means_host and stds_host may be NULL).
+ */
+int64_t sph2pob_rcnn_targets_workspace_bytes(int64_t num_images, int64_t m, int64_t k_max);
+int sph2pob_rcnn_targets_f32(const float* proposals, const int64_t* num_proposals, int64_t num_images, int64_t m, int64_t row_stride,
+                             const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets, int64_t num_gt, int64_t k_max, int box_dim,
+                             int variant, int edge, float pos_iou_thr, float neg_iou_lo, float neg_iou_hi, float min_pos_iou,
+                             int match_low_quality, int gt_max_assign_all, int64_t num, int64_t num_expected_pos, double neg_pos_ub, int64_t seed,
+                             const int64_t* seed_device, const uint32_t* ranks, int add_gt, int64_t num_classes, float pos_weight, int encode,
+                             const float* means_host, const float* stds_host, float* rois, int64_t* labels, float* label_weights,
+                             float* bbox_targets, float* bbox_weights, int64_t* pos_assigned_gt_inds, int64_t* sample_inds,
+                             unsigned char* is_gt, int64_t* num_pos, int64_t* num_neg, float* avg_factor, float* num_samples, void* workspace,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

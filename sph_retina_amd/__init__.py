@@ -10,8 +10,8 @@ from .losses import (CrossEntropyLoss, FocalLoss, L1Loss, SmoothL1Loss, Sph2PobI
                      sph_point_bbox_loss, sph_softmax_loss)
 from .bbox.nms import (DetBBoxes, SphNMS, multiclass_nms, sph_fcos_bboxes, sph_get_bboxes, sph_softmax_bboxes,  # noqa: F401,E402
                        sph_softmax_scores, sph_test_bboxes)
-from .bbox.assigners import (AnchorTargets, PointTargets, SphMaxIoUAssigner, sph_anchor_targets, sph_fcos_points,  # noqa: F401,E402
-                             sph_fcos_targets, sph_rpn_targets, sph_sample_targets, sph_train_targets)
+from .bbox.assigners import (AnchorTargets, PointTargets, RcnnTargets, SphMaxIoUAssigner, rcnn_bbox_pred, sph_anchor_targets,  # noqa: F401,E402
+                             sph_fcos_points, sph_fcos_targets, sph_rcnn_targets, sph_rpn_targets, sph_sample_targets, sph_train_targets)
 from .bbox.coder import DeltaXYWHASphBBoxCoder, DeltaXYWHSphBBoxCoder, DistancePointSphBBoxCoder  # noqa: F401,E402
 
 __version__ = '0.1.0'

@@ -25,28 +25,32 @@ _SAMPLER_KEYS = ('type', 'num', 'pos_fraction', 'neg_pos_ub', 'add_gt_as_proposa
 _SAMPLER_TYPES = ('RandomSampler', 'SphRandomSampler')
 
 
-def _sampler_options(sampler):
+def _sampler_options(sampler, who=_WHO, with_add_gt=False):
     """sampler (a dict, or an instance with these attributes) -> (num, num_expected_pos, neg_pos_ub); what the kernels do not
-    serve raises NotImplementedError naming the per-image API."""
+    serve raises NotImplementedError naming the per-image API.  `with_add_gt` (the entry samples per-image proposals: the R-CNN
+    stage): add_gt_as_proposals is served and returned as a fourth value instead of being refused."""
     if isinstance(sampler, dict):
         unknown = [k for k in sampler if k not in _SAMPLER_KEYS]
         if unknown:
-            raise TypeError(f'{_WHO}: unknown sampler key {unknown} (known: {list(_SAMPLER_KEYS)})')
+            raise TypeError(f'{who}: unknown sampler key {unknown} (known: {list(_SAMPLER_KEYS)})')
         kind, get = sampler.get('type'), sampler.get
     elif sampler is None:
-        raise TypeError(f'{_WHO} needs a sampler: dict(type=\'RandomSampler\', num=..., pos_fraction=..., add_gt_as_proposals=False)')
+        raise TypeError(f'{who} needs a sampler: dict(type=\'RandomSampler\', num=..., pos_fraction=..., add_gt_as_proposals=False)')
     else:
         kind, get = type(sampler).__name__, lambda k, d=None: getattr(sampler, k, d)
     if kind not in _SAMPLER_TYPES:
-        raise NotImplementedError(f'{_WHO} implements RandomSampler / SphRandomSampler only, not {kind}: ' + _PER_IMAGE)
-    if get('add_gt_as_proposals', True):    # mmdet's default
-        raise NotImplementedError(f'{_WHO} samples the anchors the images share: add_gt_as_proposals=True (per-image proposals, the '
+        raise NotImplementedError(f'{who} implements RandomSampler / SphRandomSampler only, not {kind}: ' + _PER_IMAGE)
+    add_gt = bool(get('add_gt_as_proposals', True))    # mmdet's default
+    if add_gt and not with_add_gt:
+        raise NotImplementedError(f'{who} samples the anchors the images share: add_gt_as_proposals=True (per-image proposals, the '
                                   'R-CNN stage) is not served: ' + _PER_IMAGE)
     num, pos_fraction, ub = get('num'), get('pos_fraction'), get('neg_pos_ub', -1)
     if num is None or pos_fraction is None:
-        raise TypeError(f'{_WHO}: the sampler needs num and pos_fraction')
+        raise TypeError(f'{who}: the sampler needs num and pos_fraction')
     if int(num) != num or num < 1 or not 0 <= pos_fraction <= 1 or ub != ub:
-        raise ValueError(f'{_WHO}: num must be an integer >= 1, pos_fraction in [0, 1] and neg_pos_ub a number; ' + _PER_IMAGE)
+        raise ValueError(f'{who}: num must be an integer >= 1, pos_fraction in [0, 1] and neg_pos_ub a number; ' + _PER_IMAGE)
+    if with_add_gt:
+        return int(num), int(num * pos_fraction), float(ub), add_gt
     return int(num), int(num * pos_fraction), float(ub)
 
 

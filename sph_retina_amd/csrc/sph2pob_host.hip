@@ -33,6 +33,7 @@
 #include "sph2pob_delta_loss.hpp"
 #include "sph2pob_softmax.hpp"
 #include "sph2pob_sample.hpp"
+#include "sph2pob_rcnn_targets.hpp"
 #include "sph2pob_point_targets.hpp"
 #include "sph2pob_point_bbox_loss.hpp"
 #include "sph2pob_bce_loss.hpp"
@@ -1360,6 +1361,92 @@ int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, i
     for (int64_t b = 0; b < num_images; b++) { sp += std::max<int64_t>(num_pos[b], 1); sn += std::max<int64_t>(num_neg[b], 1); }
     avg_factor[0] = (float)(sp + sn);
     avg_factor_pos[0] = (float)sp;
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- R-CNN stage targets on per-image proposals: sph2pob_rcnn_targets_f32 after its checks (sph2pob_rcnn_targets.hpp).  Per image
+// the pairwise and the assign twin above on its first n_b proposals, the candidate list, the sampler's rank, sizes and cut, and the
+// kernels' table rows in the kernels' order (the workspace is not used) ----
+extern "C" {
+
+int sph2pob_rcnn_targets_f32_cpu(const float* proposals, const int64_t* num_proposals, int64_t num_images, int64_t m, int64_t row_stride,
+                                 const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets, int64_t num_gt, int64_t k_max, int box_dim,
+                                 int variant, int edge, float pos_iou_thr, float neg_iou_lo, float neg_iou_hi, float min_pos_iou,
+                                 int match_low_quality, int gt_max_assign_all, int64_t num, int64_t num_expected_pos, double neg_pos_ub,
+                                 int64_t seed, const int64_t* seed_device, const uint32_t* ranks, int add_gt, int64_t num_classes, float pos_weight,
+                                 int encode, const float* means_host, const float* stds_host, float* rois, int64_t* labels, float* label_weights,
+                                 float* bbox_targets, float* bbox_weights, int64_t* pos_assigned_gt_inds, int64_t* sample_inds,
+                                 unsigned char* is_gt, int64_t* num_pos, int64_t* num_neg, float* avg_factor, float* num_samples, void* workspace,
+                                 void*) {
+    namespace RC = sph2pob_rcnn;
+    namespace SA = sph2pob_sample;
+    const RC::Table T{rois, labels, label_weights, bbox_targets, bbox_weights, pos_assigned_gt_inds, sample_inds, is_gt, num_pos, num_neg, avg_factor,
+                      num_samples};
+    if (int rc = RC::check(check_common(box_dim, variant, edge, 0), variant, proposals, num_images, m, row_stride, box_dim, gt, gt_offsets, num_gt,
+                           k_max, num, num_expected_pos, neg_pos_ub, add_gt, encode, T, false, workspace))
+        return rc;
+    const int dim = box_dim;
+    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
+    const auto sampled_row = dim == 4 ? (encode ? RC::write_sampled<4, true> : RC::write_sampled<4, false>)
+                                      : (encode ? RC::write_sampled<5, true> : RC::write_sampled<5, false>);
+    const auto padding_row = dim == 4 ? RC::write_padding<4> : RC::write_padding<5>;
+    const uint64_t sd = (uint64_t)(seed_device ? seed_device[0] : seed);
+    const int64_t C = k_max + m;
+    std::vector<float> boxes, ov, max_ov, gt_max;
+    std::vector<int64_t> cand, argmax, gt_argmax;
+    std::vector<uint32_t> rank((size_t)C), scratch;
+    int64_t total = 0;
+    for (int64_t b = 0; b < num_images; b++) {
+        const RC::ImageRows im = RC::image_rows(gt_offsets, b, num_gt, k_max);
+        const int64_t k = im.k, n = RC::image_proposals(num_proposals, b, m), koff = RC::gt_candidates(add_gt, k), count = koff + n;
+        const float* gt_b = gt + im.lo * dim;
+        const int64_t* labels_b = gt_labels ? gt_labels + im.lo : nullptr;
+        cand.assign((size_t)count, 0);   // an image without GT: every proposal is background (max_iou_assigner.py:148-165)
+        for (int64_t c = 0; c < koff; c++) cand[(size_t)c] = c + 1;
+        if (k > 0 && n > 0) {
+            boxes.resize((size_t)(n * dim)); ov.resize((size_t)(k * n)); max_ov.resize((size_t)n); argmax.resize((size_t)n);
+            gt_max.resize((size_t)k); gt_argmax.resize((size_t)k);
+            for (int64_t j = 0; j < n; j++)
+                for (int d = 0; d < dim; d++) boxes[(size_t)(j * dim + d)] = proposals[(b * m + j) * row_stride + d];
+            int rc = sph2pob_iou_pairwise_f32_cpu(gt_b, k, boxes.data(), n, ov.data(), box_dim, variant, SPH2POB_MODE_IOU, edge, SPH2POB_ANGLE_EQUATOR,
+                                                  nullptr);
+            if (!rc)
+                rc = sph2pob_assign_f32_cpu(ov.data(), k, n, pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all,
+                                            nullptr, max_ov.data(), argmax.data(), gt_max.data(), gt_argmax.data(), cand.data() + koff, nullptr,
+                                            nullptr, nullptr);
+            if (rc) return rc;
+        }
+        int64_t sides[2] = {0, 0}, kk[2];
+        for (int64_t c = 0; c < count; c++) {
+            const int s = SA::side_of(cand[(size_t)c]);
+            if (s == SA::IGNORED) continue;
+            sides[s]++;
+            rank[(size_t)c] = ranks ? ranks[b * C + c] : SA::row_rank(sd, (uint32_t)b, (uint32_t)c);
+        }
+        SA::sample_sizes(sides[SA::POS], sides[SA::NEG], num_expected_pos, num, neg_pos_ub, &kk[SA::POS], &kk[SA::NEG]);
+        SA::Pick pick[2];
+        for (int side = 0; side < 2; side++) {
+            pick[side] = SA::Pick{{0u, 0}, kk[side]};
+            sph2pob_select::host_cut<false>(count, kk[side], [&](int64_t c, uint32_t* key) { *key = rank[(size_t)c]; return SA::side_of(cand[(size_t)c]) == side; },
+                                            scratch, &pick[side].cut);
+        }
+        num_pos[b] = kk[SA::POS]; num_neg[b] = kk[SA::NEG];
+        total += kk[SA::POS] + kk[SA::NEG];
+        int64_t r = b * num;
+        for (int side = 0; side < 2; side++)   // positives in ascending c, then negatives in ascending c
+            for (int64_t c = 0; c < count; c++) {
+                const int64_t a = cand[(size_t)c];
+                if (SA::side_of(a) != side || !SA::sampled(rank[(size_t)c], c, pick[side])) continue;
+                const bool from_gt = c < koff;
+                sampled_row(T, r++, b, c, a, from_gt, from_gt ? gt_b + c * dim : proposals + (b * m + c - koff) * row_stride, gt_b, labels_b, num_classes,
+                            pos_weight, nm);
+            }
+        for (; r < (b + 1) * num; r++) padding_row(T, r, b, num_classes);
+    }
+    num_samples[0] = (float)total;
+    avg_factor[0] = (float)std::max<int64_t>(total, 1);
     return SPH2POB_OK;
 }
 

@@ -105,7 +105,8 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
-              train_cfg=None, loss_bbox=None, softmax_head=False, rpn_cfg=None, rpn_seed=0, fcos_cfg=None):
+              train_cfg=None, loss_bbox=None, softmax_head=False, rpn_cfg=None, rpn_seed=0, fcos_cfg=None, rcnn_cfg=None, rcnn_seed=0,
+              rcnn_proposals=1000, rcnn_decoded=False):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -126,8 +127,16 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     `avg_factor` (the sampled count) feed the fused losses as they stand.
     `fcos_cfg`: the step of an anchor-free head instead (`run_fcos_batch`, and nothing else of the above): a dict with the arguments
     of `fcos_step` (`fused_losses=True`: the fused regression and centerness losses) and of `sph_fcos_targets` (`regress_ranges`,
-    `strides`, optionally `center_sampling`, `center_sample_radius`, `norm_on_bbox`, `box_version`)."""
+    `strides`, optionally `center_sampling`, `center_sample_radius`, `norm_on_bbox`, `box_version`).
+    `rcnn_cfg`: the step of the second stage of a two-stage detector instead (`run_rcnn_batch`, and nothing else of the above): the
+    reference's `train_cfg.rcnn` with its RandomSampler(add_gt_as_proposals=True); `rcnn_proposals` padded proposals per image in the
+    layout of the batched inference entries, `rcnn_seed` a Python int or a () int64 device tensor, `rcnn_decoded`: the box loss on the
+    decoded boxes (reg_decoded_bbox=True) instead of on the raw deltas."""
     dev = 'cuda'
+    if rcnn_cfg is not None:
+        if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None or fcos_cfg is not None:
+            raise ValueError('rcnn_cfg is a step of its own: sph_rcnn_targets + cross_entropy + the box loss on the gathered predictions')
+        return run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed, rcnn_proposals, rcnn_decoded, dev)
     if fcos_cfg is not None:
         if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None:
             raise ValueError('fcos_cfg is a step of its own: sph_fcos_targets + sph_focal_loss + Sph2PobIoULoss on the point decode + BCE')
@@ -288,6 +297,86 @@ def run_fcos_batch(counts, num_classes, seed, reps, fcos_cfg, dev='cuda'):
            'fused_losses': bool(cfg.get('fused_losses', False)),
            'targets_decode_loss_backward_ms': (time.perf_counter() - t0) / reps * 1e3}
     return out, dict(targets=t, points=points, gts=gts, labels=labels, cls_scores=cls_scores, bbox_preds=bbox_preds, centernesses=centernesses)
+
+
+def synthetic_proposals(gts, m, seed=0, device='cuda'):
+    """Synthetic proposals in the layout of the batched inference entries: `dets` (B, m, 5) — a box and a score column — and
+    `num_dets` (B,) int64 on the device.  70 % of an image's proposals are jittered copies of its GT, the rest uniform boxes; an
+    image keeps between 60 % and 100 % of the m rows, the rest is padding the consumer never reads."""
+    g = torch.Generator().manual_seed(seed)
+    dets, counts = torch.zeros((len(gts), m, 5)), []
+    for b, gt in enumerate(gts):
+        u = torch.rand((m, 4), generator=g)
+        boxes = torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85], 1)
+        if gt.size(0) > 0:
+            near = gt.cpu()[torch.randint(0, gt.size(0), (m,), generator=g)] + torch.randn((m, 4), generator=g) * 4
+            near[:, 2:] = near[:, 2:].clamp(2, 170)
+            near[:, 1] = near[:, 1].clamp(5, 175)
+            near[:, 0] = near[:, 0] % 360
+            boxes = torch.where(torch.rand((m, 1), generator=g) < 0.3, boxes, near)
+        dets[b, :, :4], dets[b, :, 4] = boxes, torch.rand((m,), generator=g)
+        counts.append(int(m * (0.6 + 0.4 * float(torch.rand((), generator=g)))))
+    return dets.to(device), torch.tensor(counts, dtype=torch.int64).to(device)
+
+
+def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=1000, decoded=False, dev='cuda'):
+    """`run_batch(rcnn_cfg=...)`: SphStandardRoIHead._bbox_forward_train without the RoI extractor — proposals (`dets, num_dets`, read in
+    place) and concatenated GT -> `sph_rcnn_targets` -> flat `cross_entropy` on (S, C + 1) logits with `avg_factor=t.avg_factor`, and
+    the box loss on `rcnn_bbox_pred`'s gather over all S rows with `avg_factor=t.num_samples`: L1 on the raw deltas, or with
+    `decoded` Sph2PobIoULoss on `decode(rois[:, 1:], gathered)` against GT boxes.  Padding and background rows have weight 0.  The
+    step, backward included, is captured into a graph and replayed: nothing is read back."""
+    g = torch.Generator().manual_seed(seed)
+    gts, labels = [], []
+    for k in counts:
+        u = torch.rand((k, 4), generator=g)
+        gts.append(torch.stack([u[:, 0] * 360, 20 + u[:, 1] * 140, 5 + u[:, 2] * 85, 5 + u[:, 3] * 85], 1).to(dev))
+        labels.append(torch.randint(0, num_classes, (k,), generator=g).to(dev))
+    images = len(counts)
+    dets, num_dets = synthetic_proposals(gts, m, seed, dev)
+    gt, lab = torch.cat(gts), torch.cat(labels)
+    off = torch.tensor([0] + [sum(counts[:b + 1]) for b in range(images)], dtype=torch.int64).to(dev)
+    k_max = max(counts)
+    num = rcnn_cfg['sampler']['num']
+    coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
+    loss_l1, loss_iou = S.L1Loss(loss_weight=1.0), S.Sph2PobIoULoss(mode='iou', loss_weight=1.0)
+    gd = torch.Generator(device=dev).manual_seed(seed)
+    cls_score = torch.randn((images * num, num_classes + 1), generator=gd, device=dev).requires_grad_(True)
+    bbox_pred = (torch.randn((images * num, num_classes * 4), generator=gd, device=dev) * 0.05).requires_grad_(True)
+
+    def step():
+        t = S.sph_rcnn_targets(dets, gt, lab, off, num_proposals=num_dets, train_cfg=rcnn_cfg, num_classes=num_classes, seed=rcnn_seed,
+                               reg_decoded_bbox=decoded, bbox_coder=coder, k_max=k_max)
+        loss_cls = S.cross_entropy(cls_score, t.labels, t.label_weights, avg_factor=t.avg_factor)
+        picked = S.rcnn_bbox_pred(bbox_pred, t.labels, num_classes, 4, False)
+        if decoded:
+            loss_box = loss_iou(coder.decode(t.rois[:, 1:].contiguous(), picked), t.bbox_targets, t.bbox_weights, avg_factor=t.num_samples)
+        else:
+            loss_box = loss_l1(picked, t.bbox_targets, t.bbox_weights, avg_factor=t.num_samples)
+        return (loss_cls.detach(), loss_box.detach()) + torch.autograd.grad(loss_cls + loss_box, (cls_score, bbox_pred)) + (t,)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        loss_cls, loss_box, g_cls, g_box, t = step()
+    graph.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        graph.replay()
+    torch.cuda.synchronize()
+    out = {'rcnn': True, 'images': images, 'proposals': m, 'num_dets': num_dets.tolist(), 'num_gt': list(counts), 'num': num,
+           'num_pos': t.num_pos.tolist(), 'num_neg': t.num_neg.tolist(), 'avg_factor': float(t.avg_factor), 'num_samples': float(t.num_samples),
+           'loss_cls': float(loss_cls), 'loss_bbox': float(loss_box), 'decoded': decoded,
+           'grads_finite': bool(torch.isfinite(g_cls).all()) and bool(torch.isfinite(g_box).all()),
+           'cls_grad_rows': int((g_cls.abs().sum(1) > 0).sum()), 'box_grad_rows': int((g_box.abs().sum(1) > 0).sum()),
+           'graph_replay_ms': (time.perf_counter() - t0) / reps * 1e3}
+    return out, dict(targets=t, dets=dets, num_dets=num_dets, gt=gt, labels=lab, gt_offsets=off, gts=gts, cls_score=cls_score, bbox_pred=bbox_pred,
+                     cls_grad=g_cls, box_grad=g_box, coder=coder, graph=graph)
 
 
 def retina_level_anchors(device='cuda'):
