@@ -1139,6 +1139,67 @@ int sph2pob_rcnn_targets_f32(const float* proposals, const int64_t* num_proposal
                              unsigned char* is_gt, int64_t* num_pos, int64_t* num_neg, float* avg_factor, float* num_samples, void* workspace,
                              void* stream);
 
+/*
+ * sph2pob_rcnn_bboxes_f32 — inference of the second stage of a two-stage detector for a whole minibatch, on per-image rois: what
+ * SphStandardRoIHead.simple_test_bboxes -> SphShared2FCBBoxHead.get_bboxes -> multiclass_nms compute per image
+ * (sphdet/models/heads/sph_rcnn_head.py:127-177, :248-333; sphdet/bbox/nms/utils.py:6-95): softmax over K = C + 1 logits per roi,
+ * bbox_coder.decode of the per-class deltas, `scores[:, :-1] > score_thr`, the NMS, [:max_per_img].  Eleven launches whatever B
+ * is (the first of the ten behind stage 0 is a zeroing kernel, not a memset); nothing is read back, allocated or kept between
+ * calls; no atomics on floats: the same bits on every call; capturable into a hipGraph.  All inputs are read in place:
+ *   rois          (B, M, row_stride) f32: the box in columns [0, box_dim), row_stride >= box_dim — the `dets`
+ *                 (B, max_per_img, box_dim + 1) of the batched inference entries go in with their score column
+ *   num_rois      (B) int64 ON THE DEVICE, each clamped to [0, M] before use (the `num_dets` of those entries); NULL: every image
+ *                 has M rois
+ *   cls_score     (B, M, K) f32 logits, K = num_logits = C + 1, the background LAST
+ *   bbox_pred     (B, M, C box_dim) f32 deltas, class c in columns [c box_dim, (c + 1) box_dim); (B, M, box_dim) with
+ *                 reg_class_agnostic = 1; NULL: the head has no regression branch (with_reg = False)
+ *   means_host ... ctr_clamp: the delta coder's block, as sph2pob_test_bboxes_f32 takes it (the reference's delta coder accepts
+ *                 max_shape and does not use it: it is no argument)
+ *   score_thr, variant_flags, class_agnostic, iou_threshold, max_per_img: as sph2pob_test_bboxes_f32 has them
+ *   max_candidates  the capacity of an image's candidate block, see "Selection"
+ * Score.  The probability of sph2pob_softmax_scores_f32 (csrc/sph2pob_softmax.hpp, Prob: m = max_j x_j, e_j = expf(x_j - m), the sum
+ * in double in ascending class order, one divide): the bits that entry writes for the flat (B, M, K) layout.  A row with a NaN or
+ * a +inf (or without a finite logit) is NaN in all its classes and yields no candidate; other rows are not touched.
+ * Rows behind the count.  Row r >= num_rois[b] yields no candidate whatever score_thr is; its logits and deltas are never read and
+ * may be uninitialised (its roi is not read either).
+ * Selection.  Candidate (r, c), c < C, has index r C + c and is valid iff p > score_thr.  The reference hands ALL valid candidates
+ * to the NMS; this entry the first min(max_candidates, #valid) of them in (probability descending, index ascending) order — the
+ * selection of sph2pob_test_bboxes_f32 on one flat level of M rows with nms_pre = max_candidates — and reports #valid:
+ *   num_valid     (B) int64: the valid candidates of every image, truncated or not
+ * Exactness: greedy NMS decides a candidate from the higher-scored ones alone, and the detections are the kept candidates in
+ * descending score order.  So image b's rows equal those of the untruncated computation whenever num_valid[b] <= max_candidates
+ * (nothing was cut) OR num_dets[b] == max_per_img (the first max_per_img kept candidates all lie among the best max_candidates;
+ * what was cut scores below every one of them and can neither suppress them nor come before them).  Both are device values:
+ * a caller checks `(num_valid <= max_candidates) | (num_dets == max_per_img)` without a synchronisation.  With max_candidates >=
+ * M min(C, floor(1 / score_thr)) nothing is ever cut (the probabilities of a row sum to 1).
+ * Decode.  Only of the selected candidates: roi rois[b, r], deltas bbox_pred[b, r, c box_dim : (c + 1) box_dim] ([0, box_dim) when
+ * class-agnostic), the arithmetic of sph2pob_coder_decode_f32.  bbox_pred == NULL: the box is the roi with components 2 and 3
+ * clamped to [1e-7, 180 - 1e-7], both bounds narrowed to fp32 as torch's clamp_ narrows them (sph_rcnn_head.py:151-157).
+ * NMS and outputs.  Exactly what sph2pob_test_bboxes_f32 does with its candidates: every calculator it serves (STANDARD, EFFICIENT,
+ * UNBIASED, NAIVE with or without SPH2POB_FLAG_NAIVE_TAN), class_agnostic = 1 for PlanarNMS; ties by candidate position, which is
+ * the index order among equal scores — the order multiclass_nms hands its candidates over in.
+ *   dets          (B, max_per_img, box_dim + 1) f32: box and score; rows from num_dets[b] on are 0
+ *   labels        (B, max_per_img) int64 in [0, C), -1 from num_dets[b] on
+ *   prior_inds    (B, max_per_img) int64: the detection's roi row r, -1 padded
+ *   num_dets      (B) int64
+ *   workspace     sph2pob_rcnn_bboxes_workspace_bytes(B, M, K, box_dim, max_candidates) bytes, no initialisation (0 = the shapes
+ *                 are not accepted): that of sph2pob_get_bboxes_workspace_bytes for one level of M rows with nms_pre =
+ *                 max_candidates — 8 B M C bytes of survivor slots and B suppression matrices of min(max_candidates, M C)^2 / 8
+ *                 bytes are its large parts — plus 4 B M C bytes of probabilities
+ * Errors, checked in this order before anything is enqueued: box_dim -> SPH2POB_ERR_DIM; a variant other than STANDARD | EFFICIENT
+ * | UNBIASED | NAIVE, SPH2POB_FLAG_REFERENCE_ORDER or an unknown flag bit, SPH2POB_FLAG_NAIVE_TAN with a variant other than NAIVE,
+ * class_agnostic outside {0, 1}, coder_flags, max_ratio < 0, reg_class_agnostic outside {0, 1} -> SPH2POB_ERR_OPTION; B outside
+ * [1, 65 535], K outside [2, 4096], max_candidates <= 0, max_per_img < 0, M < 1, row_stride < box_dim, M C >= 2^31 - 2^17,
+ * min(max_candidates, M C) > sph2pob_batched_nms_max_boxes() -> SPH2POB_ERR_SIZE; a NULL rois, cls_score, output or workspace ->
+ * SPH2POB_ERR_NULL (num_rois, bbox_pred, means_host and stds_host may be NULL).  The CPU twin ignores the workspace.
+ */
+int64_t sph2pob_rcnn_bboxes_workspace_bytes(int64_t num_images, int64_t m, int64_t num_logits, int box_dim, int64_t max_candidates);
+int sph2pob_rcnn_bboxes_f32(const float* rois, const int64_t* num_rois, const float* cls_score, const float* bbox_pred, int64_t num_images,
+                            int64_t m, int64_t row_stride, int64_t num_logits, int box_dim, int reg_class_agnostic, float score_thr,
+                            int64_t max_candidates, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
+                            float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
+                            int64_t* labels, int64_t* prior_inds, int64_t* num_dets, int64_t* num_valid, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

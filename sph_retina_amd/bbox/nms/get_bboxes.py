@@ -18,6 +18,9 @@ probabilities alone.  Both entries here keep refusing `activation='softmax'`.
 
 FCOS heads (a centerness per point as the score factor, the distance-point coder) have `sph_fcos_bboxes` in `fcos_bboxes.py`.
 
+The R-CNN stage of the two-stage detectors (per-image rois, per-class deltas, no top-k in front of the NMS) has `sph_rcnn_bboxes` in
+`rcnn_bboxes.py`; the `dets, num_dets` of the entries here are its `rois, num_rois`.
+
 The per-image API (`multiclass_nms`, or `filter` + `bbox_coder.decode` + `sph_batched_nms` on each image and level) keeps serving
 what none of these entries does: score factors of anchor-based heads, `with_nms=False`, the `'xinyuan'` / `kent_iou` calculators, the reference
 arithmetic and more than 16 384 candidates per image.

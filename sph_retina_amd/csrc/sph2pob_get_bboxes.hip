@@ -4,7 +4,9 @@
 // (sphdet/models/heads/sph_retina_head.py:101-216, :22-99) and filter_scores_and_topk (mmdet/core/utils/misc.py:119-165) for
 // B images with a number of launches that does not depend on B, and without a host read.  gfx950 only.  sph2pob_fcos_bboxes_f32 is
 // the same pipeline for SphFCOSHead (sph_fcos_head.py:246-323, :205-244): the selection on the class scores alone, then a cand_build
-// of its own that decodes from points and multiplies the class score by the point's centerness.
+// of its own that decodes from points and multiplies the class score by the point's centerness.  sph2pob_rcnn_bboxes_f32
+// (sph2pob_rcnn_bboxes.hip) is the pipeline once more, for the R-CNN stage: one flat level of the probabilities its stage 0 wrote,
+// and cand_build_rois_kernel, whose priors are the images' own rois and whose deltas are per class.
 //
 // Selection, per (image, level), on the unique 64-bit keys (descending score bits << 32 | flat index):
 //   zero          the histograms and the per-(image, level) records
@@ -25,12 +27,14 @@
 #include "sph2pob_coder.hpp"
 #include "sph2pob_get_bboxes.hpp"   // (declares the NMS stage, sph2pob_nms_batch_launch)
 #include "sph2pob_point_targets.hpp"   // (the point coder's decode_row)
+#include "sph2pob_rcnn_bboxes.hpp"     // (the rois of the R-CNN stage and their candidate_box)
 
 namespace {
 
 using namespace sph2pob_gb;
 namespace C = sph2pob_coder;
 namespace PT = sph2pob_point;
+namespace RB = sph2pob_rcnn_bb;
 
 constexpr int kSelBlock = 256, kSelIters = 16, kChunk = kSelBlock * 4 * kSelIters;   // 16 384 scores per workgroup
 constexpr int kResBlock = 1024, kRadixBits = 11, kRadix = 1 << kRadixBits;
@@ -325,6 +329,55 @@ __global__ __launch_bounds__(kBuildBlock) void cand_build_points_kernel(Levels L
     prior[at] = lv.prior_off + ai;
 }
 
+// The R-CNN stage (sph2pob_rcnn_bboxes_f32): one flat level whose priors are the images' own rois, (B, M, row_stride), with the
+// head's per-class deltas (B, M, C DIM) — or class-agnostic ones, or none.  Key index r C + c -> roi row r, class c; the roi is one
+// 16-byte load where the row's address allows it (row_stride is arbitrary, so that is decided per row), the deltas of class c
+// are gathered from the row's own C DIM, the box is RB::candidate_box's.  The first workgroup of an image also adds up the image's
+// selection histogram — every valid candidate was counted there exactly once, whatever the cut — into num_valid
+template <int DIM>
+__global__ __launch_bounds__(kBuildBlock) void cand_build_rois_kernel(Levels L, RB::Rois R, const Meta* __restrict__ meta,
+                                                                    const unsigned long long* __restrict__ sel, const int* __restrict__ hist,
+                                                                    int num_classes, C::Norm nm, float max_ratio, int coder_flags, float ctr_clamp,
+                                                                    float* __restrict__ boxes, float* __restrict__ scores,
+                                                                    int64_t* __restrict__ labels, int* __restrict__ prior, int* __restrict__ counts,
+                                                                    int64_t* __restrict__ num_valid) {
+    __shared__ unsigned long long tile[kBuildBlock];
+    __shared__ int valid_sum;
+    const int b = blockIdx.z;
+    if (blockIdx.x == 0) {   // workgroup-uniform
+        const int* g = hist + (int64_t)b * kBins;
+        int s = 0;
+        for (int i = threadIdx.x; i < kBins; i += kBuildBlock) s += g[i];
+        if (threadIdx.x == 0) valid_sum = 0;
+        __syncthreads();
+        if (s) atomicAdd(&valid_sum, s);
+        __syncthreads();
+        if (threadIdx.x == 0) num_valid[b] = valid_sum;
+    }
+    unsigned long long mine;
+    int64_t at;
+    if (!cand_place(L, meta, sel, counts, tile, mine, at)) return;
+    const unsigned flat = (unsigned)mine;
+    if (flat >= (unsigned)L.lv[0].count) return;   // a guard only: every selected key carries an index of the level
+    const int r = (int)(flat / (unsigned)num_classes), c = (int)(flat - (unsigned)r * (unsigned)num_classes);
+    const float* row = R.rois + ((int64_t)b * R.m + r) * R.row_stride;
+    float p[5], box[5];
+    if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+        const float4 v = *reinterpret_cast<const float4*>(row);
+        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = row[k];
+    }
+    if constexpr (DIM == 5) p[4] = row[4];
+    RB::candidate_box<DIM>(R, p, b, r, c, nm, max_ratio, coder_flags, ctr_clamp, box);
+#pragma unroll
+    for (int k = 0; k < DIM; k++) boxes[at * DIM + k] = box[k];
+    scores[at] = score_of_desc_bits((unsigned)(mine >> 32));
+    labels[at] = c;
+    prior[at] = r;
+}
+
 // workspace: histograms | meta (these two are zeroed by every call) | survivors | selection | candidate block | counts | NMS stage
 struct Ws { int* hist; Meta* meta; unsigned long long* buf; unsigned long long* sel; float* boxes; float* scores; int64_t* labels; int* prior;
             int* counts; void* nms; int64_t zero_bytes, bytes; };
@@ -471,6 +524,33 @@ int sph2pob_test_bboxes_on_probs(const void* const* probs, const void* const* bb
                                                class_agnostic, iou_threshold, max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
     };
     return delta_dtype == 0 ? run(float{}) : delta_dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
+}
+
+// Stages 1-10 of sph2pob_rcnn_bboxes_f32 (sph2pob_rcnn_bboxes.hip, whose stage 0 wrote `probs` and which checked the arguments): the
+// selection on one flat level of M rows, cand_build_rois_kernel, the NMS stage.  Inside the library only
+int sph2pob_rois_bboxes_on_probs(const float* probs, const RB::Rois* rois, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
+                                 int64_t max_candidates, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
+                                 float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
+                                 int64_t* labels, int64_t* prior_inds, int64_t* num_dets, int64_t* num_valid, void* workspace, void* stream) {
+    Levels L;
+    const RB::Rois R = *rois;
+    if (int rc = RB::make_roi_level(num_images, R.m, R.row_stride, num_classes + 1, box_dim, 1 - R.per_class, variant_flags, class_agnostic,
+                                    max_candidates, max_per_img, max_ratio, coder_flags, &L))
+        return rc;
+    if (!probs || !num_valid) return SPH2POB_ERR_NULL;
+    L.lv[0].cls = probs;
+    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
+    return pipeline<float>(L, num_images, box_dim, 0, score_thr, max_candidates, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
+                           prior_inds, num_dets, workspace, stream, [&](const Ws& w, dim3 bgrid, hipStream_t s) {
+        if (box_dim == 4)
+            hipLaunchKernelGGL((cand_build_rois_kernel<4>), bgrid, dim3(kBuildBlock), 0, s, L, R, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+                               (const int*)w.hist, (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior,
+                               w.counts, num_valid);
+        else
+            hipLaunchKernelGGL((cand_build_rois_kernel<5>), bgrid, dim3(kBuildBlock), 0, s, L, R, (const Meta*)w.meta, (const unsigned long long*)w.sel,
+                               (const int*)w.hist, (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior,
+                               w.counts, num_valid);
+    });
 }
 
 // the closed-form calculators, per class: its own variant check (after the box_dim check, as documented), then the entry above

@@ -34,6 +34,7 @@
 #include "sph2pob_softmax.hpp"
 #include "sph2pob_sample.hpp"
 #include "sph2pob_rcnn_targets.hpp"
+#include "sph2pob_rcnn_bboxes.hpp"
 #include "sph2pob_point_targets.hpp"
 #include "sph2pob_point_bbox_loss.hpp"
 #include "sph2pob_bce_loss.hpp"
@@ -536,6 +537,7 @@ SPH2POB_ANCHOR_TARGETS_TWIN(sph2pob_anchor_targets_any_f32_cpu, per_pair_only)
 }  // extern "C"
 
 namespace {
+// candidate(level, l, b, prior ai, class c, selected score, box) -> the score the candidate goes into the NMS with
 template <class Candidate>
 int bboxes_cpu(const sph2pob_gb::Levels& L, int64_t num_images, int64_t num_classes, int box_dim, int activation, float score_thr, int variant,
                int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets,
@@ -565,10 +567,11 @@ int bboxes_cpu(const sph2pob_gb::Levels& L, int64_t num_images, int64_t num_clas
                 const unsigned flat = (unsigned)keys[i];
                 const int ai = (int)(flat / (unsigned)num_classes);
                 float box[5];
-                const float score = candidate(lv, l, b, ai, GB::score_of_desc_bits((unsigned)(keys[i] >> 32)), box);
+                const int c = (int)(flat - (unsigned)ai * (unsigned)num_classes);
+                const float score = candidate(lv, l, b, ai, c, GB::score_of_desc_bits((unsigned)(keys[i] >> 32)), box);
                 boxes.insert(boxes.end(), box, box + dim);
                 scores.push_back(score);
-                cls.push_back((int64_t)(flat - (unsigned)ai * (unsigned)num_classes));
+                cls.push_back((int64_t)c);
                 prior.push_back(lv.prior_off + ai);
             }
         }
@@ -623,7 +626,7 @@ int sph2pob_test_bboxes_f32_cpu(const void* const* cls_scores, const void* const
     const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
     const int dim = box_dim;
     return bboxes_cpu(L, num_images, num_classes, box_dim, activation, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                      prior_inds, num_dets, [&](const GB::Level& lv, int, int64_t b, int ai, float score, float* box) {
+                      prior_inds, num_dets, [&](const GB::Level& lv, int, int64_t b, int ai, int, float score, float* box) {
         float p[5] = {0, 0, 0, 0, 0}, d[5];
         for (int k = 0; k < dim; k++) p[k] = lv.anchors[(int64_t)ai * dim + k];
         if (dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); sph2pob_coder::decode_one<4, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
@@ -647,7 +650,7 @@ int sph2pob_fcos_bboxes_f32_cpu(const void* const* cls_scores, const void* const
         return rc;
     const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
     return bboxes_cpu(L, num_images, num_classes, box_dim, activation, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                      prior_inds, num_dets, [&](const GB::Level& lv, int l, int64_t b, int ai, float score, float* box) {
+                      prior_inds, num_dets, [&](const GB::Level& lv, int l, int64_t b, int ai, int, float score, float* box) {
         float d[5], out[5];
         if (box_dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); PT::decode_row<4, false>(lv.anchors + 2 * (int64_t)ai, d, nullptr, im, out); }
         else { GB::gather_deltas<5>(lv, b, ai, d); PT::decode_row<5, false>(lv.anchors + 2 * (int64_t)ai, d, nullptr, im, out); }
@@ -1298,6 +1301,62 @@ int sph2pob_softmax_bboxes_f32_cpu(const void* const* cls_scores, const void* co
     return sph2pob_test_bboxes_f32_cpu(in, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0, score_thr,
                                        nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, class_agnostic, iou_threshold,
                                        max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+}
+
+}  // extern "C"
+
+// ---- inference of the R-CNN stage: the twin of sph2pob_rcnn_bboxes.hip — Prob on the rows in front of every image's count (-inf
+// behind it, nothing of those rows is read), the count of the valid candidates, then the twin of the pipeline on one flat level with
+// candidate_box of sph2pob_rcnn_bboxes.hpp (the workspace is not used) ----
+extern "C" {
+
+int sph2pob_rcnn_bboxes_f32_cpu(const float* rois, const int64_t* num_rois, const float* cls_score, const float* bbox_pred, int64_t num_images,
+                                int64_t m, int64_t row_stride, int64_t num_logits, int box_dim, int reg_class_agnostic, float score_thr,
+                                int64_t max_candidates, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
+                                float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
+                                int64_t* labels, int64_t* prior_inds, int64_t* num_dets, int64_t* num_valid, void* workspace, void*) {
+    (void)workspace;
+    namespace GB = sph2pob_gb;
+    namespace RB = sph2pob_rcnn_bb;
+    GB::Levels L;
+    if (int rc = RB::make_roi_level(num_images, m, row_stride, num_logits, box_dim, reg_class_agnostic, variant, class_agnostic, max_candidates,
+                                    max_per_img, max_ratio, coder_flags, &L))
+        return rc;
+    if (!rois || !cls_score || !num_dets || !num_valid || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    const int K = (int)num_logits, C = K - 1;
+    std::vector<float> probs((size_t)(num_images * m * C));
+    parallel_for(num_images * m, 1 << 10, [&](int64_t lo, int64_t hi) {
+        for (int64_t row = lo; row < hi; row++) {
+            const int64_t b = row / m;
+            float* o = probs.data() + row * C;
+            if (row - b * m >= RB::live_rows(num_rois, b, (int)m)) {
+                for (int j = 0; j < C; j++) o[j] = -INFINITY;
+                continue;
+            }
+            const float* x = cls_score + row * K;
+            SM::Prob r;
+            r.begin();
+            for (int j = 0; j < K; j++) r.see_max(x[j]);
+            for (int j = 0; j < K; j++) r.see_sum(x[j]);
+            for (int j = 0; j < C; j++) o[j] = r.p(x[j]);
+        }
+    });
+    for (int64_t b = 0; b < num_images; b++) {
+        const float* p = probs.data() + b * m * C;
+        int64_t n = 0;
+        for (int64_t i = 0; i < m * C; i++) n += p[i] > score_thr ? 1 : 0;
+        num_valid[b] = n;
+    }
+    L.lv[0].cls = probs.data();
+    const RB::Rois R = RB::make_rois(rois, num_rois, bbox_pred, m, row_stride, C, box_dim, reg_class_agnostic);
+    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
+    return bboxes_cpu(L, num_images, C, box_dim, 0, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels, prior_inds, num_dets,
+                      [&](const GB::Level&, int, int64_t b, int r, int c, float score, float* box) {
+        const float* row = rois + (b * m + r) * row_stride;
+        if (box_dim == 4) RB::candidate_box<4>(R, row, b, r, c, nm, max_ratio, coder_flags, ctr_clamp, box);
+        else RB::candidate_box<5>(R, row, b, r, c, nm, max_ratio, coder_flags, ctr_clamp, box);
+        return score;
+    });
 }
 
 }  // extern "C"

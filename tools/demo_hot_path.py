@@ -442,14 +442,78 @@ def fcos_infer_outputs(images=8, num_classes=37, dim=4, seed=0, device='cuda', d
     return tuple([t.detach().to(dtype) for t in level] for level in (cls, box, ctr))
 
 
-def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None, softmax_head=False, fcos_head=False):
+def run_rcnn_infer(images, num_classes, seed, reps, test_cfg, proposals=1000, dev='cuda'):
+    """`run_batch_infer(rcnn_head=True)`: two-stage inference from the RPN head's outputs to the final detections.  Stage one is
+    sph_softmax_bboxes on a two-channel RPN head (K = 2, the background last) over the 5 levels, nms_pre = 1000 per level,
+    iou_threshold 0.7, max_per_img = `proposals`; its padded `dets, num_dets` go into sph_rcnn_bboxes in place, score column
+    included, with stand-in head outputs for the B * proposals rows (the RoI extractor and the FC layers are outside this project,
+    as in `run_rcnn_batch`) under test_cfg.rcnn.  The step is captured whole into one graph and replayed: nothing is read back."""
+    anchors = retina_level_anchors()
+    rpn_cls, rpn_box = softmax_head_outputs(images, 1, seed=seed)
+    coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
+    rpn_coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(1., 1., 1., 1.))
+    calc = test_cfg.get('iou_calculator', 'sph2pob_efficient')
+    rpn_cfg = dict(nms_pre=1000, score_thr=0.0, nms=dict(type='nms', iou_threshold=0.7), max_per_img=proposals, iou_calculator=calc,
+                   box_formator=test_cfg.get('box_formator', 'sph2pix'))
+    rcnn_cfg = {k: v for k, v in test_cfg.items() if k not in ('nms_pre', 'min_bbox_size')}
+    g = torch.Generator(device=dev).manual_seed(seed + 1)
+    cls_score = torch.randn((images * proposals, num_classes + 1), generator=g, device=dev) * 2
+    cls_score[:, -1] = 2.0
+    bbox_pred = torch.randn((images * proposals, num_classes * 4), generator=g, device=dev) * 0.5
+
+    def step():
+        rpn = S.sph_softmax_bboxes(rpn_cls, rpn_box, anchors, bbox_coder=rpn_coder, test_cfg=rpn_cfg, box_version=4)
+        return rpn, S.sph_rcnn_bboxes(rpn.dets, cls_score, bbox_pred, num_rois=rpn.num_dets, bbox_coder=coder, test_cfg=rcnn_cfg,
+                                      num_classes=num_classes, box_version=4)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        rpn, r = step()
+    graph.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        graph.replay()
+    torch.cuda.synchronize()
+    replay_ms = (time.perf_counter() - t0) / reps * 1e3
+
+    def eager_ms(fn):   # one stage alone, eager, on the tensors the last replay left
+        fn()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t1) / reps * 1e3
+    rpn_ms = eager_ms(lambda: S.sph_softmax_bboxes(rpn_cls, rpn_box, anchors, bbox_coder=rpn_coder, test_cfg=rpn_cfg, box_version=4))
+    rcnn_ms = eager_ms(lambda: S.sph_rcnn_bboxes(rpn.dets, cls_score, bbox_pred, num_rois=rpn.num_dets, bbox_coder=coder, test_cfg=rcnn_cfg,
+                                                 num_classes=num_classes, box_version=4))
+    out = {'anchors': sum(a.size(0) for a in anchors), 'images': images, 'rcnn_head': True, 'proposals': proposals, 'num_rois': rpn.num_dets.tolist(),
+           'num_valid': r.num_valid.tolist(), 'max_candidates': r.max_candidates, 'num_dets': r.num_dets.tolist(), 'dets': tuple(r.dets.shape),
+           'nms': calc, 'graph_replay_ms': replay_ms, 'rpn_stage_ms': rpn_ms, 'rcnn_stage_ms': rcnn_ms}
+    return out, dict(result=r, rpn=rpn, rpn_cls=rpn_cls, rpn_box=rpn_box, cls_score=cls_score, bbox_pred=bbox_pred, anchors=anchors, coder=coder,
+                     rpn_coder=rpn_coder, rpn_cfg=rpn_cfg, rcnn_cfg=rcnn_cfg, graph=graph)
+
+
+def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None, softmax_head=False, fcos_head=False,
+                    rcnn_head=False):
     """The inference half of `run()` for a minibatch (SphRetinaHead.get_bboxes over the images): the head's per-level NCHW scores
     and deltas -> sph_get_bboxes (per-level top-k, decode, NMS, max_per_img) -> padded detections, no synchronisation.  With a
     `test_cfg` (the reference's dict, e.g. PANDORA_TEST_CFG) the step is sph_test_bboxes under that configuration.
     `softmax_head=True`: the head is a softmax one (K = num_classes + 1 logits per anchor, the background last) and the step is
     sph_softmax_bboxes under `test_cfg` (the default configuration without one).  `fcos_head=True`: SphFCOSHead.get_bboxes — the
     levels are the points of `sph_fcos_points` (10 912), the head gives class logits, pixel distances and centerness logits, and
-    the step is sph_fcos_bboxes under `test_cfg` with `max_shape` = the image; 'anchors' then counts and holds the points."""
+    the step is sph_fcos_bboxes under `test_cfg` with `max_shape` = the image; 'anchors' then counts and holds the points.
+    `rcnn_head=True`: two-stage inference, see `run_rcnn_infer`."""
+    if rcnn_head:
+        return run_rcnn_infer(images, num_classes, seed, reps, test_cfg if test_cfg is not None else
+                              dict(score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100, iou_calculator=nms_calculator))
     if test_cfg is not None:
         nms_calculator = test_cfg.get('iou_calculator', nms_calculator)
     default_cfg = dict(score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100, iou_calculator=nms_calculator)
@@ -494,3 +558,4 @@ if __name__ == '__main__':
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, softmax_head=True)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, fcos_head=True)[0]), flush=True)
+    print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, rcnn_head=True)[0]), flush=True)
