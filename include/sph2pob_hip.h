@@ -500,6 +500,8 @@ int sph2pob_coder_decode_bwd_f32(const float* rois, const float* deltas, const f
  *   otherwise d = pred - target.
  * weight: (n,5) or NULL.  The backward gives the gradients w.r.t. both planar boxes (feed them to
  * sph2pob_transform_bwd_f32 to reach the spherical boxes).  grad_target may be NULL.
+ * NaN as in the reference's autograd graph: the adjoint of |d| is sgn(d) with sgn(NaN) = 0, so a NaN delta sends 0 down its own
+ * column; a NaN operand still reaches every gradient it is multiplied or divided into (a NaN width: the other box's width).
  */
 enum { SPH2POB_L1_ENCODE = 1, SPH2POB_L1_SWAP = 2, SPH2POB_L1_MODULUS = 4 };
 int sph2pob_obb_l1_fwd_f32(const float* planar_pred, const float* planar_target, const float* weight, float scale,

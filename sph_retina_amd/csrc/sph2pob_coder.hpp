@@ -120,6 +120,8 @@ SPHC_DEV float wrap_angle(float a, bool modulus) {
     float r = fmodf(a + kPiF, kPiF);  // torch `%` is a floored remainder: result takes the sign of the divisor
     return (r != 0.0f && r < 0.0f) ? r + kPiF : r;
 }
+// the adjoint of torch.abs is grad * sgn(x), and torch.sgn(NaN) is 0 ((0 < x) - (x < 0)): a NaN element loss sends a zero down
+// its own column, as in the reference's autograd graph (a NaN operand still reaches the gradients it is multiplied into)
 SPHC_DEV float sgn(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
 
 // deltas of proposals p w.r.t. gt g (bbox2delta :39-80, means 0 / stds 1)
@@ -159,6 +161,10 @@ SPHC_DEV void l1_bwd_one(const float* a, const float* b, const float* w, float* 
         obb_deltas(p, g, flags & SPH2POB_L1_MODULUS, d, pw, ph, gw, gh);
 #pragma unroll
         for (int k = 0; k < 5; k++) u[k] = (u[k] * scale) * w[k] * sgn(d[k]);
+        // log(gw / pw): autograd divides the upstream gradient by the ratio, so a NaN width reaches the gradient of the OTHER
+        // box's width (its own is gated to 0 below), although sgn(NaN) = 0 has zeroed u
+        if (d[2] != d[2]) u[2] = d[2];
+        if (d[3] != d[3]) u[3] = d[3];
         gg[0] = u[0] / pw; gp[0] = -gg[0];
         gg[1] = u[1] / ph; gp[1] = -gg[1];
         // clip(min=eps) passes gradients where the width is >= eps

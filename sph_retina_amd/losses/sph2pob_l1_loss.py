@@ -77,6 +77,13 @@ class Sph2PobL1Loss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         box_version = target.size(-1)
         G.require_hip(pred, target)
+        if weight is not None:
+            # the kernel reads the weight at stride 5: (n,) or one column per box component ((n, 4) gets its mean column
+            # below), as `loss * weight` broadcasts in the reference; anything else must not reach a launch
+            if weight.dim() not in (1, 2) or weight.size(0) != target.size(0) or \
+                    (weight.dim() == 2 and weight.size(1) != box_version):
+                raise ValueError(f'weight must be ({target.size(0)},) or ({target.size(0)}, {box_version}) for these boxes, '
+                                 f'got {tuple(weight.shape)}')
         planar_pred, planar_target = _transform('standard', pred, target, 'rad', 'arc', 'equator', jitter=True)
         if weight is not None and weight.dim() > 1 and box_version == 4:   # sph2pob_transform.py:32-34
             weight = torch.cat([weight, weight.mean(-1, keepdim=True)], dim=-1)

@@ -3,7 +3,8 @@
 the HIP kernels through the C ABI against those fixtures and the restatement.
 
 Tolerance: fp32, one rounding of exp / log apart (libm vs Sleef vs ocml): |d| <= 2e-6 * max(1, |value|) for encode and
-4e-7 relative to the box range (360 deg) for decode; gradients 2e-6 relative."""
+4e-7 relative to the box range (360 deg) for decode; gradients 2e-6 relative.  The decode's clamp gates are held
+EXACTLY, at exactly representable boundaries, to a torch float32 autograd restatement (`decode_gate_checks`)."""
 import numpy as np
 import pytest
 import torch
@@ -169,3 +170,147 @@ def test_gpu_batched_decode_equals_per_image_decode(dim, cls):
     d2 = d[:n].clone().requires_grad_(True)
     coder.decode(a[:n], d2).sum().backward()
     assert torch.equal(db.grad.reshape(n, dim), d2.grad)
+
+
+# ---- decode: the clamp gates at exactly representable boundaries ----------------------------------------------------------------
+GATE_STDS = (0.5, 0.5, 0.25, 0.25, 0.5)      # powers of two: delta * std and the products of the Jacobian are exact
+GATE_CTR_CLAMP = 6.0
+GATE_RATIO_CLIP = 16 / 1000
+
+
+def decode_restated(rois, deltas, stds, max_ratio, clip_border, add_ctr_clamp, ctr_clamp):
+    """delta2bbox as plain torch float32 ops (means 0), in the operation order of the C ABI's header comment; the gates are those of
+    torch.clamp's autograd: the gradient passes where lo <= x <= hi and is 0 one ulp outside."""
+    dim = rois.size(1)
+    den = deltas * deltas.new_tensor(stds[:dim])
+    sx, sy, dw, dh = rois[:, 2] * den[:, 0], rois[:, 3] * den[:, 1], den[:, 2], den[:, 3]
+    if add_ctr_clamp:
+        sx, sy = sx.clamp(min=-ctr_clamp, max=ctr_clamp), sy.clamp(min=-ctr_clamp, max=ctr_clamp)
+        dw, dh = dw.clamp(max=max_ratio), dh.clamp(max=max_ratio)
+    else:
+        dw, dh = dw.clamp(min=-max_ratio, max=max_ratio), dh.clamp(min=-max_ratio, max=max_ratio)
+    cols = [rois[:, 0] + sx, rois[:, 1] + sy, rois[:, 2] * dw.exp(), rois[:, 3] * dh.exp()]
+    if dim == 5:
+        cols.append(rois[:, 4] + den[:, 4] * float(np.float32(180 / np.pi)))
+    if clip_border:
+        his = (360 - 1e-7, 180 - 1e-7, 180 - 1e-7, 180 - 1e-7)
+        cols[:4] = [c.clamp(min=1e-7, max=hi) for c, hi in zip(cols[:4], his)]
+        if dim == 5:
+            cols[4] = cols[4].clamp(min=-90 + 1e-7, max=90 - 1e-7)
+    return torch.stack(cols, dim=1)
+
+
+def gate_table(dim):
+    """-> rois, den (n, dim) float32 and one name per row; den = delta * std is what the clamps see."""
+    f32 = np.float32
+    up = lambda v: np.nextafter(f32(v), f32(np.inf))
+    dn = lambda v: np.nextafter(f32(v), f32(-np.inf))
+    mr = f32(abs(np.log(GATE_RATIO_CLIP)))
+    P = np.array([100.0, 90.0, 2.0, 4.0, 10.0], f32)       # power-of-two extents: p * den is exact
+    D = np.array([1.0, -1.0, 0.5, -0.5, 0.125], f32)
+    rows, names = [], []
+
+    def add(name, p=(), d=()):
+        r, e = P.copy(), D.copy()
+        for k, v in p:
+            r[k] = v
+        for k, v in d:
+            e[k] = v
+        rows.append((r, e))
+        names.append(name)
+    add('base')
+    # sx = p[2] * den[0] = 2 * 3 = ctr_clamp exactly (sy = 4 * 1.5), one ulp beyond, one ulp inside, either sign
+    for k, v in ((0, 3.0), (1, 1.5)):
+        for s in (1, -1):
+            add(f'ctr{k}_on_{s}', d=[(k, s * f32(v))])
+            add(f'ctr{k}_beyond_{s}', d=[(k, s * up(v))])
+            add(f'ctr{k}_inside_{s}', d=[(k, s * dn(v))])
+    for k in (2, 3):
+        for s in (1, -1):
+            add(f'ratio{k}_on_{s}', d=[(k, s * mr)])
+            add(f'ratio{k}_beyond_{s}', d=[(k, s * up(mr))])
+            add(f'ratio{k}_inside_{s}', d=[(k, s * dn(mr))])
+    # the decoded x on f32(360 - 1e-7) = 360 and on 1e-7, y on f32(180 - 1e-7) = 180 and on 1e-7, and one ulp outside
+    add('x_354_plus_6', p=[(0, 354.0)], d=[(0, 3.0)])
+    for k, hi in ((0, 360.0), (1, 180.0)):
+        add(f'border{k}_hi_on', p=[(k, hi)], d=[(k, 0.0)])
+        add(f'border{k}_hi_beyond', p=[(k, up(hi))], d=[(k, 0.0)])
+        add(f'border{k}_hi_inside', p=[(k, dn(hi))], d=[(k, 0.0)])
+        add(f'border{k}_lo_on', p=[(k, f32(1e-7))], d=[(k, 0.0)])
+        add(f'border{k}_lo_beyond', p=[(k, dn(1e-7))], d=[(k, 0.0)])
+        add(f'border{k}_lo_inside', p=[(k, up(1e-7))], d=[(k, 0.0)])
+    # w = p[2] * exp(0) = p[2] on the border clamp's bounds
+    for k in (2, 3):
+        add(f'extent{k}_hi_on', p=[(k, 180.0)], d=[(k, 0.0)])
+        add(f'extent{k}_hi_beyond', p=[(k, up(180.0))], d=[(k, 0.0)])
+        add(f'extent{k}_lo_on', p=[(k, f32(1e-7))], d=[(k, 0.0)])
+        add(f'extent{k}_lo_beyond', p=[(k, dn(1e-7))], d=[(k, 0.0)])
+    if dim == 5:   # gamma on f32(+-90 -+ 1e-7) = +-90
+        for s in (1, -1):
+            add(f'gamma_on_{s}', p=[(4, s * f32(90))], d=[(4, 0.0)])
+            add(f'gamma_beyond_{s}', p=[(4, s * up(90))], d=[(4, 0.0)])
+            add(f'gamma_inside_{s}', p=[(4, s * dn(90))], d=[(4, 0.0)])
+    rois = np.stack([r[0][:dim] for r in rows])
+    den = np.stack([r[1][:dim] for r in rows])
+    return rois, den, names
+
+
+def decode_gate_checks(device):
+    """Values and gradients of decode on the gate table EQUAL the torch float32 autograd restatement evaluated on the same device,
+    for both `add_ctr_clamp` and both `clip_border` settings and both box dimensions; every gate of the table really fires."""
+    import sph_retina_amd.bbox.coder as C
+    max_ratio = abs(np.log(GATE_RATIO_CLIP))
+    for dim in (4, 5):
+        rois_np, den, names = gate_table(dim)
+        stds = GATE_STDS[:dim]
+        deltas_np = (den / np.array(stds, np.float32)).astype(np.float32)
+        assert np.array_equal(deltas_np * np.array(stds, np.float32), den)                     # exact
+        gout = cu(np.random.default_rng(dim).uniform(0.5, 1.5, den.shape).astype(np.float32), device)
+        rois = cu(rois_np, device)
+        grads = {}
+        for clip_border in (False, True):
+            for add_ctr_clamp in (False, True):
+                what = (device, dim, clip_border, add_ctr_clamp)
+                d = cu(deltas_np, device).requires_grad_(True)
+                dec = C.delta2bbox(rois, d, (0.,) * dim, stds, wh_ratio_clip=GATE_RATIO_CLIP, clip_border=clip_border,
+                                   add_ctr_clamp=add_ctr_clamp, ctr_clamp=GATE_CTR_CLAMP)
+                dec.backward(gout)
+                r = cu(deltas_np, device).requires_grad_(True)
+                ref = decode_restated(rois, r, stds, max_ratio, clip_border, add_ctr_clamp, GATE_CTR_CLAMP)
+                ref.backward(gout)
+                bad = (dec.detach() != ref.detach()).nonzero().tolist()
+                assert not bad, (what, 'values', [(names[i], k, dec[i, k].item(), ref[i, k].item()) for i, k in bad[:5]])
+                bad = (d.grad != r.grad).nonzero().tolist()
+                assert not bad, (what, 'gradients', [(names[i], k, d.grad[i, k].item(), r.grad[i, k].item()) for i, k in bad[:5]])
+                grads[(clip_border, add_ctr_clamp)] = d.grad.cpu().numpy()
+
+        def g(name, col, clip_border, add_ctr_clamp):
+            return grads[(clip_border, add_ctr_clamp)][names.index(name), col]
+        # the table does what it says: the gradient passes ON the bound and is zero one ulp beyond it
+        for k in (0, 1):
+            for s in (1, -1):
+                assert g(f'ctr{k}_on_{s}', k, False, True) != 0 and g(f'ctr{k}_inside_{s}', k, False, True) != 0
+                assert g(f'ctr{k}_beyond_{s}', k, False, True) == 0 and g(f'ctr{k}_beyond_{s}', k, False, False) != 0
+            assert g(f'border{k}_hi_on', k, True, False) != 0 and g(f'border{k}_hi_beyond', k, True, False) == 0
+            assert g(f'border{k}_lo_on', k, True, False) != 0 and g(f'border{k}_lo_beyond', k, True, False) == 0
+            assert g(f'border{k}_hi_beyond', k, False, False) != 0
+        assert g('x_354_plus_6', 0, True, True) != 0
+        for k in (2, 3):
+            assert g(f'ratio{k}_on_1', k, False, False) != 0 and g(f'ratio{k}_beyond_1', k, False, False) == 0
+            assert g(f'ratio{k}_on_-1', k, False, False) != 0 and g(f'ratio{k}_beyond_-1', k, False, False) == 0
+            assert g(f'ratio{k}_beyond_-1', k, False, True) != 0 and g(f'ratio{k}_beyond_1', k, False, True) == 0   # upper bound only
+            assert g(f'extent{k}_hi_on', k, True, False) != 0 and g(f'extent{k}_hi_beyond', k, True, False) == 0
+            assert g(f'extent{k}_lo_on', k, True, False) != 0 and g(f'extent{k}_lo_beyond', k, True, False) == 0
+        if dim == 5:
+            for s in (1, -1):
+                assert g(f'gamma_on_{s}', 4, True, False) != 0 and g(f'gamma_beyond_{s}', 4, True, False) == 0
+                assert g(f'gamma_beyond_{s}', 4, False, False) != 0
+
+
+def test_cpu_twin_decode_gates_at_exact_boundaries():
+    decode_gate_checks('cpu')
+
+
+@pytest.mark.gpu
+def test_gpu_decode_gates_at_exact_boundaries():
+    decode_gate_checks('cuda')
