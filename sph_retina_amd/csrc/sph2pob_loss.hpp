@@ -444,35 +444,49 @@ SPH_DEV float gauss_post(float d, int fun, float tau, float& dpost) {
     if (tau >= 1.0f) {
         const float q = rcp_nr(tau + v);
         g *= q * q;
-        v = 1.0f - q;
+        v = ((tau - 1.0f) + v) * q;   // 1 - 1 / (tau + v) without the cancellation: at v ~ 3e-4 `1 - q` keeps 11 bits
     }
     dpost = g;
     return v;
 }
 
+// x - log1p(x) without the cancellation near 0 (x^2 / 2 - x^3 / 3 + ...: below 2^-6 the series, truncated at 2e-8 relative)
+SPH_DEV float x_minus_log1p(float x) {
+    if (fabsf(x) < 0.015625f) return x * x * (0.5f - x * ((1.0f / 3.0f) - x * (0.25f - x * 0.2f)));
+    return x - log1pf(x);
+}
+
 // kld_loss before its sqrt / post-map, reference box a (the inverse is taken of a's covariance), other box b:
 //   0.5 d^T Sa^-1 d / alpha^2 + 0.5 tr(Sa^-1 Sb) + 0.5 ln(det Sa / det Sb) - 1,   (u, v) = d in a's axes
-SPH_DEV float kld_raw(float Aa, float Ba, float Ab, float Bb, float u, float v, float c2, float s2, float ia2, float lr) {
+// As pred -> target, 0.5 tr -> 1 and the logarithm -> 0 while the sum falls to 1e-5 and below: written as it stands the result
+// keeps the absolute error of the 1 (1e-7, i.e. 1e-2 relative, and the gradient of its square root with it).  In the
+// differences dA = Ab - Aa, dB = Bb - Ba (formed from the differences of the extents), eb = Bb - Ab, ea = Ba - Aa:
+//   0.5 tr - 1 + 0.5 ln(.) = 0.5 [ (x - log1p x) + (y - log1p y) + s2 eb ea / (Aa Ba) ],   x = dA / Aa, y = dB / Ba
+SPH_DEV float kld_raw(float Aa, float Ba, float dA, float dB, float eb, float ea, float u, float v, float s2, float ia2) {
     const float iAa = rcp_nr(Aa), iBa = rcp_nr(Ba);
     const float xy = 0.5f * (u * u * iAa + v * v * iBa);
-    const float tr = (Ab * c2 + Bb * s2) * iAa + (Ab * s2 + Bb * c2) * iBa;
-    return xy * ia2 + 0.5f * tr + 0.5f * lr - 1.0f;
+    const float shape = (x_minus_log1p(dA * iAa) + x_minus_log1p(dB * iBa)) + s2 * eb * ea * (iAa * iBa);
+    return xy * ia2 + 0.5f * shape;
 }
 // its adjoint for an upstream gradient G: accumulates d/d(Aa, Ba, Ab, Bb), d/d(centre offset x), d/d(a_a) through the
-// axes of (u, v) [(ca, sa) = cos / sin a_a] and d/d(a_a - a_b) [cs = cos * sin of a_a - a_b]
-SPH_DEV void kld_raw_adj(float G, float Aa, float Ba, float Ab, float Bb, float u, float v, float ca, float sa, float c2,
-                         float s2, float cs, float ia2, float& gAa, float& gBa, float& gAb, float& gBb, float& gdx,
-                         float& gaa, float& gdab) {
+// axes of (u, v) [(ca, sa) = cos / sin a_a] and d/d(a_a - a_b) [cs = cos * sin of a_a - a_b]; the same differences keep the
+// extent columns, which vanish as the boxes meet, free of the 1 - 1 they would otherwise be read off
+SPH_DEV void kld_raw_adj(float G, float Aa, float Ba, float Ab, float Bb, float dA, float dB, float eb, float ea, float u, float v,
+                         float ca, float sa, float s2, float cs, float ia2, float& gAa, float& gBa, float& gAb, float& gBb,
+                         float& gdx, float& gaa, float& gdab) {
     const float iAa = rcp_nr(Aa), iBa = rcp_nr(Ba);
     const float gu = G * ia2 * u * iAa, gv = G * ia2 * v * iBa;
     gdx += gu * ca - gv * sa;
     gaa += gu * v - gv * u;
     const float hG = 0.5f * G;
-    gAa += hG * (iAa - (ia2 * u * u + Ab * c2 + Bb * s2) * (iAa * iAa));
-    gBa += hG * (iBa - (ia2 * v * v + Ab * s2 + Bb * c2) * (iBa * iBa));
-    gAb += hG * ((c2 * iAa + s2 * iBa) - rcp_nr(Ab));
-    gBb += hG * ((s2 * iAa + c2 * iBa) - rcp_nr(Bb));
-    gdab += G * cs * (Bb - Ab) * (iAa - iBa);
+    // tr(Sa^-1 Sb) = p + q, p - 1 = (dA + s2 eb) / Aa, q - 1 = (dB - s2 eb) / Ba
+    gAa -= hG * iAa * ((dA + s2 * eb) * iAa + ia2 * u * u * iAa);
+    gBa -= hG * iBa * ((dB - s2 * eb) * iBa + ia2 * v * v * iBa);
+    // c2 / Aa + s2 / Ba - 1 / Ab = dA / (Aa Ab) - s2 ea / (Aa Ba),   s2 / Aa + c2 / Ba - 1 / Bb = dB / (Ba Bb) + s2 ea / (Aa Ba)
+    const float se = s2 * ea * (iAa * iBa);
+    gAb += hG * (dA * iAa * rcp_nr(Ab) - se);
+    gBb += hG * (dB * iBa * rcp_nr(Bb) + se);
+    gdab += G * cs * eb * ea * (iAa * iBa);
 }
 
 // The trailing parameters of the Gaussian launchers, and the per-pair body of their kernels and host twins.
@@ -486,23 +500,10 @@ struct GaussBody {
                        float (&gtarget)[5]) const;
 };
 
-// Per-pair Gaussian loss element; when BWD, also d(loss)/d(pred[0..DIM)) and d(loss)/d(target[0..DIM)) in 1/degree.
-template <int DIM, bool BWD, bool FAST>
-SPH_DEV float pair_gauss_loss(const float (&pred)[5], const float (&target)[5], const GaussBody& p, float (&gpred)[5],
-                              float (&gtarget)[5]) {
-    if (pair_has_nan<DIM>(pred, target)) {   // a NaN coordinate: NaN loss and NaN gradients for the pair (as pair_loss)
-        const float qnan = __builtin_nanf("");
-#pragma unroll
-        for (int k = 0; k < 5; k++) { gpred[k] = k < DIM ? qnan : 0.0f; gtarget[k] = k < DIM ? qnan : 0.0f; }
-        return qnan;
-    }
-    float b1[5], b2[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) { b1[k] = pred[k]; b2[k] = target[k]; }
-    jitter_spherical<DIM>(b1, b2);
-    LossFront f;
-    if (FAST) loss_front_fast<DIM>(b1, b2, f);
-    else loss_front_reference<DIM>(b1, b2, f);
+// The Gaussian body on the planar boxes a front end produced: the loss element and, when BWD, its gradients w.r.t. the two
+// planar boxes.
+template <bool BWD>
+SPH_DEV float gauss_body(const LossFront& f, const GaussBody& p, PlanarGrad& gP, PlanarGrad& gT) {
     const float dx = f.dx, dy = f.dy, c2 = f.c * f.c, s2 = f.s * f.s, cs = f.c * f.s;
     // xy_wh_r_2_xy_sigma: wh.clamp(1e-7, 1e7), Sigma = R diag(wh / 2)^2 R^T
     const float wP = fminf(fmaxf(f.wg, 1e-7f), 1e7f), hP = fminf(fmaxf(f.hg, 1e-7f), 1e7f);
@@ -557,7 +558,17 @@ SPH_DEV float pair_gauss_loss(const float (&pred)[5], const float (&target)[5], 
         const float Q = (AP * AT + BP * BT) * c2 + (AP * BT + BP * AT) * s2;   // tr(S_P S_T)
         const float R = Q + 2.0f * t;
         const float S = sqrt_floor(R, 1e-7f, pr);
-        const float whr = (AP + BP) + (AT + BT) - 2.0f * S;
+        float whr = (AP + BP) + (AT + BT) - 2.0f * S;
+        if (pt && pr) {
+            // no floor is active: t = w_P h_P w_T h_T / 16 and tr S_P + tr S_T - 2 S = ((tr S_P + tr S_T)^2 - 4 R) / (... + 2 S) with
+            //   (.)^2 - 4 R = (tr S_T - tr S_P)^2 + (w_P h_T - h_P w_T)^2 / 4 + 4 s2 (A_P - B_P)(A_T - B_T),
+            // every term from differences of the extents: as pred -> target the subtraction above keeps 1e-7 of a Wasserstein
+            // term that falls to 1e-5, and the gradient (1 / d) with it
+            const float dw = wT - wP, dh = hT - hP;
+            const float dtr = 0.25f * (dw * (wT + wP) + dh * (hT + hP)), cross = wP * dh - hP * dw;
+            const float num = dtr * dtr + 0.25f * cross * cross + 4.0f * s2 * (AP - BP) * (AT - BT);
+            whr = num * rcp_nr((AP + BP) + (AT + BT) + 2.0f * S);
+        }
         const float d2 = (dx * dx + dy * dy) + p.alpha * p.alpha * whr;
         const float Dd = sqrt_floor(d2, 1e-7f, pd);
         float d = Dd, norm = 1.0f, r1 = 1.0f, r2 = 1.0f;
@@ -599,9 +610,11 @@ SPH_DEV float pair_gauss_loss(const float (&pred)[5], const float (&target)[5], 
         const float ca = f.ca, sa = f.sa, cb = f.cb, sb = f.sb;
         const float uP = dx * ca + dy * sa, vP = dy * ca - dx * sa;   // centre offset in P's axes
         const float uT = dx * cb + dy * sb, vT = dy * cb - dx * sb;   // ... in T's axes
-        const float lr = logf(detP * rcp_nr(detT));
-        const float kPT = kld_raw(AP, BP, AT, BT, uP, vP, c2, s2, ia2, lr);
-        const float kTP = p.type == GAUSS_KLD ? 0.0f : kld_raw(AT, BT, AP, BP, uT, vT, c2, s2, ia2, -lr);
+        // differences of the covariances' eigenvalues, from the differences of the extents
+        const float dA = 0.25f * (wT - wP) * (wT + wP), dB = 0.25f * (hT - hP) * (hT + hP);          // A_T - A_P, B_T - B_P
+        const float eP = 0.25f * (hP - wP) * (hP + wP), eT = 0.25f * (hT - wT) * (hT + wT);          // B_P - A_P, B_T - A_T
+        const float kPT = kld_raw(AP, BP, dA, dB, eT, eP, uP, vP, s2, ia2);
+        const float kTP = p.type == GAUSS_KLD ? 0.0f : kld_raw(AT, BT, -dA, -dB, eP, eT, uT, vT, s2, ia2);
         float d, gPT = 0.0f, gTP = 0.0f;   // d(d) / d(kPT), d(d) / d(kTP)
         if (p.type == GAUSS_KLD || p.type == GAUSS_JD) {
             const float r = p.type == GAUSS_KLD ? kPT : 0.5f * (kPT + kTP);
@@ -629,10 +642,11 @@ SPH_DEV float pair_gauss_loss(const float (&pred)[5], const float (&target)[5], 
         loss = gauss_post(d, p.fun, p.tau, gd);
         if (BWD) {
             if (gPT != 0.0f)
-                kld_raw_adj(gd * gPT, AP, BP, AT, BT, uP, vP, ca, sa, c2, s2, cs, ia2, gAP, gBP, gAT, gBT, gdx, gaP, gD);
+                kld_raw_adj(gd * gPT, AP, BP, AT, BT, dA, dB, eT, eP, uP, vP, ca, sa, s2, cs, ia2, gAP, gBP, gAT, gBT, gdx, gaP, gD);
             if (gTP != 0.0f) {
                 float gDtp = 0.0f;   // d/d(a_T - a_P)
-                kld_raw_adj(gd * gTP, AT, BT, AP, BP, uT, vT, cb, sb, c2, s2, -cs, ia2, gAT, gBT, gAP, gBP, gdx, gaT, gDtp);
+                kld_raw_adj(gd * gTP, AT, BT, AP, BP, -dA, -dB, eP, eT, uT, vT, cb, sb, s2, -cs, ia2, gAT, gBT, gAP, gBP, gdx, gaT,
+                            gDtp);
                 gD -= gDtp;
             }
         }
@@ -641,8 +655,44 @@ SPH_DEV float pair_gauss_loss(const float (&pred)[5], const float (&target)[5], 
     // A = w^2 / 4: dA/dw = w / 2; the clamp of w passes the gradient on [1e-7, 1e7]
     const bool gwP = f.wg >= 1e-7f && f.wg <= 1e7f, ghP = f.hg >= 1e-7f && f.hg <= 1e7f;
     const bool gwT = f.wp >= 1e-7f && f.wp <= 1e7f, ghT = f.hp >= 1e-7f && f.hp <= 1e7f;
-    PlanarGrad gP{-gdx, gwP ? 0.5f * wP * gAP : 0.0f, ghP ? 0.5f * hP * gBP : 0.0f, gD + gaP};
-    PlanarGrad gT{gdx, gwT ? 0.5f * wT * gAT : 0.0f, ghT ? 0.5f * hT * gBT : 0.0f, gaT - gD};
+    gP = PlanarGrad{-gdx, gwP ? 0.5f * wP * gAP : 0.0f, ghP ? 0.5f * hP * gBP : 0.0f, gD + gaP};
+    gT = PlanarGrad{gdx, gwT ? 0.5f * wT * gAT : 0.0f, ghT ? 0.5f * hT * gBT : 0.0f, gaT - gD};
+    return loss;
+}
+
+// Per-pair Gaussian loss element; when BWD, also d(loss)/d(pred[0..DIM)) and d(loss)/d(target[0..DIM)) in 1/degree.
+// Reference-order arithmetic (FAST false): the VALUE is the body on the reference-order planar boxes, the reference's own
+// float32 roundings.  The GRADIENT is the adjoint on the closed-form front end's boxes: the reference-order centres come out of
+// acos(cos(A / 2)) in float32, where one ulp of the cosine moves a centre distance of half a degree by 0.25 % and the extent
+// columns of a converged pair, which are differences of such terms, by several percent; a gradient has no roundings to reproduce.
+template <int DIM, bool BWD, bool FAST>
+SPH_DEV float pair_gauss_loss(const float (&pred)[5], const float (&target)[5], const GaussBody& p, float (&gpred)[5],
+                              float (&gtarget)[5]) {
+    if (pair_has_nan<DIM>(pred, target)) {   // a NaN coordinate: NaN loss and NaN gradients for the pair (as pair_loss)
+        const float qnan = __builtin_nanf("");
+#pragma unroll
+        for (int k = 0; k < 5; k++) { gpred[k] = k < DIM ? qnan : 0.0f; gtarget[k] = k < DIM ? qnan : 0.0f; }
+        return qnan;
+    }
+    float b1[5], b2[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) { b1[k] = pred[k]; b2[k] = target[k]; }
+    jitter_spherical<DIM>(b1, b2);
+    LossFront f;
+    PlanarGrad gP{0, 0, 0, 0}, gT{0, 0, 0, 0};
+    float loss;
+    if (FAST) {
+        loss_front_fast<DIM>(b1, b2, f);
+        loss = gauss_body<BWD>(f, p, gP, gT);
+    } else {
+        loss_front_reference<DIM>(b1, b2, f);
+        loss = gauss_body<false>(f, p, gP, gT);
+        if (BWD) {
+            loss_front_fast<DIM>(b1, b2, f);
+            gauss_body<true>(f, p, gP, gT);
+        }
+    }
+    if (!BWD) return loss;
     planar_to_spherical_grads<DIM>(f, gP, gT, /*x_split=*/0.5f, pred, target, /*jitter=*/true, EDGE_ARC, gpred, gtarget);
     return loss;
 }
