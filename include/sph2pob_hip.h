@@ -1202,6 +1202,64 @@ int sph2pob_rcnn_bboxes_f32(const float* rois, const int64_t* num_rois, const fl
                             float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
                             int64_t* labels, int64_t* prior_inds, int64_t* num_dets, int64_t* num_valid, void* workspace, void* stream);
 
+/*
+ * sph2pob_roi_extract_fwd_f32 / sph2pob_roi_extract_bwd_f32 — the RoI feature extractor of the second stage for a whole minibatch:
+ * what SphStandardRoIHead._bbox_forward computes in front of the box head (sphdet/models/heads/sph_rcnn_head.py:211-230 with
+ * sphdet/bbox/box_formator.py:25-49, :76-83) and SingleRoIExtractor behind it (mmdet/models/roi_heads/roi_extractors/
+ * single_level_roi_extractor.py:36-55; RoIAlign of mmcv-full 1.6.0, pool_mode 'avg' — mmcv is not vendored in the reference: its
+ * published algorithm, restated below).  Two launches forward, two backward, whatever B and the roi count are; nothing is read
+ * back, allocated or kept between calls; capturable into a hipGraph.
+ *   feats, heights, widths, strides   HOST tables of num_levels (1 .. 8) entries: the DEVICE pointer of level l, (B, C, H_l, W_l)
+ *                 f32 read in place, its H_l, W_l and its stride (spatial_scale = 1 / stride, rounded to fp32 once)
+ *   rois          form 0: (rows, row_stride) f32, the image index in column 0 and the box in columns [1, 1 + box_dim), row_stride >=
+ *                 1 + box_dim — the reference's flat table;  form 1: (B, M, row_stride) with rows = B M, the box in columns
+ *                 [0, box_dim), row_stride >= box_dim, the image is the row's b
+ *   num_rois      form 1 only: (B) int64 ON THE DEVICE, each clamped to [0, M] before use, or NULL: every image has M
+ *   img_h, img_w  the one img_shape of the batch;  pooled_h, pooled_w in [1, 64];  sampling_ratio >= 0 (0: adaptive);  aligned in
+ *                 {0, 1};  finest_scale > 0
+ * Per roi (theta, phi, alpha, beta[, gamma]) in degrees, all in fp32, in this order, nothing contracted, division and square root
+ * correctly rounded:
+ *   x = theta / 360 img_w;  y = phi / 180 img_h;  w = alpha / 360 img_w;  h = beta / 180 img_h
+ *   box_dim 5:  a = gamma fl32(pi / 180);  (w, h) <- (|cos a| w + |sin a| h, |sin a| w + |cos a| h)
+ *   (x1, y1, x2, y2) = (x - w / 2, y - h / 2, x + w / 2, y + h / 2), y1, y2 clamped to [0, img_h], x1, x2 to [0, img_w]
+ *   level = #{k in 1 .. L - 1: fl32(sqrt((x2 - x1)(y2 - y1)) / finest_scale + 1e-6) >= 2^k}: floor(log2(.)) clamped to [0, L - 1]
+ *   s = 1 / stride of that level, off = 0.5 if aligned else 0:
+ *   sw = x1 s - off; sh = y1 s - off; ew = x2 s - off; eh = y2 s - off; rw = ew - sw; rh = eh - sh (not aligned: each max(., 1))
+ *   bin_h = rh / PH; bin_w = rw / PW; gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / PH); gw likewise, each held to
+ *   [0, 32 768]; count = max(gh gw, 1)
+ *   out[c, ph, pw] = (sum over iy < gh, then ix < gw, of bilinear(y = sh + ph bin_h + (iy + .5) bin_h / gh, x likewise)) / count
+ *   bilinear: 0 unless -1 <= y <= H and -1 <= x <= W;  y <= 0 -> 0;  y_low = (int)y;  y_low >= H - 1 -> y_high = y_low = H - 1,
+ *   y = y_low, else y_high = y_low + 1 (x likewise);  ly = y - y_low, hy = 1 - ly;
+ *   hy hx v(lo, lo) + hy lx v(lo, hi) + ly hx v(hi, lo) + ly lx v(hi, hi), added left to right
+ * Outputs of the forward:
+ *   roi_feats     (rows, C, PH, PW) f32: a fixed-order sum, the same bits on every call
+ *   rois_xyxy     (rows, 4) f32: the planar box the reference hands to RoIAlign
+ *   levels        (rows) int32
+ *   prep          rows x 32 bytes, no initialisation: the roi's record (sw, sh, bin_w, bin_h, gw, gh, image, level), which the
+ *                 backward reads in place of the rois.  Whatever it holds, the level, the image and the grid are clamped before use.
+ * Zero rows.  A row behind its image's count; a row of form 0 whose image index is not an integer of [0, B); a row with a
+ * non-finite box component: zeros in roi_feats, rois_xyxy and levels, no gradient.  Of a row behind the count nothing is read.
+ * A roi without extent (gh = 0 or gw = 0) has no sample: zeros in roi_feats.
+ * Backward: grad_feats[l] (B, C, H_l, W_l) += every term's weight times grad_out / count, for the records of `prep`, with fp32
+ * atomic adds (the summation order is not fixed: the last bits can differ between calls; the CPU twin adds serially in a fixed
+ * order).  zero_first = 1: the gradient buffers are zeroed first, by a launch on the same stream.  The gradient flows to the
+ * features only, as in mmcv.
+ * Errors, checked in this order before anything is enqueued: box_dim -> SPH2POB_ERR_DIM; form, aligned, zero_first outside {0, 1},
+ * sampling_ratio < 0, a finest_scale that is not positive and finite -> SPH2POB_ERR_OPTION; img_h, img_w < 1, a row_stride
+ * too small, form 1 with B M != rows -> SPH2POB_ERR_SIZE; num_levels outside [1, 8], pooled_h, pooled_w outside [1, 64], a stride that
+ * is not positive and finite -> SPH2POB_ERR_OPTION; negative rows, B or C, rows >= 2^31, B > 2^24, C > 2^20, H_l, W_l outside
+ * [1, 2^20], a level above 2^40 elements -> SPH2POB_ERR_SIZE; rows, B or C zero: SPH2POB_OK, nothing enqueued; a NULL table, level,
+ * rois, grad_out, output or prep -> SPH2POB_ERR_NULL (num_rois may be NULL).
+ */
+int sph2pob_roi_extract_fwd_f32(const float* const* feats, const int64_t* heights, const int64_t* widths, const float* strides, int num_levels,
+                                int64_t num_images, int64_t channels, const float* rois, int64_t rows, int64_t row_stride, int form, int64_t m,
+                                const int64_t* num_rois, int box_dim, int64_t img_h, int64_t img_w, int pooled_h, int pooled_w,
+                                int sampling_ratio, int aligned, float finest_scale, float* roi_feats, float* rois_xyxy, int32_t* levels,
+                                void* prep, void* stream);
+int sph2pob_roi_extract_bwd_f32(float* const* grad_feats, const int64_t* heights, const int64_t* widths, const float* strides, int num_levels,
+                                int64_t num_images, int64_t channels, const float* grad_out, int64_t rows, int box_dim, int pooled_h, int pooled_w,
+                                const void* prep, int zero_first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ from .bbox.nms import (DetBBoxes, SphNMS, multiclass_nms, sph_fcos_bboxes, sph_g
                        sph_softmax_scores, sph_test_bboxes)
 from .bbox.assigners import (AnchorTargets, PointTargets, RcnnTargets, SphMaxIoUAssigner, rcnn_bbox_pred, sph_anchor_targets,  # noqa: F401,E402
                              sph_fcos_points, sph_fcos_targets, sph_rcnn_targets, sph_rpn_targets, sph_sample_targets, sph_train_targets)
+from .bbox.roi_extract import RoIFeats, SphSingleRoIExtractor, sph_roi_extract  # noqa: F401,E402
 from .bbox.coder import DeltaXYWHASphBBoxCoder, DeltaXYWHSphBBoxCoder, DistancePointSphBBoxCoder  # noqa: F401,E402
 
 __version__ = '0.1.0'

@@ -38,6 +38,7 @@
 #include "sph2pob_point_targets.hpp"
 #include "sph2pob_point_bbox_loss.hpp"
 #include "sph2pob_bce_loss.hpp"
+#include "sph2pob_roi_extract.hpp"
 
 namespace {
 
@@ -1621,6 +1622,91 @@ int sph2pob_point_coder_decode_bwd_f32_cpu(const float* points, const float* dis
     const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
     if (box_dim == 4) point_coder_rows<4, 2>(points, distances, grad_boxes, grad_distances, n, im, false, 0.0f);
     else point_coder_rows<5, 2>(points, distances, grad_boxes, grad_distances, n, im, false, 0.0f);
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- the RoI feature extractor: the twins of sph2pob_roi_extract.hip — prepare_row, axis_entry and the bin sums of
+// sph2pob_roi_extract.hpp, the axis entries recomputed per use.  Forward: the rois in parallel, every output one fixed-order sum.
+// Backward: one thread, the rois, channels, bins and samples in ascending order — a fixed order where the kernel's atomics have none ----
+namespace {
+namespace RE = sph2pob_roi;
+struct RoiAxis {
+    float start, bin; int g, n;
+    RE::Axis operator()(int k) const { const int q = k / g; return RE::axis_entry(start, bin, g, q, k - q * g, n); }
+};
+}  // namespace
+
+extern "C" {
+
+int sph2pob_roi_extract_fwd_f32_cpu(const float* const* feats, const int64_t* heights, const int64_t* widths, const float* strides, int num_levels,
+                                    int64_t num_images, int64_t channels, const float* rois, int64_t rows, int64_t row_stride, int form, int64_t m,
+                                    const int64_t* num_rois, int box_dim, int64_t img_h, int64_t img_w, int pooled_h, int pooled_w,
+                                    int sampling_ratio, int aligned, float finest_scale, float* roi_feats, float* rois_xyxy, int32_t* levels,
+                                    void* prep, void*) {
+    if (box_dim != 4 && box_dim != 5) return SPH2POB_ERR_DIM;
+    if (int rc = RE::check_options(form, m, row_stride, rows, num_images, box_dim, img_h, img_w, sampling_ratio, aligned, finest_scale)) return rc;
+    RE::Levels L;
+    if (int rc = RE::make_levels(const_cast<float* const*>(feats), false, heights, widths, strides, num_levels, num_images, channels, box_dim,
+                                 pooled_h, pooled_w, rows, &L))
+        return rc;
+    if (L.num == 0) return SPH2POB_OK;
+    if (!rois || !roi_feats || !rois_xyxy || !levels || !prep) return SPH2POB_ERR_NULL;
+    const RE::Options o{box_dim, form, rows, form == 1 ? m : 1, row_stride, (int)num_images, (int)channels, (float)img_h, (float)img_w, finest_scale,
+                        pooled_h, pooled_w, sampling_ratio, aligned};
+    RE::Prep* records = static_cast<RE::Prep*>(prep);
+    const int bins = pooled_h * pooled_w;
+    parallel_for(rows, 8, [&](int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; r++) {
+            records[r] = RE::prepare_row(L, o, rois, num_rois, r, rois_xyxy + r * 4);
+            levels[r] = records[r].lvl;
+            const RE::Prep p = RE::checked(records[r], L.num, (int)num_images);
+            float* out = roi_feats + r * channels * bins;
+            if (p.b < 0 || p.gh == 0 || p.gw == 0) {
+                for (int64_t i = 0; i < channels * bins; i++) out[i] = 0.0f;
+                continue;
+            }
+            const RE::Level lv = L.lv[p.lvl];
+            const RoiAxis ty{p.sh, p.bin_h, p.gh, lv.h}, tx{p.sw, p.bin_w, p.gw, lv.w};
+            const int64_t plane = (int64_t)lv.h * lv.w;
+            for (int64_t c = 0; c < channels; c++)
+                for (int y = 0; y < pooled_h; y++)
+                    for (int x = 0; x < pooled_w; x++)
+                        out[c * bins + y * pooled_w + x] = RE::bin_forward(lv.feat + (p.b * channels + c) * plane, lv.w, p, y, x, ty, tx);
+        }
+    });
+    return SPH2POB_OK;
+}
+
+int sph2pob_roi_extract_bwd_f32_cpu(float* const* grad_feats, const int64_t* heights, const int64_t* widths, const float* strides, int num_levels,
+                                    int64_t num_images, int64_t channels, const float* grad_out, int64_t rows, int box_dim, int pooled_h,
+                                    int pooled_w, const void* prep, int zero_first, void*) {
+    if (zero_first < 0 || zero_first > 1) return (box_dim != 4 && box_dim != 5) ? SPH2POB_ERR_DIM : SPH2POB_ERR_OPTION;
+    RE::Levels L;
+    if (int rc = RE::make_levels(grad_feats, true, heights, widths, strides, num_levels, num_images, channels, box_dim, pooled_h, pooled_w, rows, &L))
+        return rc;
+    if (L.num == 0) return SPH2POB_OK;
+    if (!grad_out || !prep) return SPH2POB_ERR_NULL;
+    if (zero_first)
+        for (int l = 0; l < L.num; l++) memset(L.lv[l].grad, 0, sizeof(float) * num_images * channels * L.lv[l].h * L.lv[l].w);
+    const RE::Prep* records = static_cast<const RE::Prep*>(prep);
+    const int bins = pooled_h * pooled_w;
+    for (int64_t r = 0; r < rows; r++) {
+        const RE::Prep p = RE::checked(records[r], L.num, (int)num_images);
+        if (p.b < 0 || p.gh == 0 || p.gw == 0) continue;
+        const RE::Level lv = L.lv[p.lvl];
+        const RoiAxis ty{p.sh, p.bin_h, p.gh, lv.h}, tx{p.sw, p.bin_w, p.gw, lv.w};
+        const int64_t plane = (int64_t)lv.h * lv.w;
+        const float count = RE::bin_count(p);
+        for (int64_t c = 0; c < channels; c++) {
+            float* g = lv.grad + (p.b * channels + c) * plane;
+            for (int y = 0; y < pooled_h; y++)
+                for (int x = 0; x < pooled_w; x++)
+                    RE::bin_backward(lv.w, p, y, x, grad_out[(r * channels + c) * bins + y * pooled_w + x] / count, ty, tx,
+                                     [g](int64_t at, float v) { g[at] += v; });
+        }
+    }
     return SPH2POB_OK;
 }
 

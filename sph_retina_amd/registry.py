@@ -48,6 +48,7 @@ IOU_CALCULATORS, IOU_CALCULATORS_IS_MMDET = _mmdet_registry('mmdet.core.bbox.iou
 LOSSES, LOSSES_IS_MMDET = _mmdet_registry('mmdet.models.builder', 'LOSSES', 'loss')
 BBOX_ASSIGNERS, BBOX_ASSIGNERS_IS_MMDET = _mmdet_registry('mmdet.core.bbox.builder', 'BBOX_ASSIGNERS', 'bbox_assigner')
 BBOX_CODERS, BBOX_CODERS_IS_MMDET = _mmdet_registry('mmdet.core.bbox.builder', 'BBOX_CODERS', 'bbox_coder')
+ROI_EXTRACTORS, ROI_EXTRACTORS_IS_MMDET = _mmdet_registry('mmdet.models.builder', 'ROI_EXTRACTORS', 'roi_extractor')
 
 
 def build_iou_calculator(cfg, default_args=None):
@@ -68,3 +69,8 @@ def build_assigner(cfg):
 def build_bbox_coder(cfg):
     return BBOX_CODERS.build(cfg) if not BBOX_CODERS_IS_MMDET else \
         __import__('mmdet.core.bbox.builder', fromlist=['x']).build_bbox_coder(cfg)
+
+
+def build_roi_extractor(cfg):
+    return ROI_EXTRACTORS.build(cfg) if not ROI_EXTRACTORS_IS_MMDET else \
+        __import__('mmdet.models.builder', fromlist=['x']).build_roi_extractor(cfg)

@@ -106,7 +106,7 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
               train_cfg=None, loss_bbox=None, softmax_head=False, rpn_cfg=None, rpn_seed=0, fcos_cfg=None, rcnn_cfg=None, rcnn_seed=0,
-              rcnn_proposals=1000, rcnn_decoded=False):
+              rcnn_proposals=1000, rcnn_decoded=False, roi_extract=False, roi_channels=256):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -131,12 +131,13 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     `rcnn_cfg`: the step of the second stage of a two-stage detector instead (`run_rcnn_batch`, and nothing else of the above): the
     reference's `train_cfg.rcnn` with its RandomSampler(add_gt_as_proposals=True); `rcnn_proposals` padded proposals per image in the
     layout of the batched inference entries, `rcnn_seed` a Python int or a () int64 device tensor, `rcnn_decoded`: the box loss on the
-    decoded boxes (reg_decoded_bbox=True) instead of on the raw deltas."""
+    decoded boxes (reg_decoded_bbox=True) instead of on the raw deltas; `roi_extract=True`: the step starts from random FPN levels
+    (`sph_roi_extract` and two stand-in Linear heads in place of the random head outputs)."""
     dev = 'cuda'
     if rcnn_cfg is not None:
         if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None or fcos_cfg is not None:
             raise ValueError('rcnn_cfg is a step of its own: sph_rcnn_targets + cross_entropy + the box loss on the gathered predictions')
-        return run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed, rcnn_proposals, rcnn_decoded, dev)
+        return run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed, rcnn_proposals, rcnn_decoded, dev, roi_extract=roi_extract, channels=roi_channels)
     if fcos_cfg is not None:
         if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None:
             raise ValueError('fcos_cfg is a step of its own: sph_fcos_targets + sph_focal_loss + Sph2PobIoULoss on the point decode + BCE')
@@ -319,12 +320,32 @@ def synthetic_proposals(gts, m, seed=0, device='cuda'):
     return dets.to(device), torch.tensor(counts, dtype=torch.int64).to(device)
 
 
-def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=1000, decoded=False, dev='cuda'):
+ROI_CFG = dict(img_shape=(512, 1024), featmap_strides=(4, 8, 16, 32), output_size=7, sampling_ratio=0, finest_scale=56)   # faster_rcnn_r50_fpn.py
+
+
+def fpn_levels(images, channels=256, seed=0, device='cuda', requires_grad=False):
+    """Random FPN levels of a 512 x 1024 image at the strides of ROI_CFG: (B, channels, 128, 256) ... (B, channels, 16, 32)."""
+    g = torch.Generator(device=device).manual_seed(seed + 7)
+    h, w = ROI_CFG['img_shape']
+    return [torch.randn((images, channels, h // s, w // s), generator=g, device=device).requires_grad_(requires_grad) for s in ROI_CFG['featmap_strides']]
+
+
+def roi_heads(channels, num_classes, seed=0, device='cuda'):
+    """Two stand-in Linear heads on the flattened RoI features (the reference's shared FC layers are torch's own GEMMs)."""
+    torch.manual_seed(seed + 11)
+    fan_in = channels * ROI_CFG['output_size'] ** 2
+    return torch.nn.Linear(fan_in, num_classes + 1).to(device), torch.nn.Linear(fan_in, num_classes * 4).to(device)
+
+
+def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=1000, decoded=False, dev='cuda', roi_extract=False, channels=256):
     """`run_batch(rcnn_cfg=...)`: SphStandardRoIHead._bbox_forward_train without the RoI extractor — proposals (`dets, num_dets`, read in
     place) and concatenated GT -> `sph_rcnn_targets` -> flat `cross_entropy` on (S, C + 1) logits with `avg_factor=t.avg_factor`, and
     the box loss on `rcnn_bbox_pred`'s gather over all S rows with `avg_factor=t.num_samples`: L1 on the raw deltas, or with
     `decoded` Sph2PobIoULoss on `decode(rois[:, 1:], gathered)` against GT boxes.  Padding and background rows have weight 0.  The
-    step, backward included, is captured into a graph and replayed: nothing is read back."""
+    step, backward included, is captured into a graph and replayed: nothing is read back.
+    `roi_extract=True`: the step starts from random FPN levels instead of random head outputs — `sph_roi_extract` on `t.rois` as they
+    are, then two stand-in Linear heads give `cls_score` / `bbox_pred`; the captured graph spans features -> losses -> the gradients
+    of the levels and of the heads."""
     g = torch.Generator().manual_seed(seed)
     gts, labels = [], []
     for k in counts:
@@ -343,16 +364,31 @@ def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=100
     cls_score = torch.randn((images * num, num_classes + 1), generator=gd, device=dev).requires_grad_(True)
     bbox_pred = (torch.randn((images * num, num_classes * 4), generator=gd, device=dev) * 0.05).requires_grad_(True)
 
+    feats, leaves = None, (cls_score, bbox_pred)
+    if roi_extract:
+        feats = fpn_levels(images, channels, seed, dev, requires_grad=True)
+        fc_cls, fc_reg = roi_heads(channels, num_classes, seed, dev)
+        leaves = tuple(feats) + tuple(fc_cls.parameters()) + tuple(fc_reg.parameters())
+
     def step():
         t = S.sph_rcnn_targets(dets, gt, lab, off, num_proposals=num_dets, train_cfg=rcnn_cfg, num_classes=num_classes, seed=rcnn_seed,
                                reg_decoded_bbox=decoded, bbox_coder=coder, k_max=k_max)
+        if roi_extract:
+            x = S.sph_roi_extract(feats, t.rois, **ROI_CFG).roi_feats.flatten(1)
+            return _rcnn_losses(t, fc_cls(x), fc_reg(x))
+        return _rcnn_losses(t, cls_score, bbox_pred)
+
+    def _rcnn_losses(t, cls_score, bbox_pred):
         loss_cls = S.cross_entropy(cls_score, t.labels, t.label_weights, avg_factor=t.avg_factor)
         picked = S.rcnn_bbox_pred(bbox_pred, t.labels, num_classes, 4, False)
         if decoded:
             loss_box = loss_iou(coder.decode(t.rois[:, 1:].contiguous(), picked), t.bbox_targets, t.bbox_weights, avg_factor=t.num_samples)
         else:
             loss_box = loss_l1(picked, t.bbox_targets, t.bbox_weights, avg_factor=t.num_samples)
-        return (loss_cls.detach(), loss_box.detach()) + torch.autograd.grad(loss_cls + loss_box, (cls_score, bbox_pred)) + (t,)
+        grads = torch.autograd.grad(loss_cls + loss_box, leaves)
+        if roi_extract:
+            return loss_cls.detach(), loss_box.detach(), grads[-4], grads[-2], t, grads[:len(feats)]
+        return (loss_cls.detach(), loss_box.detach()) + grads + (t, None)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -362,7 +398,7 @@ def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=100
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        loss_cls, loss_box, g_cls, g_box, t = step()
+        loss_cls, loss_box, g_cls, g_box, t, g_feats = step()
     graph.replay()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -375,8 +411,11 @@ def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=100
            'grads_finite': bool(torch.isfinite(g_cls).all()) and bool(torch.isfinite(g_box).all()),
            'cls_grad_rows': int((g_cls.abs().sum(1) > 0).sum()), 'box_grad_rows': int((g_box.abs().sum(1) > 0).sum()),
            'graph_replay_ms': (time.perf_counter() - t0) / reps * 1e3}
+    if roi_extract:   # g_cls / g_box are then the gradients of the two heads' weights
+        out.update(roi_extract=True, feat_grads_finite=all(bool(torch.isfinite(x).all()) for x in g_feats),
+                   feat_grad_levels=[bool(x.any()) for x in g_feats])
     return out, dict(targets=t, dets=dets, num_dets=num_dets, gt=gt, labels=lab, gt_offsets=off, gts=gts, cls_score=cls_score, bbox_pred=bbox_pred,
-                     cls_grad=g_cls, box_grad=g_box, coder=coder, graph=graph)
+                     cls_grad=g_cls, box_grad=g_box, coder=coder, graph=graph, feats=feats, feat_grads=g_feats)
 
 
 def retina_level_anchors(device='cuda'):
@@ -442,12 +481,14 @@ def fcos_infer_outputs(images=8, num_classes=37, dim=4, seed=0, device='cuda', d
     return tuple([t.detach().to(dtype) for t in level] for level in (cls, box, ctr))
 
 
-def run_rcnn_infer(images, num_classes, seed, reps, test_cfg, proposals=1000, dev='cuda'):
+def run_rcnn_infer(images, num_classes, seed, reps, test_cfg, proposals=1000, dev='cuda', roi_extract=False, channels=256):
     """`run_batch_infer(rcnn_head=True)`: two-stage inference from the RPN head's outputs to the final detections.  Stage one is
     sph_softmax_bboxes on a two-channel RPN head (K = 2, the background last) over the 5 levels, nms_pre = 1000 per level,
     iou_threshold 0.7, max_per_img = `proposals`; its padded `dets, num_dets` go into sph_rcnn_bboxes in place, score column
-    included, with stand-in head outputs for the B * proposals rows (the RoI extractor and the FC layers are outside this project,
-    as in `run_rcnn_batch`) under test_cfg.rcnn.  The step is captured whole into one graph and replayed: nothing is read back."""
+    included, with random stand-in head outputs for the B * proposals rows (as in `run_rcnn_batch`; the FC layers are torch's own
+    GEMMs and not part of this project) under test_cfg.rcnn.  The step is captured whole into one graph and replayed: nothing is read back.
+    `roi_extract=True`: the head outputs come from random FPN levels instead — `sph_roi_extract` on the RPN's `dets, num_dets` as they
+    are and two stand-in Linear heads: the graph spans features -> detections."""
     anchors = retina_level_anchors()
     rpn_cls, rpn_box = softmax_head_outputs(images, 1, seed=seed)
     coder = S.DeltaXYWHSphBBoxCoder(target_means=(0., 0., 0., 0.), target_stds=(0.1, 0.1, 0.2, 0.2))
@@ -461,8 +502,17 @@ def run_rcnn_infer(images, num_classes, seed, reps, test_cfg, proposals=1000, de
     cls_score[:, -1] = 2.0
     bbox_pred = torch.randn((images * proposals, num_classes * 4), generator=g, device=dev) * 0.5
 
+    if roi_extract:
+        feats = fpn_levels(images, channels, seed, dev)
+        fc_cls, fc_reg = roi_heads(channels, num_classes, seed, dev)
+
+    @torch.no_grad()
     def step():
         rpn = S.sph_softmax_bboxes(rpn_cls, rpn_box, anchors, bbox_coder=rpn_coder, test_cfg=rpn_cfg, box_version=4)
+        if roi_extract:
+            x = S.sph_roi_extract(feats, rpn.dets, num_rois=rpn.num_dets, **ROI_CFG).roi_feats.flatten(1)
+            return rpn, S.sph_rcnn_bboxes(rpn.dets, fc_cls(x), fc_reg(x), num_rois=rpn.num_dets, bbox_coder=coder, test_cfg=rcnn_cfg,
+                                          num_classes=num_classes, box_version=4)
         return rpn, S.sph_rcnn_bboxes(rpn.dets, cls_score, bbox_pred, num_rois=rpn.num_dets, bbox_coder=coder, test_cfg=rcnn_cfg,
                                       num_classes=num_classes, box_version=4)
     side = torch.cuda.Stream()
@@ -497,12 +547,14 @@ def run_rcnn_infer(images, num_classes, seed, reps, test_cfg, proposals=1000, de
     out = {'anchors': sum(a.size(0) for a in anchors), 'images': images, 'rcnn_head': True, 'proposals': proposals, 'num_rois': rpn.num_dets.tolist(),
            'num_valid': r.num_valid.tolist(), 'max_candidates': r.max_candidates, 'num_dets': r.num_dets.tolist(), 'dets': tuple(r.dets.shape),
            'nms': calc, 'graph_replay_ms': replay_ms, 'rpn_stage_ms': rpn_ms, 'rcnn_stage_ms': rcnn_ms}
+    if roi_extract:
+        out.update(roi_extract=True, roi_extract_ms=eager_ms(lambda: S.sph_roi_extract(feats, rpn.dets, num_rois=rpn.num_dets, **ROI_CFG)))
     return out, dict(result=r, rpn=rpn, rpn_cls=rpn_cls, rpn_box=rpn_box, cls_score=cls_score, bbox_pred=bbox_pred, anchors=anchors, coder=coder,
                      rpn_coder=rpn_coder, rpn_cfg=rpn_cfg, rcnn_cfg=rcnn_cfg, graph=graph)
 
 
 def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient', seed=0, reps=1, test_cfg=None, softmax_head=False, fcos_head=False,
-                    rcnn_head=False):
+                    rcnn_head=False, roi_extract=False, roi_channels=256):
     """The inference half of `run()` for a minibatch (SphRetinaHead.get_bboxes over the images): the head's per-level NCHW scores
     and deltas -> sph_get_bboxes (per-level top-k, decode, NMS, max_per_img) -> padded detections, no synchronisation.  With a
     `test_cfg` (the reference's dict, e.g. PANDORA_TEST_CFG) the step is sph_test_bboxes under that configuration.
@@ -510,10 +562,11 @@ def run_batch_infer(images=8, num_classes=37, nms_calculator='sph2pob_efficient'
     sph_softmax_bboxes under `test_cfg` (the default configuration without one).  `fcos_head=True`: SphFCOSHead.get_bboxes — the
     levels are the points of `sph_fcos_points` (10 912), the head gives class logits, pixel distances and centerness logits, and
     the step is sph_fcos_bboxes under `test_cfg` with `max_shape` = the image; 'anchors' then counts and holds the points.
-    `rcnn_head=True`: two-stage inference, see `run_rcnn_infer`."""
+    `rcnn_head=True`: two-stage inference, see `run_rcnn_infer`; with `roi_extract=True` from random FPN levels."""
     if rcnn_head:
         return run_rcnn_infer(images, num_classes, seed, reps, test_cfg if test_cfg is not None else
-                              dict(score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100, iou_calculator=nms_calculator))
+                              dict(score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100, iou_calculator=nms_calculator),
+                              roi_extract=roi_extract, channels=roi_channels)
     if test_cfg is not None:
         nms_calculator = test_cfg.get('iou_calculator', nms_calculator)
     default_cfg = dict(score_thr=0.05, nms_pre=1000, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100, iou_calculator=nms_calculator)
@@ -559,3 +612,4 @@ if __name__ == '__main__':
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, softmax_head=True)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, fcos_head=True)[0]), flush=True)
     print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, rcnn_head=True)[0]), flush=True)
+    print(json.dumps(run_batch_infer(reps=5, test_cfg=PANDORA_TEST_CFG, rcnn_head=True, roi_extract=True)[0]), flush=True)
