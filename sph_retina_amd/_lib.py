@@ -258,6 +258,13 @@ _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_targe
              'sph2pob_point_bbox_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_bce_loss_workspace_bytes': ctypes.c_int64,
              'sph2pob_rcnn_targets_workspace_bytes': ctypes.c_int64, 'sph2pob_rcnn_bboxes_workspace_bytes': ctypes.c_int64}
 
+# Entry points of libsph2pob_host.so alone, `<name>_cpu`: the CPU statement of a route that has no device entry yet, so the name is
+# neither declared in include/sph2pob_hip.h nor exported by libsph2pob_hip.so.  name -> argtypes
+# sph2pob_roi_extract_bwd_det_f32: the arguments of sph2pob_roi_extract_bwd_f32 with a scratch pointer (not read) in front of the stream
+HOST_ONLY = {
+    'sph2pob_roi_extract_bwd_det_f32': SIGNATURES['sph2pob_roi_extract_bwd_f32'][:-1] + [ctypes.c_void_p, ctypes.c_void_p],
+}
+
 ABI_VERSION = 6
 
 
@@ -385,6 +392,13 @@ def host_lib():
         except AttributeError as e:
             raise Sph2PobLibraryError(f'{HOST_LIB_PATH} does not export {name}_cpu') from e
         fn.argtypes = SIGNATURES[name]
+        fn.restype = _int
+    for name, argtypes in HOST_ONLY.items():
+        try:
+            fn = getattr(handle, name + '_cpu')
+        except AttributeError as e:
+            raise Sph2PobLibraryError(f'{HOST_LIB_PATH} does not export {name}_cpu') from e
+        fn.argtypes = argtypes
         fn.restype = _int
     handle.sph2pob_host_threads.restype = _int
     _HOST = handle

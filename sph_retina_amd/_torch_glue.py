@@ -122,7 +122,7 @@ def call(name, device, *args):
     if device.type == 'cpu':   # the product's host twin of the same entry point (synchronous)
         fn = _FN_CACHE.get((name, 'cpu'))
         if fn is None:
-            if name not in _lib.HOST_TWINS:
+            if name not in _lib.HOST_TWINS and name not in _lib.HOST_ONLY:
                 raise RuntimeError(f'{name} has no CPU twin in libsph2pob_host.so: this operator runs on MI355X tensors only')
             fn = _FN_CACHE[(name, 'cpu')] = getattr(_lib.host_lib(), name + '_cpu')
         rc = fn(*args)

@@ -49,7 +49,7 @@ class _RoIExtractFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rois, num_rois, opt, *feats):
-        form, rows, m, dim, img_h, img_w, strides, ph, pw, ratio, aligned, finest = opt
+        form, rows, m, dim, img_h, img_w, strides, ph, pw, ratio, aligned, finest, _gather = opt
         dev = feats[0].device
         B, C = feats[0].shape[:2]
         roi_feats = torch.empty((rows, C, ph, pw), dtype=torch.float32, device=dev)
@@ -69,15 +69,19 @@ class _RoIExtractFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_feats, _grad_xyxy, _grad_levels):
         prep, = ctx.saved_tensors
-        (form, rows, m, dim, img_h, img_w, strides, ph, pw, ratio, aligned, finest), shapes = ctx.meta
+        (form, rows, m, dim, img_h, img_w, strides, ph, pw, ratio, aligned, finest, gather), shapes = ctx.meta
         dev = prep.device
         B, C = shapes[0][:2]
         empty = not (rows and B and C)
         grads = [(torch.zeros if empty else torch.empty)(s, dtype=torch.float32, device=dev) for s in shapes]
         if not empty:
             go = G.as_f32(grad_feats)
-            G.call('sph2pob_roi_extract_bwd_f32', dev, *_tables(grads, strides), B, C, G.ptr(go), rows, dim, ph, pw, G.ptr(prep), 1,
-                   G.raw_stream_of(dev))
+            if gather:   # CPU tensors only (sph_roi_extract refuses the others): the host entry takes no scratch
+                G.call('sph2pob_roi_extract_bwd_det_f32', dev, *_tables(grads, strides), B, C, G.ptr(go), rows, dim, ph, pw, G.ptr(prep), 1,
+                       None, None)
+            else:
+                G.call('sph2pob_roi_extract_bwd_f32', dev, *_tables(grads, strides), B, C, G.ptr(go), rows, dim, ph, pw, G.ptr(prep), 1,
+                       G.raw_stream_of(dev))
         return (None,) * _RoIExtractFunction._FIXED + tuple(g if need else None
                                                            for g, need in zip(grads, ctx.needs_input_grad[_RoIExtractFunction._FIXED:]))
 
@@ -91,7 +95,7 @@ def _pair(v, name):
 
 
 def sph_roi_extract(feats, rois, *, num_rois=None, img_shape, featmap_strides, output_size=7, sampling_ratio=0, aligned=True,
-                    finest_scale=56, box_version=4, pool_mode='avg', roi_scale_factor=None):
+                    finest_scale=56, box_version=4, pool_mode='avg', roi_scale_factor=None, deterministic=None):
     """RoI features of every roi of a minibatch: the reference's box transform, level mapping and RoIAlign (module docstring).
 
     `feats`: a list of 1 <= L <= 8 levels (B, C, H_l, W_l), fp32 levels are read in place; 16-bit levels are cast to fp32 (the
@@ -110,6 +114,14 @@ def sph_roi_extract(feats, rois, *, num_rois=None, img_shape, featmap_strides, o
     gradients with fp32 atomics: its summation order is NOT fixed, the last bits of a gradient can differ between calls (the CPU
     twin adds serially in a fixed order).  The gradient flows to `feats` only.  Both directions enqueue on the current stream —
     the zeroing of the gradient buffers included — allocate nothing sized by the data and read nothing back.
+
+    `deterministic` selects the gather form of the adjoint, which so far exists for CPU tensors only
+    (`sph2pob_roi_extract_bwd_det_f32_cpu`; csrc/sph2pob_roi_extract.hpp states its order and its bound): every pixel sums its rois
+    in ascending row index, per roi the bins that reach it, and is written once — the order a device route without atomics can
+    keep, so its bits are what such a route is to be held to.  True: that backward; on device tensors NotImplementedError, since no
+    device kernel computes it and nothing falls back.  False: the backward described above.  None (the default):
+    on CPU tensors True where `torch.are_deterministic_algorithms_enabled()` at the time of the call, else False; on device
+    tensors False, as before.
 
     `pool_mode='max'`, `roi_scale_factor` and per-image `img_shape`s raise NotImplementedError."""
     if pool_mode != 'avg':
@@ -169,7 +181,12 @@ def sph_roi_extract(feats, rois, *, num_rois=None, img_shape, featmap_strides, o
         raise RuntimeError(f'{_WHO}: all inputs must be on one device, got ' + ', '.join(sorted({str(t.device) for t in [rx] + xs})))
     if not torch.is_grad_enabled():
         xs = [t.detach() if t.requires_grad else t for t in xs]
-    opt = (form, rows, m, dim, img_h, img_w, tuple(strides), ph, pw, ratio, int(bool(aligned)), finest)
+    on_cpu = rx.device.type == 'cpu'
+    if deterministic and not on_cpu:
+        raise NotImplementedError(f'{_WHO}: deterministic=True has no device kernel yet (the fixed-order gather backward exists for CPU '
+                                  'tensors only); pass deterministic=False for the atomic backward')
+    gather = on_cpu and (torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic))
+    opt = (form, rows, m, dim, img_h, img_w, tuple(strides), ph, pw, ratio, int(bool(aligned)), finest, gather)
     return RoIFeats(*_RoIExtractFunction.apply(rx, num_rois, opt, *xs))
 
 
@@ -181,9 +198,10 @@ class SphSingleRoIExtractor(torch.nn.Module):
                               featmap_strides=[4, 8, 16, 32], finest_scale=56)
 
     `forward(feats, rois, img_shape=...)` takes the SPHERICAL rois (degrees), flat or padded with `num_rois`, and returns the
-    (R, out_channels, PH, PW) features; `extract` returns the whole `RoIFeats`."""
+    (R, out_channels, PH, PW) features; `extract` returns the whole `RoIFeats`.  `deterministic`: as in `sph_roi_extract`."""
 
-    def __init__(self, roi_layer, out_channels, featmap_strides, finest_scale=56, box_version=4, roi_scale_factor=None, init_cfg=None):
+    def __init__(self, roi_layer, out_channels, featmap_strides, finest_scale=56, box_version=4, roi_scale_factor=None, init_cfg=None,
+                 deterministic=None):
         super().__init__()
         cfg = dict(roi_layer)
         kind = cfg.pop('type', 'RoIAlign')
@@ -202,6 +220,7 @@ class SphSingleRoIExtractor(torch.nn.Module):
         if cfg:
             raise TypeError(f'SphSingleRoIExtractor: unknown roi_layer keys {sorted(cfg)}')
         self.out_channels, self.featmap_strides, self.finest_scale, self.box_version = int(out_channels), list(featmap_strides), finest_scale, box_version
+        self.deterministic = deterministic
 
     @property
     def num_inputs(self):
@@ -213,7 +232,7 @@ class SphSingleRoIExtractor(torch.nn.Module):
             raise ValueError(f'SphSingleRoIExtractor: the levels hold {feats[0].size(1)} channels, out_channels is {self.out_channels}')
         return sph_roi_extract(feats, rois, num_rois=num_rois, img_shape=img_shape, featmap_strides=self.featmap_strides,
                                output_size=self.output_size, sampling_ratio=self.sampling_ratio, aligned=self.aligned,
-                               finest_scale=self.finest_scale, box_version=self.box_version)
+                               finest_scale=self.finest_scale, box_version=self.box_version, deterministic=self.deterministic)
 
     def forward(self, feats, rois, img_shape, num_rois=None, roi_scale_factor=None):
         if roi_scale_factor is not None:

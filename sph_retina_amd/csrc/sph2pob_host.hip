@@ -1710,4 +1710,86 @@ int sph2pob_roi_extract_bwd_f32_cpu(float* const* grad_feats, const int64_t* hei
     return SPH2POB_OK;
 }
 
+// The gather form of the adjoint (csrc/sph2pob_roi_extract.hpp states its order and its bound) — an entry of this library alone:
+// no device kernel computes it yet, so include/sph2pob_hip.h does not declare the name.  The arguments of
+// sph2pob_roi_extract_bwd_f32 and, in front of the stream, the scratch a device route would need: not read here, NULL is fine.
+// One thread: the rows in ascending order — so every pixel takes its rois in ascending row index — into a sum of its own per level,
+// which the gradient buffer then takes once (zero_first = 1: the sum itself; 0: its value + the sum).  Per row the Wy, Wx of its
+// reach (axis_weight), per channel and pixel of the reach t_r (gather_term over the bins with a term on both axes).  The result
+// does not depend on sph2pob_host_threads()
+int sph2pob_roi_extract_bwd_det_f32_cpu(float* const* grad_feats, const int64_t* heights, const int64_t* widths, const float* strides, int num_levels,
+                                        int64_t num_images, int64_t channels, const float* grad_out, int64_t rows, int box_dim, int pooled_h,
+                                        int pooled_w, const void* prep, int zero_first, void*, void*) {
+    if (zero_first < 0 || zero_first > 1) return (box_dim != 4 && box_dim != 5) ? SPH2POB_ERR_DIM : SPH2POB_ERR_OPTION;
+    RE::Levels L;
+    if (int rc = RE::make_levels(grad_feats, true, heights, widths, strides, num_levels, num_images, channels, box_dim, pooled_h, pooled_w, rows, &L))
+        return rc;
+    if (L.num == 0) return SPH2POB_OK;
+    if (!grad_out || !prep) return SPH2POB_ERR_NULL;
+    std::vector<std::vector<float>> sums(L.num);
+    for (int l = 0; l < L.num; l++) sums[l].assign((size_t)(num_images * channels * L.lv[l].h * L.lv[l].w), 0.0f);
+    const RE::Prep* records = static_cast<const RE::Prep*>(prep);
+    const int bins = pooled_h * pooled_w;
+    std::vector<float> wy, wx, g(bins);
+    std::vector<char> fy, fx;
+    std::vector<int> ylo, yhi, xlo, xhi;
+    for (int64_t r = 0; r < rows; r++) {
+        const RE::Prep p = RE::checked(records[r], L.num, (int)num_images);
+        if (p.b < 0 || p.gh == 0 || p.gw == 0) continue;
+        const RE::Level lv = L.lv[p.lvl];
+        int y0, y1, x0, x1;
+        RE::axis_reach(p.sh, p.bin_h, pooled_h, lv.h, y0, y1);
+        RE::axis_reach(p.sw, p.bin_w, pooled_w, lv.w, x0, x1);
+        const int fh = y1 - y0 + 1, fw = x1 - x0 + 1;
+        wy.assign((size_t)pooled_h * fh, 0.0f); fy.assign((size_t)pooled_h * fh, 0);
+        wx.assign((size_t)pooled_w * fw, 0.0f); fx.assign((size_t)pooled_w * fw, 0);
+        for (int q = 0; q < pooled_h; q++)
+            for (int y = 0; y < fh; y++) {
+                int terms;
+                wy[(size_t)q * fh + y] = RE::axis_weight(p.sh, p.bin_h, p.gh, q, lv.h, y0 + y, terms);
+                fy[(size_t)q * fh + y] = terms > 0;
+            }
+        for (int q = 0; q < pooled_w; q++)
+            for (int x = 0; x < fw; x++) {
+                int terms;
+                wx[(size_t)q * fw + x] = RE::axis_weight(p.sw, p.bin_w, p.gw, q, lv.w, x0 + x, terms);
+                fx[(size_t)q * fw + x] = terms > 0;
+            }
+        // the bins [lo, hi) between a pixel's first and last flagged one: the loops below test the flags inside
+        ylo.assign(fh, pooled_h); yhi.assign(fh, 0); xlo.assign(fw, pooled_w); xhi.assign(fw, 0);
+        for (int q = 0; q < pooled_h; q++)
+            for (int y = 0; y < fh; y++)
+                if (fy[(size_t)q * fh + y]) { ylo[y] = std::min(ylo[y], q); yhi[y] = q + 1; }
+        for (int q = 0; q < pooled_w; q++)
+            for (int x = 0; x < fw; x++)
+                if (fx[(size_t)q * fw + x]) { xlo[x] = std::min(xlo[x], q); xhi[x] = q + 1; }
+        const int64_t plane = (int64_t)lv.h * lv.w;
+        const float count = RE::bin_count(p);
+        for (int64_t c = 0; c < channels; c++) {
+            for (int k = 0; k < bins; k++) g[k] = grad_out[(r * channels + c) * bins + k] / count;
+            float* sum = sums[p.lvl].data() + (p.b * channels + c) * plane;
+            for (int y = 0; y < fh; y++)
+                for (int x = 0; x < fw; x++) {
+                    float t = 0.0f;
+                    bool reached = false;
+                    for (int qy = ylo[y]; qy < yhi[y]; qy++) {
+                        if (!fy[(size_t)qy * fh + y]) continue;
+                        for (int qx = xlo[x]; qx < xhi[x]; qx++) {
+                            if (!fx[(size_t)qx * fw + x]) continue;
+                            t = RE::gather_term(t, g[qy * pooled_w + qx], wy[(size_t)qy * fh + y], wx[(size_t)qx * fw + x]);
+                            reached = true;
+                        }
+                    }
+                    if (reached) sum[(int64_t)(y0 + y) * lv.w + (x0 + x)] += t;
+                }
+        }
+    }
+    for (int l = 0; l < L.num; l++) {
+        float* grad = L.lv[l].grad;
+        const std::vector<float>& sum = sums[l];
+        for (size_t i = 0; i < sum.size(); i++) grad[i] = zero_first ? sum[i] : grad[i] + sum[i];
+    }
+    return SPH2POB_OK;
+}
+
 }  // extern "C"

@@ -202,6 +202,55 @@ SPHR_DEV void bin_backward(int w, const Prep& p, int ph, int pw, float g, AY&& a
     }
 }
 
+// ---- the gather form of the backward (sph2pob_roi_extract_bwd_det_f32_cpu in sph2pob_host.hip; no kernel computes it yet, the
+// functions below are host and device alike so that one can): the adjoint as a per-pixel gather.  The bilinear weights are
+// separable, so what roi r adds to pixel (y, x) of channel c is
+//     t_r = sum over ph, then pw, of g[c, ph, pw] (Wy_r[ph, y] Wx_r[pw, x]),   g = grad_out / count (rounded once)
+// with Wy_r[ph, y] the sum of the weights the samples iy = 0 .. gh - 1 of bin ph put on row y (each sample its lo term, then its hi
+// term), Wx_r likewise.  Only the bins with at least one term on BOTH axes are summed (a bin that does not reach the pixel adds
+// nothing, a non-finite grad_out there included), t_r starts at +0 and takes g (Wy Wx) left to right; the pixel's gradient starts at
+// +0 and takes t_r of the rois of its (image, level) in ascending row index.  Every order is fixed: the same bits on every call.
+// A pixel no roi reaches gets +0.0 (zero_first = 1) or keeps its value + 0.0.
+// The bound against the float64 evaluation on the same fp32 weights, per pixel, barring underflow, with n the number of (roi, ph, pw)
+// terms of the pixel and ty, tx the largest numbers of sample weights behind a Wy, Wx of those terms: a term carries one rounding of
+// g, at most ty - 1 additions in Wy and tx - 1 in Wx (all weights are >= 0, so the relative bounds hold), one product Wy Wx, one
+// product with g and at most n - 1 additions (the first term of a roi is added to +0, the first roi's t_r likewise: exact) —
+// k = n + ty + tx roundings, (1 + u)^k - 1 <= k u / (1 - k u) <= (k + 1) u for k <= 4095, u = 2^-24:
+//     |grad - f64| <= (n + max ty + max tx + 1) 2^-24 sum|terms|
+// (zero_first = 0 adds the finished sum to the buffer's value: one more rounding, of that sum.) ----
+
+// Wy[q, pix] of an axis of n pixels and its number of terms: the samples in ascending order, the lo term before the hi term
+SPHR_DEV float axis_weight(float start, float bin, int g, int q, int n, int pix, int& terms) {
+    float w = 0.0f;
+    int t = 0;
+    for (int i = 0; i < g; i++) {
+        const Axis a = axis_entry(start, bin, g, q, i, n);
+        if (a.lo < 0) continue;
+        if (a.lo == pix) { w += a.h; t++; }
+        if (a.hi == pix) { w += a.l; t++; }
+    }
+    terms = t;
+    return w;
+}
+
+// one step of t_r
+SPHR_DEV float gather_term(float t, float g, float wy, float wx) { return t + g * (wy * wx); }
+
+// A range of pixels [lo, hi] of an axis of n pixels that holds every pixel the samples of `bins` bins can touch — a superset: the
+// exact positions lie between start and start + bins bin, a sample's fp32 position is fewer than eight roundings of values up to
+// |start| + |end| away, and it touches floor(.) and the pixel above.  Pixels outside take no term.  Only a speed-up: axis_weight
+// decides what a pixel gets.  A NaN frame gives some range: no sample of it is valid
+SPHR_DEV void axis_reach(float start, float bin, int bins, int n, int& lo, int& hi) {
+    const float end = start + (float)bins * bin;
+    const float m = 1.0f + (fabsf(start) + fabsf(end)) * 4.76837158203125e-07f;   // 2^-21
+    float a = floorf((start < end ? start : end) - m), b = floorf((start < end ? end : start) + m) + 1.0f;
+    const float top = (float)(n - 1);
+    a = a > 0.0f ? (a < top ? a : top) : 0.0f;   // a NaN compares false: 0
+    b = b > 0.0f ? (b < top ? b : top) : 0.0f;
+    lo = (int)a;
+    hi = (int)b;
+}
+
 // Argument checks of both entries up to the pointers, in the documented order; fills the level table
 // (box_dim, the options, the sizes; an empty call — no rows, images or channels — is SPH2POB_OK with out->num = 0 whatever the
 // pointers are; then the pointers).  `table` is the level table the entry reads or writes: features forward, gradients backward
