@@ -2,11 +2,12 @@
 // level) exact top-k of the class scores above a threshold, read from the head's own layout; gather + decode of the selected
 // candidates; then the batched NMS stage of sph2pob_nms.hip.  Replaces SphRetinaHead._get_bboxes_single / _bbox_post_process
 // (sphdet/models/heads/sph_retina_head.py:101-216, :22-99) and filter_scores_and_topk (mmdet/core/utils/misc.py:119-165) for
-// B images with a number of launches that does not depend on B, and without a host read.  gfx950 only.  sph2pob_fcos_bboxes_f32 is
-// the same pipeline for SphFCOSHead (sph_fcos_head.py:246-323, :205-244): the selection on the class scores alone, then a cand_build
-// of its own that decodes from points and multiplies the class score by the point's centerness.  sph2pob_rcnn_bboxes_f32
-// (sph2pob_rcnn_bboxes.hip) is the pipeline once more, for the R-CNN stage: one flat level of the probabilities its stage 0 wrote,
-// and cand_build_rois_kernel, whose priors are the images' own rois and whose deltas are per class.
+// B images with a number of launches that does not depend on B, and without a host read.  gfx950 only.  Every head runs the same
+// pipeline() and the same cand_build_kernel; what differs is the candidate source the kernel is instantiated with, and the twin
+// (bboxes_cpu of sph2pob_host.hip) calls the same sources: DeltaSource (sph2pob_get_bboxes.hpp) for the delta coders,
+// PointSource (there) for SphFCOSHead (sph_fcos_head.py:246-323, :205-244: decode from points, class score times the point's
+// centerness) and RoiSource (sph2pob_rcnn_bboxes.hpp) for the R-CNN stage, sph2pob_rcnn_bboxes_f32 (sph2pob_rcnn_bboxes.hip: one
+// flat level of the probabilities its stage 0 wrote, the priors are the images' own rois and the deltas are per class).
 //
 // Selection, per (image, level), on the unique 64-bit keys (descending score bits << 32 | flat index):
 //   zero          the histograms and the per-(image, level) records
@@ -16,27 +17,24 @@
 //   topk_compact  stream 2: every key in those bins -> the level's survivor buffer, ballot + mbcnt compaction (the SET of
 //                 survivors is fixed by the histogram, their order in the buffer is not and is never used)
 //   topk_resolve  radix select among the survivors -> the exact nms_pre-th key; the keys up to it -> the level's selection
-//   cand_build    rank of every selected key among the level's selection (the final order), anchor and deltas gathered from the
-//                 head layout, decode_one(), box / score / label / prior index written at its place of the image's candidate block
+//   cand_build    rank of every selected key among the level's selection (the final order), then the head's candidate source:
+//                 box / score / label / prior index written at its place of the image's candidate block
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "../../include/sph2pob_hip.h"
-#include "sph2pob_coder.hpp"
-#include "sph2pob_get_bboxes.hpp"   // (declares the NMS stage, sph2pob_nms_batch_launch)
-#include "sph2pob_point_targets.hpp"   // (the point coder's decode_row)
-#include "sph2pob_rcnn_bboxes.hpp"     // (the rois of the R-CNN stage and their candidate_box)
+#include "sph2pob_get_bboxes.hpp"    // (the parameter blocks, DeltaSource and PointSource, the declaration of the NMS stage)
+#include "sph2pob_rcnn_bboxes.hpp"   // (RoiSource)
 
 namespace {
 
 using namespace sph2pob_gb;
-namespace C = sph2pob_coder;
-namespace PT = sph2pob_point;
 namespace RB = sph2pob_rcnn_bb;
 
 constexpr int kSelBlock = 256, kSelIters = 16, kChunk = kSelBlock * 4 * kSelIters;   // 16 384 scores per workgroup
+static_assert(kChunk == kChunkElems, "the level table counts its chunks in kChunkElems");
 constexpr int kResBlock = 1024, kRadixBits = 11, kRadix = 1 << kRadixBits;
 
 struct Meta { int cut, want, through, slots; };   // per (image, level); slots: the compaction's arrival counter
@@ -241,9 +239,8 @@ __global__ __launch_bounds__(kResBlock) void topk_resolve_kernel(Levels L, const
     }
 }
 
-// One lane per selected key: its rank among the level's selection (tiles of the selection in LDS).  The part of cand_build the coders
-// share: false for a lane (or a whole workgroup) without a key; else `mine` is the lane's key and `at` its row of the candidate block
-constexpr int kBuildBlock = 256;
+// One lane per selected key: its rank among the level's selection (tiles of the selection in LDS).  False for a lane (or a whole
+// workgroup) without a key; else `mine` is the lane's key and `at` its row of the candidate block
 __device__ __forceinline__ bool cand_place(const Levels& L, const Meta* __restrict__ meta, const unsigned long long* __restrict__ sel,
                                            int* __restrict__ counts, unsigned long long (&tile)[kBuildBlock], unsigned long long& mine, int64_t& at) {
     const int l = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
@@ -272,110 +269,31 @@ __device__ __forceinline__ bool cand_place(const Levels& L, const Meta* __restri
     return i < want;
 }
 
-// the delta coders: anchor and deltas gathered from the head layout, decode_one()
-template <int DIM, class T>
+// Launch 6, for every head: the source's prologue in the first workgroup of an image (nothing, except for RoiSource), the place of
+// the lane's key, key index -> (prior ai, class c), the source's guard, its box / score / prior index, the four stores
+template <class Source>
 __global__ __launch_bounds__(kBuildBlock) void cand_build_kernel(Levels L, const Meta* __restrict__ meta, const unsigned long long* __restrict__ sel,
-                                                               int num_classes, C::Norm nm, float max_ratio, int coder_flags, float ctr_clamp,
-                                                               float* __restrict__ boxes, float* __restrict__ scores, int64_t* __restrict__ labels,
-                                                               int* __restrict__ prior, int* __restrict__ counts) {
+                                                               int num_classes, Source source, float* __restrict__ boxes, float* __restrict__ scores,
+                                                               int64_t* __restrict__ labels, int* __restrict__ prior, int* __restrict__ counts,
+                                                               const int* __restrict__ hist) {
     __shared__ unsigned long long tile[kBuildBlock];
+    const int l = blockIdx.y, b = blockIdx.z;
+    if (blockIdx.x == 0 && l == 0) source.prologue(hist, b);   // workgroup-uniform
     unsigned long long mine;
     int64_t at;
     if (!cand_place(L, meta, sel, counts, tile, mine, at)) return;
-    const int l = blockIdx.y, b = blockIdx.z;
-    const Level& lv = L.lv[l];
     const unsigned flat = (unsigned)mine;
     const int ai = (int)(flat / (unsigned)num_classes), c = (int)(flat - (unsigned)ai * (unsigned)num_classes);
-    float p[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, d[5], box[5];
-#pragma unroll
-    for (int k = 0; k < DIM; k++) p[k] = lv.anchors[(int64_t)ai * DIM + k];
-    gather_deltas<DIM, T>(lv, b, ai, d);
-    C::decode_one<DIM, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr);
-#pragma unroll
-    for (int k = 0; k < DIM; k++) boxes[at * DIM + k] = box[k];
-    scores[at] = score_of_desc_bits((unsigned)(mine >> 32));
-    labels[at] = c;
-    prior[at] = lv.prior_off + ai;
-}
-
-// The point coder with a score factor (FCOS heads, sph2pob_fcos_bboxes_f32): Level::anchors holds the level's (n, 2) points, the
-// distances are gathered like deltas, the centerness like a one-channel score; the candidate's score is the class score the key
-// carries times activate(centerness), one fp32 multiply.  The centerness pointers come as a table of their own (the level table
-// keeps its size for the other kernels), read with the workgroup-uniform level index
-template <int DIM, class T>
-__global__ __launch_bounds__(kBuildBlock) void cand_build_points_kernel(Levels L, Factors F, const Meta* __restrict__ meta,
-                                                                      const unsigned long long* __restrict__ sel, int num_classes, int activation,
-                                                                      PT::Image im, float* __restrict__ boxes, float* __restrict__ scores,
-                                                                      int64_t* __restrict__ labels, int* __restrict__ prior, int* __restrict__ counts) {
-    __shared__ unsigned long long tile[kBuildBlock];
-    unsigned long long mine;
-    int64_t at;
-    if (!cand_place(L, meta, sel, counts, tile, mine, at)) return;
-    const int l = blockIdx.y, b = blockIdx.z;
     const Level& lv = L.lv[l];
-    const unsigned flat = (unsigned)mine;
-    const int ai = (int)(flat / (unsigned)num_classes), c = (int)(flat - (unsigned)ai * (unsigned)num_classes);
-    if (flat >= (unsigned)lv.count) return;   // a guard only: every selected key carries an index of its level
-    const float2 xy = reinterpret_cast<const float2*>(lv.anchors)[ai];
-    const float pt[2] = {xy.x, xy.y};
-    float d[5], box[5];
-    gather_deltas<DIM, T>(lv, b, ai, d);
-    const float factor = activate(gather_factor<T>(lv, F.p[l], b, ai), activation);
-    PT::decode_row<DIM, false>(pt, d, nullptr, im, box);
+    if (!source.has(lv, ai)) return;
+    float box[5];
+    int prior_index;
+    const float score = source(lv, l, b, ai, c, score_of_desc_bits((unsigned)(mine >> 32)), box, &prior_index);
 #pragma unroll
-    for (int k = 0; k < DIM; k++) boxes[at * DIM + k] = box[k];
-    scores[at] = factor_score(score_of_desc_bits((unsigned)(mine >> 32)), factor);
+    for (int k = 0; k < Source::kDim; k++) boxes[at * Source::kDim + k] = box[k];
+    scores[at] = score;
     labels[at] = c;
-    prior[at] = lv.prior_off + ai;
-}
-
-// The R-CNN stage (sph2pob_rcnn_bboxes_f32): one flat level whose priors are the images' own rois, (B, M, row_stride), with the
-// head's per-class deltas (B, M, C DIM) — or class-agnostic ones, or none.  Key index r C + c -> roi row r, class c; the roi is one
-// 16-byte load where the row's address allows it (row_stride is arbitrary, so that is decided per row), the deltas of class c
-// are gathered from the row's own C DIM, the box is RB::candidate_box's.  The first workgroup of an image also adds up the image's
-// selection histogram — every valid candidate was counted there exactly once, whatever the cut — into num_valid
-template <int DIM>
-__global__ __launch_bounds__(kBuildBlock) void cand_build_rois_kernel(Levels L, RB::Rois R, const Meta* __restrict__ meta,
-                                                                    const unsigned long long* __restrict__ sel, const int* __restrict__ hist,
-                                                                    int num_classes, C::Norm nm, float max_ratio, int coder_flags, float ctr_clamp,
-                                                                    float* __restrict__ boxes, float* __restrict__ scores,
-                                                                    int64_t* __restrict__ labels, int* __restrict__ prior, int* __restrict__ counts,
-                                                                    int64_t* __restrict__ num_valid) {
-    __shared__ unsigned long long tile[kBuildBlock];
-    __shared__ int valid_sum;
-    const int b = blockIdx.z;
-    if (blockIdx.x == 0) {   // workgroup-uniform
-        const int* g = hist + (int64_t)b * kBins;
-        int s = 0;
-        for (int i = threadIdx.x; i < kBins; i += kBuildBlock) s += g[i];
-        if (threadIdx.x == 0) valid_sum = 0;
-        __syncthreads();
-        if (s) atomicAdd(&valid_sum, s);
-        __syncthreads();
-        if (threadIdx.x == 0) num_valid[b] = valid_sum;
-    }
-    unsigned long long mine;
-    int64_t at;
-    if (!cand_place(L, meta, sel, counts, tile, mine, at)) return;
-    const unsigned flat = (unsigned)mine;
-    if (flat >= (unsigned)L.lv[0].count) return;   // a guard only: every selected key carries an index of the level
-    const int r = (int)(flat / (unsigned)num_classes), c = (int)(flat - (unsigned)r * (unsigned)num_classes);
-    const float* row = R.rois + ((int64_t)b * R.m + r) * R.row_stride;
-    float p[5], box[5];
-    if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
-        const float4 v = *reinterpret_cast<const float4*>(row);
-        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) p[k] = row[k];
-    }
-    if constexpr (DIM == 5) p[4] = row[4];
-    RB::candidate_box<DIM>(R, p, b, r, c, nm, max_ratio, coder_flags, ctr_clamp, box);
-#pragma unroll
-    for (int k = 0; k < DIM; k++) boxes[at * DIM + k] = box[k];
-    scores[at] = score_of_desc_bits((unsigned)(mine >> 32));
-    labels[at] = c;
-    prior[at] = r;
+    prior[at] = prior_index;
 }
 
 // workspace: histograms | meta (these two are zeroed by every call) | survivors | selection | candidate block | counts | NMS stage
@@ -396,105 +314,105 @@ Ws make_ws(void* workspace, const Levels& L, int64_t B, int box_dim) {
     w.labels = (int64_t*)(p + off); off += up(B * L.k_cap * 8);
     w.prior = (int*)(p + off); off += up(B * L.k_cap * 4);
     w.counts = (int*)(p + off); off += up(B * 4);
-    w.nms = (void*)(p + off); off += sph2pob_nms_batch_workspace_bytes(B, L.k_cap, box_dim);
+    w.nms = (void*)(p + off); off += nms_batch_workspace_bytes(B, L.k_cap, box_dim);
     w.bytes = off;
     return w;
 }
 
-// TS: the element type of cls_scores, TD: of bbox_preds (anchors and every output are fp32 / int64 whatever they are).  The public
-// entries read both as one type; the softmax entries select on fp32 probabilities and gather the head's own deltas
-// The ten launches on a checked level table: the selection on the class scores, `build(w, grid, s)` — the launch of the coder's
-// cand_build — and the NMS stage
-template <class TS, class Build>
-int pipeline(const Levels& L, int64_t num_images, int box_dim, int activation, float score_thr, int64_t nms_pre, int variant_flags,
-             int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets,
-             void* workspace, void* stream, Build&& build) {
-    if (!num_dets || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+// The ten launches on a checked level table: the selection on the class scores (TS: their element type), cand_build_kernel with the
+// head's candidate source, the NMS stage
+template <class TS, class Source>
+int pipeline(const Levels& L, const Shape& sh, const Selection& sel, const Nms& nms, const Outputs& out, void* workspace, void* stream,
+             const Source& source) {
+    if (!workspace) return SPH2POB_ERR_NULL;
+    if (int rc = out.check(nms.max_per_img)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int B = (int)num_images;
-    const Ws w = make_ws(workspace, L, B, box_dim);
-    const int pre = (int)(nms_pre < ((int64_t)1 << 30) ? nms_pre : ((int64_t)1 << 30));
+    const int B = (int)sh.num_images;
+    const Ws w = make_ws(workspace, L, B, sh.box_dim);
+    const int pre = (int)(sel.nms_pre < ((int64_t)1 << 30) ? sel.nms_pre : ((int64_t)1 << 30));
     if ((reinterpret_cast<uintptr_t>(w.hist) & 15) == 0) launch_zero<int4>(w.hist, w.zero_bytes, s);
     else launch_zero<int>(w.hist, w.zero_bytes, s);
-    hipLaunchKernelGGL(topk_hist_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.hist);
+    hipLaunchKernelGGL(topk_hist_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, sel.activation, sel.score_thr, w.hist);
     hipLaunchKernelGGL(topk_cut_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, pre, (const int*)w.hist, w.meta);
-    hipLaunchKernelGGL(topk_compact_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, activation, score_thr, w.meta, w.buf);
+    hipLaunchKernelGGL(topk_compact_kernel<TS>, dim3(L.chunks, B), dim3(kSelBlock), 0, s, L, sel.activation, sel.score_thr, w.meta, w.buf);
     hipLaunchKernelGGL(topk_resolve_kernel, dim3(L.num, B), dim3(kResBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.buf, w.sel);
     int max_cap = 0;
     for (int l = 0; l < L.num; l++) max_cap = L.lv[l].cap > max_cap ? L.lv[l].cap : max_cap;
-    build(w, dim3((max_cap + kBuildBlock - 1) / kBuildBlock, L.num, B), s);
+    hipLaunchKernelGGL(cand_build_kernel<Source>, dim3((max_cap + kBuildBlock - 1) / kBuildBlock, L.num, B), dim3(kBuildBlock), 0, s, L,
+                       (const Meta*)w.meta, (const unsigned long long*)w.sel, (int)sh.num_classes, source, w.boxes, w.scores, w.labels, w.prior,
+                       w.counts, (const int*)w.hist);
     if (int rc = launch_status()) return rc;
-    return sph2pob_nms_batch_launch(w.boxes, w.scores, w.labels, w.prior, w.counts, B, L.k_cap, box_dim, variant_flags, class_agnostic, iou_threshold,
-                                    max_per_img, w.nms, dets, labels, prior_inds, num_dets, s);
+    return nms_batch_launch(Candidates{w.boxes, w.scores, w.labels, w.prior, w.counts, L.k_cap}, B, sh.box_dim, nms, w.nms, out, s);
 }
 
-template <class TS, class TD = TS>
-int test_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
-                const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
-                float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
-                int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img,
-                float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
-    Levels L;
-    if (int rc = make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                             variant_flags, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, kChunk, &L))
-        return rc;
-    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
-    return pipeline<TS>(L, num_images, box_dim, activation, score_thr, nms_pre, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                        prior_inds, num_dets, workspace, stream, [&](const Ws& w, dim3 bgrid, hipStream_t s) {
-        if (box_dim == 4)
-            hipLaunchKernelGGL((cand_build_kernel<4, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                               (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
-        else
-            hipLaunchKernelGGL((cand_build_kernel<5, TD>), bgrid, dim3(kBuildBlock), 0, s, L, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                               (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior, w.counts);
+// the delta coders on a checked level table.  TS: the element type of the scores, TD: of the deltas (anchors and every output are
+// fp32 / int64 whatever they are)
+template <class TS, class TD>
+int delta_pipeline(const Levels& L, const Shape& sh, const Selection& sel, const Coder& cd, const Nms& nms, const Outputs& out, void* workspace,
+                   void* stream) {
+    return with_dim(sh.box_dim, [&](auto dim) {
+        return pipeline<TS>(L, sh, sel, nms, out, workspace, stream, DeltaSource<decltype(dim)::value, TD>{cd});
     });
 }
 
-// T: the element type of cls_scores, bbox_preds and centernesses (points and every output are fp32 / int64)
+// the entries on the head's own tensors.  The public ones read scores and deltas (and centernesses) as one type T
+struct Head { const void* const* cls_scores; const void* const* bbox_preds; const void* const* priors; };
 template <class T>
-int fcos_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points, const void* const* centernesses,
-                const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
-                float score_thr, int64_t nms_pre, int64_t img_h, int64_t img_w, float max_h, float max_w, int variant_flags, int class_agnostic,
-                float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace,
+int test_bboxes(const Head& h, const Shape& sh, const Selection& sel, const Coder& cd, const Nms& nms, const Outputs& out, void* workspace,
                 void* stream) {
     Levels L;
+    if (int rc = make_levels(h.cls_scores, h.bbox_preds, h.priors, sh, sel, cd, nms, &L)) return rc;
+    return delta_pipeline<T, T>(L, sh, sel, cd, nms, out, workspace, stream);
+}
+template <class T>
+int fcos_bboxes(const Head& h, const void* const* centernesses, const Shape& sh, const Selection& sel, const Frame& fr, const Nms& nms,
+                const Outputs& out, void* workspace, void* stream) {
+    Levels L;
     Factors F;
-    if (int rc = make_point_levels(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim,
-                                   activation, variant_flags, class_agnostic, nms_pre, max_per_img, img_h, img_w, max_h, max_w, kChunk, &L, &F))
-        return rc;
-    const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
-    return pipeline<T>(L, num_images, box_dim, activation, score_thr, nms_pre, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                       prior_inds, num_dets, workspace, stream, [&](const Ws& w, dim3 bgrid, hipStream_t s) {
-        if (box_dim == 4)
-            hipLaunchKernelGGL((cand_build_points_kernel<4, T>), bgrid, dim3(kBuildBlock), 0, s, L, F, (const Meta*)w.meta,
-                               (const unsigned long long*)w.sel, (int)num_classes, activation, im, w.boxes, w.scores, w.labels, w.prior, w.counts);
-        else
-            hipLaunchKernelGGL((cand_build_points_kernel<5, T>), bgrid, dim3(kBuildBlock), 0, s, L, F, (const Meta*)w.meta,
-                               (const unsigned long long*)w.sel, (int)num_classes, activation, im, w.boxes, w.scores, w.labels, w.prior, w.counts);
+    if (int rc = make_point_levels(h.cls_scores, h.bbox_preds, h.priors, centernesses, sh, sel, nms, fr, &L, &F)) return rc;
+    return with_dim(sh.box_dim, [&](auto dim) {
+        return pipeline<T>(L, sh, sel, nms, out, workspace, stream, PointSource<decltype(dim)::value, T>{F, fr.image(), sel.activation});
     });
 }
 
 }  // namespace
+
+namespace sph2pob_gb {
+int test_bboxes_on_probs(const Levels& L, const Shape& sh, const Selection& sel, const Coder& cd, const Nms& nms, const Outputs& out,
+                         void* workspace, int delta_dtype, void* stream) {
+    return with_f32_or_h16(delta_dtype, [&](auto t) { return delta_pipeline<float, decltype(t)>(L, sh, sel, cd, nms, out, workspace, stream); });
+}
+}  // namespace sph2pob_gb
+
+namespace sph2pob_rcnn_bb {
+int rois_bboxes_on_probs(const GB::Levels& L, const Rois& R, const GB::Shape& sh, const GB::Selection& sel, const GB::Coder& cd, const GB::Nms& nms,
+                         const GB::Outputs& out, int64_t* num_valid, void* workspace, void* stream) {
+    return with_dim(sh.box_dim, [&](auto dim) {
+        return pipeline<float>(L, sh, sel, nms, out, workspace, stream, RoiSource<decltype(dim)::value>{R, cd, num_valid});
+    });
+}
+}  // namespace sph2pob_rcnn_bb
 
 extern "C" {
 
 int64_t sph2pob_get_bboxes_workspace_bytes(const int64_t* level_n, int num_levels, int64_t num_images, int64_t num_classes, int box_dim,
                                            int64_t nms_pre) {
     Levels L;
-    if (make_level_shapes(level_n, nullptr, num_levels, num_images, num_classes, box_dim, 0, SPH2POB_VARIANT_EFFICIENT, 0, nms_pre, 0, 0.0f, 0,
-                          kChunk, true, &L))
+    if (make_level_shapes(Shape{level_n, nullptr, num_levels, num_images, num_classes, box_dim}, Selection{0, 0.0f, nms_pre}, Coder{},
+                          Nms{SPH2POB_VARIANT_EFFICIENT, 0, 0.0f, 0}, true, &L))
         return 0;
     return make_ws(nullptr, L, num_images, box_dim).bytes;
 }
 
+// The public entries fill the parameter blocks, here and nowhere below
 int sph2pob_test_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
                             const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, int activation,
                             float score_thr, int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio,
                             int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img,
                             float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
-    return test_bboxes<float>(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation, score_thr,
-                              nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags, class_agnostic, iou_threshold,
-                              max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+    return test_bboxes<float>(Head{cls_scores, bbox_preds, anchors}, Shape{level_n, level_hw, num_levels, num_images, num_classes, box_dim},
+                              Selection{activation, score_thr, nms_pre}, make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp),
+                              Nms{variant_flags, class_agnostic, iou_threshold, max_per_img}, Outputs{dets, labels, prior_inds, num_dets}, workspace, stream);
 }
 
 int sph2pob_test_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
@@ -503,53 +421,10 @@ int sph2pob_test_bboxes_h16(const void* const* cls_scores, const void* const* bb
                             int coder_flags, float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img,
                             float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream) {
     if (dtype != SPH2POB_DTYPE_F16 && dtype != SPH2POB_DTYPE_BF16) return SPH2POB_ERR_OPTION;
-    auto run = [&](auto t) {
-        return test_bboxes<decltype(t)>(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                                        score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags, class_agnostic,
-                                        iou_threshold, max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
-    };
-    return dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
-}
-
-// Stages 1-10 on fp32 probabilities with the deltas of the head's own type (delta_dtype 0: fp32, else SPH2POB_DTYPE_*): the pipeline
-// behind sph2pob_softmax_bboxes_f32 / _h16 (sph2pob_softmax_bboxes.hip), whose stage 0 wrote `probs`.  Inside the library only
-int sph2pob_test_bboxes_on_probs(const void* const* probs, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
-                                 const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
-                                 int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
-                                 float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
-                                 int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, int delta_dtype, void* stream) {
-    auto run = [&](auto t) {
-        return test_bboxes<float, decltype(t)>(probs, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0,
-                                               score_thr, nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags,
-                                               class_agnostic, iou_threshold, max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
-    };
-    return delta_dtype == 0 ? run(float{}) : delta_dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
-}
-
-// Stages 1-10 of sph2pob_rcnn_bboxes_f32 (sph2pob_rcnn_bboxes.hip, whose stage 0 wrote `probs` and which checked the arguments): the
-// selection on one flat level of M rows, cand_build_rois_kernel, the NMS stage.  Inside the library only
-int sph2pob_rois_bboxes_on_probs(const float* probs, const RB::Rois* rois, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
-                                 int64_t max_candidates, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
-                                 float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
-                                 int64_t* labels, int64_t* prior_inds, int64_t* num_dets, int64_t* num_valid, void* workspace, void* stream) {
-    Levels L;
-    const RB::Rois R = *rois;
-    if (int rc = RB::make_roi_level(num_images, R.m, R.row_stride, num_classes + 1, box_dim, 1 - R.per_class, variant_flags, class_agnostic,
-                                    max_candidates, max_per_img, max_ratio, coder_flags, &L))
-        return rc;
-    if (!probs || !num_valid) return SPH2POB_ERR_NULL;
-    L.lv[0].cls = probs;
-    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
-    return pipeline<float>(L, num_images, box_dim, 0, score_thr, max_candidates, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                           prior_inds, num_dets, workspace, stream, [&](const Ws& w, dim3 bgrid, hipStream_t s) {
-        if (box_dim == 4)
-            hipLaunchKernelGGL((cand_build_rois_kernel<4>), bgrid, dim3(kBuildBlock), 0, s, L, R, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                               (const int*)w.hist, (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior,
-                               w.counts, num_valid);
-        else
-            hipLaunchKernelGGL((cand_build_rois_kernel<5>), bgrid, dim3(kBuildBlock), 0, s, L, R, (const Meta*)w.meta, (const unsigned long long*)w.sel,
-                               (const int*)w.hist, (int)num_classes, nm, max_ratio, coder_flags, ctr_clamp, w.boxes, w.scores, w.labels, w.prior,
-                               w.counts, num_valid);
+    return with_h16(dtype, [&](auto t) {
+        return test_bboxes<decltype(t)>(Head{cls_scores, bbox_preds, anchors}, Shape{level_n, level_hw, num_levels, num_images, num_classes, box_dim},
+                                        Selection{activation, score_thr, nms_pre}, make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp),
+                                        Nms{variant_flags, class_agnostic, iou_threshold, max_per_img}, Outputs{dets, labels, prior_inds, num_dets}, workspace, stream);
     });
 }
 
@@ -583,9 +458,9 @@ int sph2pob_fcos_bboxes_f32(const void* const* cls_scores, const void* const* bb
                             int activation, float score_thr, int64_t nms_pre, int64_t img_h, int64_t img_w, float max_h, float max_w,
                             int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
                             int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
-    return fcos_bboxes<float>(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                              score_thr, nms_pre, img_h, img_w, max_h, max_w, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                              prior_inds, num_dets, workspace, stream);
+    return fcos_bboxes<float>(Head{cls_scores, bbox_preds, points}, centernesses, Shape{level_n, level_hw, num_levels, num_images, num_classes, box_dim},
+                              Selection{activation, score_thr, nms_pre}, Frame{img_h, img_w, max_h, max_w},
+                              Nms{variant_flags, class_agnostic, iou_threshold, max_per_img}, Outputs{dets, labels, prior_inds, num_dets}, workspace, stream);
 }
 
 int sph2pob_fcos_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points, const void* const* centernesses,
@@ -594,12 +469,11 @@ int sph2pob_fcos_bboxes_h16(const void* const* cls_scores, const void* const* bb
                             int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
                             int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream) {
     if (dtype != SPH2POB_DTYPE_F16 && dtype != SPH2POB_DTYPE_BF16) return SPH2POB_ERR_OPTION;
-    auto run = [&](auto t) {
-        return fcos_bboxes<decltype(t)>(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim,
-                                        activation, score_thr, nms_pre, img_h, img_w, max_h, max_w, variant_flags, class_agnostic, iou_threshold,
-                                        max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
-    };
-    return dtype == SPH2POB_DTYPE_F16 ? run(_Float16{}) : run(__bf16{});
+    return with_h16(dtype, [&](auto t) {
+        return fcos_bboxes<decltype(t)>(Head{cls_scores, bbox_preds, points}, centernesses, Shape{level_n, level_hw, num_levels, num_images, num_classes, box_dim},
+                                        Selection{activation, score_thr, nms_pre}, Frame{img_h, img_w, max_h, max_w},
+                                        Nms{variant_flags, class_agnostic, iou_threshold, max_per_img}, Outputs{dets, labels, prior_inds, num_dets}, workspace, stream);
+    });
 }
 
 }  // extern "C"

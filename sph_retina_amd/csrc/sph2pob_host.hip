@@ -533,32 +533,32 @@ SPH2POB_ANCHOR_TARGETS_TWIN(sph2pob_anchor_targets_any_f32_cpu, per_pair_only)
 
 // ---- detection post-processing for a minibatch: sph2pob_test_bboxes_f32 / sph2pob_get_bboxes_f32 (the same keys, in the same
 // order, sorted instead of selected; the NMS twin above on each image's candidates — one segment when class-agnostic; the
-// workspace is not used).  `candidate(lv, l, b, ai, class score, box)` is the coder's part of cand_build: it decodes the box of anchor
-// or point `ai` and returns the score the candidate goes on with ----
+// workspace is not used).  `source` is the head's candidate source, the one cand_build_kernel is instantiated with
+// (sph2pob_get_bboxes.hpp, sph2pob_rcnn_bboxes.hpp): it decodes the box of anchor, point or roi `ai` and returns the score the
+// candidate goes on with ----
 }  // extern "C"
 
+namespace GB = sph2pob_gb;
 namespace {
-// candidate(level, l, b, prior ai, class c, selected score, box) -> the score the candidate goes into the NMS with
-template <class Candidate>
-int bboxes_cpu(const sph2pob_gb::Levels& L, int64_t num_images, int64_t num_classes, int box_dim, int activation, float score_thr, int variant,
-               int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets,
-               Candidate&& candidate) {
-    namespace GB = sph2pob_gb;
-    if (!num_dets || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
-    const int dim = box_dim;
+
+template <class Source>
+int bboxes_cpu(const GB::Levels& L, const GB::Shape& sh, const GB::Selection& sel, const GB::Nms& nms, const GB::Outputs& out, const Source& source) {
+    if (int rc = out.check(nms.max_per_img)) return rc;
+    constexpr int dim = Source::kDim;
+    const int64_t max_per_img = nms.max_per_img;
     std::vector<unsigned long long> keys, order;
     std::vector<float> boxes, scores, sorted;
     std::vector<int64_t> cls, prior, cls_sorted;
     std::vector<unsigned char> keep;
-    for (int64_t b = 0; b < num_images; b++) {
+    for (int64_t b = 0; b < sh.num_images; b++) {
         boxes.clear(); scores.clear(); cls.clear(); prior.clear();
         for (int l = 0; l < L.num; l++) {
             const GB::Level& lv = L.lv[l];
             const float* base = lv.cls + b * (int64_t)lv.count;
             keys.clear();
             for (int m = 0; m < lv.count; m++) {
-                const float s = GB::activate(base[m], activation);
-                if (!(s > score_thr)) continue;
+                const float s = GB::activate(base[m], sel.activation);
+                if (!(s > sel.score_thr)) continue;
                 const int ch = m / lv.hw, p = m - ch * lv.hw;
                 keys.push_back(((unsigned long long)GB::desc_score_bits(s) << 32) | (unsigned)(p * lv.ac + ch));
             }
@@ -566,20 +566,21 @@ int bboxes_cpu(const sph2pob_gb::Levels& L, int64_t num_images, int64_t num_clas
             std::partial_sort(keys.begin(), keys.begin() + want, keys.end());
             for (size_t i = 0; i < want; i++) {
                 const unsigned flat = (unsigned)keys[i];
-                const int ai = (int)(flat / (unsigned)num_classes);
+                const int ai = (int)(flat / (unsigned)sh.num_classes), c = (int)(flat - (unsigned)ai * (unsigned)sh.num_classes);
+                if (!source.has(lv, ai)) continue;
                 float box[5];
-                const int c = (int)(flat - (unsigned)ai * (unsigned)num_classes);
-                const float score = candidate(lv, l, b, ai, c, GB::score_of_desc_bits((unsigned)(keys[i] >> 32)), box);
+                int prior_index;
+                const float score = source(lv, l, b, ai, c, GB::score_of_desc_bits((unsigned)(keys[i] >> 32)), box, &prior_index);
                 boxes.insert(boxes.end(), box, box + dim);
                 scores.push_back(score);
                 cls.push_back((int64_t)c);
-                prior.push_back(lv.prior_off + ai);
+                prior.push_back(prior_index);
             }
         }
         // the batched NMS on this image: (class | descending score | position) order, the sweeps, the kept by (score | position)
         const int64_t k = (int64_t)scores.size();
         order.resize(k);
-        for (int64_t j = 0; j < k; j++) order[j] = GB::nms_class_key(class_agnostic ? 0 : cls[j], scores[j], (int)j);
+        for (int64_t j = 0; j < k; j++) order[j] = GB::nms_class_key(nms.class_agnostic ? 0 : cls[j], scores[j], (int)j);
         std::sort(order.begin(), order.end());
         sorted.resize(k * dim); cls_sorted.resize(k); keep.assign(k, 0);
         for (int64_t r = 0; r < k; r++) {
@@ -588,7 +589,8 @@ int bboxes_cpu(const sph2pob_gb::Levels& L, int64_t num_images, int64_t num_clas
             cls_sorted[r] = cls[j];
         }
         if (k > 0)
-            if (int rc = sph2pob_nms_segmented_f32_cpu(sorted.data(), class_agnostic ? nullptr : cls_sorted.data(), k, box_dim, variant, iou_threshold, k, nullptr, keep.data(), nullptr))
+            if (int rc = sph2pob_nms_segmented_f32_cpu(sorted.data(), nms.class_agnostic ? nullptr : cls_sorted.data(), k, dim, nms.variant_flags,
+                                                       nms.iou_threshold, k, nullptr, keep.data(), nullptr))
                 return rc;
         keys.clear();
         for (int64_t r = 0; r < k; r++) {
@@ -597,17 +599,23 @@ int bboxes_cpu(const sph2pob_gb::Levels& L, int64_t num_images, int64_t num_clas
         }
         std::sort(keys.begin(), keys.end());
         const int64_t n = std::min<int64_t>((int64_t)keys.size(), max_per_img);
-        num_dets[b] = n;
+        out.num_dets[b] = n;
         for (int64_t r = 0; r < max_per_img; r++) {
             const int64_t e = b * max_per_img + r;
             const int64_t j = r < n ? (int64_t)(unsigned)keys[r] : -1;
-            for (int c = 0; c < dim; c++) dets[e * (dim + 1) + c] = j >= 0 ? boxes[j * dim + c] : 0.0f;
-            dets[e * (dim + 1) + dim] = j >= 0 ? scores[j] : 0.0f;
-            labels[e] = j >= 0 ? cls[j] : -1;
-            prior_inds[e] = j >= 0 ? prior[j] : -1;
+            for (int c = 0; c < dim; c++) out.dets[e * (dim + 1) + c] = j >= 0 ? boxes[j * dim + c] : 0.0f;
+            out.dets[e * (dim + 1) + dim] = j >= 0 ? scores[j] : 0.0f;
+            out.labels[e] = j >= 0 ? cls[j] : -1;
+            out.prior_inds[e] = j >= 0 ? prior[j] : -1;
         }
     }
     return SPH2POB_OK;
+}
+
+// the delta coders on a checked level table
+int delta_bboxes_cpu(const GB::Levels& L, const GB::Shape& sh, const GB::Selection& sel, const GB::Coder& cd, const GB::Nms& nms,
+                     const GB::Outputs& out) {
+    return GB::with_dim(sh.box_dim, [&](auto dim) { return bboxes_cpu(L, sh, sel, nms, out, GB::DeltaSource<decltype(dim)::value>{cd}); });
 }
 }  // namespace
 
@@ -619,21 +627,13 @@ int sph2pob_test_bboxes_f32_cpu(const void* const* cls_scores, const void* const
                                 int coder_flags, float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img,
                                 float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
     (void)workspace;
-    namespace GB = sph2pob_gb;
+    const GB::Shape sh{level_n, level_hw, num_levels, num_images, num_classes, box_dim};
+    const GB::Selection sel{activation, score_thr, nms_pre};
+    const GB::Coder cd = GB::make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp);
+    const GB::Nms nms{variant, class_agnostic, iou_threshold, max_per_img};
     GB::Levels L;
-    if (int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, activation,
-                                 variant, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &L))
-        return rc;
-    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
-    const int dim = box_dim;
-    return bboxes_cpu(L, num_images, num_classes, box_dim, activation, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                      prior_inds, num_dets, [&](const GB::Level& lv, int, int64_t b, int ai, int, float score, float* box) {
-        float p[5] = {0, 0, 0, 0, 0}, d[5];
-        for (int k = 0; k < dim; k++) p[k] = lv.anchors[(int64_t)ai * dim + k];
-        if (dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); sph2pob_coder::decode_one<4, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
-        else { GB::gather_deltas<5>(lv, b, ai, d); sph2pob_coder::decode_one<5, false>(p, d, nm, max_ratio, coder_flags, ctr_clamp, box, nullptr); }
-        return score;
-    });
+    if (int rc = GB::make_levels(cls_scores, bbox_preds, anchors, sh, sel, cd, nms, &L)) return rc;
+    return delta_bboxes_cpu(L, sh, sel, cd, nms, GB::Outputs{dets, labels, prior_inds, num_dets});
 }
 // FCOS heads: the point coder's decode_row, score = class score * activate(centerness), one fp32 multiply (the kernel's)
 int sph2pob_fcos_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* points,
@@ -642,21 +642,16 @@ int sph2pob_fcos_bboxes_f32_cpu(const void* const* cls_scores, const void* const
                                 int64_t img_h, int64_t img_w, float max_h, float max_w, int variant, int class_agnostic, float iou_threshold,
                                 int64_t max_per_img, float* dets, int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
     (void)workspace;
-    namespace GB = sph2pob_gb;
-    namespace PT = sph2pob_point;
+    const GB::Shape sh{level_n, level_hw, num_levels, num_images, num_classes, box_dim};
+    const GB::Selection sel{activation, score_thr, nms_pre};
+    const GB::Frame fr{img_h, img_w, max_h, max_w};
+    const GB::Nms nms{variant, class_agnostic, iou_threshold, max_per_img};
     GB::Levels L;
     GB::Factors F;
-    if (int rc = GB::make_point_levels(cls_scores, bbox_preds, points, centernesses, level_n, level_hw, num_levels, num_images, num_classes, box_dim,
-                                       activation, variant, class_agnostic, nms_pre, max_per_img, img_h, img_w, max_h, max_w, 1 << 14, &L, &F))
-        return rc;
-    const PT::Image im{(float)img_w, (float)img_h, max_w, max_h};
-    return bboxes_cpu(L, num_images, num_classes, box_dim, activation, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels,
-                      prior_inds, num_dets, [&](const GB::Level& lv, int l, int64_t b, int ai, int, float score, float* box) {
-        float d[5], out[5];
-        if (box_dim == 4) { GB::gather_deltas<4>(lv, b, ai, d); PT::decode_row<4, false>(lv.anchors + 2 * (int64_t)ai, d, nullptr, im, out); }
-        else { GB::gather_deltas<5>(lv, b, ai, d); PT::decode_row<5, false>(lv.anchors + 2 * (int64_t)ai, d, nullptr, im, out); }
-        for (int k = 0; k < box_dim; k++) box[k] = out[k];
-        return GB::factor_score(score, GB::activate(GB::gather_factor<float>(lv, F.p[l], b, ai), activation));
+    if (int rc = GB::make_point_levels(cls_scores, bbox_preds, points, centernesses, sh, sel, nms, fr, &L, &F)) return rc;
+    return GB::with_dim(box_dim, [&](auto dim) {
+        return bboxes_cpu(L, sh, sel, nms, GB::Outputs{dets, labels, prior_inds, num_dets},
+                          GB::PointSource<decltype(dim)::value>{F, fr.image(), activation});
     });
 }
 int sph2pob_get_bboxes_f32_cpu(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
@@ -1279,36 +1274,33 @@ int sph2pob_softmax_bboxes_f32_cpu(const void* const* cls_scores, const void* co
                                    const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
                                    int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
                                    float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
-                                   int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
-    namespace GB = sph2pob_gb;
+                                   int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void*) {
+    (void)workspace;
+    const GB::Shape sh{level_n, level_hw, num_levels, num_images, num_classes, box_dim};
+    const GB::Selection sel{0, score_thr, nms_pre};
+    const GB::Coder cd = GB::make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp);
+    const GB::Nms nms{variant, class_agnostic, iou_threshold, max_per_img};
+    const GB::Outputs outs{dets, labels, prior_inds, num_dets};
     GB::Levels G;
-    const int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0, variant,
-                                   class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &G);
-    if (rc == SPH2POB_ERR_DIM || rc == SPH2POB_ERR_OPTION) return rc;
-    if (num_classes > SM::kMaxK - 1) return SPH2POB_ERR_SIZE;
-    if (rc) return rc;
-    if (!num_dets || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    if (int rc = SM::make_softmax_levels(cls_scores, bbox_preds, anchors, sh, sel, cd, nms, outs, &G)) return rc;
     SM::ProbLevels L;
     std::vector<std::vector<float>> probs(num_levels);
-    const void* in[GB::kMaxLevels];
     void* out[GB::kMaxLevels];
     for (int l = 0; l < num_levels; l++) out[l] = const_cast<void*>(cls_scores[l]);   // (shapes first: nothing is sized before the checks)
-    if (int rc2 = SM::make_prob_levels(cls_scores, out, level_n, level_hw, num_levels, num_images, num_classes, 4, &L)) return rc2;
+    if (int rc = SM::make_prob_levels(cls_scores, out, level_n, level_hw, num_levels, num_images, num_classes, 4, &L)) return rc;
     for (int l = 0; l < num_levels; l++) {
         probs[l].resize((size_t)(num_images * level_n[l] * num_classes));
-        in[l] = L.lv[l].out = probs[l].data();
+        G.lv[l].cls = L.lv[l].out = probs[l].data();   // the selection runs on the probabilities
     }
     softmax_prob_rows(L, level_n, num_images, (int)num_classes + 1);
-    return sph2pob_test_bboxes_f32_cpu(in, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0, score_thr,
-                                       nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant, class_agnostic, iou_threshold,
-                                       max_per_img, dets, labels, prior_inds, num_dets, workspace, stream);
+    return delta_bboxes_cpu(G, sh, sel, cd, nms, outs);
 }
 
 }  // extern "C"
 
 // ---- inference of the R-CNN stage: the twin of sph2pob_rcnn_bboxes.hip — Prob on the rows in front of every image's count (-inf
 // behind it, nothing of those rows is read), the count of the valid candidates, then the twin of the pipeline on one flat level with
-// candidate_box of sph2pob_rcnn_bboxes.hpp (the workspace is not used) ----
+// RoiSource of sph2pob_rcnn_bboxes.hpp (the workspace is not used) ----
 extern "C" {
 
 int sph2pob_rcnn_bboxes_f32_cpu(const float* rois, const int64_t* num_rois, const float* cls_score, const float* bbox_pred, int64_t num_images,
@@ -1317,13 +1309,15 @@ int sph2pob_rcnn_bboxes_f32_cpu(const float* rois, const int64_t* num_rois, cons
                                 float ctr_clamp, int variant, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
                                 int64_t* labels, int64_t* prior_inds, int64_t* num_dets, int64_t* num_valid, void* workspace, void*) {
     (void)workspace;
-    namespace GB = sph2pob_gb;
     namespace RB = sph2pob_rcnn_bb;
+    const GB::Shape sh{&m, nullptr, 1, num_images, num_logits - 1, box_dim};
+    const GB::Selection sel{0, score_thr, max_candidates};
+    const GB::Coder cd = GB::make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp);
+    const GB::Nms nms{variant, class_agnostic, iou_threshold, max_per_img};
+    const GB::Outputs out{dets, labels, prior_inds, num_dets};
     GB::Levels L;
-    if (int rc = RB::make_roi_level(num_images, m, row_stride, num_logits, box_dim, reg_class_agnostic, variant, class_agnostic, max_candidates,
-                                    max_per_img, max_ratio, coder_flags, &L))
-        return rc;
-    if (!rois || !cls_score || !num_dets || !num_valid || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    if (int rc = RB::make_roi_level(sh, row_stride, reg_class_agnostic, sel, cd, nms, &L)) return rc;
+    if (!rois || !cls_score || !num_valid || out.check(max_per_img)) return SPH2POB_ERR_NULL;
     const int K = (int)num_logits, C = K - 1;
     std::vector<float> probs((size_t)(num_images * m * C));
     parallel_for(num_images * m, 1 << 10, [&](int64_t lo, int64_t hi) {
@@ -1350,14 +1344,7 @@ int sph2pob_rcnn_bboxes_f32_cpu(const float* rois, const int64_t* num_rois, cons
     }
     L.lv[0].cls = probs.data();
     const RB::Rois R = RB::make_rois(rois, num_rois, bbox_pred, m, row_stride, C, box_dim, reg_class_agnostic);
-    const sph2pob_coder::Norm nm = sph2pob_coder::make_norm(means_host, stds_host, box_dim);
-    return bboxes_cpu(L, num_images, C, box_dim, 0, score_thr, variant, class_agnostic, iou_threshold, max_per_img, dets, labels, prior_inds, num_dets,
-                      [&](const GB::Level&, int, int64_t b, int r, int c, float score, float* box) {
-        const float* row = rois + (b * m + r) * row_stride;
-        if (box_dim == 4) RB::candidate_box<4>(R, row, b, r, c, nm, max_ratio, coder_flags, ctr_clamp, box);
-        else RB::candidate_box<5>(R, row, b, r, c, nm, max_ratio, coder_flags, ctr_clamp, box);
-        return score;
-    });
+    return GB::with_dim(box_dim, [&](auto dim) { return bboxes_cpu(L, sh, sel, nms, out, RB::RoiSource<decltype(dim)::value>{R, cd, nullptr}); });
 }
 
 }  // extern "C"

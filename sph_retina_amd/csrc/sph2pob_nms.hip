@@ -747,42 +747,47 @@ int sph2pob_batched_nms_f32(const float* boxes, const float* scores, const int64
     return launch_status();
 }
 
+}  // extern "C"
+
 // The NMS stage of sph2pob_test_bboxes_f32 (sph2pob_get_bboxes.hip; declared in sph2pob_get_bboxes.hpp): the four kernels above with
 // the image as grid dimension y.  Candidate blocks have the fixed stride k_cap, every kernel reads its image's live count from
 // `counts`.  The caller has checked the variant; the kernels are what sph2pob_batched_nms_f32 launches for one image.
 // class_agnostic: the sort is by score alone and mask and sweep see one segment per image (no class array), as
-// sph2pob_batched_nms_f32 with idxs == NULL; labels_out are still the candidates' own.
-int64_t sph2pob_nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim) { return nms_ws(nullptr, num_images, k_cap, box_dim).bytes; }
-int sph2pob_nms_batch_launch(const float* boxes, const float* scores, const int64_t* labels, const int* prior, const int* counts,
-                             int64_t num_images, int k_cap, int box_dim, int variant_flags, int class_agnostic, float iou_threshold,
-                             int64_t max_per_img, void* nms_workspace, float* dets, int64_t* labels_out, int64_t* prior_out, int64_t* num_dets,
-                             void* stream) {
+// sph2pob_batched_nms_f32 with idxs == NULL; the labels written out are still the candidates' own.
+namespace sph2pob_gb {
+int64_t nms_batch_workspace_bytes(int64_t num_images, int k_cap, int box_dim) { return nms_ws(nullptr, num_images, k_cap, box_dim).bytes; }
+int nms_batch_launch(const Candidates& cand, int64_t num_images, int box_dim, const Nms& nms, void* nms_workspace, const Outputs& out,
+                     void* stream) {
     hipStream_t s = (hipStream_t)stream;
+    const int k_cap = cand.k_cap;
     const int64_t k = k_cap;
     const unsigned B = (unsigned)num_images;
     const NmsWs w = nms_ws(nms_workspace, num_images, k, box_dim);
-    const int rows = (int)max_per_img;
-    const int64_t* sort_cls = class_agnostic ? nullptr : labels;   // what the order is built on
-    const int64_t* seg_cls = class_agnostic ? nullptr : w.cls;     // the segments of the sorted order
+    const int rows = (int)nms.max_per_img;
+    const int64_t* sort_cls = nms.class_agnostic ? nullptr : cand.labels;   // what the order is built on
+    const int64_t* seg_cls = nms.class_agnostic ? nullptr : w.cls;          // the segments of the sorted order
     by_sort_size(k, box_dim, [&](auto size) {
         using Z = decltype(size);
-        hipLaunchKernelGGL((nms_prepare_batch_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k, B), dim3(Z::BS), 0, s, boxes, scores, sort_cls, counts,
-                           k_cap, w.boxes, w.cls, w.order, w.skey, w.status);
+        hipLaunchKernelGGL((nms_prepare_batch_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k, B), dim3(Z::BS), 0, s, cand.boxes, cand.scores, sort_cls,
+                           cand.counts, k_cap, w.boxes, w.cls, w.order, w.skey, w.status);
     });
     if (int rc = launch_status()) return rc;
-    if (int rc = dispatch(variant_flags, box_dim,
-                          MaskBatchLaunch{w.boxes, seg_cls, counts, k_cap, B, iou_threshold, w.mask, w.mask_stride, nms_edge(variant_flags), s}))
+    if (int rc = dispatch(nms.variant_flags, box_dim, MaskBatchLaunch{w.boxes, seg_cls, cand.counts, k_cap, B, nms.iou_threshold, w.mask,
+                                                                      w.mask_stride, nms_edge(nms.variant_flags), s}))
         return rc;
     hipLaunchKernelGGL(nms_sweep_batch_kernel, dim3((unsigned)((k + kSweepCands - 1) / kSweepCands), B), dim3(kSweepBlock), 0, s, w.mask,
-                       w.mask_stride, seg_cls, counts, k_cap, w.keep);
+                       w.mask_stride, seg_cls, cand.counts, k_cap, w.keep);
     if (int rc = launch_status()) return rc;
     by_sort_size(k, box_dim, [&](auto size) {
         using Z = decltype(size);
-        hipLaunchKernelGGL((nms_select_batch_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k, B), dim3(Z::BS), 0, s, w.boxes, w.keep, w.skey, counts,
-                           k_cap, rows, labels, prior, dets, labels_out, prior_out, num_dets);
+        hipLaunchKernelGGL((nms_select_batch_kernel<Z::T, Z::D, Z::IPW, Z::BS>), Z::grid(k, B), dim3(Z::BS), 0, s, w.boxes, w.keep, w.skey,
+                           cand.counts, k_cap, rows, cand.labels, cand.prior, out.dets, out.labels, out.prior_inds, out.num_dets);
     });
     return launch_status();
 }
+}  // namespace sph2pob_gb
+
+extern "C" {
 
 int sph2pob_nms_f32(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim, int variant_flags,
                     float iou_threshold, void* workspace, unsigned char* keep, void* stream) {

@@ -6,9 +6,9 @@
 //
 // Here: the argument checks, the workspace and stage 0, the probabilities of the rows in front of every image's count (Prob of
 // sph2pob_softmax.hpp, the bits of sph2pob_softmax_scores_f32 on the flat layout) as a (B, M, C) block of the workspace, -inf behind
-// the count.  Stages 1-10 are pipeline() of sph2pob_get_bboxes.hip on that block as one flat level of M rows, with
-// cand_build_rois_kernel (there, next to its siblings: it shares their cand_place) as the `build`: only the SELECTED candidates are
-// decoded — at most max_candidates of the M C per image, where the reference decodes all of them.
+// the count.  Stages 1-10 are pipeline() of sph2pob_get_bboxes.hip on that block as one flat level of M rows, with RoiSource
+// (sph2pob_rcnn_bboxes.hpp) as the candidate source of cand_build_kernel: only the SELECTED candidates are decoded — at most
+// max_candidates of the M C per image, where the reference decodes all of them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -93,11 +93,14 @@ int sph2pob_rcnn_bboxes_f32(const float* rois, const int64_t* num_rois, const fl
                             int64_t max_candidates, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
                             float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
                             int64_t* labels, int64_t* prior_inds, int64_t* num_dets, int64_t* num_valid, void* workspace, void* stream) {
+    const GB::Shape sh{&m, nullptr, 1, num_images, num_logits - 1, box_dim};
+    const GB::Selection sel{0, score_thr, max_candidates};
+    const GB::Coder cd = GB::make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp);
+    const GB::Nms nms{variant_flags, class_agnostic, iou_threshold, max_per_img};
+    const GB::Outputs out{dets, labels, prior_inds, num_dets};
     GB::Levels L;
-    if (int rc = make_roi_level(num_images, m, row_stride, num_logits, box_dim, reg_class_agnostic, variant_flags, class_agnostic, max_candidates,
-                                max_per_img, max_ratio, coder_flags, &L))
-        return rc;
-    if (!rois || !cls_score || !num_dets || !num_valid || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
+    if (int rc = make_roi_level(sh, row_stride, reg_class_agnostic, sel, cd, nms, &L)) return rc;
+    if (!rois || !cls_score || !num_valid || !workspace || out.check(max_per_img)) return SPH2POB_ERR_NULL;
     const int64_t C = num_logits - 1;
     const int64_t base = base_bytes(num_images, m, C, box_dim, max_candidates);
     // the probabilities follow the pipeline's workspace, 256-byte aligned: an image's block is as aligned as it would be in a tensor
@@ -111,10 +114,9 @@ int sph2pob_rcnn_bboxes_f32(const float* rois, const int64_t* num_rois, const fl
     else
         hipLaunchKernelGGL((rcnn_prob_kernel<false>), grid, block, 0, s, cls_score, num_rois, (int)m, K, probs);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-    const Rois R = make_rois(rois, num_rois, bbox_pred, m, row_stride, C, box_dim, reg_class_agnostic);
-    return sph2pob_rois_bboxes_on_probs(probs, &R, num_images, C, box_dim, score_thr, max_candidates, means_host, stds_host, max_ratio, coder_flags,
-                                        ctr_clamp, variant_flags, class_agnostic, iou_threshold, max_per_img, dets, labels, prior_inds, num_dets,
-                                        num_valid, workspace, stream);
+    L.lv[0].cls = probs;
+    return rois_bboxes_on_probs(L, make_rois(rois, num_rois, bbox_pred, m, row_stride, C, box_dim, reg_class_agnostic), sh, sel, cd, nms, out,
+                                num_valid, workspace, stream);
 }
 
 }  // extern "C"

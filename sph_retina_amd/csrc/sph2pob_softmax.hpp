@@ -11,6 +11,7 @@
 
 #include "../../include/sph2pob_hip.h"
 #include "sph2pob_class_levels.hpp"
+#include "sph2pob_get_bboxes.hpp"
 #include "sph2pob_head_loss.hpp"
 #include "sph2pob_select.hpp"
 
@@ -222,6 +223,18 @@ inline int make_prob_levels(const void* const* logits, void* const* out, const i
     L.blocks = (int)blocks;   // (every level holds fewer than 2^31 elements: fewer than 2^26 workgroups in all)
     *res = L;
     return SPH2POB_OK;
+}
+// Argument checks of sph2pob_softmax_bboxes_f32 / _h16 and the twin, in the documented order: box_dim and the options as
+// sph2pob_test_bboxes_f32 has them, K = C + 1 <= kMaxK with the sizes (C >= 1 is the pipeline's own check), the rest of that entry's
+// checks, then the output pointers.  Fills the level table of the pipeline, its scores still the head's logits
+inline int make_softmax_levels(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const sph2pob_gb::Shape& sh,
+                               const sph2pob_gb::Selection& sel, const sph2pob_gb::Coder& cd, const sph2pob_gb::Nms& nms,
+                               const sph2pob_gb::Outputs& out, sph2pob_gb::Levels* res) {
+    const int rc = sph2pob_gb::make_levels(cls_scores, bbox_preds, anchors, sh, sel, cd, nms, res);
+    if (rc == SPH2POB_ERR_DIM || rc == SPH2POB_ERR_OPTION) return rc;
+    if (sh.num_classes > kMaxK - 1) return SPH2POB_ERR_SIZE;
+    if (rc) return rc;
+    return out.check(nms.max_per_img);
 }
 // the first logit of an NCHW item and of the probabilities it writes: position p of anchor (b, a) — class j lies j * hw further on
 SPHF_DEV void prob_nchw_span(int64_t ba, int64_t p, int hw, int K, int64_t* in, int64_t* out) {

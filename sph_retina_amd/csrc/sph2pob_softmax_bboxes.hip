@@ -175,7 +175,7 @@ int prob_launch(const ProbLevels& L, int K, hipStream_t s) {
 }
 // dtype 0: fp32 logits, else SPH2POB_DTYPE_*
 int prob_launch_dtype(const ProbLevels& L, int K, int dtype, hipStream_t s) {
-    return dtype == 0 ? prob_launch<float>(L, K, s) : dtype == SPH2POB_DTYPE_F16 ? prob_launch<_Float16>(L, K, s) : prob_launch<__bf16>(L, K, s);
+    return GB::with_f32_or_h16(dtype, [&](auto t) { return prob_launch<decltype(t)>(L, K, s); });
 }
 
 int softmax_scores(const void* const* logits, const int64_t* level_n, const int64_t* level_hw, int num_levels, int64_t num_images,
@@ -189,33 +189,25 @@ int softmax_scores(const void* const* logits, const int64_t* level_n, const int6
 // image's block is as aligned as it would be in a tensor of its own, so the streaming stages keep their 16-byte loads
 int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
 
-int softmax_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
-                   const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
-                   int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp,
-                   int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets, int64_t* labels,
-                   int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream) {
+int softmax_bboxes(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const GB::Shape& sh,
+                   const GB::Selection& sel, const GB::Coder& cd, const GB::Nms& nms, const GB::Outputs& out, void* workspace, int dtype,
+                   void* stream) {
     GB::Levels G;
-    // (1 << 14: the streaming chunk of sph2pob_get_bboxes.hip, which runs these checks again on the probabilities)
-    const int rc = GB::make_levels(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, 0,
-                                   variant_flags, class_agnostic, nms_pre, max_per_img, max_ratio, coder_flags, 1 << 14, &G);
-    if (rc == SPH2POB_ERR_DIM || rc == SPH2POB_ERR_OPTION) return rc;
-    if (num_classes > kMaxK - 1) return SPH2POB_ERR_SIZE;   // with the sizes: K = C + 1 in [2, 4096] (C >= 1 is the pipeline's own check)
-    if (rc) return rc;
-    if (!num_dets || !workspace || (max_per_img > 0 && (!dets || !labels || !prior_inds))) return SPH2POB_ERR_NULL;
-    const int64_t base = sph2pob_get_bboxes_workspace_bytes(level_n, num_levels, num_images, num_classes, box_dim, nms_pre);
+    if (int rc = make_softmax_levels(cls_scores, bbox_preds, anchors, sh, sel, cd, nms, out, &G)) return rc;
+    if (!workspace) return SPH2POB_ERR_NULL;
+    const int64_t base = sph2pob_get_bboxes_workspace_bytes(sh.level_n, sh.num_levels, sh.num_images, sh.num_classes, sh.box_dim, sel.nms_pre);
     char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + (uintptr_t)base + 255) & ~(uintptr_t)255);
-    const void* probs[GB::kMaxLevels];
     void* outs[GB::kMaxLevels];
-    for (int l = 0; l < num_levels; l++) {
-        probs[l] = outs[l] = p;
-        p += up256(num_images * level_n[l] * num_classes * 4);
+    for (int l = 0; l < sh.num_levels; l++) {
+        outs[l] = p;
+        p += up256(sh.num_images * sh.level_n[l] * sh.num_classes * 4);
     }
     ProbLevels L;
-    if (int rc2 = make_prob_levels(cls_scores, outs, level_n, level_hw, num_levels, num_images, num_classes, dtype ? 2 : 4, &L)) return rc2;
-    if (int rc2 = prob_launch_dtype(L, (int)num_classes + 1, dtype, (hipStream_t)stream)) return rc2;
-    return sph2pob_test_bboxes_on_probs(probs, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, score_thr,
-                                        nms_pre, means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags, class_agnostic,
-                                        iou_threshold, max_per_img, dets, labels, prior_inds, num_dets, workspace, dtype, stream);
+    if (int rc = make_prob_levels(cls_scores, outs, sh.level_n, sh.level_hw, sh.num_levels, sh.num_images, sh.num_classes, dtype ? 2 : 4, &L))
+        return rc;
+    if (int rc = prob_launch_dtype(L, (int)sh.num_classes + 1, dtype, (hipStream_t)stream)) return rc;
+    for (int l = 0; l < sh.num_levels; l++) G.lv[l].cls = (const float*)outs[l];   // the selection runs on the probabilities
+    return GB::test_bboxes_on_probs(G, sh, sel, cd, nms, out, workspace, dtype, stream);
 }
 
 bool h16(int dtype) { return dtype == SPH2POB_DTYPE_F16 || dtype == SPH2POB_DTYPE_BF16; }
@@ -244,14 +236,16 @@ int64_t sph2pob_softmax_bboxes_workspace_bytes(const int64_t* level_n, int num_l
     return bytes;
 }
 
+// the two entries fill the parameter blocks (activation 0: the selection is on probabilities)
 int sph2pob_softmax_bboxes_f32(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
                                const int64_t* level_hw, int num_levels, int64_t num_images, int64_t num_classes, int box_dim, float score_thr,
                                int64_t nms_pre, const float* means_host, const float* stds_host, float max_ratio, int coder_flags,
                                float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
                                int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, void* stream) {
-    return softmax_bboxes(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, score_thr, nms_pre,
-                          means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags, class_agnostic, iou_threshold, max_per_img,
-                          dets, labels, prior_inds, num_dets, workspace, 0, stream);
+    return softmax_bboxes(cls_scores, bbox_preds, anchors, GB::Shape{level_n, level_hw, num_levels, num_images, num_classes, box_dim},
+                          GB::Selection{0, score_thr, nms_pre}, GB::make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp),
+                          GB::Nms{variant_flags, class_agnostic, iou_threshold, max_per_img}, GB::Outputs{dets, labels, prior_inds, num_dets}, workspace, 0,
+                          stream);
 }
 
 int sph2pob_softmax_bboxes_h16(const void* const* cls_scores, const void* const* bbox_preds, const void* const* anchors, const int64_t* level_n,
@@ -260,9 +254,10 @@ int sph2pob_softmax_bboxes_h16(const void* const* cls_scores, const void* const*
                                float ctr_clamp, int variant_flags, int class_agnostic, float iou_threshold, int64_t max_per_img, float* dets,
                                int64_t* labels, int64_t* prior_inds, int64_t* num_dets, void* workspace, int dtype, void* stream) {
     if (!h16(dtype)) return SPH2POB_ERR_OPTION;
-    return softmax_bboxes(cls_scores, bbox_preds, anchors, level_n, level_hw, num_levels, num_images, num_classes, box_dim, score_thr, nms_pre,
-                          means_host, stds_host, max_ratio, coder_flags, ctr_clamp, variant_flags, class_agnostic, iou_threshold, max_per_img,
-                          dets, labels, prior_inds, num_dets, workspace, dtype, stream);
+    return softmax_bboxes(cls_scores, bbox_preds, anchors, GB::Shape{level_n, level_hw, num_levels, num_images, num_classes, box_dim},
+                          GB::Selection{0, score_thr, nms_pre}, GB::make_coder(means_host, stds_host, box_dim, max_ratio, coder_flags, ctr_clamp),
+                          GB::Nms{variant_flags, class_agnostic, iou_threshold, max_per_img}, GB::Outputs{dets, labels, prior_inds, num_dets}, workspace,
+                          dtype, stream);
 }
 
 }  // extern "C"

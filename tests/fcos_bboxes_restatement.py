@@ -24,17 +24,17 @@ FIELDS = ('dets', 'labels', 'prior_inds', 'num_dets')
 
 
 def small_scene(dim=4, layout='nchw', device='cpu', seed=0, images=IMAGES, zero_image=ZERO_IMAGE, shapes=SHAPES, strides=STRIDES,
-                per_position=1, live=(0.08, 0.04)):
+                per_position=1, live=(0.08, 0.04), num_classes=C):
     """-> (class probabilities, distances, centerness probabilities, points), in the NCHW or the flat layout.
 
     Class probabilities: a fraction `live[l]` of a level's scores is uniform in (0.0501, 0.0701), the rest below 0.04; image
     `zero_image` has every score below the threshold.  So level 0 has ~330 valid scores (> nms_pre = 100) and level 1 ~40, and
     a selected score times a centerness uniform in (0, 1) falls below the threshold five times in six: of an image's ~140
     candidates some 25 have a product above it, fewer than max_per_img = 60, so detections below the threshold are kept whatever
-    the NMS removes.  Distances uniform in [1, 80) pixels — the points come from `sph_fcos_points` on strides 8 and 16, so corners near the border leave the image —
+    the NMS removes.  `num_classes`: C of the scene.  Distances uniform in [1, 80) pixels — the points come from `sph_fcos_points` on strides 8 and 16, so corners near the border leave the image —
     and an angle in [-60, 60) when dim = 5.  `per_position` > 1 repeats every point A times (ai = p A + a)."""
     g = torch.Generator().manual_seed(seed)
-    a = per_position
+    a, C = per_position, num_classes
     points = [p.repeat_interleave(a, 0).contiguous().to(device) for p in S.sph_fcos_points(shapes, strides)]
     cls, box, ctr = [], [], []
     for (h, w), frac in zip(shapes, live):

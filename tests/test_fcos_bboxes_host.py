@@ -24,19 +24,27 @@ def same(x, y):
     return all(torch.equal(getattr(x, f), getattr(y, f)) for f in FIELDS)
 
 
-def check_exact(device, dim, layout, variant, max_shape):
-    """The small scene against the composition, and the scene does its job: in every non-empty image a kept detection has a
-    product below score_thr, two kept detections stand in the opposite order of their class scores, and level 0 contributed
-    exactly nms_pre candidates while level 1 stayed below it."""
-    cls, box, ctr, points = small_scene(dim, layout, device)
-    coder, cfg = coder_for(dim), cfg_with(CFGS[variant], **SMALL)
+# One flat level of 10 x 30 = 300 points, C = 3, B = 2 under a per-level cap of 257: image 0 has ~540 valid scores, so its selection
+# fills a second 256-key tile of cand_build's rank loop and a second workgroup of the level, while image 1 selects nothing
+SECOND_TILE = dict(images=2, zero_image=1, shapes=((10, 30),), strides=(8,), live=(0.6,), num_classes=3)
+
+
+def check_exact(device, dim, layout, variant, max_shape, scene=None):
+    """The small scene (or the `scene` of small_scene arguments, under a per-level cap of 257) against the composition, and the
+    scene does its job: in every non-empty image a kept detection has a product below score_thr, two kept detections stand in
+    the opposite order of their class scores, and level 0 contributed exactly nms_pre candidates while level 1 stayed below it."""
+    cls, box, ctr, points = small_scene(dim, layout, device, **(scene or {}))
+    small = dict(SMALL, nms_pre=257) if scene else SMALL
+    images, zero = (scene['images'], scene['zero_image']) if scene else (IMAGES, ZERO_IMAGE)
+    coder, cfg = coder_for(dim), cfg_with(CFGS[variant], **small)
     r = S.sph_fcos_bboxes(cls, box, ctr, points, bbox_coder=coder, test_cfg=cfg, box_version=dim, activation='none', max_shape=max_shape)
     counts, levels, kept_cls = check_batch(r, cls, box, ctr, points, coder, cfg, dim, max_shape=max_shape)
-    assert counts[ZERO_IMAGE] == 0 and levels[ZERO_IMAGE] == [0, 0]
-    for b in (b for b in range(IMAGES) if b != ZERO_IMAGE):
+    assert counts[zero] == 0 and levels[zero] == [0] * len(points)
+    for b in (b for b in range(images) if b != zero):
         k = counts[b]
         product, cls_score = r.dets[b, :k, dim].cpu(), kept_cls[b].cpu()
-        assert 0 < k <= SMALL['max_per_img'] and levels[b][0] == SMALL['nms_pre'] and 0 < levels[b][1] < SMALL['nms_pre'], (counts, levels)
+        assert 0 < k <= small['max_per_img'] and levels[b][0] == small['nms_pre'], (counts, levels)
+        assert all(0 < n < small['nms_pre'] for n in levels[b][1:]), (counts, levels)
         assert int((product < THR).sum()) >= 1, b                       # the threshold was applied before the multiplication
         assert bool((product[:-1] >= product[1:]).all())
         assert int((cls_score[:-1] < cls_score[1:]).sum()) >= 1, b      # the NMS order is not the selection order
@@ -55,6 +63,10 @@ def check_exact(device, dim, layout, variant, max_shape):
 @pytest.mark.parametrize('dim', [4, 5])
 def test_exact_against_the_composition(dim, layout, variant, max_shape):
     check_exact('cpu', dim, layout, variant, max_shape)
+
+
+def test_exact_past_one_tile_beside_an_empty_image():
+    check_exact('cpu', 4, 'flat', 'unbiased', None, SECOND_TILE)
 
 
 def check_selection_ignores_the_centerness(device, layout):

@@ -37,6 +37,10 @@ def test_exact_against_the_composition(S, dim, layout, variant, max_shape):
     H.check_exact('cuda', dim, layout, variant, max_shape)
 
 
+def test_exact_past_one_tile_beside_an_empty_image(S):
+    H.check_exact('cuda', 4, 'flat', 'unbiased', None, H.SECOND_TILE)
+
+
 @pytest.mark.parametrize('layout', ['nchw', 'flat'])
 def test_selection_ignores_the_centerness(S, layout):
     H.check_selection_ignores_the_centerness('cuda', layout)

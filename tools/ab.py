@@ -26,6 +26,9 @@ Workloads (all through the C ABI, buffers allocated once, HIP events around `--l
             same on bf16 levels, forward + first backward with g = 1 and g = 0.5: sph2pob_*_sum_h16 where the arm's library has
             them, the cast route (.float(), the _f32 entry, the stash scaling, .to(bfloat16)) where it has not (the parent build)
   test_bboxes_h16  sph2pob_test_bboxes on bf16 levels at that shape (PANDORA's test_cfg): the _h16 entry, or .float() + the _f32 entry
+  bboxes    one call per batched inference entry under PANDORA's test_cfg, fp32, BFoV, 8 images x 37 classes, the inputs of the
+            tools/time_*_bboxes.py scripts: sph2pob_test_bboxes_f32 and sph2pob_softmax_bboxes_f32 on the 98 208 anchors,
+            sph2pob_fcos_bboxes_f32 on the 10 912 points, sph2pob_rcnn_bboxes_f32 on 1 000 padded rois per image
   adjoint   sph2pob_transform_bwd_f32 / _general_f32, every instantiated (variant, dim) x edge x angle x jitter, --pairs N
 Every arm's outputs are compared with the first arm's (bit equality is reported, not assumed).
 """
@@ -381,6 +384,68 @@ def workloads(args, torch, G):
                 return lib.sph2pob_test_bboxes_f32(ptrs(*[G.ptr(x) for x in cf]), ptrs(*[G.ptr(x) for x in bf32]), ap, *mid, st)
             return launch, o
         yield f'test_bboxes bf16 unbiased {images} x {sum(a.size(0) for a in anchors)}', make
+    elif args.workload == 'bboxes':
+        import math
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        import rcnn_bboxes_restatement as R
+        import sph_retina_amd as S
+        from tools import demo_hot_path as D
+        images, classes, levels = 8, 37, len(D.LEVEL_SHAPES)
+        ptrs, i64s, f4 = ctypes.c_void_p * levels, ctypes.c_int64 * levels, ctypes.c_float * 4
+        f32, i64 = dict(dtype=torch.float32, device='cuda'), dict(dtype=torch.int64, device='cuda')
+        coder = (f4(0, 0, 0, 0), f4(0.1, 0.1, 0.2, 0.2), abs(math.log(16 / 1000)), 1, 32.0)   # means, stds, max_ratio, coder_flags, ctr_clamp
+        nms = (5, 0, 0.5, 100)                                                                # unbiased, per class, iou_threshold, max_per_img
+
+        def outputs(extra=0):
+            return [torch.empty((images, 100, 5), **f32), torch.empty((images, 100), **i64), torch.empty((images, 100), **i64)] + \
+                [torch.empty((images,), **i64) for _ in range(1 + extra)]
+
+        def workspace(shared, need):
+            """One workspace per entry for all arms (they run one after the other on one stream): byte-identical selection kernels
+            differed by up to 10 us between arms that had a workspace each, more than any difference between the builds."""
+            ws = shared.setdefault('ws', torch.empty(need, dtype=torch.uint8, device='cuda'))
+            assert ws.numel() == need
+            return ws
+
+        def table(tensors):
+            return ptrs(*[G.ptr(t) for t in tensors])
+
+        def dense(name, symbol, ws_symbol, heads, priors, per_position, head_args):
+            """A dense head's entry: `heads` are its level tensor lists in the order of the entry's pointer tables."""
+            ns, hws = i64s(*[per_position * h * w for h, w in D.LEVEL_SHAPES]), i64s(*[h * w for h, w in D.LEVEL_SHAPES])
+            tables = [table(x) for x in heads[:2]] + [table(priors)] + [table(x) for x in heads[2:]]
+
+            shared = {}
+
+            def make(lib, held=(heads, priors)):   # (the tables hold addresses only: the tensors live as long as the launch does)
+                o = outputs()
+                ws = workspace(shared, getattr(lib, ws_symbol)(ns, levels, images, classes, 4, 1000))
+                fn = getattr(lib, symbol)
+                return (lambda: fn(*tables, ns, hws, levels, images, classes, 4, *head_args, *nms, *[G.ptr(t) for t in o], G.ptr(ws), st)), o
+            return f'bboxes {name} unbiased {images} x {sum(p.size(0) for p in priors)}', make
+
+        anchors = D.retina_level_anchors()
+        yield dense('test_bboxes_f32', 'sph2pob_test_bboxes_f32', 'sph2pob_get_bboxes_workspace_bytes', D.head_outputs(images, classes, dim=4, seed=4),
+                    anchors, 9, (0, 0.05, 1000, *coder))
+        yield dense('softmax_bboxes_f32', 'sph2pob_softmax_bboxes_f32', 'sph2pob_softmax_bboxes_workspace_bytes',
+                    D.softmax_head_outputs(images, classes, seed=1), anchors, 9, (0.05, 1000, *coder))
+        points = S.sph_fcos_points(D.LEVEL_SHAPES, D.FCOS_CFG['strides'], device='cuda')
+        yield dense('fcos_bboxes_f32', 'sph2pob_fcos_bboxes_f32', 'sph2pob_get_bboxes_workspace_bytes', D.fcos_infer_outputs(images, classes, seed=1),
+                    points, 1, (1, 0.05, 1000, 512, 1024, 512.0, 1024.0))
+
+        m, cap = 1000, 16384   # the default capacity of sph_rcnn_bboxes at score_thr 0.05: min(M * 20, sph2pob_batched_nms_max_boxes())
+        g = torch.Generator().manual_seed(m)
+        counts = tuple(int(m * (0.6 + 0.4 * float(torch.rand((), generator=g)))) for _ in range(images))
+        rois, num, logits, box = R.scene(4, 5, 'per_class', 'cuda', seed=m, counts=counts, m=m, num_classes=classes)
+
+        shared = {}
+
+        def make(lib):
+            o = outputs(extra=1)   # num_valid
+            ws = workspace(shared, lib.sph2pob_rcnn_bboxes_workspace_bytes(images, m, classes + 1, 4, cap))
+            return (lambda: lib.sph2pob_rcnn_bboxes_f32(G.ptr(rois), G.ptr(num), G.ptr(logits), G.ptr(box), images, m, rois.size(2), classes + 1, 4, 0,
+                                                        0.05, cap, *coder, *nms, *[G.ptr(t) for t in o], G.ptr(ws), st)), o
+        yield f'bboxes rcnn_bboxes_f32 unbiased {images} x {m} rois', make
     elif args.workload == 'adjoint':
         n = int(args.pairs.split(',')[0])
         g = torch.Generator().manual_seed(7)

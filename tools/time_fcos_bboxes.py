@@ -10,7 +10,7 @@ Device events around each step, median / p10 / p90 over settled steps; the sides
 synchronise per step adds the launch latency of the first kernel to every figure alike; the differences are not affected.)
 
 python tools/time_fcos_bboxes.py --profile — (i) and (iii) alone, fp32, PANDORA, 40 calls each and no events: the program
-of a `rocprofv3 --kernel-trace --stats` run of its own (cand_build_points_kernel beside cand_build_kernel).
+of a `rocprofv3 --kernel-trace --stats` run of its own (cand_build_kernel<PointSource> beside cand_build_kernel<DeltaSource>).
 
 python tools/time_fcos_bboxes.py --split KERNEL_TRACE.csv KERNEL_STATS.csv OUT_STATS.csv OUT_SPLIT.json — needs no GPU: from that
 run's kernel trace, the average device time of each of the library's kernels per call and side (a call begins at its zero_kernel;
@@ -24,8 +24,12 @@ import statistics
 import sys
 
 PROFILE_CALLS, PROFILE_SKIP = 40, 5
-STAGES = ('zero_kernel', 'topk_hist', 'topk_cut', 'topk_compact', 'topk_resolve', 'cand_build_points', 'cand_build', 'nms_prepare', 'nms_mask_compact',
-          'nms_sweep', 'nms_select')
+# what a kernel's name holds -> its stage, the first match counts: cand_build_kernel<Source> is told apart by its candidate source,
+# and a trace of a build that still had cand_build_points_kernel reads the same (the stage names are those of the recorded
+# profiles/fcos_bboxes_kernel_split.json)
+STAGES = {'zero_kernel': 'zero_kernel', 'topk_hist': 'topk_hist', 'topk_cut': 'topk_cut', 'topk_compact': 'topk_compact', 'topk_resolve': 'topk_resolve',
+          'PointSource': 'cand_build_points', 'cand_build_points': 'cand_build_points', 'cand_build': 'cand_build', 'nms_prepare': 'nms_prepare', 'nms_mask_compact': 'nms_mask_compact',
+          'nms_sweep': 'nms_sweep', 'nms_select': 'nms_select'}
 
 
 def ours(name):
@@ -42,7 +46,7 @@ def split_trace(trace_csv, stats_csv, out_stats, out_split):
         if 'zero_kernel' in r['Kernel_Name']:
             calls.append([])
         if calls:
-            stage = next(s for s in STAGES if s in r['Kernel_Name'])
+            stage = next(stage for needle, stage in STAGES.items() if needle in r['Kernel_Name'])
             calls[-1].append((stage, int(r['End_Timestamp']) - int(r['Start_Timestamp'])))
     assert len(calls) == 2 * PROFILE_CALLS, len(calls)
     split = dict(source='rocprofv3 --kernel-trace --stats -- python tools/time_fcos_bboxes.py --profile (fp32, PANDORA, B = 8, 10 912 points; '
