@@ -10,7 +10,8 @@
  * prec selects where float32 roundings happen:
  *   0  everything in double — what the reference computes when it is handed float64 tensors ("truth" fixtures);
  *   1  float32 spherical jitter and float32 deg2rad (sph_iou_api.py:121, unbiased_iou_bfov.py:189), then double —
- *      the definition the HIP kernel implements;
+ *      the definition the HIP kernel implements, which also keeps a candidate vertex by the exact sign of P . N where the
+ *      reference rounds to 8 decimals (ub_nonneg);
  *   2  the reference's own mixed arithmetic on float32 tensors: numpy keeps float32 wherever both operands are
  *      float32 (sin/cos of the inputs, V_lookat, V_up, N_up, N_down, the rotation matrix entries, the two areas)
  *      and is float64 elsewhere (V_right carries an np.zeros float64 column, :24-25).  sinf/cosf/acosf of libm stand
@@ -89,8 +90,9 @@ static inline double ub_angle(ub_vec a, ub_vec b) { /* interArea :49-53 */
     c = c < -1 ? -1 : (c > 1 ? 1 : c);
     return acos(c);
 }
-/* np.round(x, 8) >= 0 */
-static inline int ub_nonneg(double d) { return rint(d * 1e8) / 1e8 >= 0; }
+/* np.round(x, 8) >= 0; prec 1 (the kernel's definition): the exact sign — the rounding keeps candidates up to 5e-9 outside a
+ * plane, and a vertex set with one of those is not a polygon (csrc/sph2pob_unbiased.hpp, ub_inside) */
+static inline int ub_nonneg(double d, int prec) { return prec == 1 ? d >= 0 : rint(d * 1e8) / 1e8 >= 0; }
 
 static double ub_area(double fx, double fy, int prec) { /* area :10-12 */
     if (prec == 2) {
@@ -121,10 +123,14 @@ static double unbiased_pair_iou(const double* in1, const double* in2, int dim, i
     /* remove_outer_points (bfov :105-139): 8 corners, then 16 plane pairs x 2 antipodal points */
     for (int k = 0; k < 8; k++) {
         int inside = 1;
-        for (int j = 0; j < 8; j++) inside &= ub_nonneg(ub_dot(V[k], N[j]));
+        const int (*E)[2] = k < 4 ? E1 : E2;
+        int base = k < 4 ? 0 : 4;
+        for (int j = 0; j < 8; j++) {
+            /* prec 1: a vertex lies on its own two planes by construction, the sign of that rounding noise is not asked */
+            if (prec == 1 && (j == base + E[k & 3][0] || j == base + E[k & 3][1])) continue;
+            inside &= ub_nonneg(ub_dot(V[k], N[j]), prec);
+        }
         if (inside) {
-            const int (*E)[2] = k < 4 ? E1 : E2;
-            int base = k < 4 ? 0 : 4;
             sum += ub_angle(N[base + E[k & 3][0]], N[base + E[k & 3][1]]);
             count++;
         }
@@ -139,8 +145,9 @@ static double unbiased_pair_iou(const double* in1, const double* in2, int dim, i
             ub_vec q = {{t2.v[0] / nrm2, t2.v[1] / nrm2, t2.v[2] / nrm2}};
             int in_p = 1, in_q = 1;
             for (int k = 0; k < 8; k++) {
-                in_p &= ub_nonneg(ub_dot(p, N[k]));
-                in_q &= ub_nonneg(ub_dot(q, N[k]));
+                if (prec == 1 && (k == i || k == 4 + j)) continue;
+                in_p &= ub_nonneg(ub_dot(p, N[k]), prec);
+                in_q &= ub_nonneg(ub_dot(q, N[k]), prec);
             }
             if (in_p) { sum += ub_angle(N[i], N[4 + j]); count++; }
             if (in_q) { sum += ub_angle(N[4 + j], N[i]); count++; }

@@ -9,8 +9,9 @@
 //      look-at axis by gamma (roll_T);
 //   2. candidate vertices of the intersection: the 8 box corners and, for each of the 16 (plane of box 1, plane of
 //      box 2) pairs, the two antipodal intersection points of the great circles (remove_outer_points :105-139);
-//   3. a candidate is kept when np.round(P . N_k, 8) >= 0 for all 8 normals; each kept vertex contributes the angle
-//      acos(-N_a . N_b) between the two planes that meet there; area = sum - (count - 2) * pi (interArea :49-62).
+//   3. a candidate is kept when np.round(P . N_k, 8) >= 0 for all 8 normals (default arithmetic: when P . N_k >= 0, see
+//      ub_inside); each kept vertex contributes the angle acos(-N_a . N_b) between the two planes that meet there;
+//      area = sum - (count - 2) * pi (interArea :49-62).
 //
 // Identities used (exact in real arithmetic, 1e-16-level in floating point; never at a decision threshold except
 // where the reference's own decision is already rounding noise):
@@ -172,10 +173,20 @@ SPH_DEV void ub_minmax(const DVec& t, const DVec& n, double& lo, double& hi) {
 // np.round(d / (|t| + off), 8) >= 0 for the smallest (most negative) dot product d = lo <= 0 of a candidate, i.e.
 // lo * 1e8 >= -0.5 * (sqrt(tt) + off).  |t| <= ~1 (cross product of unit normals), so the square root is only needed
 // inside the 5e-9 band where the reference's rounding decides; NaN (tt != tt) is never inside.
+//
+// That rounding keeps a candidate up to 5e-9 OUTSIDE a plane, and a set with such a candidate is not a polygon: where a
+// corner of one box lies that close outside an edge of the other (nearly coincident edge planes: slivers, boxes that
+// share an extent and are 3 eps apart after the jitter), the set holds the corner AND the two edge crossings that
+// replace it, one vertex and (angle - pi) ~ -1.5 sr too many; the reference's own float64 then returns a negative
+// intersection (IoU 0 after the clamp, or a wrong positive value where the true intersection exceeds 1.5 sr).  The
+// default arithmetic (BAND = false) therefore keeps a candidate by the exact sign, which the geometry decides down to
+// the 1e-16 of the dot products; lo = 0 (coincident planes: t = 0) is inside under both rules.  Reference arithmetic
+// keeps the reference's rounding.
+template <bool BAND>
 SPH_DEV bool ub_inside(double lo, double tt, double off) {
     if (!(tt == tt)) return false;
     if (lo >= 0.0) return true;
-    if (lo * 1e8 < -0.51) return false;
+    if (!BAND || lo * 1e8 < -0.51) return false;
     return lo * 1e8 >= -0.5 * (sqrt(tt) + off);
 }
 
@@ -214,7 +225,7 @@ SPH_DEV float unbiased_pair_iou(const float (&in1)[5], const float (&in2)[5]) {
                     if (k != ea[c] && k != eb[c]) ub_minmax(t, P.n[k], lo, hi);
                     ub_minmax(t, Q.n[k], lo, hi);
                 }
-                if (tt > 0.0 && ub_inside(lo, tt, 0.0)) {
+                if (tt > 0.0 && ub_inside<R>(lo, tt, 0.0)) {
                     sum += P.corner;
                     count++;
                 }
@@ -233,7 +244,7 @@ SPH_DEV float unbiased_pair_iou(const float (&in1)[5], const float (&in2)[5]) {
                     if (k != i) ub_minmax(t, A.n[k], lo, hi);
                     if (k != j) ub_minmax(t, B.n[k], lo, hi);
                 }
-                const bool in_p = ub_inside(lo, tt, 1e-10), in_q = ub_inside(-hi, tt, 1e-10);
+                const bool in_p = ub_inside<R>(lo, tt, 1e-10), in_q = ub_inside<R>(-hi, tt, 1e-10);
                 if (in_p || in_q) {
                     const double ang = ub_acos_clip(-ddot(A.n[i], B.n[j]));
                     const int c = (in_p ? 1 : 0) + (in_q ? 1 : 0);

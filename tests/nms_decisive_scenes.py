@@ -11,6 +11,9 @@ over the site distance is about 0.97 - 0.99 (same site), 0.82, 0.67, 0.54 | 0.43
 for RBFoV, the unbiased and the naive IoU (whose pixel ladder depends on the row): at threshold 0.5 a kept box removes the boxes
 up to three sites away on either side, nothing else, and no IoU comes near 0.5.
 
+Off the lattice: `geographic` — near-duplicate clusters at the poles, across the seam and wider than 90 degrees, accepted box by
+box so that the same condition holds (see there).
+
 Scores are distinct floats handed out through a seeded permutation: a scene is described in RANK order (rank = row of the box in
 the descending-score order, so a test places any box in any 64-row block of the kernels) and shuffled before it is returned.
 
@@ -120,13 +123,17 @@ class Scene:
 def make_scene(sites, classes=None, dim=4, seed=0):
     """`sites` (k, 2) and `classes` (k,) in RANK order -> Scene.  Scores: k distinct floats, descending with the rank, handed to
     the boxes through a seeded permutation of the input positions."""
-    sites = np.asarray(sites, np.int64).reshape(-1, 2)
-    k = len(sites)
+    return scene_of_boxes(site_boxes(np.asarray(sites, np.int64).reshape(-1, 2), dim), classes, seed)
+
+
+def scene_of_boxes(ranked, classes=None, seed=0):
+    """Boxes (k, dim) float32 and `classes` (k,) in RANK order -> Scene, with the scores and the shuffle of make_scene."""
+    k, dim = ranked.shape
     at = np.random.default_rng([seed, k]).permutation(k)
     by_rank = np.linspace(0.95, 0.05, k).astype(np.float32) if k > 1 else np.array([0.5], np.float32)
     assert k < 2 or (np.diff(by_rank) < 0).all()
     boxes, scores, idxs = np.empty((k, dim), np.float32), np.empty(k, np.float32), np.zeros(k, np.int64)
-    boxes[at], scores[at] = site_boxes(sites, dim), by_rank
+    boxes[at], scores[at] = ranked, by_rank
     if classes is not None:
         idxs[at] = np.asarray(classes, np.int64)
     return Scene(boxes, scores, idxs, at)
@@ -291,6 +298,50 @@ def crowded_top(n_near, k, dim=4, seed=0):
     rest = np.concatenate([np.stack([np.full(n_near, row), centre + near], 1), others])
     rest = rest[rng.permutation(len(rest))]
     return make_scene(np.concatenate([[[row, centre]], rest]), None, dim, seed)
+
+
+GEO_KINDS = ('polar', 'seam', 'wide')
+GEO_CALCULATORS = ('unbiased', 'standard', 'efficient')
+GEO_K = 330                               # two classes of ~165: five 64-row blocks in all, each class across three
+GEO_BAND = 0.02                           # no pair of one class has a float64 IoU within this of the threshold, under any calculator
+GEO_NOISE = np.array([1.5, 1.5, 1.0, 1.0, 2.0])
+
+
+@functools.lru_cache(maxsize=None)
+def geographic(kind, dim, seed=0):
+    """Boxes where the lattice never goes: at the poles (phi within 8 degrees of either), across the 0 / 360 seam (theta within 3
+    degrees of it on both sides), or wider than 90 degrees (tests/sphere_regimes.py; polar and seam extents 8 - 60 degrees).
+    GEO_K boxes in two classes: 60 % near-duplicates of 40 cluster centres of the kind (GEO_NOISE degrees of noise, theta
+    wrapped), 40 % free boxes of the kind.  Plain random clusters do not meet the margin condition (their deciding pairs come
+    within 5e-6 ... 1.5e-3 of the threshold), so the scene is built by seeded rejection in rank order: a candidate is accepted
+    only if its float64 IoU with EVERY accepted box of its class lies outside (THR - GEO_BAND, THR + GEO_BAND) under each of
+    GEO_CALCULATORS; `reference` then asserts MARGIN on the deciding pairs as for every other scene."""
+    from oracle import oracle as O
+    import sphere_regimes as R
+    rng = np.random.default_rng([seed, 11, dim, GEO_KINDS.index(kind)])
+    ext = None if kind == 'wide' else (8, 60)
+    centres = R.boxes(kind, 40, dim, seed=100 + seed, ext=ext).astype(np.float64)
+    free = R.boxes(kind, 40 * GEO_K, dim, seed=200 + seed, ext=ext).astype(np.float64)
+    fns = [f64_iou(O, c) for c in GEO_CALCULATORS]
+    ranked, classes, n_free, tries = [], [], 0, 0
+    while len(ranked) < GEO_K:
+        tries += 1
+        assert tries < 40 * GEO_K, (kind, dim, len(ranked))
+        if rng.random() < 0.6:
+            b = centres[rng.integers(0, len(centres))] + rng.standard_normal(dim) * GEO_NOISE[:dim]
+            b[0] %= 360
+            b[1] = np.clip(b[1], 0.05, 179.95)
+            b[2:4] = np.clip(b[2:4], 8 if ext else 91, 60 if ext else 179.5)
+        else:
+            b, n_free = free[n_free], n_free + 1
+        b, c = b.astype(np.float32)[None], int(rng.integers(0, 2))
+        same = [r for r, rc in zip(ranked, classes) if rc == c]
+        # (the candidate in the bboxes1 role: the jitter's asymmetry, ~1e-4, is far inside GEO_BAND - MARGIN)
+        if same and any((np.abs(f(b, np.concatenate(same)) - THR) < GEO_BAND).any() for f in fns):
+            continue
+        ranked.append(b)
+        classes.append(c)
+    return scene_of_boxes(np.concatenate(ranked), classes, seed)
 
 
 SEGMENT_SIZES = (1, 63, 64, 65, 1, 1, 128, 2, 191, 1, 300)

@@ -169,23 +169,31 @@ def assert_invariants(got, num, dim, num_classes, add_gt, gt_counts):
 B, M, NUM_PROPOSALS, GT_COUNTS = 4, 100, (100, 37, 0, 64), (5, 0, 1, 70)
 
 
-def draw(dim, seed, m=M, num_proposals=NUM_PROPOSALS, gt_counts=GT_COUNTS, extra=1):
+def draw(dim, seed, m=M, num_proposals=NUM_PROPOSALS, gt_counts=GT_COUNTS, extra=1, geographic=False):
     """-> proposals (B, m, dim + extra) CPU (a score column behind the box; rows behind an image's count hold NaN: never read),
     [gt_b], [labels_b].  GT away from the poles and the seam; 70 % of an image's proposals are jittered copies of its GT (IoUs from
     ~0.2 to ~0.9), the rest uniform boxes; proposals 3 and 9 of image 0 are one box, GT 2 moved by half a degree (the GT's maximum at
-    two columns)."""
+    two columns).  geographic: the GT of image b are instead polar, seam, wide and mixed boxes of tests/sphere_regimes.py (b = 0 ... 3;
+    the first two with extents 10 - 45 degrees), the copies wrapped in theta and kept inside (0, 180) in phi."""
     rng = np.random.default_rng(seed)
     props = np.full((len(num_proposals), m, dim + extra), np.nan, np.float32)
     gts, labs = [], []
     for b, (n, k) in enumerate(zip(num_proposals, gt_counts)):
         gt = np.stack([rng.uniform(30, 330, k), rng.uniform(50, 130, k), rng.uniform(10, 45, k), rng.uniform(10, 45, k), rng.uniform(-40, 40, k)], 1)
         anywhere = np.stack([rng.uniform(5, 355, n), rng.uniform(30, 150, n), rng.uniform(5, 50, n), rng.uniform(5, 50, n), rng.uniform(-60, 60, n)], 1)
+        if geographic:
+            import sphere_regimes
+            kind = sphere_regimes.KINDS[b % 4]
+            gt[:, :dim] = sphere_regimes.boxes(kind, k, dim, seed=seed + b, ext=(10, 45))
         boxes = anywhere
         if k > 0 and n > 0:
             near = gt[rng.integers(0, k, n)] + np.concatenate([rng.normal(0, 4, (n, 2)), rng.normal(0, 4, (n, 2)), rng.normal(0, 8, (n, 1))], 1)
-            near[:, 2:4] = np.clip(near[:, 2:4], 5, 60)
+            near[:, 2:4] = np.clip(near[:, 2:4], 5, 179.5 if geographic else 60)
             boxes = np.where(rng.random((n, 1)) < 0.3, anywhere, near)
             boxes[:, 4] += 0.37
+            if geographic:
+                boxes[:, 0] %= 360
+                boxes[:, 1] = np.clip(boxes[:, 1], 0.05, 179.95)
         if b == 0 and k > 2 and n > 9:
             boxes[3] = gt[2]
             boxes[3, :2] += 0.5

@@ -1,7 +1,9 @@
 """Shared by tests/test_train_targets_host.py and tests/test_gpu_train_targets.py: the backends `sph_train_targets` sends to
 `sph2pob_anchor_targets_any_f32`, `train_cfg` dicts in the reference's form, scenes whose anchors are drawn near the GT (so that
 positives, negatives and ignored columns all occur), and the premise every test asserts: the per-image overlaps are finite and
-in [0, 1]."""
+in [0, 1].  draw() keeps its GT away from the poles and the seam; draw_geographic() puts them there — at either pole, across the
+0 / 360 seam, or wider than 90 degrees — with the anchors jittered copies wrapped in theta (run_geographic: the cases of
+tests/test_sphere_regimes_host.py and tests/test_gpu_sphere_regimes.py)."""
 import numpy as np
 import torch
 
@@ -57,6 +59,55 @@ def draw(n, counts, dim, seed, far=0.3):
         labs.append(labels[lo:lo + k].clone())
         lo += k
     return an_t.contiguous(), gts, labs
+
+
+GEO_KINDS = ('polar', 'seam', 'wide')
+
+
+def draw_geographic(n, counts, dim, seed, kind, far=0.3):
+    """The same shape of scene as draw(), with the GT where draw() never puts them (tests/sphere_regimes.py): `kind` = 'polar'
+    (phi within 8 degrees of either pole), 'seam' (theta within 3 degrees of 0 / 360, both sides, so that a GT's jittered copies
+    land on either side of it) or 'wide' (extents 91 - 179.5 degrees; polar and seam: 10 - 45).  1 - far of the anchors are
+    jittered copies of a random GT, theta wrapped into [0, 360) and phi kept inside (0, 180); the rest lie anywhere."""
+    import sphere_regimes as R
+    rng = np.random.default_rng([seed, 17, GEO_KINDS.index(kind)])
+    K = max(sum(counts), 1)
+    wide = kind == 'wide'
+    gt = np.zeros((K, 5))
+    gt[:, :dim] = R.boxes(kind, K, dim, seed=seed, ext=None if wide else (10, 45))
+    src = gt[rng.integers(0, K, n)]
+    near = src + np.concatenate([rng.normal(0, 5, (n, 2)), rng.normal(0, 4, (n, 2)), rng.normal(0, 8, (n, 1))], 1)
+    near[:, 2:4] = np.clip(near[:, 2:4], *((91, 179.5) if wide else (5, 60)))
+    ext = (91, 179.5) if wide else (5, 50)
+    anywhere = np.stack([rng.uniform(0, 360, n), rng.uniform(0.5, 179.5, n), rng.uniform(*ext, n), rng.uniform(*ext, n), rng.uniform(-60, 60, n)], 1)
+    anchors = np.where(rng.random((n, 1)) < far, anywhere, near)
+    anchors[:, 0] %= 360
+    anchors[:, 1] = np.clip(anchors[:, 1], 0.05, 179.95)
+    anchors[:, 4] += 0.37   # no anchor shares a GT's angle
+    gt_t, an_t = torch.from_numpy(gt[:, :dim].astype(np.float32)), torch.from_numpy(anchors[:, :dim].astype(np.float32))
+    labels = torch.from_numpy(rng.integers(0, 37, K))
+    gts, labs, lo = [], [], 0
+    for k in counts:
+        gts.append(gt_t[lo:lo + k].clone())
+        labs.append(labels[lo:lo + k].clone())
+        lo += k
+    return an_t.contiguous(), gts, labs
+
+
+def run_geographic(device, backend, dim, formator, kind, n=549, counts=(9, 1, 0, 17), closed_form=False):
+    """A geographic scene through sph_train_targets (closed_form: through sph_anchor_targets) against the per-image API, with
+    positives, negatives and ignored columns all present -> the output."""
+    anchors, gts, labs = to(device, *draw_geographic(n, counts, dim, seed=71, kind=kind))
+    cfg = train_cfg(backend, dim, formator, pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0.3)
+    a = assigner_of(cfg)
+    assert_premise(a, anchors, gts)
+    if closed_form:
+        out = S.sph_anchor_targets(anchors, gts, labs, assigner=a, num_classes=37)
+    else:
+        out = S.sph_train_targets(anchors, gts, labs, train_cfg=cfg, num_classes=37)
+    check_batch(out, a, anchors, gts, labs, 37)
+    assert int(out.num_pos.sum()) > 0 and int(out.num_neg.sum()) > 0 and int((out.gt_inds == -1).sum()) > 0, (backend, dim, kind)
+    return out
 
 
 def assert_premise(assigner, anchors, gts):
