@@ -79,6 +79,7 @@ const char* sph2pob_error_string(int code);
  * box_iou_rotated -> clamp: sphdet/iou/sph_iou_api.py:48-86 (and the wrappers at :91-98).
  * b1, b2: (n, box_dim) f32; out: (n) f32.  Algorithmic HBM traffic: 2*4*box_dim + 4 bytes per pair.
  */
+/* Precondition (b1, b2): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_iou_aligned_f32(const float* b1, const float* b2, float* out, int64_t n, int box_dim, int variant,
                             int mode, int edge, int angle, void* stream);
 
@@ -88,6 +89,7 @@ int sph2pob_iou_aligned_f32(const float* b1, const float* b2, float* out, int64_
  * This is the call MaxIoUAssigner makes: overlaps = iou_calculator(gt_bboxes, bboxes)
  * (mmdet/core/bbox/assigners/max_iou_assigner.py:113).
  */
+/* Precondition (b1, b2): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_iou_pairwise_f32(const float* b1, int64_t m, const float* b2, int64_t n, float* out, int box_dim,
                              int variant, int mode, int edge, int angle, void* stream);
 
@@ -99,6 +101,7 @@ int sph2pob_iou_pairwise_f32(const float* b1, int64_t m, const float* b2, int64_
  * sphdet/iou/sph2pob_standard.py:8-80, sph2pob_efficient.py:9-73, sph2pob_legacy.py:8-31.
  * variant: STANDARD, EFFICIENT or LEGACY (BFoV only); any other variant returns SPH2POB_ERR_OPTION.
  */
+/* Precondition (b1, b2): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_transform_f32(const float* b1, const float* b2, float* planar1, float* planar2, int64_t n,
                           int box_dim, int variant, int edge, int angle, int jitter, void* stream);
 
@@ -110,6 +113,7 @@ int sph2pob_transform_f32(const float* b1, const float* b2, float* planar1, floa
  * torch autograd through the ~70 transform ops.  With jitter != 0 the clamp gates of both jitters are applied.
  * Any variant other than STANDARD or EFFICIENT returns SPH2POB_ERR_OPTION.
  */
+/* Precondition (b1, b2): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_transform_bwd_f32(const float* b1, const float* b2, const float* grad_planar1, const float* grad_planar2,
                               float* grad_b1, float* grad_b2, int64_t n, int box_dim, int variant, int edge, int jitter,
                               void* stream);
@@ -122,6 +126,7 @@ int sph2pob_transform_bwd_f32(const float* b1, const float* b2, const float* gra
  * jitter != 0: the adjoint of jitter_spherical -> transform -> jitter_rotated (Sph2PobTransfrom('sph2pob_legacy'),
  * sphdet/losses/sph2pob_transform.py:12-16, :28-30).
  */
+/* Precondition (b1, b2): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_transform_bwd_general_f32(const float* b1, const float* b2, const float* grad_planar1,
                                       const float* grad_planar2, float* grad_b1, float* grad_b2, int64_t n, int box_dim,
                                       int variant, int edge, int angle, int jitter, void* stream);
@@ -147,6 +152,7 @@ int sph2pob_planar_iou_f32(const float* p1, int64_t m, const float* p2, int64_t 
  * the per-box mean is taken as OBBIoULoss.forward does, sph2pob_iou_loss.py:43-48].  iou (optional, may be NULL)
  * receives the clamped planar IoU.  eps = the loss's eps (default 1e-6, sph2pob_iou_loss.py:17).
  */
+/* Precondition (pred, target): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_loss_fwd_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                          float* loss, float* iou, int64_t n, int box_dim, int loss_mode, float eps, void* stream);
 
@@ -157,6 +163,7 @@ int sph2pob_loss_fwd_f32(const float* pred, const float* target, const float* we
  * Replaces torch autograd through the ~150 ops the reference records for this loss.  Recomputes the forward in
  * registers: reads only pred, target, weight and grad_out.
  */
+/* Precondition (pred, target, grad_pred, grad_target): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_loss_bwd_f32(const float* pred, const float* target, const float* weight, int weight_dim,
                          const float* grad_out, int grad_stride, float scale, float* grad_pred, float* grad_target,
                          int64_t n, int box_dim, int loss_mode, float eps, void* stream);
@@ -169,6 +176,7 @@ int sph2pob_loss_bwd_f32(const float* pred, const float* target, const float* we
  * sph2pob_loss_sum_workspace_floats(n) floats.  Backward: sph2pob_loss_bwd_f32 with grad_stride 0 and the same scale.
  */
 int64_t sph2pob_loss_sum_workspace_floats(int64_t n);
+/* Precondition (pred, target): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_loss_fwd_sum_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                              float* out, float* workspace, int64_t n, int box_dim, int loss_mode, float eps,
                              void* stream);
@@ -184,6 +192,7 @@ int sph2pob_loss_fwd_sum_f32(const float* pred, const float* target, const float
  * out may be the stash itself (in place); in place with a scalar upstream gradient of exactly 1.0 — a plain
  * `loss.backward()` — the launch returns after one scalar load per workgroup: the stash already is the gradient.
  */
+/* Precondition (pred, target, grad_pred, grad_target; sph2pob_loss_grad_scale_f32 reads and writes one element at a time): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_loss_fwd_grad_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                               float* loss, float* out_sum, float* workspace, float* grad_pred, float* grad_target,
                               int64_t n, int box_dim, int loss_mode, float eps, void* stream);
@@ -215,6 +224,7 @@ enum { SPH2POB_GAUSS_GWD = 0, SPH2POB_GAUSS_KLD = 1, SPH2POB_GAUSS_JD = 2, SPH2P
 enum { SPH2POB_GAUSS_FUN_NONE = 0, SPH2POB_GAUSS_FUN_LOG1P = 1, SPH2POB_GAUSS_FUN_SQRT = 2, SPH2POB_GAUSS_FUN_LN = 3,
        SPH2POB_GAUSS_FUN_EXP = 4 };
 enum { SPH2POB_GAUSS_OPT_SQRT = 1, SPH2POB_GAUSS_OPT_NORMALIZE = 2 };
+/* Precondition (pred, target, grad_pred, grad_target of the four sph2pob_gauss_loss entries): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_gauss_loss_fwd_f32(const float* pred, const float* target, const float* weight, int weight_dim, float scale,
                                float* loss, int64_t n, int box_dim, int type_flags, int fun, float tau, float alpha,
                                int opts, float beta, float eps, void* stream);
@@ -249,6 +259,7 @@ int sph2pob_sum_f32(const float* x, int64_t n, float scale, float* out, float* w
  */
 int sph2pob_nms_max_boxes(void);
 int64_t sph2pob_nms_workspace_bytes(int64_t k);
+/* Precondition (boxes_sorted): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_nms_f32(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim, int variant,
                     float iou_threshold, void* workspace, unsigned char* keep, void* stream);
 /* Same with a caller-supplied bound on the largest class segment (boxes of one class): the suppression matrix is then
@@ -258,6 +269,7 @@ int sph2pob_nms_f32(const float* boxes_sorted, const int64_t* cls_sorted, int64_
  * (box, class) candidates above score_thr to the NMS (sphdet/bbox/nms/utils.py:6-15): 5 000 boxes x 37 classes is
  * beyond the one-matrix limit of sph2pob_nms_f32 but ~1 700 per class. */
 int64_t sph2pob_nms_segmented_workspace_bytes(int64_t k, int64_t max_segment);
+/* Precondition (boxes_sorted): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_nms_segmented_f32(const float* boxes_sorted, const int64_t* cls_sorted, int64_t k, int box_dim, int variant,
                               float iou_threshold, int64_t max_segment, void* workspace, unsigned char* keep,
                               void* stream);
@@ -274,6 +286,7 @@ int sph2pob_nms_segmented_f32(const float* boxes_sorted, const int64_t* cls_sort
  */
 int sph2pob_batched_nms_max_boxes(void);
 int64_t sph2pob_batched_nms_workspace_bytes(int64_t k, int box_dim);
+/* Precondition (boxes): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_batched_nms_f32(const float* boxes, const float* scores, const int64_t* idxs, int64_t k, int box_dim, int variant,
                             float iou_threshold, int64_t max_num, void* workspace, int64_t* keep, float* dets, int* status,
                             void* stream);
@@ -385,6 +398,7 @@ int sph2pob_assign_f32(const float* overlaps, int64_t k, int64_t n, float pos_io
  */
 int64_t sph2pob_iou_assign_workspace_bytes(int64_t k, int64_t n);
 int64_t sph2pob_iou_assign_state_bytes(int64_t k, int64_t n);
+/* Precondition (gt, boxes of the three sph2pob_iou_assign entries): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_iou_assign_reduce_f32(const float* gt, int64_t k, const float* boxes, int64_t n, int box_dim, int variant, int edge,
                                   const unsigned char* ignore, int64_t col_offset, float* overlaps, int64_t* gt_keys,
                                   void* workspace, void* state, void* stream);
@@ -435,6 +449,7 @@ int sph2pob_iou_assign_f32(const float* gt, int64_t k, const float* boxes, int64
  */
 int64_t sph2pob_anchor_targets_workspace_bytes(int64_t num_images, int64_t num_gt, int64_t k_max, int64_t n);
 int64_t sph2pob_anchor_targets_state_bytes(int64_t num_images, int64_t k_max, int64_t n);
+/* Precondition (anchors, gt, bbox_targets, bbox_weights): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
                                int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
                                float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
@@ -458,6 +473,7 @@ int sph2pob_anchor_targets_f32(const float* anchors, int64_t n, const float* gt,
  * pairwise entry answers) -> SPH2POB_ERR_DIM; STANDARD | EFFICIENT (they have their own entry), SPH2POB_FLAG_REFERENCE_ORDER, a
  * bad edge -> SPH2POB_ERR_OPTION; then the sizes and the NULL checks.
  */
+/* Precondition (anchors, gt, bbox_targets, bbox_weights): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_anchor_targets_any_f32(const float* anchors, int64_t n, const float* gt, const int64_t* gt_labels, const int64_t* gt_offsets,
                                    int64_t num_images, int64_t num_gt, int64_t k_max, int box_dim, int variant, int edge, float pos_iou_thr,
                                    float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all,
@@ -481,6 +497,7 @@ int sph2pob_anchor_targets_any_f32(const float* anchors, int64_t n, const float*
  *          decoded boxes feed Sph2PobIoULoss: sphdet/models/heads/sph_retina_head.py:255-264).
  */
 enum { SPH2POB_CODER_CLIP_BORDER = 1, SPH2POB_CODER_CTR_CLAMP = 2 };
+/* Precondition (proposals, gt, deltas; rois, deltas, boxes, grad_boxes, grad_deltas of the decode entries): BFoV box arrays (box_dim == 4) must be 16-byte aligned; the Python layer copies a view that is not. */
 int sph2pob_coder_encode_f32(const float* proposals, const float* gt, const float* means_host, const float* stds_host,
                              float* deltas, int64_t n, int box_dim, void* stream);
 int sph2pob_coder_decode_f32(const float* rois, const float* deltas, const float* means_host, const float* stds_host,
@@ -969,6 +986,7 @@ int sph2pob_point_coder_decode_bwd_f32(const float* points, const float* distanc
  * nothing read back, nothing allocated, capturable.  The arguments of sph2pob_test_bboxes_f32, with the anchor table and the delta
  * coder's block (means_host ... ctr_clamp) replaced:
  *   points        host array of L device pointers, (n_l, 2) fp32 pixel coordinates, 8-byte aligned, shared by the images
+ *                 (each point is one 8-byte load that nothing checks: the Python layer copies a view that is not 16-byte aligned)
  *   bbox_preds    the distances (l, t, r, b[, gamma]) in pixels, laid out like cls_scores with box_dim channels per point
  *   centernesses  host array of L device pointers, laid out like cls_scores with ONE channel per point: NCHW (B, A, H_l, W_l) —
  *                 point ai = p A + a of image b is element (b A + a) H_l W_l + p — or flat (B, n_l)

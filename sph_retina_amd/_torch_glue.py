@@ -70,6 +70,20 @@ def as_f32_nograd(t):
     return as_f32(t.detach() if t.requires_grad else t)
 
 
+def aligned16(t):
+    """`t` itself (the same object) when its storage starts on a 16-byte boundary or it is empty, else a clone (allocations are
+    256-byte aligned).  For the operands of the older BFoV kernels, which read a (n, 4) box row, or an FCOS point, as one 16- or
+    8-byte access without looking at the pointer (`load_box<4>`, the delta coder's `load_row<4>` / `store_row<4>`): a contiguous
+    view that starts inside a buffer (a slice of a flat bucket, `buf[1:].view(n, 4)`) is only element aligned.  The entries whose
+    launcher picks a scalar kind from the address are NOT fed through this."""
+    return t if t.data_ptr() % 16 == 0 or t.numel() == 0 else t.clone()
+
+
+def boxes16(t, dim):
+    """aligned16 of a BFoV (dim == 4) box array; RBFoV rows (dim == 5) are read one element at a time."""
+    return t if dim != 4 or t.data_ptr() % 16 == 0 or t.numel() == 0 else t.clone()
+
+
 def h16_dtype_code(levels):
     """SPH2POB_DTYPE_* when the head outputs of a call are read where they are by the *_h16 entries — all on the GPU, contiguous
     and of ONE dtype in {float16, bfloat16} — and 0 otherwise: mixed dtypes, non-contiguous levels, CPU tensors and fp32 keep

@@ -133,7 +133,7 @@ def _batched_call(who, symbol, variant, anchors, gt_bboxes, gt_labels, gt_offset
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f'{who}: anchors, gt_bboxes, gt_labels and gt_offsets must be on one device, got '
                            + ', '.join(sorted({str(t.device) for t in tensors})))
-    bx, gt = G.as_f32_nograd(anchors[..., :dim]), G.as_f32_nograd(gt)
+    bx, gt = G.boxes16(G.as_f32_nograd(anchors[..., :dim]), dim), G.boxes16(G.as_f32_nograd(gt), dim)
     gt_offsets = gt_offsets.contiguous()
     if gl is not None:
         gl = gl.to(torch.int64).contiguous()

@@ -121,6 +121,7 @@ def fused_assign(gt_bboxes, bboxes, gt_labels=None, variant='standard', pos_iou_
         raise RuntimeError('fused_assign runs on MI355X tensors (on the CPU: iou_calculator + assign_wrt_overlaps)')
     gt, bx = G.as_f32_nograd(gt_bboxes), G.as_f32_nograd(bboxes)
     k, n, dim = gt.size(0), bx.size(0), gt.size(1)
+    gt, bx = G.boxes16(gt, dim), G.boxes16(bx, dim)
     assert bx.size(1) == dim and dim in (4, 5) and k > 0 and n > 0
     dev = bx.device
     neg_lo, neg_hi = _thresholds(neg_iou_thr)

@@ -32,8 +32,8 @@ def bbox2delta(proposals, gt, means=None, stds=None):
     means = (0.,) * dim if means is None else means
     stds = (1.,) * dim if stds is None else stds
     G.require_hip(proposals, gt)
-    p = G.as_f32(proposals.detach()).reshape(-1, dim)
-    g = G.as_f32(gt.detach()).reshape(-1, dim)
+    p = G.boxes16(G.as_f32(proposals.detach()).reshape(-1, dim), dim)
+    g = G.boxes16(G.as_f32(gt.detach()).reshape(-1, dim), dim)
     out = torch.empty_like(p)
     n = p.size(0)
     if n:
@@ -57,7 +57,7 @@ class _DecodeFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         rois, deltas = ctx.saved_tensors
         means, stds, num_classes, dim, max_ratio, flags, ctr_clamp = ctx.cfg
-        g = G.as_f32(grad_out)
+        g = G.boxes16(G.as_f32(grad_out), dim)
         gd = torch.empty_like(deltas)
         G.call('sph2pob_coder_decode_bwd_f32', rois.device, G.ptr(rois), G.ptr(deltas), G.ptr(g), _host_vec(means, dim),
                _host_vec(stds, dim), G.ptr(gd), rois.size(0), num_classes, dim, max_ratio, flags, ctr_clamp,
@@ -79,8 +79,8 @@ def delta2bbox(rois, deltas, means=None, stds=None, max_shape=None, wh_ratio_cli
     num_classes = deltas.size(1) // dim
     assert rois.size(0) == num_bboxes and deltas.size(1) == num_classes * dim
     G.require_hip(rois, deltas)
-    r = G.as_f32(rois.detach())
-    d = G.as_f32(deltas)
+    r = G.boxes16(G.as_f32(rois.detach()), dim)
+    d = G.boxes16(G.as_f32(deltas), dim)
     flags = (1 if clip_border else 0) | (2 if add_ctr_clamp else 0)
     max_ratio = abs(math.log(wh_ratio_clip))
     return _DecodeFunction.apply(r, d, tuple(means), tuple(stds), num_classes, dim, float(max_ratio), flags,

@@ -109,14 +109,13 @@ def _delta_block(bbox_coder, wh_ratio_clip):
 
 
 def _priors_level(t, l, dim, points):
-    """A level's priors as contiguous fp32: (n, dim) anchors, or (n, 2) points on an 8-byte boundary (the kernel reads a point as
-    one 8-byte load)."""
+    """A level's priors as contiguous fp32: (n, dim) anchors (read one element at a time), or (n, 2) points on a 16-byte boundary
+    (the kernel reads a point as one 8-byte load without looking at the pointer: `_torch_glue.aligned16`)."""
     prior = G.as_f32_nograd(t[..., :2 if points else dim])
     if points:
         if prior.dim() != 2 or prior.size(1) != 2:
             raise ValueError(f'level {l}: points must be (n, 2), got {tuple(t.shape)}')
-        if prior.data_ptr() % 8:
-            prior = prior.clone()
+        prior = G.aligned16(prior)
     return prior
 
 

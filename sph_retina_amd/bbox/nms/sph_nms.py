@@ -43,6 +43,7 @@ def _variant_of(iou_calculator):
 def _nms_sorted(boxes_sorted, cls_sorted, iou_threshold, variant):
     """keep flags (uint8, K) for boxes sorted by (class, -score)."""
     k, dim = boxes_sorted.shape
+    boxes_sorted = G.boxes16(boxes_sorted, dim)
     lib = _lib.lib()
     dev = boxes_sorted.device
     keep = torch.empty((k,), dtype=torch.uint8, device=dev)
@@ -75,7 +76,7 @@ def _fused_nms(boxes, scores, idxs, iou_threshold, max_num, variant):
     lib = _lib.lib()
     k, dim = boxes.shape
     dev = boxes.device
-    b, sc = G.as_f32_nograd(boxes), G.as_f32_nograd(scores)
+    b, sc = G.boxes16(G.as_f32_nograd(boxes), dim), G.as_f32_nograd(scores)
     ix = None if idxs is None else idxs.to(torch.int64).contiguous()
     rows = max(min(int(max_num), k), 0)
     need = lib.sph2pob_batched_nms_workspace_bytes(k, dim)

@@ -46,7 +46,7 @@ def _sph2pob_iou_auxiliary(bboxes1, bboxes2, variant, mode, is_aligned, calculat
         # calculator='diff'): IoU = 1 - (IoU-mode loss element), gradients from the fused loss backward kernel
         from ..losses.sph2pob_iou_loss import sph2pob_iou_loss
         return 1.0 - sph2pob_iou_loss(bboxes1, bboxes2, mode='iou', reduction='none')
-    b1, b2 = G.as_f32_nograd(bboxes1), G.as_f32_nograd(bboxes2)
+    b1, b2 = G.boxes16(G.as_f32_nograd(bboxes1), dim), G.boxes16(G.as_f32_nograd(bboxes2), dim)
     if is_aligned:
         assert rows == cols
         out = torch.empty((rows,), dtype=torch.float32, device=b1.device)
@@ -115,7 +115,7 @@ class _Sph2PobTransformFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sph_gt, sph_pred, variant, rbb_edge, rbb_angle, jitter):
         n, dim = sph_gt.shape
-        b1, b2 = G.as_f32(sph_gt.detach()), G.as_f32(sph_pred.detach())
+        b1, b2 = G.boxes16(G.as_f32(sph_gt.detach()), dim), G.boxes16(G.as_f32(sph_pred.detach()), dim)
         o1 = torch.empty((n, 5), dtype=torch.float32, device=b1.device)
         o2 = torch.empty((n, 5), dtype=torch.float32, device=b1.device)
         if n:

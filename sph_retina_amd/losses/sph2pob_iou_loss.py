@@ -48,7 +48,7 @@ class _Sph2PobLossFunction(torch.autograd.Function):
     def forward(ctx, pred, target, weight, fam, tail, scale, reduce):
         G.require_hip(pred, target)
         n, dim = pred.shape
-        p, t = _f32c(pred), _f32c(target)
+        p, t = G.boxes16(_f32c(pred), dim), G.boxes16(_f32c(target), dim)
         w = _f32c(weight) if weight is not None else None
         wd = 0 if w is None else (1 if w.dim() == 1 else w.size(1))
         wp = w.data_ptr() if w is not None and n else None

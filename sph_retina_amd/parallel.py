@@ -110,6 +110,7 @@ class _HipAssignOp:
         G.require_hip(gt, shard)
         gt, shard = G.as_f32_nograd(gt), G.as_f32_nograd(shard)
         k, n, dim = gt.size(0), shard.size(0), gt.size(1)
+        gt, shard = G.boxes16(gt, dim), G.boxes16(shard, dim)   # finalize() reads the same two through the context
         dev = shard.device
         ws, state = G.assign_workspace(dev, lib.sph2pob_iou_assign_workspace_bytes(k, n), lib.sph2pob_iou_assign_state_bytes(k, n))
         keys = torch.empty((k,), dtype=torch.int64, device=dev)
