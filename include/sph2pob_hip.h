@@ -1278,6 +1278,49 @@ int sph2pob_roi_extract_bwd_f32(float* const* grad_feats, const int64_t* heights
                                 int64_t num_images, int64_t channels, const float* grad_out, int64_t rows, int box_dim, int pooled_h, int pooled_w,
                                 const void* prep, int zero_first, void* stream);
 
+/* ---- fused box loss of the R-CNN head on its per-class deltas: the regression half of SphShared2FCBBoxHead.loss ---------------
+ * Replaces (sphdet/models/heads/sph_rcnn_head.py:97-124) pos_inds = (labels >= 0) & (labels < C) ->
+ * bbox_pred.view(S, -1, dim)[pos_inds, labels[pos_inds]] (-> bbox_coder.decode with reg_decoded_bbox) -> loss_bbox(..., weights,
+ * avg_factor) and its backward — the index backward builds a zero tensor and scatters into it — by one pass over the Linear
+ * head's output where it is.  The arguments both entries share:
+ *   bbox_pred    (rows, num_slots * dim) f32: slot c of row r holds the deltas of class c
+ *   grad         NULL (forward only), or (rows, num_slots * dim): the gradient of out[0] for an upstream gradient of 1.  EVERY
+ *                element is written, exactly once: zeros, and a live row's dim values in its label's slot
+ *   rows         S >= 0;  num_slots: num_classes, or 1 (reg_class_agnostic: every class reads slot 0);  num_classes: C >= 1
+ *   labels       (rows) int64.  A row takes part when 0 <= label < C AND the family's weight rule holds; any other label
+ *                (background C, ignore -1, ...) makes a dead row whatever its weight is — the reference's pos_inds, not a clamp
+ *   targets      (rows, dim);  weight: NULL (all ones), (rows) when weight_dim == 1, (rows, dim) when weight_dim == dim
+ *   scale, avg_factor, out, workspace   as for sph2pob_bbox_loss_sum_f32; workspace holds
+ *                sph2pob_rcnn_loss_workspace_bytes(rows, num_slots, box_dim) bytes (0: shape not accepted), for either entry
+ * sph2pob_rcnn_delta_loss_sum_f32 — L1 / SmoothL1 on ENCODED deltas: beta, the element function, the weight rule (any component
+ *   != 0) and the product (scale_eff * w_k) * s_k are those of sph2pob_delta_loss_sum_f32.
+ * sph2pob_rcnn_bbox_loss_sum_f32 — decode + IoU-family loss: means_host ... eps, the weight rule (row mean != 0) and the product
+ *   ((scale_eff * w) * dL/dbox_k) * J_k are those of sph2pob_bbox_loss_sum_f32; the box a row's deltas are applied to is
+ *   rois[r * roi_stride + roi_offset + k], k < dim: (rows, 1 + dim) rois with the image index in front are read in place with
+ *   roi_stride = 1 + dim, roi_offset = 1; plain (rows, dim) boxes with (dim, 0).
+ * On the selected slots the gradient has the BITS sph2pob_delta_loss_sum_f32 / sph2pob_bbox_loss_sum_f32 give on the gathered
+ * rows as one flattened level (B = 1); out[0] differs from theirs by the order of the double partials only.  A dead row is NEVER
+ * READ in bbox_pred, targets or rois, and of a live row only the label's slot is: NaN or Inf elsewhere stays inert; a dead row's
+ * loss and whole gradient row are exact +0.0f.  Two launches; nothing is read back, nothing is allocated; capturable.  The
+ * gradient leaves in whole 16-byte stores when grad is 16-byte aligned and num_slots * dim is a multiple of 4, one element at a
+ * time with the same values otherwise.  rows == 0 writes out[0] = 0.
+ * Errors, checked in this order before anything is enqueued: the option checks of the flat sibling with its codes (delta: box_dim
+ * -> SPH2POB_ERR_DIM, weight_dim, beta -> SPH2POB_ERR_OPTION; bbox: loss_mode flags -> OPTION, box_dim -> DIM, loss mode,
+ * weight_dim, coder_flags, max_ratio -> OPTION); num_classes outside [1, 20 480], num_slots < 1 or neither 1 nor num_classes ->
+ * SPH2POB_ERR_OPTION; rows < 0, num_slots * dim > 4096 * 5, rows * num_slots * dim >= 2^31 - 4096 -> SPH2POB_ERR_SIZE;
+ * roi_offset < 0 or roi_stride < roi_offset + dim -> SPH2POB_ERR_SIZE; a NULL out or workspace, or bbox_pred, labels, targets
+ * or rois with rows -> SPH2POB_ERR_NULL.
+ */
+int64_t sph2pob_rcnn_loss_workspace_bytes(int64_t rows, int64_t num_slots, int box_dim);
+int sph2pob_rcnn_delta_loss_sum_f32(const float* bbox_pred, float* grad, int64_t rows, int64_t num_slots, int64_t num_classes, int box_dim,
+                                    const int64_t* labels, const float* targets, const float* weight, int weight_dim, float beta,
+                                    float scale, const float* avg_factor, float* out, void* workspace, void* stream);
+int sph2pob_rcnn_bbox_loss_sum_f32(const float* bbox_pred, float* grad, int64_t rows, int64_t num_slots, int64_t num_classes, int box_dim,
+                                   const int64_t* labels, const float* rois, int64_t roi_stride, int64_t roi_offset, const float* targets,
+                                   const float* weight, int weight_dim, const float* means_host, const float* stds_host, float max_ratio,
+                                   int coder_flags, float ctr_clamp, int loss_mode, float eps, float scale, const float* avg_factor,
+                                   float* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ from .iou import (SphOverlaps2D, sph2pob_efficient_iou, sph2pob_legacy_iou, sph2
 
 from .losses import (CrossEntropyLoss, FocalLoss, L1Loss, SmoothL1Loss, Sph2PobIoULoss, SphIoULoss, binary_cross_entropy, cross_entropy,  # noqa: F401,E402
                      sigmoid_focal_loss, sph_bbox_loss, sph_delta_loss, sph_focal_loss, sph_bce_loss, sph_gauss_bbox_loss,
-                     sph_point_bbox_loss, sph_softmax_loss)
+                     sph_point_bbox_loss, sph_softmax_loss, accuracy, sph_rcnn_bbox_loss, sph_rcnn_loss)
 from .bbox.nms import (DetBBoxes, SphNMS, multiclass_nms, sph_fcos_bboxes, sph_get_bboxes, sph_rcnn_bboxes, sph_softmax_bboxes,  # noqa: F401,E402
                        sph_softmax_scores, sph_test_bboxes)
 from .bbox.assigners import (AnchorTargets, PointTargets, RcnnTargets, SphMaxIoUAssigner, rcnn_bbox_pred, sph_anchor_targets,  # noqa: F401,E402

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_hip.so')
 HOST_LIB_PATH = os.path.join(LIB_DIR, 'libsph2pob_host.so')
 SOURCES = ['sph2pob_iou.hip', 'sph2pob_assign.hip', 'sph2pob_loss.hip', 'sph2pob_nms.hip', 'sph2pob_coder.hip', 'sph2pob_get_bboxes.hip',
            'sph2pob_focal.hip', 'sph2pob_bbox_loss.hip', 'sph2pob_delta_loss.hip', 'sph2pob_gauss_bbox_loss.hip', 'sph2pob_softmax.hip', 'sph2pob_softmax_bboxes.hip', 'sph2pob_sample.hip',
-           'sph2pob_point_targets.hip', 'sph2pob_point_bbox_loss.hip', 'sph2pob_bce_loss.hip', 'sph2pob_rcnn_targets.hip', 'sph2pob_rcnn_bboxes.hip', 'sph2pob_roi_extract.hip']
+           'sph2pob_point_targets.hip', 'sph2pob_point_bbox_loss.hip', 'sph2pob_bce_loss.hip', 'sph2pob_rcnn_targets.hip', 'sph2pob_rcnn_bboxes.hip', 'sph2pob_roi_extract.hip', 'sph2pob_rcnn_loss.hip']
 HOST_SOURCES = ['sph2pob_host.hip']
 HOST_FLAGS = ['--offload-arch=gfx950', '--cuda-host-only', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-pthread']
 
@@ -50,9 +50,10 @@ HOST_TWINS = ['sph2pob_iou_aligned_f32', 'sph2pob_iou_pairwise_f32', 'sph2pob_pl
               'sph2pob_softmax_loss_fwd_f32', 'sph2pob_softmax_loss_bwd_f32', 'sph2pob_softmax_scores_f32', 'sph2pob_softmax_bboxes_f32',
               'sph2pob_sample_targets_f32', 'sph2pob_point_targets_f32', 'sph2pob_point_coder_encode_f32', 'sph2pob_point_coder_decode_f32',
               'sph2pob_point_coder_decode_bwd_f32', 'sph2pob_fcos_bboxes_f32', 'sph2pob_point_bbox_loss_sum_f32', 'sph2pob_bce_loss_sum_f32',
-              'sph2pob_rcnn_targets_f32', 'sph2pob_rcnn_bboxes_f32', 'sph2pob_roi_extract_fwd_f32', 'sph2pob_roi_extract_bwd_f32']
+              'sph2pob_rcnn_targets_f32', 'sph2pob_rcnn_bboxes_f32', 'sph2pob_roi_extract_fwd_f32', 'sph2pob_roi_extract_bwd_f32',
+              'sph2pob_rcnn_delta_loss_sum_f32', 'sph2pob_rcnn_bbox_loss_sum_f32']
 HEADERS = ['sph2pob_device.hpp', 'sph2pob_loss.hpp', 'sph2pob_fast.hpp', 'sph2pob_unbiased.hpp', 'sph2pob_coder.hpp', 'sph2pob_get_bboxes.hpp', 'sph2pob_assign.hpp', 'sph2pob_head_loss.hpp', 'sph2pob_focal.hpp', 'sph2pob_bbox_loss.hpp', 'sph2pob_delta_loss.hpp', 'sph2pob_span_loss.hpp', 'sph2pob_gauss_bbox_loss.hpp', 'sph2pob_softmax.hpp', 'sph2pob_sample.hpp',
-           'sph2pob_point_targets.hpp', 'sph2pob_point_bbox_loss.hpp', 'sph2pob_bce_loss.hpp', 'sph2pob_rcnn_targets.hpp', 'sph2pob_rcnn_bboxes.hpp', 'sph2pob_roi_extract.hpp', 'sph2pob_class_levels.hpp', 'sph2pob_select.hpp', 'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
+           'sph2pob_point_targets.hpp', 'sph2pob_point_bbox_loss.hpp', 'sph2pob_bce_loss.hpp', 'sph2pob_rcnn_targets.hpp', 'sph2pob_rcnn_bboxes.hpp', 'sph2pob_roi_extract.hpp', 'sph2pob_rcnn_loss.hpp', 'sph2pob_class_levels.hpp', 'sph2pob_select.hpp', 'sph2pob_kernels_common.hpp', 'sph2pob_iou_entry.hpp', os.path.join('..', '..', 'include', 'sph2pob_hip.h')]
 # -fno-slp-vectorize: hipcc otherwise pairs scalar fp32 mul/add into v_pk_* (+ v_mov shuffles); packed fp32 issues at
 # half the rate of plain VALU on gfx950 (tools/ubench/valu_rate2.hip), measured 12 % slower on the dominant kernel
 # -amdgpu-kernarg-preload-count: gfx950 hands the first kernel arguments to a wave in SGPRs at launch instead of making
@@ -229,6 +230,16 @@ SIGNATURES = {
                                     _int, _int, _int, _int, ctypes.c_float] + [ctypes.c_void_p] * 5,
     # level tables (grad_feats, heights, widths, strides), num_levels, B, C, grad_out, rows, box_dim, pooled_h, pooled_w, prep, zero_first, stream
     'sph2pob_roi_extract_bwd_f32': [ctypes.c_void_p] * 4 + [_int, _i64, _i64, _c_f32p, _i64, _int, _int, _int, ctypes.c_void_p, _int, ctypes.c_void_p],
+    'sph2pob_rcnn_loss_workspace_bytes': [_i64, _i64, _int],
+    # bbox_pred, grad, rows, num_slots, num_classes, box_dim, labels, targets, weight, weight_dim, beta, scale, avg_factor, out,
+    # workspace, stream
+    'sph2pob_rcnn_delta_loss_sum_f32': [_c_f32p, _c_f32p, _i64, _i64, _i64, _int, ctypes.c_void_p, _c_f32p, _c_f32p, _int, ctypes.c_float,
+                                        ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p],
+    # bbox_pred, grad, rows, num_slots, num_classes, box_dim, labels, rois, roi_stride, roi_offset, targets, weight, weight_dim, means,
+    # stds, max_ratio, coder_flags, ctr_clamp, loss_mode, eps, scale, avg_factor, out, workspace, stream
+    'sph2pob_rcnn_bbox_loss_sum_f32': [_c_f32p, _c_f32p, _i64, _i64, _i64, _int, ctypes.c_void_p, _c_f32p, _i64, _i64, _c_f32p, _c_f32p, _int,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, _int, ctypes.c_float, _int, ctypes.c_float,
+                                       ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p],
     'sph2pob_coder_encode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int,
                                  ctypes.c_void_p],
     'sph2pob_coder_decode_f32': [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _int, _int,
@@ -256,7 +267,8 @@ _RESTYPES = {'sph2pob_loss_sum_workspace_floats': ctypes.c_int64, 'sph2pob_targe
              'sph2pob_softmax_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_softmax_bboxes_workspace_bytes': ctypes.c_int64,
              'sph2pob_sample_targets_workspace_bytes': ctypes.c_int64, 'sph2pob_point_targets_workspace_bytes': ctypes.c_int64,
              'sph2pob_point_bbox_loss_workspace_bytes': ctypes.c_int64, 'sph2pob_bce_loss_workspace_bytes': ctypes.c_int64,
-             'sph2pob_rcnn_targets_workspace_bytes': ctypes.c_int64, 'sph2pob_rcnn_bboxes_workspace_bytes': ctypes.c_int64}
+             'sph2pob_rcnn_targets_workspace_bytes': ctypes.c_int64, 'sph2pob_rcnn_bboxes_workspace_bytes': ctypes.c_int64,
+             'sph2pob_rcnn_loss_workspace_bytes': ctypes.c_int64}
 
 # Entry points of libsph2pob_host.so alone, `<name>_cpu`: the CPU statement of a route that has no device entry yet, so the name is
 # neither declared in include/sph2pob_hip.h nor exported by libsph2pob_hip.so.  name -> argtypes

@@ -31,6 +31,7 @@
 #include "sph2pob_bbox_loss.hpp"
 #include "sph2pob_gauss_bbox_loss.hpp"
 #include "sph2pob_delta_loss.hpp"
+#include "sph2pob_rcnn_loss.hpp"
 #include "sph2pob_softmax.hpp"
 #include "sph2pob_sample.hpp"
 #include "sph2pob_rcnn_targets.hpp"
@@ -1098,6 +1099,128 @@ int sph2pob_delta_loss_sum_f32_cpu(const void* const* bbox_preds, void* const* g
     double total = 0.0;
     if (L.rows > 0)
         total = box_dim == 4 ? delta_loss_rows<4>(L, targets, weight, wd, beta, k0) : delta_loss_rows<5>(L, targets, weight, wd, beta, k0);
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+}  // extern "C"
+
+// ---- fused box loss of the R-CNN head on its per-class deltas: the twins of sph2pob_rcnn_loss.hip on the same row rule
+// (slot_of, then the family's weight rule) and the row bodies of the two twins above ----
+namespace {
+namespace RL = sph2pob_rcnn_loss;
+
+// f(row, slot, g, acc) for every row whose label is a class; f returns whether the row takes part and then has added its weighted
+// losses to acc and left the DIM gradient values in g.  The row's W gradient floats are written once: zeros and, for a live row,
+// g in its slot.  One double partial per kFocalRows rows, added in order: the total does not move with the thread count.
+template <int DIM, class F>
+double rcnn_rows_sum(const RL::Shape& sh, const int64_t* labels, float* grad, F&& f) {
+    const int64_t rows = sh.rows, chunks = (rows + kFocalRows - 1) / kFocalRows;
+    std::vector<double> part((size_t)chunks, 0.0);
+    parallel_for(chunks, 4, [&](int64_t lo, int64_t hi) {
+        for (int64_t ch = lo; ch < hi; ch++) {
+            double acc = 0.0;
+            for (int64_t row = ch * kFocalRows; row < std::min(rows, (ch + 1) * kFocalRows); row++) {
+                float g[DIM];
+                int slot = RL::slot_of(labels[row], sh.classes, sh.slots);
+                if (slot >= 0 && !f(row, slot, g, acc)) slot = -1;
+                if (!grad) continue;
+                float* gr = grad + row * sh.w;
+                for (int c = 0; c < sh.w; c++) {
+                    const int k = c - slot * DIM;
+                    gr[c] = (slot >= 0 && k >= 0 && k < DIM) ? g[k] : 0.0f;
+                }
+            }
+            part[(size_t)ch] = acc;
+        }
+    });
+    double total = 0.0;
+    for (double v : part) total += v;
+    return total;
+}
+
+template <int DIM>
+double rcnn_delta_rows(const RL::Shape& sh, const float* pred, float* grad, const int64_t* labels, const float* targets, const float* weight,
+                       int wd, float beta, float k0) {
+    return rcnn_rows_sum<DIM>(sh, labels, grad, [&](int64_t row, int slot, float (&g)[DIM], double& acc) {
+        float wk[DIM];
+        if (!DL::row_weights<DIM>(weight, wd, false, row, wk)) return false;
+        const float* dp = pred + row * sh.w + slot * DIM;
+        for (int k = 0; k < DIM; k++) {
+            float lo1, sk;
+            DL::element(dp[k], targets[row * DIM + k], beta, lo1, sk);
+            acc += (double)(lo1 * wk[k]);
+            g[k] = (k0 * wk[k]) * sk;
+        }
+        return true;
+    });
+}
+
+template <int DIM, bool FAST>
+double rcnn_bbox_rows(const RL::Shape& sh, const float* pred, float* grad, const int64_t* labels, const float* rois, int64_t roi_stride,
+                      int64_t roi_offset, const float* targets, const float* weight, int wd, const C::Norm& nm, float max_ratio, int cflags,
+                      float ctr_clamp, const IouBody& body, float k0) {
+    return rcnn_rows_sum<DIM>(sh, labels, grad, [&](int64_t row, int slot, float (&g)[DIM], double& acc) {
+        const float w = element_weight<DIM>(weight, wd, row);
+        if (!(w != 0.0f)) return false;
+        const float* ap = rois + row * roi_stride + roi_offset;
+        const float* dp = pred + row * sh.w + slot * DIM;
+        float p[5], d[5], t[5], box[5] = {0, 0, 0, 0, 0}, jac[5], gx[5], gy[5];
+        for (int k = 0; k < 5; k++) {
+            p[k] = k < DIM ? ap[k] : 0.0f;
+            d[k] = k < DIM ? dp[k] : 0.0f;
+            t[k] = k < DIM ? targets[row * DIM + k] : 0.0f;
+        }
+        C::decode_one<DIM, true>(p, d, nm, max_ratio, cflags, ctr_clamp, box, jac);
+        const float lo1 = body.template eval<DIM, true, FAST>(box, t, nullptr, gx, gy);
+        acc += (double)(lo1 * w);
+        const float gw = k0 * w;
+        for (int k = 0; k < DIM; k++) g[k] = (gw * gx[k]) * jac[k];
+        return true;
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int sph2pob_rcnn_delta_loss_sum_f32_cpu(const float* bbox_pred, float* grad, int64_t rows, int64_t num_slots, int64_t num_classes,
+                                        int box_dim, const int64_t* labels, const float* targets, const float* weight, int weight_dim,
+                                        float beta, float scale, const float* avg_factor, float* out, void* workspace, void*) {
+    if (int rc = DL::check_options(box_dim, weight, weight_dim, beta)) return rc;
+    RL::Shape sh;
+    if (int rc = RL::make_shape(rows, num_slots, num_classes, box_dim, &sh)) return rc;
+    if (int rc = RL::check_tensors(sh, bbox_pred, labels, targets, false, nullptr, 0, 0, box_dim, out, workspace)) return rc;
+    const float k0 = RL::effective_scale(scale, avg_factor);
+    const int wd = weight ? weight_dim : 0;
+    double total = 0.0;
+    if (sh.rows > 0)
+        total = box_dim == 4 ? rcnn_delta_rows<4>(sh, bbox_pred, grad, labels, targets, weight, wd, beta, k0)
+                             : rcnn_delta_rows<5>(sh, bbox_pred, grad, labels, targets, weight, wd, beta, k0);
+    out[0] = (float)(total * (double)k0);
+    return SPH2POB_OK;
+}
+
+int sph2pob_rcnn_bbox_loss_sum_f32_cpu(const float* bbox_pred, float* grad, int64_t rows, int64_t num_slots, int64_t num_classes, int box_dim,
+                                       const int64_t* labels, const float* rois, int64_t roi_stride, int64_t roi_offset,
+                                       const float* targets, const float* weight, int weight_dim, const float* means_host,
+                                       const float* stds_host, float max_ratio, int coder_flags, float ctr_clamp, int loss_mode, float eps,
+                                       float scale, const float* avg_factor, float* out, void* workspace, void*) {
+    if (int rc = BL::check_options(box_dim, weight, weight_dim, max_ratio, coder_flags, loss_mode)) return rc;
+    RL::Shape sh;
+    if (int rc = RL::make_shape(rows, num_slots, num_classes, box_dim, &sh)) return rc;
+    if (int rc = RL::check_tensors(sh, bbox_pred, labels, targets, true, rois, roi_stride, roi_offset, box_dim, out, workspace)) return rc;
+    const C::Norm nm = C::make_norm(means_host, stds_host, box_dim);
+    const float k0 = RL::effective_scale(scale, avg_factor);
+    const bool fast = !(loss_mode & SPH2POB_FLAG_REFERENCE_ORDER);
+    const IouBody body{loss_mode & 0xff, eps};
+    double total = 0.0;
+    if (sh.rows > 0) {
+#define SPH_RCNN_ROWS(D, F) rcnn_bbox_rows<D, F>(sh, bbox_pred, grad, labels, rois, roi_stride, roi_offset, targets, weight, weight_dim, nm, \
+                                                 max_ratio, coder_flags, ctr_clamp, body, k0)
+        if (box_dim == 4) total = fast ? SPH_RCNN_ROWS(4, true) : SPH_RCNN_ROWS(4, false);
+        else total = fast ? SPH_RCNN_ROWS(5, true) : SPH_RCNN_ROWS(5, false);
+#undef SPH_RCNN_ROWS
+    }
     out[0] = (float)(total * (double)k0);
     return SPH2POB_OK;
 }

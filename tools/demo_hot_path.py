@@ -106,7 +106,7 @@ def run(num_gt=64, num_classes=37, backend='sph2pob_standard_iou', nms_calculato
 
 def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sph2pob_standard_iou', seed=0, reps=1, fused_reg=False, base_config=False,
               train_cfg=None, loss_bbox=None, softmax_head=False, rpn_cfg=None, rpn_seed=0, fcos_cfg=None, rcnn_cfg=None, rcnn_seed=0,
-              rcnn_proposals=1000, rcnn_decoded=False, roi_extract=False, roi_channels=256):
+              rcnn_proposals=1000, rcnn_decoded=False, roi_extract=False, roi_channels=256, fused_losses=False):
     """The training half of `run()` for a minibatch (AnchorHead.get_targets + loss_single over the images): anchors x the
     images' ragged GT -> sph_anchor_targets -> decode -> Sph2PobIoULoss(ciou) and the classification loss on the head's NCHW
     logits (sph_focal_loss), both with the device avg_factor -> backward.  `fused_reg=True` takes the regression half through
@@ -132,12 +132,16 @@ def run_batch(counts=(64, 1, 0, 17, 64, 3, 128, 33), num_classes=37, backend='sp
     reference's `train_cfg.rcnn` with its RandomSampler(add_gt_as_proposals=True); `rcnn_proposals` padded proposals per image in the
     layout of the batched inference entries, `rcnn_seed` a Python int or a () int64 device tensor, `rcnn_decoded`: the box loss on the
     decoded boxes (reg_decoded_bbox=True) instead of on the raw deltas; `roi_extract=True`: the step starts from random FPN levels
-    (`sph_roi_extract` and two stand-in Linear heads in place of the random head outputs)."""
+    (`sph_roi_extract` and two stand-in Linear heads in place of the random head outputs); `fused_losses=True`: the head's `loss()` as
+    the one call `sph_rcnn_loss` — the box loss reads the (S, C * 4) head output in place instead of the gather."""
     dev = 'cuda'
+    if fused_losses and rcnn_cfg is None:
+        raise ValueError('fused_losses routes the two-stage step (rcnn_cfg) through sph_rcnn_loss')
     if rcnn_cfg is not None:
         if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None or fcos_cfg is not None:
             raise ValueError('rcnn_cfg is a step of its own: sph_rcnn_targets + cross_entropy + the box loss on the gathered predictions')
-        return run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed, rcnn_proposals, rcnn_decoded, dev, roi_extract=roi_extract, channels=roi_channels)
+        return run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed, rcnn_proposals, rcnn_decoded, dev, roi_extract=roi_extract, channels=roi_channels,
+                              fused_losses=fused_losses)
     if fcos_cfg is not None:
         if train_cfg is not None or loss_bbox is not None or fused_reg or base_config or softmax_head or rpn_cfg is not None:
             raise ValueError('fcos_cfg is a step of its own: sph_fcos_targets + sph_focal_loss + Sph2PobIoULoss on the point decode + BCE')
@@ -337,7 +341,8 @@ def roi_heads(channels, num_classes, seed=0, device='cuda'):
     return torch.nn.Linear(fan_in, num_classes + 1).to(device), torch.nn.Linear(fan_in, num_classes * 4).to(device)
 
 
-def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=1000, decoded=False, dev='cuda', roi_extract=False, channels=256):
+def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=1000, decoded=False, dev='cuda', roi_extract=False, channels=256,
+                   fused_losses=False):
     """`run_batch(rcnn_cfg=...)`: SphStandardRoIHead._bbox_forward_train without the RoI extractor — proposals (`dets, num_dets`, read in
     place) and concatenated GT -> `sph_rcnn_targets` -> flat `cross_entropy` on (S, C + 1) logits with `avg_factor=t.avg_factor`, and
     the box loss on `rcnn_bbox_pred`'s gather over all S rows with `avg_factor=t.num_samples`: L1 on the raw deltas, or with
@@ -345,7 +350,9 @@ def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=100
     step, backward included, is captured into a graph and replayed: nothing is read back.
     `roi_extract=True`: the step starts from random FPN levels instead of random head outputs — `sph_roi_extract` on `t.rois` as they
     are, then two stand-in Linear heads give `cls_score` / `bbox_pred`; the captured graph spans features -> losses -> the gradients
-    of the levels and of the heads."""
+    of the levels and of the heads.
+    `fused_losses=True`: `_rcnn_losses` is `sph_rcnn_loss` — the same cross-entropy node, and the box loss as ONE fused node on
+    `bbox_pred` as the head wrote it (the reference's row rule, the (S, C * 4) gradient written once) in place of gather -> (decode) -> loss."""
     g = torch.Generator().manual_seed(seed)
     gts, labels = [], []
     for k in counts:
@@ -379,11 +386,17 @@ def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=100
         return _rcnn_losses(t, cls_score, bbox_pred)
 
     def _rcnn_losses(t, cls_score, bbox_pred):
-        loss_cls = S.cross_entropy(cls_score, t.labels, t.label_weights, avg_factor=t.avg_factor)
-        picked = S.rcnn_bbox_pred(bbox_pred, t.labels, num_classes, 4, False)
-        if decoded:
+        if fused_losses:
+            out = S.sph_rcnn_loss(cls_score, bbox_pred, t, num_classes=num_classes, bbox_coder=coder, reg_decoded_bbox=decoded,
+                                  loss_bbox=dict(type='Sph2PobIoULoss', mode='iou') if decoded else dict(type='L1Loss'))
+            loss_cls, loss_box = out['loss_cls'], out['loss_bbox']
+        elif decoded:
+            loss_cls = S.cross_entropy(cls_score, t.labels, t.label_weights, avg_factor=t.avg_factor)
+            picked = S.rcnn_bbox_pred(bbox_pred, t.labels, num_classes, 4, False)
             loss_box = loss_iou(coder.decode(t.rois[:, 1:].contiguous(), picked), t.bbox_targets, t.bbox_weights, avg_factor=t.num_samples)
         else:
+            loss_cls = S.cross_entropy(cls_score, t.labels, t.label_weights, avg_factor=t.avg_factor)
+            picked = S.rcnn_bbox_pred(bbox_pred, t.labels, num_classes, 4, False)
             loss_box = loss_l1(picked, t.bbox_targets, t.bbox_weights, avg_factor=t.num_samples)
         grads = torch.autograd.grad(loss_cls + loss_box, leaves)
         if roi_extract:
@@ -407,7 +420,7 @@ def run_rcnn_batch(counts, num_classes, seed, reps, rcnn_cfg, rcnn_seed=0, m=100
     torch.cuda.synchronize()
     out = {'rcnn': True, 'images': images, 'proposals': m, 'num_dets': num_dets.tolist(), 'num_gt': list(counts), 'num': num,
            'num_pos': t.num_pos.tolist(), 'num_neg': t.num_neg.tolist(), 'avg_factor': float(t.avg_factor), 'num_samples': float(t.num_samples),
-           'loss_cls': float(loss_cls), 'loss_bbox': float(loss_box), 'decoded': decoded,
+           'loss_cls': float(loss_cls), 'loss_bbox': float(loss_box), 'decoded': decoded, 'fused_losses': fused_losses,
            'grads_finite': bool(torch.isfinite(g_cls).all()) and bool(torch.isfinite(g_box).all()),
            'cls_grad_rows': int((g_cls.abs().sum(1) > 0).sum()), 'box_grad_rows': int((g_box.abs().sum(1) > 0).sum()),
            'graph_replay_ms': (time.perf_counter() - t0) / reps * 1e3}
