@@ -24,7 +24,7 @@ from ... import _lib
 from ... import _torch_glue as G
 from .anchor_targets import _PER_IMAGE, _concat
 from .max_iou_assigner import _FUSED_BACKENDS, _thresholds
-from .sample_targets import _sampler_options
+from .sample_targets import _draw_arguments, _sampler_options
 from .train_targets import _PER_PAIR_BACKENDS, _build_assigner, _refuse_backend
 
 _WHO = 'sph_rcnn_targets'
@@ -166,21 +166,7 @@ def sph_rcnn_targets(proposals, gt_bboxes, gt_labels, gt_offsets=None, *, num_pr
         raise ValueError('k_max must be >= 0')
     C = k_max + M
 
-    seed_dev = None
-    if isinstance(seed, torch.Tensor):
-        if seed.dtype != torch.int64 or seed.dim() != 0 or seed.device != dev:
-            raise ValueError(f'{_WHO}: a tensor seed must be a () int64 tensor on {dev}')
-        seed_dev, seed = seed, 0
-    else:
-        seed = int(seed) & 0xffffffffffffffff
-        seed = seed - (1 << 64) if seed >> 63 else seed
-    if ranks is not None:
-        if ranks.shape != (B, C) or ranks.device != dev or ranks.dtype.is_floating_point:
-            raise ValueError(f'{_WHO}: ranks must be a ({B}, {C}) integer tensor on {dev} (k_max + M candidate slots per image)')
-        if ranks.dtype != torch.int32:   # the 32 bits of a value in [0, 2^32): what the kernels read as uint32
-            r64 = ranks.to(torch.int64)
-            ranks = torch.where(r64 >= 1 << 31, r64 - (1 << 32), r64).to(torch.int32)
-        ranks = ranks.contiguous()
+    seed, seed_dev, ranks = _draw_arguments(_WHO, seed, ranks, (B, C), dev, slots=' (k_max + M candidate slots per image)')
     means = stds = None
     if not reg_decoded_bbox:
         if bbox_coder is None or getattr(bbox_coder, 'box_dim', None) != dim:

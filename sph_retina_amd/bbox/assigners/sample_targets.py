@@ -54,6 +54,29 @@ def _sampler_options(sampler, who=_WHO, with_add_gt=False):
     return int(num), int(num * pos_fraction), float(ub)
 
 
+def _draw_arguments(who, seed, ranks, ranks_shape, dev, slots=''):
+    """The draw of a sampling entry -> (seed, seed_dev, ranks) as `G.call` takes them.  `seed`: a () int64 tensor on `dev` (then
+    seed_dev, with seed 0), or a Python int taken modulo 2^64 as a signed 64-bit value.  `ranks`: None, or an integer tensor of
+    `ranks_shape` on `dev`, returned as the contiguous int32 tensor whose 32 bits the kernels read as uint32.  `slots`: what the
+    caller's message adds about its ranks' shape."""
+    seed_dev = None
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or seed.dim() != 0 or seed.device != dev:
+            raise ValueError(f'{who}: a tensor seed must be a () int64 tensor on {dev}')
+        seed_dev, seed = seed, 0
+    else:
+        seed = int(seed) & 0xffffffffffffffff
+        seed = seed - (1 << 64) if seed >> 63 else seed
+    if ranks is not None:
+        if ranks.shape != tuple(ranks_shape) or ranks.device != dev or ranks.dtype.is_floating_point:
+            raise ValueError(f'{who}: ranks must be a ({", ".join(str(v) for v in ranks_shape)}) integer tensor on {dev}{slots}')
+        if ranks.dtype != torch.int32:   # the 32 bits of a value in [0, 2^32): what the kernels read as uint32
+            r64 = ranks.to(torch.int64)
+            ranks = torch.where(r64 >= 1 << 31, r64 - (1 << 32), r64).to(torch.int32)
+        ranks = ranks.contiguous()
+    return seed, seed_dev, ranks
+
+
 def sph_sample_targets(targets, *, sampler, num_classes, seed, ranks=None, inplace=False):
     """Sample `targets` (an `AnchorTargets` of `sph_anchor_targets` / `sph_train_targets`) as the module docstring says.
 
@@ -75,21 +98,7 @@ def sph_sample_targets(targets, *, sampler, num_classes, seed, ranks=None, inpla
     if any(not f.is_contiguous() for f in fields) or t.labels.dtype != torch.int64 or t.gt_inds.dtype != torch.int64 or \
             any(f.dtype != torch.float32 for f in fields[2:]) or t.bbox_targets.shape != (B, n, dim) or t.bbox_weights.shape != (B, n, dim):
         raise ValueError(f'{_WHO}: targets must hold the contiguous int64 / fp32 tensors sph_anchor_targets writes')
-    seed_dev = None
-    if isinstance(seed, torch.Tensor):
-        if seed.dtype != torch.int64 or seed.dim() != 0 or seed.device != dev:
-            raise ValueError(f'{_WHO}: a tensor seed must be a () int64 tensor on {dev}')
-        seed_dev, seed = seed, 0
-    else:
-        seed = int(seed) & 0xffffffffffffffff
-        seed = seed - (1 << 64) if seed >> 63 else seed
-    if ranks is not None:
-        if ranks.shape != (B, n) or ranks.device != dev or ranks.dtype.is_floating_point:
-            raise ValueError(f'{_WHO}: ranks must be a ({B}, {n}) integer tensor on {dev}')
-        if ranks.dtype != torch.int32:   # the 32 bits of a value in [0, 2^32): what the kernels read as uint32
-            r64 = ranks.to(torch.int64)
-            ranks = torch.where(r64 >= 1 << 31, r64 - (1 << 32), r64).to(torch.int32)
-        ranks = ranks.contiguous()
+    seed, seed_dev, ranks = _draw_arguments(_WHO, seed, ranks, (B, n), dev)
     f32, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
     if inplace:
         outs = fields[1:]

@@ -10,37 +10,15 @@
 
 namespace {
 
-using sph2pob_assign::Rule;
-using sph2pob_assign::threshold_index;
+using namespace sph2pob_assign;   // the rule, the image's rows and the packed keys
 static_assert(kBlock == sph2pob_assign::kTile, "one thread per column of a tile");
 
 // a run-time flag as a compile-time one: the launchers pick a kernel's boolean template arguments through generic lambdas
 template <class F>
 auto with_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 
-// ---- packed keys: order-preserving, for max / first-argmax reductions with one atomic.  (float bits mapped to an unsigned order)
-// << 32 | an index that DEcreases with the position, so that the maximum key is the maximum value and, among equal values, the
-// SMALLEST index — what torch.max(dim) returns.  IoUs are >= +0 (the kernels never produce -0) or -1 for ignored columns. ----
-__device__ __forceinline__ unsigned ordered_bits(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// the column key (and the matrix route's row key): low word = ~index
-__device__ __forceinline__ unsigned long long pack_max_key(float v, int64_t j) {
-    return ((unsigned long long)ordered_bits(v) << 32) | (unsigned)(0xffffffffu - (unsigned)j);
-}
-__device__ __forceinline__ int64_t max_key_index(unsigned long long key) { return (int64_t)(0xffffffffu - (unsigned)key); }
-// the fused assigner's row key keeps bit 0 of the low word free for a "this value occurs at more than one column of the
-// tile" flag: low = (0x7fffffff - index) << 1 | flag (indices < 2^31)
-__device__ __forceinline__ unsigned long long pack_row_key(float v, unsigned j) {
-    return ((unsigned long long)ordered_bits(v) << 32) | ((0x7fffffffu - j) << 1);
-}
-__device__ __forceinline__ unsigned row_key_index(unsigned long long key) { return 0x7fffffffu - ((unsigned)key >> 1); }
-__device__ __forceinline__ float unpack_max_val(unsigned long long key) {
-    unsigned u = (unsigned)(key >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return __uint_as_float(u);
-}
+// ---- packed keys (ordered_bits, the column and the row key, unpack_max_val, wave_max_*: sph2pob_assign.hpp): what only the fused
+// route adds ----
 // what a row holds when no tile contributed (no ignore mask: IoU 0 at the shard's first column)
 __device__ __forceinline__ unsigned long long row_floor(bool has_ignore, unsigned col_offset) {
     return has_ignore ? 0ull : pack_row_key(0.0f, col_offset);
@@ -50,22 +28,6 @@ __device__ __forceinline__ unsigned long long acc_to_key(unsigned long long a, u
 // keys travel between ranks as SIGNED 64-bit integers (torch.distributed has no unsigned MAX): top bit flipped
 __device__ __forceinline__ long long key_to_signed(unsigned long long k) { return (long long)(k ^ 0x8000000000000000ull); }
 __device__ __forceinline__ unsigned long long key_from_signed(long long k) { return (unsigned long long)k ^ 0x8000000000000000ull; }
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        unsigned long long w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 // ---- one layout of the fused routes' two buffers, per image, in 64-bit words.
 // workspace: col_part[chunks][n], then row_part[k][tiles] (what pairwise_compact_tile writes; overwritten by every call).
@@ -633,15 +595,6 @@ __global__ __launch_bounds__(kBlock) void assign_fused_finalize_kernel(const flo
 // the target construction of mmdet's AnchorHead._get_targets_single (anchor_head.py:254-285, PseudoSampler) as the finalize
 // pass's epilogue.  Two launches for B images; every image owns a slice of the workspace and of the state, laid out for k_max
 // rows whatever its own count (Layout). ----
-// rows of image b in the concatenated GT: offsets clamped to [0, K], the count to [0, k_max] (later rows are not assigned)
-struct ImageRows { int64_t lo; int k; };
-__device__ __forceinline__ ImageRows image_rows(const int64_t* __restrict__ gt_offsets, int b, int64_t K, int k_max) {
-    int64_t lo = gt_offsets[b], hi = gt_offsets[b + 1];
-    lo = lo < 0 ? 0 : (lo > K ? K : lo);
-    hi = hi < 0 ? 0 : (hi > K ? K : hi);
-    const int64_t k = hi - lo;
-    return ImageRows{lo, k < 0 ? 0 : (k > k_max ? k_max : (int)k)};
-}
 // an image's rows in chunks of equal size, at most rows_per_wg each
 __device__ __forceinline__ int image_chunks(int k, int rows_per_wg) { return (k + rows_per_wg - 1) / rows_per_wg; }
 
@@ -719,7 +672,7 @@ __global__ __launch_bounds__(kBlock) void anchor_targets_pairwise_any_kernel(con
         const unsigned long long eq = __builtin_amdgcn_ballot_w64(ob == wm);
         if (lane == 0 && wm != 0u) {   // wm == 0: a wave past n
             const unsigned col = (unsigned)(jraw + __builtin_ctzll(eq));
-            const unsigned long long old = atomicMax(&row_key[i], ((unsigned long long)wm << 32) | ((0x7fffffffu - col) << 1));
+            const unsigned long long old = atomicMax(&row_key[i], pack_row_key_bits(wm, col));
             if (__popcll(eq) > 1 || (unsigned)(old >> 32) == wm) row_tie[i] = 1;
         }
     }

@@ -1,6 +1,7 @@
 // Shared by the assigner unit (sph2pob_assign.hip: the matrix epilogue, the fused route, the batched anchor targets) and its CPU
 // twins (sph2pob_host.hip): the assignment rule and its threshold step, the target row of one anchor, and the argument checks, so
-// that a CPU tensor gets the rule, the targets and the checks a device tensor gets.
+// that a CPU tensor gets the rule, the targets and the checks a device tensor gets.  Also here, once, for every target unit
+// (sph2pob_rcnn_targets.{hpp,hip} too): the GT rows of an image (image_rows) and, device only, the packed max / first-argmax keys.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,6 +53,63 @@ SPHA_DEV TargetRow target_row(int64_t a, const float* anchor, const float* g, co
     }
     return r;
 }
+
+// rows of image b in the concatenated GT (K rows), as the batched anchor targets, the R-CNN stage targets and their twins take
+// them: offsets clamped to [0, K], the count to [0, k_max] (later rows are not assigned)
+// (sph2pob_point_targets.hpp::image_rows is a DIFFERENT rule: an out-of-range begin gives no rows there, not a clamp)
+struct ImageRows { int64_t lo; int k; };
+SPHA_DEV ImageRows image_rows(const int64_t* gt_offsets, int64_t b, int64_t K, int64_t k_max) {
+    int64_t lo = gt_offsets[b], hi = gt_offsets[b + 1];
+    lo = lo < 0 ? 0 : (lo > K ? K : lo);
+    hi = hi < 0 ? 0 : (hi > K ? K : hi);
+    const int64_t k = hi - lo;
+    return ImageRows{lo, (int)(k < 0 ? 0 : (k > k_max ? k_max : k))};
+}
+
+#if defined(__HIPCC__)
+// ---- packed keys: order-preserving, for max / first-argmax reductions with one atomic.  (float bits mapped to an unsigned order)
+// << 32 | an index that DEcreases with the position, so that the maximum key is the maximum value and, among equal values, the
+// SMALLEST index — what torch.max(dim) returns.  IoUs are >= +0 (the kernels never produce -0) or -1 for ignored columns; a NaN
+// sorts above every number.  `*_bits`: from a value's ordered bits (a wave has reduced them already). ----
+__device__ __forceinline__ unsigned ordered_bits(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// the column key (and the matrix route's row key): low word = ~index
+__device__ __forceinline__ unsigned long long pack_max_key_bits(unsigned ordered, unsigned j) {
+    return ((unsigned long long)ordered << 32) | (unsigned)(0xffffffffu - j);
+}
+__device__ __forceinline__ unsigned long long pack_max_key(float v, int64_t j) { return pack_max_key_bits(ordered_bits(v), (unsigned)j); }
+__device__ __forceinline__ int64_t max_key_index(unsigned long long key) { return (int64_t)(0xffffffffu - (unsigned)key); }
+// the fused assigner's row key keeps bit 0 of the low word free for a "this value occurs at more than one column of the
+// tile" flag: low = (0x7fffffff - index) << 1 | flag (indices < 2^31)
+__device__ __forceinline__ unsigned long long pack_row_key_bits(unsigned ordered, unsigned j) {
+    return ((unsigned long long)ordered << 32) | ((0x7fffffffu - j) << 1);
+}
+__device__ __forceinline__ unsigned long long pack_row_key(float v, unsigned j) { return pack_row_key_bits(ordered_bits(v), j); }
+__device__ __forceinline__ unsigned row_key_index(unsigned long long key) { return 0x7fffffffu - ((unsigned)key >> 1); }
+__device__ __forceinline__ float unpack_max_val(unsigned long long key) {
+    unsigned u = (unsigned)(key >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        unsigned long long w = __shfl_xor(v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned w = __shfl_xor(v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+#endif
 
 // ---- argument checks, in the documented order.  `rc` is what check_common(box_dim, variant, edge, 0) answered
 // (sph2pob_iou_entry.hpp, next to dispatch()). ----

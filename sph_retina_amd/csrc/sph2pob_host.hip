@@ -474,8 +474,8 @@ int anchor_targets_cpu(const float* anchors, int64_t n, const float* gt, const i
     std::vector<int64_t> argmax(n), gt_argmax;
     int64_t total = 0;
     for (int64_t b = 0; b < num_images; b++) {
-        const int64_t lo = std::min(std::max<int64_t>(gt_offsets[b], 0), num_gt), hi = std::min(std::max<int64_t>(gt_offsets[b + 1], 0), num_gt);
-        const int64_t k = std::min(std::max<int64_t>(hi - lo, 0), k_max);
+        const A::ImageRows im = A::image_rows(gt_offsets, b, num_gt, k_max);
+        const int64_t lo = im.lo, k = im.k;
         int64_t* gi = assigned_gt_inds + b * n;
         float* mo = max_overlaps + b * n;
         const float* gt_b = gt + lo * dim;
@@ -1472,8 +1472,8 @@ int sph2pob_rcnn_bboxes_f32_cpu(const float* rois, const int64_t* num_rois, cons
 
 }  // extern "C"
 
-// ---- random sampling of anchor targets: the rank and the sizes of the kernels (sph2pob_sample.hpp); the cut of a side by
-// sph2pob_select.hpp's host_cut instead of the radix select (the workspace is not used) ----
+// ---- random sampling of anchor targets: sph2pob_sample.hpp's host_select per image (the kernels' rank and sizes; the cut of a side
+// by sph2pob_select.hpp's host_cut instead of the radix select), then the rows applied in place (the workspace is not used) ----
 extern "C" {
 
 int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, int64_t n, int box_dim, const int64_t* labels_in,
@@ -1486,27 +1486,15 @@ int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, i
     if (int rc = SA::check_shape(num_images, n, box_dim, num_expected_pos, num, neg_pos_ub)) return rc;
     if (!gt_inds || !labels_in || !label_weights_in || !bbox_targets_in || !bbox_weights_in || !labels || !label_weights || !bbox_targets ||
         !bbox_weights || !sample_flags || !num_pos || !num_neg || !avg_factor || !avg_factor_pos) return SPH2POB_ERR_NULL;
-    const uint64_t sd = (uint64_t)(seed_device ? seed_device[0] : seed);
+    const uint64_t sd = SA::seed_of(seed, seed_device);
     parallel_for(num_images, 1, [&](int64_t lo, int64_t hi) {
         std::vector<uint32_t> rank((size_t)n);
         std::vector<uint32_t> scratch;
         for (int64_t b = lo; b < hi; b++) {
             const int64_t* g = gt_inds + b * n;
-            int64_t count[2] = {0, 0}, k[2];
-            for (int64_t i = 0; i < n; i++) {
-                const int c = SA::side_of(g[i]);
-                if (c == SA::IGNORED) continue;
-                count[c]++;
-                rank[(size_t)i] = ranks ? ranks[b * n + i] : SA::row_rank(sd, (uint32_t)b, (uint32_t)i);
-            }
-            SA::sample_sizes(count[SA::POS], count[SA::NEG], num_expected_pos, num, neg_pos_ub, &k[SA::POS], &k[SA::NEG]);
-            SA::Pick pick[2];
-            for (int side = 0; side < 2; side++) {
-                pick[side] = SA::Pick{{0u, 0}, k[side]};
-                sph2pob_select::host_cut<false>(n, k[side], [&](int64_t i, uint32_t* key) { *key = rank[(size_t)i]; return SA::side_of(g[i]) == side; },
-                                                scratch, &pick[side].cut);
-            }
-            num_pos[b] = k[SA::POS]; num_neg[b] = k[SA::NEG];
+            const auto pick = SA::host_select([&](int64_t i) { return g[i]; }, n, b, ranks ? ranks + b * n : nullptr, sd, num_expected_pos, num,
+                                              neg_pos_ub, rank, scratch);
+            num_pos[b] = pick[SA::POS].k; num_neg[b] = pick[SA::NEG].k;
             for (int64_t i = 0; i < n; i++) {
                 const int64_t r = b * n + i;
                 const int c = SA::side_of(g[i]);
@@ -1537,8 +1525,8 @@ int sph2pob_sample_targets_f32_cpu(const int64_t* gt_inds, int64_t num_images, i
 }  // extern "C"
 
 // ---- R-CNN stage targets on per-image proposals: sph2pob_rcnn_targets_f32 after its checks (sph2pob_rcnn_targets.hpp).  Per image
-// the pairwise and the assign twin above on its first n_b proposals, the candidate list, the sampler's rank, sizes and cut, and the
-// kernels' table rows in the kernels' order (the workspace is not used) ----
+// the pairwise and the assign twin above on its first n_b proposals, the candidate list, the sampler's host_select on it, and the
+// kernels' table rows compacted in the kernels' order (the workspace is not used) ----
 extern "C" {
 
 int sph2pob_rcnn_targets_f32_cpu(const float* proposals, const int64_t* num_proposals, int64_t num_images, int64_t m, int64_t row_stride,
@@ -1562,14 +1550,14 @@ int sph2pob_rcnn_targets_f32_cpu(const float* proposals, const int64_t* num_prop
     const auto sampled_row = dim == 4 ? (encode ? RC::write_sampled<4, true> : RC::write_sampled<4, false>)
                                       : (encode ? RC::write_sampled<5, true> : RC::write_sampled<5, false>);
     const auto padding_row = dim == 4 ? RC::write_padding<4> : RC::write_padding<5>;
-    const uint64_t sd = (uint64_t)(seed_device ? seed_device[0] : seed);
+    const uint64_t sd = SA::seed_of(seed, seed_device);
     const int64_t C = k_max + m;
     std::vector<float> boxes, ov, max_ov, gt_max;
     std::vector<int64_t> cand, argmax, gt_argmax;
     std::vector<uint32_t> rank((size_t)C), scratch;
     int64_t total = 0;
     for (int64_t b = 0; b < num_images; b++) {
-        const RC::ImageRows im = RC::image_rows(gt_offsets, b, num_gt, k_max);
+        const sph2pob_assign::ImageRows im = sph2pob_assign::image_rows(gt_offsets, b, num_gt, k_max);
         const int64_t k = im.k, n = RC::image_proposals(num_proposals, b, m), koff = RC::gt_candidates(add_gt, k), count = koff + n;
         const float* gt_b = gt + im.lo * dim;
         const int64_t* labels_b = gt_labels ? gt_labels + im.lo : nullptr;
@@ -1588,22 +1576,10 @@ int sph2pob_rcnn_targets_f32_cpu(const float* proposals, const int64_t* num_prop
                                             nullptr, nullptr);
             if (rc) return rc;
         }
-        int64_t sides[2] = {0, 0}, kk[2];
-        for (int64_t c = 0; c < count; c++) {
-            const int s = SA::side_of(cand[(size_t)c]);
-            if (s == SA::IGNORED) continue;
-            sides[s]++;
-            rank[(size_t)c] = ranks ? ranks[b * C + c] : SA::row_rank(sd, (uint32_t)b, (uint32_t)c);
-        }
-        SA::sample_sizes(sides[SA::POS], sides[SA::NEG], num_expected_pos, num, neg_pos_ub, &kk[SA::POS], &kk[SA::NEG]);
-        SA::Pick pick[2];
-        for (int side = 0; side < 2; side++) {
-            pick[side] = SA::Pick{{0u, 0}, kk[side]};
-            sph2pob_select::host_cut<false>(count, kk[side], [&](int64_t c, uint32_t* key) { *key = rank[(size_t)c]; return SA::side_of(cand[(size_t)c]) == side; },
-                                            scratch, &pick[side].cut);
-        }
-        num_pos[b] = kk[SA::POS]; num_neg[b] = kk[SA::NEG];
-        total += kk[SA::POS] + kk[SA::NEG];
+        const auto pick = SA::host_select([&](int64_t c) { return cand[(size_t)c]; }, count, b, ranks ? ranks + b * C : nullptr, sd, num_expected_pos,
+                                          num, neg_pos_ub, rank, scratch);
+        num_pos[b] = pick[SA::POS].k; num_neg[b] = pick[SA::NEG].k;
+        total += pick[SA::POS].k + pick[SA::NEG].k;
         int64_t r = b * num;
         for (int side = 0; side < 2; side++)   // positives in ascending c, then negatives in ascending c
             for (int64_t c = 0; c < count; c++) {

@@ -48,6 +48,7 @@ inline LevelRow level_of_point(const Levels& L, int p) {
 }
 
 // the rows of an image that are used: its first k_max, and nothing outside the GT tensor whatever the offsets (device data) say
+// (sph2pob_assign.hpp::image_rows is a DIFFERENT rule: it clamps an out-of-range begin into the tensor, here such an image has no rows)
 SPHF_DEV int image_rows(int64_t begin, int64_t end, int64_t num_gt, int64_t k_max) {
     if (begin < 0 || begin > num_gt) return 0;
     int64_t k = end - begin;

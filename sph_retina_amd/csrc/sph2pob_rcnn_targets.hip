@@ -13,9 +13,8 @@
 //                           at a time into LDS; `overlaps[i, j] == gt_max[i]` can only hold when gt_max[i] <= the column's own
 //                           maximum, and only then the pair is evaluated again (same function, same inputs, same bits).  A slot
 //                           behind the image's candidates gets -1, which the select and the compaction skip.
-//   rcnn_select_kernel      one workgroup per (image, side): counts both sides, writes the rank word of its side's candidates and
-//                           finds the k-th smallest rank by the four-digit radix select and the tie walk of sph2pob_select.hpp; the
-//                           sizes, the generator and the Pick are sph2pob_sample.hpp's.
+//   rcnn_select_kernel      one workgroup per (image, side): sph2pob_sample.hpp's select_side, the body of sample_select_kernel, on
+//                           the image's candidate slots (counts, rank words, radix select, tie walk, Pick).
 //   rcnn_compact_kernel     one workgroup per image: an exclusive scan of the sampled flags over the candidates, 1 024 at a time,
 //                           both sides' counts in the halves of one word (num <= 65 535), and the table row of every sampled
 //                           candidate at its place — positives in ascending c, then negatives in ascending c, then padding.  Its
@@ -29,32 +28,14 @@ namespace {
 using namespace sph2pob_rcnn;
 using sph2pob_assign::Rule;
 using sph2pob_assign::threshold_index;
+// the packed max / first-argmax keys: sph2pob_assign.hpp's, the column key for rows and columns alike
+using sph2pob_assign::max_key_index;
+using sph2pob_assign::ordered_bits;
+using sph2pob_assign::pack_max_key_bits;
+using sph2pob_assign::unpack_max_val;
+using sph2pob_assign::wave_max_u32;
 namespace SA = sph2pob_sample;
 static_assert(kBlock == kTile, "one thread per column of a tile");
-
-// packed keys for max / first-argmax reductions: (float bits mapped to an unsigned order) << 32 | ~index, so that the maximum key is
-// the maximum value and, among equal values, the SMALLEST index: what torch.max(dim) returns.  A NaN sorts above every number.
-__device__ __forceinline__ unsigned ordered_bits(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long pack_key(unsigned ordered, unsigned index) {
-    return ((unsigned long long)ordered << 32) | (0xffffffffu - index);
-}
-__device__ __forceinline__ unsigned key_index(unsigned long long key) { return 0xffffffffu - (unsigned)key; }
-__device__ __forceinline__ float key_value(unsigned long long key) {
-    unsigned u = (unsigned)(key >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return __uint_as_float(u);
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 struct Boxes {
     const float* proposals; const int64_t* num_proposals; int64_t M, row_stride;
@@ -71,8 +52,8 @@ __global__ __launch_bounds__(kBlock) void rcnn_pairwise_kernel(Boxes X, int edge
     const ImageRows im = image_rows(X.gt_offsets, b, X.K, X.k_max);
     const int n = (int)image_proposals(X.num_proposals, b, X.M);
     const int r0 = chunk * kRows;
-    if (r0 >= (int)im.k || tile * kTile >= n) return;   // workgroup-uniform
-    const int rows = (int)im.k - r0 < kRows ? (int)im.k - r0 : kRows;
+    if (r0 >= im.k || tile * kTile >= n) return;   // workgroup-uniform
+    const int rows = im.k - r0 < kRows ? im.k - r0 : kRows;
     if ((int)threadIdx.x < rows) {
         float g[5];
         load_row<DIM>(X.gt + (im.lo + r0 + threadIdx.x) * DIM, g);
@@ -92,12 +73,12 @@ __global__ __launch_bounds__(kBlock) void rcnn_pairwise_kernel(Boxes X, int edge
         for (int c = 0; c < 5; c++) g[c] = row_raw[i][c];
         const float v = pair_iou_of<VARIANT, DIM>(g, a, edge);
         const unsigned ob = ordered_bits(v);
-        const unsigned long long key = pack_key(ob, (unsigned)(r0 + i));
+        const unsigned long long key = pack_max_key_bits(ob, (unsigned)(r0 + i));
         ck = key > ck ? key : ck;
         const unsigned mine = valid ? ob : 0u;
         const unsigned wm = wave_max_u32(mine);
         const unsigned long long eq = __builtin_amdgcn_ballot_w64(mine == wm);
-        if (lane == 0 && wm != 0u) atomicMax(&row_key[i], pack_key(wm, (unsigned)(jraw + __builtin_ctzll(eq))));   // wm == 0: a wave past n
+        if (lane == 0 && wm != 0u) atomicMax(&row_key[i], pack_max_key_bits(wm, (unsigned)(jraw + __builtin_ctzll(eq))));   // wm == 0: a wave past n
     }
     __syncthreads();
     if (valid) col_part[((int64_t)b * S.chunks + chunk) * S.M + jraw] = ck;
@@ -111,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void rcnn_candidates_kernel(Boxes X, int ed
     __shared__ unsigned long long gt_key[kBlock];
     const int b = blockIdx.y;
     const ImageRows im = image_rows(X.gt_offsets, b, X.K, X.k_max);
-    const int k = (int)im.k, n = (int)image_proposals(X.num_proposals, b, X.M);
+    const int k = im.k, n = (int)image_proposals(X.num_proposals, b, X.M);
     const int koff = (int)gt_candidates(add_gt, k);
     const int64_t c0 = (int64_t)blockIdx.x * kBlock, c = c0 + threadIdx.x;
     const bool slot = c < S.C, proposal = slot && c >= koff && c < (int64_t)koff + n;
@@ -125,8 +106,8 @@ __global__ __launch_bounds__(kBlock) void rcnn_candidates_kernel(Boxes X, int ed
             const unsigned long long v = col_part[((int64_t)b * S.chunks + ch) * S.M + j];
             ck = v > ck ? v : ck;
         }
-        m = key_value(ck);
-        a = threshold_index(m, (int64_t)key_index(ck), rule);
+        m = unpack_max_val(ck);
+        a = threshold_index(m, max_key_index(ck), rule);
     }
     // the low-quality step (max_iou_assigner.py:192-207); workgroup-uniform: the tile holds a proposal of an image with GT
     if (rule.low_quality && k > 0 && n > 0 && c0 + kBlock > koff && c0 < (int64_t)koff + n) {
@@ -149,10 +130,10 @@ __global__ __launch_bounds__(kBlock) void rcnn_candidates_kernel(Boxes X, int ed
             if (proposal) {
                 for (int ii = 0; ii < rows; ii++) {   // later GTs overwrite earlier ones: the largest matching row wins
                     const unsigned long long key = gt_key[ii];
-                    const float gm = key_value(key);
+                    const float gm = unpack_max_val(key);
                     if (!(gm >= rule.min_pos)) continue;
                     if (!rule.assign_all) {
-                        if (key_index(key) == (unsigned)j) best = r0 + ii;
+                        if (max_key_index(key) == j) best = r0 + ii;
                     } else if (!(gm > m)) {   // IoU(i, j) <= m: equality needs gm <= m
                         float g[5];
                         load_row<DIM>(X.gt + (im.lo + r0 + ii) * DIM, g);
@@ -167,88 +148,13 @@ __global__ __launch_bounds__(kBlock) void rcnn_candidates_kernel(Boxes X, int ed
     if (slot) cand[(int64_t)b * S.C + c] = a;
 }
 
-struct Draw {
-    int64_t num_expected_pos, num;
-    double neg_pos_ub;
-    int64_t seed;
-    const int64_t* seed_dev;     // wins over `seed` when non-NULL
-    const uint32_t* ranks;       // (B, C) caller's ranks instead of the generator, or NULL
-};
-
-// One workgroup of kCompactBlock threads per (image, side) over the image's C candidate slots; slot c belongs to thread
-// c % kCompactBlock in every pass.  The candidates are a few thousand: every pass is a few iterations
-__global__ __launch_bounds__(kCompactBlock) void rcnn_select_kernel(const int64_t* __restrict__ cand, int C, int64_t c_pad, Draw D,
+// one workgroup of kCompactBlock threads per (image, side) over the image's C candidate slots: sph2pob_sample.hpp's select_side.  The
+// candidates are a few thousand, every pass a few iterations: one load ahead
+__global__ __launch_bounds__(kCompactBlock) void rcnn_select_kernel(const int64_t* __restrict__ cand, int C, int64_t c_pad, SA::Draw D,
                                                                     uint32_t* __restrict__ keys, SA::Pick* __restrict__ picks) {
-    constexpr int kWaves = kCompactBlock / 64;
-    __shared__ unsigned hist[256];
-    __shared__ unsigned s_count[2], s_prefix, s_rem, s_ties, s_wave[kWaves];
-    __shared__ int s_upto;
-    const int b = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;
-    const int64_t* gb = cand + (int64_t)b * C;
-    const uint32_t* rank_in = D.ranks ? D.ranks + (int64_t)b * C : nullptr;
-    uint32_t* kb = keys + (int64_t)b * c_pad;
-    if (tid == 0) { s_count[0] = 0u; s_count[1] = 0u; s_prefix = 0u; s_rem = 0u; s_ties = 0u; s_upto = 0; }
-    const uint64_t seed = (uint64_t)(D.seed_dev ? D.seed_dev[0] : D.seed);
-    int64_t k = 0;
-    for (int d = 0; d < 4; d++) {   // most significant digit first
-        const int shift = 24 - 8 * d;
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        const unsigned prefix = s_prefix, rem_in = s_rem;
-        if (d == 0) {
-            unsigned np = 0u, nn = 0u;
-            for (int i = tid; i < C; i += kCompactBlock) {
-                const int s = SA::side_of(gb[i]);
-                np += s == SA::POS; nn += s == SA::NEG;
-                if (s == side) {
-                    const uint32_t r = rank_in ? rank_in[i] : SA::row_rank(seed, (uint32_t)b, (uint32_t)i);
-                    kb[i] = r;
-                    atomicAdd(&hist[r >> 24], 1u);
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { np += __shfl_down(np, o, 64); nn += __shfl_down(nn, o, 64); }
-            if ((tid & 63) == 0) { atomicAdd(&s_count[SA::POS], np); atomicAdd(&s_count[SA::NEG], nn); }
-        } else if (rem_in > 0u) {   // workgroup-uniform
-            const unsigned known = 0xffffffffu << (shift + 8);   // the digits already fixed
-            for (int i = tid; i < C; i += kCompactBlock) {
-                if (SA::side_of(gb[i]) != side) continue;
-                const uint32_t r = kb[i];
-                if (((r ^ prefix) & known) == 0u) atomicAdd(&hist[(r >> shift) & 255u], 1u);
-            }
-        }
-        __syncthreads();
-        if (d == 0) {
-            int64_t kp, kn;
-            SA::sample_sizes((int64_t)s_count[SA::POS], (int64_t)s_count[SA::NEG], D.num_expected_pos, D.num, D.neg_pos_ub, &kp, &kn);
-            k = side == SA::POS ? kp : kn;
-        }
-        sph2pob_select::digit_decision<false>(hist, s_wave, &s_prefix, &s_rem, &s_ties, prefix, shift,
-                                              [&](unsigned) { return d == 0 ? (unsigned)k : rem_in; });
-    }
-    const unsigned take = s_rem, cut = s_prefix;
-    const bool walk = take > 0u && take < s_ties;   // workgroup-uniform; otherwise every tied candidate is taken
-    __syncthreads();
-    if (walk) {   // in-order walk: the index of the take-th candidate tied at the cut
-        unsigned running = 0u;
-        for (int i0 = 0; i0 < C; i0 += kCompactBlock) {
-            const int i = i0 + tid;
-            const bool tie = i < C && SA::side_of(gb[i]) == side && kb[i] == cut;
-            const unsigned long long mk = __ballot(tie);
-            const unsigned in_wave = (unsigned)__popcll(mk & ((1ull << (tid & 63)) - 1ull));
-            const unsigned before = sph2pob_select::tie_scan<kWaves>(in_wave, (unsigned)__popcll(mk), s_wave, running);
-            if (tie && before + 1u == take) s_upto = i + 1;
-            __syncthreads();
-            if (running >= take) break;   // workgroup-uniform
-        }
-    }
-    if (tid == 0) {
-        SA::Pick p;
-        p.cut.key = take > 0u ? cut : 0u;
-        p.cut.upto = take > 0u ? (walk ? s_upto : C) : 0;
-        p.k = k;
-        picks[2 * b + side] = p;
-    }
+    const int b = blockIdx.x;
+    SA::select_side<kCompactBlock, 1>(cand + (int64_t)b * C, C, D.ranks ? D.ranks + (int64_t)b * C : nullptr, keys + (int64_t)b * c_pad, D,
+                                      picks);
 }
 
 template <int DIM, bool ENCODE>
@@ -307,7 +213,7 @@ __global__ __launch_bounds__(kCompactBlock) void rcnn_compact_kernel(Boxes X, Sh
 }
 
 struct RcnnLaunch {
-    Boxes X; int edge; Shape S; Rule rule; int add_gt; Draw D; int64_t num_classes; float pos_weight; bool encode; sph2pob_coder::Norm nm;
+    Boxes X; int edge; Shape S; Rule rule; int add_gt; SA::Draw D; int64_t num_classes; float pos_weight; bool encode; sph2pob_coder::Norm nm;
     Table T; Workspace W; hipStream_t s; bool fast = true;
     template <int V, int D_> int run() {
         if (!fast) return SPH2POB_ERR_OPTION;
@@ -351,7 +257,7 @@ int sph2pob_rcnn_targets_f32(const float* proposals, const int64_t* num_proposal
     return dispatch(variant, box_dim,
                     RcnnLaunch{Boxes{proposals, num_proposals, m, row_stride, gt, gt_labels, gt_offsets, num_gt, (int)k_max}, naive_edge(variant, edge), S,
                                Rule{pos_iou_thr, neg_iou_lo, neg_iou_hi, min_pos_iou, match_low_quality, gt_max_assign_all}, add_gt,
-                               Draw{num_expected_pos, num, neg_pos_ub, seed, seed_device, ranks}, num_classes, pos_weight, encode != 0,
+                               SA::Draw{num_expected_pos, num, neg_pos_ub, seed, seed_device, ranks}, num_classes, pos_weight, encode != 0,
                                sph2pob_coder::make_norm(means_host, stds_host, box_dim), T, carve(workspace, S), (hipStream_t)stream});
 }
 

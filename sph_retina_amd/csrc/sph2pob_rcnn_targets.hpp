@@ -1,10 +1,10 @@
 // R-CNN stage targets on per-image proposals (sph2pob_rcnn_targets_f32): per image MaxIoUAssigner.assign(proposals_b, gt_b), the
 // reference's SphRandomSampler.sample(..., add_gt_as_proposals) (sphdet/bbox/sampler/sph_random_sampler.py:24-52), bbox2roi and
 // SphShared2FCBBoxHead._get_target_single (sphdet/models/heads/sph_rcnn_head.py:30-66).  Shared by the kernels
-// (sph2pob_rcnn_targets.hip) and their CPU twin (sph2pob_host.hip): the per-pair function of a variant, the image's rows, the
+// (sph2pob_rcnn_targets.hip) and their CPU twin (sph2pob_host.hip): the per-pair function of a variant, the image's proposals, the
 // candidate list, the table row of one sampled candidate, the argument checks and the workspace — so that a CPU tensor gets the
-// table a device tensor gets.  The assignment rule is sph2pob_assign.hpp's, the generator, the sizes and the cut are
-// sph2pob_sample.hpp's / sph2pob_select.hpp's.
+// table a device tensor gets.  The assignment rule, the image's GT rows and the packed keys are sph2pob_assign.hpp's; the
+// generator, the sizes, the draw and the select of a side are sph2pob_sample.hpp's, the cut sph2pob_select.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,16 +33,9 @@ SPH_DEV float pair_iou_of(const float (&g)[5], const float (&a)[5], int edge) {
     return v == 0.0f ? 0.0f : v;
 }
 
-// rows of image b in the concatenated GT, as sph2pob_anchor_targets_f32 takes them: offsets clamped to [0, K], the count to
-// [0, k_max]; and its proposals: the count clamped to [0, M] (no counts: M)
-struct ImageRows { int64_t lo; int64_t k; };
-SPHF_DEV ImageRows image_rows(const int64_t* gt_offsets, int64_t b, int64_t K, int64_t k_max) {
-    int64_t lo = gt_offsets[b], hi = gt_offsets[b + 1];
-    lo = lo < 0 ? 0 : (lo > K ? K : lo);
-    hi = hi < 0 ? 0 : (hi > K ? K : hi);
-    const int64_t k = hi - lo;
-    return ImageRows{lo, k < 0 ? 0 : (k > k_max ? k_max : k)};
-}
+// rows of image b in the concatenated GT: sph2pob_assign.hpp's rule; and its proposals: the count clamped to [0, M] (no counts: M)
+using sph2pob_assign::image_rows;
+using sph2pob_assign::ImageRows;
 SPHF_DEV int64_t image_proposals(const int64_t* num_proposals, int64_t b, int64_t M) {
     if (!num_proposals) return M;
     const int64_t n = num_proposals[b];

@@ -1,12 +1,10 @@
 // Random sampling of anchor targets for a minibatch (the rank, the sizes and the selection rule: sph2pob_sample.hpp): two launches
 // whatever B is, no host read.
-//   sample_select_kernel  one workgroup per (image, side), grid (B, 2).  The first pass over the image's assigned_gt_inds counts
-//                         P_b and N_b (both workgroups count both: k_neg needs k_pos, and they do not communicate) and writes the
-//                         rank of every row of the workgroup's side into the workspace — Philox is 20 quarter-rate integer multiplies a row, so
-//                         it is evaluated once and the later passes and the apply pass read the word back.  Then the k-th smallest
-//                         rank by a four-digit radix select (LDS histogram, integer atomics; random ranks spread over the bins, so
-//                         the atomics seldom meet) and, only when the rows tied at that rank are not all taken, one in-order walk
-//                         for the row index up to which they are.  Digit decision and tie scan: sph2pob_select.hpp, ascending.
+//   sample_select_kernel  one workgroup per (image, side), grid (B, 2): sph2pob_sample.hpp's select_side (the body the R-CNN stage's
+//                         rcnn_select_kernel runs too) on the image's assigned_gt_inds.  It writes the rank of every row of the
+//                         workgroup's side into the workspace — Philox is 20 quarter-rate integer multiplies a row, so it is
+//                         evaluated once and the later passes and the apply pass read the word back (random ranks spread over the
+//                         histogram's bins, so its atomics seldom meet) — and leaves the side's Pick.
 //   sample_apply_kernel   a streaming pass over (B, n): a row that stays in the sample, or is ignored, keeps its targets (copied
 //                         when the output is another buffer, untouched when it is the input); a row that leaves gets the background
 //                         label and zeros.  Four rows per thread with 16-byte accesses when n % 4 == 0 and the bases allow.  Its
@@ -18,115 +16,12 @@ namespace {
 
 using namespace sph2pob_sample;
 
-struct Draw {
-    int64_t num_expected_pos, num;
-    double neg_pos_ub;
-    int64_t seed;
-    const int64_t* seed_dev;     // wins over `seed` when non-NULL
-    const uint32_t* ranks;       // (B, n) caller's ranks instead of the generator, or NULL
-};
-
-// One workgroup of kSelectBlock threads per (image, side).  Row i of the image belongs to thread i % kSelectBlock in every pass, so
-// a thread reads back the rank words it wrote itself.
+// one workgroup of kSelectBlock threads per (image, side): the image's rows, then sph2pob_sample.hpp's select_side, 8 loads ahead
 __global__ __launch_bounds__(kSelectBlock) void sample_select_kernel(const int64_t* __restrict__ gt_inds, int n, int64_t n_pad, Draw D,
                                                                      uint32_t* __restrict__ keys, Pick* __restrict__ picks) {
-    constexpr int kWaves = kSelectBlock / 64, kAhead = 8;
-    __shared__ unsigned hist[256];
-    __shared__ unsigned s_count[2], s_prefix, s_rem, s_ties, s_wave[kWaves];
-    __shared__ int s_upto;
-    const int b = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;
-    const int64_t* gb = gt_inds + (int64_t)b * n;
-    const uint32_t* rank_in = D.ranks ? D.ranks + (int64_t)b * n : nullptr;
-    uint32_t* kb = keys + (int64_t)b * n_pad;
-    if (tid == 0) { s_count[0] = 0u; s_count[1] = 0u; s_prefix = 0u; s_rem = 0u; s_ties = 0u; s_upto = 0; }
-    const uint64_t seed = (uint64_t)(D.seed_dev ? D.seed_dev[0] : D.seed);
-    int64_t k = 0;
-
-    // radix select, most significant digit first: after digit d the top 8 (d + 1) bits of the k-th smallest rank are known
-    for (int d = 0; d < 4; d++) {
-        const int shift = 24 - 8 * d;
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        const unsigned prefix = s_prefix, rem_in = s_rem;
-        if (d == 0) {
-            unsigned np = 0u, nn = 0u;
-            for (int64_t i0 = tid; i0 < n; i0 += kAhead * kSelectBlock) {   // kAhead independent loads in flight, then the arithmetic
-                int64_t g[kAhead];
-                uint32_t r[kAhead];
-#pragma unroll
-                for (int u = 0; u < kAhead; u++) {
-                    const int64_t i = i0 + (int64_t)u * kSelectBlock;
-                    g[u] = i < n ? gb[i] : -1;   // past the end: an ignored row
-                    r[u] = rank_in && i < n ? rank_in[i] : 0u;
-                }
-#pragma unroll
-                for (int u = 0; u < kAhead; u++) {
-                    const int64_t i = i0 + (int64_t)u * kSelectBlock;
-                    const int c = side_of(g[u]);
-                    np += c == POS; nn += c == NEG;
-                    if (c == side) {
-                        if (!rank_in) r[u] = row_rank(seed, (uint32_t)b, (uint32_t)i);
-                        kb[i] = r[u];
-                        atomicAdd(&hist[r[u] >> 24], 1u);
-                    }
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { np += __shfl_down(np, o, 64); nn += __shfl_down(nn, o, 64); }
-            if ((tid & 63) == 0) { atomicAdd(&s_count[POS], np); atomicAdd(&s_count[NEG], nn); }
-        } else if (rem_in > 0u) {   // workgroup-uniform
-            const unsigned known = 0xffffffffu << (shift + 8);   // the digits already fixed
-            for (int64_t i0 = tid; i0 < n; i0 += kAhead * kSelectBlock) {
-                int64_t g[kAhead];
-                uint32_t r[kAhead];
-#pragma unroll
-                for (int u = 0; u < kAhead; u++) {   // both loads of every row at once: the word of a row of the other side is not used
-                    const int64_t i = i0 + (int64_t)u * kSelectBlock;
-                    g[u] = i < n ? gb[i] : -1;
-                    r[u] = i < n ? kb[i] : 0u;
-                }
-#pragma unroll
-                for (int u = 0; u < kAhead; u++) {
-                    if (side_of(g[u]) == side && ((r[u] ^ prefix) & known) == 0u) atomicAdd(&hist[(r[u] >> shift) & 255u], 1u);
-                }
-            }
-        }
-        __syncthreads();
-        if (d == 0) {
-            int64_t kp, kn;
-            sample_sizes((int64_t)s_count[POS], (int64_t)s_count[NEG], D.num_expected_pos, D.num, D.neg_pos_ub, &kp, &kn);
-            k = side == POS ? kp : kn;   // <= the side's rows < 2^31
-        }
-        // the digit: the one bin that holds the rem-th smallest rank
-        sph2pob_select::digit_decision<false>(hist, s_wave, &s_prefix, &s_rem, &s_ties, prefix, shift,
-                                              [&](unsigned) { return d == 0 ? (unsigned)k : rem_in; });
-    }
-    const unsigned take = s_rem;          // rows tied at the k-th rank that are taken (>= 1 when anything is)
-    const unsigned cut = s_prefix;
-    const bool walk = take > 0u && take < s_ties;   // workgroup-uniform; otherwise every tied row is taken
-    __syncthreads();
-
-    // in-order walk: the index of the take-th row tied at the cut
-    if (walk) {
-        unsigned running = 0u;
-        for (int64_t i0 = 0; i0 < n; i0 += kSelectBlock) {   // whole workgroups: barriers inside
-            const int64_t i = i0 + tid;
-            const bool tie = i < n && side_of(gb[i]) == side && kb[i] == cut;
-            const unsigned long long m = __ballot(tie);
-            const unsigned in_wave = (unsigned)__popcll(m & ((1ull << (tid & 63)) - 1ull));
-            const unsigned before = sph2pob_select::tie_scan<kWaves>(in_wave, (unsigned)__popcll(m), s_wave, running);
-            if (tie && before + 1u == take) s_upto = (int)(i + 1);   // one thread of one iteration
-            __syncthreads();
-            if (running >= take) break;   // workgroup-uniform
-        }
-    }
-    if (tid == 0) {
-        Pick p;
-        p.cut.key = take > 0u ? cut : 0u;
-        p.cut.upto = take > 0u ? (walk ? s_upto : n) : 0;
-        p.k = k;
-        picks[2 * b + side] = p;
-    }
+    const int b = blockIdx.x;
+    select_side<kSelectBlock, 8>(gt_inds + (int64_t)b * n, n, D.ranks ? D.ranks + (int64_t)b * n : nullptr, keys + (int64_t)b * n_pad, D,
+                                 picks);
 }
 
 struct Targets {

@@ -230,6 +230,40 @@ def to(device, proposals, gts, labs):
     return proposals.to(device), [g.to(device) for g in gts], [l.to(device) for l in labs]
 
 
+def run_select_edge(device, C):
+    """The select body at C candidate slots (sample_targets_restatement.SELECT_EDGES: the R-CNN entry runs the sampler's select on
+    k_max + M slots): B = 2, image 0 with 8 GT (none at C = 1: the one slot is a proposal) and C - 8 proposals, image 1 without GT and
+    without proposals, so all its slots are ignored; caller ranks that tie at the cut of both sides (ranks_tied_at_the_cut on the
+    per-image route's assignment).  On `device` against the CPU twin, the restatement and the rows known beforehand, exactly."""
+    from sample_targets_restatement import TIE, ranks_tied_at_the_cut, sample_sizes
+    k = 8 if C > 8 else 0
+    m = C - k
+    proposals, gts, labs = draw(4, seed=C, m=m, num_proposals=(m, 0), gt_counts=(k, 0))
+    num, frac = max(1, C // 4), 0.25 if C > 1 else 0.0
+    cfg = rcnn_cfg('sph2pob_standard_iou', 4, num=num, pos_fraction=frac, neg_iou_thr=0.3)
+    res = assign_single(assigner_of(cfg), proposals[0, :m, :4].float(), gts[0], labs[0])
+    cand = torch.cat([torch.arange(1, k + 1), res.gt_inds])
+    P, N = int((cand > 0).sum()), int((cand == 0).sum())
+    k_pos, k_neg = sample_sizes(P, N, num, frac, -1)
+    assert C == 1 or (0 < k_pos < P and 0 < k_neg < N and P + N < C)     # both sides are cut, and some slots are ignored
+    r0, taken = ranks_tied_at_the_cut(cand, k_pos, k_neg, np.random.default_rng(C))
+    ranks = torch.stack([r0, torch.full((C,), TIE)])
+    counts = torch.tensor((m, 0), dtype=torch.int64)
+    kw = dict(train_cfg=cfg, num_classes=37, seed=0, reg_decoded_bbox=True)
+    twin = S.sph_rcnn_targets(proposals, gts, labs, num_proposals=counts, ranks=ranks, **kw)
+    dev = to(device, proposals, gts, labs)
+    got = S.sph_rcnn_targets(*dev, num_proposals=counts.to(device), ranks=ranks.to(device), **kw)
+    for f in FIELDS + ('num_pos', 'num_neg', 'avg_factor', 'num_samples'):
+        assert same_bits(getattr(got, f).cpu(), getattr(twin, f)), (C, f)
+    assert_equal(got, rcnn_batch(cfg, dev[0], (m, 0), dev[1], dev[2], 37, ranks.to(device)), ('select edge', C))
+    inds = got.sample_inds.cpu()
+    assert torch.equal(inds[:k_pos], taken[0]) and torch.equal(inds[k_pos:k_pos + k_neg], taken[1]) and bool((inds[k_pos + k_neg:] == -1).all())
+    assert got.num_pos.tolist() == [k_pos, 0] and got.num_neg.tolist() == [k_neg, 0]
+    if C > 2048:    # the tie walk ended behind the workgroup's first round of 1 024 slots
+        assert all(int(rows.max()) >= 1024 for rows in taken)
+    return got
+
+
 def run_case(device, case, seed=4242, scene=None):
     """One case of the table on the scene of the issue (or `scene`: the keyword arguments of draw): equal to the restatement, the
     invariants, the inputs unchanged.  -> (got, want, cfg, tensors)."""

@@ -175,6 +175,64 @@ def run_case(S, device, case, seed=12345):
     return got
 
 
+TIE = 0x80000000
+# rows of an image against the select workgroup's 1 024 threads and its 8 rows per thread and pass: one row, one short of a round,
+# one past it, and one past the 8 192 rows of the first pass's first iteration
+SELECT_EDGES = (1, 1023, 1025, 8 * 1024 + 1)
+
+
+def ranks_tied_at_the_cut(gt_inds, k_pos, k_neg, rng):
+    """Caller ranks for one image whose sample is known beforehand.  gt_inds (n,): the assigned indices; k_pos, k_neg: the sample sizes.
+    A side with S rows of which 0 < k < S are wanted: the later half of its rows (by index, h = S // 2 of them) share the rank TIE,
+    max(0, k - (h - 1)) of the earlier rows rank below it (all different) and every other row above; the cut falls inside the tied
+    block, k - (those below) < h of the tied rows are taken: the in-order walk runs, and stops among the side's last rows.
+    -> ranks (n,) int64 in [0, 2^32), [rows sampled as positives, rows sampled as negatives] (ascending)."""
+    ranks = torch.from_numpy(rng.integers(TIE + 1, 1 << 32, gt_inds.numel()))
+    taken = []
+    for rows, k in ((torch.nonzero(gt_inds > 0).squeeze(-1), k_pos), (torch.nonzero(gt_inds == 0).squeeze(-1), k_neg)):
+        S = rows.numel()
+        if not 0 < k < S:
+            taken.append(rows if k >= S else rows[:0])
+            continue
+        h = S // 2
+        early, tied = rows[:S - h], rows[S - h:]
+        below = max(0, k - (h - 1))
+        low = early[torch.from_numpy(rng.permutation(S - h)[:below])]
+        ranks[low] = torch.from_numpy(rng.permutation(below)) * 1000 + 5
+        ranks[tied] = TIE
+        taken.append(torch.cat([low, tied[:k - below]]).sort()[0])
+    return ranks, taken
+
+
+def run_select_edge(S, device, n):
+    """B = 2, image 0 with n rows of every side whose ranks tie at the cut (ranks_tied_at_the_cut), image 1 all ignored: the sample on
+    `device` against the CPU twin, the restatement and the rows known beforehand — everything exactly."""
+    P = (n + 1) // 2
+    N = n - P - n // 8
+    num, frac = max(1, n // 2), 0.5 if n > 1 else 1.0
+    cpu = make_targets(n, 4, ((P, N), (0, 0)), seed=n)
+    k_pos, k_neg = sample_sizes(P, N, num, frac, -1)
+    r0, taken = ranks_tied_at_the_cut(cpu.gt_inds[0], k_pos, k_neg, np.random.default_rng(n))
+    ranks = torch.stack([r0, torch.full((n,), TIE)])
+    kw = dict(sampler=sampler_cfg(num, frac), num_classes=37, seed=0)
+    twin = S.sph_sample_targets(cpu, ranks=ranks, **kw)
+    got = S.sph_sample_targets(to(cpu, device), ranks=ranks.to(device), **kw)
+    for k in ('labels', 'label_weights', 'bbox_targets', 'bbox_weights', 'sample_flags', 'num_pos', 'num_neg', 'avg_factor', 'avg_factor_pos'):
+        assert same_bits(getattr(got, k).cpu(), getattr(twin, k)), (n, k)
+    assert_equal(got, sample_batch(cpu, 37, num, frac, -1, ranks), ('select edge', n))
+    flags = got.sample_flags.cpu()
+    for side in (0, 1):
+        assert torch.equal(torch.nonzero(flags[0] == side + 1).squeeze(-1), taken[side]), (n, side)
+    assert got.num_pos.tolist() == [k_pos, 0] and got.num_neg.tolist() == [k_neg, 0] and not bool(flags[1].any())
+    if n > 1:       # the walk ran on both sides: tied rows were taken, and tied rows were left
+        for side, rows in enumerate(taken):
+            tied = (r0 == TIE) & ((cpu.gt_inds[0] > 0) if side == 0 else (cpu.gt_inds[0] == 0))
+            assert 0 < int(tied[rows].sum()) < int(tied.sum()), (n, side)
+    if n > 2048:    # ... and ended behind the workgroup's first round of 1 024 rows (n = 1 025 has a single row there: it cannot)
+        assert all(int(rows.max()) >= 1024 for rows in taken)
+    return got
+
+
 def run_ties(S, device):
     """Caller-supplied ranks: all equal, and a block of tied ranks straddling the cut."""
     n = 300

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import rcnn_targets_restatement as R
-from sample_targets_restatement import ranks_of, same_bits
+from sample_targets_restatement import SELECT_EDGES, ranks_of, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +71,14 @@ def test_more_candidates_than_one_compaction_round(S):
     cfg = R.rcnn_cfg('sph2pob_standard_iou', 4, num=64, pos_fraction=0.25, neg_iou_thr=0.3)
     tied = S.sph_rcnn_targets(proposals, gts, labs, num_proposals=n_dev, train_cfg=cfg, num_classes=37, seed=0, ranks=ranks, reg_decoded_bbox=True)
     R.assert_equal(tied, R.rcnn_batch(cfg, proposals, (1100, 1030), gts, labs, 37, ranks), 'equal ranks')
+
+
+@pytest.mark.parametrize('C', SELECT_EDGES)
+def test_ties_at_the_cut_at_the_select_edges(S, C):
+    """The select body (sph2pob_sample.hpp's select_side, one slot ahead) at the edges of its rounds, as k_max + M candidate slots, with
+    caller ranks whose sample is known beforehand; B = 2, the second image all ignored; against the CPU twin, the restatement and the
+    known candidates, exactly."""
+    R.run_select_edge('cuda', C)
 
 
 def test_ties_and_generator(S):

@@ -34,6 +34,13 @@ def test_caller_ranks_and_ties(S):
     R.run_ties(S, 'cuda')
 
 
+@pytest.mark.parametrize('n', R.SELECT_EDGES)
+def test_ties_at_the_cut_at_the_select_edges(S, n):
+    """The select body (sph2pob_sample.hpp's select_side, 8 rows ahead) at the edges of its rounds, with caller ranks whose sample is
+    known beforehand; B = 2, the second image all ignored; against the CPU twin, the restatement and the known rows, exactly."""
+    R.run_select_edge(S, 'cuda', n)
+
+
 def test_unaligned_views_take_the_scalar_pass(S):
     """n % 4 == 0 but the targets start 4 bytes off a 16-byte boundary: the one-row-per-thread apply pass, the same result."""
     n, counts = 2048, ((100, 1900), (0, 2048), (1500, 500))

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import rcnn_targets_restatement as R
-from sample_targets_restatement import ranks_of, same_bits
+from sample_targets_restatement import SELECT_EDGES, ranks_of, same_bits
 
 import sph_retina_amd as S
 
@@ -84,6 +84,11 @@ def test_more_than_one_tile_and_more_than_256_gt(backend):
     scene = dict(m=300, num_proposals=(300, 257), gt_counts=(260, 3))
     for rule in (R.LOW, dict(R.LOW, gt_max_assign_all=False)):
         R.run_case('cpu', (backend, 4, rule, 64, 0.25, -1, True, -1, True), scene=scene)
+
+
+@pytest.mark.parametrize('C', SELECT_EDGES)
+def test_ties_at_the_cut_at_the_select_edges(C):
+    R.run_select_edge('cpu', C)
 
 
 def test_ties_take_the_lowest_candidates():

@@ -41,6 +41,63 @@ def test_caller_ranks_and_ties():
     R.run_ties(S, 'cpu')
 
 
+@pytest.mark.parametrize('n', R.SELECT_EDGES)
+def test_ties_at_the_cut_at_the_select_edges(n):
+    R.run_select_edge(S, 'cpu', n)
+
+
+def test_draw_arguments_serve_both_entries():
+    """`_draw_arguments`, the one place `sph_sample_targets` and `sph_rcnn_targets` normalise `seed` and `ranks`: a Python seed taken
+    modulo 2^64 as a signed 64-bit value, ranks of any integer dtype as the int32 tensor holding their 32 bits, and the messages."""
+    import rcnn_targets_restatement as RR
+    from sph_retina_amd.bbox.assigners.sample_targets import _draw_arguments
+    cpu = torch.device('cpu')
+    for seed, want in ((-1, -1), (2 ** 63, -2 ** 63), (2 ** 64 + 5, 5), (0, 0), (2 ** 63 - 1, 2 ** 63 - 1)):
+        assert _draw_arguments('who', seed, None, (1, 1), cpu) == (want, None, None)
+    dev_seed = torch.tensor(7, dtype=torch.int64)
+    s, s_dev, r = _draw_arguments('who', dev_seed, None, (1, 1), cpu)
+    assert s == 0 and s_dev is dev_seed and r is None
+    bits = torch.tensor([[0, 1, -1, -2 ** 31, 2 ** 31 - 1, 200]], dtype=torch.int32)         # 0, 1, 2^32 - 1, 2^31, 2^31 - 1, 200 as uint32
+    values = torch.tensor([[0, 1, 2 ** 32 - 1, 2 ** 31, 2 ** 31 - 1, 200]], dtype=torch.int64)
+    for given in (values, bits, torch.tensor([[0, 1, 255, 128, 127, 200]], dtype=torch.uint8)):
+        r = _draw_arguments('who', 0, given, (1, 6), cpu)[2]
+        assert r.dtype == torch.int32 and r.is_contiguous()
+        assert torch.equal(r, bits if given.dtype != torch.uint8 else given.to(torch.int32))
+    assert _draw_arguments('who', 0, values.t().contiguous().t(), (1, 6), cpu)[2].is_contiguous()
+    for bad, tail in ((values[:, :5], ''), (values.float(), ' (six)'), (values.to('meta'), '')):
+        with pytest.raises(ValueError, match=r'^who: ranks must be a \(1, 6\) integer tensor on cpu' + tail.replace('(', r'\(').replace(')', r'\)') + '$'):
+            _draw_arguments('who', 0, bad, (1, 6), cpu, slots=tail)
+    for bad in (torch.tensor([7]), torch.tensor(7, dtype=torch.int32), torch.tensor(7).to('meta')):
+        with pytest.raises(ValueError, match=r'^who: a tensor seed must be a \(\) int64 tensor on cpu$'):
+            _draw_arguments('who', bad, None, (1, 1), cpu)
+    # both entries go through it: the same sample for the same seed however it is written and for the same ranks in any dtype, and
+    # each entry's own message
+    t = R.make_targets(100, 4, ((30, 60),), seed=4)
+    kw = dict(sampler=R.sampler_cfg(16, 0.5), num_classes=37)
+    want = S.sph_sample_targets(t, seed=-3, **kw)
+    assert torch.equal(S.sph_sample_targets(t, seed=2 ** 64 - 3, **kw).sample_flags, want.sample_flags)
+    assert torch.equal(S.sph_sample_targets(t, seed=torch.tensor(-3), **kw).sample_flags, want.sample_flags)
+    small = torch.from_numpy(np.random.default_rng(1).integers(0, 256, (1, 100)))
+    by_dtype = [S.sph_sample_targets(t, seed=0, ranks=small.to(d), **kw).sample_flags for d in (torch.uint8, torch.int32, torch.int64)]
+    assert torch.equal(by_dtype[0], by_dtype[1]) and torch.equal(by_dtype[0], by_dtype[2])
+    with pytest.raises(ValueError, match=r'^sph_sample_targets: ranks must be a \(1, 100\) integer tensor on cpu$'):
+        S.sph_sample_targets(t, seed=0, ranks=small.float(), **kw)
+    proposals, gts, labs = RR.draw(4, seed=3)
+    cfg = RR.rcnn_cfg('sph2pob_standard_iou', 4, num=16, neg_iou_thr=0.3)
+    C = max(RR.GT_COUNTS) + RR.M
+    rk = dict(num_proposals=torch.tensor(RR.NUM_PROPOSALS), train_cfg=cfg, num_classes=37, reg_decoded_bbox=True)
+    a = S.sph_rcnn_targets(proposals, gts, labs, seed=-3, **rk)
+    for other in (2 ** 64 - 3, torch.tensor(-3)):
+        assert torch.equal(S.sph_rcnn_targets(proposals, gts, labs, seed=other, **rk).sample_inds, a.sample_inds)
+    small = torch.from_numpy(np.random.default_rng(2).integers(0, 256, (RR.B, C)))
+    by_dtype = [S.sph_rcnn_targets(proposals, gts, labs, seed=0, ranks=small.to(d), **rk).sample_inds for d in (torch.uint8, torch.int32, torch.int64)]
+    assert torch.equal(by_dtype[0], by_dtype[1]) and torch.equal(by_dtype[0], by_dtype[2])
+    with pytest.raises(ValueError, match=rf'^sph_rcnn_targets: ranks must be a \({RR.B}, {C}\) integer tensor on cpu \(k_max \+ M candidate slots per image\)$'):
+        S.sph_rcnn_targets(proposals, gts, labs, seed=0, ranks=small[:, 1:], **rk)
+    with pytest.raises(ValueError, match=r'^sph_rcnn_targets: a tensor seed must be a \(\) int64 tensor on cpu$'):
+        S.sph_rcnn_targets(proposals, gts, labs, seed=torch.tensor([3]), **rk)
+
+
 def test_uniformity():
     """Seeds 0 .. 1999, image 0, 64 positives at rows 0 .. 63, 16 taken: every row's inclusion frequency lies in [0.21, 0.29] (the
     binomial sd is 0.0097: about +-4 sd; deterministic, the seeds are fixed)."""
